@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — posting-list hot path on MI355X: postings/s and fraction of the HBM roofline.
 
-One run times BOTH halves of the metric ("intersect + segment-merge") and prints ONE JSON line on rank 0:
+A `--full` run times BOTH halves of the metric ("intersect + segment-merge") and prints ONE JSON line on rank 0:
 
 * headline (`value`, `roofline`, `cpu_baseline`): BASELINE.json configs[1] — 2-term intersection over a 100M-doc
   index, Zipf ranks 2 and 3 (≈50M and ≈33M postings), block-Δ-varint (DV1) lists resident in HBM, decoded in-kernel;
@@ -21,6 +21,12 @@ One run times BOTH halves of the metric ("intersect + segment-merge") and prints
 * `c5` (every N): configs[4] — one 8-term AND over a 1B-doc index (Zipf ranks 2 ... 16384, a common core in every list),
   the doc-id space cut into N contiguous ranges (sharding.doc_range), every rank checked bit-exactly against the oracle on
   its range, results concatenated in rank order with ii2_allgatherv inside the timed region.
+
+A plain run (`--gpus 1 --steps N --warmup W`) measures the headline and nothing else: it sets up the two lists, warms up, times
+the N steps and prints the line (`value`, `ms_per_step`, the `roofline` read off the timed steps' event pair).  Everything else
+above - the result checks, `roofline.sampled_pass_us`, `roofline.cold`, `roofline.with_tombstones`, `union`, `allgatherv`,
+`cpu_baseline`, `merge`, `merge_strong`, `c5`, and any `--workload` but all / intersect - needs `--full`.
+`--dump-outputs DIR` writes what the headline's last timed step computed to DIR/<name>.npy (intersect_dump()).
 
 N > 1: one process per GPU.  `python bench.py --gpus N` starts the N ranks itself (torch.distributed.run on 127.0.0.1)
 when no launcher did (WORLD_SIZE unset) — before this process touches the GPU; under a launcher the ranks read
@@ -78,7 +84,20 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 on a ONE-GPU box: every rank uses cuda:0, the process group is gloo and the exchange takes the "
                          "torch fallback (RCCL refuses two ranks on one device) - checks the multi-rank control flow, the numbers mean nothing")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the result checks, the sampled, cold, tombstone and union variants, the exchange, the CPU "
+                         "baseline and the merge, merge_strong and c5 objects (without it a run times the headline and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.workload not in ("all", "intersect"):
+        if not args.full:
+            ap.error("--workload %s is measured with --full" % args.workload)
+        if args.dump_outputs:
+            ap.error("--dump-outputs writes the headline intersection's outputs: --workload all or intersect")
+    return args
 
 
 def self_launch(args):
@@ -178,6 +197,32 @@ def cpu_baseline_intersect(lists, removed, reps, threads=1):
     return n_post / dt, np.concatenate(res) if res else np.empty(0, np.uint32), dt
 
 
+DUMP_SAMPLE_IDS = 3_000_000     # --dump-outputs: ids kept of a longer result (ids + positions as float64: 48 MB, under 64 MB)
+DUMP_SEED = 20241016
+
+
+def intersect_dump(ids):
+    """--dump-outputs of the headline: what a caller of the timed path receives - the count and the ascending ids - as float64
+    arrays (every uint32 id is exact in float64).  A result longer than DUMP_SAMPLE_IDS is kept as a fixed, seeded sample of
+    positions (the positions are written too) plus the sum of all ids, so a change anywhere in it still shows."""
+    n = int(ids.size)
+    if n > DUMP_SAMPLE_IDS:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_IDS, replace=False))
+    else:
+        pos = np.arange(n)
+    return {"intersect_count": np.array([n], np.float64),
+            "intersect_ids_sum": np.array([ids.astype(np.uint64).sum()], np.float64),
+            "intersect_ids_pos": pos.astype(np.float64),
+            "intersect_ids": ids[pos].astype(np.float64)}
+
+
+def dump_outputs(out_dir, arrays, world=1, rank=0):
+    """Writes out_dir/<name>.npy (one set per rank when world > 1: <name>_rank<r>.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), arr)
+
+
 class Job:
     """Process-wide state of one bench run."""
 
@@ -202,7 +247,8 @@ class Job:
                 dist.init_process_group("nccl", device_id=torch.device("cuda", device))
         from inverted_index_2_amd import Context
         self.ctx = Context(device)
-        self.ctx.selftest()
+        if args.full:
+            self.ctx.selftest()
         self.parts = {}            # the bench objects measured so far (what the watchdog prints if a later exchange gets stuck)
         if self.world > 1 and self.rank == 0:
             import signal
@@ -337,14 +383,15 @@ def bench_intersect(job):
     out = ctx.empty(cap)
     d_count = ctx.empty(8, np.uint64)
 
-    # correctness of this rank's result before timing: bit-exact id sequence
     _, n_out = ctx.intersect(lists, tomb=tomb, out=out)
-    got = out.download(n_out)
-    want_np = np.intersect1d(a, b, assume_unique=True)
-    if removed is not None:
-        want_np = np.setdiff1d(want_np, removed, assume_unique=True)
-    if n_out != want_np.size or not np.array_equal(got, want_np):
-        raise SystemExit(f"rank {rank}: GPU intersection differs from the numpy cross-check")
+    if args.full:
+        # correctness of this rank's result before timing: bit-exact id sequence
+        got = out.download(n_out)
+        want_np = np.intersect1d(a, b, assume_unique=True)
+        if removed is not None:
+            want_np = np.setdiff1d(want_np, removed, assume_unique=True)
+        if n_out != want_np.size or not np.array_equal(got, want_np):
+            raise SystemExit(f"rank {rank}: GPU intersection differs from the numpy cross-check")
 
     def timed(pairs, steps):
         for i in range(args.warmup):
@@ -360,14 +407,17 @@ def bench_intersect(job):
         return job.max_over_ranks(dt), ctx.profile_region_ms() * 1e-3
 
     dt, dev_s = timed([lists], args.steps)
-    # per-pass device time sampled with an event pair around single passes (a pair idles the stream ~10 us, so
-    # this loop is separate from the timed one)
-    ctx.set_option("profile.events", 1)
-    ctx.profile_read()
-    for _ in range(max(10, min(args.steps, 40))):
-        ctx.intersect_async(lists, tomb, out, d_count)
-    pass_ms, pass_n = ctx.profile_read()
-    ctx.set_option("profile.events", 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, intersect_dump(out.download(int(d_count.download(1)[0]))), world, rank)
+    if args.full:
+        # per-pass device time sampled with an event pair around single passes (a pair idles the stream ~10 us, so
+        # this loop is separate from the timed one)
+        ctx.set_option("profile.events", 1)
+        ctx.profile_read()
+        for _ in range(max(10, min(args.steps, 40))):
+            ctx.intersect_async(lists, tomb, out, d_count)
+        pass_ms, pass_n = ctx.profile_read()
+        ctx.set_option("profile.events", 0)
 
     info = seg.info
     # algorithmic bytes of one pass (SURVEY.md §8 d): encoded payload + 8 B per block of skip table
@@ -381,7 +431,7 @@ def bench_intersect(job):
 
     # cold variant: rotate over distinct list pairs so that no pass finds its input in the Infinity Cache
     cold = None
-    if args.cold_pairs > 1:
+    if args.full and args.cold_pairs > 1:
         pairs = [lists]
         keep = [seg]
         n_in_cold, alg_cold = n_in, alg_bytes
@@ -428,13 +478,15 @@ def bench_intersect(job):
             "traffic": traffic, "traffic_source": traffic_src,
             "algorithmic_bytes_per_launch": int(alg_bytes), "kernel_avg_us": kern_avg_s * 1e6, "launches_timed": int(args.steps),
             "timing": "one HIP event pair on the library's stream around the %d timed passes" % args.steps,
-            "sampled_pass_us": (pass_ms / pass_n * 1e3) if pass_n else None, "sampled_passes": int(pass_n),
         },
     }
+    if args.full:
+        res["roofline"]["sampled_pass_us"] = (pass_ms / pass_n * 1e3) if pass_n else None
+        res["roofline"]["sampled_passes"] = int(pass_n)
     if cold is not None:
         res["roofline"]["cold_frac"] = cold["frac"]
         res["roofline"]["cold"] = cold
-    if tomb is None:
+    if args.full and tomb is None:
         # north_star's form of the query: the same passes with the tombstone filter on (1 % of the docs removed, a D/8-byte
         # bitmap: +12.5 MB algorithmic at 100M docs) - SURVEY §0 D4: off = the reference's Read, on = north_star
         removed_t = synth.geometric_postings(0.01, D, synth.term_seed(10**6), offset).astype(np.uint32)
@@ -460,7 +512,7 @@ def bench_intersect(job):
 
     # the same two lists as a UNION (PrefixSearch's append + sort + compact over the lists of the matching terms,
     # inverted_index.go:274-292): ii2_union's streaming path (the dense kernel with OR semantics), numpy-checked
-    if tomb is None and world == 1:
+    if args.full and tomb is None and world == 1:
         try:
             u_out = ctx.empty(int(a.size + b.size) + 16)
             _, n_u = ctx.union(lists, out=u_out)
@@ -491,7 +543,7 @@ def bench_intersect(job):
 
     # the exchange step, once, after the timed region: rank-order concatenation of the results
     job.parts["intersect"] = res           # (measured: a stuck exchange below no longer takes the headline with it)
-    if world > 1:
+    if args.full and world > 1:
         def exchange():
             job.torch.cuda.synchronize()
             g0 = time.perf_counter()
@@ -510,7 +562,7 @@ def bench_intersect(job):
             print(f"rank {rank}: all-gatherv result is not the rank-order concatenation", file=sys.stderr, flush=True)
             job.rc = 4
 
-    if not args.no_cpu_baseline and world == 1:       # the CPU baseline is a rank-0, N = 1 figure
+    if args.full and not args.no_cpu_baseline and world == 1:       # the CPU baseline is a rank-0, N = 1 figure
         reps = 10                                       # ~4 s single-thread + a few seconds on the pool
         v1, res1, per1 = cpu_baseline_intersect([a, b], removed, reps, threads=1)
         if not np.array_equal(res1, got):
@@ -1167,11 +1219,11 @@ def main():
                 raise
             parts[name] = {"error": repr(e)}
             job.rc = max(job.rc, 6)
-    if args.workload in ("all", "merge") and world == 1:
+    if args.full and args.workload in ("all", "merge") and world == 1:
         secondary("merge", bench_merge)
-    if args.workload in ("all", "strong") or (args.workload == "merge" and world > 1):
+    if args.full and (args.workload in ("all", "strong") or (args.workload == "merge" and world > 1)):
         secondary("merge_strong", bench_merge_strong)
-    if args.workload in ("all", "c5"):
+    if args.full and args.workload in ("all", "c5"):
         secondary("c5", bench_c5)
     result = assemble(job, parts)
     if job.rehearse:

@@ -31,6 +31,6 @@ sq c5 k_isect scripts/c5_loop.py steps=5
 # the PMC summaries go where bench.py looks for them (profiles/, this box's copy of the tree): the bench lines below then carry `traffic`
 python3 scripts/r04_collect.py $out > /dev/null
 mkdir -p $out/bench
-timeout -k 5 1000 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o bench -- python3 bench.py --steps 20 --warmup 5 > $out/bench_under_profiler.json 2> $out/bench_under_profiler.err || echo "bench profile failed"
+timeout -k 5 1000 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o bench -- python3 bench.py --full --steps 20 --warmup 5 > $out/bench_under_profiler.json 2> $out/bench_under_profiler.err || echo "bench profile failed"
 find $out/bench -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats.csv \;
 ls $out

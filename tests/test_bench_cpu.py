@@ -38,6 +38,49 @@ def test_bench_argument_contract():
     finally:
         sys.argv = argv
     assert (a.gpus, a.steps, a.warmup, a.workload) == (1, 7, 2, "all")
+    assert a.full is False and a.dump_outputs is None          # a plain run times the headline alone, dumps nothing
+
+
+def test_secondary_workloads_need_full():
+    import sys
+
+    import pytest
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--full", "--workload", "strong", "--dump-outputs", "d"]
+        with pytest.raises(SystemExit):
+            b.parse()                                          # the dump is the headline's
+        sys.argv = ["bench.py", "--workload", "merge"]
+        with pytest.raises(SystemExit):
+            b.parse()
+        sys.argv = ["bench.py", "--full", "--workload", "merge"]
+        assert b.parse().full
+        sys.argv = ["bench.py", "--workload", "intersect", "--dump-outputs", "d"]
+        assert b.parse().dump_outputs == "d"
+    finally:
+        sys.argv = argv
+
+
+def test_intersect_dump_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs: float64 arrays, every sampled id exact, the same sample on every run, at most 64 MB in all."""
+    b = _bench()
+    rng = np.random.default_rng(9)
+    ids = np.sort(rng.choice(100_000_000, b.DUMP_SAMPLE_IDS + 12_345, replace=False)).astype(np.uint32)
+    d = b.intersect_dump(ids)
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert sum(v.nbytes for v in d.values()) <= 64 << 20
+    assert int(d["intersect_count"][0]) == ids.size and d["intersect_ids"].size == b.DUMP_SAMPLE_IDS
+    pos = d["intersect_ids_pos"].astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and np.array_equal(d["intersect_ids"].astype(np.uint32), ids[pos])
+    assert d["intersect_ids_sum"][0] == float(ids.astype(np.uint64).sum())
+    d2 = b.intersect_dump(ids.copy())
+    assert all(np.array_equal(d[k], d2[k]) for k in d)
+    small = b.intersect_dump(ids[:1000])
+    assert np.array_equal(small["intersect_ids"], ids[:1000].astype(np.float64))
+    b.dump_outputs(str(tmp_path / "out"), small)
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(k + ".npy" for k in small)
+    assert np.array_equal(np.load(tmp_path / "out" / "intersect_ids.npy"), small["intersect_ids"])
 
 
 def test_gpus_n_starts_n_ranks():
