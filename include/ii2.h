@@ -85,7 +85,8 @@ int ii2_abi_version(void);
 int ii2_ctx_create(int device, uint32_t flags, ii2_ctx **out);
 void ii2_ctx_destroy(ii2_ctx *ctx);
 const char *ii2_last_error(const ii2_ctx *ctx);     /* ctx may be NULL: last create error */
-int ii2_ctx_sync(ii2_ctx *ctx);                     /* waits for the ctx stream */
+int ii2_ctx_sync(ii2_ctx *ctx);                     /* waits for the ctx stream; fails once when an ii2_intersect_async
+                                                     * since the previous sync gave up (see ii2_ctx_counters) */
 void *ii2_ctx_stream(ii2_ctx *ctx);                 /* the hipStream_t, for event timing */
 int ii2_ctx_device(const ii2_ctx *ctx);             /* the device ordinal the context is bound to (-1 for NULL) */
 
@@ -316,8 +317,12 @@ int ii2_selftest(ii2_ctx *ctx);
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel
- *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0)
- *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters)
+ *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0);
+ *                                           tests: -1 / -2 force a give-up of the one-pass encoder's look-back (see below)
+ *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters).
+ *                                           intersect.and2_spin < 0 (tests) forces a give-up: -1 workgroup 1 at once, -2 one
+ *                                           workgroup in the middle of the grid only after the last workgroup has stored the count
+ *                                           (which then looks valid; the host learns it from the error word alone)
  *   merge.alone                             Mi input postings above which a merge's tile kernel does not share the GPU with another
  *                                           context's (default 64: big ones only get in each other's way, small ones hide each other's tails)
  *   debug.no_chain                          experiments: the kernels that wait between workgroups (one-launch AND, one-pass encoder,
@@ -342,8 +347,13 @@ int ii2_profile_read(ii2_ctx *ctx, double *total_ms, uint64_t *launches);
  * between workgroups of one launch ran out.  Those launches (the merge's direct placement, the one-launch AND, the one-pass
  * encoder) order their output by letting a workgroup wait for workgroups with smaller indices; that terminates because the
  * hardware starts a launch's workgroups in index order, which HIP does not promise - hence the bound, and the repeat on a path
- * without such waits (results identical).  out[2] = host waits (stream synchronisations) spent inside ii2_allgatherv* /
- * ii2_seg_allgather / ii2_seg_concat so far.  n = number of words `out` holds (3 are written). */
+ * without such waits (results identical).  A synchronous call (ii2_intersect, ii2_merge_segments_to_seg) notices its own
+ * launch's give-up - by the count or byte count, which is all ones, or by the launch's error word when the give-up came after
+ * the count was stored - and returns the repeated, exact result; nothing of it is reported later.  A launch of
+ * ii2_intersect_async that gave up makes the next ii2_ctx_sync fail (once), whatever calls came in between.
+ * out[2] = host waits (stream synchronisations) spent inside ii2_allgatherv* / ii2_seg_allgather / ii2_seg_concat so far.
+ * out[3] = stream waits the per-device order of those launches (across contexts) put in front of this context's launches:
+ * 0 while one context works alone.  n = number of words `out` holds (up to 4 are written). */
 int ii2_ctx_counters(ii2_ctx *ctx, uint64_t *out, uint32_t n);
 int ii2_profile_region(ii2_ctx *ctx, int begin);
 int ii2_profile_region_ms(ii2_ctx *ctx, double *ms);

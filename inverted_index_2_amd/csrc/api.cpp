@@ -27,6 +27,8 @@ static int fail(ii2_ctx *ctx, int code, const char *msg) {
     if (ctx) ctx->err = msg;
     return code;
 }
+static void lb_fold_pending(ii2_ctx *ctx);      // look-back error word of asynchronous launches (below, ii2_lookback_prepare)
+static int lb_note_pending(ii2_ctx *ctx);
 
 // temp device allocation freed at scope exit (cold paths only: encode / import / host calls)
 struct DevBuf {
@@ -190,15 +192,21 @@ int ii2_ctx_sync(ii2_ctx *ctx) {
     if (!ctx) return II2_EINVAL;
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // asynchronous two-list ANDs since the last look: did a bounded wait of any of them run out?  (its count is all ones, or -
+    // when the workgroup gave up after the last one had stored the count - its ids are incomplete)  Those a synchronous call
+    // or the records' reset came after were looked at then (lb_note_pending).
+    lb_fold_pending(ctx);
+    bool failed = ctx->lb_async_failed;
+    ctx->lb_async_failed = false;
     if (ctx->lb_pending && ctx->d_lb) {
-        // asynchronous two-list ANDs since the last look: did a bounded wait of any of them run out?  (its count is all ones)
         unsigned long long e = 0;
         const uint32_t first = ctx->lb_pending;
         ctx->lb_pending = 0;
         HIP_TRY(ctx, hipMemcpy(&e, ctx->d_lb, sizeof e, hipMemcpyDeviceToHost));
-        if (e >= first && e <= ctx->lb_epoch)
-            return fail(ctx, II2_EHIP, "ii2_intersect_async: a workgroup's bounded wait ran out (that call's count is all ones); repeat it with ii2_intersect");
+        failed |= e >= first && e <= ctx->lb_epoch;
     }
+    if (failed)
+        return fail(ctx, II2_EHIP, "ii2_intersect_async: a workgroup's bounded wait ran out (that call's count is all ones or its ids are incomplete); repeat it with ii2_intersect");
     return II2_OK;
 }
 
@@ -399,10 +407,11 @@ int ii2_seg_encode_stream_unlocked(ii2_ctx *ctx, uint64_t n_lists, const uint64_
     uint32_t *d_part = ws_take<uint32_t>(ctx, n_part);
     HIP_TRY(ctx, launch_enc_list_blocks(d_post_off, n_lists, d_nblk, st));
     HIP_TRY(ctx, scan_excl_u32(d_scan_tmp, tmpb, d_nblk, seg->d_blk_off, n_lists + 1, st));
+    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
     LookBack lb;
     if (int rcl = ii2_lookback_prepare(ctx, (size_t)enc_stream_workgroups(n_postings), &lb)) return rcl;
     ctx->lb_pending = 0;                           // (this call looks at its own result below)
-    if (ctx->opt_encode_stream < 0) lb.spin = 0xFFFFFFFFu;      // tests: a wait runs out, the two-pass encoder takes over
+    if (ctx->opt_encode_stream < 0) lb.spin = ctx->opt_encode_stream == -2 ? LB_SPIN_LATE : LB_SPIN_EARLY;      // tests: a wait runs out (-2: late), the two-pass encoder takes over
     uint64_t *d_res = ctx->d_mail + 8;
     unsigned long long *d_dbg = nullptr;
     if (ctx->opt_debug_stamps == 3) {              // diagnostics: the encoder's cycle counters
@@ -417,13 +426,17 @@ int ii2_seg_encode_stream_unlocked(ii2_ctx *ctx, uint64_t n_lists, const uint64_
         })) return rcq;
     HIP_TRY(ctx, launch_enc_list_meta(d_post_off, d_values, n_lists, seg->d_cnt, seg->d_last_doc, st));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + 8, d_res, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_OWN, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     // the mirrors a finished segment keeps (list spans of small segments) depend on nothing the host still has to learn: they are
     // enqueued behind the encoder and ONE wait serves the byte count and them
     bool count_view = false;
     if (int rcf = seg_finish_enqueue(ctx, seg.get(), true, &count_view)) return rcf;
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    lb_fold_pending(ctx);
     const uint64_t nbytes = ctx->h_mail[8], nb = ctx->h_mail[9];
-    if (nbytes == ~0ull || nb > nb_bound) {        // a bounded wait ran out, or the bound did not hold: the exact two-pass form
+    // a bounded wait ran out (the byte count is all ones - or looks valid when the workgroup gave up after the last one had
+    // stored it: the error word tells), or the bound did not hold: the exact two-pass form
+    if (nbytes == ~0ull || ctx->h_mail[II2_MAIL_LB_OWN] == lb.epoch || nb > nb_bound) {
         ctx->lb_fallbacks++;
         seg.reset();
         return ii2_seg_encode_dev_unlocked(ctx, n_lists, d_post_off, d_values, n_postings, out);
@@ -930,13 +943,14 @@ int ii2_lookback_launch(ii2_ctx *ctx, bool exclusive, const std::function<hipErr
         HIP_TRY(ctx, hipEventRecord(c.ev_x, c.x_stream));
         c.x_recorded = true; c.x_owner = c.x_stream; c.x_stream = nullptr;
     }
-    if (c.x_recorded && c.x_owner != me) HIP_TRY(ctx, hipStreamWaitEvent(me, c.ev_x, 0));
+    if (c.x_recorded && c.x_owner != me) { HIP_TRY(ctx, hipStreamWaitEvent(me, c.ev_x, 0)); ctx->lb_waits++; }
     if (exclusive) {
         // ... and behind every shared kernel since then
         for (unsigned i = 0; i < c.n_s; i++) {
             if (c.s_stream[i] == me) continue;
             HIP_TRY(ctx, hipEventRecord(c.ev_s[i], c.s_stream[i]));
             HIP_TRY(ctx, hipStreamWaitEvent(me, c.ev_s[i], 0));
+            ctx->lb_waits++;
         }
         c.n_s = 0;
         HIP_TRY(ctx, launch());
@@ -947,6 +961,7 @@ int ii2_lookback_launch(ii2_ctx *ctx, bool exclusive, const std::function<hipErr
         if (!known && c.n_s == 16u) {          // (more than 16 streams with a shared kernel in flight: this one queues behind the first)
             HIP_TRY(ctx, hipEventRecord(c.ev_s[0], c.s_stream[0]));
             HIP_TRY(ctx, hipStreamWaitEvent(me, c.ev_s[0], 0));
+            ctx->lb_waits++;
             c.s_stream[0] = me;
             known = true;
         }
@@ -968,10 +983,36 @@ void ii2_lookback_forget(ii2_ctx *ctx) {
     c.n_s = k;
 }
 
+// The error word holds the epoch of the LAST launch that gave up, and ii2_ctx_sync looks at it for the asynchronous launches
+// since the previous sync (lb_pending .. lb_epoch).  A synchronous call's own launch may overwrite it, and new records clear
+// it: before either, the word is copied into the mailbox behind those launches (lb_note_pending), and once the stream has
+// passed the copy (lb_fold_pending) a give-up among them is kept for ii2_ctx_sync.  A synchronous call's own give-up is
+// handled by that call (repeated, exact) and never reported there.
+static void lb_fold_pending(ii2_ctx *ctx) {
+    if (!ctx->lb_snap_first) return;
+    const uint64_t e = ctx->h_mail[II2_MAIL_LB_PENDING];
+    if (e >= ctx->lb_snap_first && e <= ctx->lb_snap_last) ctx->lb_async_failed = true;
+    ctx->lb_snap_first = ctx->lb_snap_last = 0;
+}
+static int lb_note_pending(ii2_ctx *ctx) {
+    if (!ctx->lb_pending || !ctx->d_lb) return II2_OK;
+    if (ctx->lb_snap_first) {                       // (an earlier copy nobody has looked at: only after a call that failed)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        lb_fold_pending(ctx);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_PENDING, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->lb_snap_first = ctx->lb_pending;
+    ctx->lb_snap_last = ctx->lb_epoch;
+    ctx->lb_pending = 0;
+    return II2_OK;
+}
+
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb) {
     hipStream_t st = ctx->stream;
     if (n_wg > ctx->lb_cap || ctx->lb_epoch >= (1u << 24) - 1u) {
+        if (int rcn = lb_note_pending(ctx)) return rcn;       // (the records are about to be cleared)
         HIP_TRY(ctx, hipStreamSynchronize(st));
+        lb_fold_pending(ctx);
         if (n_wg > ctx->lb_cap) {
             if (ctx->d_lb) (void)hipFree(ctx->d_lb);
             ctx->d_lb = nullptr;
@@ -1107,7 +1148,8 @@ static int intersect_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *se
             // one launch (k_and2_fused): the look-back records live in a buffer of their own (only these kernels write it, every
             // word tagged with its launch's number: nothing to clear between launches)
             if (int rcl = ii2_lookback_prepare(ctx, grid, &dp.lb)) return rcl;
-            if (ctx->opt_and2_spin) dp.lb.spin = ctx->opt_and2_spin > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_and2_spin, 0x7FFFFFFF) : 0xFFFFFFFFu;
+            if (ctx->opt_and2_spin)
+                dp.lb.spin = ctx->opt_and2_spin > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_and2_spin, 0x7FFFFFFF) : ctx->opt_and2_spin == -2 ? LB_SPIN_LATE : LB_SPIN_EARLY;
             const double spanA = (double)dp.last_doc[1] - (double)dp.first_doc[1] + 1.0;
             dp.a_scale = (float)((double)views[1].nblk / spanA);
             dp.b_dpb = (float)per_block_span;
@@ -1376,15 +1418,20 @@ int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const ui
     // the count lands in the pinned host mailbox directly (the kernels write it once, at their end): one stream
     // synchronisation, no copy behind it
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
     int rc = intersect_unlocked(ctx, n, segs, list_idx, tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail);
     if (rc) return rc;
+    const uint32_t own = ctx->lb_pending;           // epoch of this call's one-launch AND (0: it took another path)
+    ctx->lb_pending = 0;
+    if (own) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_OWN, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (!d_cnt) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_COUNT, ctx->d_mail, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    lb_fold_pending(ctx);
     *count = ctx->h_mail[II2_MAIL_COUNT];
-    if (*count == ~0ull && ctx->lb_pending) {
-        // a bounded wait of the one-launch two-list AND ran out (its workgroups did not start in index order): nothing is
-        // wrong with the inputs — the same query again through the two-kernel form, which has no inter-workgroup waits
-        ctx->lb_pending = 0;
+    if (own && (*count == ~0ull || ctx->h_mail[II2_MAIL_LB_OWN] == own)) {
+        // a bounded wait of the one-launch two-list AND ran out (its workgroups did not start in index order; the count is all
+        // ones, or looks valid when the workgroup gave up after the last one had stored it): nothing is wrong with the inputs —
+        // the same query again through the two-kernel form, which has no inter-workgroup waits
         ctx->lb_fallbacks++;
         const int64_t keep = ctx->opt_intersect_and2;
         ctx->opt_intersect_and2 = 2;
@@ -1395,7 +1442,6 @@ int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const ui
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         *count = ctx->h_mail[II2_MAIL_COUNT];
     }
-    ctx->lb_pending = 0;
     if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_intersect: result does not fit the output buffer (content unspecified)");
     return II2_OK;
 }
@@ -1428,6 +1474,7 @@ int ii2_ctx_counters(ii2_ctx *ctx, uint64_t *out, uint32_t n) {
     if (n > 0) out[0] = ctx->merge_fallbacks;
     if (n > 1) out[1] = ctx->lb_fallbacks;
     if (n > 2) out[2] = ctx->comm_syncs;
+    if (n > 3) out[3] = ctx->lb_waits;
     return II2_OK;
 }
 

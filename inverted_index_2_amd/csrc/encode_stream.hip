@@ -77,7 +77,8 @@ struct EncStreamParams {
     uint32_t *blk_list;          // [n_blocks + 1]
     uint64_t payload_cap;        // bytes the payload may take (the call fails, nothing useful written, when the bytes exceed it)
     const uint32_t *part;        // [waves] list that holds every wave's first position (k_enc_partition)
-    uint64_t *d_result;          // [0] payload bytes (all ones: a bounded wait ran out or the payload did not fit), [1] blocks
+    uint64_t *d_result;          // [0] payload bytes (all ones: a bounded wait ran out or the payload did not fit - a wait that runs
+                                 // out after the last workgroup looked shows only in the error word), [1] blocks
     LookBack lb;
     unsigned long long *debug;   // optional per-workgroup cycle counters [2048][8] (option debug.stamps: diagnostics)
 };
@@ -400,9 +401,11 @@ template <bool STAMPS> __global__ __launch_bounds__(256) void k_enc_stream(EncSt
         uint32_t pm = 0;
         const bool ok = STAMPS ? lb_prefix(p.lb, g, gridDim.x, total, &pre, &polls, &pm) : lb_prefix(p.lb, g, gridDim.x, total, &pre);
         tacc[7] = polls | ((unsigned long long)pm << 32);
+        bool late = false;                  // (tests: a give-up after the last workgroup has stored the byte count - lookback.h)
+        if (p.lb.spin == LB_SPIN_LATE && ok && total != 0u && lb_late_pick(g, gridDim.x)) late = lb_late_wait(p.lb);
         if (l == 0) {
             wg_off = ok ? pre : 0ull;
-            if (!ok) { wg_err = 1u; lb_fail(p.lb); }
+            if (!ok || late) { wg_err = 1u; lb_fail(p.lb); }
         }
     }
     lds_barrier();
@@ -422,6 +425,7 @@ template <bool STAMPS> __global__ __launch_bounds__(256) void k_enc_stream(EncSt
             p.blk_list[nblk] = 0xFFFFFFFFu;
             for (uint32_t k = 0; k < 16u; k++) p.payload[nbytes + k] = 0;
         }
+        if (p.lb.spin == LB_SPIN_LATE) lb_late_done(p.lb);
     }
     if (A.nloc == 0u || err || !fits || big) return;
     es_tile_flush(p, A, st, base);

@@ -15,6 +15,8 @@
 // mailbox layout (u64 words; h_mail and d_mail both hold II2_MAIL_WORDS)
 constexpr size_t II2_MAIL_WORDS = 1024;
 constexpr size_t II2_MAIL_COUNT = 200;     // word of h_mail that receives the result count of ii2_intersect / ii2_union
+constexpr size_t II2_MAIL_LB_OWN = 24;     // the look-back error word behind a synchronous call's own launch ...
+constexpr size_t II2_MAIL_LB_PENDING = 25; // ... and in front of it, as the asynchronous launches before it left it
 constexpr size_t II2_MAIL_COMM = 256;      // all-gatherv: {count, cap} of this rank, then of every rank (2 + 2 * II2_MAX_RANKS words)
 
 struct ii2_ctx {
@@ -66,7 +68,11 @@ struct ii2_ctx {
     size_t lb_cap = 0;                  // workgroups the records hold
     uint32_t lb_epoch = 0;              // launches so far
     uint64_t lb_fallbacks = 0;          // calls repeated through the two-kernel form
-    uint32_t lb_pending = 0;            // epoch of a fused launch whose error word has not been looked at yet (0: none)
+    uint32_t lb_pending = 0;            // first epoch of the look-back launches whose error word has not been looked at yet (0: none)
+    uint32_t lb_snap_first = 0;         // epochs lb_pending .. lb_epoch as they were when the error word was copied into
+    uint32_t lb_snap_last = 0;          //   h_mail[II2_MAIL_LB_PENDING] (0: no such copy waiting to be looked at)
+    bool lb_async_failed = false;       // one of those gave up: ii2_ctx_sync reports it
+    uint64_t lb_waits = 0;              // stream waits ii2_lookback_launch put in front of this context's launches (per-device order)
     int64_t opt_intersect_and2 = 1;     // dense 2-list ANDs: the shorter list's postings are tested against the longer one's bitmap (intersect_and2.hip)
     int64_t opt_profile_events = 0;     // N > 0: bracket the dominant kernel of every Nth call with HIP events
     uint64_t prof_calls = 0;
@@ -260,8 +266,10 @@ struct LookBack {
     unsigned long long *grp;     // [2 * ceil(workgroups / 64)]
     unsigned long long *err;     // = epoch when a bounded wait ran out
     uint32_t epoch;              // this launch's number, 1 .. 2^24 - 1
-    uint32_t spin;               // polls a wait may take (0: default; 0xFFFFFFFF: tests - workgroup 1 gives up at once)
+    uint32_t spin;               // polls a wait may take (0: default; or one of the two test values below)
 };
+constexpr uint32_t LB_SPIN_EARLY = 0xFFFFFFFFu;     // tests: workgroup 1 gives up at once
+constexpr uint32_t LB_SPIN_LATE = 0xFFFFFFFEu;      // tests: one workgroup gives up after the last one has stored the count (lookback.h)
 
 // dense streaming intersection (intersect_dense.hip)
 constexpr uint32_t DENSE_MAXL = 4;             // lists it takes

@@ -593,8 +593,9 @@ __global__ __launch_bounds__(256) void k_and2_expand(DenseParams p) {
 // writes them out once it knows where — the number of ids of all workgroups before its own.
 //
 // That prefix comes from the look-back of lookback.h (two hops behind the slowest workgroup it depends on; every wait bounded:
-// a workgroup that runs out of patience leaves without writing ids, the last workgroup then poisons the count - all ones - and
-// the host repeats a failed call through the two kernels above).
+// a workgroup that runs out of patience leaves without writing ids and stores the launch's epoch into the error word; the last
+// workgroup poisons the count - all ones - if it already sees that word set, but a give-up may come after it looked, so the host
+// reads the error word itself and repeats a failed call through the two kernels above).
 constexpr uint32_t A2F_STAGE_W = (A2_STAGE + 1u) / 2u;            // stage in words (aliases the bitmap, which is dead by then)
 constexpr uint32_t A2F_WAVE_LDS = (A2F_STAGE_W > A2_NW ? A2F_STAGE_W : A2_NW) + A2_HS;
 static_assert(A2F_STAGE_W % 4u == 0u, "16-byte alignment of the per-wave LDS regions");
@@ -866,9 +867,11 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
     if (wv == 0u) {
         unsigned long long pre = 0ull;
         const bool ok = lb_prefix(p.lb, g, gridDim.x, total, &pre);
+        bool late = false;                  // (tests: a give-up after the last workgroup has stored the count - lookback.h)
+        if (p.lb.spin == LB_SPIN_LATE && ok && total != 0u && lb_late_pick(g, gridDim.x)) late = lb_late_wait(p.lb);
         if (l == 0) {
             wg_off = ok ? pre : 0ull;
-            if (!ok) { wg_err = 1u; lb_fail(p.lb); }
+            if (!ok || late) { wg_err = 1u; lb_fail(p.lb); }
         }
     }
     II2_STAMP(6)              // look-back
@@ -878,6 +881,7 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
     if (g == gridDim.x - 1u && threadIdx.x == 0) {          // the last workgroup: the total, or all ones when some workgroup gave up
         const bool anyerr = err || lb_failed(p.lb);
         *p.d_count = anyerr ? ~0ull : wg_off + total;
+        if (p.lb.spin == LB_SPIN_LATE) lb_late_done(p.lb);
     }
     if (work && !err && count != 0u) {
         if (!wide) {

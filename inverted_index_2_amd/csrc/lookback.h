@@ -36,7 +36,8 @@ __device__ __forceinline__ unsigned long long lb_ld(const unsigned long long *q)
 __device__ __forceinline__ void lb_st(unsigned long long *q, unsigned long long v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long lb_tag(const LookBack &lb) { return (unsigned long long)lb.epoch << LB_VALUE_BITS; }
 __device__ __forceinline__ bool lb_ready(const LookBack &lb, unsigned long long rec) { return (uint32_t)(rec >> LB_VALUE_BITS) == lb.epoch; }
-__device__ __forceinline__ uint32_t lb_limit(const LookBack &lb) { return lb.spin ? lb.spin : LB_SPIN; }
+// (lb.spin = LB_SPIN_EARLY / LB_SPIN_LATE, tests: every wait but the forced give-up keeps the default bound)
+__device__ __forceinline__ uint32_t lb_limit(const LookBack &lb) { return lb.spin == 0u || lb.spin >= LB_SPIN_LATE ? LB_SPIN : lb.spin; }
 
 // sum over the wave of values < 2^40 (all lanes active): two 20-bit halves through the DPP scan - a 64-bit shuffle butterfly is
 // twelve LDS round trips on the one wave every other wave of the workgroup is waiting for
@@ -80,7 +81,7 @@ __device__ __forceinline__ bool lb_prefix(const LookBack &lb, uint32_t g, uint32
                                           uint32_t *polls = nullptr, uint32_t *polls_members = nullptr) {
     const uint32_t l = (uint32_t)lane_id(), G = g / LB_GROUP, gi = g % LB_GROUP;
     const uint32_t limit = lb_limit(lb);
-    if (lb.spin == 0xFFFFFFFFu && g == 1u) return false;
+    if (lb.spin == LB_SPIN_EARLY && g == 1u) return false;
     // Three sets of records, ALL requested in the same round (an uncached load under a streaming kernel's traffic is ~3 us: three
     // rounds one after the other were most of a workgroup's life in k_enc_stream):
     //   a   members of my group before me;
@@ -148,5 +149,35 @@ __device__ __forceinline__ bool lb_prefix(const LookBack &lb, uint32_t g, uint32
 // ONE lane: a wait ran out
 __device__ __forceinline__ void lb_fail(const LookBack &lb) { lb_st(lb.err, (unsigned long long)lb.epoch); }
 __device__ __forceinline__ bool lb_failed(const LookBack &lb) { return lb_ld(lb.err) == (unsigned long long)lb.epoch; }
+
+// ---- tests only (lb.spin == LB_SPIN_LATE): a give-up that comes after the last workgroup has looked at the error word.
+// The host must notice it by the error word alone: the count / byte count the last workgroup stored looks valid.
+// The chosen workgroup is in the middle of the grid, is not a group's last workgroup (nobody reads a prefix of it) and is not
+// the launch's last one, so once its own prefix is known nothing waits for it and every other workgroup finishes.  It waits for
+// the "last workgroup done" word, lb.err[1] (a free header word: agg[] starts at lb.err + 8), to carry this launch's epoch and
+// only then gives up (lb_fail, no output).  A bound that runs out first injects nothing: the host then sees no repeat at all, so
+// the test fails loudly instead of passing on an early give-up by chance.
+__device__ __forceinline__ bool lb_late_pick(uint32_t g, uint32_t n_wg) {
+    if (n_wg < 3u) return false;
+    uint32_t c = n_wg / 2u;                  // <= n_wg - 2
+    if (lb_is_leader(c, n_wg)) c--;
+    return g == c;
+}
+// ONE WAVE of the chosen workgroup, after its lb_prefix: true when the last workgroup is done (then give up)
+__device__ __forceinline__ bool lb_late_wait(const LookBack &lb) {
+    for (uint32_t spins = 0; spins <= LB_SPIN; spins++) {
+        if (lb_ld(lb.err + 1) == (unsigned long long)lb.epoch) return true;
+        __builtin_amdgcn_s_sleep(16);
+    }
+    return false;
+}
+// ONE lane of the last workgroup, after it has stored its count.  That store's value came from the lb_failed load, so the load
+// has returned before the count store could issue; the wait makes the same order explicit to the compiler and the hardware
+// for this store, which has no data dependency of its own.  A give-up the chosen workgroup stores after seeing this word is
+// therefore one that lb_failed did NOT see.
+__device__ __forceinline__ void lb_late_done(const LookBack &lb) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lb_st(lb.err + 1, (unsigned long long)lb.epoch);
+}
 
 }  // namespace ii2

@@ -194,7 +194,9 @@ static int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n
         HIP_TRY(ctx, launch_merge_pack(p, d_tile_off, st));
     }
     HIP_TRY(ctx, launch_merge_large_counts(p, d_tile_off, st));
-    // (the same launch leaves the direct placement's error word and the tile count in the mailbox: one copy fetches everything)
+    // (the same launch leaves the direct placement's error word and the tile count in the mailbox: one copy fetches everything.
+    // Being a later kernel, it reads the word after EVERY workgroup of the tile kernel has finished - no give-up can come after
+    // the look, unlike the last-workgroup check of the look-back kernels, lookback.h)
     HIP_TRY(ctx, launch_count_nonzero(d_cnt, T, ctx->d_mail + 2, st, p.direct ? &p.sync->error : nullptr, p.n_tiles_dev, ctx->d_mail));
     // all-or-nothing: like the packing pass, the offsets are only written when the result fits the caller's buffer
     if (d_out_off) HIP_TRY(ctx, scan_excl_u32_to_u64_guarded(d_scan, scan_b, d_cnt, d_out_off, n1, ctx->d_mail, out_cap, st));

@@ -121,10 +121,11 @@ class Context:
 
     def counters(self):
         """(merges repeated on the packing path, look-back launches repeated on their second path, host waits inside the exchange
-        entry points) - see ii2_ctx_counters."""
-        out = (C.c_uint64 * 3)()
-        self._ck(self.lib.ii2_ctx_counters(self.h, out, 3))
-        return int(out[0]), int(out[1]), int(out[2])
+        entry points, stream waits the per-device order of look-back launches put in front of this context's) - see
+        ii2_ctx_counters."""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.ii2_ctx_counters(self.h, out, 4))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     def profile_read(self):
         """(total device ms, launches) of the dominant kernel since the last read (option profile.events)."""

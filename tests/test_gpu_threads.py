@@ -71,7 +71,8 @@ def test_kernels_that_wait_between_workgroups_do_not_starve_each_other_across_co
     lower-numbered workgroups of their own launch.  Two such kernels from two contexts side by side can hold each other's slots
     (seen: three contexts encoding at once - every encoder ran out its bounded waits, seconds each, and handed over to its
     second path): the library orders them per device (api.cpp: ii2_lookback_launch).  Four contexts on four threads, launches big
-    enough to fill the chip several times over: right results, and NO launch repeated on its second path."""
+    enough to fill the chip several times over: right results on every repetition, NO launch repeated on its second path, and
+    the order did put waits in front of the workers' launches (counters()[3]; with debug.no_chain = 1 it stays 0)."""
     D = 40_000_000
     a, b = synth.zipf_list(2, D), synth.zipf_list(3, D)                 # dense: the one-launch AND (~4000 workgroups... of 256 docs x 16 blocks)
     shared = ctx.encode_lists([a, b])
@@ -94,10 +95,10 @@ def test_kernels_that_wait_between_workgroups_do_not_starve_each_other_across_co
                 assert st.n_out == ref_vals.size
                 out, n = c.intersect([(shared, 0), (shared, 1)])
                 assert n == want_and.size
+                assert np.array_equal(out.download(n), want_and), ("intersect", i, rep)
                 if rep == 4:
                     po, v = m.decode()
                     assert np.array_equal(po, ref_off) and np.array_equal(v, ref_vals), ("merge_to_segment", i)
-                    assert np.array_equal(out.download(n), want_and), ("intersect", i)
                 m.free()
         except BaseException as e:  # noqa: BLE001
             errors.append((i, repr(e)))
@@ -110,6 +111,8 @@ def test_kernels_that_wait_between_workgroups_do_not_starve_each_other_across_co
     assert not errors, errors
     repeats = [w.counters()[:2] for w in workers]
     assert all(r == (0, 0) for r in repeats), repeats
+    waits = [w.counters()[3] for w in workers]
+    assert sum(waits) > 0, waits
     for w in workers:
         w.close()
 
