@@ -261,24 +261,6 @@ struct ii2_align {
     }
 };
 
-#define HIP_TRY(ctx, expr)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return II2_EHIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-static int fail(ii2_ctx *ctx, int code, const char *msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-int ii2_ws_reserve(ii2_ctx *ctx, size_t bytes);          // api.cpp
-int ii2_seg_adopt_view(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, uint32_t *d_blk_off, uint32_t *d_cnt, uint32_t *d_last_doc,
-                       uint32_t *d_blk_list, ii2_seg **out);   // api.cpp
-
 extern "C" {
 
 static int dict_create_unlocked(ii2_ctx *ctx, const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n, int where, ii2_dict **out) {

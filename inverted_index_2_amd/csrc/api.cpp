@@ -1,6 +1,6 @@
-// api.cpp — the C ABI of libii2_hip.so (include/ii2.h): contexts, segments, tombstones,
-// intersect / union / merge entry points and the host-buffer convenience calls.
-// There is deliberately no CPU implementation behind any entry point.
+// api.cpp — the C ABI of libii2_hip.so (include/ii2.h): contexts, workspace, segments and their encoders,
+// tombstones, the per-device order of look-back kernels, self-test, counters and options.  AND / OR live in
+// setop.cpp, the merge in ops.cpp.  There is deliberately no CPU implementation behind any entry point.
 #include <algorithm>
 #include <functional>
 #include <cstdio>
@@ -13,32 +13,6 @@
 using namespace ii2;
 
 static thread_local std::string g_create_err;
-
-#define HIP_TRY(ctx, expr)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return II2_EHIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-static int fail(ii2_ctx *ctx, int code, const char *msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-static void lb_fold_pending(ii2_ctx *ctx);      // look-back error word of asynchronous launches (below, ii2_lookback_prepare)
-static int lb_note_pending(ii2_ctx *ctx);
-
-// temp device allocation freed at scope exit (cold paths only: encode / import / host calls)
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return ii2::dm_malloc_retry(&p, bytes ? bytes : 16); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // Workspace: reserve the total up front, then carve.
 int ii2_ws_reserve(ii2_ctx *ctx, size_t bytes) {
@@ -53,12 +27,6 @@ int ii2_ws_reserve(ii2_ctx *ctx, size_t bytes) {
     ctx->ws_cap = want;
     return II2_OK;
 }
-template <class T> static T *ws_take(ii2_ctx *ctx, size_t count) {
-    size_t bytes = align_up(count * sizeof(T));
-    T *p = (T *)(ctx->ws + ctx->ws_used);
-    ctx->ws_used += bytes;
-    return p;
-}
 
 void *ii2_pool_get(ii2_ctx *ctx, int slot, size_t bytes) {
     if (bytes <= ctx->pool_cap[slot] && ctx->pool[slot]) return ctx->pool[slot];
@@ -70,6 +38,13 @@ void *ii2_pool_get(ii2_ctx *ctx, int slot, size_t bytes) {
     if (ii2::dm_malloc_retry((void **)&ctx->pool[slot], want) != hipSuccess) return nullptr;
     ctx->pool_cap[slot] = want;
     return ctx->pool[slot];
+}
+
+int ensure_debug(ii2_ctx *ctx, bool clear) {
+    const size_t bytes = (size_t)2048 * 8 * sizeof(unsigned long long);
+    if (!ctx->d_debug && ii2::dm_malloc_retry((void **)&ctx->d_debug, bytes) != hipSuccess) return fail(ctx, II2_ENOMEM, "debug buffer allocation failed");
+    if (clear) HIP_TRY(ctx, hipMemsetAsync(ctx->d_debug, 0, bytes, ctx->stream));
+    return II2_OK;
 }
 
 bool ii2_profile_pair(ii2_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1) {
@@ -415,9 +390,7 @@ int ii2_seg_encode_stream_unlocked(ii2_ctx *ctx, uint64_t n_lists, const uint64_
     uint64_t *d_res = ctx->d_mail + 8;
     unsigned long long *d_dbg = nullptr;
     if (ctx->opt_debug_stamps == 3) {              // diagnostics: the encoder's cycle counters
-        if (!ctx->d_debug && ii2::dm_malloc_retry((void **)&ctx->d_debug, (size_t)2048 * 8 * sizeof(unsigned long long)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "debug buffer allocation failed");
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_debug, 0, (size_t)2048 * 8 * sizeof(unsigned long long), st));
+        if (int rcd = ensure_debug(ctx, true)) return rcd;
         d_dbg = ctx->d_debug;
     }
     if (int rcq = ii2_lookback_launch(ctx, true, [&] {
@@ -723,7 +696,6 @@ int ii2_seg_host_cnt(ii2_ctx *ctx, const ii2_seg *seg) {
     return II2_OK;
 }
 
-// a view over src's store whose four per-slot arrays were built on the device (align.hip); takes ownership of them
 int ii2_seg_adopt_view(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, uint32_t *d_blk_off, uint32_t *d_cnt, uint32_t *d_last_doc,
                        uint32_t *d_blk_list, ii2_seg **out) {
     ii2_seg *seg = new (std::nothrow) ii2_seg();
@@ -817,86 +789,7 @@ void ii2_tomb_free(ii2_tomb *t) {
 
 }  // extern "C"
 
-// ---- intersect ------------------------------------------------------------------------------
-static int make_list_view(ii2_ctx *ctx, const ii2_seg *seg, uint64_t idx, ListView *v) {
-    if (!seg || idx >= seg->n_lists) return fail(ctx, II2_EINVAL, "list index out of range");
-    if (seg->device != ctx->device) return fail(ctx, II2_EINVAL, "segment lives on another device");
-    if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
-    const uint32_t b0 = seg->h_blk_off[idx], b1 = seg->h_blk_off[idx + 1];
-    v->skip = seg->d_skip + b0;
-    v->payload = seg->d_payload;
-    v->last_doc = seg->d_last_doc + idx;
-    v->nblk = b1 - b0;
-    v->pad = 0;
-    return II2_OK;
-}
-
-// device-side address of a word of the pinned host mailbox (hipHostMalloc memory is mapped), or null if the runtime
-// does not give one
-uint64_t *ii2_mapped_mail(ii2_ctx *ctx, uint32_t word) {
-    if (!ctx->d_mail_mapped) {
-        void *dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, ctx->h_mail, 0) != hipSuccess || !dp) { (void)hipGetLastError(); return nullptr; }
-        ctx->d_mail_mapped = (uint64_t *)dp;
-    }
-    return ctx->d_mail_mapped + word;
-}
-
-// AND / OR of lists that hold <= SMALL_SET_BLOCKS blocks together: one single-workgroup kernel (setop_small.hip).
-// *taken = false when the query is too large (or the path is switched off).
-static int ii2_setop_small_unlocked(ii2_ctx *ctx, bool is_union, uint32_t n, const ListView *views, const ii2_seg *const *segs,
-                             const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *d_count, bool *taken) {
-    *taken = false;
-    if (!ctx->opt_small_setop || n == 0 || n > MAX_LISTS) return II2_OK;
-    SmallSetParams sp;
-    std::memset(&sp, 0, sizeof sp);
-    uint32_t m = 0, nb = 0;
-    for (uint32_t i = 0; i < n; i++) {             // by blocks first: no size is fetched for a query that is too large anyway
-        if (views[i].nblk == 0 && !is_union) return II2_OK;      // (an AND with an empty list is answered by the caller)
-        if (views[i].nblk > SMALL_SET_BLOCKS - nb) return II2_OK;
-        nb += views[i].nblk;
-    }
-    nb = 0;
-    uint32_t np = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (views[i].nblk == 0) continue;
-        if (int rc = ii2_seg_host_cnt(ctx, segs[i])) return rc;
-        const uint32_t c = segs[i]->h_cnt[list_idx ? list_idx[i] : 0];
-        // an AND pays off below ~2k postings (the general path is four launches, ~14-20 us whatever the size); an OR up
-        // to the kernel's capacity (the merge passes are ~40 launches)
-        if (c > (is_union ? SMALL_SET_POSTINGS : SMALL_SET_POSTINGS / 4u) - np) return II2_OK;
-        sp.lists[m] = views[i];
-        sp.blk_base[m] = nb;
-        sp.lpre[m] = np;
-        nb += views[i].nblk;
-        np += c;
-        m++;
-    }
-    if (m == 0) return II2_OK;
-    sp.blk_base[m] = nb;
-    sp.lpre[m] = np;
-    sp.n_lists = m;
-    sp.n_blocks = nb;
-    sp.is_union = is_union ? 1u : 0u;
-    sp.tomb = tomb ? tomb->d_words : nullptr;
-    sp.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-    sp.out = d_out;
-    sp.out_cap = cap;
-    sp.d_count = d_count;
-    if (!ctx->d_small) {
-        const size_t bytes = ((size_t)SMALL_SET_POSTINGS + 16) * sizeof(uint32_t);
-        if (ii2::dm_malloc_retry((void **)&ctx->d_small, bytes) != hipSuccess) return fail(ctx, II2_ENOMEM, "small set-operation scratch allocation failed");
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_small, 0, bytes, ctx->stream));
-    }
-    sp.sorted = ctx->d_small;
-    sp.ticket = ctx->d_small + (size_t)SMALL_SET_POSTINGS;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    HIP_TRY(ctx, launch_setop_small(sp, ctx->stream, e0, e1));
-    *taken = true;
-    return II2_OK;
-}
-
+// ---- look-back kernels ------------------------------------------------------------------------
 // Look-back records for a launch of n_wg workgroups (lookback.h): a buffer of the context's own that only those kernels write,
 // every word tagged with its launch's number - nothing to clear between launches (cleared when it grows or the numbers wrap).
 // Kernels whose workgroups wait for lower-numbered workgroups of the SAME launch (lookback.h) must not share the GPU with
@@ -988,13 +881,13 @@ void ii2_lookback_forget(ii2_ctx *ctx) {
 // it: before either, the word is copied into the mailbox behind those launches (lb_note_pending), and once the stream has
 // passed the copy (lb_fold_pending) a give-up among them is kept for ii2_ctx_sync.  A synchronous call's own give-up is
 // handled by that call (repeated, exact) and never reported there.
-static void lb_fold_pending(ii2_ctx *ctx) {
+void lb_fold_pending(ii2_ctx *ctx) {
     if (!ctx->lb_snap_first) return;
     const uint64_t e = ctx->h_mail[II2_MAIL_LB_PENDING];
     if (e >= ctx->lb_snap_first && e <= ctx->lb_snap_last) ctx->lb_async_failed = true;
     ctx->lb_snap_first = ctx->lb_snap_last = 0;
 }
-static int lb_note_pending(ii2_ctx *ctx) {
+int lb_note_pending(ii2_ctx *ctx) {
     if (!ctx->lb_pending || !ctx->d_lb) return II2_OK;
     if (ctx->lb_snap_first) {                       // (an earlier copy nobody has looked at: only after a call that failed)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1035,416 +928,7 @@ int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb) {
     return II2_OK;
 }
 
-// first doc, first doc of the last block and last doc of a non-empty list: fetched once per (segment, list), then cached
-static int list_span(ii2_ctx *ctx, const ii2_seg *seg, uint64_t idx, const ListView &v, ii2_seg::ListSpan *out) {
-    if (seg->h_spans.size() == 3 * seg->n_lists && idx < seg->n_lists) {      // mirrored when the segment was created: no fetch, no sync
-        *out = ii2_seg::ListSpan{seg->h_spans[3 * idx], seg->h_spans[3 * idx + 1], seg->h_spans[3 * idx + 2]};
-        return II2_OK;
-    }
-    {
-        std::lock_guard<std::mutex> sg(seg->span_mu);
-        auto hit = seg->span_cache.find(idx);
-        if (hit != seg->span_cache.end()) { *out = hit->second; return II2_OK; }
-    }
-    ii2_skip e[2];
-    uint32_t last = 0;
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(&e[0], v.skip, sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(&e[1], v.skip + (v.nblk - 1), sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(&last, v.last_doc, sizeof last, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    *out = ii2_seg::ListSpan{e[0].first_doc, e[1].first_doc, last};
-    std::lock_guard<std::mutex> sg(seg->span_mu);
-    seg->span_cache[idx] = *out;
-    return II2_OK;
-}
-
-static int intersect_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
-                              const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *d_count) {
-    if (n == 0 || n > MAX_LISTS || !segs || !d_count) return fail(ctx, II2_EINVAL, "ii2_intersect: bad argument");
-    hipStream_t st = ctx->stream;
-    IntersectParams p;
-    std::memset(&p, 0, sizeof p);
-    std::vector<ListView> views(n);
-    bool any_empty = false;
-    for (uint32_t i = 0; i < n; i++) {
-        int rc = make_list_view(ctx, segs[i], list_idx ? list_idx[i] : 0, &views[i]);
-        if (rc) return rc;
-        any_empty |= views[i].nblk == 0;
-    }
-    if (any_empty) {
-        HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
-        return II2_OK;
-    }
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_intersect: output buffer is NULL");
-    if (ctx->opt_intersect_g <= 0) {
-        bool taken = false;
-        if (int rc = ii2_setop_small_unlocked(ctx, false, n, views.data(), segs, list_idx, tomb, d_out, cap, d_count, &taken)) return rc;
-        if (taken) return II2_OK;
-    }
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return views[a].nblk < views[b].nblk; });
-    std::vector<const ii2_seg *> vseg(n);
-    std::vector<uint64_t> vidx(n);
-    {
-        std::vector<ListView> sorted(n);
-        for (uint32_t i = 0; i < n; i++) { sorted[i] = views[order[i]]; vseg[i] = segs[order[i]]; vidx[i] = list_idx ? list_idx[order[i]] : 0; }
-        views.swap(sorted);
-    }
-    for (uint32_t i = 0; i < n; i++) p.lists[i] = views[i];
-    p.n_lists = n;
-    const uint32_t nblk0 = views[0].nblk;
-    // tile height: aim the tile's doc span at the LDS byte map; keep >= ~8 tiles per CU
-    uint32_t G = 1;
-    double per_block_span = 0;                   // docs per driver block (tile-height heuristics)
-    uint32_t dense_first_doc = 0, dense_last_doc = 0;
-    if (ctx->opt_intersect_g > 0) G = (uint32_t)std::min<int64_t>(ctx->opt_intersect_g, ISECT_GMAX);
-    else if (nblk0 > 1) {
-        ii2_seg::ListSpan ends;
-        if (int rc = list_span(ctx, vseg[0], vidx[0], views[0], &ends)) return rc;
-        const double per_block = (double)(ends.last_block_first_doc - ends.first_doc) / (double)(nblk0 - 1);
-        per_block_span = per_block;
-        dense_first_doc = ends.first_doc;
-        dense_last_doc = ends.last_doc;
-        const double g = per_block > 0 ? 0.85 * ISECT_SMAX / per_block : ISECT_GMAX;
-        G = g >= ISECT_GMAX ? ISECT_GMAX : g < 1 ? 1u : (uint32_t)g;
-        while (G > 1 && nblk0 / G < 8u * (uint32_t)ctx->cu_count) G >>= 1;
-    }
-    // Lists that are dense together (the headline 2-term query): every wave streams through its own run of driver
-    // blocks, no partition pass, no workgroup barriers (intersect_dense.hip).  The driver must be dense enough for
-    // the 1-bit-per-doc result bitmap to stay small next to the payload.
-    if (ctx->opt_intersect_dense && ctx->opt_intersect_g <= 0 && n >= 2 && n <= DENSE_MAXL && nblk0 >= 1024 &&
-        per_block_span > 0 && per_block_span <= 1100.0) {
-        DenseParams dp;
-        std::memset(&dp, 0, sizeof dp);
-        for (uint32_t i = 0; i < n; i++) {
-            dp.lists[i] = views[i];
-            ii2_seg::ListSpan sp;
-            if (int rc = list_span(ctx, vseg[i], vidx[i], views[i], &sp)) return rc;
-            dp.first_doc[i] = sp.first_doc;
-            dp.last_doc[i] = sp.last_doc;
-        }
-        dp.n_lists = n;
-        // a wave's passes take 16 driver blocks each; one round (16 blocks) per wave by default: more, shorter waves balance
-        // better than fewer, longer ones (measured on Zipf rank pairs 1/2 ... 2/3/5), and waves never wait for each other
-        uint32_t bpw = ctx->opt_dense_bpw > 0 ? (uint32_t)ctx->opt_dense_bpw : 16u;
-        bpw = std::min<uint32_t>(std::max<uint32_t>((bpw + 15u) & ~15u, 16u), 1024u);
-        dp.bpw = bpw;
-        dp.n_waves = (nblk0 + bpw - 1) / bpw;
-        const uint32_t grid = (dp.n_waves + 3u) / 4u;
-        dp.n_meta = grid * 4u;
-        dp.base32 = dense_first_doc & ~31u;
-        // two lists: the longer one is marked, the shorter one's postings are tested where they sit (intersect_and2.hip): the
-        // hand-over to the second kernel is one bit per posting of the shorter list instead of a result bitmap
-        const bool and2 = n == 2 && ctx->opt_intersect_and2 && bpw == 16u;
-        const uint64_t bm_words = and2 ? (uint64_t)dp.n_meta * 128u : (((uint64_t)dense_last_doc - dp.base32) >> 5) + 1 + dp.n_meta + 8;
-        size_t need = align_up(bm_words * sizeof(uint32_t)) + align_up((size_t)dp.n_meta * sizeof(uint4)) + align_up((size_t)grid * sizeof(uint32_t)) + 4096;
-        int rc = ii2_ws_reserve(ctx, need);
-        if (rc) return rc;
-        dp.bitmap = ws_take<uint32_t>(ctx, bm_words);
-        dp.hmask = and2 ? reinterpret_cast<uint2 *>(dp.bitmap) : nullptr;
-        if (and2 && ctx->opt_intersect_and2 == 1) {
-            // one launch (k_and2_fused): the look-back records live in a buffer of their own (only these kernels write it, every
-            // word tagged with its launch's number: nothing to clear between launches)
-            if (int rcl = ii2_lookback_prepare(ctx, grid, &dp.lb)) return rcl;
-            if (ctx->opt_and2_spin)
-                dp.lb.spin = ctx->opt_and2_spin > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_and2_spin, 0x7FFFFFFF) : ctx->opt_and2_spin == -2 ? LB_SPIN_LATE : LB_SPIN_EARLY;
-            const double spanA = (double)dp.last_doc[1] - (double)dp.first_doc[1] + 1.0;
-            dp.a_scale = (float)((double)views[1].nblk / spanA);
-            dp.b_dpb = (float)per_block_span;
-        }
-        dp.meta = ws_take<uint4>(ctx, dp.n_meta);
-        dp.wg_sum = ws_take<uint32_t>(ctx, grid);
-        dp.tomb = tomb ? tomb->d_words : nullptr;
-        dp.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-        dp.out = d_out;
-        dp.out_cap = cap;
-        dp.d_count = d_count;
-        dp.debug = nullptr;
-        if (ctx->opt_debug_stamps) {
-            if (!ctx->d_debug && ii2::dm_malloc_retry((void **)&ctx->d_debug, (size_t)2048 * 8 * sizeof(unsigned long long)) != hipSuccess)
-                return fail(ctx, II2_ENOMEM, "debug buffer allocation failed");
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_debug, 0, (size_t)2048 * 8 * sizeof(unsigned long long), st));
-            dp.debug = ctx->d_debug;
-            dp.debug_expand = ctx->opt_debug_stamps == 2 ? 1u : 0u;
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ii2_profile_pair(ctx, &e0, &e1);
-        if (and2 && dp.lb.agg) {           // (the one-launch form waits between workgroups: one such kernel per device at a time)
-            if (int rcq = ii2_lookback_launch(ctx, true, [&] { return launch_intersect_and2(dp, st, e0, e1); })) return rcq;
-        } else {
-            HIP_TRY(ctx, and2 ? launch_intersect_and2(dp, st, e0, e1) : launch_intersect_dense(dp, st, e0, e1));
-        }
-        return II2_OK;
-    }
-    // a tiny sparse driver (a rare term against long lists) would keep only a handful of workgroups busy, each decoding
-    // one block of the long list per candidate, one after the other: split its blocks over several tiles
-    uint32_t sub = 1;
-    if (n >= 2 && G == 1 && (per_block_span >= 8192.0 || (nblk0 == 1 && views[n - 1].nblk >= 64)) && ctx->opt_intersect_g <= 0) {
-        const uint32_t want_tiles = (ctx->opt_intersect_subtiles > 0 ? (uint32_t)ctx->opt_intersect_subtiles : 4u) * (uint32_t)ctx->cu_count;
-        if (nblk0 < want_tiles) sub = std::min<uint32_t>(ctx->opt_intersect_submax > 0 ? (uint32_t)ctx->opt_intersect_submax : 16u, (want_tiles + nblk0 - 1u) / nblk0);
-    }
-    p.G = G;
-    // the pipelined gallop pays when a driver block faces many blocks of a long list (candidates then hit distinct blocks)
-    p.sparse_driver = ((per_block_span >= 8192.0 && views[n - 1].nblk / 16u >= nblk0) || sub > 1) ? 1u : 0u;
-    p.sub = sub;
-    p.n_tiles = ((nblk0 + G - 1) / G) * sub;
-    const size_t dstride = 2 + 4 * (size_t)n;
-    p.desc_words = (uint32_t)dstride;
-    uint32_t slot_words = (ISECT_SMAX + 32u) / 32u;
-    if (slot_words < G * 256u) slot_words = G * 256u;
-    slot_words = (slot_words + 3u) & ~3u;
-    p.slot_words = slot_words;
-    size_t need = align_up((size_t)p.n_tiles * dstride * sizeof(uint32_t)) + align_up((size_t)p.n_tiles * slot_words * sizeof(uint32_t)) +
-                  2 * align_up(((size_t)p.n_tiles + 2) * sizeof(uint32_t)) + align_up(((size_t)p.n_tiles / 64 + p.n_tiles / 4096 + 4) * sizeof(uint32_t)) + 4096;
-    int rc = ii2_ws_reserve(ctx, need);
-    if (rc) return rc;
-    p.ranges = ws_take<uint32_t>(ctx, (size_t)p.n_tiles * dstride);
-    p.tmp = ws_take<uint32_t>(ctx, (size_t)p.n_tiles * slot_words);
-    p.tile_count = ws_take<uint32_t>(ctx, (size_t)p.n_tiles + 1);
-    p.n_sums1 = p.n_tiles / 64 + 1;
-    p.n_sums = p.n_sums1;
-    p.sums = ws_take<uint32_t>(ctx, p.n_sums);
-    uint64_t *d_tile_off = nullptr;
-    const uint32_t wgs_default = 5u;    // LDS per workgroup: ~29 KB
-    p.max_grid = (uint32_t)ctx->cu_count * (ctx->opt_intersect_wgs > 0 ? (uint32_t)ctx->opt_intersect_wgs : wgs_default);
-    p.bitmap_mode = ctx->opt_intersect_bitmap ? 1u : 0u;
-    // measured on 100M-doc Zipf pairs: the gallop path wins from ~32 docs per driver posting on (ranks 30/60: 80 -> 64 us),
-    // the map tiles below that (ranks 10/20: 78 vs 100 us)
-    p.map_docs_per_block = ctx->opt_intersect_map_docs > 0 ? (uint32_t)ctx->opt_intersect_map_docs : 8192u;
-    p.tomb = tomb ? tomb->d_words : nullptr;
-    p.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-    p.out = d_out;
-    p.out_cap = cap;
-    p.d_count = d_count;
-    p.debug = nullptr;
-    if (ctx->opt_debug_stamps) {
-        if (!ctx->d_debug && ii2::dm_malloc_retry((void **)&ctx->d_debug, (size_t)2048 * 8 * sizeof(unsigned long long)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "debug buffer allocation failed");
-        p.debug = ctx->d_debug;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    HIP_TRY(ctx, launch_intersect(p, d_tile_off, st, e0, e1));
-    return II2_OK;
-}
-
-// Union of lists that are dense TOGETHER (>= 1 posting per 16 docs of their common range): the byte-map tiles of
-// the intersection with OR semantics over fixed doc ranges — no decode-to-raw, no fold, ~20x the merge path's rate.
-int ii2_union_dense_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
-                             uint32_t *d_out, uint64_t cap, uint64_t *d_count, bool *taken) {
-    *taken = false;
-    if (!ctx->opt_union_dense || n == 0 || n > MAX_LISTS) return II2_OK;
-    hipStream_t st = ctx->stream;
-    IntersectParams p;
-    std::memset(&p, 0, sizeof p);
-    uint32_t m = 0;
-    uint64_t total_blocks = 0;
-    const ii2_seg *nz_seg[MAX_LISTS];
-    uint64_t nz_idx[MAX_LISTS];
-    for (uint32_t i = 0; i < n; i++) {
-        ListView v;
-        int rc = make_list_view(ctx, segs[i], list_idx ? list_idx[i] : 0, &v);
-        if (rc) return rc;
-        if (v.nblk == 0) continue;
-        nz_seg[m] = segs[i];
-        nz_idx[m] = list_idx ? list_idx[i] : 0;
-        p.lists[m++] = v;
-        total_blocks += v.nblk;
-    }
-    if (m == 0) return II2_OK;
-    if (total_blocks <= SMALL_SET_BLOCKS) {
-        if (int rc = ii2_setop_small_unlocked(ctx, true, m, p.lists, nz_seg, nz_idx, tomb, d_out, cap, d_count, taken)) return rc;
-        if (*taken) return II2_OK;
-    }
-    // a few lists of medium size: decode, rank every id by bisection in the other lists, filter, write (union_rank.hip)
-    if (ctx->opt_union_rank && m <= UNION_RANK_MAXL && total_blocks <= UNION_RANK_MAX_POSTINGS / II2_DV1_BLOCK + m) {
-        UnionRankParams up;
-        std::memset(&up, 0, sizeof up);
-        uint64_t np = 0;
-        uint32_t nb = 0;
-        for (uint32_t i = 0; i < m; i++) {
-            if (int rc = ii2_seg_host_cnt(ctx, nz_seg[i])) return rc;
-            up.lists[i] = p.lists[i];
-            up.blk_base[i] = nb;
-            up.lpre[i] = (uint32_t)np;
-            nb += p.lists[i].nblk;
-            np += nz_seg[i]->h_cnt[nz_idx[i]];
-        }
-        if (np <= UNION_RANK_MAX_POSTINGS) {
-            up.blk_base[m] = nb;
-            up.lpre[m] = (uint32_t)np;
-            up.n_lists = m;
-            up.n_blocks = nb;
-            const uint32_t nwg = (uint32_t)((np + 2047) / 2048);
-            const size_t need = 2 * align_up(np * sizeof(uint32_t)) + align_up(((size_t)nwg + 1) * sizeof(uint32_t)) + 4096;
-            if (int rc = ii2_ws_reserve(ctx, need)) return rc;
-            up.raw = ws_take<uint32_t>(ctx, np);
-            up.sorted = ws_take<uint32_t>(ctx, np);
-            up.wg_cnt = ws_take<uint32_t>(ctx, (size_t)nwg + 1);
-            up.tomb = tomb ? tomb->d_words : nullptr;
-            up.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-            up.out = d_out;
-            up.out_cap = cap;
-            up.d_count = d_count;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            ii2_profile_pair(ctx, &e0, &e1);
-            HIP_TRY(ctx, launch_union_rank(up, st, e0, e1));
-            *taken = true;
-            return II2_OK;
-        }
-    }
-    if (total_blocks < 64) return II2_OK;
-    p.n_lists = m;
-    // Few long lists, the longest one dense: the streaming kernel of the dense intersection with OR semantics — every
-    // wave walks its own run of blocks of the longest list (the pacer), the other lists mark into the same bitmap
-    // (intersect_dense.hip).  The lists' ends are cached per (segment, list): no host sync after the first use.
-    if (ctx->opt_union_stream && m >= 2 && m <= DENSE_MAXL) {
-        uint32_t pace = 0;
-        for (uint32_t i = 1; i < m; i++) if (p.lists[i].nblk > p.lists[pace].nblk) pace = i;
-        if (p.lists[pace].nblk >= 1024) {
-            DenseParams dp;
-            std::memset(&dp, 0, sizeof dp);
-            uint32_t u_lo = 0xFFFFFFFFu, u_hi = 0;
-            ii2_seg::ListSpan psp{};
-            for (uint32_t i = 0, o = 1; i < m; i++) {
-                ii2_seg::ListSpan sp;
-                if (int rc = list_span(ctx, nz_seg[i], nz_idx[i], p.lists[i], &sp)) return rc;
-                const uint32_t at = i == pace ? 0u : o++;
-                dp.lists[at] = p.lists[i];
-                dp.first_doc[at] = sp.first_doc;
-                dp.last_doc[at] = sp.last_doc;
-                if (i == pace) psp = sp;
-                u_lo = std::min(u_lo, sp.first_doc);
-                u_hi = std::max(u_hi, sp.last_doc);
-            }
-            const uint32_t nblk0 = dp.lists[0].nblk;
-            const double per_block = (double)(psp.last_block_first_doc - psp.first_doc) / (double)(nblk0 - 1);
-            // the stretches before the pacer's first and after its last doc are one wave's work each: keep them short
-            const uint64_t own = (uint64_t)psp.last_doc - psp.first_doc + 1, all = (uint64_t)u_hi - u_lo + 1;
-            if (per_block > 0 && per_block <= 1100.0 && all <= own + own / 4 + 65536) {
-                dp.n_lists = m;
-                dp.is_union = 1u;
-                dp.u_lo = u_lo;
-                dp.u_hi = u_hi;
-                dp.bpw = 16u;
-                dp.n_waves = (nblk0 + dp.bpw - 1) / dp.bpw;
-                const uint32_t grid = (dp.n_waves + 3u) / 4u;
-                dp.n_meta = grid * 4u;
-                dp.base32 = u_lo & ~31u;
-                const uint64_t bm_words = (((uint64_t)u_hi - dp.base32) >> 5) + 1 + dp.n_meta + 8;
-                size_t need = align_up(bm_words * sizeof(uint32_t)) + align_up((size_t)dp.n_meta * sizeof(uint4)) + align_up((size_t)grid * sizeof(uint32_t)) + 4096;
-                if (int rc = ii2_ws_reserve(ctx, need)) return rc;
-                dp.bitmap = ws_take<uint32_t>(ctx, bm_words);
-                dp.meta = ws_take<uint4>(ctx, dp.n_meta);
-                dp.wg_sum = ws_take<uint32_t>(ctx, grid);
-                dp.tomb = tomb ? tomb->d_words : nullptr;
-                dp.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-                dp.out = d_out;
-                dp.out_cap = cap;
-                dp.d_count = d_count;
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                ii2_profile_pair(ctx, &e0, &e1);
-                HIP_TRY(ctx, launch_intersect_dense(dp, st, e0, e1));
-                *taken = true;
-                return II2_OK;
-            }
-        }
-    }
-    // the lists' common doc range from their cached ends (one round trip per list the first time it is used, none after)
-    uint32_t mm[2] = {0xFFFFFFFFu, 0u};
-    for (uint32_t i = 0; i < m; i++) {
-        ii2_seg::ListSpan sp;
-        if (int rc = list_span(ctx, nz_seg[i], nz_idx[i], p.lists[i], &sp)) return rc;
-        mm[0] = std::min(mm[0], sp.first_doc);
-        mm[1] = std::max(mm[1], sp.last_doc);
-    }
-    if (mm[1] < mm[0]) return II2_OK;
-    constexpr uint32_t S = ISECT_SMAX - 64u;               // tile span: a multiple of 32 below the byte-map size
-    const uint32_t base = mm[0] & ~31u;
-    const uint64_t span = (uint64_t)mm[1] - base + 1;
-    if (total_blocks * II2_DV1_BLOCK * (uint64_t)ctx->opt_union_sparsity < span) return II2_OK;       // too sparse (the tile count grows with the span): the merge passes do better
-    const uint64_t n_tiles = (span + S - 1) / S;
-    if (n_tiles >= (1ull << 24)) return II2_OK;
-    p.op_union = 1u;
-    p.sub = 1u;
-    p.u_base = base;
-    p.u_span = S;
-    p.u_max = mm[1];
-    p.n_tiles = (uint32_t)n_tiles;
-    const size_t dstride = 2 + 4 * (size_t)m;
-    p.desc_words = (uint32_t)dstride;
-    p.slot_words = ((ISECT_SMAX + 32u) / 32u + 3u) & ~3u;
-    size_t need = align_up((size_t)p.n_tiles * dstride * sizeof(uint32_t)) + align_up((size_t)p.n_tiles * p.slot_words * sizeof(uint32_t)) +
-                  2 * align_up(((size_t)p.n_tiles + 2) * sizeof(uint32_t)) + align_up(((size_t)p.n_tiles / 64 + 4) * sizeof(uint32_t)) + 4096;
-    int rc = ii2_ws_reserve(ctx, need);
-    if (rc) return rc;
-    p.ranges = ws_take<uint32_t>(ctx, (size_t)p.n_tiles * dstride);
-    p.tmp = ws_take<uint32_t>(ctx, (size_t)p.n_tiles * p.slot_words);
-    p.tile_count = ws_take<uint32_t>(ctx, (size_t)p.n_tiles + 1);
-    p.n_sums1 = p.n_tiles / 64 + 1;
-    p.n_sums = p.n_sums1;
-    p.sums = ws_take<uint32_t>(ctx, p.n_sums);
-    p.max_grid = (uint32_t)ctx->cu_count * (ctx->opt_intersect_wgs > 0 ? (uint32_t)ctx->opt_intersect_wgs : 5u);
-    p.bitmap_mode = ctx->opt_intersect_bitmap ? 1u : 0u;
-    p.tomb = tomb ? tomb->d_words : nullptr;
-    p.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
-    p.out = d_out;
-    p.out_cap = cap;
-    p.d_count = d_count;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    HIP_TRY(ctx, launch_intersect(p, nullptr, st, e0, e1));
-    *taken = true;
-    return II2_OK;
-}
-
 extern "C" {
-
-int ii2_intersect_async(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
-                        const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *d_count) {
-    if (!ctx) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return intersect_unlocked(ctx, n, segs, list_idx, tomb, d_out, cap, d_count);
-}
-
-int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
-                  const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (!ctx || !count) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the count lands in the pinned host mailbox directly (the kernels write it once, at their end): one stream
-    // synchronisation, no copy behind it
-    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
-    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
-    int rc = intersect_unlocked(ctx, n, segs, list_idx, tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail);
-    if (rc) return rc;
-    const uint32_t own = ctx->lb_pending;           // epoch of this call's one-launch AND (0: it took another path)
-    ctx->lb_pending = 0;
-    if (own) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_OWN, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (!d_cnt) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_COUNT, ctx->d_mail, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    lb_fold_pending(ctx);
-    *count = ctx->h_mail[II2_MAIL_COUNT];
-    if (own && (*count == ~0ull || ctx->h_mail[II2_MAIL_LB_OWN] == own)) {
-        // a bounded wait of the one-launch two-list AND ran out (its workgroups did not start in index order; the count is all
-        // ones, or looks valid when the workgroup gave up after the last one had stored it): nothing is wrong with the inputs —
-        // the same query again through the two-kernel form, which has no inter-workgroup waits
-        ctx->lb_fallbacks++;
-        const int64_t keep = ctx->opt_intersect_and2;
-        ctx->opt_intersect_and2 = 2;
-        rc = intersect_unlocked(ctx, n, segs, list_idx, tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail);
-        ctx->opt_intersect_and2 = keep;
-        if (rc) return rc;
-        if (!d_cnt) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_COUNT, ctx->d_mail, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        *count = ctx->h_mail[II2_MAIL_COUNT];
-    }
-    if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_intersect: result does not fit the output buffer (content unspecified)");
-    return II2_OK;
-}
 
 int ii2_selftest(ii2_ctx *ctx) {
     if (!ctx) return II2_EINVAL;

@@ -154,14 +154,46 @@ struct ii2_tomb {
 void ii2_comm_destroy_internal(ii2_ctx *ctx);
 int ii2_seg_alloc_internal(ii2_ctx *ctx, uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_bytes, ii2_seg **out, bool with_meta = false);   // ctx->mu held
 int ii2_seg_rebase_internal(ii2_ctx *ctx, ii2_seg *seg, int world, const uint64_t *lo, const uint64_t *bo, const uint64_t *qo);            // ctx->mu held
+// host helpers of every entry point
+#define HIP_TRY(ctx, expr)                                                                 \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
+            return II2_EHIP;                                                               \
+        }                                                                                  \
+    } while (0)
+
+static inline int fail(ii2_ctx *ctx, int code, const char *msg) {
+    if (ctx) ctx->err = msg;
+    return code;
+}
+static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// Workspace: ii2_ws_reserve the total up front (api.cpp; ctx->mu held), then carve it with ws_take
+int ii2_ws_reserve(ii2_ctx *ctx, size_t bytes);
+template <class T> static inline T *ws_take(ii2_ctx *ctx, size_t count) {
+    T *p = (T *)(ctx->ws + ctx->ws_used);
+    ctx->ws_used += align_up(count * sizeof(T));
+    return p;
+}
+
+// temp device allocation freed at scope exit (cold paths only: encode / import / host calls)
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return ii2::dm_malloc_retry(&p, bytes ? bytes : 16); }
+    template <class T> T *as() const { return (T *)p; }
+};
+
 void *ii2_pool_get(ii2_ctx *ctx, int slot, size_t bytes);      // grow-only ctx buffer `slot`, at least `bytes` (nullptr: out of memory); ctx->mu held
-uint64_t *ii2_mapped_mail(ii2_ctx *ctx, uint32_t word);
+int ensure_debug(ii2_ctx *ctx, bool clear);                    // ctx->d_debug: option debug.stamps' cycle counters, made on first use (clear: zeroed first)
 int ii2_seg_host_cnt(ii2_ctx *ctx, const ii2_seg *seg);       // fills seg->h_cnt on first use (thread-safe)
 int ii2_seg_host_blk_off(ii2_ctx *ctx, const ii2_seg *seg);   // fills seg->h_blk_off on first use (thread-safe)
 bool ii2_profile_pair(ii2_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1);   // false when profiling is off
-// union through the intersection tiles (OR); *taken = false when the lists are too sparse for it (caller merges instead)
-int ii2_union_dense_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
-                             uint32_t *d_out, uint64_t cap, uint64_t *d_count, bool *taken);
+// a view over src's store whose four per-slot arrays were built on the device (align.hip); takes ownership of them
+int ii2_seg_adopt_view(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, uint32_t *d_blk_off, uint32_t *d_cnt, uint32_t *d_last_doc,
+                       uint32_t *d_blk_list, ii2_seg **out);
 int ii2_seg_encode_dev_unlocked(ii2_ctx *ctx, uint64_t n_lists, const uint64_t *d_post_off, const uint32_t *d_values,
                                 uint64_t n_postings, ii2_seg **out);
 int ii2_seg_decode_dev_unlocked(ii2_ctx *ctx, const ii2_seg *seg, uint64_t *d_post_off, uint32_t *d_values);
@@ -307,6 +339,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held
 void ii2_lookback_forget(ii2_ctx *ctx);      // api.cpp: the context's stream is about to be destroyed
 int ii2_lookback_launch(ii2_ctx *ctx, bool exclusive, const std::function<hipError_t()> &launch);      // api.cpp; ctx->mu held: kernels that wait between workgroups, ordered per device
+int lb_note_pending(ii2_ctx *ctx);      // api.cpp: the error word as the asynchronous launches so far left it, copied behind them ...
+void lb_fold_pending(ii2_ctx *ctx);     // ... and looked at once the stream has passed the copy (ii2_ctx_sync reports a give-up among them)
 namespace ii2 {
 
 constexpr size_t SELFTEST_SCRATCH = 64 * 4 * 1408;
@@ -355,7 +389,7 @@ hipError_t launch_max_u32(const uint32_t *v, uint64_t n, uint32_t *out, hipStrea
 // intersect
 constexpr uint32_t ISECT_GMAX = 16;         // driver blocks per tile (max)
 constexpr uint32_t ISECT_SMAX = 16384;      // doc span a tile's LDS byte map can cover
-hipError_t launch_intersect(const IntersectParams &p, uint64_t *d_tile_off, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_intersect(const IntersectParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // merge / union (merge.hip)
 constexpr uint32_t MERGE_THREADS = 256;     // threads per workgroup of the tile kernel
@@ -435,3 +469,7 @@ hipError_t launch_count_nonzero(const uint32_t *v, uint64_t n, uint64_t *out, hi
                                 uint64_t *mail = nullptr);      // mail: also mail[3] = *err (0 without), mail[4] = *n_tiles
 
 }  // namespace ii2
+
+// k SegViews over n_terms aligned term slots -> d_out_off (u64[n_terms+1], may be null), d_out_values (ops.cpp; ctx->mu held)
+int merge_core(ii2_ctx *ctx, uint32_t k, const ii2::SegView *views, uint64_t n_terms, uint64_t blocks_ub, uint64_t postings_ub,
+               const ii2_tomb *tomb, uint64_t *d_out_off, uint32_t *d_out_values, uint64_t out_cap, ii2_merge_stats *stats);

@@ -975,7 +975,7 @@ __global__ __launch_bounds__(256) void k_isect_expand(IntersectParams p) {
     }
 }
 
-hipError_t launch_intersect(const IntersectParams &p, uint64_t *d_tile_off, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+hipError_t launch_intersect(const IntersectParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (p.n_tiles == 0) return hipSuccess;
     const uint64_t nthr = (uint64_t)p.n_tiles * (p.op_union ? p.n_lists : p.n_lists > 1u ? p.n_lists - 1u : 1u);
     const uint64_t pthr = std::max<uint64_t>(std::max<uint64_t>(nthr * 64u, p.n_sums), p.n_tiles);

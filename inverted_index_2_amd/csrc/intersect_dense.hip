@@ -18,7 +18,7 @@
 //
 // Exact for any input the general kernel accepts (multi-byte gaps, short blocks, sparse stretches take slower
 // paths inside the same loop); the host only picks this kernel when the driver is dense enough for the result
-// bitmap to be small (api.cpp).
+// bitmap to be small (setop.cpp).
 #include <algorithm>
 
 #include "dv1_device.h"

@@ -351,21 +351,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_merge_small(SmallParams p) {
 
 using namespace ii2;
 
-#define HIP_TRY(ctx, expr)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return II2_EHIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-static int fail(ii2_ctx *ctx, int code, const char *msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Both entry points: the merge (out: a new segment; emptied terms dropped) and the read (raw: post_off / values on the host,
 // every union term).  list_first (may be NULL): the list of segment s that holds its dictionary's first term.
 static int small_core(ii2_ctx *ctx, uint32_t k, const ii2_seg *const *segs, const uint8_t *term_bytes, const uint64_t *term_off,
@@ -421,9 +406,9 @@ static int small_core(ii2_ctx *ctx, uint32_t k, const ii2_seg *const *segs, cons
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_small_in, hi, offsetof(SmallIn, removed) + n_removed * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (long_terms) HIP_TRY(ctx, hipMemcpyAsync((uint8_t *)ctx->d_small_in + offsetof(SmallIn, tbytes), hi->tbytes, term_off[n], hipMemcpyHostToDevice, st));
     // the new segment's arrays: one allocation sized for the limits
-    const size_t o_blk = 0, o_skip = o_blk + up256((SM_T + 1) * sizeof(uint32_t)), o_pay = o_skip + up256((SM_NB + 1) * sizeof(ii2_skip)),
-                 o_cnt = o_pay + up256((size_t)SM_P * 5 + 16), o_last = o_cnt + up256((SM_T + 1) * sizeof(uint32_t)), o_bl = o_last + up256((SM_T + 1) * sizeof(uint32_t)),
-                 slab_bytes = o_bl + up256((SM_NB + 1) * sizeof(uint32_t));
+    const size_t o_blk = 0, o_skip = o_blk + align_up((SM_T + 1) * sizeof(uint32_t)), o_pay = o_skip + align_up((SM_NB + 1) * sizeof(ii2_skip)),
+                 o_cnt = o_pay + align_up((size_t)SM_P * 5 + 16), o_last = o_cnt + align_up((SM_T + 1) * sizeof(uint32_t)), o_bl = o_last + align_up((SM_T + 1) * sizeof(uint32_t)),
+                 slab_bytes = o_bl + align_up((SM_NB + 1) * sizeof(uint32_t));
     uint8_t *slab = nullptr;
     if (!raw && dm_alloc((void **)&slab, slab_bytes) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_merge_small: segment allocation failed");
     SmallParams p;

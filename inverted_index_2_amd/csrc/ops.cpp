@@ -1,5 +1,5 @@
-// ops.cpp — segment merge and union entry points, and the host-buffer convenience calls
-// (include/ii2.h).  Planning (which terms share a tile) runs on the device; the host only
+// ops.cpp — segment merge entry points and the host-buffer merge (include/ii2.h); ii2_union's
+// merge passes come through merge_core.  Planning (which terms share a tile) runs on the device; the host only
 // reads back three scalars per call.
 #include <algorithm>
 #include <cstdio>
@@ -10,30 +10,6 @@
 #include "internal.h"
 
 using namespace ii2;
-
-#define HIP_TRY(ctx, expr)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return II2_EHIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-static int fail(ii2_ctx *ctx, int code, const char *msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return ii2::dm_malloc_retry(&p, bytes ? bytes : 16); }
-    template <class T> T *as() const { return (T *)p; }
-};
-
-int ii2_ws_reserve(ii2_ctx *ctx, size_t bytes);          // api.cpp
 
 template <class T> static T *carve(uint8_t *&cursor, size_t count) {
     T *p = (T *)cursor;
@@ -46,8 +22,8 @@ template <class T> static T *carve(uint8_t *&cursor, size_t count) {
 // array is sized from them, so the call enqueues all its kernels without a single host round trip and only reads three
 // scalars back at the end.  Nothing is decoded ahead of the tile kernel: the plan works on the segments' per-list counts,
 // first / last docs and skip tables.
-static int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n_terms, uint64_t blocks_ub, uint64_t postings_ub,
-                      const ii2_tomb *tomb, uint64_t *d_out_off, uint32_t *d_out_values, uint64_t out_cap, ii2_merge_stats *stats) {
+int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n_terms, uint64_t blocks_ub, uint64_t postings_ub,
+               const ii2_tomb *tomb, uint64_t *d_out_off, uint32_t *d_out_values, uint64_t out_cap, ii2_merge_stats *stats) {
     hipStream_t st = ctx->stream;
     const uint64_t T = n_terms;
     if (T >= (1ull << 30) - 2) return fail(ctx, II2_ERANGE, "merge: 2^30 or more term slots in one call");
@@ -166,8 +142,7 @@ static int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n
     p.d_total = ctx->d_mail;                    // [0] total, [2] surviving terms
     p.debug = nullptr;
     if (ctx->opt_debug_stamps) {
-        if (!ctx->d_debug && ii2::dm_malloc_retry((void **)&ctx->d_debug, (size_t)2048 * 8 * sizeof(unsigned long long)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "debug buffer allocation failed");
+        if (int rcd = ensure_debug(ctx, false)) return rcd;
         p.debug = ctx->d_debug;
     }
     // 2 workgroups of ~75 KB LDS per CU.  When the caller's buffer is known to hold any result (out_cap >= all input postings)
@@ -293,47 +268,6 @@ int ii2_merge_segments_to_seg(ii2_ctx *ctx, uint32_t k, const ii2_seg *const *se
     return ii2_seg_encode_stream_unlocked(ctx, T, off, vals, local.n_out, local.n_terms_out, bytes_in + 5 * blocks_in, out);
 }
 
-int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
-              uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (!ctx || !count) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0 || n > MAX_LISTS || !segs) return fail(ctx, II2_EINVAL, "ii2_union: list count must be 1..64");
-    std::vector<SegView> views(n);
-    bool any = false;
-    uint64_t blocks_ub = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t li = list_idx ? list_idx[i] : 0;
-        if (!segs[i] || segs[i]->device != ctx->device || li >= segs[i]->n_lists) return fail(ctx, II2_EINVAL, "ii2_union: bad list");
-        if (int rc0 = ii2_seg_host_blk_off(ctx, segs[i])) return rc0;
-        // a one-term view of the segment: blk_off shifted to the list
-        views[i] = SegView{segs[i]->d_blk_off + li, segs[i]->d_skip, segs[i]->d_payload, segs[i]->d_cnt + li, segs[i]->d_blk_list, segs[i]->d_last_doc + li, (uint32_t)li, 0u};
-        any |= segs[i]->h_blk_off[li + 1] > segs[i]->h_blk_off[li];
-        blocks_ub += segs[i]->h_blk_off[li + 1] - segs[i]->h_blk_off[li];
-    }
-    if (!any) { *count = 0; return II2_OK; }
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union: output buffer is NULL");
-    {   // lists dense together: OR over byte-map tiles instead of the merge passes
-        bool taken = false;
-        uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);      // the count goes straight into the pinned host mailbox
-        int rc = ii2_union_dense_unlocked(ctx, n, segs, list_idx, tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail, &taken);
-        if (rc) return rc;
-        if (taken) {
-            if (!d_cnt) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_COUNT, ctx->d_mail, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            *count = ctx->h_mail[II2_MAIL_COUNT];
-            if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_union: result does not fit the output buffer (content unspecified)");
-            return II2_OK;
-        }
-    }
-    ii2_merge_stats st;
-    std::memset(&st, 0, sizeof st);
-    int rc = merge_core(ctx, n, views.data(), 1, blocks_ub, blocks_ub * II2_DV1_BLOCK, tomb, nullptr, d_out, cap, &st);
-    if (rc) return rc;
-    *count = st.n_out;
-    return II2_OK;
-}
-
 // ---- host-buffer convenience -----------------------------------------------------------------
 int ii2_merge_host(ii2_ctx *ctx, uint32_t k, uint64_t n_terms, const uint64_t *seg_off, const uint64_t *seg_base,
                    const uint32_t *values, const uint32_t *removed, uint64_t n_removed, uint64_t *out_off,
@@ -372,51 +306,6 @@ int ii2_merge_host(ii2_ctx *ctx, uint32_t k, uint64_t n_terms, const uint64_t *s
     for (ii2_seg *s : segs) ii2_seg_free(s);
     ii2_tomb_free(tomb);
     return rc;
-}
-
-static int lists_host(ii2_ctx *ctx, bool is_union, uint32_t n, const uint64_t *list_off, const uint32_t *values,
-                      const uint32_t *removed, uint64_t n_removed, uint32_t *out, uint64_t cap, uint64_t *count) {
-    if (!ctx || !list_off || !count || n == 0 || n > MAX_LISTS) return fail(ctx, II2_EINVAL, "bad argument");
-    ii2_seg *seg = nullptr;
-    ii2_tomb *tomb = nullptr;
-    int rc = ii2_seg_encode(ctx, n, list_off, values, II2_HOST, &seg);
-    if (!rc && n_removed) rc = ii2_tomb_create(ctx, removed, n_removed, II2_HOST, &tomb);
-    if (!rc) {
-        uint64_t bound = 0;
-        if (is_union) bound = list_off[n] - list_off[0];
-        else {
-            bound = ~0ull;
-            for (uint32_t i = 0; i < n; i++) bound = std::min<uint64_t>(bound, list_off[i + 1] - list_off[i]);
-        }
-        DevBuf d_out;
-        if (d_out.alloc((bound + 1) * sizeof(uint32_t)) != hipSuccess) rc = fail(ctx, II2_ENOMEM, "result allocation failed");
-        std::vector<const ii2_seg *> segs(n, seg);
-        std::vector<uint64_t> idx(n);
-        for (uint32_t i = 0; i < n; i++) idx[i] = i;
-        uint64_t c = 0;
-        if (!rc)
-            rc = is_union ? ii2_union(ctx, n, segs.data(), idx.data(), tomb, d_out.as<uint32_t>(), bound + 1, &c)
-                          : ii2_intersect(ctx, n, segs.data(), idx.data(), tomb, d_out.as<uint32_t>(), bound + 1, &c);
-        if (!rc && c > cap) rc = fail(ctx, II2_ECAPACITY, "output buffer too small; nothing was written");
-        if (!rc && c) {
-            if (!out) rc = fail(ctx, II2_EINVAL, "output buffer is NULL");
-            else rc = ii2_copy_d2h(ctx, out, d_out.p, c * sizeof(uint32_t));
-        }
-        if (!rc) *count = c;
-    }
-    ii2_seg_free(seg);
-    ii2_tomb_free(tomb);
-    return rc;
-}
-
-int ii2_intersect_host(ii2_ctx *ctx, uint32_t n, const uint64_t *list_off, const uint32_t *values, const uint32_t *removed,
-                       uint64_t n_removed, uint32_t *out, uint64_t cap, uint64_t *count) {
-    return lists_host(ctx, false, n, list_off, values, removed, n_removed, out, cap, count);
-}
-
-int ii2_union_host(ii2_ctx *ctx, uint32_t n, const uint64_t *list_off, const uint32_t *values, const uint32_t *removed,
-                   uint64_t n_removed, uint32_t *out, uint64_t cap, uint64_t *count) {
-    return lists_host(ctx, true, n, list_off, values, removed, n_removed, out, cap, count);
 }
 
 }  // extern "C"
