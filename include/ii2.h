@@ -243,6 +243,16 @@ int ii2_intersect_async(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, co
  * (inverted_index.go:274-292).  cap >= sum of the list lengths is always enough. */
 int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
               const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count);
+/* Union of every list in n list ranges: lists [list_first[i], list_end[i]) of segs[i], for any number of lists
+ * (PrefixSearch: a prefix is one run of consecutive terms in each sorted dictionary).  Ascending, deduplicated ids,
+ * minus the tombstones when tomb != NULL.  cap >= the postings of all the lists is always enough; on II2_ECAPACITY
+ * nothing is written to d_out and *count holds the size needed.  Empty ranges and empty lists are allowed; n == 0 or
+ * no postings: *count = 0, d_out untouched (may be NULL).  Segments and views (ii2_seg_select*, merged segments) alike;
+ * a segment may appear in several ranges and ranges may overlap.  Up to II2_MAX_LISTS non-empty lists take the paths of
+ * ii2_union; more are unioned block by block through a per-context doc bitmap (at most 128 MiB + 64 KiB, kept until
+ * ii2_ctx_destroy; a doc range wider than 2^30 docs is done window by window). */
+int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
+                     const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count);
 
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
@@ -314,6 +324,9 @@ int ii2_selftest(ii2_ctx *ctx);
  *   union.stream, union.dense, union.sparsity   unions through the streaming kernel / through the OR tiles (the latter up
  *                                           to `sparsity` docs of the lists' common range per posting, default 2048)
  *   setop.small, union.rank                 short-list ANDs / ORs in one launch; ORs of a few medium lists by ranking
+ *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
+ *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
+ *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel

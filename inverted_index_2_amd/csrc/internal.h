@@ -82,6 +82,14 @@ struct ii2_ctx {
     unsigned long long *d_debug = nullptr;
     uint64_t *d_mail_mapped = nullptr;  // h_mail as the device sees it (result counts of the synchronous calls go there directly)
     uint32_t *d_small = nullptr;        // small set operations: ascending ids [8192] + the workgroup ticket (setop_small.hip)
+    int64_t opt_union_many = 0;         // 1: ii2_union_ranges takes the block-wise path (union_many.hip) even for <= 64 lists
+    int64_t opt_union_many_no_atomics = 0;     // timing experiments: its mark kernel decodes and combines but sets no bit
+    int64_t opt_union_many_window_log2 = 30;   // docs per window of that path: 1 << this (tests shrink it; 11 .. 30)
+    uint32_t *d_um_bits = nullptr;      // its doc bitmap + summary: all-zero between calls (grow-only, <= 128 MiB + 64 KiB)
+    size_t um_bits_words = 0;
+    bool um_dirty = false;              // a call stopped between mark and compact: scratch and staging are cleared / waited for first
+    void *h_um = nullptr;               // pinned staging of its range descriptors (grow-only)
+    size_t h_um_cap = 0;
     void *comm = nullptr;               // ncclComm_t
     int world = 1, rank = 0;
     uint64_t comm_syncs = 0;            // host waits inside the exchange entry points (what a chunked exchange pays per chunk)
@@ -334,6 +342,45 @@ struct DenseParams {
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})
 hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// OR of any number of lists, block by block (union_many.hip)
+struct UmRange {
+    const ii2_skip *skip;        // the range's segment
+    const uint8_t *payload;
+    const uint32_t *blk_list;
+    const uint32_t *last_doc;
+    uint32_t b0, b1;             // its blocks [b0, b1) ...
+    uint32_t l0, l1;             // ... owned by its lists [l0, l1)
+};
+struct UnionManyParams {
+    const UmRange *ranges;       // [n_ranges], none without blocks
+    const uint32_t *pre;         // [n_ranges + 1] exclusive prefix of the ranges' blocks
+    uint32_t n_ranges;
+    uint32_t n_blocks;           // pre[n_ranges]
+    uint32_t per_wave;           // query blocks per wave of the mark kernel
+    uint32_t check_window;       // 1: several windows - the mark kernel skips blocks whose docs miss this one
+    uint32_t win_lo;             // first doc of the window (a multiple of 32: word i <-> tombstone word win_lo / 32 + i)
+    uint32_t win_docs;           // docs of the window (<= 2^30)
+    uint32_t n_sum;              // summary words (each covers 64 x 32 bitmap words = 65536 docs)
+    uint32_t window;             // index of the window: run[window & 1] = ids before it
+    uint32_t *bitmap;            // [n_sum * 2048]
+    uint32_t *summary;           // [n_sum]: bit c of word s <=> some bit of bitmap words (32 s + c) * 64 .. + 63
+    uint32_t *cnt;               // [n_sum + 1] ids per summary word
+    uint64_t *off;               // [n_sum + 1] their exclusive prefix
+    uint64_t *run;               // [2]
+    uint32_t *bounds;            // [2] k_um_bounds: smallest first doc, largest last doc
+    const uint32_t *tomb;        // may be null
+    uint32_t tomb_nwords;
+    uint32_t write;              // 0: count and clear only
+    uint32_t no_atomics;         // timing experiments (option debug.union_many_no_atomics): the mark kernel sets no bit (results wrong)
+    uint32_t *out;
+    uint64_t out_cap;
+    uint64_t *d_count;
+};
+hipError_t launch_union_many_bounds(const UnionManyParams &p, hipStream_t s);
+hipError_t launch_union_many_mark(const UnionManyParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_union_many_count(const UnionManyParams &p, uint32_t grid, hipStream_t s);
+hipError_t launch_union_many_compact(const UnionManyParams &p, uint32_t grid, hipStream_t s);
 
 }  // namespace ii2
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held

@@ -4,6 +4,8 @@
 //        kernels (intersect_and2.hip), n-list dense (intersect_dense.hip) - then the tiles (intersect.hip).
 //   OR:  the small kernel, rank (union_rank.hip), stream (intersect_dense.hip), the byte-map tiles (intersect.hip), then
 //        the merge passes (ops.cpp: merge_core).
+//   OR of list ranges (ii2_union_ranges): up to 64 non-empty lists the OR chooser above, more lists block by block
+//        (union_many.hip).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -423,6 +425,9 @@ static int union_unlocked(ii2_ctx *ctx, const SetList *all, uint32_t n, const Se
     return II2_OK;
 }
 
+static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t blocks_ub, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                       uint64_t *count);
+
 extern "C" {
 
 int ii2_intersect_async(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
@@ -478,6 +483,14 @@ int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64
     for (uint32_t i = 0; i < n; i++) blocks_ub += L[i].v.nblk;
     if (!blocks_ub) { *count = 0; return II2_OK; }
     if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union: output buffer is NULL");
+    return union_lists(ctx, L, n, blocks_ub, tomb, d_out, cap, count);
+}
+
+}  // extern "C"
+
+// OR of n collected lists (blocks_ub > 0 blocks in all) through the chooser, else the merge passes; ctx->mu held
+static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t blocks_ub, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                       uint64_t *count) {
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);      // the count goes straight into the pinned host mailbox
     const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
     bool taken = false;
@@ -500,6 +513,197 @@ int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64
     *count = st.n_out;
     return II2_OK;
 }
+// ---- OR of list ranges ------------------------------------------------------------------------
+// one range of a call, checked: lists [l0, l1) of seg own its blocks [b0, b1)
+struct RangeIn {
+    const ii2_seg *seg;
+    uint64_t l0, l1;
+    uint32_t b0, b1;
+};
+
+// The block-wise OR (union_many.hip) of the ranges' blocks: per window of the doc range mark, count, scan, compact.
+static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                      uint64_t *count) {
+    hipStream_t st = ctx->stream;
+    const size_t nr = rs.size();
+    if (ctx->um_dirty) {        // the last call stopped half-way: its copy from the staging block may still be pending, its marks are still set
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctx->d_um_bits) HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, ctx->um_bits_words * sizeof(uint32_t), st));
+        ctx->um_dirty = false;
+    }
+    // range descriptors + block prefix: thousands of entries, through a grow-only pinned block
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), stage_bytes = desc_bytes + align_up((nr + 1) * sizeof(uint32_t));
+    if (ctx->h_um_cap < stage_bytes) {
+        if (ctx->h_um) (void)hipHostFree(ctx->h_um);
+        ctx->h_um = nullptr;
+        ctx->h_um_cap = 0;
+        const size_t want = align_up(stage_bytes + stage_bytes / 4, 1 << 16);
+        if (hipHostMalloc(&ctx->h_um, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_union_ranges: staging allocation failed");
+        ctx->h_um_cap = want;
+    }
+    UmRange *hr = (UmRange *)ctx->h_um;
+    uint32_t *hpre = (uint32_t *)((uint8_t *)ctx->h_um + desc_bytes);
+    uint32_t acc = 0;
+    for (size_t r = 0; r < nr; r++) {
+        const ii2_seg *s = rs[r].seg;
+        hr[r] = UmRange{s->d_skip, s->d_payload, s->d_blk_list, s->d_last_doc, rs[r].b0, rs[r].b1, (uint32_t)rs[r].l0, (uint32_t)rs[r].l1};
+        hpre[r] = acc;
+        acc += rs[r].b1 - rs[r].b0;
+    }
+    hpre[nr] = acc;
+    // the doc range: from the lists' mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    bool mirrored = true;
+    for (const RangeIn &q : rs) {
+        const ii2_seg *s = q.seg;
+        if (s->h_spans.size() != 3 * s->n_lists) { mirrored = false; break; }
+        for (uint64_t j = q.l0; j < q.l1; j++) {
+            if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
+            lo = std::min(lo, s->h_spans[3 * j]);
+            hi = std::max(hi, s->h_spans[3 * j + 2]);
+        }
+    }
+    const int64_t wl = std::min<int64_t>(std::max<int64_t>(ctx->opt_union_many_window_log2, 11), 30);
+    const uint64_t W = 1ull << wl;                               // docs per window
+    // workspace: descriptors, counts, offsets, scan temp, the running offset and the bounds (sized for the largest window possible
+    // before the bounds are known: min(W, 2^32) docs)
+    const uint64_t n_sum_max = (W + 65535) / 65536;
+    UnionManyParams p;
+    std::memset(&p, 0, sizeof p);
+    const size_t scan_tmp = scan_temp_bytes(n_sum_max + 1);
+    if (int rc = ii2_ws_reserve(ctx, stage_bytes + 2 * align_up((n_sum_max + 1) * sizeof(uint64_t)) + scan_tmp + 2 * 256 + 4096)) return rc;
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, stage_bytes);
+    p.ranges = (const UmRange *)d_stage;
+    p.pre = (const uint32_t *)(d_stage + desc_bytes);
+    p.cnt = ws_take<uint32_t>(ctx, n_sum_max + 1);
+    p.off = ws_take<uint64_t>(ctx, n_sum_max + 1);
+    void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
+    p.run = ws_take<uint64_t>(ctx, 2);
+    p.bounds = ws_take<uint32_t>(ctx, 2);
+    p.n_ranges = (uint32_t)nr;
+    p.n_blocks = (uint32_t)n_blocks;
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, ctx->h_um, stage_bytes, hipMemcpyHostToDevice, st));
+    if (!mirrored) {
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
+        HIP_TRY(ctx, launch_union_many_bounds(p, st));
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        lo = hb[0];
+        hi = hb[1];
+    }
+    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_union_ranges: inconsistent list bounds");
+    const uint32_t base = lo & ~31u;
+    const uint64_t span = (uint64_t)hi - base + 1;
+    const uint64_t n_win = (span + W - 1) / W;
+    // the scratch: bitmap + summary of the largest window, zero
+    const uint64_t n_sum_call = (std::min(span, W) + 65535) / 65536;
+    const size_t words = n_sum_call * 2048 + n_sum_call;
+    if (ctx->um_bits_words < words) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
+        ctx->d_um_bits = nullptr;
+        ctx->um_bits_words = 0;
+        if (ii2::dm_malloc_retry((void **)&ctx->d_um_bits, words * sizeof(uint32_t)) != hipSuccess)
+            return fail(ctx, II2_ENOMEM, "ii2_union_ranges: scratch allocation failed");
+        ctx->um_bits_words = words;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, words * sizeof(uint32_t), st));
+    }
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    p.d_count = d_cnt ? d_cnt : ctx->d_mail;
+    p.tomb = tomb ? tomb->d_words : nullptr;
+    p.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
+    p.out = d_out;
+    p.out_cap = cap;
+    p.check_window = n_win > 1 ? 1u : 0u;
+    p.no_atomics = ctx->opt_union_many_no_atomics ? 1u : 0u;
+    const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
+    p.per_wave = (uint32_t)std::max<uint64_t>(1, (n_blocks + target_waves - 1) / target_waves);
+    // several windows whose result may not fit: count first (nothing written), then write
+    const bool count_first = n_win > 1 && cap < n_blocks * II2_DV1_BLOCK;
+    for (int pass = count_first ? 0 : 1; pass < 2; pass++) {
+        p.write = (uint32_t)pass;
+        for (uint64_t w = 0; w < n_win; w++) {
+            const uint64_t wlo = base + w * W;
+            const uint64_t docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1);
+            p.window = (uint32_t)w;
+            p.win_lo = (uint32_t)wlo;
+            p.win_docs = (uint32_t)docs;
+            p.n_sum = (uint32_t)((docs + 65535) / 65536);
+            p.bitmap = ctx->d_um_bits;
+            p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 1 + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            ii2_profile_pair(ctx, &e0, &e1);
+            HIP_TRY(ctx, launch_union_many_mark(p, st, e0, e1));
+            HIP_TRY(ctx, launch_union_many_count(p, grid, st));
+            HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, p.cnt, p.off, p.n_sum + 1, st));
+            HIP_TRY(ctx, launch_union_many_compact(p, grid, st));
+        }
+        if (int rc = read_count(ctx, p.d_count, count)) return rc;
+        ctx->um_dirty = false;
+        if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_union_ranges: result does not fit the output buffer (nothing written)");
+    }
+    return II2_OK;
+}
+
+static int union_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad argument");
+    std::vector<RangeIn> rs;
+    uint64_t n_blocks = 0, n_nonempty = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const ii2_seg *seg = segs[i];
+        const uint64_t l0 = list_first[i], l1 = list_end[i];
+        if (!seg || l0 > l1 || l1 > seg->n_lists || seg->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad range");
+        if (l0 == l1) continue;
+        if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
+        // the lists [l0, l1) must own the consecutive blocks blk_off[l0] .. blk_off[l1] (views skip only empty lists between
+        // selected ones): checked, not assumed
+        const std::vector<uint32_t> &bo = seg->h_blk_off;
+        for (uint64_t j = l0; j < l1; j++) {
+            if (bo[j + 1] < bo[j]) return fail(ctx, II2_EINVAL, "ii2_union_ranges: the segment's list table does not ascend");
+            n_nonempty += bo[j + 1] > bo[j] ? 1u : 0u;
+        }
+        if (bo[l1] > seg->n_blocks) return fail(ctx, II2_EINVAL, "ii2_union_ranges: the segment's list table does not ascend");
+        if (bo[l1] == bo[l0]) continue;
+        rs.push_back(RangeIn{seg, l0, l1, bo[l0], bo[l1]});
+        n_blocks += bo[l1] - bo[l0];
+    }
+    if (!n_blocks) { *count = 0; return II2_OK; }
+    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_union_ranges: more than 2^32 - 2 blocks in one call");
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union_ranges: output buffer is NULL");
+    // up to 64 lists: the tuned OR paths - when the result surely fits (they may write part of a result that does not)
+    if (!ctx->opt_union_many && n_nonempty <= MAX_LISTS) {
+        SetList L[MAX_LISTS];
+        uint32_t m = 0;
+        uint64_t n_post = 0;
+        for (const RangeIn &q : rs) {
+            if (cap < n_blocks * II2_DV1_BLOCK)
+                if (int rc = ii2_seg_host_cnt(ctx, q.seg)) return rc;
+            for (uint64_t j = q.l0; j < q.l1; j++) {
+                const uint32_t b0 = q.seg->h_blk_off[j], b1 = q.seg->h_blk_off[j + 1];
+                if (b1 == b0) continue;
+                L[m++] = SetList{ListView{q.seg->d_skip + b0, q.seg->d_payload, q.seg->d_last_doc + j, b1 - b0, 0u}, q.seg, j};
+                n_post += cap < n_blocks * II2_DV1_BLOCK ? q.seg->h_cnt[j] : (uint64_t)(b1 - b0) * II2_DV1_BLOCK;
+            }
+        }
+        if (cap >= n_post) return union_lists(ctx, L, m, n_blocks, tomb, d_out, cap, count);
+    }
+    return union_many(ctx, rs, n_blocks, tomb, d_out, cap, count);
+}
+
+extern "C" int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return union_ranges_unlocked(ctx, n, segs, list_first, list_end, tomb, d_out, cap, count);
+}
+
+extern "C" {
 
 // ---- host-buffer convenience -----------------------------------------------------------------
 static int lists_host(ii2_ctx *ctx, bool is_union, uint32_t n, const uint64_t *list_off, const uint32_t *values,

@@ -290,6 +290,20 @@ class Context:
         self._ck(self.lib.ii2_union(self.h, len(lists), segs, idx, tomb.h if tomb else None, _ptr(out), out.count, C.byref(cnt)))
         return out, cnt.value
 
+    def union_ranges(self, ranges, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
+        """PrefixSearch's union over any number of lists (ii2_union_ranges): ranges = [(Segment, first, end), ...], every list
+        [first, end) of the segment.  Returns (DeviceArray ids, count); the default `out` holds 256 ids per block of the lists."""
+        ranges = [(s, int(a), int(b)) for s, a, b in ranges]
+        n = len(ranges)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s, _, _ in ranges])
+        first = (C.c_uint64 * max(n, 1))(*[a for _, a, _ in ranges])
+        end = (C.c_uint64 * max(n, 1))(*[b for _, _, b in ranges])
+        if out is None:
+            out = self.empty(max(sum(s.range_blocks(a, b, self) for s, a, b in ranges) * 256, 1))
+        cnt = C.c_uint64()
+        self._ck(self.lib.ii2_union_ranges(self.h, n, segs, first, end, tomb.h if tomb else None, _ptr(out), out.count, C.byref(cnt)))
+        return out, cnt.value
+
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):
         """Shard.Merge's loop body (shard.go:163-212).  Returns (out_off u64[T+1], out_values, MergeStats)."""
@@ -466,6 +480,13 @@ class Segment:
             c._ck(c.lib.ii2_seg_export(c.h, self.h, _ptr(blk), None, None))
             self._blk_off = blk
         return int(self._blk_off[i + 1] - self._blk_off[i])
+
+    def range_blocks(self, first: int, end: int, ctx: Optional["Context"] = None) -> int:
+        """Blocks of the lists [first, end) (0 for an empty or out-of-range span; the library checks the range)."""
+        if not 0 <= first < end <= self.info.n_lists:
+            return 0
+        self.list_blocks(first, ctx)
+        return max(int(self._blk_off[end]) - int(self._blk_off[first]), 0)
 
     def decode(self):
         """Decode step (Reader.Next -> intcomp.UncompressUint32, file/reader.go:79-100)."""

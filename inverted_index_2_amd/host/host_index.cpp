@@ -366,9 +366,10 @@ class Shard {
     }
 
     size_t SegmentCount() const { std::lock_guard<std::mutex> g(mu_); return segments_.size(); }
+    // the segments as they are now (a reader's hold on them, as Read takes it)
+    std::vector<std::shared_ptr<Segment>> snapshot() const { std::lock_guard<std::mutex> g(mu_); return segments_; }
 
    private:
-    std::vector<std::shared_ptr<Segment>> snapshot() const { std::lock_guard<std::mutex> g(mu_); return segments_; }
 
     // segments.go:56-64 — insert before the first segment with terms >= new.terms (mu_ held, or the constructor)
     void add(Segment s) {
@@ -703,9 +704,21 @@ class InvertedIndex {
         }
         return out;
     }
+    // The reference reads each selected shard from its smallest prefix on (the merged terms of all its segments), keeps the
+    // terms that start with a prefix, stops at the first term past the greatest prefix (its first len(greatest) bytes compare
+    // greater), then sorts and compacts the collected lists.  Here no list leaves the device: in every segment the lists of
+    // a prefix are one run of consecutive terms, [lower_bound(prefix), end of the prefix's run) cut at the end of the greatest
+    // prefix's run, and ONE ii2_union_ranges call per prefix unions the runs of every segment of every shard.
     std::map<Term, std::vector<uint32_t>> PrefixSearch(std::vector<Term> prefixes) const {   // inverted_index.go:192-295
         std::sort(prefixes.begin(), prefixes.end(), term_less);
-        std::map<Term, std::vector<std::vector<uint32_t>>> found;
+        prefixes.erase(std::unique(prefixes.begin(), prefixes.end()), prefixes.end());
+        struct Ranges {
+            std::vector<const ii2_seg *> segs;
+            std::vector<uint64_t> first, end;
+        };
+        std::map<Term, Ranges> found;
+        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the unions are done
+        std::vector<const ii2_seg *> distinct;
         for (auto &s : shard_list()) {
             Term mn, mx;
             if (!s.second->MinMax(&mn, &mx)) continue;
@@ -718,16 +731,45 @@ class InvertedIndex {
                 mine.push_back(p);
             }
             if (mine.empty()) continue;
-            const Term &greatest = mine.back();
-            for (auto &tv : s.second->Read(&mine.front(), nullptr)) {
-                const Term tp = tv.term.substr(0, std::min(tv.term.size(), greatest.size()));
-                if (term_less(greatest, tp)) break;
-                for (auto &p : mine)
-                    if (tv.term.compare(0, p.size(), p) == 0 && tv.term.size() >= p.size()) found[p].push_back(tv.values);
+            for (auto &sg : s.second->snapshot()) {
+                const std::vector<Term> &T = sg->terms;
+                const size_t stop = prefix_end(T, mine.back());
+                bool used = false;
+                for (auto &p : mine) {
+                    const size_t j0 = std::lower_bound(T.begin(), T.end(), p, term_less) - T.begin();
+                    const size_t j1 = std::min(prefix_end(T, p), stop);
+                    if (j0 >= j1) continue;
+                    Ranges &r = found[p];
+                    r.segs.push_back(sg->seg->h);
+                    r.first.push_back(j0);
+                    r.end.push_back(j1);
+                    used = true;
+                }
+                if (used) { held.push_back(sg); distinct.push_back(sg->seg->h); }
             }
         }
         std::map<Term, std::vector<uint32_t>> out;
-        for (auto &f : found) out[f.first] = lists_op(true, f.second);        // :288-292 sort + compact, on the GPU
+        if (found.empty()) return out;
+        // the union of lists of a set of segments holds at most the postings of those segments
+        uint64_t cap = 0;
+        std::sort(distinct.begin(), distinct.end());
+        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+        for (const ii2_seg *h : distinct) {
+            ii2_seg_info info;
+            ii2_seg_get_info(h, &info);
+            cap += info.n_postings;
+        }
+        DevMem d_out(ctx_);
+        ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
+        for (auto &f : found) {                                               // :288-292 sort + compact, on the GPU
+            const Ranges &r = f.second;
+            uint64_t n = 0;
+            ck(ctx_, ii2_union_ranges(ctx_, r.segs.size(), r.segs.data(), r.first.data(), r.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n),
+               "prefix search");
+            std::vector<uint32_t> ids(n);
+            if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "prefix search");
+            out[f.first] = std::move(ids);
+        }
         return out;
     }
     // additive: ids present under every term
@@ -745,6 +787,10 @@ class InvertedIndex {
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
 
    private:
+    // the first term at or after `p` in the sorted dictionary T that does not start with p (the terms that do are one run)
+    static size_t prefix_end(const std::vector<Term> &T, const Term &p) {
+        return std::partition_point(T.begin(), T.end(), [&](const Term &t) { return term_less(t, p) || t.compare(0, p.size(), p) == 0; }) - T.begin();
+    }
     // shards are never removed: a snapshot of (key, pointer) pairs in key order is all a reader needs (ii.shardsM)
     std::vector<std::pair<uint32_t, Shard *>> shard_list() const {
         std::lock_guard<std::mutex> g(mu_);
