@@ -253,6 +253,20 @@ int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64
  * ii2_ctx_destroy; a doc range wider than 2^30 docs is done window by window). */
 int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
                      const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count);
+/* AND of ORs over list ranges: the ascending, duplicate-free ids that lie in at least one list of EVERY group, minus the
+ * tombstones when tomb != NULL.  Group g is the ranges group_first[g] .. group_first[g + 1] - 1 of the range arrays, each range
+ * being lists [list_first[i], list_end[i]) of segs[i] exactly as ii2_union_ranges takes them (segments and views alike; a
+ * segment may appear in several ranges and groups; ranges may overlap).  A term of an unmerged shard is one group holding one
+ * one-list range per segment that has the term; a prefix is one run per segment.
+ * n_groups == 0, or any group without postings: *count = 0, d_out untouched (may be NULL).  n_groups == 1 is the union of
+ * that group.  cap >= the postings of the group with the fewest postings is always enough; on II2_ECAPACITY nothing is written
+ * and *count holds the size needed.  Up to II2_MAX_LISTS groups of one non-empty list each take the paths of ii2_intersect
+ * when the result surely fits; otherwise the union of the group with the fewest postings is filtered by every other group in
+ * ascending order of postings (a probe of its lists per run of candidates, or a mark of its blocks into the doc bitmap that
+ * ii2_union_ranges uses; see option intersect.ranges_mark).  Any number of groups. */
+int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                         const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                         uint32_t *d_out, uint64_t cap, uint64_t *count);
 
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
@@ -327,6 +341,11 @@ int ii2_selftest(ii2_ctx *ctx);
  *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)
+ *   intersect.ranges                        ii2_intersect_ranges: 1 = the group path even for single-list groups (default 0: they go to
+ *                                           ii2_intersect's paths when the result surely fits)
+ *   intersect.ranges_mark                   its filters mark a group into the doc bitmap when the group holds at most N postings per
+ *                                           (list x 256 candidates) or the candidates are fewer than 1024 per CU, else probe its lists
+ *                                           (default 64; 0: always probe)
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel

@@ -153,6 +153,8 @@ void ii2_ctx_destroy(ii2_ctx *ctx) {
     if (ctx->d_small) (void)hipFree(ctx->d_small);
     if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
     if (ctx->h_um) (void)hipHostFree(ctx->h_um);
+    if (ctx->d_ir) (void)hipFree(ctx->d_ir);
+    if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
     if (ctx->d_mail) (void)hipFree(ctx->d_mail);
     if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
     for (hipEvent_t e : ctx->region_ev) if (e) (void)hipEventDestroy(e);
@@ -996,6 +998,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "union.many") ctx->opt_union_many = value;
     else if (k == "union.many_window_log2") ctx->opt_union_many_window_log2 = value;
     else if (k == "debug.union_many_no_atomics") ctx->opt_union_many_no_atomics = value;
+    else if (k == "intersect.ranges") ctx->opt_intersect_ranges = value;
+    else if (k == "intersect.ranges_mark") ctx->opt_ir_mark = value;
     else if (k == "union.sparsity") ctx->opt_union_sparsity = value > 0 ? value : 2048;
     else if (k == "intersect.map_docs") ctx->opt_intersect_map_docs = value;
     else if (k == "intersect.dense") ctx->opt_intersect_dense = value;

@@ -90,6 +90,13 @@ struct ii2_ctx {
     bool um_dirty = false;              // a call stopped between mark and compact: scratch and staging are cleared / waited for first
     void *h_um = nullptr;               // pinned staging of its range descriptors (grow-only)
     size_t h_um_cap = 0;
+    int64_t opt_intersect_ranges = 0;   // 1: ii2_intersect_ranges takes the group path even where ii2_intersect's paths would do
+    int64_t opt_ir_mark = 64;           // ... whose filters mark a group with at most this many postings per (list x 256 candidates), or
+                                        //     fewer than 4 runs of 256 candidates per CU (0: always probe)
+    uint32_t *d_ir = nullptr;           // its two candidate arrays (ping-pong; grow-only: the driver's union reserves the workspace itself)
+    size_t ir_words = 0;
+    void *h_ir = nullptr;               // pinned staging of its filters' descriptors (grow-only)
+    size_t h_ir_cap = 0;
     void *comm = nullptr;               // ncclComm_t
     int world = 1, rank = 0;
     uint64_t comm_syncs = 0;            // host waits inside the exchange entry points (what a chunked exchange pays per chunk)
@@ -381,6 +388,35 @@ hipError_t launch_union_many_bounds(const UnionManyParams &p, hipStream_t s);
 hipError_t launch_union_many_mark(const UnionManyParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_union_many_count(const UnionManyParams &p, uint32_t grid, hipStream_t s);
 hipError_t launch_union_many_compact(const UnionManyParams &p, uint32_t grid, hipStream_t s);
+
+// AND of ORs over list ranges: the filters of the group path (intersect_ranges.hip)
+constexpr uint32_t IR_PROBE_RUN = 256;          // consecutive candidates per wave of the probe
+struct IrList {
+    const ii2_skip *skip;        // the list's first block entry (skip[nblk] is readable)
+    const uint8_t *payload;
+    const uint32_t *last_doc;    // the list's last doc id
+    uint32_t nblk;
+    uint32_t lo, hi;             // its first and last doc, mirrored on the host; lo > hi: not mirrored (the kernel reads them)
+    uint32_t pad;
+};
+struct IrParams {
+    const uint32_t *cand;        // [n_cand] the candidates, ascending
+    uint64_t n_cand;
+    uint32_t *flag;              // [n_cand + 1] 1 = found in the group (flag[n_cand] = 0), then in place their exclusive scan
+    const IrList *lists;         // probe: the group's non-empty lists
+    uint32_t n_lists;
+    uint32_t win_lo, win_docs;   // mark: the window (win_lo a multiple of 32) ...
+    uint32_t n_sum;              // ... its summary words ...
+    uint32_t *bitmap;            // ... and the doc bitmap + summary it was marked into (UnionManyParams)
+    uint32_t *summary;
+    uint32_t *out;               // compact: the survivors, when all of them fit out_cap
+    uint64_t out_cap;
+    uint64_t *d_count;
+};
+hipError_t launch_ir_probe(const IrParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_ir_test(const IrParams &p, hipStream_t s);
+hipError_t launch_ir_clear(const IrParams &p, uint32_t grid, hipStream_t s);
+hipError_t launch_ir_compact(const IrParams &p, hipStream_t s);
 
 }  // namespace ii2
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held

@@ -6,6 +6,10 @@
 //        the merge passes (ops.cpp: merge_core).
 //   OR of list ranges (ii2_union_ranges): up to 64 non-empty lists the OR chooser above, more lists block by block
 //        (union_many.hip).
+//   AND of ORs over list ranges (ii2_intersect_ranges): no group, a group without blocks or groups whose doc spans do not
+//        overlap (count 0, no launch); one group: the OR of list ranges; up to 64 groups of one non-empty list each whose
+//        result surely fits: the AND chooser above (ii2_intersect); otherwise the group path - the OR of the group with the
+//        fewest postings as candidates, then per further group a probe or mark filter (intersect_ranges.hip).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -427,6 +431,8 @@ static int union_unlocked(ii2_ctx *ctx, const SetList *all, uint32_t n, const Se
 
 static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t blocks_ub, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                        uint64_t *count);
+static int intersect_sync(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out,
+                          uint64_t cap, uint64_t *count);
 
 extern "C" {
 
@@ -443,6 +449,14 @@ int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const ui
     if (!ctx || !count) return II2_EINVAL;
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return intersect_sync(ctx, n, segs, list_idx, tomb, d_out, cap, count);
+}
+
+}  // extern "C"
+
+// ii2_intersect with ctx->mu held (ii2_intersect_ranges hands single-list groups to it)
+static int intersect_sync(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out,
+                          uint64_t cap, uint64_t *count) {
     // the count lands in the pinned host mailbox directly (the kernels write it once, at their end): one stream
     // synchronisation, no copy behind it
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
@@ -470,6 +484,8 @@ int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const ui
     if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_intersect: result does not fit the output buffer (content unspecified)");
     return II2_OK;
 }
+
+extern "C" {
 
 int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
               uint32_t *d_out, uint64_t cap, uint64_t *count) {
@@ -521,16 +537,69 @@ struct RangeIn {
     uint32_t b0, b1;
 };
 
+// docs per window of the block-wise paths (option union.many_window_log2)
+static uint64_t um_window(const ii2_ctx *ctx) {
+    return 1ull << std::min<int64_t>(std::max<int64_t>(ctx->opt_union_many_window_log2, 11), 30);
+}
+
+// the per-context doc bitmap is all-zero between calls: a call that stopped half-way (its copy from the staging block may still be
+// pending, its marks are still set) is cleaned up by the next one
+static int um_scratch_clean(ii2_ctx *ctx) {
+    if (!ctx->um_dirty) return II2_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_um_bits) HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, ctx->um_bits_words * sizeof(uint32_t), ctx->stream));
+    ctx->um_dirty = false;
+    return II2_OK;
+}
+
+// ... and holds the bitmap + summary of the largest window of a doc span (grow-only, zeroed when it grows)
+static int um_scratch_reserve(ii2_ctx *ctx, const char *who, uint64_t span, uint64_t W) {
+    const uint64_t n_sum_call = (std::min(span, W) + 65535) / 65536;
+    const size_t words = n_sum_call * 2048 + n_sum_call;
+    if (ctx->um_bits_words >= words) return II2_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
+    ctx->d_um_bits = nullptr;
+    ctx->um_bits_words = 0;
+    if (ii2::dm_malloc_retry((void **)&ctx->d_um_bits, words * sizeof(uint32_t)) != hipSuccess)
+        return fail(ctx, II2_ENOMEM, (std::string(who) + ": scratch allocation failed").c_str());
+    ctx->um_bits_words = words;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, words * sizeof(uint32_t), ctx->stream));
+    return II2_OK;
+}
+
+// The ranges [0, n) of segs / list_first / list_end, checked (`who` names the entry point in the messages); those that own
+// blocks are appended to rs.  *n_blocks, *n_nonempty grow by their blocks and non-empty lists.
+static int collect_ranges(ii2_ctx *ctx, const char *who, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
+                          const uint64_t *list_end, std::vector<RangeIn> &rs, uint64_t *n_blocks, uint64_t *n_nonempty) {
+    const std::string w(who);
+    for (uint64_t i = 0; i < n; i++) {
+        const ii2_seg *seg = segs[i];
+        const uint64_t l0 = list_first[i], l1 = list_end[i];
+        if (!seg || l0 > l1 || l1 > seg->n_lists || seg->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": bad range").c_str());
+        if (l0 == l1) continue;
+        if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
+        // the lists [l0, l1) must own the consecutive blocks blk_off[l0] .. blk_off[l1] (views skip only empty lists between
+        // selected ones): checked, not assumed
+        const std::vector<uint32_t> &bo = seg->h_blk_off;
+        for (uint64_t j = l0; j < l1; j++) {
+            if (bo[j + 1] < bo[j]) return fail(ctx, II2_EINVAL, (w + ": the segment's list table does not ascend").c_str());
+            *n_nonempty += bo[j + 1] > bo[j] ? 1u : 0u;
+        }
+        if (bo[l1] > seg->n_blocks) return fail(ctx, II2_EINVAL, (w + ": the segment's list table does not ascend").c_str());
+        if (bo[l1] == bo[l0]) continue;
+        rs.push_back(RangeIn{seg, l0, l1, bo[l0], bo[l1]});
+        *n_blocks += bo[l1] - bo[l0];
+    }
+    return II2_OK;
+}
+
 // The block-wise OR (union_many.hip) of the ranges' blocks: per window of the doc range mark, count, scan, compact.
 static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                       uint64_t *count) {
     hipStream_t st = ctx->stream;
     const size_t nr = rs.size();
-    if (ctx->um_dirty) {        // the last call stopped half-way: its copy from the staging block may still be pending, its marks are still set
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (ctx->d_um_bits) HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, ctx->um_bits_words * sizeof(uint32_t), st));
-        ctx->um_dirty = false;
-    }
+    if (int rc = um_scratch_clean(ctx)) return rc;
     // range descriptors + block prefix: thousands of entries, through a grow-only pinned block
     const size_t desc_bytes = align_up(nr * sizeof(UmRange)), stage_bytes = desc_bytes + align_up((nr + 1) * sizeof(uint32_t));
     if (ctx->h_um_cap < stage_bytes) {
@@ -563,8 +632,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
             hi = std::max(hi, s->h_spans[3 * j + 2]);
         }
     }
-    const int64_t wl = std::min<int64_t>(std::max<int64_t>(ctx->opt_union_many_window_log2, 11), 30);
-    const uint64_t W = 1ull << wl;                               // docs per window
+    const uint64_t W = um_window(ctx);                          // docs per window
     // workspace: descriptors, counts, offsets, scan temp, the running offset and the bounds (sized for the largest window possible
     // before the bounds are known: min(W, 2^32) docs)
     const uint64_t n_sum_max = (W + 65535) / 65536;
@@ -599,18 +667,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     const uint64_t span = (uint64_t)hi - base + 1;
     const uint64_t n_win = (span + W - 1) / W;
     // the scratch: bitmap + summary of the largest window, zero
-    const uint64_t n_sum_call = (std::min(span, W) + 65535) / 65536;
-    const size_t words = n_sum_call * 2048 + n_sum_call;
-    if (ctx->um_bits_words < words) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
-        ctx->d_um_bits = nullptr;
-        ctx->um_bits_words = 0;
-        if (ii2::dm_malloc_retry((void **)&ctx->d_um_bits, words * sizeof(uint32_t)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "ii2_union_ranges: scratch allocation failed");
-        ctx->um_bits_words = words;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, words * sizeof(uint32_t), st));
-    }
+    if (int rc = um_scratch_reserve(ctx, "ii2_union_ranges", span, W)) return rc;
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
     p.d_count = d_cnt ? d_cnt : ctx->d_mail;
     p.tomb = tomb ? tomb->d_words : nullptr;
@@ -649,32 +706,24 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     return II2_OK;
 }
 
+static int union_collected(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, uint64_t n_nonempty, const ii2_tomb *tomb,
+                           uint32_t *d_out, uint64_t cap, uint64_t *count);
+
 static int union_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
                                  const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
     if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad argument");
     std::vector<RangeIn> rs;
     uint64_t n_blocks = 0, n_nonempty = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const ii2_seg *seg = segs[i];
-        const uint64_t l0 = list_first[i], l1 = list_end[i];
-        if (!seg || l0 > l1 || l1 > seg->n_lists || seg->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad range");
-        if (l0 == l1) continue;
-        if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
-        // the lists [l0, l1) must own the consecutive blocks blk_off[l0] .. blk_off[l1] (views skip only empty lists between
-        // selected ones): checked, not assumed
-        const std::vector<uint32_t> &bo = seg->h_blk_off;
-        for (uint64_t j = l0; j < l1; j++) {
-            if (bo[j + 1] < bo[j]) return fail(ctx, II2_EINVAL, "ii2_union_ranges: the segment's list table does not ascend");
-            n_nonempty += bo[j + 1] > bo[j] ? 1u : 0u;
-        }
-        if (bo[l1] > seg->n_blocks) return fail(ctx, II2_EINVAL, "ii2_union_ranges: the segment's list table does not ascend");
-        if (bo[l1] == bo[l0]) continue;
-        rs.push_back(RangeIn{seg, l0, l1, bo[l0], bo[l1]});
-        n_blocks += bo[l1] - bo[l0];
-    }
+    if (int rc = collect_ranges(ctx, "ii2_union_ranges", n, segs, list_first, list_end, rs, &n_blocks, &n_nonempty)) return rc;
     if (!n_blocks) { *count = 0; return II2_OK; }
     if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_union_ranges: more than 2^32 - 2 blocks in one call");
     if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union_ranges: output buffer is NULL");
+    return union_collected(ctx, rs, n_blocks, n_nonempty, tomb, d_out, cap, count);
+}
+
+// OR of collected ranges (n_blocks > 0 blocks, n_nonempty non-empty lists) into d_out, all or nothing
+static int union_collected(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, uint64_t n_nonempty, const ii2_tomb *tomb,
+                           uint32_t *d_out, uint64_t cap, uint64_t *count) {
     // up to 64 lists: the tuned OR paths - when the result surely fits (they may write part of a result that does not)
     if (!ctx->opt_union_many && n_nonempty <= MAX_LISTS) {
         SetList L[MAX_LISTS];
@@ -701,6 +750,303 @@ extern "C" int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return union_ranges_unlocked(ctx, n, segs, list_first, list_end, tomb, d_out, cap, count);
+}
+
+// ---- AND of ORs over list ranges ----------------------------------------------------------------
+// one group of a call: its checked ranges rs[r0, r1), their blocks, non-empty lists and postings, and its doc span
+struct GroupIn {
+    size_t r0, r1;
+    uint64_t n_blocks, n_nonempty, n_post;
+    uint32_t lo, hi;
+    bool span_known;
+};
+
+// the pinned staging block of the group path's descriptors: `bytes` of it, once the stream has passed the last copy from it
+static int ir_stage(ii2_ctx *ctx, size_t bytes, uint8_t **h) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (a no-op after the count read that ends every step)
+    if (ctx->h_ir_cap < bytes) {
+        if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
+        ctx->h_ir = nullptr;
+        ctx->h_ir_cap = 0;
+        const size_t want = align_up(bytes + bytes / 4, 1 << 16);
+        if (hipHostMalloc(&ctx->h_ir, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_intersect_ranges: staging allocation failed");
+        ctx->h_ir_cap = want;
+    }
+    *h = (uint8_t *)ctx->h_ir;
+    return II2_OK;
+}
+
+// the block-wise descriptors of rs[r0, r1) (union_many.hip): UmRange[r1 - r0], then the exclusive block prefix [r1 - r0 + 1]
+static size_t um_desc_bytes(size_t nr) { return align_up(nr * sizeof(UmRange)) + align_up((nr + 1) * sizeof(uint32_t)); }
+static void um_desc_fill(const std::vector<RangeIn> &rs, size_t r0, size_t r1, uint8_t *h) {
+    const size_t nr = r1 - r0;
+    UmRange *hr = (UmRange *)h;
+    uint32_t *hpre = (uint32_t *)(h + align_up(nr * sizeof(UmRange)));
+    uint32_t acc = 0;
+    for (size_t r = 0; r < nr; r++) {
+        const RangeIn &q = rs[r0 + r];
+        const ii2_seg *s = q.seg;
+        hr[r] = UmRange{s->d_skip, s->d_payload, s->d_blk_list, s->d_last_doc, q.b0, q.b1, (uint32_t)q.l0, (uint32_t)q.l1};
+        hpre[r] = acc;
+        acc += q.b1 - q.b0;
+    }
+    hpre[nr] = acc;
+}
+
+// The group path: the driver's union (the group with the fewest postings, minus the tombstones) is the candidate array, then
+// one filter pass per further group in ascending order of postings - probe or mark (intersect_ranges.hip), scan, compact -
+// until no candidate is left.  The last pass writes d_out only when the whole result fits.  One count read per group.
+static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::vector<GroupIn> &gs, const ii2_tomb *tomb, uint32_t *d_out,
+                            uint64_t cap, uint64_t *count) {
+    hipStream_t st = ctx->stream;
+    // the spans not mirrored on the host: one bounds reduction per such group (k_um_bounds), one wait for all of them
+    std::vector<size_t> need;
+    for (size_t g = 0; g < gs.size(); g++) if (!gs[g].span_known) need.push_back(g);
+    if (!need.empty()) {
+        size_t bytes = 0;
+        for (size_t g : need) bytes += um_desc_bytes(gs[g].r1 - gs[g].r0);
+        const size_t bounds_bytes = align_up(2 * need.size() * sizeof(uint32_t));
+        uint8_t *h = nullptr;
+        if (int rc = ir_stage(ctx, bytes + bounds_bytes, &h)) return rc;
+        if (int rc = ii2_ws_reserve(ctx, bytes + bounds_bytes + 4096)) return rc;
+        uint8_t *d = ws_take<uint8_t>(ctx, bytes + bounds_bytes);       // the descriptors, then {smallest first doc, largest last doc} per group
+        uint32_t *hb = (uint32_t *)(h + bytes), *d_bounds = (uint32_t *)(d + bytes);
+        size_t at = 0;
+        for (size_t i = 0; i < need.size(); i++) {
+            um_desc_fill(rs, gs[need[i]].r0, gs[need[i]].r1, h + at);
+            at += um_desc_bytes(gs[need[i]].r1 - gs[need[i]].r0);
+            hb[2 * i] = 0xFFFFFFFFu;
+            hb[2 * i + 1] = 0u;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d, h, bytes + bounds_bytes, hipMemcpyHostToDevice, st));
+        at = 0;
+        for (size_t i = 0; i < need.size(); i++) {
+            const GroupIn &G = gs[need[i]];
+            const size_t nr = G.r1 - G.r0;
+            UnionManyParams p;
+            std::memset(&p, 0, sizeof p);
+            p.ranges = (const UmRange *)(d + at);
+            p.pre = (const uint32_t *)(d + at + align_up(nr * sizeof(UmRange)));
+            p.n_ranges = (uint32_t)nr;
+            p.n_blocks = (uint32_t)G.n_blocks;
+            p.bounds = d_bounds + 2 * i;
+            HIP_TRY(ctx, launch_union_many_bounds(p, st));
+            at += um_desc_bytes(nr);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(hb, d_bounds, 2 * need.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (size_t i = 0; i < need.size(); i++) {
+            gs[need[i]].lo = hb[2 * i];
+            gs[need[i]].hi = hb[2 * i + 1];
+        }
+    }
+    uint32_t clo = 0, chi = 0xFFFFFFFFu;
+    for (const GroupIn &G : gs) {
+        if (G.lo > G.hi) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: inconsistent list bounds");
+        clo = std::max(clo, G.lo);
+        chi = std::min(chi, G.hi);
+    }
+    if (clo > chi) { *count = 0; return II2_OK; }
+    // the driver's union: the candidates
+    size_t drv = 0;
+    for (size_t g = 1; g < gs.size(); g++) if (gs[g].n_post < gs[drv].n_post) drv = g;
+    const uint64_t half = (gs[drv].n_post + 64) & ~63ull;
+    if (ctx->ir_words < 2 * half) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctx->d_ir) (void)hipFree(ctx->d_ir);
+        ctx->d_ir = nullptr;
+        ctx->ir_words = 0;
+        const size_t want = 2 * half + half / 2;
+        if (ii2::dm_malloc_retry((void **)&ctx->d_ir, want * sizeof(uint32_t)) != hipSuccess)
+            return fail(ctx, II2_ENOMEM, "ii2_intersect_ranges: candidate allocation failed");
+        ctx->ir_words = want;
+    }
+    uint32_t *buf[2] = {ctx->d_ir, ctx->d_ir + half};
+    uint64_t nc = 0;
+    {
+        const GroupIn &D = gs[drv];
+        const std::vector<RangeIn> sub(rs.begin() + D.r0, rs.begin() + D.r1);
+        if (int rc = union_collected(ctx, sub, D.n_blocks, D.n_nonempty, tomb, buf[0], D.n_post, &nc)) return rc;
+    }
+    std::vector<size_t> order;
+    for (size_t g = 0; g < gs.size(); g++) if (g != drv) order.push_back(g);
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return gs[a].n_post < gs[b].n_post; });
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    uint32_t src = 0;
+    for (size_t k = 0; k < order.size() && nc; k++) {
+        const GroupIn &G = gs[order[k]];
+        const bool last = k + 1 == order.size();
+        const size_t nr = G.r1 - G.r0;
+        // probe: one search per list and run of 256 candidates, the runs' block walks one after the other (latency-bound: it needs
+        // enough runs to fill the GPU); mark: every posting of the group once.  Measured: the probe wins on long
+        // lists against millions of candidates, the mark on many lists and on few candidates (option intersect.ranges_mark).
+        const uint64_t runs = (nc + IR_PROBE_RUN - 1) / IR_PROBE_RUN;
+        const bool mark = ctx->opt_ir_mark > 0 &&
+                          (runs < 4u * (uint64_t)ctx->cu_count || (double)G.n_post <= (double)ctx->opt_ir_mark * (double)G.n_nonempty * (double)runs);
+        const size_t desc_bytes = mark ? um_desc_bytes(nr) : align_up(G.n_nonempty * sizeof(IrList));
+        uint8_t *h = nullptr;
+        if (int rc = ir_stage(ctx, desc_bytes, &h)) return rc;
+        if (mark) um_desc_fill(rs, G.r0, G.r1, h);
+        else {
+            IrList *hl = (IrList *)h;
+            size_t m = 0;
+            for (size_t r = G.r0; r < G.r1; r++) {
+                const ii2_seg *s = rs[r].seg;
+                const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+                for (uint64_t j = rs[r].l0; j < rs[r].l1; j++) {
+                    const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1];
+                    if (b1 == b0) continue;
+                    hl[m++] = IrList{s->d_skip + b0, s->d_payload, s->d_last_doc + j, b1 - b0, mirrored ? s->h_spans[3 * j] : 1u,
+                                     mirrored ? s->h_spans[3 * j + 2] : 0u, 0u};
+                }
+            }
+        }
+        const size_t scan_tmp = scan_temp_bytes(nc + 1);
+        if (int rc = ii2_ws_reserve(ctx, desc_bytes + align_up((nc + 1) * sizeof(uint32_t)) + scan_tmp + 4096)) return rc;
+        uint8_t *d_desc = ws_take<uint8_t>(ctx, desc_bytes);
+        IrParams ip;
+        std::memset(&ip, 0, sizeof ip);
+        ip.cand = buf[src];
+        ip.n_cand = nc;
+        ip.flag = ws_take<uint32_t>(ctx, nc + 1);
+        void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
+        HIP_TRY(ctx, hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        if (mark) {
+            HIP_TRY(ctx, hipMemsetAsync(ip.flag, 0, (nc + 1) * sizeof(uint32_t), st));
+            if (int rc = um_scratch_clean(ctx)) return rc;
+            const uint64_t W = um_window(ctx);
+            const uint32_t base = clo & ~31u;
+            const uint64_t span = (uint64_t)chi - base + 1;
+            if (int rc = um_scratch_reserve(ctx, "ii2_intersect_ranges", span, W)) return rc;
+            UnionManyParams p;
+            std::memset(&p, 0, sizeof p);
+            p.ranges = (const UmRange *)d_desc;
+            p.pre = (const uint32_t *)(d_desc + align_up(nr * sizeof(UmRange)));
+            p.n_ranges = (uint32_t)nr;
+            p.n_blocks = (uint32_t)G.n_blocks;
+            p.check_window = 1u;                        // blocks outside the candidates' span are not decoded
+            const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
+            p.per_wave = (uint32_t)std::max<uint64_t>(1, (G.n_blocks + target_waves - 1) / target_waves);
+            ctx->um_dirty = true;
+            for (uint64_t wlo = base; wlo <= chi; wlo += W) {
+                const uint64_t docs = std::min<uint64_t>(W, (uint64_t)chi - wlo + 1);
+                p.win_lo = (uint32_t)wlo;
+                p.win_docs = (uint32_t)docs;
+                p.n_sum = (uint32_t)((docs + 65535) / 65536);
+                p.bitmap = ctx->d_um_bits;
+                p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+                ip.win_lo = p.win_lo;
+                ip.win_docs = p.win_docs;
+                ip.n_sum = p.n_sum;
+                ip.bitmap = p.bitmap;
+                ip.summary = p.summary;
+                const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+                HIP_TRY(ctx, launch_union_many_mark(p, st, e0, e1));
+                HIP_TRY(ctx, launch_ir_test(ip, st));
+                HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
+                e0 = e1 = nullptr;
+            }
+        } else {
+            ip.lists = (const IrList *)d_desc;
+            ip.n_lists = (uint32_t)G.n_nonempty;
+            HIP_TRY(ctx, hipMemsetAsync(ip.flag + nc, 0, sizeof(uint32_t), st));
+            HIP_TRY(ctx, launch_ir_probe(ip, st, e0, e1));
+        }
+        HIP_TRY(ctx, scan_excl_u32(d_scan, scan_tmp, ip.flag, ip.flag, nc + 1, st));
+        ip.out = last ? d_out : buf[src ^ 1u];
+        ip.out_cap = last ? cap : nc;
+        ip.d_count = d_cnt ? d_cnt : ctx->d_mail;
+        HIP_TRY(ctx, launch_ir_compact(ip, st));
+        if (int rc = read_count(ctx, ip.d_count, &nc)) return rc;
+        ctx->um_dirty = false;
+        if (last && nc > cap) {
+            *count = nc;
+            return fail(ctx, II2_ECAPACITY, "ii2_intersect_ranges: result does not fit the output buffer (nothing written)");
+        }
+        src ^= 1u;
+    }
+    *count = nc;            // (0 when a pass before the last one left no candidate: nothing written)
+    return II2_OK;
+}
+
+static int intersect_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                                     const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                                     uint64_t *count) {
+    if (n_groups == 0) { *count = 0; return II2_OK; }
+    if (!group_first) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: bad argument");
+    for (uint64_t g = 0; g < n_groups; g++)
+        if (group_first[g + 1] < group_first[g]) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: group_first does not ascend");
+    if (group_first[n_groups] > group_first[0] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: bad argument");
+    std::vector<RangeIn> rs;
+    std::vector<GroupIn> gs(n_groups);
+    uint64_t n_blocks = 0;
+    for (uint64_t g = 0; g < n_groups; g++) {
+        const uint64_t a = group_first[g], b = group_first[g + 1];
+        GroupIn &G = gs[g];
+        std::memset(&G, 0, sizeof G);
+        G.r0 = rs.size();
+        if (int rc = collect_ranges(ctx, "ii2_intersect_ranges", b - a, segs + a, list_first + a, list_end + a, rs, &G.n_blocks, &G.n_nonempty)) return rc;
+        G.r1 = rs.size();
+        n_blocks += G.n_blocks;
+    }
+    for (const GroupIn &G : gs) if (!G.n_blocks) { *count = 0; return II2_OK; }
+    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_intersect_ranges: more than 2^32 - 2 blocks in one call");
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: output buffer is NULL");
+    // postings (the driver, the order of the filters, the hand-off's capacity) and the doc spans mirrored on the host
+    for (GroupIn &G : gs) {
+        G.lo = 0xFFFFFFFFu;
+        G.hi = 0;
+        G.span_known = true;
+        for (size_t r = G.r0; r < G.r1; r++) {
+            const ii2_seg *s = rs[r].seg;
+            if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
+            const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+            G.span_known = G.span_known && mirrored;
+            for (uint64_t j = rs[r].l0; j < rs[r].l1; j++) {
+                if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
+                G.n_post += s->h_cnt[j];
+                if (!mirrored) continue;
+                G.lo = std::min(G.lo, s->h_spans[3 * j]);
+                G.hi = std::max(G.hi, s->h_spans[3 * j + 2]);
+            }
+        }
+    }
+    uint32_t clo = 0, chi = 0xFFFFFFFFu;
+    for (const GroupIn &G : gs) {
+        if (!G.span_known) continue;
+        clo = std::max(clo, G.lo);
+        chi = std::min(chi, G.hi);
+    }
+    if (clo > chi) { *count = 0; return II2_OK; }
+    if (n_groups == 1) return union_collected(ctx, rs, n_blocks, gs[0].n_nonempty, tomb, d_out, cap, count);
+    // one non-empty list per group, up to 64 groups, a result that surely fits: the tuned AND (ii2_intersect, look-back repeat included)
+    if (!ctx->opt_intersect_ranges && n_groups <= MAX_LISTS) {
+        const ii2_seg *hs[MAX_LISTS];
+        uint64_t hl[MAX_LISTS];
+        uint64_t shortest = ~0ull;
+        bool single = true;
+        for (uint64_t g = 0; g < n_groups && single; g++) {
+            const GroupIn &G = gs[g];
+            single = G.n_nonempty == 1;
+            for (size_t r = G.r0; r < G.r1 && single; r++)
+                for (uint64_t j = rs[r].l0; j < rs[r].l1; j++)
+                    if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) { hs[g] = rs[r].seg; hl[g] = j; }
+            shortest = std::min(shortest, G.n_post);
+        }
+        if (single && cap >= shortest) return intersect_sync(ctx, (uint32_t)n_groups, hs, hl, tomb, d_out, cap, count);
+    }
+    return intersect_groups(ctx, rs, gs, tomb, d_out, cap, count);
+}
+
+extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                                    const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                                    uint64_t *count) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
 }
 
 extern "C" {

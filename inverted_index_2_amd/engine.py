@@ -304,6 +304,27 @@ class Context:
         self._ck(self.lib.ii2_union_ranges(self.h, n, segs, first, end, tomb.h if tomb else None, _ptr(out), out.count, C.byref(cnt)))
         return out, cnt.value
 
+    def intersect_ranges(self, groups, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
+        """AND of ORs over list ranges (ii2_intersect_ranges): groups = [[(Segment, first, end), ...], ...]; the ids found in at
+        least one list of every group.  Returns (DeviceArray ids, count); the default `out` holds 256 ids per block of the group
+        with the fewest blocks."""
+        groups = [[(s, int(a), int(b)) for s, a, b in g] for g in groups]
+        ranges = [r for g in groups for r in g]
+        n = len(ranges)
+        gf = np.zeros(len(groups) + 1, np.uint64)
+        gf[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64) if groups else []
+        group_first = (C.c_uint64 * len(gf))(*[int(x) for x in gf])
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s, _, _ in ranges])
+        first = (C.c_uint64 * max(n, 1))(*[a for _, a, _ in ranges])
+        end = (C.c_uint64 * max(n, 1))(*[b for _, _, b in ranges])
+        if out is None:
+            blocks = [sum(s.range_blocks(a, b, self) for s, a, b in g) for g in groups]
+            out = self.empty(max(min(blocks, default=0) * 256, 1))
+        cnt = C.c_uint64()
+        self._ck(self.lib.ii2_intersect_ranges(self.h, len(groups), group_first, segs, first, end, tomb.h if tomb else None, _ptr(out),
+                                               out.count, C.byref(cnt)))
+        return out, cnt.value
+
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):
         """Shard.Merge's loop body (shard.go:163-212).  Returns (out_off u64[T+1], out_values, MergeStats)."""

@@ -772,16 +772,59 @@ class InvertedIndex {
         }
         return out;
     }
-    // additive: ids present under every term
+    // additive: ids present under every term.  A term's postings are spread over the segments of its shard (every Put writes
+    // one): one group per term, one one-list range per segment that holds it, and ONE ii2_intersect_ranges call - no list is
+    // merged, downloaded or uploaded again.  Like Read, no tombstone filter.
     std::vector<uint32_t> Intersect(const std::vector<Term> &terms) const {
-        std::vector<std::vector<uint32_t>> lists;
+        if (terms.empty()) return {};
+        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
+        std::vector<uint64_t> group_first{0};
+        std::vector<const ii2_seg *> segs;
+        std::vector<uint64_t> first, end;
+        // The output's size: the C ABI gives no per-list counts, so each term is bounded by its segments - a list of a segment
+        // holds at most its postings minus one per other list (every list a shard's segment holds is non-empty: a Put writes one
+        // posting per term, a merge drops empty terms), exact for Put segments, loose for merged ones.  The smallest term's bound
+        // is enough, but it may be a whole merged segment: past FIRST_CAP ids the first call tries FIRST_CAP, and a result that
+        // does not fit is written by a second call with the size the first one reported (II2_ECAPACITY writes nothing).
+        constexpr uint64_t FIRST_CAP = 1u << 22;
+        uint64_t bound = ~0ull;
         for (auto &t : terms) {
-            std::vector<uint32_t> v;
-            if (Shard *sh = find_shard(shard_key(t)))
-                for (auto &tv : sh->Read(&t, &t)) v = tv.values;
-            lists.push_back(std::move(v));
+            uint64_t post = 0;
+            if (Shard *sh = find_shard(shard_key(t))) {
+                for (auto &sg : sh->snapshot()) {
+                    const std::vector<Term> &T = sg->terms;
+                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
+                    if (j == T.size() || T[j] != t) continue;
+                    ii2_seg_info info;
+                    ii2_seg_get_info(sg->seg->h, &info);
+                    held.push_back(sg);
+                    segs.push_back(sg->seg->h);
+                    first.push_back(j);
+                    end.push_back(j + 1);
+                    post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
+                }
+            }
+            if (segs.size() == group_first.back()) return {};    // a term in no segment: nothing is under every term
+            group_first.push_back(segs.size());
+            bound = std::min(bound, post);
         }
-        return lists_op(false, lists);
+        uint64_t cap = std::min(bound, FIRST_CAP), n = 0;
+        DevMem d_out(ctx_);
+        for (int attempt = 0;; attempt++) {
+            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect");
+            const int rc = ii2_intersect_ranges(ctx_, terms.size(), group_first.data(), segs.data(), first.data(), end.data(), nullptr,
+                                                (uint32_t *)d_out.p, cap + 1, &n);
+            if (rc != II2_ECAPACITY || attempt) {
+                ck(ctx_, rc, "intersect");
+                break;
+            }
+            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect");
+            d_out.p = nullptr;
+            cap = n;
+        }
+        std::vector<uint32_t> ids(n);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect");
+        return ids;
     }
     size_t ShardCount() const { std::lock_guard<std::mutex> g(mu_); return shards_.size(); }
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
@@ -818,22 +861,6 @@ class InvertedIndex {
             it = shards_.emplace(key, std::make_unique<Shard>(ctx_, dir)).first;
         }
         return *it->second;
-    }
-    std::vector<uint32_t> lists_op(bool is_union, const std::vector<std::vector<uint32_t>> &lists) const {
-        std::vector<uint64_t> off(lists.size() + 1, 0);
-        std::vector<uint32_t> flat;
-        for (size_t i = 0; i < lists.size(); i++) {
-            flat.insert(flat.end(), lists[i].begin(), lists[i].end());
-            off[i + 1] = flat.size();
-        }
-        std::vector<uint32_t> out(flat.size() + 1);
-        uint64_t n = 0;
-        if (lists.empty()) return {};
-        int rc = is_union ? ii2_union_host(ctx_, (uint32_t)lists.size(), off.data(), flat.data(), nullptr, 0, out.data(), out.size(), &n)
-                          : ii2_intersect_host(ctx_, (uint32_t)lists.size(), off.data(), flat.data(), nullptr, 0, out.data(), out.size(), &n);
-        ck(ctx_, rc, is_union ? "prefix search" : "intersect");
-        out.resize(n);
-        return out;
     }
     ii2_ctx *ctx_;
     std::string basedir_;
