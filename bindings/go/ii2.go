@@ -340,6 +340,45 @@ func (c *Ctx) MergeSegmentsToSeg(segs []*Segment, removed []uint32) (*Segment, e
 	return &Segment{out}, nil
 }
 
+// Query ops of QueryBatch (II2_OP_AND / II2_OP_OR).
+const (
+	OpAnd uint8 = 0
+	OpOr  uint8 = 1
+)
+
+// ErrCapacity: the packed results of a QueryBatch did not fit `out`; the returned offsets hold the sizes needed.
+var ErrCapacity = fmt.Errorf("gpu: results do not fit the output buffer")
+
+// QueryBatch answers MANY AND / OR queries over resident segments in one call (ii2_query_batch): a number of launches
+// and one wait that do not depend on len(op).  Query q owns the ranges queryFirst[q] .. queryFirst[q+1]-1; a range is lists
+// [listFirst[i], listEnd[i]) of segs[i].  OpOr: the union of every list in the query's ranges (one query per prefix replaces
+// PrefixSearch's per-prefix append + slices.Sort + slices.Compact, inverted_index.go:274-292); OpAnd: every list in the
+// ranges is one operand.  The results are packed back to back into the device buffer out (capacity capIDs ids) in query
+// order; the returned offsets (len(op)+1) delimit them.  All-or-nothing: on ErrCapacity nothing was written and
+// offsets[len(op)] is the capacity to call again with.
+func (c *Ctx) QueryBatch(op []uint8, queryFirst []uint64, segs []*Segment, listFirst, listEnd []uint64, out unsafe.Pointer, capIDs uint64) ([]uint64, error) {
+	if len(queryFirst) != len(op)+1 || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return nil, fmt.Errorf("query batch: array lengths disagree")
+	}
+	offsets := make([]uint64, len(op)+1)
+	if len(op) == 0 {
+		return offsets, nil
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	rc := C.ii2_query_batch(c.h, C.uint64_t(len(op)), (*C.uint8_t)(unsafe.Pointer(&op[0])), u64ptr(queryFirst),
+		(**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(out), C.uint64_t(capIDs), u64ptr(offsets))
+	if rc == C.II2_ECAPACITY {
+		return offsets, ErrCapacity
+	}
+	if rc != 0 {
+		return nil, c.err("query batch", rc)
+	}
+	return offsets, nil
+}
+
 // Union replaces PrefixSearch's append + slices.Sort + slices.Compact (inverted_index.go:274-292).
 func (c *Ctx) Union(listOff []uint64, values, removed []uint32) ([]uint32, error) {
 	return c.lists(true, listOff, values, removed)

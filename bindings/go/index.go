@@ -10,6 +10,10 @@ package gpu
 //	func (ii *InvertedIndex) PrefixSearch(prefixes [][]byte) (found map[string][]uint32, err error)
 //	func (s *Shard) Merge(reqCount, mCount int) (mergedSegmentsLen int, err error)
 //	func (s *Shard) Read(min, max []byte) (go_iterators.Iterator[file.TermValues], error)
+//
+// PrefixSearch: every prefix is one run of consecutive terms in each segment's sorted dictionary; collect the runs of ALL
+// prefixes and make ONE Ctx.QueryBatch call (an OpOr query per prefix) and one download instead of a union per prefix - what
+// the C++ host mirror's InvertedIndex::PrefixSearch does (host/host_index.cpp).
 
 import (
 	"errors"

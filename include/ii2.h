@@ -18,7 +18,9 @@
  *     unspecified (the merge entry points write nothing in that case).
  *   - per-call limits (II2_ERANGE beyond them): a merge takes < 2^32 input postings, < 2^31 input
  *     blocks and < 2^30 term slots; ii2_align_terms takes < 2^31 terms; one segment holds < 2^31
- *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls).
+ *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls);
+ *     ii2_query_batch takes <= 2^20 queries whose result bounds (AND: the shortest operand, OR: the postings of
+ *     its ranges) add up to < 2^32 ids.
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
  *     internal mutex, so a ctx may be shared by goroutines / threads (InvertedIndex.Merge
  *     fans Shard.Merge over `concurrency` goroutines, inverted_index.go:83-103); use one
@@ -268,6 +270,35 @@ int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_
                          const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
                          uint32_t *d_out, uint64_t cap, uint64_t *count);
 
+/* MANY AND / OR queries in one call: what a search front end sends in bulk.  Replaces the per-prefix loop of PrefixSearch
+ * (PrefixSearch(prefixes [][]byte), inverted_index.go:192: inverted_index.go:274-292 once per prefix) and a loop over the
+ * build-defined Intersect (ii2_intersect) - a launch, and for the synchronous calls a stream wait, per query - by a number of
+ * launches and ONE wait that do not depend on the number of queries.
+ * Query q owns the ranges query_first[q] .. query_first[q + 1] - 1 of the range arrays (query_first[0] = 0), a range being lists
+ * [list_first[i], list_end[i]) of segs[i] exactly as ii2_union_ranges takes them (segments and views alike; a segment or list
+ * may appear in any number of ranges and queries; ranges may overlap).  All five arrays live in host memory.
+ *   op[q] == II2_OP_OR    the union of every list in the query's ranges: the result of ii2_union_ranges on them (no range or
+ *                         no postings: an empty result);
+ *   op[q] == II2_OP_AND   every list in the query's ranges is one operand: the result of ii2_intersect on them (1 ..
+ *                         II2_MAX_LISTS lists; an empty operand gives an empty result).
+ * tomb (may be NULL) applies to every query.  The results are packed back to back in d_out (device) in query order and
+ * out_off[n_queries + 1] (host) receives their offsets, out_off[0] = 0; each result is bit-identical to what the single-query
+ * entry point returns for that query.  cap >= the sum over the queries of their bounds (AND: the shortest operand, OR: the
+ * postings of the ranges) is always enough.
+ * All-or-nothing.  Every query is checked before anything is launched: an AND without a list or with more than II2_MAX_LISTS
+ * lists, a bad range, a segment of another device or an unknown op is II2_EINVAL, the message names the query's index, nothing
+ * is launched and nothing written.  When the packed results exceed cap the call returns II2_ECAPACITY, d_out is untouched and
+ * out_off is completely filled (allocate out_off[n_queries] ids and call again; d_out may be NULL when cap is 0).
+ * n_queries == 0: out_off[0] = 0, d_out may be NULL.
+ * Queries that fit one workgroup (at most 8192 postings in at most 128 blocks and II2_MAX_LISTS non-empty lists) are answered
+ * together, one workgroup each, in one launch per size class; the others go one after the other through the paths of
+ * ii2_intersect / ii2_union_ranges (and may cost a wait each) and are packed with the rest.  The staged results live in a
+ * per-context buffer that grows to the largest batch seen and is kept until ii2_ctx_destroy. */
+enum { II2_OP_AND = 0, II2_OP_OR = 1 };
+int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const uint64_t *query_first,
+                    const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                    const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *out_off);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -338,6 +369,10 @@ int ii2_selftest(ii2_ctx *ctx);
  *   union.stream, union.dense, union.sparsity   unions through the streaming kernel / through the OR tiles (the latter up
  *                                           to `sparsity` docs of the lists' common range per posting, default 2048)
  *   setop.small, union.rank                 short-list ANDs / ORs in one launch; ORs of a few medium lists by ranking
+ *   batch.small                             ii2_query_batch: 1 (default) the small queries of a batch share the batch kernel, 0 every
+ *                                           query of a batch goes through the single-query paths one after the other
+ *   batch.tiny                              ... and those of at most 2048 postings in at most 32 blocks run as 256-thread workgroups
+ *                                           (1, default: up to seven per CU) or, like the rest, as 1024-thread ones (0)
  *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)

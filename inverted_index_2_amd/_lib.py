@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libii2_hip.so")
 
 II2_HOST, II2_DEVICE = 0, 1
 II2_UNIQUE_ID_BYTES = 128
+II2_OP_AND, II2_OP_OR = 0, 1
 ERRORS = {0: "OK", -1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ERANGE", -6: "ECOMM", -7: "ENODEVICE"}
 
 
@@ -72,6 +73,7 @@ PROTOTYPES = {
     "ii2_union": (C.c_int, [vp, C.c_uint32, vpp, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_union_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_intersect_ranges": (C.c_int, [vp, C.c_uint64, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
+    "ii2_query_batch": (C.c_int, [vp, C.c_uint64, u8p, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

@@ -155,6 +155,8 @@ void ii2_ctx_destroy(ii2_ctx *ctx) {
     if (ctx->h_um) (void)hipHostFree(ctx->h_um);
     if (ctx->d_ir) (void)hipFree(ctx->d_ir);
     if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
+    if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+    if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
     if (ctx->d_mail) (void)hipFree(ctx->d_mail);
     if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
     for (hipEvent_t e : ctx->region_ev) if (e) (void)hipEventDestroy(e);
@@ -995,6 +997,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "union.stream") ctx->opt_union_stream = value;
     else if (k == "setop.small") ctx->opt_small_setop = value;
     else if (k == "union.rank") ctx->opt_union_rank = value;
+    else if (k == "batch.small") ctx->opt_batch_small = value;
+    else if (k == "batch.tiny") ctx->opt_batch_tiny = value;
     else if (k == "union.many") ctx->opt_union_many = value;
     else if (k == "union.many_window_log2") ctx->opt_union_many_window_log2 = value;
     else if (k == "debug.union_many_no_atomics") ctx->opt_union_many_no_atomics = value;

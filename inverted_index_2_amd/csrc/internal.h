@@ -97,6 +97,12 @@ struct ii2_ctx {
     size_t ir_words = 0;
     void *h_ir = nullptr;               // pinned staging of its filters' descriptors (grow-only)
     size_t h_ir_cap = 0;
+    int64_t opt_batch_small = 1;        // ii2_query_batch: small queries share the batch kernel (0: every query through the single-query paths)
+    int64_t opt_batch_tiny = 1;         // ... those of <= 2048 postings in <= 32 blocks in its 256-thread form (0: all in the 1024-thread form)
+    uint8_t *d_batch = nullptr;         // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
+    size_t batch_cap = 0;
+    void *h_batch = nullptr;            // pinned: the descriptor table on its way up, the offsets on their way down (grow-only)
+    size_t h_batch_cap = 0;
     void *comm = nullptr;               // ncclComm_t
     int world = 1, rank = 0;
     uint64_t comm_syncs = 0;            // host waits inside the exchange entry points (what a chunked exchange pays per chunk)
@@ -286,6 +292,45 @@ struct SmallSetParams {
     uint32_t *ticket;            // zero between launches (the last workgroup resets it)
 };
 hipError_t launch_setop_small(const SmallSetParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// many small AND / OR queries in one launch (setop_batch.hip): the queries and their lists come from a device table
+constexpr uint32_t BATCH_TINY_POSTINGS = 2048; // the 256-thread form: postings the lists of a query may hold together ...
+constexpr uint32_t BATCH_TINY_BLOCKS = 32;     // ... in at most this many blocks (larger ones: SMALL_SET_POSTINGS / SMALL_SET_BLOCKS, 1024 threads)
+constexpr uint64_t BATCH_MAX_QUERIES = 1u << 20;
+struct BatchList {
+    const ii2_skip *skip;        // the list's first block entry (skip[nblk] is readable)
+    const uint8_t *payload;
+    uint32_t nblk;               // > 0
+    uint32_t cnt;                // its postings: 256 (nblk - 1) < cnt <= 256 nblk
+};
+struct BatchQuery {
+    uint64_t stage_off;          // its slot of the staging buffer starts here ...
+    uint32_t bound;              // ... and holds this many ids (AND: the shortest list, OR: all postings)
+    uint32_t first_list;         // its lists: lists[first_list .. first_list + n_lists), all non-empty
+    uint32_t n_lists;            // 1 .. MAX_LISTS
+    uint32_t is_union;
+    uint32_t slot;               // its word of the counts array (= its index in the caller's batch)
+    uint32_t pad;
+};
+struct BatchParams {
+    const BatchQuery *queries;   // [n_tiny + n_small], the tiny ones first
+    const BatchList *lists;
+    const uint32_t *tomb;        // may be null
+    uint32_t tomb_nwords;
+    uint32_t n_tiny, n_small;
+    uint32_t *stage;
+    uint32_t *cnt;               // [queries of the batch + 1]
+};
+struct BatchPackParams {
+    const uint32_t *stage;
+    const uint64_t *stage_off;   // [n_queries] every query's staging slot
+    const uint64_t *off;         // [n_queries + 1] exclusive prefix of the counts
+    uint32_t *out;
+    uint64_t cap;
+    uint32_t n_queries;
+};
+hipError_t launch_setop_batch(const BatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_batch_pack(const BatchPackParams &p, uint64_t max_bound, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // OR of a few medium-size lists by ranking (union_rank.hip)
 constexpr uint32_t UNION_RANK_MAXL = 8;

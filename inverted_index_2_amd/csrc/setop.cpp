@@ -10,8 +10,11 @@
 //        overlap (count 0, no launch); one group: the OR of list ranges; up to 64 groups of one non-empty list each whose
 //        result surely fits: the AND chooser above (ii2_intersect); otherwise the group path - the OR of the group with the
 //        fewest postings as candidates, then per further group a probe or mark filter (intersect_ranges.hip).
+//   Many AND / OR queries in one call (ii2_query_batch): the small ones in one launch per size class (setop_batch.hip), the
+//        others one by one through the choosers above; all of them staged, then packed in query order.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "internal.h"
@@ -1047,6 +1050,219 @@ extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint6
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
+}
+
+// ---- many queries in one call ---------------------------------------------------------------------
+// one query of a batch as the host plans it
+namespace {
+struct BatchPlan {
+    uint64_t bound;              // ids its staging slot holds: AND the shortest operand, OR every posting of its ranges
+    uint64_t stage_off;
+    size_t l0;                   // its lists in the call's flat list array: AND every operand, OR the non-empty ones (at most 65 kept)
+    uint32_t nl;
+    uint32_t n_blocks;
+    uint8_t kind;                // BP_*
+    uint8_t is_union;
+};
+enum { BP_EMPTY = 0, BP_TINY = 1, BP_SMALL = 2, BP_LARGE = 3 };
+}  // namespace
+
+// grow-only blocks of the batch path: the device block (never the bump workspace: the large queries of a batch reserve from that)
+// and the pinned one
+static int batch_reserve(ii2_ctx *ctx, size_t dev_bytes, size_t host_bytes) {
+    if (ctx->batch_cap < dev_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_batch) (void)hipFree(ctx->d_batch);
+        ctx->d_batch = nullptr;
+        ctx->batch_cap = 0;
+        const size_t want = align_up(dev_bytes + dev_bytes / 4, 1 << 20);
+        if (ii2::dm_malloc_retry((void **)&ctx->d_batch, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_query_batch: staging allocation failed");
+        ctx->batch_cap = want;
+    }
+    if (ctx->h_batch_cap < host_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+        ctx->h_batch = nullptr;
+        ctx->h_batch_cap = 0;
+        const size_t want = align_up(host_bytes + host_bytes / 4, 1 << 16);
+        if (hipHostMalloc(&ctx->h_batch, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_query_batch: pinned staging allocation failed");
+        ctx->h_batch_cap = want;
+    }
+    return II2_OK;
+}
+
+static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
+                                const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                                uint64_t *out_off) {
+    if (nq == 0) { out_off[0] = 0; return II2_OK; }
+    if (!op || !query_first) return fail(ctx, II2_EINVAL, "ii2_query_batch: bad argument");
+    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, "ii2_query_batch: more than 2^20 queries in one call");
+    if (!d_out && cap) return fail(ctx, II2_EINVAL, "ii2_query_batch: output buffer is NULL");
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_query_batch: the tombstones live on another device");
+    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, ("ii2_query_batch: query " + std::to_string(q) + ": " + what).c_str()); };
+    if (query_first[nq] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_query_batch: bad argument");
+    // 1. every query checked and sized before anything is launched
+    std::vector<BatchPlan> plan(nq);
+    std::vector<SetList> lists;
+    lists.reserve(2 * nq);
+    uint64_t stage_ids = 0, max_bound = 0;
+    uint32_t n_kind[4] = {0, 0, 0, 0};
+    size_t n_table_lists = 0;
+    const ii2_seg *mirrored = nullptr;     // the segment whose host mirrors were looked at last
+    for (uint64_t q = 0; q < nq; q++) {
+        if (op[q] != II2_OP_AND && op[q] != II2_OP_OR) return bad(q, "unknown op");
+        const uint64_t r0 = query_first[q], r1 = query_first[q + 1];
+        if (r0 > r1 || (q == 0 && r0 != 0)) return bad(q, "query_first does not ascend from 0");
+        const bool is_union = op[q] == II2_OP_OR;
+        BatchPlan &pl = plan[q];
+        pl = BatchPlan{0, 0, lists.size(), 0, 0, BP_EMPTY, (uint8_t)is_union};
+        uint64_t n_ops = 0, blocks = 0, post = 0, shortest = ~0ull;
+        bool regular = true;       // every kept list's count agrees with its blocks (what the batch kernel's staging relies on)
+        for (uint64_t r = r0; r < r1; r++) {
+            const ii2_seg *seg = segs[r];
+            const uint64_t a = list_first[r], b = list_end[r];
+            if (!seg || a > b || b > seg->n_lists) return bad(q, "bad range");
+            if (seg->device != ctx->device) return bad(q, "segment lives on another device");
+            if (a == b) continue;
+            if (seg != mirrored) {             // (both take the segment's lock: once per run of ranges of one segment)
+                if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
+                if (int rc = ii2_seg_host_cnt(ctx, seg)) return rc;
+                mirrored = seg;
+            }
+            const std::vector<uint32_t> &bo = seg->h_blk_off;
+            if (bo[b] > seg->n_blocks) return bad(q, "the segment's list table does not ascend");
+            if (!is_union && n_ops + (b - a) > MAX_LISTS) return bad(q, "an AND takes 1..64 lists");
+            for (uint64_t j = a; j < b; j++) {
+                if (bo[j + 1] < bo[j]) return bad(q, "the segment's list table does not ascend");
+                const uint32_t nb = bo[j + 1] - bo[j], c = seg->h_cnt[j];
+                n_ops++;
+                blocks += nb;
+                post += c;
+                shortest = std::min<uint64_t>(shortest, c);
+                if (is_union && nb == 0) continue;
+                if (nb == 0 || c > (uint64_t)nb * II2_DV1_BLOCK || c + II2_DV1_BLOCK <= (uint64_t)nb * II2_DV1_BLOCK) regular = false;
+                if (pl.nl <= MAX_LISTS) {              // (an OR of more lists is a large query: it goes by its ranges)
+                    lists.push_back(SetList{ListView{seg->d_skip + bo[j], seg->d_payload, seg->d_last_doc + j, nb, 0u}, seg, j});
+                    pl.nl++;
+                }
+            }
+        }
+        if (!is_union && n_ops == 0) return bad(q, "an AND takes 1..64 lists");
+        if (blocks >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_query_batch: more than 2^32 - 2 blocks in one query");
+        pl.n_blocks = (uint32_t)blocks;
+        pl.bound = is_union ? post : shortest;
+        if (pl.bound == 0 || blocks == 0) { pl.bound = 0; pl.kind = BP_EMPTY; }       // an empty operand / no posting: an empty result, no launch
+        else if (!ctx->opt_batch_small || !regular || pl.nl > MAX_LISTS || blocks > SMALL_SET_BLOCKS || post > SMALL_SET_POSTINGS) pl.kind = BP_LARGE;
+        else pl.kind = ctx->opt_batch_tiny && blocks <= BATCH_TINY_BLOCKS && post <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
+        n_kind[pl.kind]++;
+        if (pl.kind == BP_TINY || pl.kind == BP_SMALL) n_table_lists += pl.nl;
+        pl.stage_off = stage_ids;
+        stage_ids += pl.bound;
+        max_bound = std::max(max_bound, pl.bound);
+        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, "ii2_query_batch: the result bounds of the queries add up to 2^32 ids or more");
+    }
+    // 2. the blocks: [queries | lists | staging offsets | counts] travel up in one copy; offsets, scan temp and staged ids stay below
+    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
+    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_soff = o_lists + align_up(n_table_lists * sizeof(BatchList));
+    const size_t o_cnt = o_soff + align_up(nq * sizeof(uint64_t)), up_bytes = o_cnt + align_up((nq + 1) * sizeof(uint32_t));
+    const size_t off_bytes = align_up((nq + 1) * sizeof(uint64_t)), scan_tmp = scan_temp_bytes(nq + 1);
+    const size_t o_off = up_bytes, o_scan = o_off + off_bytes, o_stage = o_scan + scan_tmp;
+    if (int rc = batch_reserve(ctx, o_stage + align_up((stage_ids + 4) * sizeof(uint32_t)), up_bytes + off_bytes)) return rc;
+    uint8_t *h = (uint8_t *)ctx->h_batch, *d = ctx->d_batch;
+    uint32_t *d_stage = (uint32_t *)(d + o_stage);
+    BatchQuery *hq = (BatchQuery *)h;
+    BatchList *hl = (BatchList *)(h + o_lists);
+    uint64_t *h_soff = (uint64_t *)(h + o_soff);
+    uint32_t *h_cnt = (uint32_t *)(h + o_cnt);
+    uint64_t *h_off = (uint64_t *)(h + up_bytes);
+    // 3. the large queries, one after the other through the single-query paths, into their staging slots (each with its own wait);
+    // two-list ANDs in the two-kernel form: nothing of a batch waits between workgroups
+    std::vector<const ii2_seg *> one_segs;
+    std::vector<uint64_t> one_idx;
+    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY], at_list = 0;
+    for (uint64_t q = 0; q < nq; q++) {
+        const BatchPlan &pl = plan[q];
+        h_soff[q] = pl.stage_off;
+        h_cnt[q] = 0;
+        if (pl.kind == BP_EMPTY) continue;
+        if (pl.kind == BP_LARGE) {
+            uint64_t count = 0;
+            uint32_t *slot = d_stage + pl.stage_off;
+            int rc;
+            if (pl.is_union) {
+                const uint64_t r0 = query_first[q];
+                rc = union_ranges_unlocked(ctx, query_first[q + 1] - r0, segs + r0, list_first + r0, list_end + r0, tomb, slot, pl.bound, &count);
+            } else {
+                one_segs.clear();
+                one_idx.clear();
+                for (uint32_t i = 0; i < pl.nl; i++) { one_segs.push_back(lists[pl.l0 + i].seg); one_idx.push_back(lists[pl.l0 + i].idx); }
+                const int64_t keep = ctx->opt_intersect_and2;
+                if (keep == 1) ctx->opt_intersect_and2 = 2;
+                rc = intersect_sync(ctx, pl.nl, one_segs.data(), one_idx.data(), tomb, slot, pl.bound, &count);
+                ctx->opt_intersect_and2 = keep;
+            }
+            if (rc) {
+                ctx->err = "ii2_query_batch: query " + std::to_string(q) + ": " + ctx->err;
+                return rc;
+            }
+            h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
+            continue;
+        }
+        BatchQuery &bq = hq[pl.kind == BP_TINY ? at_tiny++ : at_small++];
+        bq = BatchQuery{pl.stage_off, (uint32_t)pl.bound, at_list, pl.nl, pl.is_union, (uint32_t)q, 0u};
+        for (uint32_t i = 0; i < pl.nl; i++) {
+            const SetList &sl = lists[pl.l0 + i];
+            hl[at_list++] = BatchList{sl.v.skip, sl.v.payload, sl.v.nblk, sl.seg->h_cnt[sl.idx]};
+        }
+    }
+    h_cnt[nq] = 0;
+    // 4. table up, the small queries in one launch per size class, counts -> offsets, pack (tests the capacity on the device),
+    // offsets down: one wait
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    if (n_table) {
+        BatchParams bp;
+        std::memset(&bp, 0, sizeof bp);
+        bp.queries = (const BatchQuery *)d;
+        bp.lists = (const BatchList *)(d + o_lists);
+        bp.tomb = tomb ? tomb->d_words : nullptr;
+        bp.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
+        bp.n_tiny = n_kind[BP_TINY];
+        bp.n_small = n_kind[BP_SMALL];
+        bp.stage = d_stage;
+        bp.cnt = (uint32_t *)(d + o_cnt);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_setop_batch(bp, st, e0, e1));
+    }
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d + o_scan, scan_tmp, (const uint32_t *)(d + o_cnt), (uint64_t *)(d + o_off), nq + 1, st));
+    BatchPackParams pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.stage = d_stage;
+    pp.stage_off = (const uint64_t *)(d + o_soff);
+    pp.off = (const uint64_t *)(d + o_off);
+    pp.out = d_out;
+    pp.cap = cap;
+    pp.n_queries = (uint32_t)nq;
+    {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st, e0, e1));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(h_off, d + o_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(out_off, h_off, (nq + 1) * sizeof(uint64_t));
+    if (out_off[nq] > cap) return fail(ctx, II2_ECAPACITY, "ii2_query_batch: the results do not fit the output buffer (nothing written; out_off holds the sizes)");
+    return II2_OK;
+}
+
+extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
+                               const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                               uint64_t *out_off) {
+    if (!ctx || !out_off) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return query_batch_unlocked(ctx, n_queries, op, query_first, segs, list_first, list_end, tomb, d_out, cap, out_off);
 }
 
 extern "C" {

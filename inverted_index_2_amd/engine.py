@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, MergeStats, SegInfo
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, MergeStats, SegInfo
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -39,6 +39,32 @@ def _ptr(a) -> C.c_void_p:
     if isinstance(a, int):
         return C.c_void_p(a)
     raise TypeError(type(a))
+
+
+_BATCH_OPS = {"and": II2_OP_AND, "or": II2_OP_OR}
+
+
+def pack_batch(queries):
+    """The flat arrays ii2_query_batch takes, from queries = [("and" | "or", [(segment, first, end), ...]), ...]: (op u8 [Q],
+    query_first u64 [Q + 1], segments [R], list_first u64 [R], list_end u64 [R]) with R ranges in all; query q owns the ranges
+    query_first[q] .. query_first[q + 1] - 1.  Pure host code: the segments are passed through as they are."""
+    op = np.zeros(len(queries), np.uint8)
+    query_first = np.zeros(len(queries) + 1, np.uint64)
+    segs, first, end = [], [], []
+    for q, (name, ranges) in enumerate(queries):
+        key = name.lower() if isinstance(name, str) else name
+        if key not in _BATCH_OPS:
+            raise ValueError(f"query {q}: unknown op {name!r} (\"and\" or \"or\")")
+        op[q] = _BATCH_OPS[key]
+        for s, a, b in ranges:
+            a, b = int(a), int(b)
+            if a < 0 or b < 0:
+                raise ValueError(f"query {q}: negative list index")
+            segs.append(s)
+            first.append(a)
+            end.append(b)
+        query_first[q + 1] = len(segs)
+    return op, query_first, segs, np.array(first, np.uint64), np.array(end, np.uint64)
 
 
 class DeviceArray:
@@ -324,6 +350,29 @@ class Context:
         self._ck(self.lib.ii2_intersect_ranges(self.h, len(groups), group_first, segs, first, end, tomb.h if tomb else None, _ptr(out),
                                                out.count, C.byref(cnt)))
         return out, cnt.value
+
+    def query_batch(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
+        """Many AND / OR queries in one call (ii2_query_batch): queries = [("and" | "or", [(Segment, first, end), ...]), ...] -
+        an "or" is the union of every list in its ranges, an "and" takes every list in its ranges as one operand.  Returns
+        (DeviceArray ids, offsets): result q is ids[offsets[q] : offsets[q + 1]].  The default `out` holds 256 ids per block
+        of each query's bound (and: its operand with the fewest blocks; or: every block of its ranges)."""
+        op, query_first, qsegs, first, end = pack_batch(queries)
+        n = len(qsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in qsegs])
+        if out is None:
+            blocks = 0
+            for q, (_, ranges) in enumerate(queries):
+                if op[q] == II2_OP_OR:
+                    blocks += sum(s.range_blocks(int(a), int(b), self) for s, a, b in ranges)
+                elif sum(max(min(int(b), s.info.n_lists) - int(a), 0) for s, a, b in ranges) <= 64:      # (more: the library rejects it)
+                    blocks += min((s.list_blocks(j, self) for s, a, b in ranges
+                                   for j in range(int(a), min(int(b), s.info.n_lists))), default=0)
+            out = self.empty(max(blocks * 256, 1))
+        off = np.zeros(len(queries) + 1, np.uint64)
+        self._ck(self.lib.ii2_query_batch(self.h, len(queries), op.ctypes.data_as(_lib.u8p), query_first.ctypes.data_as(_lib.u64p), segs,
+                                          first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None,
+                                          _ptr(out), out.count, off.ctypes.data_as(_lib.u64p)))
+        return out, off
 
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):

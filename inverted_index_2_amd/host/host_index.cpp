@@ -708,7 +708,7 @@ class InvertedIndex {
     // terms that start with a prefix, stops at the first term past the greatest prefix (its first len(greatest) bytes compare
     // greater), then sorts and compacts the collected lists.  Here no list leaves the device: in every segment the lists of
     // a prefix are one run of consecutive terms, [lower_bound(prefix), end of the prefix's run) cut at the end of the greatest
-    // prefix's run, and ONE ii2_union_ranges call per prefix unions the runs of every segment of every shard.
+    // prefix's run, and ONE ii2_query_batch call - an OR query per prefix - unions the runs of every segment of every shard.
     std::map<Term, std::vector<uint32_t>> PrefixSearch(std::vector<Term> prefixes) const {   // inverted_index.go:192-295
         std::sort(prefixes.begin(), prefixes.end(), term_less);
         prefixes.erase(std::unique(prefixes.begin(), prefixes.end()), prefixes.end());
@@ -718,7 +718,6 @@ class InvertedIndex {
         };
         std::map<Term, Ranges> found;
         std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the unions are done
-        std::vector<const ii2_seg *> distinct;
         for (auto &s : shard_list()) {
             Term mn, mx;
             if (!s.second->MinMax(&mn, &mx)) continue;
@@ -745,30 +744,69 @@ class InvertedIndex {
                     r.end.push_back(j1);
                     used = true;
                 }
-                if (used) { held.push_back(sg); distinct.push_back(sg->seg->h); }
+                if (used) held.push_back(sg);
             }
         }
         std::map<Term, std::vector<uint32_t>> out;
         if (found.empty()) return out;
-        // the union of lists of a set of segments holds at most the postings of those segments
-        uint64_t cap = 0;
-        std::sort(distinct.begin(), distinct.end());
-        distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-        for (const ii2_seg *h : distinct) {
-            ii2_seg_info info;
-            ii2_seg_get_info(h, &info);
-            cap += info.n_postings;
-        }
-        DevMem d_out(ctx_);
-        ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
-        for (auto &f : found) {                                               // :288-292 sort + compact, on the GPU
-            const Ranges &r = f.second;
-            uint64_t n = 0;
-            ck(ctx_, ii2_union_ranges(ctx_, r.segs.size(), r.segs.data(), r.first.data(), r.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n),
-               "prefix search");
-            std::vector<uint32_t> ids(n);
-            if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "prefix search");
-            out[f.first] = std::move(ids);
+        // ONE ii2_query_batch call, one wait and one download for all the prefixes (an OR query each).  The output's size: the C
+        // ABI gives no per-list counts, so a prefix is bounded by the postings of the segments its runs lie in; past FIRST_CAP
+        // ids the first call tries FIRST_CAP, and results that do not fit are written by a second call with the size the first
+        // one reported (II2_ECAPACITY writes nothing and fills the offsets).  Prefixes whose bounds add up to the call's limit
+        // of 2^32 ids go in several calls; one that reaches it alone goes through ii2_union_ranges.
+        constexpr uint64_t FIRST_CAP = 1u << 22, CALL_IDS = 0xFFFFFFFFull;
+        auto it = found.begin();
+        while (it != found.end()) {
+            std::vector<const Term *> names;
+            std::vector<uint8_t> op;
+            std::vector<uint64_t> query_first{0}, first, end;
+            std::vector<const ii2_seg *> segs;
+            uint64_t bound = 0;
+            for (; it != found.end(); ++it) {
+                const Ranges &r = it->second;
+                uint64_t b = 0;
+                for (const ii2_seg *h : r.segs) {
+                    ii2_seg_info info;
+                    ii2_seg_get_info(h, &info);
+                    b += info.n_postings;
+                }
+                if (!names.empty() && bound + b >= CALL_IDS) break;
+                bound += b;
+                names.push_back(&it->first);
+                op.push_back(II2_OP_OR);
+                segs.insert(segs.end(), r.segs.begin(), r.segs.end());
+                first.insert(first.end(), r.first.begin(), r.first.end());
+                end.insert(end.end(), r.end.begin(), r.end.end());
+                query_first.push_back(segs.size());
+            }
+            DevMem d_out(ctx_);
+            if (bound >= CALL_IDS) {                                          // (one prefix, alone in its call)
+                uint64_t n = 0;
+                ck(ctx_, ii2_dev_alloc(ctx_, (bound + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
+                ck(ctx_, ii2_union_ranges(ctx_, segs.size(), segs.data(), first.data(), end.data(), nullptr, (uint32_t *)d_out.p, bound + 1, &n),
+                   "prefix search");
+                std::vector<uint32_t> ids(n);
+                if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "prefix search");
+                out[*names[0]] = std::move(ids);
+                continue;
+            }
+            std::vector<uint64_t> off(names.size() + 1, 0);
+            uint64_t cap = std::min(bound, FIRST_CAP);
+            for (int attempt = 0;; attempt++) {
+                ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
+                const int rc = ii2_query_batch(ctx_, names.size(), op.data(), query_first.data(), segs.data(), first.data(), end.data(), nullptr,
+                                               (uint32_t *)d_out.p, cap + 1, off.data());
+                if (rc != II2_ECAPACITY || attempt) {
+                    ck(ctx_, rc, "prefix search");
+                    break;
+                }
+                ck(ctx_, ii2_dev_free(ctx_, d_out.p), "prefix search");
+                d_out.p = nullptr;
+                cap = off.back();
+            }
+            std::vector<uint32_t> all(off.back());                            // :288-292 sort + compact, on the GPU
+            if (!all.empty()) ck(ctx_, ii2_copy_d2h(ctx_, all.data(), d_out.p, all.size() * sizeof(uint32_t)), "prefix search");
+            for (size_t q = 0; q < names.size(); q++) out[*names[q]] = std::vector<uint32_t>(all.begin() + off[q], all.begin() + off[q + 1]);
         }
         return out;
     }
