@@ -379,6 +379,74 @@ func (c *Ctx) QueryBatch(op []uint8, queryFirst []uint64, segs []*Segment, listF
 	return offsets, nil
 }
 
+// AndNotRanges answers one boolean query with excluded (NOT) groups over resident segments (ii2_andnot_ranges): the ids that
+// lie in at least one list of EVERY required group and in NO list of ANY excluded group.  Group g owns the ranges
+// groupFirst[g] .. groupFirst[g+1]-1, a range being lists [listFirst[i], listEnd[i]) of segs[i]; groupNot[g] is 0 for a
+// required group and 1 for an excluded one (at least one group must be required; groupNot == nil: every group is required,
+// the call is ii2_intersect_ranges).  The ids go to the device buffer out (capacity capIDs ids; the postings of the smallest
+// required group are always enough) and their number is returned.  All-or-nothing: on ErrCapacity nothing was written and
+// the returned count is the capacity to call again with.
+func (c *Ctx) AndNotRanges(groupFirst []uint64, groupNot []uint8, segs []*Segment, listFirst, listEnd []uint64, out unsafe.Pointer, capIDs uint64) (uint64, error) {
+	nGroups := len(groupFirst) - 1
+	if nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return 0, fmt.Errorf("andnot ranges: array lengths disagree")
+	}
+	if nGroups == 0 {
+		return 0, nil
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if groupNot != nil {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	var n C.uint64_t
+	rc := C.ii2_andnot_ranges(c.h, C.uint64_t(nGroups), u64ptr(groupFirst), flags, (**C.ii2_seg)(unsafe.Pointer(&hs[0])),
+		u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(out), C.uint64_t(capIDs), &n)
+	if rc == C.II2_ECAPACITY {
+		return uint64(n), ErrCapacity
+	}
+	if rc != 0 {
+		return 0, c.err("andnot ranges", rc)
+	}
+	return uint64(n), nil
+}
+
+// AndNotRangesHost is AndNotRanges with the result in host memory: a device buffer of firstCap ids (the caller's bound of the
+// smallest required group, or less), a second call with the size the first one reported when the result did not fit (nothing
+// was written then), one download.
+func (c *Ctx) AndNotRangesHost(groupFirst []uint64, groupNot []uint8, segs []*Segment, listFirst, listEnd []uint64, firstCap uint64) ([]uint32, error) {
+	capIDs := firstCap
+	for attempt := 0; ; attempt++ {
+		var d unsafe.Pointer
+		if rc := C.ii2_dev_alloc(c.h, C.size_t((capIDs+1)*4), &d); rc != 0 {
+			return nil, c.err("andnot ranges", rc)
+		}
+		n, err := c.AndNotRanges(groupFirst, groupNot, segs, listFirst, listEnd, d, capIDs+1)
+		if err == ErrCapacity && attempt == 0 {
+			C.ii2_dev_free(c.h, d)
+			capIDs = n
+			continue
+		}
+		if err != nil {
+			C.ii2_dev_free(c.h, d)
+			return nil, err
+		}
+		ids := make([]uint32, n)
+		var rc C.int
+		if n > 0 {
+			rc = C.ii2_copy_d2h(c.h, unsafe.Pointer(&ids[0]), d, C.size_t(n*4))
+		}
+		C.ii2_dev_free(c.h, d)
+		if rc != 0 {
+			return nil, c.err("andnot ranges", rc)
+		}
+		return ids, nil
+	}
+}
+
 // Union replaces PrefixSearch's append + slices.Sort + slices.Compact (inverted_index.go:274-292).
 func (c *Ctx) Union(listOff []uint64, values, removed []uint32) ([]uint32, error) {
 	return c.lists(true, listOff, values, removed)

@@ -217,3 +217,68 @@ func ShardRead(c *Ctx, s HostShard, nSegs int, min, max []byte) (Iterator[TermVa
 	}
 	return &readIterator{terms: terms, off: outOff, values: outVals, host: s}, nil
 }
+
+// ResidentIndex is what a host that keeps its segments resident (Ctx.Encode once per segment) provides for the additive
+// boolean queries: where a term's postings are.
+type ResidentIndex interface {
+	// TermLists returns, for every segment of the term's shard that holds the term, the resident segment and the term's list
+	// index in it, and an upper bound of the term's postings (0 lists: the term is in no segment).  The segments stay
+	// read-locked until Release.
+	TermLists(term []byte) (segs []*Segment, lists []uint64, postingsBound uint64)
+	Release()
+}
+
+// IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
+// "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
+// flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does
+// (host/host_index.cpp).  An excluded term found in no segment is dropped; a required one gives the empty result.  Like Read,
+// no tombstone filter.
+func IntersectExcept(c *Ctx, ix ResidentIndex, terms, except [][]byte) ([]uint32, error) {
+	if len(terms) == 0 {
+		return nil, nil
+	}
+	defer ix.Release()
+	const firstCap = uint64(1) << 22
+	groupFirst := []uint64{0}
+	var groupNot []uint8
+	var segs []*Segment
+	var first, end []uint64
+	bound := ^uint64(0)
+	add := func(t []byte, not uint8) uint64 {
+		s, l, post := ix.TermLists(t)
+		if len(s) == 0 {
+			return 0
+		}
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, not)
+		if post == 0 {
+			post = 1
+		}
+		return post
+	}
+	for _, t := range terms {
+		post := add(t, 0)
+		if post == 0 {
+			return nil, nil // a required term in no segment: nothing is under every term
+		}
+		if post < bound {
+			bound = post
+		}
+	}
+	for _, t := range except {
+		add(t, 1) // (in no segment: it removes nothing)
+	}
+	if bound > firstCap {
+		bound = firstCap
+	}
+	ids, err := c.AndNotRangesHost(groupFirst, groupNot, segs, first, end, bound)
+	if err != nil {
+		return nil, fmt.Errorf("intersect except: %w", err)
+	}
+	return ids, nil
+}

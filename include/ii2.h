@@ -20,7 +20,9 @@
  *     blocks and < 2^30 term slots; ii2_align_terms takes < 2^31 terms; one segment holds < 2^31
  *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls);
  *     ii2_query_batch takes <= 2^20 queries whose result bounds (AND: the shortest operand, OR: the postings of
- *     its ranges) add up to < 2^32 ids.
+ *     its ranges) add up to < 2^32 ids.  The one-launch form of ii2_andnot_ranges takes queries whose non-empty lists - required
+ *     and excluded - are at most II2_MAX_LISTS and hold at most 8192 postings in at most 128 blocks, by default only while
+ *     postings x lists <= 32768 (what the form costs; beyond it, or beyond the kernel, a query takes the general form: no error).
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
  *     internal mutex, so a ctx may be shared by goroutines / threads (InvertedIndex.Merge
  *     fans Shard.Merge over `concurrency` goroutines, inverted_index.go:83-103); use one
@@ -270,6 +272,32 @@ int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_
                          const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
                          uint32_t *d_out, uint64_t cap, uint64_t *count);
 
+/* AND of ORs over list ranges MINUS excluded groups - boolean queries with NOT ("docs with `error` and `db` but not
+ * `healthcheck`"): the ascending, duplicate-free ids that lie in at least one list of EVERY required group and in NO list of ANY
+ * excluded group, minus the tombstones when tomb != NULL.  Groups and ranges are exactly those of ii2_intersect_ranges (segments
+ * and views alike; a list may appear in any number of ranges and groups; ranges may overlap; any number of groups and lists).
+ * group_not (host memory, n_groups bytes): 0 = group g is required, 1 = it is excluded.
+ *   - group_not == NULL: the call IS ii2_intersect_ranges (same code path, same results, same errors).  An all-zero array gives
+ *     the same result (the path may differ).
+ *   - n_groups == 0: *count = 0.  n_groups > 0 and no required group: II2_EINVAL - the library has no doc universe to complement.
+ *     A flag other than 0 / 1: II2_EINVAL.  Bad ranges are rejected as ii2_intersect_ranges rejects them, under this entry point's
+ *     name.  Every check happens before anything is launched or written.
+ *   - a required group without postings, or required groups whose doc spans do not overlap: *count = 0, nothing launched, d_out
+ *     may be NULL.  An excluded group without postings is ignored, and so is any excluded list whose doc span misses the required
+ *     groups' common span; the excluded groups never narrow that span.
+ *   - one required group is allowed: (a OR b) NOT c.  A list that is both required and excluded removes its ids.
+ *   - cap >= the postings of the required group with the fewest postings is always enough.  All-or-nothing on EVERY path: on
+ *     II2_ECAPACITY nothing is written to d_out and *count holds the size needed (the required part, which may go through the paths
+ *     of ii2_intersect, is computed into a per-context array that always holds it, kept until ii2_ctx_destroy).
+ *   - the tombstones are applied once, to the required part.
+ * Short queries (see the conventions above; option andnot.small) are ONE launch and one wait: every list decoded into LDS group by
+ * group, every id ranked together with its group's tag, a run of equal ids kept when it holds every required tag and not the
+ * excluded one.  The general form runs the required groups through the paths of ii2_intersect_ranges, then one exclusion pass over
+ * the survivors - all excluded ranges as one group, the probe / mark filter with the flag turned round (intersect.ranges_mark). */
+int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                      const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                      const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count);
+
 /* MANY AND / OR queries in one call: what a search front end sends in bulk.  Replaces the per-prefix loop of PrefixSearch
  * (PrefixSearch(prefixes [][]byte), inverted_index.go:192: inverted_index.go:274-292 once per prefix) and a loop over the
  * build-defined Intersect (ii2_intersect) - a launch, and for the synchronous calls a stream wait, per query - by a number of
@@ -381,6 +409,9 @@ int ii2_selftest(ii2_ctx *ctx);
  *   intersect.ranges_mark                   its filters mark a group into the doc bitmap when the group holds at most N postings per
  *                                           (list x 256 candidates) or the candidates are fewer than 1024 per CU, else probe its lists
  *                                           (default 64; 0: always probe)
+ *   andnot.small                            ii2_andnot_ranges: 1 (default) queries of at most II2_MAX_LISTS non-empty lists, 8192 postings and
+ *                                           128 blocks with postings x lists <= 32768 whose result surely fits run as one launch; 2 the
+ *                                           same up to the kernel's capacity (no postings x lists bound); 0 never (always the general form)
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel

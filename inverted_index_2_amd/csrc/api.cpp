@@ -155,6 +155,7 @@ void ii2_ctx_destroy(ii2_ctx *ctx) {
     if (ctx->h_um) (void)hipHostFree(ctx->h_um);
     if (ctx->d_ir) (void)hipFree(ctx->d_ir);
     if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
+    if (ctx->d_an) (void)hipFree(ctx->d_an);
     if (ctx->d_batch) (void)hipFree(ctx->d_batch);
     if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
     if (ctx->d_mail) (void)hipFree(ctx->d_mail);
@@ -1004,6 +1005,7 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "debug.union_many_no_atomics") ctx->opt_union_many_no_atomics = value;
     else if (k == "intersect.ranges") ctx->opt_intersect_ranges = value;
     else if (k == "intersect.ranges_mark") ctx->opt_ir_mark = value;
+    else if (k == "andnot.small") ctx->opt_andnot_small = value;
     else if (k == "union.sparsity") ctx->opt_union_sparsity = value > 0 ? value : 2048;
     else if (k == "intersect.map_docs") ctx->opt_intersect_map_docs = value;
     else if (k == "intersect.dense") ctx->opt_intersect_dense = value;

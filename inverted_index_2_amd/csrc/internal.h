@@ -97,6 +97,9 @@ struct ii2_ctx {
     size_t ir_words = 0;
     void *h_ir = nullptr;               // pinned staging of its filters' descriptors (grow-only)
     size_t h_ir_cap = 0;
+    int64_t opt_andnot_small = 1;       // ii2_andnot_ranges: short queries in one launch (setop_groups.hip); 0: never, 2: up to the kernel's capacity
+    uint32_t *d_an = nullptr;           // its required part's result, the candidates of the exclusion pass (grow-only; neither d_ir, which the
+    size_t an_words = 0;                //     group path ping-pongs in, nor workspace, which the driver's union reserves itself)
     int64_t opt_batch_small = 1;        // ii2_query_batch: small queries share the batch kernel (0: every query through the single-query paths)
     int64_t opt_batch_tiny = 1;         // ... those of <= 2048 postings in <= 32 blocks in its 256-thread form (0: all in the 1024-thread form)
     uint8_t *d_batch = nullptr;         // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
@@ -330,6 +333,25 @@ struct BatchPackParams {
     uint32_t n_queries;
 };
 hipError_t launch_setop_batch(const BatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// a short AND of ORs minus excluded lists in one workgroup (setop_groups.hip): the lists group by group, the required groups
+// first (tags 0 .. n_req - 1), the lists of all excluded groups last (tag n_req)
+constexpr uint64_t ANDNOT_SMALL_WORK = 32768;   // postings x lists up to which ii2_andnot_ranges takes it by default (setop.cpp: andnot_small)
+struct GroupSetParams {
+    ListView lists[MAX_LISTS];   // non-empty lists in tag order
+    uint32_t blk_base[MAX_LISTS + 1];   // first block of each list in the concatenated block list
+    uint32_t lpre[MAX_LISTS + 1];       // exclusive prefix of the lists' posting counts; lpre[n_lists] <= SMALL_SET_POSTINGS
+    uint8_t tag[MAX_LISTS];      // the group of each list, ascending
+    uint32_t n_lists;
+    uint32_t n_blocks;           // <= SMALL_SET_BLOCKS
+    uint32_t n_req;              // required groups, 1 .. n_lists
+    uint32_t tomb_nwords;
+    const uint32_t *tomb;        // may be null
+    uint32_t *out;
+    uint64_t out_cap;            // nothing is written when the result is longer
+    uint64_t *d_count;
+};
+hipError_t launch_setop_groups(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_batch_pack(const BatchPackParams &p, uint64_t max_bound, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // OR of a few medium-size lists by ranking (union_rank.hip)
@@ -448,6 +470,7 @@ struct IrParams {
     const uint32_t *cand;        // [n_cand] the candidates, ascending
     uint64_t n_cand;
     uint32_t *flag;              // [n_cand + 1] 1 = found in the group (flag[n_cand] = 0), then in place their exclusive scan
+    uint32_t drop;               // 1: an exclusion - 1 = NOT found in the group (mark: the flags start at 1 and hits clear them)
     const IrList *lists;         // probe: the group's non-empty lists
     uint32_t n_lists;
     uint32_t win_lo, win_docs;   // mark: the window (win_lo a multiple of 32) ...

@@ -1,7 +1,8 @@
 // intersect_ranges.hip — AND of ORs over list ranges (ii2_intersect_ranges): the filters of the group path.  The candidates
 // (the union of the group with the fewest postings, setop.cpp) are an ascending id array; each further group is one pass
 // that flags the candidates found in at least one of its lists, then scan.hip turns the flags into offsets in place and
-// k_ir_compact writes the survivors in order.  Two ways to flag:
+// k_ir_compact writes the survivors in order.  An excluded group (ii2_andnot_ranges) is the same pass with the flag turned
+// round (IrParams::drop): the candidates NOT found survive.  Two ways to flag:
 //   probe (k_ir_probe): one wave per run of IR_PROBE_RUN consecutive candidates.  Per list of the group it finds the block of
 //        its first open candidate with the guess-then-walk search (upper_bound_guess), then walks forward: the next 64 skip
 //        entries in one load, a new search only past them.  Every block it lands on is decoded once into LDS and the open
@@ -97,16 +98,17 @@ __global__ __launch_bounds__(256) void k_ir_probe(IrParams p) {
     }
 #pragma unroll
     for (uint32_t k = 0; k < CH; k++)
-        if (valid[k]) p.flag[c0 + k * 64u + l] = found[k] ? 1u : 0u;
+        if (valid[k]) p.flag[c0 + k * 64u + l] = (found[k] ? 1u : 0u) ^ p.drop;      // (an exclusion keeps what was NOT found)
 }
 
-// mark mode: every candidate inside the window whose bit the group's blocks set is flagged (flags start at zero)
+// mark mode: every candidate inside the window whose bit the group's blocks set is flagged (flags start at zero); an exclusion
+// (p.drop) starts them at one - a candidate outside every window survives - and a set bit clears the flag
 __global__ __launch_bounds__(256) void k_ir_test(IrParams p) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= p.n_cand) return;
     const uint32_t rel = p.cand[i] - p.win_lo;
     if (p.cand[i] < p.win_lo || rel >= p.win_docs) return;
-    if ((p.bitmap[rel >> 5] >> (rel & 31u)) & 1u) p.flag[i] = 1u;
+    if ((p.bitmap[rel >> 5] >> (rel & 31u)) & 1u) p.flag[i] = 1u ^ p.drop;
 }
 
 // mark mode: the scratch back to zero - one wave per summary word, as k_um_compact clears it

@@ -10,6 +10,11 @@
 //        overlap (count 0, no launch); one group: the OR of list ranges; up to 64 groups of one non-empty list each whose
 //        result surely fits: the AND chooser above (ii2_intersect); otherwise the group path - the OR of the group with the
 //        fewest postings as candidates, then per further group a probe or mark filter (intersect_ranges.hip).
+//   AND of ORs minus excluded groups (ii2_andnot_ranges): group_not == NULL: the call above.  No group (count 0); a required group
+//        without blocks or required groups whose doc spans do not overlap (count 0, no launch); up to 64 non-empty lists of 8192
+//        postings in 128 blocks, a result that surely fits: one launch (setop_groups.hip); otherwise the required groups through
+//        the chooser above into a candidate array, then ONE exclusion pass over the excluded lists that reach the candidates'
+//        span - the probe / mark filter with the flag turned round - or, without such a list, a copy.
 //   Many AND / OR queries in one call (ii2_query_batch): the small ones in one launch per size class (setop_batch.hip), the
 //        others one by one through the choosers above; all of them staged, then packed in query order.
 #include <algorithm>
@@ -796,6 +801,123 @@ static void um_desc_fill(const std::vector<RangeIn> &rs, size_t r0, size_t r1, u
     hpre[nr] = acc;
 }
 
+// one filter pass of the group path: the group's ranges rs[r0, r1) with their sizes, the doc span the mark's windows cover, and
+// whether the candidates found survive (a required group) or those NOT found (the excluded lists of ii2_andnot_ranges)
+struct IrPass {
+    size_t r0, r1;
+    uint64_t n_blocks, n_nonempty, n_post;
+    uint32_t lo, hi;
+    bool drop;
+};
+
+// a non-empty list of a pass that its probe looks at: every one of a required group; of an exclusion those whose mirrored doc
+// span meets [lo, hi] (a list elsewhere removes nothing)
+static bool ir_list_counts(const IrPass &G, const ii2_seg *s, uint64_t j) {
+    if (s->h_blk_off[j + 1] == s->h_blk_off[j]) return false;
+    if (!G.drop || s->h_spans.size() != 3 * s->n_lists) return true;
+    return s->h_spans[3 * j] <= G.hi && s->h_spans[3 * j + 2] >= G.lo;
+}
+
+// The candidates cand[0, nc) (ascending, nc > 0) filtered by one group - probe or mark (intersect_ranges.hip), scan, compact - into
+// out, which is written only when all *n_out survivors fit out_cap.  One count read.
+static int ir_filter_pass(ii2_ctx *ctx, const char *who, const std::vector<RangeIn> &rs, const IrPass &G, const uint32_t *cand, uint64_t nc,
+                          uint32_t *out, uint64_t out_cap, uint64_t *n_out) {
+    hipStream_t st = ctx->stream;
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    const size_t nr = G.r1 - G.r0;
+    // probe: one search per list and run of 256 candidates, the runs' block walks one after the other (latency-bound: it needs
+    // enough runs to fill the GPU); mark: every posting of the group once.  Measured: the probe wins on long
+    // lists against millions of candidates, the mark on many lists and on few candidates (option intersect.ranges_mark).
+    const uint64_t runs = (nc + IR_PROBE_RUN - 1) / IR_PROBE_RUN;
+    const bool mark = ctx->opt_ir_mark > 0 &&
+                      (runs < 4u * (uint64_t)ctx->cu_count || (double)G.n_post <= (double)ctx->opt_ir_mark * (double)G.n_nonempty * (double)runs);
+    const size_t desc_bytes = mark ? um_desc_bytes(nr) : align_up(G.n_nonempty * sizeof(IrList));
+    uint8_t *h = nullptr;
+    if (int rc = ir_stage(ctx, desc_bytes, &h)) return rc;
+    size_t m = 0;
+    if (mark) um_desc_fill(rs, G.r0, G.r1, h);
+    else {
+        IrList *hl = (IrList *)h;
+        for (size_t r = G.r0; r < G.r1; r++) {
+            const ii2_seg *s = rs[r].seg;
+            const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+            for (uint64_t j = rs[r].l0; j < rs[r].l1 && m < G.n_nonempty; j++) {
+                if (!ir_list_counts(G, s, j)) continue;
+                const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1];
+                hl[m++] = IrList{s->d_skip + b0, s->d_payload, s->d_last_doc + j, b1 - b0, mirrored ? s->h_spans[3 * j] : 1u,
+                                 mirrored ? s->h_spans[3 * j + 2] : 0u, 0u};
+            }
+        }
+    }
+    const size_t scan_tmp = scan_temp_bytes(nc + 1);
+    if (int rc = ii2_ws_reserve(ctx, desc_bytes + align_up((nc + 1) * sizeof(uint32_t)) + scan_tmp + 4096)) return rc;
+    uint8_t *d_desc = ws_take<uint8_t>(ctx, desc_bytes);
+    IrParams ip;
+    std::memset(&ip, 0, sizeof ip);
+    ip.cand = cand;
+    ip.n_cand = nc;
+    ip.drop = G.drop ? 1u : 0u;
+    ip.flag = ws_take<uint32_t>(ctx, nc + 1);
+    void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
+    HIP_TRY(ctx, hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    if (mark) {
+        if (G.drop) {                                   // a candidate outside every window survives: the flags start at one
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ip.flag, 1, nc, st));
+            HIP_TRY(ctx, hipMemsetAsync(ip.flag + nc, 0, sizeof(uint32_t), st));
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(ip.flag, 0, (nc + 1) * sizeof(uint32_t), st));
+        }
+        if (int rc = um_scratch_clean(ctx)) return rc;
+        const uint64_t W = um_window(ctx);
+        const uint32_t base = G.lo & ~31u;
+        const uint64_t span = (uint64_t)G.hi - base + 1;
+        if (int rc = um_scratch_reserve(ctx, who, span, W)) return rc;
+        UnionManyParams p;
+        std::memset(&p, 0, sizeof p);
+        p.ranges = (const UmRange *)d_desc;
+        p.pre = (const uint32_t *)(d_desc + align_up(nr * sizeof(UmRange)));
+        p.n_ranges = (uint32_t)nr;
+        p.n_blocks = (uint32_t)G.n_blocks;
+        p.check_window = 1u;                        // blocks outside the candidates' span are not decoded
+        const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
+        p.per_wave = (uint32_t)std::max<uint64_t>(1, (G.n_blocks + target_waves - 1) / target_waves);
+        ctx->um_dirty = true;
+        for (uint64_t wlo = base; wlo <= G.hi; wlo += W) {
+            const uint64_t docs = std::min<uint64_t>(W, (uint64_t)G.hi - wlo + 1);
+            p.win_lo = (uint32_t)wlo;
+            p.win_docs = (uint32_t)docs;
+            p.n_sum = (uint32_t)((docs + 65535) / 65536);
+            p.bitmap = ctx->d_um_bits;
+            p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+            ip.win_lo = p.win_lo;
+            ip.win_docs = p.win_docs;
+            ip.n_sum = p.n_sum;
+            ip.bitmap = p.bitmap;
+            ip.summary = p.summary;
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+            HIP_TRY(ctx, launch_union_many_mark(p, st, e0, e1));
+            HIP_TRY(ctx, launch_ir_test(ip, st));
+            HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
+            e0 = e1 = nullptr;
+        }
+    } else {
+        ip.lists = (const IrList *)d_desc;
+        ip.n_lists = (uint32_t)m;
+        HIP_TRY(ctx, hipMemsetAsync(ip.flag + nc, 0, sizeof(uint32_t), st));
+        HIP_TRY(ctx, launch_ir_probe(ip, st, e0, e1));
+    }
+    HIP_TRY(ctx, scan_excl_u32(d_scan, scan_tmp, ip.flag, ip.flag, nc + 1, st));
+    ip.out = out;
+    ip.out_cap = out_cap;
+    ip.d_count = d_cnt ? d_cnt : ctx->d_mail;
+    HIP_TRY(ctx, launch_ir_compact(ip, st));
+    if (int rc = read_count(ctx, ip.d_count, n_out)) return rc;
+    ctx->um_dirty = false;
+    return II2_OK;
+}
+
 // The group path: the driver's union (the group with the fewest postings, minus the tombstones) is the candidate array, then
 // one filter pass per further group in ascending order of postings - probe or mark (intersect_ranges.hip), scan, compact -
 // until no candidate is left.  The last pass writes d_out only when the whole result fits.  One count read per group.
@@ -874,96 +996,12 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
     std::vector<size_t> order;
     for (size_t g = 0; g < gs.size(); g++) if (g != drv) order.push_back(g);
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return gs[a].n_post < gs[b].n_post; });
-    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
     uint32_t src = 0;
     for (size_t k = 0; k < order.size() && nc; k++) {
         const GroupIn &G = gs[order[k]];
         const bool last = k + 1 == order.size();
-        const size_t nr = G.r1 - G.r0;
-        // probe: one search per list and run of 256 candidates, the runs' block walks one after the other (latency-bound: it needs
-        // enough runs to fill the GPU); mark: every posting of the group once.  Measured: the probe wins on long
-        // lists against millions of candidates, the mark on many lists and on few candidates (option intersect.ranges_mark).
-        const uint64_t runs = (nc + IR_PROBE_RUN - 1) / IR_PROBE_RUN;
-        const bool mark = ctx->opt_ir_mark > 0 &&
-                          (runs < 4u * (uint64_t)ctx->cu_count || (double)G.n_post <= (double)ctx->opt_ir_mark * (double)G.n_nonempty * (double)runs);
-        const size_t desc_bytes = mark ? um_desc_bytes(nr) : align_up(G.n_nonempty * sizeof(IrList));
-        uint8_t *h = nullptr;
-        if (int rc = ir_stage(ctx, desc_bytes, &h)) return rc;
-        if (mark) um_desc_fill(rs, G.r0, G.r1, h);
-        else {
-            IrList *hl = (IrList *)h;
-            size_t m = 0;
-            for (size_t r = G.r0; r < G.r1; r++) {
-                const ii2_seg *s = rs[r].seg;
-                const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
-                for (uint64_t j = rs[r].l0; j < rs[r].l1; j++) {
-                    const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1];
-                    if (b1 == b0) continue;
-                    hl[m++] = IrList{s->d_skip + b0, s->d_payload, s->d_last_doc + j, b1 - b0, mirrored ? s->h_spans[3 * j] : 1u,
-                                     mirrored ? s->h_spans[3 * j + 2] : 0u, 0u};
-                }
-            }
-        }
-        const size_t scan_tmp = scan_temp_bytes(nc + 1);
-        if (int rc = ii2_ws_reserve(ctx, desc_bytes + align_up((nc + 1) * sizeof(uint32_t)) + scan_tmp + 4096)) return rc;
-        uint8_t *d_desc = ws_take<uint8_t>(ctx, desc_bytes);
-        IrParams ip;
-        std::memset(&ip, 0, sizeof ip);
-        ip.cand = buf[src];
-        ip.n_cand = nc;
-        ip.flag = ws_take<uint32_t>(ctx, nc + 1);
-        void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
-        HIP_TRY(ctx, hipMemcpyAsync(d_desc, h, desc_bytes, hipMemcpyHostToDevice, st));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ii2_profile_pair(ctx, &e0, &e1);
-        if (mark) {
-            HIP_TRY(ctx, hipMemsetAsync(ip.flag, 0, (nc + 1) * sizeof(uint32_t), st));
-            if (int rc = um_scratch_clean(ctx)) return rc;
-            const uint64_t W = um_window(ctx);
-            const uint32_t base = clo & ~31u;
-            const uint64_t span = (uint64_t)chi - base + 1;
-            if (int rc = um_scratch_reserve(ctx, "ii2_intersect_ranges", span, W)) return rc;
-            UnionManyParams p;
-            std::memset(&p, 0, sizeof p);
-            p.ranges = (const UmRange *)d_desc;
-            p.pre = (const uint32_t *)(d_desc + align_up(nr * sizeof(UmRange)));
-            p.n_ranges = (uint32_t)nr;
-            p.n_blocks = (uint32_t)G.n_blocks;
-            p.check_window = 1u;                        // blocks outside the candidates' span are not decoded
-            const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
-            p.per_wave = (uint32_t)std::max<uint64_t>(1, (G.n_blocks + target_waves - 1) / target_waves);
-            ctx->um_dirty = true;
-            for (uint64_t wlo = base; wlo <= chi; wlo += W) {
-                const uint64_t docs = std::min<uint64_t>(W, (uint64_t)chi - wlo + 1);
-                p.win_lo = (uint32_t)wlo;
-                p.win_docs = (uint32_t)docs;
-                p.n_sum = (uint32_t)((docs + 65535) / 65536);
-                p.bitmap = ctx->d_um_bits;
-                p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
-                ip.win_lo = p.win_lo;
-                ip.win_docs = p.win_docs;
-                ip.n_sum = p.n_sum;
-                ip.bitmap = p.bitmap;
-                ip.summary = p.summary;
-                const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
-                HIP_TRY(ctx, launch_union_many_mark(p, st, e0, e1));
-                HIP_TRY(ctx, launch_ir_test(ip, st));
-                HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
-                e0 = e1 = nullptr;
-            }
-        } else {
-            ip.lists = (const IrList *)d_desc;
-            ip.n_lists = (uint32_t)G.n_nonempty;
-            HIP_TRY(ctx, hipMemsetAsync(ip.flag + nc, 0, sizeof(uint32_t), st));
-            HIP_TRY(ctx, launch_ir_probe(ip, st, e0, e1));
-        }
-        HIP_TRY(ctx, scan_excl_u32(d_scan, scan_tmp, ip.flag, ip.flag, nc + 1, st));
-        ip.out = last ? d_out : buf[src ^ 1u];
-        ip.out_cap = last ? cap : nc;
-        ip.d_count = d_cnt ? d_cnt : ctx->d_mail;
-        HIP_TRY(ctx, launch_ir_compact(ip, st));
-        if (int rc = read_count(ctx, ip.d_count, &nc)) return rc;
-        ctx->um_dirty = false;
+        const IrPass pass{G.r0, G.r1, G.n_blocks, G.n_nonempty, G.n_post, clo, chi, false};
+        if (int rc = ir_filter_pass(ctx, "ii2_intersect_ranges", rs, pass, buf[src], nc, last ? d_out : buf[src ^ 1u], last ? cap : nc, &nc)) return rc;
         if (last && nc > cap) {
             *count = nc;
             return fail(ctx, II2_ECAPACITY, "ii2_intersect_ranges: result does not fit the output buffer (nothing written)");
@@ -974,30 +1012,30 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
     return II2_OK;
 }
 
-static int intersect_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
-                                     const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
-                                     uint64_t *count) {
-    if (n_groups == 0) { *count = 0; return II2_OK; }
-    if (!group_first) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: bad argument");
+// The groups of a call, checked (`who` names the entry point in the messages): the ranges of group g that own blocks are
+// rs[gs[g].r0, gs[g].r1); *n_blocks = the blocks of all of them.  n_groups > 0.
+static int collect_groups(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                          const uint64_t *list_first, const uint64_t *list_end, std::vector<RangeIn> &rs, std::vector<GroupIn> &gs, uint64_t *n_blocks) {
+    const std::string w(who);
+    if (!group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
     for (uint64_t g = 0; g < n_groups; g++)
-        if (group_first[g + 1] < group_first[g]) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: group_first does not ascend");
-    if (group_first[n_groups] > group_first[0] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: bad argument");
-    std::vector<RangeIn> rs;
-    std::vector<GroupIn> gs(n_groups);
-    uint64_t n_blocks = 0;
+        if (group_first[g + 1] < group_first[g]) return fail(ctx, II2_EINVAL, (w + ": group_first does not ascend").c_str());
+    if (group_first[n_groups] > group_first[0] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    gs.resize(n_groups);
     for (uint64_t g = 0; g < n_groups; g++) {
         const uint64_t a = group_first[g], b = group_first[g + 1];
         GroupIn &G = gs[g];
         std::memset(&G, 0, sizeof G);
         G.r0 = rs.size();
-        if (int rc = collect_ranges(ctx, "ii2_intersect_ranges", b - a, segs + a, list_first + a, list_end + a, rs, &G.n_blocks, &G.n_nonempty)) return rc;
+        if (int rc = collect_ranges(ctx, who, b - a, segs + a, list_first + a, list_end + a, rs, &G.n_blocks, &G.n_nonempty)) return rc;
         G.r1 = rs.size();
-        n_blocks += G.n_blocks;
+        *n_blocks += G.n_blocks;
     }
-    for (const GroupIn &G : gs) if (!G.n_blocks) { *count = 0; return II2_OK; }
-    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_intersect_ranges: more than 2^32 - 2 blocks in one call");
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: output buffer is NULL");
-    // postings (the driver, the order of the filters, the hand-off's capacity) and the doc spans mirrored on the host
+    return II2_OK;
+}
+
+// postings (the driver, the order of the filters, the hand-off's capacity) and the doc spans mirrored on the host
+static int group_sizes(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::vector<GroupIn> &gs) {
     for (GroupIn &G : gs) {
         G.lo = 0xFFFFFFFFu;
         G.hi = 0;
@@ -1016,14 +1054,30 @@ static int intersect_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint
             }
         }
     }
-    uint32_t clo = 0, chi = 0xFFFFFFFFu;
+    return II2_OK;
+}
+
+// the doc span the groups whose spans are known have in common (*clo > *chi: none - nothing lies in every group)
+static void common_span(const std::vector<GroupIn> &gs, uint32_t *clo, uint32_t *chi) {
+    *clo = 0;
+    *chi = 0xFFFFFFFFu;
     for (const GroupIn &G : gs) {
         if (!G.span_known) continue;
-        clo = std::max(clo, G.lo);
-        chi = std::min(chi, G.hi);
+        *clo = std::max(*clo, G.lo);
+        *chi = std::min(*chi, G.hi);
     }
-    if (clo > chi) { *count = 0; return II2_OK; }
-    if (n_groups == 1) return union_collected(ctx, rs, n_blocks, gs[0].n_nonempty, tomb, d_out, cap, count);
+}
+
+// AND of sized groups that all own blocks and whose known spans overlap, d_out != NULL: the first path of the chooser that fits
+static int intersect_sized(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::vector<GroupIn> &gs, const ii2_tomb *tomb, uint32_t *d_out,
+                           uint64_t cap, uint64_t *count) {
+    const uint64_t n_groups = gs.size();
+    if (n_groups == 1) {
+        const GroupIn &G = gs[0];
+        if (G.r0 == 0 && G.r1 == rs.size()) return union_collected(ctx, rs, G.n_blocks, G.n_nonempty, tomb, d_out, cap, count);
+        const std::vector<RangeIn> sub(rs.begin() + G.r0, rs.begin() + G.r1);
+        return union_collected(ctx, sub, G.n_blocks, G.n_nonempty, tomb, d_out, cap, count);
+    }
     // one non-empty list per group, up to 64 groups, a result that surely fits: the tuned AND (ii2_intersect, look-back repeat included)
     if (!ctx->opt_intersect_ranges && n_groups <= MAX_LISTS) {
         const ii2_seg *hs[MAX_LISTS];
@@ -1043,6 +1097,24 @@ static int intersect_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint
     return intersect_groups(ctx, rs, gs, tomb, d_out, cap, count);
 }
 
+static int intersect_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                                     const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
+                                     uint64_t *count) {
+    if (n_groups == 0) { *count = 0; return II2_OK; }
+    std::vector<RangeIn> rs;
+    std::vector<GroupIn> gs;
+    uint64_t n_blocks = 0;
+    if (int rc = collect_groups(ctx, "ii2_intersect_ranges", n_groups, group_first, segs, list_first, list_end, rs, gs, &n_blocks)) return rc;
+    for (const GroupIn &G : gs) if (!G.n_blocks) { *count = 0; return II2_OK; }
+    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_intersect_ranges: more than 2^32 - 2 blocks in one call");
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_intersect_ranges: output buffer is NULL");
+    if (int rc = group_sizes(ctx, rs, gs)) return rc;
+    uint32_t clo, chi;
+    common_span(gs, &clo, &chi);
+    if (clo > chi) { *count = 0; return II2_OK; }
+    return intersect_sized(ctx, rs, gs, tomb, d_out, cap, count);
+}
+
 extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
                                     const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                                     uint64_t *count) {
@@ -1050,6 +1122,186 @@ extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint6
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
+}
+
+// ---- AND of ORs minus excluded groups -----------------------------------------------------------------
+// The one-launch form (setop_groups.hip): the non-empty lists of the required groups, group by group, then the excluded lists
+// that count, when they are at most MAX_LISTS lists of SMALL_SET_POSTINGS postings in SMALL_SET_BLOCKS blocks and the result
+// surely fits.  *taken = false when the query is too large (or option andnot.small is 0).
+static int andnot_small(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std::vector<GroupIn> &req, const std::vector<RangeIn> &rx,
+                        const IrPass &ex, uint64_t shortest, const SetOut &o, bool *taken) {
+    *taken = false;
+    if (!ctx->opt_andnot_small || o.cap < shortest || req.size() > MAX_LISTS) return II2_OK;
+    GroupSetParams gp;
+    std::memset(&gp, 0, sizeof gp);
+    uint32_t m = 0, nb = 0;
+    uint64_t sum = 0;
+    bool fits = true;
+    auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
+        const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1], c = s->h_cnt[j];
+        // (every block of a list but its last is full: what the kernel's layout of the decoded blocks relies on)
+        if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || c > (uint64_t)(b1 - b0) * II2_DV1_BLOCK ||
+            c + II2_DV1_BLOCK <= (uint64_t)(b1 - b0) * II2_DV1_BLOCK) {
+            fits = false;
+            return;
+        }
+        gp.lists[m] = ListView{s->d_skip + b0, s->d_payload, s->d_last_doc + j, b1 - b0, 0u};
+        gp.blk_base[m] = nb;
+        gp.lpre[m] = (uint32_t)sum;
+        gp.tag[m] = (uint8_t)tag;
+        m++;
+        nb += b1 - b0;
+        sum += c;
+    };
+    for (size_t g = 0; g < req.size() && fits; g++)
+        for (size_t r = req[g].r0; r < req[g].r1 && fits; r++)
+            for (uint64_t j = rs[r].l0; j < rs[r].l1 && fits; j++)
+                if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) add(rs[r].seg, j, (uint32_t)g);
+    for (size_t r = ex.r0; r < ex.r1 && fits && ex.n_nonempty; r++)
+        for (uint64_t j = rx[r].l0; j < rx[r].l1 && fits; j++)
+            if (ir_list_counts(ex, rx[r].seg, j)) add(rx[r].seg, j, (uint32_t)req.size());
+    if (!fits) return II2_OK;
+    // The kernel ranks every id by one bisection per other list: its time grows with postings x lists, the general form's with
+    // the number of groups.  Measured (scripts/andnot_probe.py): at the kernel's capacity, 64 lists x 8000
+    // postings, 410 us against the general form's 165 - 180 (four groups).  Sweep, 2 required + 1 excluded group, 4 - 64 lists:
+    // ~60 us + 0.68 ns per posting x list against 133 - 145 us - the one-launch form wins every point up to postings x lists =
+    // 65 536 (1.3 - 2.2x), ties at ~130 000 and loses beyond.  The limit is deliberately below that crossover: the general
+    // form's wait was half as long on another machine of the same kind (63 - 68 us for three groups).
+    // (option andnot.small = 2 lifts the limit to the kernel's capacity: tests, measurements)
+    if (ctx->opt_andnot_small == 1 && sum * m > ANDNOT_SMALL_WORK) return II2_OK;
+    gp.blk_base[m] = nb;
+    gp.lpre[m] = (uint32_t)sum;
+    gp.n_lists = m;
+    gp.n_blocks = nb;
+    gp.n_req = (uint32_t)req.size();
+    set_out(gp, o);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    HIP_TRY(ctx, launch_setop_groups(gp, ctx->stream, e0, e1));
+    *taken = true;
+    return II2_OK;
+}
+
+static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                                  const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                                  uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!group_not) return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
+    if (n_groups == 0) { *count = 0; return II2_OK; }
+    // 1. everything checked before anything is launched or written
+    uint64_t n_req = 0;
+    for (uint64_t g = 0; g < n_groups; g++) {
+        if (group_not[g] > 1) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: a group_not flag is neither 0 nor 1");
+        n_req += group_not[g] ? 0u : 1u;
+    }
+    if (!n_req) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: no required group (the library has no doc universe to complement)");
+    std::vector<RangeIn> rs, rx;               // the ranges of all groups; those of the excluded groups, back to back: ONE logical group
+    std::vector<GroupIn> all, req;
+    uint64_t n_blocks = 0;
+    if (int rc = collect_groups(ctx, "ii2_andnot_ranges", n_groups, group_first, segs, list_first, list_end, rs, all, &n_blocks)) return rc;
+    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_andnot_ranges: more than 2^32 - 2 blocks in one call");
+    IrPass ex{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
+    for (uint64_t g = 0; g < n_groups; g++) {
+        if (!group_not[g]) {
+            if (!all[g].n_blocks) { *count = 0; return II2_OK; }       // a required group without postings
+            req.push_back(all[g]);
+        } else {                                                        // (an excluded group without postings adds nothing)
+            rx.insert(rx.end(), rs.begin() + all[g].r0, rs.begin() + all[g].r1);
+            ex.n_blocks += all[g].n_blocks;
+        }
+    }
+    ex.r1 = rx.size();
+    if (int rc = group_sizes(ctx, rs, req)) return rc;
+    // the common span of the REQUIRED groups only: an excluded group never narrows it
+    uint32_t clo, chi;
+    common_span(req, &clo, &chi);
+    if (clo > chi) { *count = 0; return II2_OK; }
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: output buffer is NULL");
+    uint64_t shortest = ~0ull;
+    bool req_known = true;
+    for (const GroupIn &G : req) { shortest = std::min(shortest, G.n_post); req_known = req_known && G.span_known; }
+    // 2. the excluded lists that count: non-empty, their doc span (where the host mirrors it) meeting the common span
+    ex.lo = clo;
+    ex.hi = chi;
+    uint32_t elo = 0xFFFFFFFFu, ehi = 0;
+    bool ex_known = true;
+    for (const RangeIn &q : rx) {
+        const ii2_seg *s = q.seg;
+        if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
+        const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+        ex_known = ex_known && mirrored;
+        for (uint64_t j = q.l0; j < q.l1; j++) {
+            if (!ir_list_counts(ex, s, j)) continue;
+            ex.n_nonempty++;
+            ex.n_post += s->h_cnt[j];
+            if (!mirrored) continue;
+            elo = std::min(elo, s->h_spans[3 * j]);
+            ehi = std::max(ehi, s->h_spans[3 * j + 2]);
+        }
+    }
+    if (ex.n_nonempty && ex_known) { ex.lo = std::max(clo, elo); ex.hi = std::min(chi, ehi); }     // (lo <= hi: every list that counts meets [clo, chi])
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    // 3. short lists: one launch
+    {
+        const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
+        bool taken = false;
+        if (int rc = andnot_small(ctx, rs, req, rx, ex, shortest, o, &taken)) return rc;
+        if (taken) {
+            if (int rc = read_count(ctx, o.d_count, count)) return rc;
+            if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_andnot_ranges: result does not fit the output buffer (nothing written)");
+            return II2_OK;
+        }
+    }
+    // 4. the required part through the AND chooser - straight into d_out when nothing is excluded and the result surely fits,
+    // else into the candidate array, which holds the shortest required group: neither a capacity error nor a partly written
+    // result can occur there (tombstones are applied here, once)
+    if (!ex.n_nonempty && cap >= shortest) return intersect_sized(ctx, rs, req, tomb, d_out, cap, count);
+    if (ctx->an_words < shortest + 1) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_an) (void)hipFree(ctx->d_an);
+        ctx->d_an = nullptr;
+        ctx->an_words = 0;
+        const size_t want = (size_t)((shortest + 1 + (shortest + 1) / 4 + 63) & ~63ull);
+        if (ii2::dm_malloc_retry((void **)&ctx->d_an, want * sizeof(uint32_t)) != hipSuccess)
+            return fail(ctx, II2_ENOMEM, "ii2_andnot_ranges: candidate allocation failed");
+        ctx->an_words = want;
+    }
+    uint64_t nc = 0;
+    if (int rc = intersect_sized(ctx, rs, req, tomb, ctx->d_an, shortest, &nc)) return rc;
+    // 5. one exclusion pass over the candidates into d_out, written only when all survivors fit
+    bool pass = nc && ex.n_nonempty;
+    if (pass && !req_known) {
+        // the candidates' span is not known from the host mirrors: their first and last id bound the mark's windows
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, ctx->d_an, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(hb + 1, ctx->d_an + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ex.lo = std::max(ex.lo, hb[0]);
+        ex.hi = std::min(ex.hi, hb[1]);
+        pass = ex.lo <= ex.hi;                      // (else no excluded list reaches a candidate)
+    }
+    if (pass) {
+        if (int rc = ir_filter_pass(ctx, "ii2_andnot_ranges", rx, ex, ctx->d_an, nc, d_out, cap, &nc)) return rc;
+        *count = nc;
+        if (nc > cap) return fail(ctx, II2_ECAPACITY, "ii2_andnot_ranges: result does not fit the output buffer (nothing written)");
+        return II2_OK;
+    }
+    // no candidate, or no excluded list that reaches one: the candidates are the result
+    *count = nc;
+    if (nc > cap) return fail(ctx, II2_ECAPACITY, "ii2_andnot_ranges: result does not fit the output buffer (nothing written)");
+    if (nc) {
+        HIP_TRY(ctx, hipMemcpyAsync(d_out, ctx->d_an, nc * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return II2_OK;
+}
+
+extern "C" int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                                 const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                                 uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return andnot_ranges_unlocked(ctx, n_groups, group_first, group_not, segs, list_first, list_end, tomb, d_out, cap, count);
 }
 
 // ---- many queries in one call ---------------------------------------------------------------------

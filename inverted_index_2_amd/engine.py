@@ -67,6 +67,29 @@ def pack_batch(queries):
     return op, query_first, segs, np.array(first, np.uint64), np.array(end, np.uint64)
 
 
+def pack_andnot(groups, exclude):
+    """The flat arrays ii2_andnot_ranges takes, from groups / exclude = [[(segment, first, end), ...], ...]: (group_first u64
+    [G + 1], group_not u8 [G], segments [R], list_first u64 [R], list_end u64 [R]) - the required groups first (flags 0), then the
+    excluded ones (flags 1); group g owns the ranges group_first[g] .. group_first[g + 1] - 1.  Pure host code: the segments are
+    passed through as they are."""
+    groups, exclude = list(groups), list(exclude)
+    n = len(groups) + len(exclude)
+    group_first = np.zeros(n + 1, np.uint64)
+    group_not = np.zeros(n, np.uint8)
+    group_not[len(groups):] = 1
+    segs, first, end = [], [], []
+    for g, ranges in enumerate(groups + exclude):
+        for s, a, b in ranges:
+            a, b = int(a), int(b)
+            if a < 0 or b < 0:
+                raise ValueError(f"group {g}: negative list index")
+            segs.append(s)
+            first.append(a)
+            end.append(b)
+        group_first[g + 1] = len(segs)
+    return group_first, group_not, segs, np.array(first, np.uint64), np.array(end, np.uint64)
+
+
 class DeviceArray:
     """A raw HBM buffer owned by a Context."""
 
@@ -349,6 +372,22 @@ class Context:
         cnt = C.c_uint64()
         self._ck(self.lib.ii2_intersect_ranges(self.h, len(groups), group_first, segs, first, end, tomb.h if tomb else None, _ptr(out),
                                                out.count, C.byref(cnt)))
+        return out, cnt.value
+
+    def andnot_ranges(self, groups, exclude, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
+        """AND of ORs minus excluded groups (ii2_andnot_ranges): groups and exclude are lists of groups as intersect_ranges takes
+        them; the ids found in at least one list of every group of `groups` and in no list of any group of `exclude`.  Returns
+        (DeviceArray ids, count); the default `out` holds 256 ids per block of the required group with the fewest blocks."""
+        group_first, group_not, gsegs, first, end = pack_andnot(groups, exclude)
+        n = len(gsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in gsegs])
+        if out is None:
+            blocks = [sum(s.range_blocks(int(a), int(b), self) for s, a, b in g) for g in groups]
+            out = self.empty(max(min(blocks, default=0) * 256, 1))
+        cnt = C.c_uint64()
+        self._ck(self.lib.ii2_andnot_ranges(self.h, len(group_not), group_first.ctypes.data_as(_lib.u64p), group_not.ctypes.data_as(_lib.u8p),
+                                            segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None,
+                                            _ptr(out), out.count, C.byref(cnt)))
         return out, cnt.value
 
     def query_batch(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):

@@ -61,6 +61,7 @@ def _lib_typed():
         lib.ii2h_read.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64, C.c_int, u64p]
         lib.ii2h_prefix_search.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         for f in ("ii2h_result_term_len", "ii2h_result_values_len"):
             getattr(lib, f).restype = C.c_uint64
@@ -197,6 +198,17 @@ class InvertedIndex(_Target):
         blob, off = _pack(list(terms))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect(self.h, blob.ctypes.data, off.ctypes.data, len(terms), C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
+        return out[: n.value].tolist()
+
+    def intersect_except(self, terms: List[bytes], exclude: List[bytes]) -> List[int]:
+        """ids under every term of `terms` and under no term of `exclude` (IntersectExcept: one ii2_andnot_ranges call)."""
+        blob, off = _pack(list(terms))
+        x_blob, x_off = _pack(list(exclude))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_except(self.h, blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data, x_off.ctypes.data,
+                                                len(exclude), C.byref(n)))
         out = np.zeros(max(n.value, 1), np.uint32)
         self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
         return out[: n.value].tolist()

@@ -15,6 +15,7 @@
 //   InvertedIndex.Put / Read / Merge / PutRemoved / PrefixSearch   inverted_index.go:41-340
 //   shardKey                                         shard.go:362-378
 //   Intersect(terms)                                 additive
+//   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
 //
 // Built as its own library (libii2_host.so) that only sees include/ii2.h and links libii2_hip.so:
 // the product library exports the C ABI and nothing else.  A small C facade (ii2h_*) at the bottom
@@ -864,6 +865,69 @@ class InvertedIndex {
         if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect");
         return ids;
     }
+    // additive: ids present under every term of `terms` and under none of `except` ("error AND db NOT healthcheck").  One group
+    // per term as Intersect builds them, the excluded terms' groups flagged, and ONE ii2_andnot_ranges call: no second query, no
+    // second download, no set difference on the host.  An excluded term found in no segment is dropped; a required one gives the
+    // empty result.  Like Intersect and Read, no tombstone filter.
+    std::vector<uint32_t> IntersectExcept(const std::vector<Term> &terms, const std::vector<Term> &except) const {
+        if (terms.empty()) return {};
+        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
+        std::vector<uint64_t> group_first{0};
+        std::vector<uint8_t> group_not;
+        std::vector<const ii2_seg *> segs;
+        std::vector<uint64_t> first, end;
+        // one one-list range per segment that holds the term; returns the term's postings bound (see Intersect), 0: in no segment
+        auto gather = [&](const Term &t) {
+            uint64_t post = 0;
+            if (Shard *sh = find_shard(shard_key(t))) {
+                for (auto &sg : sh->snapshot()) {
+                    const std::vector<Term> &T = sg->terms;
+                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
+                    if (j == T.size() || T[j] != t) continue;
+                    ii2_seg_info info;
+                    ii2_seg_get_info(sg->seg->h, &info);
+                    held.push_back(sg);
+                    segs.push_back(sg->seg->h);
+                    first.push_back(j);
+                    end.push_back(j + 1);
+                    post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
+                }
+            }
+            return post;
+        };
+        // the output's size: the smallest REQUIRED term's bound, as in Intersect (an exclusion only removes ids)
+        constexpr uint64_t FIRST_CAP = 1u << 22;
+        uint64_t bound = ~0ull;
+        for (auto &t : terms) {
+            const uint64_t post = gather(t);
+            if (!post) return {};                                // a required term in no segment: nothing is under every term
+            group_first.push_back(segs.size());
+            group_not.push_back(0);
+            bound = std::min(bound, post);
+        }
+        for (auto &t : except) {
+            if (!gather(t)) continue;                            // an excluded term in no segment removes nothing
+            group_first.push_back(segs.size());
+            group_not.push_back(1);
+        }
+        uint64_t cap = std::min(bound, FIRST_CAP), n = 0;
+        DevMem d_out(ctx_);
+        for (int attempt = 0;; attempt++) {
+            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect except");
+            const int rc = ii2_andnot_ranges(ctx_, group_not.size(), group_first.data(), group_not.data(), segs.data(), first.data(), end.data(),
+                                             nullptr, (uint32_t *)d_out.p, cap + 1, &n);
+            if (rc != II2_ECAPACITY || attempt) {
+                ck(ctx_, rc, "intersect except");
+                break;
+            }
+            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect except");
+            d_out.p = nullptr;
+            cap = n;
+        }
+        std::vector<uint32_t> ids(n);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
+        return ids;
+    }
     size_t ShardCount() const { std::lock_guard<std::mutex> g(mu_); return shards_.size(); }
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
 
@@ -1058,6 +1122,10 @@ int ii2h_prefix_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off
 }
 int ii2h_intersect(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->Intersect(unpack_terms(bytes, off, n)); *n_ids = t->ids.size(); })
+}
+int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
+                          uint64_t n_x, uint64_t *n_ids) {
+    H_TRY(t, { t->ids = t->index->IntersectExcept(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
 }
 int ii2h_removed_values(ii2h_target *t, uint64_t *n_ids) {
     H_TRY(t, { Shard *s = t->shard ? t->shard.get() : t->index->OnlyShard(); t->ids = s ? s->RemovedValues() : std::vector<uint32_t>(); *n_ids = t->ids.size(); })
