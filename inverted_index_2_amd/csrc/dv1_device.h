@@ -364,6 +364,11 @@ __device__ __forceinline__ uint32_t upper_bound_guess(Get get, uint32_t lo, uint
     return lo;
 }
 
+// doc id v is deleted: its bit of the tombstone bitmap (nwords words; null: nothing is deleted) is set
+__device__ __forceinline__ bool tomb_has(const uint32_t *tomb, uint32_t nwords, uint32_t v) {
+    return tomb && (v >> 5) < nwords && ((tomb[v >> 5] >> (v & 31u)) & 1u) != 0u;
+}
+
 __device__ __forceinline__ unsigned varint_len(uint32_t v) {
     return v < (1u << 7) ? 1u : v < (1u << 14) ? 2u : v < (1u << 21) ? 3u : v < (1u << 28) ? 4u : 5u;
 }

@@ -17,6 +17,8 @@
 //        span - the probe / mark filter with the flag turned round - or, without such a list, a copy.
 //   Many AND / OR queries in one call (ii2_query_batch): the small ones in one launch per size class (setop_batch.hip), the
 //        others one by one through the choosers above; all of them staged, then packed in query order.
+// The file is in that order, every section closed by its entry points (those of the AND and the OR chooser together, behind the
+// OR section: each of the two is also called by the sections below), the helpers that several sections share in front.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -42,6 +44,19 @@ struct SetOut {
 };
 }  // namespace
 
+// the kernels' view of list j of seg (its host block table is loaded)
+static ListView list_view(const ii2_seg *seg, uint64_t j) {
+    const uint32_t b0 = seg->h_blk_off[j], b1 = seg->h_blk_off[j + 1];
+    return ListView{seg->d_skip + b0, seg->d_payload, seg->d_last_doc + j, b1 - b0, 0u};
+}
+
+// the lists' doc spans were mirrored on the host when the segment was created
+static bool spans_mirrored(const ii2_seg *seg) { return seg->h_spans.size() == 3 * seg->n_lists; }
+
+// every block of a list of c postings in nb blocks but its last is full (what the one-workgroup kernels' layout of the decoded
+// blocks relies on)
+static bool blocks_full(uint32_t nb, uint64_t c) { return c <= (uint64_t)nb * II2_DV1_BLOCK && c + II2_DV1_BLOCK > (uint64_t)nb * II2_DV1_BLOCK; }
+
 // the n lists of a call, checked and viewed once (a union names every rejection "ii2_union: bad list")
 static int collect_lists(ii2_ctx *ctx, bool is_union, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, SetList *L) {
     for (uint32_t i = 0; i < n; i++) {
@@ -50,16 +65,18 @@ static int collect_lists(ii2_ctx *ctx, bool is_union, uint32_t n, const ii2_seg 
         if (!seg || idx >= seg->n_lists) return fail(ctx, II2_EINVAL, is_union ? "ii2_union: bad list" : "list index out of range");
         if (seg->device != ctx->device) return fail(ctx, II2_EINVAL, is_union ? "ii2_union: bad list" : "segment lives on another device");
         if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
-        const uint32_t b0 = seg->h_blk_off[idx], b1 = seg->h_blk_off[idx + 1];
-        L[i] = SetList{ListView{seg->d_skip + b0, seg->d_payload, seg->d_last_doc + idx, b1 - b0, 0u}, seg, idx};
+        L[i] = SetList{list_view(seg, idx), seg, idx};
     }
     return II2_OK;
 }
 
-// the output and tombstone fields of every kernel's parameters
+// the tombstone fields, and with them the output fields, of every kernel's parameters
+template <class P> static void set_tomb(P &p, const ii2_tomb *tomb) {
+    p.tomb = tomb ? tomb->d_words : nullptr;
+    p.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
+}
 template <class P> static void set_out(P &p, const SetOut &o) {
-    p.tomb = o.tomb ? o.tomb->d_words : nullptr;
-    p.tomb_nwords = o.tomb ? (uint32_t)std::min<uint64_t>(o.tomb->n_words, 0xFFFFFFFFull) : 0;
+    set_tomb(p, o.tomb);
     p.out = o.d_out;
     p.out_cap = o.cap;
     p.d_count = o.d_count;
@@ -90,7 +107,7 @@ template <class P> static int fill_concat(ii2_ctx *ctx, const SetList *L, uint32
 static int list_span(ii2_ctx *ctx, const SetList &l, ii2_seg::ListSpan *out) {
     const ii2_seg *seg = l.seg;
     const uint64_t idx = l.idx;
-    if (seg->h_spans.size() == 3 * seg->n_lists && idx < seg->n_lists) {      // mirrored when the segment was created: no fetch, no sync
+    if (spans_mirrored(seg) && idx < seg->n_lists) {      // mirrored when the segment was created: no fetch, no sync
         *out = ii2_seg::ListSpan{seg->h_spans[3 * idx], seg->h_spans[3 * idx + 1], seg->h_spans[3 * idx + 2]};
         return II2_OK;
     }
@@ -109,6 +126,31 @@ static int list_span(ii2_ctx *ctx, const SetList &l, ii2_seg::ListSpan *out) {
     *out = ii2_seg::ListSpan{e[0].first_doc, e[1].first_doc, last};
     std::lock_guard<std::mutex> sg(seg->span_mu);
     seg->span_cache[idx] = *out;
+    return II2_OK;
+}
+
+// The grow-only per-context blocks.  A device block that holds `have` units and must hold `need`: the stream is waited for, the
+// block freed and `want` >= need units of unit_bytes allocated (`err`: the text of II2_ENOMEM) ...
+template <class T> static int grow_device(ii2_ctx *ctx, T **block, size_t *have, size_t need, size_t want, size_t unit_bytes, const char *err) {
+    if (*have >= need) return II2_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*block) (void)hipFree(*block);
+    *block = nullptr;
+    *have = 0;
+    if (ii2::dm_malloc_retry((void **)block, want * unit_bytes) != hipSuccess) return fail(ctx, II2_ENOMEM, err);
+    *have = want;
+    return II2_OK;
+}
+// ... and a pinned one of `bytes` (a quarter more is taken); sync: the stream may still be copying from the old block
+static int grow_pinned(ii2_ctx *ctx, void **block, size_t *cap, size_t bytes, bool sync, const char *err) {
+    if (*cap >= bytes) return II2_OK;
+    if (sync) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*block) (void)hipHostFree(*block);
+    *block = nullptr;
+    *cap = 0;
+    const size_t want = align_up(bytes + bytes / 4, 1 << 16);
+    if (hipHostMalloc(block, want) != hipSuccess) return fail(ctx, II2_ENOMEM, err);
+    *cap = want;
     return II2_OK;
 }
 
@@ -323,6 +365,37 @@ static int intersect_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *se
     return II2_OK;
 }
 
+// ii2_intersect with ctx->mu held (ii2_intersect_ranges hands single-list groups to it)
+static int intersect_sync(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out,
+                          uint64_t cap, uint64_t *count) {
+    // the count lands in the pinned host mailbox directly (the kernels write it once, at their end): one stream
+    // synchronisation, no copy behind it
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
+    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
+    int rc = intersect_unlocked(ctx, n, segs, list_idx, o);
+    if (rc) return rc;
+    const uint32_t own = ctx->lb_pending;           // epoch of this call's one-launch AND (0: it took another path)
+    ctx->lb_pending = 0;
+    if (own) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_OWN, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = read_count(ctx, o.d_count, count))) return rc;
+    lb_fold_pending(ctx);
+    if (own && (*count == ~0ull || ctx->h_mail[II2_MAIL_LB_OWN] == own)) {
+        // a bounded wait of the one-launch two-list AND ran out (its workgroups did not start in index order; the count is all
+        // ones, or looks valid when the workgroup gave up after the last one had stored it): nothing is wrong with the inputs —
+        // the same query again through the two-kernel form, which has no inter-workgroup waits
+        ctx->lb_fallbacks++;
+        const int64_t keep = ctx->opt_intersect_and2;
+        ctx->opt_intersect_and2 = 2;
+        rc = intersect_unlocked(ctx, n, segs, list_idx, o);
+        ctx->opt_intersect_and2 = keep;
+        if (rc) return rc;
+        if ((rc = read_count(ctx, o.d_count, count))) return rc;
+    }
+    if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_intersect: result does not fit the output buffer (content unspecified)");
+    return II2_OK;
+}
+
 // ---- OR -------------------------------------------------------------------------------------
 // Few long lists, the longest one dense: the streaming kernel of the dense intersection with OR semantics - every wave
 // walks its own run of blocks of the longest list (the pacer), the other lists mark into the same bitmap
@@ -437,81 +510,6 @@ static int union_unlocked(ii2_ctx *ctx, const SetList *all, uint32_t n, const Se
     return II2_OK;
 }
 
-static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t blocks_ub, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
-                       uint64_t *count);
-static int intersect_sync(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out,
-                          uint64_t cap, uint64_t *count);
-
-extern "C" {
-
-int ii2_intersect_async(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
-                        const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *d_count) {
-    if (!ctx) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return intersect_unlocked(ctx, n, segs, list_idx, SetOut{tomb, d_out, cap, d_count});
-}
-
-int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
-                  const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (!ctx || !count) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return intersect_sync(ctx, n, segs, list_idx, tomb, d_out, cap, count);
-}
-
-}  // extern "C"
-
-// ii2_intersect with ctx->mu held (ii2_intersect_ranges hands single-list groups to it)
-static int intersect_sync(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb, uint32_t *d_out,
-                          uint64_t cap, uint64_t *count) {
-    // the count lands in the pinned host mailbox directly (the kernels write it once, at their end): one stream
-    // synchronisation, no copy behind it
-    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
-    const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
-    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
-    int rc = intersect_unlocked(ctx, n, segs, list_idx, o);
-    if (rc) return rc;
-    const uint32_t own = ctx->lb_pending;           // epoch of this call's one-launch AND (0: it took another path)
-    ctx->lb_pending = 0;
-    if (own) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_mail + II2_MAIL_LB_OWN, ctx->d_lb, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = read_count(ctx, o.d_count, count))) return rc;
-    lb_fold_pending(ctx);
-    if (own && (*count == ~0ull || ctx->h_mail[II2_MAIL_LB_OWN] == own)) {
-        // a bounded wait of the one-launch two-list AND ran out (its workgroups did not start in index order; the count is all
-        // ones, or looks valid when the workgroup gave up after the last one had stored it): nothing is wrong with the inputs —
-        // the same query again through the two-kernel form, which has no inter-workgroup waits
-        ctx->lb_fallbacks++;
-        const int64_t keep = ctx->opt_intersect_and2;
-        ctx->opt_intersect_and2 = 2;
-        rc = intersect_unlocked(ctx, n, segs, list_idx, o);
-        ctx->opt_intersect_and2 = keep;
-        if (rc) return rc;
-        if ((rc = read_count(ctx, o.d_count, count))) return rc;
-    }
-    if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_intersect: result does not fit the output buffer (content unspecified)");
-    return II2_OK;
-}
-
-extern "C" {
-
-int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
-              uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (!ctx || !count) return II2_EINVAL;
-    std::lock_guard<std::mutex> g(ctx->mu);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n == 0 || n > MAX_LISTS || !segs) return fail(ctx, II2_EINVAL, "ii2_union: list count must be 1..64");
-    SetList L[MAX_LISTS];
-    if (int rc = collect_lists(ctx, true, n, segs, list_idx, L)) return rc;
-    uint64_t blocks_ub = 0;
-    for (uint32_t i = 0; i < n; i++) blocks_ub += L[i].v.nblk;
-    if (!blocks_ub) { *count = 0; return II2_OK; }
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union: output buffer is NULL");
-    return union_lists(ctx, L, n, blocks_ub, tomb, d_out, cap, count);
-}
-
-}  // extern "C"
-
 // OR of n collected lists (blocks_ub > 0 blocks in all) through the chooser, else the merge passes; ctx->mu held
 static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t blocks_ub, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                        uint64_t *count) {
@@ -537,6 +535,43 @@ static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t bloc
     *count = st.n_out;
     return II2_OK;
 }
+
+// ---- the entry points of the two choosers ------------------------------------------------------
+extern "C" {
+
+int ii2_intersect_async(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
+                        const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *d_count) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return intersect_unlocked(ctx, n, segs, list_idx, SetOut{tomb, d_out, cap, d_count});
+}
+
+int ii2_intersect(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx,
+                  const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return intersect_sync(ctx, n, segs, list_idx, tomb, d_out, cap, count);
+}
+
+int ii2_union(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *segs, const uint64_t *list_idx, const ii2_tomb *tomb,
+              uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0 || n > MAX_LISTS || !segs) return fail(ctx, II2_EINVAL, "ii2_union: list count must be 1..64");
+    SetList L[MAX_LISTS];
+    if (int rc = collect_lists(ctx, true, n, segs, list_idx, L)) return rc;
+    uint64_t blocks_ub = 0;
+    for (uint32_t i = 0; i < n; i++) blocks_ub += L[i].v.nblk;
+    if (!blocks_ub) { *count = 0; return II2_OK; }
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union: output buffer is NULL");
+    return union_lists(ctx, L, n, blocks_ub, tomb, d_out, cap, count);
+}
+
+}  // extern "C"
+
 // ---- OR of list ranges ------------------------------------------------------------------------
 // one range of a call, checked: lists [l0, l1) of seg own its blocks [b0, b1)
 struct RangeIn {
@@ -565,13 +600,8 @@ static int um_scratch_reserve(ii2_ctx *ctx, const char *who, uint64_t span, uint
     const uint64_t n_sum_call = (std::min(span, W) + 65535) / 65536;
     const size_t words = n_sum_call * 2048 + n_sum_call;
     if (ctx->um_bits_words >= words) return II2_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
-    ctx->d_um_bits = nullptr;
-    ctx->um_bits_words = 0;
-    if (ii2::dm_malloc_retry((void **)&ctx->d_um_bits, words * sizeof(uint32_t)) != hipSuccess)
-        return fail(ctx, II2_ENOMEM, (std::string(who) + ": scratch allocation failed").c_str());
-    ctx->um_bits_words = words;
+    if (int rc = grow_device(ctx, &ctx->d_um_bits, &ctx->um_bits_words, words, words, sizeof(uint32_t), (std::string(who) + ": scratch allocation failed").c_str()))
+        return rc;
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, words * sizeof(uint32_t), ctx->stream));
     return II2_OK;
 }
@@ -602,6 +632,37 @@ static int collect_ranges(ii2_ctx *ctx, const char *who, uint64_t n, const ii2_s
     return II2_OK;
 }
 
+// the block-wise descriptors of rs[r0, r1) (union_many.hip): UmRange[r1 - r0], then the exclusive block prefix [r1 - r0 + 1]
+static size_t um_desc_bytes(size_t nr) { return align_up(nr * sizeof(UmRange)) + align_up((nr + 1) * sizeof(uint32_t)); }
+static void um_desc_fill(const std::vector<RangeIn> &rs, size_t r0, size_t r1, uint8_t *h) {
+    const size_t nr = r1 - r0;
+    UmRange *hr = (UmRange *)h;
+    uint32_t *hpre = (uint32_t *)(h + align_up(nr * sizeof(UmRange)));
+    uint32_t acc = 0;
+    for (size_t r = 0; r < nr; r++) {
+        const RangeIn &q = rs[r0 + r];
+        const ii2_seg *s = q.seg;
+        hr[r] = UmRange{s->d_skip, s->d_payload, s->d_blk_list, s->d_last_doc, q.b0, q.b1, (uint32_t)q.l0, (uint32_t)q.l1};
+        hpre[r] = acc;
+        acc += q.b1 - q.b0;
+    }
+    hpre[nr] = acc;
+}
+
+// the window fields of the block-wise paths' parameters: `docs` docs from wlo on, in the per-context bitmap + summary
+static void um_set_window(const ii2_ctx *ctx, UnionManyParams &p, uint64_t wlo, uint64_t docs) {
+    p.win_lo = (uint32_t)wlo;
+    p.win_docs = (uint32_t)docs;
+    p.n_sum = (uint32_t)((docs + 65535) / 65536);
+    p.bitmap = ctx->d_um_bits;
+    p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+}
+// query blocks per wave of the mark kernel
+static uint32_t um_per_wave(const ii2_ctx *ctx, uint64_t n_blocks) {
+    const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
+    return (uint32_t)std::max<uint64_t>(1, (n_blocks + target_waves - 1) / target_waves);
+}
+
 // The block-wise OR (union_many.hip) of the ranges' blocks: per window of the doc range mark, count, scan, compact.
 static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                       uint64_t *count) {
@@ -609,31 +670,15 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     const size_t nr = rs.size();
     if (int rc = um_scratch_clean(ctx)) return rc;
     // range descriptors + block prefix: thousands of entries, through a grow-only pinned block
-    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), stage_bytes = desc_bytes + align_up((nr + 1) * sizeof(uint32_t));
-    if (ctx->h_um_cap < stage_bytes) {
-        if (ctx->h_um) (void)hipHostFree(ctx->h_um);
-        ctx->h_um = nullptr;
-        ctx->h_um_cap = 0;
-        const size_t want = align_up(stage_bytes + stage_bytes / 4, 1 << 16);
-        if (hipHostMalloc(&ctx->h_um, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_union_ranges: staging allocation failed");
-        ctx->h_um_cap = want;
-    }
-    UmRange *hr = (UmRange *)ctx->h_um;
-    uint32_t *hpre = (uint32_t *)((uint8_t *)ctx->h_um + desc_bytes);
-    uint32_t acc = 0;
-    for (size_t r = 0; r < nr; r++) {
-        const ii2_seg *s = rs[r].seg;
-        hr[r] = UmRange{s->d_skip, s->d_payload, s->d_blk_list, s->d_last_doc, rs[r].b0, rs[r].b1, (uint32_t)rs[r].l0, (uint32_t)rs[r].l1};
-        hpre[r] = acc;
-        acc += rs[r].b1 - rs[r].b0;
-    }
-    hpre[nr] = acc;
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), stage_bytes = um_desc_bytes(nr);
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes, false, "ii2_union_ranges: staging allocation failed")) return rc;
+    um_desc_fill(rs, 0, nr, (uint8_t *)ctx->h_um);
     // the doc range: from the lists' mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
     bool mirrored = true;
     for (const RangeIn &q : rs) {
         const ii2_seg *s = q.seg;
-        if (s->h_spans.size() != 3 * s->n_lists) { mirrored = false; break; }
+        if (!spans_mirrored(s)) { mirrored = false; break; }
         for (uint64_t j = q.l0; j < q.l1; j++) {
             if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
             lo = std::min(lo, s->h_spans[3 * j]);
@@ -678,27 +723,20 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     if (int rc = um_scratch_reserve(ctx, "ii2_union_ranges", span, W)) return rc;
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
     p.d_count = d_cnt ? d_cnt : ctx->d_mail;
-    p.tomb = tomb ? tomb->d_words : nullptr;
-    p.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
+    set_tomb(p, tomb);
     p.out = d_out;
     p.out_cap = cap;
     p.check_window = n_win > 1 ? 1u : 0u;
     p.no_atomics = ctx->opt_union_many_no_atomics ? 1u : 0u;
-    const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
-    p.per_wave = (uint32_t)std::max<uint64_t>(1, (n_blocks + target_waves - 1) / target_waves);
+    p.per_wave = um_per_wave(ctx, n_blocks);
     // several windows whose result may not fit: count first (nothing written), then write
     const bool count_first = n_win > 1 && cap < n_blocks * II2_DV1_BLOCK;
     for (int pass = count_first ? 0 : 1; pass < 2; pass++) {
         p.write = (uint32_t)pass;
         for (uint64_t w = 0; w < n_win; w++) {
             const uint64_t wlo = base + w * W;
-            const uint64_t docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1);
             p.window = (uint32_t)w;
-            p.win_lo = (uint32_t)wlo;
-            p.win_docs = (uint32_t)docs;
-            p.n_sum = (uint32_t)((docs + 65535) / 65536);
-            p.bitmap = ctx->d_um_bits;
-            p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+            um_set_window(ctx, p, wlo, std::min<uint64_t>(W, (uint64_t)hi - wlo + 1));
             const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 1 + 3) / 4, (uint64_t)ctx->cu_count * 8u);
             hipEvent_t e0 = nullptr, e1 = nullptr;
             ii2_profile_pair(ctx, &e0, &e1);
@@ -712,21 +750,6 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
         if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_union_ranges: result does not fit the output buffer (nothing written)");
     }
     return II2_OK;
-}
-
-static int union_collected(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, uint64_t n_nonempty, const ii2_tomb *tomb,
-                           uint32_t *d_out, uint64_t cap, uint64_t *count);
-
-static int union_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
-                                 const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad argument");
-    std::vector<RangeIn> rs;
-    uint64_t n_blocks = 0, n_nonempty = 0;
-    if (int rc = collect_ranges(ctx, "ii2_union_ranges", n, segs, list_first, list_end, rs, &n_blocks, &n_nonempty)) return rc;
-    if (!n_blocks) { *count = 0; return II2_OK; }
-    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_union_ranges: more than 2^32 - 2 blocks in one call");
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union_ranges: output buffer is NULL");
-    return union_collected(ctx, rs, n_blocks, n_nonempty, tomb, d_out, cap, count);
 }
 
 // OR of collected ranges (n_blocks > 0 blocks, n_nonempty non-empty lists) into d_out, all or nothing
@@ -743,13 +766,25 @@ static int union_collected(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_
             for (uint64_t j = q.l0; j < q.l1; j++) {
                 const uint32_t b0 = q.seg->h_blk_off[j], b1 = q.seg->h_blk_off[j + 1];
                 if (b1 == b0) continue;
-                L[m++] = SetList{ListView{q.seg->d_skip + b0, q.seg->d_payload, q.seg->d_last_doc + j, b1 - b0, 0u}, q.seg, j};
+                L[m++] = SetList{list_view(q.seg, j), q.seg, j};
                 n_post += cap < n_blocks * II2_DV1_BLOCK ? q.seg->h_cnt[j] : (uint64_t)(b1 - b0) * II2_DV1_BLOCK;
             }
         }
         if (cap >= n_post) return union_lists(ctx, L, m, n_blocks, tomb, d_out, cap, count);
     }
     return union_many(ctx, rs, n_blocks, tomb, d_out, cap, count);
+}
+
+static int union_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_union_ranges: bad argument");
+    std::vector<RangeIn> rs;
+    uint64_t n_blocks = 0, n_nonempty = 0;
+    if (int rc = collect_ranges(ctx, "ii2_union_ranges", n, segs, list_first, list_end, rs, &n_blocks, &n_nonempty)) return rc;
+    if (!n_blocks) { *count = 0; return II2_OK; }
+    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_union_ranges: more than 2^32 - 2 blocks in one call");
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_union_ranges: output buffer is NULL");
+    return union_collected(ctx, rs, n_blocks, n_nonempty, tomb, d_out, cap, count);
 }
 
 extern "C" int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
@@ -772,33 +807,9 @@ struct GroupIn {
 // the pinned staging block of the group path's descriptors: `bytes` of it, once the stream has passed the last copy from it
 static int ir_stage(ii2_ctx *ctx, size_t bytes, uint8_t **h) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (a no-op after the count read that ends every step)
-    if (ctx->h_ir_cap < bytes) {
-        if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
-        ctx->h_ir = nullptr;
-        ctx->h_ir_cap = 0;
-        const size_t want = align_up(bytes + bytes / 4, 1 << 16);
-        if (hipHostMalloc(&ctx->h_ir, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_intersect_ranges: staging allocation failed");
-        ctx->h_ir_cap = want;
-    }
+    if (int rc = grow_pinned(ctx, &ctx->h_ir, &ctx->h_ir_cap, bytes, false, "ii2_intersect_ranges: staging allocation failed")) return rc;
     *h = (uint8_t *)ctx->h_ir;
     return II2_OK;
-}
-
-// the block-wise descriptors of rs[r0, r1) (union_many.hip): UmRange[r1 - r0], then the exclusive block prefix [r1 - r0 + 1]
-static size_t um_desc_bytes(size_t nr) { return align_up(nr * sizeof(UmRange)) + align_up((nr + 1) * sizeof(uint32_t)); }
-static void um_desc_fill(const std::vector<RangeIn> &rs, size_t r0, size_t r1, uint8_t *h) {
-    const size_t nr = r1 - r0;
-    UmRange *hr = (UmRange *)h;
-    uint32_t *hpre = (uint32_t *)(h + align_up(nr * sizeof(UmRange)));
-    uint32_t acc = 0;
-    for (size_t r = 0; r < nr; r++) {
-        const RangeIn &q = rs[r0 + r];
-        const ii2_seg *s = q.seg;
-        hr[r] = UmRange{s->d_skip, s->d_payload, s->d_blk_list, s->d_last_doc, q.b0, q.b1, (uint32_t)q.l0, (uint32_t)q.l1};
-        hpre[r] = acc;
-        acc += q.b1 - q.b0;
-    }
-    hpre[nr] = acc;
 }
 
 // one filter pass of the group path: the group's ranges rs[r0, r1) with their sizes, the doc span the mark's windows cover, and
@@ -814,7 +825,7 @@ struct IrPass {
 // span meets [lo, hi] (a list elsewhere removes nothing)
 static bool ir_list_counts(const IrPass &G, const ii2_seg *s, uint64_t j) {
     if (s->h_blk_off[j + 1] == s->h_blk_off[j]) return false;
-    if (!G.drop || s->h_spans.size() != 3 * s->n_lists) return true;
+    if (!G.drop || !spans_mirrored(s)) return true;
     return s->h_spans[3 * j] <= G.hi && s->h_spans[3 * j + 2] >= G.lo;
 }
 
@@ -840,7 +851,7 @@ static int ir_filter_pass(ii2_ctx *ctx, const char *who, const std::vector<Range
         IrList *hl = (IrList *)h;
         for (size_t r = G.r0; r < G.r1; r++) {
             const ii2_seg *s = rs[r].seg;
-            const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+            const bool mirrored = spans_mirrored(s);
             for (uint64_t j = rs[r].l0; j < rs[r].l1 && m < G.n_nonempty; j++) {
                 if (!ir_list_counts(G, s, j)) continue;
                 const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1];
@@ -881,16 +892,10 @@ static int ir_filter_pass(ii2_ctx *ctx, const char *who, const std::vector<Range
         p.n_ranges = (uint32_t)nr;
         p.n_blocks = (uint32_t)G.n_blocks;
         p.check_window = 1u;                        // blocks outside the candidates' span are not decoded
-        const uint64_t target_waves = (uint64_t)ctx->cu_count * 32u;
-        p.per_wave = (uint32_t)std::max<uint64_t>(1, (G.n_blocks + target_waves - 1) / target_waves);
+        p.per_wave = um_per_wave(ctx, G.n_blocks);
         ctx->um_dirty = true;
         for (uint64_t wlo = base; wlo <= G.hi; wlo += W) {
-            const uint64_t docs = std::min<uint64_t>(W, (uint64_t)G.hi - wlo + 1);
-            p.win_lo = (uint32_t)wlo;
-            p.win_docs = (uint32_t)docs;
-            p.n_sum = (uint32_t)((docs + 65535) / 65536);
-            p.bitmap = ctx->d_um_bits;
-            p.summary = ctx->d_um_bits + (size_t)p.n_sum * 2048;
+            um_set_window(ctx, p, wlo, std::min<uint64_t>(W, (uint64_t)G.hi - wlo + 1));
             ip.win_lo = p.win_lo;
             ip.win_docs = p.win_docs;
             ip.n_sum = p.n_sum;
@@ -976,16 +981,8 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
     size_t drv = 0;
     for (size_t g = 1; g < gs.size(); g++) if (gs[g].n_post < gs[drv].n_post) drv = g;
     const uint64_t half = (gs[drv].n_post + 64) & ~63ull;
-    if (ctx->ir_words < 2 * half) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (ctx->d_ir) (void)hipFree(ctx->d_ir);
-        ctx->d_ir = nullptr;
-        ctx->ir_words = 0;
-        const size_t want = 2 * half + half / 2;
-        if (ii2::dm_malloc_retry((void **)&ctx->d_ir, want * sizeof(uint32_t)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "ii2_intersect_ranges: candidate allocation failed");
-        ctx->ir_words = want;
-    }
+    if (int rc = grow_device(ctx, &ctx->d_ir, &ctx->ir_words, 2 * half, 2 * half + half / 2, sizeof(uint32_t), "ii2_intersect_ranges: candidate allocation failed"))
+        return rc;
     uint32_t *buf[2] = {ctx->d_ir, ctx->d_ir + half};
     uint64_t nc = 0;
     {
@@ -1043,7 +1040,7 @@ static int group_sizes(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::vector
         for (size_t r = G.r0; r < G.r1; r++) {
             const ii2_seg *s = rs[r].seg;
             if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
-            const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+            const bool mirrored = spans_mirrored(s);
             G.span_known = G.span_known && mirrored;
             for (uint64_t j = rs[r].l0; j < rs[r].l1; j++) {
                 if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
@@ -1139,13 +1136,11 @@ static int andnot_small(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std:
     bool fits = true;
     auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
         const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1], c = s->h_cnt[j];
-        // (every block of a list but its last is full: what the kernel's layout of the decoded blocks relies on)
-        if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || c > (uint64_t)(b1 - b0) * II2_DV1_BLOCK ||
-            c + II2_DV1_BLOCK <= (uint64_t)(b1 - b0) * II2_DV1_BLOCK) {
+        if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || !blocks_full(b1 - b0, c)) {
             fits = false;
             return;
         }
-        gp.lists[m] = ListView{s->d_skip + b0, s->d_payload, s->d_last_doc + j, b1 - b0, 0u};
+        gp.lists[m] = list_view(s, j);
         gp.blk_base[m] = nb;
         gp.lpre[m] = (uint32_t)sum;
         gp.tag[m] = (uint8_t)tag;
@@ -1227,7 +1222,7 @@ static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_
     for (const RangeIn &q : rx) {
         const ii2_seg *s = q.seg;
         if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
-        const bool mirrored = s->h_spans.size() == 3 * s->n_lists;
+        const bool mirrored = spans_mirrored(s);
         ex_known = ex_known && mirrored;
         for (uint64_t j = q.l0; j < q.l1; j++) {
             if (!ir_list_counts(ex, s, j)) continue;
@@ -1255,16 +1250,9 @@ static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_
     // else into the candidate array, which holds the shortest required group: neither a capacity error nor a partly written
     // result can occur there (tombstones are applied here, once)
     if (!ex.n_nonempty && cap >= shortest) return intersect_sized(ctx, rs, req, tomb, d_out, cap, count);
-    if (ctx->an_words < shortest + 1) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_an) (void)hipFree(ctx->d_an);
-        ctx->d_an = nullptr;
-        ctx->an_words = 0;
-        const size_t want = (size_t)((shortest + 1 + (shortest + 1) / 4 + 63) & ~63ull);
-        if (ii2::dm_malloc_retry((void **)&ctx->d_an, want * sizeof(uint32_t)) != hipSuccess)
-            return fail(ctx, II2_ENOMEM, "ii2_andnot_ranges: candidate allocation failed");
-        ctx->an_words = want;
-    }
+    if (int rc = grow_device(ctx, &ctx->d_an, &ctx->an_words, shortest + 1, (size_t)((shortest + 1 + (shortest + 1) / 4 + 63) & ~63ull), sizeof(uint32_t),
+                             "ii2_andnot_ranges: candidate allocation failed"))
+        return rc;
     uint64_t nc = 0;
     if (int rc = intersect_sized(ctx, rs, req, tomb, ctx->d_an, shortest, &nc)) return rc;
     // 5. one exclusion pass over the candidates into d_out, written only when all survivors fit
@@ -1322,25 +1310,9 @@ enum { BP_EMPTY = 0, BP_TINY = 1, BP_SMALL = 2, BP_LARGE = 3 };
 // grow-only blocks of the batch path: the device block (never the bump workspace: the large queries of a batch reserve from that)
 // and the pinned one
 static int batch_reserve(ii2_ctx *ctx, size_t dev_bytes, size_t host_bytes) {
-    if (ctx->batch_cap < dev_bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_batch) (void)hipFree(ctx->d_batch);
-        ctx->d_batch = nullptr;
-        ctx->batch_cap = 0;
-        const size_t want = align_up(dev_bytes + dev_bytes / 4, 1 << 20);
-        if (ii2::dm_malloc_retry((void **)&ctx->d_batch, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_query_batch: staging allocation failed");
-        ctx->batch_cap = want;
-    }
-    if (ctx->h_batch_cap < host_bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
-        ctx->h_batch = nullptr;
-        ctx->h_batch_cap = 0;
-        const size_t want = align_up(host_bytes + host_bytes / 4, 1 << 16);
-        if (hipHostMalloc(&ctx->h_batch, want) != hipSuccess) return fail(ctx, II2_ENOMEM, "ii2_query_batch: pinned staging allocation failed");
-        ctx->h_batch_cap = want;
-    }
-    return II2_OK;
+    if (int rc = grow_device(ctx, &ctx->d_batch, &ctx->batch_cap, dev_bytes, align_up(dev_bytes + dev_bytes / 4, 1 << 20), 1, "ii2_query_batch: staging allocation failed"))
+        return rc;
+    return grow_pinned(ctx, &ctx->h_batch, &ctx->h_batch_cap, host_bytes, true, "ii2_query_batch: pinned staging allocation failed");
 }
 
 static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
@@ -1392,9 +1364,9 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
                 post += c;
                 shortest = std::min<uint64_t>(shortest, c);
                 if (is_union && nb == 0) continue;
-                if (nb == 0 || c > (uint64_t)nb * II2_DV1_BLOCK || c + II2_DV1_BLOCK <= (uint64_t)nb * II2_DV1_BLOCK) regular = false;
+                if (nb == 0 || !blocks_full(nb, c)) regular = false;
                 if (pl.nl <= MAX_LISTS) {              // (an OR of more lists is a large query: it goes by its ranges)
-                    lists.push_back(SetList{ListView{seg->d_skip + bo[j], seg->d_payload, seg->d_last_doc + j, nb, 0u}, seg, j});
+                    lists.push_back(SetList{list_view(seg, j), seg, j});
                     pl.nl++;
                 }
             }
@@ -1477,8 +1449,7 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
         std::memset(&bp, 0, sizeof bp);
         bp.queries = (const BatchQuery *)d;
         bp.lists = (const BatchList *)(d + o_lists);
-        bp.tomb = tomb ? tomb->d_words : nullptr;
-        bp.tomb_nwords = tomb ? (uint32_t)std::min<uint64_t>(tomb->n_words, 0xFFFFFFFFull) : 0;
+        set_tomb(bp, tomb);
         bp.n_tiny = n_kind[BP_TINY];
         bp.n_small = n_kind[BP_SMALL];
         bp.stage = d_stage;

@@ -4,19 +4,18 @@
 // per OR — and short lists are what most terms of a real dictionary have (PrefixSearch, inverted_index.go:274-292,
 // unions the lists of every matching term).
 //
-//   1. every workgroup decodes all blocks into its LDS, one wave per block (redundant across workgroups, but cheaper than
-//      a second launch); the host knows every list's size, so list j is one ascending stretch raw[lpre[j] ...];
-//   2. an id's rank among all ids = its position in its own list + one bisection per other list (ties broken by the
-//      list number, so the ranks are a permutation) — no sort network.  One workgroup stores every id at its rank in
-//      LDS; when the bisections are too many for one CU (many lists) the ids are shared out over up to 32 workgroups,
-//      which store into a small global array, and the workgroup that finishes last (a device-wide ticket) goes on;
-//   3. over the ascending ids: the first id of every run
-//      of equal ids survives — for an AND only when the run is n_lists long (each list holds an id once, so
-//      id[i + n_lists - 1] == id[i] says it all) — unless the tombstone bitmap has it; block scan, write-out, count.
+// The decode, rank and block-scan stages are those of small_set_device.h; particular to this kernel:
+//   - the lists come in the by-value parameter block;
+//   - one workgroup stores every id at its rank in LDS; when the bisections are too many for one CU (many lists) the ids
+//     are shared out over up to 32 workgroups, which all decode every block, store into a small global array, and the
+//     workgroup that finishes last (a device-wide ticket) goes on;
+//   - over the ascending ids the first id of every run of equal ids survives — for an AND only when the run is n_lists
+//     long (each list holds an id once, so id[i + n_lists - 1] == id[i] says it all) — unless the tombstone bitmap has it;
+//   - what fits out_cap is written, the count is the whole result's.
 #include <hip/hip_runtime.h>
 
-#include "dv1_device.h"
 #include "internal.h"
+#include "small_set_device.h"
 
 namespace ii2 {
 
@@ -30,7 +29,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_setop_small(SmallSetParams p) {
     __shared__ uint32_t wsum[SS_WAVES];
     __shared__ uint32_t last_s;
     __shared__ uint8_t blist[SMALL_SET_BLOCKS];                     // the list every block belongs to
-    const uint32_t tid = threadIdx.x, l = tid & 63u, wv = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     if (tid <= p.n_lists) {
         lpre[tid] = p.lpre[tid];
         lbase[tid] = p.blk_base[tid];
@@ -40,102 +39,19 @@ __global__ __launch_bounds__(SS_THREADS) void k_setop_small(SmallSetParams p) {
         }
     }
     __syncthreads();
-    // 1. decode: block b of the concatenated block list, one wave each (wave w: blocks w, w + 16, ...); every block of
-    // a list but its last is full, so block bi of list j starts at raw[lpre[j] + 256 bi].  The skip entries of all the
-    // wave's blocks are requested first, then the first 256 payload bytes of all of them, then they are decoded: two
-    // memory round trips per wave instead of two per block.
-    constexpr uint32_t PER_WAVE = SMALL_SET_BLOCKS / SS_WAVES;
-    uint32_t bj[PER_WAVE], q0[PER_WAVE], q1[PER_WAVE], f0[PER_WAVE], pw[PER_WAVE];
-#pragma unroll
-    for (uint32_t t = 0; t < PER_WAVE; t++) {
-        const uint32_t b = wv + t * SS_WAVES;
-        bj[t] = 0xFFFFFFFFu; q0[t] = 0; q1[t] = 0; f0[t] = 0;
-        if (b < p.n_blocks) {
-            const uint32_t j = blist[b];                                  // (wave-uniform)
-            const ii2_skip *sk = p.lists[j].skip + (b - lbase[j]);
-            const ii2_skip e0 = sk[0], e1 = sk[1];
-            bj[t] = j; q0[t] = e0.byte_off; q1[t] = e1.byte_off; f0[t] = e0.first_doc;
-        }
-    }
-#pragma unroll
-    for (uint32_t t = 0; t < PER_WAVE; t++) {
-        pw[t] = 0;
-        if (bj[t] != 0xFFFFFFFFu && q0[t] + 4u * l < q1[t]) pw[t] = load_u32_unaligned(p.lists[bj[t]].payload + q0[t] + 4u * l);
-    }
-#pragma unroll
-    for (uint32_t t = 0; t < PER_WAVE; t++) {
-        if (bj[t] == 0xFFFFFFFFu) continue;                               // (wave-uniform)
-        const uint32_t b = wv + t * SS_WAVES, j = bj[t];
-        const uint32_t at = lpre[j] + (b - lbase[j]) * II2_DV1_BLOCK, end = lpre[j + 1u];
-        const uint8_t *pl = p.lists[j].payload;
-        const uint32_t first_q = q0[t], pre = pw[t];
-        decode_block_wave([&](uint32_t myq) -> uint32_t { return myq == first_q + 4u * l ? pre : load_u32_unaligned(pl + myq); },
-                          q0[t], q1[t], f0[t], [&](uint32_t ix, uint32_t id) { if (at + ix < end) raw[at + ix] = id; });
-    }
+    // 1. decode (redundant across workgroups, but cheaper than a second launch)
+    ss_decode<SS_WAVES, SMALL_SET_BLOCKS / SS_WAVES>(p.n_blocks, blist, lbase, lpre, raw, [&](uint32_t j) { return p.lists[j].skip; },
+                                                     [&](uint32_t j) { return p.lists[j].payload; });
     __syncthreads();
     const uint32_t n_total = lpre[p.n_lists];
-    // 2. ranks: this workgroup's share of the ids (list-major numbering e = 0 .. n_total), at most eight per thread
+    // 2. ranks: this workgroup's share of the ids, at most eight per thread
     const uint32_t per_wg = (n_total + gridDim.x - 1u) / gridDim.x;
     const uint32_t e_end = (blockIdx.x + 1u) * per_wg < n_total ? (blockIdx.x + 1u) * per_wg : n_total;
-    uint32_t top = 1;                                // the largest power of two <= the longest list
-    for (uint32_t c = l; c < p.n_lists; c += 64u) top = lcnt[c] > top ? lcnt[c] : top;
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)top, d, 64); top = o > top ? o : top; }
-    top = 1u << (31u - (uint32_t)__clz((int)top));
     uint32_t rk[8], xv[8];
-#pragma unroll 4
-    for (uint32_t q = 0; q < 8u; q++) {
-        const uint32_t e = blockIdx.x * per_wg + tid + q * SS_THREADS;
-        rk[q] = 0xFFFFFFFFu;
-        xv[q] = 0;
-        if (e >= e_end) continue;
-        uint32_t j = 0;                                                   // my list: the last j with lpre[j] <= e
-        for (uint32_t st = 32u; st > 0u; st >>= 1) if (j + st < p.n_lists && lpre[j + st] <= e) j += st;
-        const uint32_t i = e - lpre[j];
-        const uint32_t x = raw[lpre[j] + i];
-        uint32_t r = i;
-        if (p.n_lists <= 8u) {
-            for (uint32_t c = 0; c < p.n_lists; c++) {
-                if (c == j) continue;
-                const uint32_t *B = raw + lpre[c];
-                uint32_t lo = 0, hi = lcnt[c];                            // first index with B[i] > x (c < j) or >= x (c > j)
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    const uint32_t y = B[mid];
-                    if (y < x || (c < j && y == x)) lo = mid + 1u; else hi = mid;
-                }
-                r += lo;
-            }
-        } else {
-            // many lists: a bisection per list is a chain of dependent LDS reads, and the chains of 63 lists one after the
-            // other were most of the kernel's time — branch-free bisections with the same steps for every list, eight
-            // lists (eight independent chains) at a time
-            for (uint32_t c0 = 0; c0 < p.n_lists; c0 += 8u) {
-                uint32_t pos[8], n[8], base[8];
 #pragma unroll
-                for (uint32_t u = 0; u < 8u; u++) {
-                    const uint32_t c = c0 + u;
-                    const bool on = c < p.n_lists && c != j;
-                    n[u] = on ? lcnt[c] : 0u;
-                    base[u] = on ? lpre[c] : 0u;
-                    pos[u] = 0;
-                }
-                for (uint32_t st = top; st > 0u; st >>= 1) {
-#pragma unroll
-                    for (uint32_t u = 0; u < 8u; u++) {
-                        const uint32_t cand = pos[u] + st;
-                        if (cand <= n[u]) {
-                            const uint32_t y = raw[base[u] + cand - 1u];
-                            if (y < x || (c0 + u < j && y == x)) pos[u] = cand;     // ties: lists before mine go first
-                        }
-                    }
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < 8u; u++) r += pos[u];
-            }
-        }
-        rk[q] = r;
-        xv[q] = x;
-    }
+    for (uint32_t q = 0; q < 8u; q++) { rk[q] = 0xFFFFFFFFu; xv[q] = 0; }
+    ss_rank<SS_THREADS, 8u>(p.n_lists, lcnt, lpre, raw, blockIdx.x * per_wg, e_end,
+                            [&](uint32_t q, uint32_t r, uint32_t x, uint32_t) { rk[q] = r; xv[q] = x; });
     const bool solo = gridDim.x == 1u;               // one workgroup: the ascending ids replace the decoded blocks in LDS
     if (solo) {
         __syncthreads();                             // (every rank is computed: raw may be overwritten)
@@ -177,15 +93,12 @@ __global__ __launch_bounds__(SS_THREADS) void k_setop_small(SmallSetParams p) {
             bool keep = i == 0u || prev != v;                             // first of its run
             prev = v;
             if (keep && !p.is_union) keep = i + p.n_lists - 1u < n_total && key(i + p.n_lists - 1u) == v;
-            if (keep && p.tomb && (v >> 5) < p.tomb_nwords) keep = ((p.tomb[v >> 5] >> (v & 31u)) & 1u) == 0u;
+            if (keep && tomb_has(p.tomb, p.tomb_nwords, v)) keep = false;
             if (keep) { keepmask |= 1u << q; cnt++; }
         }
     }
-    const uint32_t incl = wave_incl_scan(cnt);
-    if (l == 63u) wsum[wv] = incl;
-    __syncthreads();
-    uint32_t pos = incl - cnt, total = 0;
-    for (uint32_t w = 0; w < SS_WAVES; w++) { if (w < wv) pos += wsum[w]; total += wsum[w]; }
+    uint32_t total;
+    uint32_t pos = ss_block_scan<SS_WAVES>(cnt, wsum, &total);
 #pragma unroll
     for (uint32_t q = 0; q < 8u; q++)
         if ((keepmask >> q) & 1u) { if (pos < p.out_cap) p.out[pos] = kept[q]; pos++; }

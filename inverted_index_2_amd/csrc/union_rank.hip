@@ -81,7 +81,7 @@ __device__ __forceinline__ uint32_t ur_flags(const UnionRankParams &p, uint32_t 
         v[q] = x;
         bool keep = i == 0u || prev != x;                                  // first of its run
         prev = x;
-        if (keep && p.tomb && (x >> 5) < p.tomb_nwords) keep = ((p.tomb[x >> 5] >> (x & 31u)) & 1u) == 0u;
+        if (keep && tomb_has(p.tomb, p.tomb_nwords, x)) keep = false;
         if (keep) mask |= 1u << q;
     }
     return mask;

@@ -1,7 +1,14 @@
-"""GPU probe: latency of small queries (2-term AND / OR of short lists), back to back on one stream."""
-import sys, os, time
+"""GPU probe: latency of small queries (2-term AND / OR of short lists), back to back on one stream.
+--lib points at a library built from the commit to compare with."""
+import argparse, sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+ap = argparse.ArgumentParser()
+ap.add_argument("--lib", default=None, help="libii2_hip.so to load instead of the package's own")
+args = ap.parse_args()
+from inverted_index_2_amd import _lib
+if args.lib:
+    _lib.LIB_PATH = os.path.abspath(args.lib)
 from inverted_index_2_amd import Context
 ctx = Context(0)
 rng = np.random.default_rng(1)
