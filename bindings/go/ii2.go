@@ -379,6 +379,49 @@ func (c *Ctx) QueryBatch(op []uint8, queryFirst []uint64, segs []*Segment, listF
 	return offsets, nil
 }
 
+// QueryBatchGroups answers MANY AND-of-ORs / NOT queries over resident segments in one call (ii2_query_batch_groups): QueryBatch
+// for an index that is not fully merged, where a term is a group - one short list per Put segment that holds it.  Query q owns
+// the groups queryFirst[q] .. queryFirst[q+1]-1; groupFirst, groupNot and the range arrays are those of AndNotRanges over all
+// groups of the batch (groupNot == nil: every group is required), and result q is what AndNotRanges returns for query q's
+// groups: one required group is a union, several an AND of ORs, excluded groups a NOT.  A query without groups, or with a
+// required group without postings, gives an empty result; a query with groups but no required one is an error that names the
+// query.  Replaces a loop over Intersect / IntersectExcept (index.go) by a number of launches and one wait that do not depend
+// on the number of queries.  The results are packed back to back into the device buffer out (capacity capIDs ids; the sum over
+// the queries of the postings of their smallest required group is always enough) in query order; the returned offsets
+// (len(queryFirst)) delimit them.  All-or-nothing: on ErrCapacity nothing was written and the last offset is the capacity to
+// call again with.
+func (c *Ctx) QueryBatchGroups(queryFirst, groupFirst []uint64, groupNot []uint8, segs []*Segment, listFirst, listEnd []uint64, out unsafe.Pointer, capIDs uint64) ([]uint64, error) {
+	nQueries := len(queryFirst) - 1
+	if nQueries < 0 || len(groupFirst) == 0 || (groupNot != nil && len(groupNot) != len(groupFirst)-1) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return nil, fmt.Errorf("query batch groups: array lengths disagree")
+	}
+	// the C side reads groupFirst[0 .. queryFirst[nQueries]] and the range arrays up to groupFirst's last element
+	if queryFirst[nQueries] != uint64(len(groupFirst)-1) || groupFirst[len(groupFirst)-1] != uint64(len(segs)) {
+		return nil, fmt.Errorf("query batch groups: queryFirst / groupFirst do not end at the lengths of the arrays they index")
+	}
+	offsets := make([]uint64, nQueries+1)
+	if nQueries == 0 {
+		return offsets, nil
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if len(groupNot) != 0 {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	rc := C.ii2_query_batch_groups(c.h, C.uint64_t(nQueries), u64ptr(queryFirst), u64ptr(groupFirst), flags,
+		(**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(out), C.uint64_t(capIDs), u64ptr(offsets))
+	if rc == C.II2_ECAPACITY {
+		return offsets, ErrCapacity
+	}
+	if rc != 0 {
+		return nil, c.err("query batch groups", rc)
+	}
+	return offsets, nil
+}
+
 // AndNotRanges answers one boolean query with excluded (NOT) groups over resident segments (ii2_andnot_ranges): the ids that
 // lie in at least one list of EVERY required group and in NO list of ANY excluded group.  Group g owns the ranges
 // groupFirst[g] .. groupFirst[g+1]-1, a range being lists [listFirst[i], listEnd[i]) of segs[i]; groupNot[g] is 0 for a
@@ -390,6 +433,9 @@ func (c *Ctx) AndNotRanges(groupFirst []uint64, groupNot []uint8, segs []*Segmen
 	nGroups := len(groupFirst) - 1
 	if nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
 		return 0, fmt.Errorf("andnot ranges: array lengths disagree")
+	}
+	if groupFirst[nGroups] != uint64(len(segs)) { // the C side reads the range arrays up to groupFirst's last element
+		return 0, fmt.Errorf("andnot ranges: groupFirst does not end at the number of ranges")
 	}
 	if nGroups == 0 {
 		return 0, nil

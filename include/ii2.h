@@ -20,7 +20,10 @@
  *     blocks and < 2^30 term slots; ii2_align_terms takes < 2^31 terms; one segment holds < 2^31
  *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls);
  *     ii2_query_batch takes <= 2^20 queries whose result bounds (AND: the shortest operand, OR: the postings of
- *     its ranges) add up to < 2^32 ids.  The one-launch form of ii2_andnot_ranges takes queries whose non-empty lists - required
+ *     its ranges) add up to < 2^32 ids; ii2_query_batch_groups takes <= 2^20 queries whose result bounds (the postings of each query's
+ *     smallest required group) add up to < 2^32 ids, a query of at most II2_MAX_LISTS non-empty lists - required and excluded -
+ *     that hold at most 8192 postings in at most 128 blocks shares the batch's launch (larger ones run one by one: no error).
+ *     The one-launch form of ii2_andnot_ranges takes queries whose non-empty lists - required
  *     and excluded - are at most II2_MAX_LISTS and hold at most 8192 postings in at most 128 blocks, by default only while
  *     postings x lists <= 32768 (what the form costs; beyond it, or beyond the kernel, a query takes the general form: no error).
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
@@ -327,6 +330,39 @@ int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const u
                     const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
                     const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *out_off);
 
+/* MANY AND-of-ORs / NOT queries in one call: ii2_query_batch for an index that is not fully merged.  There a term is not one
+ * list but a group - one short list per Put segment of its shard that holds it (shard.go:33-67, :135-146) - so a front end's
+ * "a AND b NOT c" is an ii2_andnot_ranges query, which ii2_query_batch's AND (every list an operand, no NOT) cannot express.
+ * Replaces a loop over the build-defined Intersect / IntersectExcept (ii2_intersect_ranges / ii2_andnot_ranges: a launch and a
+ * stream wait per query) and, with one required group per prefix, many prefixes ANDed (PrefixSearch(prefixes [][]byte),
+ * inverted_index.go:192, followed by an intersection on the host) by a number of launches and ONE wait that do not depend on
+ * the number of queries.
+ * Query q owns the groups query_first[q] .. query_first[q + 1] - 1 (query_first[0] = 0); group_first[G + 1], group_not[G] and
+ * the range arrays are exactly those of ii2_andnot_ranges over all G = query_first[n_queries] groups of the batch
+ * (group_first[0] = 0; group_not == NULL: every group is required; segments and views alike; a list may appear in any number
+ * of ranges, groups and queries).  All six arrays live in host memory.  The result of query q is bit-identical to what
+ * ii2_andnot_ranges - ii2_intersect_ranges when group_not == NULL - returns for its groups:
+ *   - one required group and nothing excluded is that group's union: OR, AND, AND of ORs and NOT are all one shape;
+ *   - a query without a group, a required group without postings or required groups whose doc spans do not overlap: an empty
+ *     result; an excluded group without postings is ignored; a list both required and excluded removes its ids;
+ *   - tomb (may be NULL) applies to every query, once per query.
+ * The results are packed back to back in d_out (device) in query order and out_off[n_queries + 1] (host) receives their
+ * offsets, out_off[0] = 0.  cap >= the sum over the queries of the postings of their smallest required group is always enough.
+ * All-or-nothing.  Every query is checked before anything is launched: a query that has groups but no required one, a flag
+ * other than 0 / 1, a bad range, query_first / group_first not ascending from 0, or a segment of another device is
+ * II2_EINVAL, the message names the query's index ("... query 17: ..."), nothing is launched and nothing written (tombstones
+ * of another device: II2_EINVAL as well).  More than 2^20 queries, or result bounds that add up to 2^32 ids or more:
+ * II2_ERANGE.  When the packed results exceed cap the call returns II2_ECAPACITY, d_out is untouched and out_off is completely
+ * filled (allocate out_off[n_queries] ids and call again; d_out may be NULL when cap is 0).  n_queries == 0: out_off[0] = 0.
+ * Queries that fit one workgroup (see the conventions above; option batch.groups) are answered together, one workgroup each, in
+ * one launch per size class (option batch.tiny): every list decoded into LDS group by group, every id ranked with its group's
+ * tag, a run of equal ids kept when it holds every required tag and not the excluded one.  The others go one after the other
+ * through the paths of ii2_andnot_ranges (and cost its waits each) and are packed with the rest.  The staged results live in
+ * the per-context buffer of ii2_query_batch. */
+int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,
+                           const uint8_t *group_not, const ii2_seg *const *segs, const uint64_t *list_first,
+                           const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *out_off);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -401,6 +437,9 @@ int ii2_selftest(ii2_ctx *ctx);
  *                                           query of a batch goes through the single-query paths one after the other
  *   batch.tiny                              ... and those of at most 2048 postings in at most 32 blocks run as 256-thread workgroups
  *                                           (1, default: up to seven per CU) or, like the rest, as 1024-thread ones (0)
+ *   batch.groups                            ii2_query_batch_groups: 1 (default) the queries that fit one workgroup share the batch kernel
+ *                                           (batch.tiny picks its form as above), 0 every query of a batch goes through the paths of
+ *                                           ii2_andnot_ranges one after the other
  *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)

@@ -75,6 +75,7 @@ PROTOTYPES = {
     "ii2_intersect_ranges": (C.c_int, [vp, C.c_uint64, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_andnot_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_query_batch": (C.c_int, [vp, C.c_uint64, u8p, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
+    "ii2_query_batch_groups": (C.c_int, [vp, C.c_uint64, u64p, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

@@ -101,7 +101,8 @@ struct ii2_ctx {
     uint32_t *d_an = nullptr;           // its required part's result, the candidates of the exclusion pass (grow-only; neither d_ir, which the
     size_t an_words = 0;                //     group path ping-pongs in, nor workspace, which the driver's union reserves itself)
     int64_t opt_batch_small = 1;        // ii2_query_batch: small queries share the batch kernel (0: every query through the single-query paths)
-    int64_t opt_batch_tiny = 1;         // ... those of <= 2048 postings in <= 32 blocks in its 256-thread form (0: all in the 1024-thread form)
+    int64_t opt_batch_tiny = 1;         // ... of both entry points: those of <= 2048 postings in <= 32 blocks in the 256-thread form (0: all in the 1024-thread one)
+    int64_t opt_batch_groups = 1;       // ii2_query_batch_groups: queries that fit share its batch kernel (0: every query through ii2_andnot_ranges' paths)
     uint8_t *d_batch = nullptr;         // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
     size_t batch_cap = 0;
     void *h_batch = nullptr;            // pinned: the descriptor table on its way up, the offsets on their way down (grow-only)
@@ -313,7 +314,7 @@ struct BatchQuery {
     uint32_t n_lists;            // 1 .. MAX_LISTS
     uint32_t is_union;
     uint32_t slot;               // its word of the counts array (= its index in the caller's batch)
-    uint32_t pad;
+    uint32_t n_req;              // ii2_query_batch_groups: its required groups, 1 .. n_lists (ii2_query_batch: 0)
 };
 struct BatchParams {
     const BatchQuery *queries;   // [n_tiny + n_small], the tiny ones first
@@ -353,6 +354,15 @@ struct GroupSetParams {
 };
 hipError_t launch_setop_groups(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_batch_pack(const BatchPackParams &p, uint64_t max_bound, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// many short AND-of-ORs / NOT queries in one launch (setop_groups_batch.hip): the batch kernel's table (is_union unused), every
+// query's lists in tag order as k_setop_groups takes them - the required groups first (tags 0 .. n_req - 1), the lists of all
+// its excluded groups last (tag n_req) - and one tag byte per list of the table
+struct GroupBatchParams {
+    BatchParams b;
+    const uint8_t *tag;          // [lists of the table]
+};
+hipError_t launch_setop_groups_batch(const GroupBatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // OR of a few medium-size lists by ranking (union_rank.hip)
 constexpr uint32_t UNION_RANK_MAXL = 8;

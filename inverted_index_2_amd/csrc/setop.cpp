@@ -17,6 +17,9 @@
 //        span - the probe / mark filter with the flag turned round - or, without such a list, a copy.
 //   Many AND / OR queries in one call (ii2_query_batch): the small ones in one launch per size class (setop_batch.hip), the
 //        others one by one through the choosers above; all of them staged, then packed in query order.
+//   Many AND-of-ORs / NOT queries in one call (ii2_query_batch_groups): every query an ii2_andnot_ranges call - those that fit
+//        one workgroup in one launch per size class (setop_groups_batch.hip), the others one by one through that entry point's
+//        paths; staged and packed by the same code as the flat batch.
 // The file is in that order, every section closed by its entry points (those of the AND and the OR chooser together, behind the
 // OR section: each of the two is also called by the sections below), the helpers that several sections share in front.
 #include <algorithm>
@@ -610,21 +613,20 @@ static int um_scratch_reserve(ii2_ctx *ctx, const char *who, uint64_t span, uint
 // blocks are appended to rs.  *n_blocks, *n_nonempty grow by their blocks and non-empty lists.
 static int collect_ranges(ii2_ctx *ctx, const char *who, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
                           const uint64_t *list_end, std::vector<RangeIn> &rs, uint64_t *n_blocks, uint64_t *n_nonempty) {
-    const std::string w(who);
     for (uint64_t i = 0; i < n; i++) {
         const ii2_seg *seg = segs[i];
         const uint64_t l0 = list_first[i], l1 = list_end[i];
-        if (!seg || l0 > l1 || l1 > seg->n_lists || seg->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": bad range").c_str());
+        if (!seg || l0 > l1 || l1 > seg->n_lists || seg->device != ctx->device) return fail(ctx, II2_EINVAL, (std::string(who) + ": bad range").c_str());
         if (l0 == l1) continue;
         if (int rc = ii2_seg_host_blk_off(ctx, seg)) return rc;
         // the lists [l0, l1) must own the consecutive blocks blk_off[l0] .. blk_off[l1] (views skip only empty lists between
         // selected ones): checked, not assumed
         const std::vector<uint32_t> &bo = seg->h_blk_off;
         for (uint64_t j = l0; j < l1; j++) {
-            if (bo[j + 1] < bo[j]) return fail(ctx, II2_EINVAL, (w + ": the segment's list table does not ascend").c_str());
+            if (bo[j + 1] < bo[j]) return fail(ctx, II2_EINVAL, (std::string(who) + ": the segment's list table does not ascend").c_str());
             *n_nonempty += bo[j + 1] > bo[j] ? 1u : 0u;
         }
-        if (bo[l1] > seg->n_blocks) return fail(ctx, II2_EINVAL, (w + ": the segment's list table does not ascend").c_str());
+        if (bo[l1] > seg->n_blocks) return fail(ctx, II2_EINVAL, (std::string(who) + ": the segment's list table does not ascend").c_str());
         if (bo[l1] == bo[l0]) continue;
         rs.push_back(RangeIn{seg, l0, l1, bo[l0], bo[l1]});
         *n_blocks += bo[l1] - bo[l0];
@@ -1013,11 +1015,10 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
 // rs[gs[g].r0, gs[g].r1); *n_blocks = the blocks of all of them.  n_groups > 0.
 static int collect_groups(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
                           const uint64_t *list_first, const uint64_t *list_end, std::vector<RangeIn> &rs, std::vector<GroupIn> &gs, uint64_t *n_blocks) {
-    const std::string w(who);
-    if (!group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (!group_first) return fail(ctx, II2_EINVAL, (std::string(who) + ": bad argument").c_str());
     for (uint64_t g = 0; g < n_groups; g++)
-        if (group_first[g + 1] < group_first[g]) return fail(ctx, II2_EINVAL, (w + ": group_first does not ascend").c_str());
-    if (group_first[n_groups] > group_first[0] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+        if (group_first[g + 1] < group_first[g]) return fail(ctx, II2_EINVAL, (std::string(who) + ": group_first does not ascend").c_str());
+    if (group_first[n_groups] > group_first[0] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, (std::string(who) + ": bad argument").c_str());
     gs.resize(n_groups);
     for (uint64_t g = 0; g < n_groups; g++) {
         const uint64_t a = group_first[g], b = group_first[g + 1];
@@ -1303,6 +1304,7 @@ struct BatchPlan {
     uint32_t n_blocks;
     uint8_t kind;                // BP_*
     uint8_t is_union;
+    uint8_t n_req;               // ii2_query_batch_groups: its required groups when it takes the batch kernel (<= MAX_LISTS)
 };
 enum { BP_EMPTY = 0, BP_TINY = 1, BP_SMALL = 2, BP_LARGE = 3 };
 }  // namespace
@@ -1313,6 +1315,64 @@ static int batch_reserve(ii2_ctx *ctx, size_t dev_bytes, size_t host_bytes) {
     if (int rc = grow_device(ctx, &ctx->d_batch, &ctx->batch_cap, dev_bytes, align_up(dev_bytes + dev_bytes / 4, 1 << 20), 1, "ii2_query_batch: staging allocation failed"))
         return rc;
     return grow_pinned(ctx, &ctx->h_batch, &ctx->h_batch_cap, host_bytes, true, "ii2_query_batch: pinned staging allocation failed");
+}
+
+// The blocks of a batch call, nq queries whose staging slots hold stage_ids ids: [the entry point's table, table_bytes | staging
+// offsets | counts] are filled in the pinned block h and travel up in one copy; offsets, scan temp and staged ids stay below.
+namespace {
+struct BatchMem {
+    size_t o_soff, o_cnt, up_bytes, o_off, o_scan, scan_tmp, o_stage;
+    uint8_t *h, *d;
+    uint32_t *d_stage;
+    uint64_t *h_soff;            // [nq] every query's staging slot
+    uint32_t *h_cnt;             // [nq + 1] the counts of the queries that no batch kernel answers (theirs: 0); [nq] = 0
+};
+}  // namespace
+static int batch_blocks(ii2_ctx *ctx, size_t table_bytes, uint64_t nq, uint64_t stage_ids, BatchMem *m) {
+    m->o_soff = table_bytes;
+    m->o_cnt = m->o_soff + align_up(nq * sizeof(uint64_t));
+    m->up_bytes = m->o_cnt + align_up((nq + 1) * sizeof(uint32_t));
+    const size_t off_bytes = align_up((nq + 1) * sizeof(uint64_t));
+    m->scan_tmp = scan_temp_bytes(nq + 1);
+    m->o_off = m->up_bytes;
+    m->o_scan = m->o_off + off_bytes;
+    m->o_stage = m->o_scan + m->scan_tmp;
+    if (int rc = batch_reserve(ctx, m->o_stage + align_up((stage_ids + 4) * sizeof(uint32_t)), m->up_bytes + off_bytes)) return rc;
+    m->h = (uint8_t *)ctx->h_batch;
+    m->d = ctx->d_batch;
+    m->d_stage = (uint32_t *)(m->d + m->o_stage);
+    m->h_soff = (uint64_t *)(m->h + m->o_soff);
+    m->h_cnt = (uint32_t *)(m->h + m->o_cnt);
+    return II2_OK;
+}
+
+// The end of a batch call, behind its batch kernels: counts -> offsets, pack (tests the capacity on the device), offsets down;
+// the call's one wait.  `who` names the entry point in the message.
+static int batch_finish(ii2_ctx *ctx, const char *who, const BatchMem &m, uint64_t nq, uint64_t max_bound, uint32_t *d_out, uint64_t cap,
+                        uint64_t *out_off) {
+    hipStream_t st = ctx->stream;
+    uint8_t *d = m.d;
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d + m.o_scan, m.scan_tmp, (const uint32_t *)(d + m.o_cnt), (uint64_t *)(d + m.o_off), nq + 1, st));
+    BatchPackParams pp;
+    std::memset(&pp, 0, sizeof pp);
+    pp.stage = m.d_stage;
+    pp.stage_off = (const uint64_t *)(d + m.o_soff);
+    pp.off = (const uint64_t *)(d + m.o_off);
+    pp.out = d_out;
+    pp.cap = cap;
+    pp.n_queries = (uint32_t)nq;
+    {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st, e0, e1));
+    }
+    uint64_t *h_off = (uint64_t *)(m.h + m.up_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(h_off, d + m.o_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(out_off, h_off, (nq + 1) * sizeof(uint64_t));
+    if (out_off[nq] > cap)
+        return fail(ctx, II2_ECAPACITY, (std::string(who) + ": the results do not fit the output buffer (nothing written; out_off holds the sizes)").c_str());
+    return II2_OK;
 }
 
 static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
@@ -1387,18 +1447,15 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
     }
     // 2. the blocks: [queries | lists | staging offsets | counts] travel up in one copy; offsets, scan temp and staged ids stay below
     const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
-    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_soff = o_lists + align_up(n_table_lists * sizeof(BatchList));
-    const size_t o_cnt = o_soff + align_up(nq * sizeof(uint64_t)), up_bytes = o_cnt + align_up((nq + 1) * sizeof(uint32_t));
-    const size_t off_bytes = align_up((nq + 1) * sizeof(uint64_t)), scan_tmp = scan_temp_bytes(nq + 1);
-    const size_t o_off = up_bytes, o_scan = o_off + off_bytes, o_stage = o_scan + scan_tmp;
-    if (int rc = batch_reserve(ctx, o_stage + align_up((stage_ids + 4) * sizeof(uint32_t)), up_bytes + off_bytes)) return rc;
-    uint8_t *h = (uint8_t *)ctx->h_batch, *d = ctx->d_batch;
-    uint32_t *d_stage = (uint32_t *)(d + o_stage);
+    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery));
+    BatchMem m;
+    if (int rc = batch_blocks(ctx, o_lists + align_up(n_table_lists * sizeof(BatchList)), nq, stage_ids, &m)) return rc;
+    uint8_t *h = m.h, *d = m.d;
+    uint32_t *d_stage = m.d_stage;
     BatchQuery *hq = (BatchQuery *)h;
     BatchList *hl = (BatchList *)(h + o_lists);
-    uint64_t *h_soff = (uint64_t *)(h + o_soff);
-    uint32_t *h_cnt = (uint32_t *)(h + o_cnt);
-    uint64_t *h_off = (uint64_t *)(h + up_bytes);
+    uint64_t *h_soff = m.h_soff;
+    uint32_t *h_cnt = m.h_cnt;
     // 3. the large queries, one after the other through the single-query paths, into their staging slots (each with its own wait);
     // two-list ANDs in the two-kernel form: nothing of a batch waits between workgroups
     std::vector<const ii2_seg *> one_segs;
@@ -1443,7 +1500,7 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
     // 4. table up, the small queries in one launch per size class, counts -> offsets, pack (tests the capacity on the device),
     // offsets down: one wait
     hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d, h, m.up_bytes, hipMemcpyHostToDevice, st));
     if (n_table) {
         BatchParams bp;
         std::memset(&bp, 0, sizeof bp);
@@ -1453,30 +1510,12 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
         bp.n_tiny = n_kind[BP_TINY];
         bp.n_small = n_kind[BP_SMALL];
         bp.stage = d_stage;
-        bp.cnt = (uint32_t *)(d + o_cnt);
+        bp.cnt = (uint32_t *)(d + m.o_cnt);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
         HIP_TRY(ctx, launch_setop_batch(bp, st, e0, e1));
     }
-    HIP_TRY(ctx, scan_excl_u32_to_u64(d + o_scan, scan_tmp, (const uint32_t *)(d + o_cnt), (uint64_t *)(d + o_off), nq + 1, st));
-    BatchPackParams pp;
-    std::memset(&pp, 0, sizeof pp);
-    pp.stage = d_stage;
-    pp.stage_off = (const uint64_t *)(d + o_soff);
-    pp.off = (const uint64_t *)(d + o_off);
-    pp.out = d_out;
-    pp.cap = cap;
-    pp.n_queries = (uint32_t)nq;
-    {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ii2_profile_pair(ctx, &e0, &e1);
-        HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st, e0, e1));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(h_off, d + o_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(out_off, h_off, (nq + 1) * sizeof(uint64_t));
-    if (out_off[nq] > cap) return fail(ctx, II2_ECAPACITY, "ii2_query_batch: the results do not fit the output buffer (nothing written; out_off holds the sizes)");
-    return II2_OK;
+    return batch_finish(ctx, "ii2_query_batch", m, nq, max_bound, d_out, cap, out_off);
 }
 
 extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
@@ -1486,6 +1525,191 @@ extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return query_batch_unlocked(ctx, n_queries, op, query_first, segs, list_first, list_end, tomb, d_out, cap, out_off);
+}
+
+// ---- many AND-of-ORs / NOT queries in one call ------------------------------------------------------
+// Query q owns the groups query_first[q] .. query_first[q + 1] - 1 of an ii2_andnot_ranges call; its result is that call's.
+// The plan of a query follows andnot_ranges_unlocked step by step - same helpers, same order of the checks - so that the two
+// agree on what is empty and on which excluded lists count; what differs is where a short query runs.
+static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_first, const uint64_t *group_first, const uint8_t *group_not,
+                                       const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                                       uint32_t *d_out, uint64_t cap, uint64_t *out_off) {
+    const char *const who = "ii2_query_batch_groups";
+    const std::string w(who);
+    if (nq == 0) { out_off[0] = 0; return II2_OK; }
+    if (!query_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
+    if (!d_out && cap) return fail(ctx, II2_EINVAL, (w + ": output buffer is NULL").c_str());
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": the tombstones live on another device").c_str());
+    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, (w + ": query " + std::to_string(q) + ": " + what).c_str()); };
+    // a helper's message "<entry point>: ..." gets the query's index behind the name (built on the error path only)
+    auto named = [&](uint64_t q, int rc) {
+        if (ctx->err.compare(0, w.size() + 2, w + ": ") == 0) ctx->err.insert(w.size(), ": query " + std::to_string(q));
+        return rc;
+    };
+    if (query_first[0] != 0) return bad(0, "query_first does not ascend from 0");
+    for (uint64_t q = 0; q < nq; q++)
+        if (query_first[q + 1] < query_first[q]) return bad(q, "query_first does not ascend from 0");
+    if (query_first[nq] && !group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (query_first[nq] && group_first[0] != 0) return bad(0, "group_first does not ascend from 0");
+    // 1. every query checked and sized before anything is launched
+    std::vector<BatchPlan> plan(nq);
+    std::vector<BatchList> tl;             // the table's lists and their tags, the queries in batch order (tiny and small ones alike)
+    std::vector<uint8_t> tt;
+    std::vector<RangeIn> rs, rx;
+    std::vector<GroupIn> all, req;
+    uint64_t stage_ids = 0, max_bound = 0;
+    uint32_t n_kind[4] = {0, 0, 0, 0};
+    for (uint64_t q = 0; q < nq; q++) {
+        const uint64_t g0 = query_first[q], ng = query_first[q + 1] - g0;
+        BatchPlan &pl = plan[q];
+        pl = BatchPlan{0, stage_ids, tl.size(), 0, 0, BP_EMPTY, 0, 0};
+        auto planned = [&]() { n_kind[pl.kind]++; };
+        if (ng == 0) { planned(); continue; }                              // no group: an empty result
+        uint64_t n_req = 0;
+        for (uint64_t g = g0; g < g0 + ng; g++) {
+            if (group_not && group_not[g] > 1) return bad(q, "a group_not flag is neither 0 nor 1");
+            n_req += group_not && group_not[g] ? 0u : 1u;
+        }
+        if (!n_req) return bad(q, "no required group (the library has no doc universe to complement)");
+        rs.clear();
+        rx.clear();
+        all.clear();
+        req.clear();
+        uint64_t n_blocks = 0;
+        if (int rc = collect_groups(ctx, who, ng, group_first + g0, segs, list_first, list_end, rs, all, &n_blocks)) return named(q, rc);
+        if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull)
+            return fail(ctx, II2_ERANGE, (w + ": query " + std::to_string(q) + ": more than 2^32 - 2 blocks in one query").c_str());
+        IrPass ex{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
+        bool empty = false;
+        for (uint64_t g = 0; g < ng; g++) {
+            if (!group_not || !group_not[g0 + g]) {
+                if (!all[g].n_blocks) empty = true;                          // a required group without postings
+                req.push_back(all[g]);
+            } else {
+                rx.insert(rx.end(), rs.begin() + all[g].r0, rs.begin() + all[g].r1);
+            }
+        }
+        if (empty) { planned(); continue; }
+        ex.r1 = rx.size();
+        if (int rc = group_sizes(ctx, rs, req)) return named(q, rc);
+        uint32_t clo, chi;
+        common_span(req, &clo, &chi);
+        if (clo > chi) { planned(); continue; }                            // the required spans do not overlap
+        uint64_t shortest = ~0ull;
+        for (const GroupIn &G : req) shortest = std::min(shortest, G.n_post);
+        pl.bound = shortest;
+        pl.kind = BP_LARGE;
+        // A query fits the batch kernel when its non-empty required lists and the excluded lists that count are at most MAX_LISTS
+        // lists of SMALL_SET_POSTINGS postings in SMALL_SET_BLOCKS blocks.  ANDNOT_SMALL_WORK is NOT applied: that bound prices one
+        // workgroup against the general form's waits inside a single call; in a batch the alternative is those waits once per
+        // query, one after the other, while the other CUs sit idle (DESIGN.md §4.1i has the case at the kernel's capacity).
+        if (ctx->opt_batch_groups && req.size() <= MAX_LISTS) {
+            ex.lo = clo;
+            ex.hi = chi;
+            uint32_t m = 0, nb = 0;
+            uint64_t sum = 0;
+            bool fits = true;
+            auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
+                const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1], c = s->h_cnt[j];
+                if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || !blocks_full(b1 - b0, c)) {
+                    fits = false;
+                    return;
+                }
+                tl.push_back(BatchList{s->d_skip + b0, s->d_payload, b1 - b0, c});
+                tt.push_back((uint8_t)tag);
+                m++;
+                nb += b1 - b0;
+                sum += c;
+            };
+            for (size_t g = 0; g < req.size() && fits; g++)
+                for (size_t r = req[g].r0; r < req[g].r1 && fits; r++)
+                    for (uint64_t j = rs[r].l0; j < rs[r].l1 && fits; j++)
+                        if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) add(rs[r].seg, j, (uint32_t)g);
+            for (size_t r = 0; r < rx.size() && fits; r++) {
+                if (int rc = ii2_seg_host_cnt(ctx, rx[r].seg)) return rc;
+                for (uint64_t j = rx[r].l0; j < rx[r].l1 && fits; j++)
+                    if (ir_list_counts(ex, rx[r].seg, j)) add(rx[r].seg, j, (uint32_t)req.size());
+            }
+            if (fits) {
+                pl.nl = m;
+                pl.n_blocks = nb;
+                pl.kind = ctx->opt_batch_tiny && nb <= BATCH_TINY_BLOCKS && sum <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
+                pl.n_req = (uint8_t)req.size();
+            } else {
+                tl.resize(pl.l0);
+                tt.resize(pl.l0);
+            }
+        }
+        planned();
+        stage_ids += pl.bound;
+        max_bound = std::max(max_bound, pl.bound);
+        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": the result bounds of the queries add up to 2^32 ids or more").c_str());
+    }
+    // 2. the blocks: [queries | lists | tags | staging offsets | counts] travel up in one copy (batch_blocks)
+    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
+    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
+    BatchMem m;
+    if (int rc = batch_blocks(ctx, o_tags + align_up(tt.size()), nq, stage_ids, &m)) return rc;
+    BatchQuery *hq = (BatchQuery *)m.h;
+    if (!tl.empty()) {
+        std::memcpy(m.h + o_lists, tl.data(), tl.size() * sizeof(BatchList));
+        std::memcpy(m.h + o_tags, tt.data(), tt.size());
+    }
+    // 3. the large queries, one after the other through ii2_andnot_ranges' paths, into their staging slots (each with its own
+    // waits); two-list ANDs in the two-kernel form for the duration: nothing of a batch waits between workgroups
+    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY];
+    for (uint64_t q = 0; q < nq; q++) {
+        const BatchPlan &pl = plan[q];
+        m.h_soff[q] = pl.stage_off;
+        m.h_cnt[q] = 0;
+        if (pl.kind == BP_EMPTY) continue;
+        if (pl.kind == BP_LARGE) {
+            const uint64_t g0 = query_first[q];
+            uint64_t count = 0;
+            const int64_t keep = ctx->opt_intersect_and2;
+            if (keep == 1) ctx->opt_intersect_and2 = 2;
+            const int rc = andnot_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr, segs, list_first,
+                                                  list_end, tomb, m.d_stage + pl.stage_off, pl.bound, &count);
+            ctx->opt_intersect_and2 = keep;
+            if (rc) {
+                ctx->err = w + ": query " + std::to_string(q) + ": " + ctx->err;
+                return rc;
+            }
+            m.h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
+            continue;
+        }
+        hq[pl.kind == BP_TINY ? at_tiny++ : at_small++] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
+    }
+    m.h_cnt[nq] = 0;
+    // 4. table up, the queries that fit in one launch per size class, then the flat batch's scan, pack and wait (batch_finish)
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(m.d, m.h, m.up_bytes, hipMemcpyHostToDevice, st));
+    if (n_table) {
+        GroupBatchParams gp;
+        std::memset(&gp, 0, sizeof gp);
+        gp.b.queries = (const BatchQuery *)m.d;
+        gp.b.lists = (const BatchList *)(m.d + o_lists);
+        gp.tag = m.d + o_tags;
+        set_tomb(gp.b, tomb);
+        gp.b.n_tiny = n_kind[BP_TINY];
+        gp.b.n_small = n_kind[BP_SMALL];
+        gp.b.stage = m.d_stage;
+        gp.b.cnt = (uint32_t *)(m.d + m.o_cnt);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_setop_groups_batch(gp, st, e0, e1));
+    }
+    return batch_finish(ctx, who, m, nq, max_bound, d_out, cap, out_off);
+}
+
+extern "C" int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,
+                                      const uint8_t *group_not, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                      const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *out_off) {
+    if (!ctx || !out_off) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return query_batch_groups_unlocked(ctx, n_queries, query_first, group_first, group_not, segs, list_first, list_end, tomb, d_out, cap, out_off);
 }
 
 extern "C" {

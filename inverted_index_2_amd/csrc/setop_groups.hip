@@ -9,10 +9,10 @@
 //     groups last under one tag, n_req (NOT g1 AND NOT g2 = NOT (g1 OR g2));
 //   - the id AND its list's tag are stored at the rank.  Lists are in tag order, so the tags inside a run of equal ids ascend;
 //   - the thread that holds the head of a run (a run is at most n_lists <= 64 long: a list holds an id once) walks it and
-//     counts the tag changes among the required tags: the id survives when every required tag occurs and the run's last
-//     tag is not the excluded one.  The same id in two lists of one group - or the same list twice - repeats a tag and is
-//     counted once.  Then the tombstone test, the block scan, the write-out - only when the whole result fits out_cap - and
-//     the count.
+//     counts the tag changes among the required tags (ss_group_run_kept, shared with setop_groups_batch.hip): the id survives
+//     when every required tag occurs and the run's last tag is not the excluded one.  The same id in two lists of one group -
+//     or the same list twice - repeats a tag and is counted once.  Then the tombstone test, the block scan, the write-out -
+//     only when the whole result fits out_cap - and the count.
 // The kernel waits for no other workgroup.
 #include <hip/hip_runtime.h>
 
@@ -82,15 +82,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_setop_groups(GroupSetParams p) {
             kept[q] = v;
             bool keep = i == 0u || prev != v;                             // first of its run
             prev = v;
-            if (keep) {
-                uint32_t seen = 0, last = 0xFFFFFFFFu;
-                for (uint32_t k = i; k < n_total && raw[k] == v; k++) {
-                    const uint32_t t = tags[k];
-                    seen += (t != last && t < n_req) ? 1u : 0u;
-                    last = t;
-                }
-                keep = seen == n_req && last < n_req;
-            }
+            if (keep) keep = ss_group_run_kept(raw, tags, i, n_total, n_req);
             if (keep && tomb_has(p.tomb, p.tomb_nwords, v)) keep = false;
             if (keep) { keepmask |= 1u << q; cnt++; }
         }

@@ -1,5 +1,6 @@
 // small_set_device.h — the three stages that the short-list set-op kernels share: k_setop_small (setop_small.hip),
-// k_setop_batch in both sizes (setop_batch.hip) and k_setop_groups (setop_groups.hip).
+// k_setop_batch in both sizes (setop_batch.hip), k_setop_groups (setop_groups.hip) and k_setop_groups_batch in both sizes
+// (setop_groups_batch.hip) - and the survive rule of the two group kernels, ss_group_run_kept.
 //
 // A short query - at most MAX_LISTS lists that hold at most PER_THREAD x THREADS postings in PER_WAVE x WAVES DV1 blocks -
 // is decoded, ordered and filtered in the LDS of one workgroup:
@@ -131,6 +132,21 @@ __device__ __forceinline__ uint32_t ss_block_scan(uint32_t cnt, uint32_t *wsum, 
     for (uint32_t w = 0; w < WAVES; w++) { if (w < wv) pos += wsum[w]; sum += wsum[w]; }
     *total = sum;
     return pos;
+}
+
+// The survive rule of the group kernels.  raw[0, n_total): every id at its rank; tags[]: the group tag of the id at that rank -
+// the required groups are tags 0 .. n_req - 1, the excluded lists tag n_req; lists are in tag order, so the tags inside a run of
+// equal ids ascend.  i is the head of a run (at most MAX_LISTS long: a list holds an id once): the id survives when every
+// required tag occurs in the run and its last tag is not the excluded one.  A repeated tag is counted once.
+__device__ __forceinline__ bool ss_group_run_kept(const uint32_t *raw, const uint8_t *tags, uint32_t i, uint32_t n_total, uint32_t n_req) {
+    const uint32_t v = raw[i];
+    uint32_t seen = 0, last = 0xFFFFFFFFu;
+    for (uint32_t k = i; k < n_total && raw[k] == v; k++) {
+        const uint32_t t = tags[k];
+        seen += (t != last && t < n_req) ? 1u : 0u;
+        last = t;
+    }
+    return seen == n_req && last < n_req;
 }
 
 }  // namespace ii2

@@ -90,6 +90,32 @@ def pack_andnot(groups, exclude):
     return group_first, group_not, segs, np.array(first, np.uint64), np.array(end, np.uint64)
 
 
+def pack_group_batch(queries):
+    """The flat arrays ii2_query_batch_groups takes, from queries = [(groups, exclude), ...] with groups / exclude = [[(segment,
+    first, end), ...], ...] as pack_andnot takes them: (query_first u64 [Q + 1], group_first u64 [G + 1], group_not u8 [G],
+    segments [R], list_first u64 [R], list_end u64 [R]) - within every query the required groups first (flags 0), then the
+    excluded ones (flags 1); query q owns the groups query_first[q] .. query_first[q + 1] - 1, group g the ranges
+    group_first[g] .. group_first[g + 1] - 1.  Pure host code: the segments are passed through as they are."""
+    query_first = np.zeros(len(queries) + 1, np.uint64)
+    group_first, group_not = [0], []
+    segs, first, end = [], [], []
+    for q, (groups, exclude) in enumerate(queries):
+        groups, exclude = list(groups), list(exclude)
+        for g, ranges in enumerate(groups + exclude):
+            for s, a, b in ranges:
+                a, b = int(a), int(b)
+                if a < 0 or b < 0:
+                    raise ValueError(f"query {q}: group {g}: negative list index")
+                segs.append(s)
+                first.append(a)
+                end.append(b)
+            group_first.append(len(segs))
+            group_not.append(0 if g < len(groups) else 1)
+        query_first[q + 1] = len(group_not)
+    return (query_first, np.array(group_first, np.uint64), np.array(group_not, np.uint8), segs, np.array(first, np.uint64),
+            np.array(end, np.uint64))
+
+
 class DeviceArray:
     """A raw HBM buffer owned by a Context."""
 
@@ -411,6 +437,26 @@ class Context:
         self._ck(self.lib.ii2_query_batch(self.h, len(queries), op.ctypes.data_as(_lib.u8p), query_first.ctypes.data_as(_lib.u64p), segs,
                                           first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None,
                                           _ptr(out), out.count, off.ctypes.data_as(_lib.u64p)))
+        return out, off
+
+    def query_batch_groups(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
+        """Many AND-of-ORs / NOT queries in one call (ii2_query_batch_groups): queries = [(groups, exclude), ...], each pair as
+        andnot_ranges takes it - the ids found in at least one list of every group of `groups` and in no list of any group of
+        `exclude`; one group and no exclusion is a union.  Returns (DeviceArray ids, offsets): result q is ids[offsets[q] :
+        offsets[q + 1]].  The default `out` holds 256 ids per block of each query's required group with the fewest blocks."""
+        query_first, group_first, group_not, qsegs, first, end = pack_group_batch(queries)
+        n = len(qsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in qsegs])
+        if out is None:
+            blocks = 0
+            for groups, _ in queries:
+                blocks += min((sum(s.range_blocks(int(a), int(b), self) for s, a, b in g) for g in groups), default=0)
+            out = self.empty(max(blocks * 256, 1))
+        off = np.zeros(len(queries) + 1, np.uint64)
+        self._ck(self.lib.ii2_query_batch_groups(self.h, len(queries), query_first.ctypes.data_as(_lib.u64p), group_first.ctypes.data_as(_lib.u64p),
+                                                 group_not.ctypes.data_as(_lib.u8p), segs, first.ctypes.data_as(_lib.u64p),
+                                                 end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None, _ptr(out), out.count,
+                                                 off.ctypes.data_as(_lib.u64p)))
         return out, off
 
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,

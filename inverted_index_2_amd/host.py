@@ -62,6 +62,7 @@ def _lib_typed():
         lib.ii2h_prefix_search.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         for f in ("ii2h_result_term_len", "ii2h_result_values_len"):
             getattr(lib, f).restype = C.c_uint64
@@ -177,7 +178,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectMany)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -212,6 +213,20 @@ class InvertedIndex(_Target):
         out = np.zeros(max(n.value, 1), np.uint32)
         self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
         return out[: n.value].tolist()
+
+    def intersect_batch(self, queries) -> List[List[int]]:
+        """Many intersect_except queries, queries = [(terms, exclude), ...], in one device call (IntersectMany: one
+        ii2_query_batch_groups call - a second one when the results exceed its first buffer - and one download); result q is
+        that of intersect_except(*queries[q])."""
+        queries = [(list(t), list(x)) for t, x in queries]
+        blob, off = _pack([term for t, x in queries for term in t + x])
+        q_first = np.zeros(len(queries) + 1, np.uint64)
+        q_first[1:] = np.cumsum([len(t) + len(x) for t, x in queries], dtype=np.uint64) if queries else []
+        q_req = np.array([len(t) for t, _ in queries], np.uint64)
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_batch(self.h, blob.ctypes.data, off.ctypes.data, q_first.ctypes.data, q_req.ctypes.data, len(queries),
+                                               C.byref(n)))
+        return [vals for _, vals in self._results(n.value)]
 
     @property
     def n_shards(self) -> int:

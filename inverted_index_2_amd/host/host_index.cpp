@@ -16,6 +16,7 @@
 //   shardKey                                         shard.go:362-378
 //   Intersect(terms)                                 additive
 //   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
+//   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //
 // Built as its own library (libii2_host.so) that only sees include/ii2.h and links libii2_hip.so:
 // the product library exports the C ABI and nothing else.  A small C facade (ii2h_*) at the bottom
@@ -30,6 +31,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/ii2.h"
@@ -928,6 +930,90 @@ class InvertedIndex {
         if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
         return ids;
     }
+    // additive: MANY IntersectExcept queries, queries[q] = (terms, except), in one ii2_query_batch_groups call - with a second one
+    // when the results exceed FIRST_CAP ids, see below - one wait and one download.  Per term the groups are built exactly as IntersectExcept builds them - one one-list range per segment of the
+    // term's shard that holds it, the excluded terms' groups flagged, an excluded term found in no segment dropped.  A required
+    // term found in no segment (or no term at all) makes that query one without groups - its result is empty, the call goes
+    // on.  The library takes result bounds below 2^32 ids per call (II2_ERANGE beyond: send such a bulk in parts).  Like
+    // Intersect and Read, no tombstone filter.
+    std::vector<std::vector<uint32_t>> IntersectMany(const std::vector<std::pair<std::vector<Term>, std::vector<Term>>> &queries) const {
+        std::vector<std::vector<uint32_t>> out(queries.size());
+        if (queries.empty()) return out;
+        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
+        std::vector<uint64_t> query_first{0}, group_first{0};
+        std::vector<uint8_t> group_not;
+        std::vector<const ii2_seg *> segs;
+        std::vector<uint64_t> first, end;
+        // one one-list range per segment that holds the term; returns the term's postings bound (see Intersect), 0: in no segment
+        auto gather = [&](const Term &t) {
+            uint64_t post = 0;
+            if (Shard *sh = find_shard(shard_key(t))) {
+                for (auto &sg : sh->snapshot()) {
+                    const std::vector<Term> &T = sg->terms;
+                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
+                    if (j == T.size() || T[j] != t) continue;
+                    ii2_seg_info info;
+                    ii2_seg_get_info(sg->seg->h, &info);
+                    held.push_back(sg);
+                    segs.push_back(sg->seg->h);
+                    first.push_back(j);
+                    end.push_back(j + 1);
+                    post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
+                }
+            }
+            return post;
+        };
+        // the output's size: per query the smallest REQUIRED term's bound, as in Intersect; past FIRST_CAP ids in all the first
+        // call tries FIRST_CAP, and results that do not fit are written by a second call with the size the first one reported
+        // (II2_ECAPACITY writes nothing and fills the offsets)
+        constexpr uint64_t FIRST_CAP = 1u << 22;
+        uint64_t total = 0;
+        for (auto &qe : queries) {
+            const size_t g_mark = group_first.size(), n_mark = group_not.size(), r_mark = segs.size();
+            uint64_t bound = qe.first.empty() ? 0 : ~0ull;
+            for (auto &t : qe.first) {
+                const uint64_t post = gather(t);
+                bound = std::min(bound, post);
+                if (!post) break;                                // a required term in no segment: nothing is under every term
+                group_first.push_back(segs.size());
+                group_not.push_back(0);
+            }
+            if (bound) {
+                for (auto &t : qe.second) {
+                    if (!gather(t)) continue;                    // an excluded term in no segment removes nothing
+                    group_first.push_back(segs.size());
+                    group_not.push_back(1);
+                }
+            } else {                                             // the query keeps its place, without a group
+                group_first.resize(g_mark);
+                group_not.resize(n_mark);
+                segs.resize(r_mark);
+                first.resize(r_mark);
+                end.resize(r_mark);
+            }
+            query_first.push_back(group_not.size());
+            total += bound;
+        }
+        std::vector<uint64_t> off(queries.size() + 1, 0);
+        uint64_t cap = std::min(total, FIRST_CAP);
+        DevMem d_out(ctx_);
+        for (int attempt = 0;; attempt++) {
+            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect batch");
+            const int rc = ii2_query_batch_groups(ctx_, queries.size(), query_first.data(), group_first.data(), group_not.data(), segs.data(),
+                                                  first.data(), end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, off.data());
+            if (rc != II2_ECAPACITY || attempt) {
+                ck(ctx_, rc, "intersect batch");
+                break;
+            }
+            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect batch");
+            d_out.p = nullptr;
+            cap = off.back();
+        }
+        std::vector<uint32_t> all(off.back());
+        if (!all.empty()) ck(ctx_, ii2_copy_d2h(ctx_, all.data(), d_out.p, all.size() * sizeof(uint32_t)), "intersect batch");
+        for (size_t q = 0; q < queries.size(); q++) out[q].assign(all.begin() + off[q], all.begin() + off[q + 1]);
+        return out;
+    }
     size_t ShardCount() const { std::lock_guard<std::mutex> g(mu_); return shards_.size(); }
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
 
@@ -1126,6 +1212,23 @@ int ii2h_intersect(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, ui
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->IntersectExcept(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
+}
+// n_q queries over the terms (bytes, off): query q owns terms q_first[q] .. q_first[q + 1] - 1, the first q_req[q] of them required, the
+// others excluded.  Result q: the values of the target's result q (its term is empty)
+int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req, uint64_t n_q,
+                         uint64_t *n_results) {
+    H_TRY(t, {
+        const std::vector<Term> terms = unpack_terms(bytes, off, n_q ? q_first[n_q] : 0);
+        std::vector<std::pair<std::vector<Term>, std::vector<Term>>> queries(n_q);
+        for (uint64_t q = 0; q < n_q; q++) {
+            const uint64_t a = q_first[q], m = std::min(a + q_req[q], q_first[q + 1]);
+            queries[q].first.assign(terms.begin() + a, terms.begin() + m);
+            queries[q].second.assign(terms.begin() + m, terms.begin() + q_first[q + 1]);
+        }
+        t->result.clear();
+        for (auto &ids : t->index->IntersectMany(queries)) t->result.push_back(TermValues{Term(), std::move(ids)});
+        *n_results = t->result.size();
+    })
 }
 int ii2h_removed_values(ii2h_target *t, uint64_t *n_ids) {
     H_TRY(t, { Shard *s = t->shard ? t->shard.get() : t->index->OnlyShard(); t->ids = s ? s->RemovedValues() : std::vector<uint32_t>(); *n_ids = t->ids.size(); })

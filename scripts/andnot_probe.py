@@ -33,8 +33,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from inverted_index_2_amd import _lib  # noqa: E402
 if args.lib:
     _lib.LIB_PATH = os.path.abspath(args.lib)
-    if not hasattr(C.CDLL(_lib.LIB_PATH), "ii2_andnot_ranges"):      # a library from before the entry point: the yardstick only
-        _lib.PROTOTYPES.pop("ii2_andnot_ranges", None)
+    other = C.CDLL(_lib.LIB_PATH)
+    for name in [n for n in _lib.PROTOTYPES if not hasattr(other, n)]:      # a library from before an entry point (this probe's
+        _lib.PROTOTYPES.pop(name)                                           # ii2_andnot_ranges among them: the yardstick only)
 from inverted_index_2_amd import Context, synth  # noqa: E402
 
 N = max(int(os.environ.get("PROBE_N", "15")), 10)

@@ -34,8 +34,9 @@ args = ap.parse_args()
 from inverted_index_2_amd import _lib  # noqa: E402
 if args.lib:
     _lib.LIB_PATH = os.path.abspath(args.lib)
-    if not hasattr(C.CDLL(_lib.LIB_PATH), "ii2_query_batch"):      # a library from before the entry point: the yardstick only
-        _lib.PROTOTYPES.pop("ii2_query_batch", None)
+    other = C.CDLL(_lib.LIB_PATH)
+    for name in [n for n in _lib.PROTOTYPES if not hasattr(other, n)]:      # a library from before an entry point (this probe's
+        _lib.PROTOTYPES.pop(name)                                           # ii2_query_batch among them: the yardstick only)
 from inverted_index_2_amd import Context, synth  # noqa: E402
 from inverted_index_2_amd.engine import pack_batch  # noqa: E402
 
