@@ -494,6 +494,14 @@ int ii2_profile_read(ii2_ctx *ctx, double *total_ms, uint64_t *launches);
 int ii2_ctx_counters(ii2_ctx *ctx, uint64_t *out, uint32_t n);
 int ii2_profile_region(ii2_ctx *ctx, int begin);
 int ii2_profile_region_ms(ii2_ctx *ctx, double *ms);
+/* How often this context took each kernel path since it was created: out[i] = count of path i.  n = words `out` holds
+ * (at most that many are written); returns the number of path ids the library knows.  A path is one host decision that selects a
+ * kernel, a template instantiation or a kernel sequence (DESIGN.md has the list); a path chosen through another - a batch's
+ * single query, the driver union of the group path, the required part of a NOT - is counted as well.  Host words only: the
+ * kernels and their arguments are the same with or without a reader. */
+int ii2_ctx_paths(ii2_ctx *ctx, uint64_t *out, uint32_t n);
+/* Name of path i ("and.small", "or.rank", ...), NULL beyond the last id.  Needs no context and no GPU. */
+const char *ii2_path_name(uint32_t i);
 
 #ifdef __cplusplus
 }

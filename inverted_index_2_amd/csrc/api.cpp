@@ -969,6 +969,29 @@ int ii2_ctx_counters(ii2_ctx *ctx, uint64_t *out, uint32_t n) {
     return II2_OK;
 }
 
+// the names of ii2::Path, in the enum's order
+static const char *const PATH_NAMES[] = {
+    "and.small", "and.and2_fused", "and.and2_split", "and.dense2", "and.dense3", "and.dense4",
+    "and.tiles_pair", "and.tiles", "and.tiles_wide", "and.tiles_sub", "and.tiles_wide_sub",
+    "or.small", "or.rank", "or.stream2", "or.stream3", "or.stream4", "or.tiles", "or.tiles_wide", "or.merge",
+    "or.many", "or.many_window", "or.many_count_first",
+    "ir.handoff", "ir.groups", "ir.probe", "ir.mark", "ir.probe_drop", "ir.mark_drop",
+    "andnot.small", "andnot.general",
+    "batch.tiny", "batch.small", "batch.single", "batch.pack",
+    "gbatch.tiny", "gbatch.small", "gbatch.single", "gbatch.pack",
+    "span.fetch", "span.bounds",
+};
+static_assert(sizeof PATH_NAMES / sizeof PATH_NAMES[0] == ii2::P_COUNT, "one name per ii2::Path");
+
+int ii2_ctx_paths(ii2_ctx *ctx, uint64_t *out, uint32_t n) {
+    if (!ctx || (!out && n)) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    for (uint32_t i = 0; i < n && i < ii2::P_COUNT; i++) out[i] = ctx->paths[i];
+    return (int)ii2::P_COUNT;
+}
+
+const char *ii2_path_name(uint32_t i) { return i < ii2::P_COUNT ? PATH_NAMES[i] : nullptr; }
+
 int ii2_debug_read(ii2_ctx *ctx, uint64_t *out, uint64_t n_words) {
     if (!ctx || !out || !ctx->d_debug) return II2_EINVAL;
     std::lock_guard<std::mutex> g(ctx->mu);

@@ -12,6 +12,23 @@
 
 #include "../../include/ii2.h"
 
+// The kernel paths of the set operations (ii2_ctx_paths / ii2_path_name): one id per host decision that selects
+// another kernel, template instantiation or kernel sequence.  The names live in api.cpp (PATH_NAMES), in this order.
+namespace ii2 {
+enum Path : uint32_t {
+    P_AND_SMALL, P_AND_AND2_FUSED, P_AND_AND2_SPLIT, P_AND_DENSE2, P_AND_DENSE3, P_AND_DENSE4,
+    P_AND_TILES_PAIR, P_AND_TILES, P_AND_TILES_WIDE, P_AND_TILES_SUB, P_AND_TILES_WIDE_SUB,
+    P_OR_SMALL, P_OR_RANK, P_OR_STREAM2, P_OR_STREAM3, P_OR_STREAM4, P_OR_TILES, P_OR_TILES_WIDE, P_OR_MERGE,
+    P_OR_MANY, P_OR_MANY_WINDOW, P_OR_MANY_COUNT_FIRST,
+    P_IR_HANDOFF, P_IR_GROUPS, P_IR_PROBE, P_IR_MARK, P_IR_PROBE_DROP, P_IR_MARK_DROP,
+    P_ANDNOT_SMALL, P_ANDNOT_GENERAL,
+    P_BATCH_TINY, P_BATCH_SMALL, P_BATCH_SINGLE, P_BATCH_PACK,
+    P_GBATCH_TINY, P_GBATCH_SMALL, P_GBATCH_SINGLE, P_GBATCH_PACK,
+    P_SPAN_FETCH, P_SPAN_BOUNDS,
+    P_COUNT
+};
+}  // namespace ii2
+
 // mailbox layout (u64 words; h_mail and d_mail both hold II2_MAIL_WORDS)
 constexpr size_t II2_MAIL_WORDS = 1024;
 constexpr size_t II2_MAIL_COUNT = 200;     // word of h_mail that receives the result count of ii2_intersect / ii2_union
@@ -111,7 +128,9 @@ struct ii2_ctx {
     int world = 1, rank = 0;
     uint64_t comm_syncs = 0;            // host waits inside the exchange entry points (what a chunked exchange pays per chunk)
     int cu_count = 256;
+    uint64_t paths[ii2::P_COUNT] = {};  // how often each kernel path was taken (ii2_ctx_paths): host words, bumped under mu where the launch is decided
 };
+static inline void took(ii2_ctx *ctx, ii2::Path p) { ctx->paths[p]++; }
 
 // skip table + payload of one encoded segment; shared by the views made with ii2_seg_select
 namespace ii2 {
@@ -334,6 +353,8 @@ struct BatchPackParams {
     uint32_t n_queries;
 };
 hipError_t launch_setop_batch(const BatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+constexpr uint32_t BATCH_FORM_TINY = 1u, BATCH_FORM_SMALL = 2u;
+uint32_t setop_batch_forms(const BatchParams &p);      // the forms of the batch kernel that launch runs (BATCH_FORM_*)
 
 // a short AND of ORs minus excluded lists in one workgroup (setop_groups.hip): the lists group by group, the required groups
 // first (tags 0 .. n_req - 1), the lists of all excluded groups last (tag n_req)
@@ -363,6 +384,7 @@ struct GroupBatchParams {
     const uint8_t *tag;          // [lists of the table]
 };
 hipError_t launch_setop_groups_batch(const GroupBatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+uint32_t setop_groups_batch_forms(const GroupBatchParams &p);      // the forms of its kernel that launch runs (BATCH_FORM_*)
 
 // OR of a few medium-size lists by ranking (union_rank.hip)
 constexpr uint32_t UNION_RANK_MAXL = 8;
@@ -426,6 +448,9 @@ struct DenseParams {
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})
 hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the kernel (sequence) those two launchers run for p: what they switch on and what setop.cpp records
+Path intersect_dense_path(const DenseParams &p);
+Path intersect_and2_path(const DenseParams &p);
 
 // OR of any number of lists, block by block (union_many.hip)
 struct UmRange {
@@ -551,6 +576,7 @@ hipError_t launch_max_u32(const uint32_t *v, uint64_t n, uint32_t *out, hipStrea
 constexpr uint32_t ISECT_GMAX = 16;         // driver blocks per tile (max)
 constexpr uint32_t ISECT_SMAX = 16384;      // doc span a tile's LDS byte map can cover
 hipError_t launch_intersect(const IntersectParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+Path intersect_tiles_path(const IntersectParams &p);      // the k_isect_tiles instantiation that launcher runs for p (what setop.cpp records)
 
 // merge / union (merge.hip)
 constexpr uint32_t MERGE_THREADS = 256;     // threads per workgroup of the tile kernel

@@ -975,6 +975,16 @@ __global__ __launch_bounds__(256) void k_isect_expand(IntersectParams p) {
     }
 }
 
+// the instantiation of the tile kernel for p: 64 lists need the wide descriptor load, split driver blocks the gallop-only form,
+// the plain two-list query the one with its list count compiled in
+Path intersect_tiles_path(const IntersectParams &p) {
+    const bool wide = desc_stride(p.n_lists) > 256u;
+    if (p.op_union) return wide ? P_OR_TILES_WIDE : P_OR_TILES;
+    if (p.sub > 1u) return wide ? P_AND_TILES_WIDE_SUB : P_AND_TILES_SUB;
+    if (wide) return P_AND_TILES_WIDE;
+    return p.n_lists == 2u && !p.sparse_driver ? P_AND_TILES_PAIR : P_AND_TILES;
+}
+
 hipError_t launch_intersect(const IntersectParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (p.n_tiles == 0) return hipSuccess;
     const uint64_t nthr = (uint64_t)p.n_tiles * (p.op_union ? p.n_lists : p.n_lists > 1u ? p.n_lists - 1u : 1u);
@@ -983,13 +993,15 @@ hipError_t launch_intersect(const IntersectParams &p, hipStream_t s, hipEvent_t 
     hipLaunchKernelGGL(k_isect_partition, dim3((unsigned)((pthr + 255) / 256)), dim3(256), 0, s, p);
     {
         const uint32_t grid = p.n_tiles < p.max_grid ? p.n_tiles : p.max_grid;
-        if (p.op_union && desc_stride(p.n_lists) > 256u) hipLaunchKernelGGL((k_isect_tiles<true, 0u, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.op_union) hipLaunchKernelGGL((k_isect_tiles<false, 0u, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.sub > 1u && desc_stride(p.n_lists) > 256u) hipLaunchKernelGGL((k_isect_tiles<true, 0u, false, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.sub > 1u) hipLaunchKernelGGL((k_isect_tiles<false, 0u, false, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (desc_stride(p.n_lists) > 256u) hipLaunchKernelGGL((k_isect_tiles<true, 0u, false>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.n_lists == 2u && !p.sparse_driver) hipLaunchKernelGGL((k_isect_tiles<false, 2u, false>), dim3(grid), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_isect_tiles<false, 0u, false>), dim3(grid), dim3(256), 0, s, p);
+        switch (intersect_tiles_path(p)) {
+        case P_OR_TILES_WIDE: hipLaunchKernelGGL((k_isect_tiles<true, 0u, true>), dim3(grid), dim3(256), 0, s, p); break;
+        case P_OR_TILES: hipLaunchKernelGGL((k_isect_tiles<false, 0u, true>), dim3(grid), dim3(256), 0, s, p); break;
+        case P_AND_TILES_WIDE_SUB: hipLaunchKernelGGL((k_isect_tiles<true, 0u, false, true>), dim3(grid), dim3(256), 0, s, p); break;
+        case P_AND_TILES_SUB: hipLaunchKernelGGL((k_isect_tiles<false, 0u, false, true>), dim3(grid), dim3(256), 0, s, p); break;
+        case P_AND_TILES_WIDE: hipLaunchKernelGGL((k_isect_tiles<true, 0u, false>), dim3(grid), dim3(256), 0, s, p); break;
+        case P_AND_TILES_PAIR: hipLaunchKernelGGL((k_isect_tiles<false, 2u, false>), dim3(grid), dim3(256), 0, s, p); break;
+        default: hipLaunchKernelGGL((k_isect_tiles<false, 0u, false>), dim3(grid), dim3(256), 0, s, p); break;
+        }
     }
     if (p.n_tiles > SUMS_FROM_TILES) hipLaunchKernelGGL(k_isect_sums, dim3((p.n_sums + 3u) / 4u), dim3(256), 0, s, p);
     const uint32_t egrid = p.n_tiles < 4096u ? p.n_tiles : 4096u;

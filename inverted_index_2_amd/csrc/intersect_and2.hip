@@ -944,10 +944,13 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
 #undef II2_STAMP
 }
 
+// one launch (the look-back records are set) or two kernels
+Path intersect_and2_path(const DenseParams &p) { return p.lb.agg != nullptr ? P_AND_AND2_FUSED : P_AND_AND2_SPLIT; }
+
 hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
     const uint32_t grid = (p.n_waves + 3u) / 4u;
-    if (p.lb.agg != nullptr) {
+    if (intersect_and2_path(p) == P_AND_AND2_FUSED) {
         hipLaunchKernelGGL(k_and2_fused, dim3(grid), dim3(256), 0, s, p);
         if (ev1) (void)hipEventRecord(ev1, s);
         return hipGetLastError();

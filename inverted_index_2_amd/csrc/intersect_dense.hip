@@ -522,16 +522,23 @@ __global__ __launch_bounds__(256) void k_dense_expand(DenseParams p) {
 #undef II2_STAMP
 }
 
+// the instantiation of the streaming kernel for p: AND or OR, the list count compiled in
+Path intersect_dense_path(const DenseParams &p) {
+    const uint32_t k = p.n_lists <= 2u ? 0u : p.n_lists == 3u ? 1u : 2u;
+    return (Path)((p.is_union ? P_OR_STREAM2 : P_AND_DENSE2) + k);
+}
+
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
     const uint32_t grid = (p.n_waves + 3u) / 4u;
-    if (p.is_union) {
-        if (p.n_lists == 2u) hipLaunchKernelGGL((k_dense_tiles<2u, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (p.n_lists == 3u) hipLaunchKernelGGL((k_dense_tiles<3u, true>), dim3(grid), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((k_dense_tiles<4u, true>), dim3(grid), dim3(256), 0, s, p);
-    } else if (p.n_lists == 2u) hipLaunchKernelGGL((k_dense_tiles<2u, false>), dim3(grid), dim3(256), 0, s, p);
-    else if (p.n_lists == 3u) hipLaunchKernelGGL((k_dense_tiles<3u, false>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_dense_tiles<4u, false>), dim3(grid), dim3(256), 0, s, p);
+    switch (intersect_dense_path(p)) {
+    case P_OR_STREAM2: hipLaunchKernelGGL((k_dense_tiles<2u, true>), dim3(grid), dim3(256), 0, s, p); break;
+    case P_OR_STREAM3: hipLaunchKernelGGL((k_dense_tiles<3u, true>), dim3(grid), dim3(256), 0, s, p); break;
+    case P_OR_STREAM4: hipLaunchKernelGGL((k_dense_tiles<4u, true>), dim3(grid), dim3(256), 0, s, p); break;
+    case P_AND_DENSE2: hipLaunchKernelGGL((k_dense_tiles<2u, false>), dim3(grid), dim3(256), 0, s, p); break;
+    case P_AND_DENSE3: hipLaunchKernelGGL((k_dense_tiles<3u, false>), dim3(grid), dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((k_dense_tiles<4u, false>), dim3(grid), dim3(256), 0, s, p); break;
+    }
     hipLaunchKernelGGL(k_dense_expand, dim3(grid), dim3(256), 0, s, p);
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();

@@ -122,6 +122,7 @@ static int list_span(ii2_ctx *ctx, const SetList &l, ii2_seg::ListSpan *out) {
     ii2_skip e[2];
     uint32_t last = 0;
     hipStream_t st = ctx->stream;
+    took(ctx, P_SPAN_FETCH);
     HIP_TRY(ctx, hipMemcpyAsync(&e[0], l.v.skip, sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(&e[1], l.v.skip + (l.v.nblk - 1), sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(&last, l.v.last_doc, sizeof last, hipMemcpyDeviceToHost, st));
@@ -207,6 +208,7 @@ static int setop_small(ii2_ctx *ctx, bool is_union, const SetList *L, uint32_t n
     sp.ticket = ctx->d_small + (size_t)SMALL_SET_POSTINGS;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, is_union ? P_OR_SMALL : P_AND_SMALL);
     HIP_TRY(ctx, launch_setop_small(sp, ctx->stream, e0, e1));
     *taken = true;
     return II2_OK;
@@ -295,6 +297,7 @@ static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double pe
     hipStream_t st = ctx->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, and2 ? intersect_and2_path(dp) : intersect_dense_path(dp));
     if (and2 && dp.lb.agg) {           // (the one-launch form waits between workgroups: one such kernel per device at a time)
         if (int rcq = ii2_lookback_launch(ctx, true, [&] { return launch_intersect_and2(dp, st, e0, e1); })) return rcq;
     } else {
@@ -364,6 +367,7 @@ static int intersect_unlocked(ii2_ctx *ctx, uint32_t n, const ii2_seg *const *se
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, intersect_tiles_path(p));
     HIP_TRY(ctx, launch_intersect(p, ctx->stream, e0, e1));
     return II2_OK;
 }
@@ -433,6 +437,7 @@ static int union_stream(ii2_ctx *ctx, const SetList *L, uint32_t m, const SetOut
     if (int rc = dense_setup(ctx, dp, 16u, false, o)) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, intersect_dense_path(dp));
     HIP_TRY(ctx, launch_intersect_dense(dp, ctx->stream, e0, e1));
     *taken = true;
     return II2_OK;
@@ -468,6 +473,7 @@ static int union_unlocked(ii2_ctx *ctx, const SetList *all, uint32_t n, const Se
             set_out(up, o);
             hipEvent_t e0 = nullptr, e1 = nullptr;
             ii2_profile_pair(ctx, &e0, &e1);
+            took(ctx, P_OR_RANK);
             HIP_TRY(ctx, launch_union_rank(up, ctx->stream, e0, e1));
             *taken = true;
             return II2_OK;
@@ -508,6 +514,7 @@ static int union_unlocked(ii2_ctx *ctx, const SetList *all, uint32_t n, const Se
     if (int rc = tiles_setup(ctx, p, 1u, o)) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, intersect_tiles_path(p));
     HIP_TRY(ctx, launch_intersect(p, ctx->stream, e0, e1));
     *taken = true;
     return II2_OK;
@@ -534,6 +541,7 @@ static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t bloc
     }
     ii2_merge_stats st;
     std::memset(&st, 0, sizeof st);
+    took(ctx, P_OR_MERGE);
     if (int rc = merge_core(ctx, n, views, 1, blocks_ub, blocks_ub * II2_DV1_BLOCK, tomb, nullptr, d_out, cap, &st)) return rc;
     *count = st.n_out;
     return II2_OK;
@@ -670,6 +678,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
                       uint64_t *count) {
     hipStream_t st = ctx->stream;
     const size_t nr = rs.size();
+    took(ctx, P_OR_MANY);
     if (int rc = um_scratch_clean(ctx)) return rc;
     // range descriptors + block prefix: thousands of entries, through a grow-only pinned block
     const size_t desc_bytes = align_up(nr * sizeof(UmRange)), stage_bytes = um_desc_bytes(nr);
@@ -710,6 +719,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     if (!mirrored) {
         HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
         HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
+        took(ctx, P_SPAN_BOUNDS);
         HIP_TRY(ctx, launch_union_many_bounds(p, st));
         uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
         HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -733,6 +743,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     p.per_wave = um_per_wave(ctx, n_blocks);
     // several windows whose result may not fit: count first (nothing written), then write
     const bool count_first = n_win > 1 && cap < n_blocks * II2_DV1_BLOCK;
+    if (count_first) took(ctx, P_OR_MANY_COUNT_FIRST);
     for (int pass = count_first ? 0 : 1; pass < 2; pass++) {
         p.write = (uint32_t)pass;
         for (uint64_t w = 0; w < n_win; w++) {
@@ -742,6 +753,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
             const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 1 + 3) / 4, (uint64_t)ctx->cu_count * 8u);
             hipEvent_t e0 = nullptr, e1 = nullptr;
             ii2_profile_pair(ctx, &e0, &e1);
+            took(ctx, P_OR_MANY_WINDOW);
             HIP_TRY(ctx, launch_union_many_mark(p, st, e0, e1));
             HIP_TRY(ctx, launch_union_many_count(p, grid, st));
             HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, p.cnt, p.off, p.n_sum + 1, st));
@@ -844,6 +856,7 @@ static int ir_filter_pass(ii2_ctx *ctx, const char *who, const std::vector<Range
     const uint64_t runs = (nc + IR_PROBE_RUN - 1) / IR_PROBE_RUN;
     const bool mark = ctx->opt_ir_mark > 0 &&
                       (runs < 4u * (uint64_t)ctx->cu_count || (double)G.n_post <= (double)ctx->opt_ir_mark * (double)G.n_nonempty * (double)runs);
+    took(ctx, mark ? (G.drop ? P_IR_MARK_DROP : P_IR_MARK) : (G.drop ? P_IR_PROBE_DROP : P_IR_PROBE));
     const size_t desc_bytes = mark ? um_desc_bytes(nr) : align_up(G.n_nonempty * sizeof(IrList));
     uint8_t *h = nullptr;
     if (int rc = ir_stage(ctx, desc_bytes, &h)) return rc;
@@ -962,6 +975,7 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
             p.n_ranges = (uint32_t)nr;
             p.n_blocks = (uint32_t)G.n_blocks;
             p.bounds = d_bounds + 2 * i;
+            took(ctx, P_SPAN_BOUNDS);
             HIP_TRY(ctx, launch_union_many_bounds(p, st));
             at += um_desc_bytes(nr);
         }
@@ -980,6 +994,7 @@ static int intersect_groups(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::v
     }
     if (clo > chi) { *count = 0; return II2_OK; }
     // the driver's union: the candidates
+    took(ctx, P_IR_GROUPS);
     size_t drv = 0;
     for (size_t g = 1; g < gs.size(); g++) if (gs[g].n_post < gs[drv].n_post) drv = g;
     const uint64_t half = (gs[drv].n_post + 64) & ~63ull;
@@ -1090,7 +1105,10 @@ static int intersect_sized(ii2_ctx *ctx, const std::vector<RangeIn> &rs, std::ve
                     if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) { hs[g] = rs[r].seg; hl[g] = j; }
             shortest = std::min(shortest, G.n_post);
         }
-        if (single && cap >= shortest) return intersect_sync(ctx, (uint32_t)n_groups, hs, hl, tomb, d_out, cap, count);
+        if (single && cap >= shortest) {
+            took(ctx, P_IR_HANDOFF);
+            return intersect_sync(ctx, (uint32_t)n_groups, hs, hl, tomb, d_out, cap, count);
+        }
     }
     return intersect_groups(ctx, rs, gs, tomb, d_out, cap, count);
 }
@@ -1173,6 +1191,7 @@ static int andnot_small(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std:
     set_out(gp, o);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, P_ANDNOT_SMALL);
     HIP_TRY(ctx, launch_setop_groups(gp, ctx->stream, e0, e1));
     *taken = true;
     return II2_OK;
@@ -1250,6 +1269,7 @@ static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_
     // 4. the required part through the AND chooser - straight into d_out when nothing is excluded and the result surely fits,
     // else into the candidate array, which holds the shortest required group: neither a capacity error nor a partly written
     // result can occur there (tombstones are applied here, once)
+    took(ctx, P_ANDNOT_GENERAL);
     if (!ex.n_nonempty && cap >= shortest) return intersect_sized(ctx, rs, req, tomb, d_out, cap, count);
     if (int rc = grow_device(ctx, &ctx->d_an, &ctx->an_words, shortest + 1, (size_t)((shortest + 1 + (shortest + 1) / 4 + 63) & ~63ull), sizeof(uint32_t),
                              "ii2_andnot_ranges: candidate allocation failed"))
@@ -1348,7 +1368,7 @@ static int batch_blocks(ii2_ctx *ctx, size_t table_bytes, uint64_t nq, uint64_t 
 
 // The end of a batch call, behind its batch kernels: counts -> offsets, pack (tests the capacity on the device), offsets down;
 // the call's one wait.  `who` names the entry point in the message.
-static int batch_finish(ii2_ctx *ctx, const char *who, const BatchMem &m, uint64_t nq, uint64_t max_bound, uint32_t *d_out, uint64_t cap,
+static int batch_finish(ii2_ctx *ctx, const char *who, Path pack, const BatchMem &m, uint64_t nq, uint64_t max_bound, uint32_t *d_out, uint64_t cap,
                         uint64_t *out_off) {
     hipStream_t st = ctx->stream;
     uint8_t *d = m.d;
@@ -1364,6 +1384,7 @@ static int batch_finish(ii2_ctx *ctx, const char *who, const BatchMem &m, uint64
     {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
+        took(ctx, pack);
         HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st, e0, e1));
     }
     uint64_t *h_off = (uint64_t *)(m.h + m.up_bytes);
@@ -1467,6 +1488,7 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
         h_cnt[q] = 0;
         if (pl.kind == BP_EMPTY) continue;
         if (pl.kind == BP_LARGE) {
+            took(ctx, P_BATCH_SINGLE);
             uint64_t count = 0;
             uint32_t *slot = d_stage + pl.stage_off;
             int rc;
@@ -1513,9 +1535,12 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
         bp.cnt = (uint32_t *)(d + m.o_cnt);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
+        const uint32_t forms = setop_batch_forms(bp);
+        if (forms & BATCH_FORM_TINY) took(ctx, P_BATCH_TINY);
+        if (forms & BATCH_FORM_SMALL) took(ctx, P_BATCH_SMALL);
         HIP_TRY(ctx, launch_setop_batch(bp, st, e0, e1));
     }
-    return batch_finish(ctx, "ii2_query_batch", m, nq, max_bound, d_out, cap, out_off);
+    return batch_finish(ctx, "ii2_query_batch", P_BATCH_PACK, m, nq, max_bound, d_out, cap, out_off);
 }
 
 extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
@@ -1665,6 +1690,7 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
         m.h_cnt[q] = 0;
         if (pl.kind == BP_EMPTY) continue;
         if (pl.kind == BP_LARGE) {
+            took(ctx, P_GBATCH_SINGLE);
             const uint64_t g0 = query_first[q];
             uint64_t count = 0;
             const int64_t keep = ctx->opt_intersect_and2;
@@ -1698,9 +1724,12 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
         gp.b.cnt = (uint32_t *)(m.d + m.o_cnt);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
+        const uint32_t forms = setop_groups_batch_forms(gp);
+        if (forms & BATCH_FORM_TINY) took(ctx, P_GBATCH_TINY);
+        if (forms & BATCH_FORM_SMALL) took(ctx, P_GBATCH_SMALL);
         HIP_TRY(ctx, launch_setop_groups_batch(gp, st, e0, e1));
     }
-    return batch_finish(ctx, who, m, nq, max_bound, d_out, cap, out_off);
+    return batch_finish(ctx, who, P_GBATCH_PACK, m, nq, max_bound, d_out, cap, out_off);
 }
 
 extern "C" int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,

@@ -113,11 +113,15 @@ __global__ __launch_bounds__(PACK_THREADS) void k_batch_pack(BatchPackParams p) 
     }
 }
 
+// one launch per size class that holds a query
+uint32_t setop_batch_forms(const BatchParams &p) { return (p.n_tiny ? BATCH_FORM_TINY : 0u) | (p.n_small ? BATCH_FORM_SMALL : 0u); }
+
 hipError_t launch_setop_batch(const BatchParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
-    if (p.n_tiny)
+    const uint32_t forms = setop_batch_forms(p);
+    if (forms & BATCH_FORM_TINY)
         hipLaunchKernelGGL((k_setop_batch<256u, BATCH_TINY_POSTINGS, BATCH_TINY_BLOCKS>), dim3(p.n_tiny), dim3(256), 0, s, p, 0u);
-    if (p.n_small)
+    if (forms & BATCH_FORM_SMALL)
         hipLaunchKernelGGL((k_setop_batch<1024u, SMALL_SET_POSTINGS, SMALL_SET_BLOCKS>), dim3(p.n_small), dim3(1024), 0, s, p, p.n_tiny);
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();

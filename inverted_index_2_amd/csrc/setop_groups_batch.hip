@@ -104,11 +104,15 @@ __global__ __launch_bounds__(THREADS) void k_setop_groups_batch(GroupBatchParams
     if (tid == 0) p.cnt[bq.slot] = total < bq.bound ? total : bq.bound;
 }
 
+// one launch per size class that holds a query
+uint32_t setop_groups_batch_forms(const GroupBatchParams &p) { return (p.b.n_tiny ? BATCH_FORM_TINY : 0u) | (p.b.n_small ? BATCH_FORM_SMALL : 0u); }
+
 hipError_t launch_setop_groups_batch(const GroupBatchParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
-    if (p.b.n_tiny)
+    const uint32_t forms = setop_groups_batch_forms(p);
+    if (forms & BATCH_FORM_TINY)
         hipLaunchKernelGGL((k_setop_groups_batch<256u, BATCH_TINY_POSTINGS, BATCH_TINY_BLOCKS>), dim3(p.b.n_tiny), dim3(256), 0, s, p, 0u);
-    if (p.b.n_small)
+    if (forms & BATCH_FORM_SMALL)
         hipLaunchKernelGGL((k_setop_groups_batch<1024u, SMALL_SET_POSTINGS, SMALL_SET_BLOCKS>), dim3(p.b.n_small), dim3(1024), 0, s, p, p.b.n_tiny);
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();

@@ -116,6 +116,17 @@ def pack_group_batch(queries):
             np.array(end, np.uint64))
 
 
+def path_names():
+    """The names of the kernel paths the library counts (ii2_path_name), in id order.  Needs no context and no GPU."""
+    lib = _lib.load()
+    names = []
+    while True:
+        name = lib.ii2_path_name(len(names))
+        if name is None:
+            return names
+        names.append(name.decode())
+
+
 class DeviceArray:
     """A raw HBM buffer owned by a Context."""
 
@@ -201,6 +212,16 @@ class Context:
         out = (C.c_uint64 * 4)()
         self._ck(self.lib.ii2_ctx_counters(self.h, out, 4))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def paths(self):
+        """{path name: how often this context took that kernel path since it was created} (ii2_ctx_paths; the names come from
+        ii2_path_name).  The difference between two reads is what the calls in between launched."""
+        names = path_names()
+        out = (C.c_uint64 * len(names))()
+        n = self.lib.ii2_ctx_paths(self.h, out, len(names))
+        if n != len(names):
+            raise II2Error(-1, "ii2_ctx_paths: the library knows another number of paths than ii2_path_name")
+        return {name: int(out[i]) for i, name in enumerate(names)}
 
     def profile_read(self):
         """(total device ms, launches) of the dominant kernel since the last read (option profile.events)."""

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from inverted_index_2_amd import Context, II2Error, synth
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, path_delta, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -61,9 +61,17 @@ def andnot(ctx, groups, exclude, tomb=None):
 
 def check_all_modes(ctx, groups, exclude, want, tomb=None, modes=ALL_MODES):
     for m in modes:
-        with Options(ctx, **m):
+        with Options(ctx, **m), path_delta(ctx) as took:
             got = andnot(ctx, groups, exclude, tomb)
         assert np.array_equal(got, want), m
+        # one launch or the general form, never both; the one-launch form is the whole call; the forced filter is the one that ran
+        small, general = took.get("andnot.small", 0), took.get("andnot.general", 0)
+        assert small + general <= 1 and (small + general == 1 or not want.size), (m, took)
+        assert not small or (took == {"andnot.small": 1} and m.get("andnot__small") != 0), (m, took)
+        if m.get("intersect__ranges_mark") == 0:
+            assert "ir.mark" not in took and "ir.mark_drop" not in took, (m, took)
+        elif m.get("intersect__ranges_mark") == ALWAYS_MARK:
+            assert "ir.probe" not in took and "ir.probe_drop" not in took, (m, took)
 
 
 def raw(ctx, groups, flags, out, cap, tomb=None):
@@ -400,9 +408,10 @@ def test_one_launch_form_is_one_pass(ctx, pools):
     with Options(ctx, profile__events=1):
         ctx.profile_read()
         for small in (1, 0):
-            with Options(ctx, andnot__small=small):
+            with Options(ctx, andnot__small=small), path_delta(ctx) as took:
                 andnot(ctx, groups, exclude)
                 _, passes[small] = ctx.profile_read()
+            assert (took == {"andnot.small": 1}) if small else (took.get("andnot.general") == 1 and "andnot.small" not in took), took
     print("bracketed passes (andnot.small):", passes)
     assert passes[1] == 1
     assert passes[0] >= 2

@@ -4,18 +4,21 @@ import pytest
 
 from inverted_index_2_amd import synth
 from oracle import oracle as orc
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, path_delta, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-def _check(ctx, lists, removed=None):
+def _check(ctx, lists, removed=None, path=None):
+    """path: the kernel path every one of the calls must take (Context.paths()), and no other."""
     seg = ctx.encode_lists(lists)
     tomb = ctx.tombstones(removed) if removed is not None else None
     want = orc.intersect(lists, np.sort(removed) if removed is not None else ())
     for bitmap in (1, 0):      # very dense tiles: per-list bitmaps (default) vs the byte map
         ctx.set_option("intersect.bitmap", bitmap)
-        out, n = ctx.intersect([(seg, i) for i in range(len(lists))], tomb=tomb)
+        with path_delta(ctx) as took:
+            out, n = ctx.intersect([(seg, i) for i in range(len(lists))], tomb=tomb)
+        assert path is None or took == {path: 1}, (bitmap, took)
         got = out.download(n)
         assert n == want.size, (bitmap, n, want.size)
         assert np.array_equal(got, want), bitmap
@@ -23,7 +26,9 @@ def _check(ctx, lists, removed=None):
     # split over two segments as well (lists from different segments)
     if len(lists) >= 2:
         s0, s1 = ctx.encode_lists(lists[:1]), ctx.encode_lists(lists[1:])
-        out, n = ctx.intersect([(s0, 0)] + [(s1, i) for i in range(len(lists) - 1)], tomb=tomb)
+        with path_delta(ctx) as took:
+            out, n = ctx.intersect([(s0, 0)] + [(s1, i) for i in range(len(lists) - 1)], tomb=tomb)
+        assert path is None or took == {path: 1}, took
         assert np.array_equal(out.download(n), want)
 
 
@@ -148,8 +153,8 @@ def test_sixty_four_lists(ctx):
     rng = np.random.default_rng(64)
     core = sorted_unique(rng, 5000, 300_000)
     lists = [np.union1d(core, sorted_unique(rng, int(rng.integers(20_000, 60_000)), 300_000)).astype(np.uint32) for _ in range(64)]
-    _check(ctx, lists)
-    _check(ctx, lists[:63], removed=core[::7].copy())
+    _check(ctx, lists, path="and.tiles_wide")
+    _check(ctx, lists[:63], removed=core[::7].copy(), path="and.tiles")                # 254 descriptor words: the common instantiation
 
 
 @pytest.mark.parametrize("seed", range(4))
@@ -175,8 +180,8 @@ def test_rare_term_against_long_lists(ctx, n_rare):
     long1 = _gap_list(rng, 2_000_000, [1, 5, 20, 60], [.25, .25, .25, .25])
     long2 = sorted_unique(rng, 900_000, U)
     rare = np.union1d(sorted_unique(rng, n_rare, U), rng.choice(np.intersect1d(long1, long2), min(n_rare, 40), replace=False)).astype(np.uint32)
-    _check(ctx, [rare, long1])
-    _check(ctx, [long2, rare, long1], removed=rare[::3].copy())
+    _check(ctx, [rare, long1], path="and.tiles_sub")
+    _check(ctx, [long2, rare, long1], removed=rare[::3].copy(), path="and.tiles_sub")
 
 
 @pytest.mark.parametrize("n_lists", [4, 6, 8])
@@ -198,7 +203,7 @@ def test_rare_term_against_many_long_lists_all_at_once(ctx, n_lists):
         longs.append(np.union1d(base, keep).astype(np.uint32))
     longs[-1] = longs[-1][longs[-1] >= rare[40]]                                            # no block of this list before the 40th candidate
     lists = [rare, second] + longs
-    _check(ctx, lists)
-    _check(ctx, lists[::-1], removed=rare[::15].copy())
+    _check(ctx, lists, path="and.tiles_sub")
+    _check(ctx, lists[::-1], removed=rare[::15].copy(), path="and.tiles_sub")
     got = orc.intersect(lists)
     assert 100 < got.size < rare.size

@@ -8,7 +8,7 @@ import pytest
 
 from inverted_index_2_amd import synth
 from oracle import oracle as orc
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import blocks_of, ctx, path_delta, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 AND2_DEFAULT = 1
@@ -16,6 +16,30 @@ AND2_DEFAULT = 1
 
 def bernoulli(rng, p, lo, hi):
     return (np.flatnonzero(rng.random(hi - lo) < p) + lo).astype(np.uint32)
+
+
+def _docs_per_block(l):
+    """what the choosers look at: (first doc of the last block - first doc) / (blocks - 1)"""
+    n = blocks_of(l)
+    return (int(l[(n - 1) * 256]) - int(l[0])) / (n - 1)
+
+
+def dense_driver(lists):
+    """The AND chooser sends these lists to the streaming kernels: 2 - 4 lists, and the one with the fewest blocks (the first of
+    them) holds >= 1024 blocks at <= 1100 docs per block."""
+    nb = [blocks_of(l) for l in lists]
+    return 2 <= len(lists) <= 4 and min(nb) >= 1024 and 0 < _docs_per_block(lists[int(np.argmin(nb))]) <= 1100
+
+
+def stream_pacer(lists):
+    """The OR chooser sends these lists to the streaming kernel (when neither the one-workgroup kernel nor the ranking takes them
+    first): 2 - 4 lists, the one with the most blocks (the first of them) holds >= 1024 blocks at <= 1100 docs per block, and
+    the lists reach at most a quarter of its span + 65536 docs beyond it."""
+    nb = [blocks_of(l) for l in lists]
+    p = lists[int(np.argmax(nb))]
+    own = int(p[-1]) - int(p[0]) + 1
+    reach = max(int(l[-1]) for l in lists) - min(int(l[0]) for l in lists) + 1
+    return 2 <= len(lists) <= 4 and max(nb) >= 1024 and 0 < _docs_per_block(p) <= 1100 and reach <= own + own // 4 + 65536
 
 
 def _check(ctx, lists, removed=None, split=False):
@@ -40,7 +64,16 @@ def _check(ctx, lists, removed=None, split=False):
         ctx.set_option("intersect.dense", dense)
         ctx.set_option("intersect.and2", and2)
         out.upload(np.full(out.count, 0xDEADBEEF, np.uint32))
-        _, n = ctx.intersect(ls, tomb=tomb, out=out)
+        with path_delta(ctx) as took:
+            _, n = ctx.intersect(ls, tomb=tomb, out=out)
+        if not (dense and dense_driver(lists)):
+            assert took and not any(k.startswith(("and.dense", "and.and2")) for k in took), (dense, and2, took)
+        elif len(lists) > 2 or and2 == 0:
+            assert took == {f"and.dense{len(lists)}": 1}, (dense, and2, took)
+        elif and2 == 2:
+            assert took == {"and.and2_split": 1}, (dense, and2, took)
+        else:                                      # (one launch; a look-back wait that ran out repeats it through the two kernels)
+            assert took in ({"and.and2_fused": 1}, {"and.and2_fused": 1, "and.and2_split": 1}), (dense, and2, took)
         got = out.download(n)
         assert n == want.size, (dense, and2, n, want.size)
         assert np.array_equal(got, want), (dense, and2)
@@ -49,8 +82,10 @@ def _check(ctx, lists, removed=None, split=False):
     ctx.set_option("intersect.and2", AND2_DEFAULT)
     for bpw in (32, 64):                           # longer waves: several rounds per wave, carried boundary words
         ctx.set_option("intersect.dense_bpw", bpw)
-        _, n = ctx.intersect(ls, tomb=tomb, out=out)
+        with path_delta(ctx) as took:
+            _, n = ctx.intersect(ls, tomb=tomb, out=out)
         assert n == want.size and np.array_equal(out.download(n), want), bpw
+        assert not dense_driver(lists) or took == {f"and.dense{len(lists)}": 1}, (bpw, took)      # (two lists: and2 needs 16 blocks per wave)
     ctx.set_option("intersect.dense_bpw", 0)
     return want
 
@@ -60,6 +95,7 @@ def test_dense_bernoulli_lists(ctx, ps):
     rng = np.random.default_rng(int(sum(ps) * 1000))
     U = 1_600_000                                   # >= 1024 driver blocks at these densities
     lists = [bernoulli(rng, p, 0, U) for p in ps]
+    assert dense_driver(lists)
     want = _check(ctx, lists)
     assert want.size > 1000
     removed = bernoulli(rng, 0.02, 0, U)
@@ -167,12 +203,24 @@ def _check_union(ctx, lists, removed=None, split=False):
         seg = ctx.encode_lists(lists)
         ls = [(seg, i) for i in range(len(lists))]
     out = ctx.empty(sum(l.size for l in lists) + 16)
-    for stream in (1, 0):                          # the streaming kernel, then the fixed-range OR tiles as a second opinion
+    # the streaming kernel - by default behind the ranking, which takes <= 2^20 postings first, and with the ranking off - then the
+    # fixed-range OR tiles as a second opinion
+    postings = sum(l.size for l in lists)
+    for stream, rank in ((1, 1), (1, 0), (0, 1)):
         ctx.set_option("union.stream", stream)
-        _, n = ctx.union(ls, tomb=tomb, out=out)
-        assert n == want.size, (stream, n, want.size)
-        assert np.array_equal(out.download(n), want), stream
+        ctx.set_option("union.rank", rank)
+        with path_delta(ctx) as took:
+            _, n = ctx.union(ls, tomb=tomb, out=out)
+        assert n == want.size, (stream, rank, n, want.size)
+        assert np.array_equal(out.download(n), want), (stream, rank)
+        if rank and postings <= 1 << 20:
+            assert took == {"or.rank": 1}, (stream, rank, took)
+        elif stream and stream_pacer(lists):
+            assert took == {f"or.stream{len(lists)}": 1}, (stream, rank, took)
+        else:
+            assert took and not any(k.startswith("or.stream") for k in took), (stream, rank, took)
     ctx.set_option("union.stream", 1)
+    ctx.set_option("union.rank", 1)
     return want
 
 
@@ -181,6 +229,7 @@ def test_stream_union_bernoulli_lists(ctx, ps):
     rng = np.random.default_rng(int(sum(ps) * 977))
     U = 1_600_000
     lists = [bernoulli(rng, p, 0, U) for p in ps]
+    assert stream_pacer(lists)
     _check_union(ctx, lists)
     _check_union(ctx, lists, removed=bernoulli(rng, 0.05, 0, U))
     _check_union(ctx, lists[::-1], split=True)

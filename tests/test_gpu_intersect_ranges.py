@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from inverted_index_2_amd import Context, II2Error, synth
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, path_delta, sorted_unique  # noqa: F401
 from tests.test_config1_cpu import c1_segments
 
 pytestmark = pytest.mark.gpu
@@ -69,9 +69,22 @@ MODES = [{}, {"intersect__ranges": 1}, {"intersect__ranges": 1, "intersect__rang
 
 def check_all_modes(ctx, groups, want, tomb=None):
     for m in MODES:
-        with Options(ctx, **m):
+        with Options(ctx, **m), path_delta(ctx) as took:
             got = isect(ctx, groups, tomb)
         assert np.array_equal(got, want), m
+        # the mode took the paths it names: a non-empty result of two or more groups means every filter pass ran
+        forced = m.get("intersect__ranges") == 1
+        assert not (forced and "ir.handoff" in took), (m, took)
+        assert took.get("ir.handoff", 0) + took.get("ir.groups", 0) <= 1, (m, took)
+        if forced and len(groups) > 1 and want.size:
+            assert took.get("ir.groups") == 1, (m, took)
+            passes = len(groups) - 1
+            if m.get("intersect__ranges_mark") == 0:
+                assert took.get("ir.probe") == passes and "ir.mark" not in took, (m, took)
+            elif m.get("intersect__ranges_mark") == ALWAYS_MARK:
+                assert took.get("ir.mark") == passes and "ir.probe" not in took, (m, took)
+            else:
+                assert took.get("ir.probe", 0) + took.get("ir.mark", 0) == passes, (m, took)
 
 
 def test_c1_as_configured(ctx):

@@ -3,7 +3,7 @@ postings together) against numpy, with the general paths (option setop.small = 0
 import numpy as np
 import pytest
 
-from tests.gpu_util import ctx  # noqa: F401
+from tests.gpu_util import blocks_of, ctx, path_delta  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,12 +21,27 @@ def _check(ctx, lists, removed=None):
     seg = ctx.encode_lists(lists)
     ls = [(seg, i) for i in range(len(lists))]
     out = ctx.empty(sum(l.size for l in lists) + 8)
+    # what the one-workgroup kernel takes: non-empty lists of <= 128 blocks and <= 2048 (AND) / 8192 (OR) postings in all
+    blocks, postings = sum(blocks_of(l) for l in lists), sum(l.size for l in lists)
+    empty = any(l.size == 0 for l in lists)
     for small in (1, 0):
         ctx.set_option("setop.small", small)
-        _, n = ctx.intersect(ls, tomb=tomb, out=out)
+        with path_delta(ctx) as took:
+            _, n = ctx.intersect(ls, tomb=tomb, out=out)
         assert n == want_and.size and np.array_equal(out.download(n), want_and.astype(np.uint32)), ("and", small)
-        _, n = ctx.union(ls, tomb=tomb, out=out)
+        if empty:
+            assert took == {}, took
+        elif small and blocks <= 128 and postings <= 2048:
+            assert took == {"and.small": 1}, took
+        else:
+            assert took and "and.small" not in took, took
+        with path_delta(ctx) as took:
+            _, n = ctx.union(ls, tomb=tomb, out=out)
         assert n == want_or.size and np.array_equal(out.download(n), want_or.astype(np.uint32)), ("or", small)
+        if small and blocks <= 128 and postings <= 8192:                      # (an OR skips empty lists)
+            assert took == {"or.small": 1}, took
+        else:
+            assert took and "or.small" not in took, took
     ctx.set_option("setop.small", 1)
     seg.free()
     out.free()
@@ -113,10 +128,18 @@ def test_union_by_ranking(ctx, seed):
         seg = ctx.encode_lists(lists)
         ls = [(seg, i) for i in range(len(lists))]
         out = ctx.empty(sum(l.size for l in lists) + 8)
+        blocks, postings = sum(blocks_of(l) for l in lists), sum(l.size for l in lists)
         for rank in (1, 0):
             ctx.set_option("union.rank", rank)
-            _, n = ctx.union(ls, tomb=tomb, out=out)
+            with path_delta(ctx) as took:
+                _, n = ctx.union(ls, tomb=tomb, out=out)
             assert n == want.size and np.array_equal(out.download(n), want.astype(np.uint32)), rank
+            if blocks <= 128 and postings <= 8192:                                 # (the one-workgroup kernel comes first)
+                assert took == {"or.small": 1}, took
+            elif rank and postings <= 1 << 20:                                     # <= 8 lists of <= 2^20 postings in all
+                assert took == {"or.rank": 1}, took
+            else:
+                assert took and "or.rank" not in took, took
         ctx.set_option("union.rank", 1)
         seg.free()
         out.free()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from inverted_index_2_amd import II2Error
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, path_delta, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -138,7 +138,7 @@ def _paths_lists(rng):
     rank = [sorted_unique(rng, 60_000, 8_000_000) for _ in range(4)]
     stream = [sorted_unique(rng, 800_000, 1_200_000), sorted_unique(rng, 400_000, 1_200_000)]
     tile = [sorted_unique(rng, 150_000, 2_000_000) for _ in range(10)]
-    return {"small": small, "rank": rank, "stream": stream, "tile": tile}
+    return {"or.small": small, "or.rank": rank, "or.stream2": stream, "or.tiles": tile}       # (the key: the path ii2_union takes)
 
 
 def test_many_path_matches_union_on_few_lists(ctx):
@@ -149,13 +149,18 @@ def test_many_path_matches_union_on_few_lists(ctx):
         seg = ctx.encode_lists(lists)
         pairs = [(seg, i) for i in range(len(lists))]
         for t in (None, tomb):
-            out, n = ctx.union(pairs, tomb=t)
+            with path_delta(ctx) as took:
+                out, n = ctx.union(pairs, tomb=t)
+            assert took == {name: 1}, (name, took)
             want = out.download(n)
             assert np.array_equal(want, truth(lists, removed if t else ())), name
-            got = union(ctx, [(seg, 0, len(lists))], t)                  # <= 64 lists: ii2_union's own path
+            with path_delta(ctx) as took:
+                got = union(ctx, [(seg, 0, len(lists))], t)              # <= 64 lists: ii2_union's own path
+            assert took == {name: 1}, (name, took)
             assert np.array_equal(got, want), name
-            with Option(ctx, "union.many", 1, 0):
+            with Option(ctx, "union.many", 1, 0), path_delta(ctx) as took:
                 got = union(ctx, [(seg, 0, len(lists))], t)
+            assert took == {"or.many": 1, "or.many_window": 1}, (name, took)       # one window of 2^30 docs
             assert np.array_equal(got, want), name
 
 
