@@ -75,6 +75,28 @@ func (c *Ctx) Encode(postOff []uint64, values []uint32) (*Segment, error) {
 	return &Segment{s}, nil
 }
 
+// BuildStats mirrors ii2_build_stats.
+type BuildStats struct {
+	Pairs, Postings, NonEmpty uint64
+	Passes                    uint32
+}
+
+// SegBuild is the build step (ii2_seg_build): ONE segment of nLists lists from (list, value) pairs in any order, repeats
+// allowed - list t ends up holding, ascending and duplicate-free, every values[i] with listID[i] == t.  It replaces N calls of
+// Shard.Put (shard.go:33-67) and the merges that fold their direct segments (shard.go:163-212); no tombstone filter, as in Put.
+// A listID >= nLists is an error and leaves nothing allocated.
+func (c *Ctx) SegBuild(nLists uint64, listID, values []uint32) (*Segment, BuildStats, error) {
+	if len(listID) != len(values) {
+		return nil, BuildStats{}, fmt.Errorf("gpu: build: %d list ids for %d values", len(listID), len(values))
+	}
+	var s *C.ii2_seg
+	var st C.ii2_build_stats
+	if rc := C.ii2_seg_build(c.h, C.uint64_t(nLists), C.uint64_t(len(listID)), u32ptr(listID), u32ptr(values), C.II2_HOST, &s, &st); rc != 0 {
+		return nil, BuildStats{}, c.err("build", rc)
+	}
+	return &Segment{s}, BuildStats{uint64(st.n_pairs), uint64(st.n_postings), uint64(st.n_nonempty), uint32(st.n_passes)}, nil
+}
+
 // Decode is the decode step (file/reader.go:79-100).
 func (c *Ctx) Decode(s *Segment) (postOff []uint64, values []uint32, err error) {
 	var info C.ii2_seg_info

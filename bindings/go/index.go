@@ -16,8 +16,10 @@ package gpu
 // the C++ host mirror's InvertedIndex::PrefixSearch does (host/host_index.cpp).
 
 import (
+	"bytes"
 	"errors"
 	"fmt"
+	"sort"
 	"sync"
 	"sync/atomic"
 )
@@ -110,6 +112,92 @@ func ShardMerge(c *Ctx, s HostShard, reqCount, mCount int) (mergedSegmentsLen in
 		}
 	}
 	return n, nil
+}
+
+// Doc is one Put: the terms of a document and its value.
+type Doc struct {
+	Terms [][]byte
+	Val   uint32
+}
+
+// BatchShard is what the unchanged Go host code provides for a bulk Put: a place for one ordinary (non-direct) segment.
+type BatchShard interface {
+	// AddSegment makes a segment visible under a fresh key exactly as Put adds its own (shard.go:64): terms is its sorted
+	// dictionary, seg holds one list per term.  A shard on disk writes it like a merged segment first (file.NewWriter: term
+	// file, then the value file from Ctx.ExportSegment, both renamed when complete).
+	AddSegment(terms [][]byte, seg *Segment) error
+}
+
+// PutBatch is the bulk form of Shard.Put (additive; shard.go:33-67 N times plus the merges shard.go:163-212 that would fold the
+// N direct segments): the shard's dictionary is the sorted, duplicate-free terms of all docs (bytes.Compare order), every
+// (doc, term) is one (index of the term, val) pair, and ONE Ctx.SegBuild call sorts and encodes them into one segment.  No docs
+// or no terms: no segment.  Put itself is unchanged.
+func PutBatch(c *Ctx, s BatchShard, docs []Doc) error {
+	var terms [][]byte
+	for _, d := range docs {
+		terms = append(terms, d.Terms...)
+	}
+	if len(terms) == 0 {
+		return nil
+	}
+	sort.Slice(terms, func(i, j int) bool { return bytes.Compare(terms[i], terms[j]) < 0 })
+	n := 1
+	for i := 1; i < len(terms); i++ { // slices.Compact by bytes.Equal
+		if !bytes.Equal(terms[i], terms[n-1]) {
+			terms[n] = terms[i]
+			n++
+		}
+	}
+	terms = terms[:n]
+	var listID, vals []uint32
+	for _, d := range docs {
+		for _, t := range d.Terms {
+			i := sort.Search(len(terms), func(i int) bool { return bytes.Compare(terms[i], t) >= 0 })
+			listID = append(listID, uint32(i))
+			vals = append(vals, d.Val)
+		}
+	}
+	seg, _, err := c.SegBuild(uint64(len(terms)), listID, vals)
+	if err != nil {
+		return fmt.Errorf("s: put batch: %w", err)
+	}
+	if err = s.AddSegment(terms, seg); err != nil {
+		seg.Free()
+		return fmt.Errorf("s: put batch: %w", err)
+	}
+	return nil
+}
+
+// IndexPutBatch is the bulk form of InvertedIndex.Put (inverted_index.go:113-145): every doc's terms are grouped by shardKey
+// (shard.go:362-378) as Put groups them, and each shard that receives something gets one PutBatch.  shardOf returns the shard
+// of a key, creating it when needed (newShard, inverted_index.go:163-190).
+func IndexPutBatch(c *Ctx, shardKey func(term []byte) uint16, shardOf func(key uint16) (BatchShard, error), docs []Doc) error {
+	groups := map[uint16][]Doc{}
+	var keys []uint16
+	for _, d := range docs {
+		mine := map[uint16][][]byte{}
+		for _, t := range d.Terms {
+			k := shardKey(t)
+			mine[k] = append(mine[k], t)
+		}
+		for k, ts := range mine {
+			if _, seen := groups[k]; !seen {
+				keys = append(keys, k)
+			}
+			groups[k] = append(groups[k], Doc{ts, d.Val})
+		}
+	}
+	sort.Slice(keys, func(i, j int) bool { return keys[i] < keys[j] })
+	for _, k := range keys {
+		s, err := shardOf(k)
+		if err != nil {
+			return fmt.Errorf("index put batch: %w", err)
+		}
+		if err = PutBatch(c, s, groups[k]); err != nil {
+			return fmt.Errorf("index put batch: %w", err)
+		}
+	}
+	return nil
 }
 
 // IndexMerge is the body of InvertedIndex.Merge (inverted_index.go:62-109): `concurrency` workers,

@@ -19,6 +19,7 @@
  *   - per-call limits (II2_ERANGE beyond them): a merge takes < 2^32 input postings, < 2^31 input
  *     blocks and < 2^30 term slots; ii2_align_terms takes < 2^31 terms; one segment holds < 2^31
  *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls);
+ *     ii2_seg_build takes < 2^32 pairs for < 2^31 lists (the encoder's limits on the segment it makes apply unchanged);
  *     ii2_query_batch takes <= 2^20 queries whose result bounds (AND: the shortest operand, OR: the postings of
  *     its ranges) add up to < 2^32 ids; ii2_query_batch_groups takes <= 2^20 queries whose result bounds (the postings of each query's
  *     smallest required group) add up to < 2^32 ids, a query of at most II2_MAX_LISTS non-empty lists - required and excluded -
@@ -111,6 +112,25 @@ int ii2_copy_d2h(ii2_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes
  * list ascending and duplicate-free — what the index itself always produces. */
 int ii2_seg_encode(ii2_ctx *ctx, uint64_t n_lists, const uint64_t *post_off, const uint32_t *values,
                    int where, ii2_seg **out);
+/* Build step (bulk Put).  Replaces N calls of Shard.Put (shard.go:33-67), each of which writes its own direct segment, followed
+ * by the merges that fold those segments (shard.go:163-212): ONE segment from n_pairs (list, value) pairs in any order, repeats
+ * allowed.  *out is the DV1 segment of n_lists lists in which list t holds, ascending and duplicate-free, every v for which
+ * (t, v) occurs among the pairs - bit for bit what ii2_seg_encode returns for the same lists given in CSR form, and a segment
+ * like any other (merge, union, select, export, ii2_seg_allgather).  No tombstone filter: a Put applies none.
+ * list_id[n_pairs] and values[n_pairs] both live where `where` says.  n_pairs == 0: the segment of n_lists empty lists (the arrays
+ * may be NULL); n_lists == 0 with n_pairs > 0: II2_EINVAL.  A list_id >= n_lists is II2_EINVAL (found on the device while the
+ * keys are formed; the message names the first such pair), *out stays NULL and nothing stays allocated.
+ * On the device: a least-significant-digit radix sort of the keys list_id << 32 | value (8-bit digits, only the digits that can
+ * differ: stats->n_passes = ceil((32 + bit_width(n_lists - 1)) / 8), 0 without pairs), a pass that drops equal neighbours, a
+ * lookup of every list's offset, one readback and the two-pass encoder.  No workgroup of it waits for another (seg_build.hip). */
+typedef struct {
+    uint64_t n_pairs;      /* pairs read */
+    uint64_t n_postings;   /* distinct (list, value) pairs = postings of the segment */
+    uint64_t n_nonempty;   /* lists with >= 1 posting */
+    uint32_t n_passes;     /* radix passes run */
+} ii2_build_stats;
+int ii2_seg_build(ii2_ctx *ctx, uint64_t n_lists, uint64_t n_pairs, const uint32_t *list_id,
+                  const uint32_t *values, int where, ii2_seg **out, ii2_build_stats *stats /* may be NULL */);
 /* Adopt an already DV1-encoded segment (blk_off[n_lists+1], skip[n_blocks+1], payload[n_bytes]).
  * The caller states the lengths of its arrays; blk_off[n_lists] must equal n_blocks and
  * skip[n_blocks].byte_off must equal n_bytes, else II2_EINVAL — the library never reads past the

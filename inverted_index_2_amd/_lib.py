@@ -26,6 +26,10 @@ class MergeStats(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_terms_out", C.c_uint64), ("n_tiles", C.c_uint64)]
 
 
+class BuildStats(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_postings", C.c_uint64), ("n_nonempty", C.c_uint64), ("n_passes", C.c_uint32)]
+
+
 vp = C.c_void_p
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
@@ -46,6 +50,7 @@ PROTOTYPES = {
     "ii2_copy_h2d": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "ii2_copy_d2h": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "ii2_seg_encode": (C.c_int, [vp, C.c_uint64, vp, vp, C.c_int, vpp]),
+    "ii2_seg_build": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_int, vpp, C.POINTER(BuildStats)]),
     "ii2_seg_import": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_int, vpp]),
     "ii2_seg_decode": (C.c_int, [vp, vp, vp, vp, C.c_int]),
     "ii2_seg_export": (C.c_int, [vp, vp, vp, vp, vp]),

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, MergeStats, SegInfo
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, BuildStats, MergeStats, SegInfo
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -264,6 +264,25 @@ class Context:
             po[1:] = np.cumsum([a.size for a in arrs])
         flat = np.concatenate(arrs) if arrs else np.empty(0, np.uint32)
         return self.encode(po, flat)
+
+    def build_segment(self, list_ids, values, n_lists: int, where: int = II2_HOST):
+        """Build step (ii2_seg_build): one segment of n_lists lists from (list id, value) pairs in any order, repeats allowed -
+        the bulk form of Shard.Put (shard.go:33-67) and the merges that fold its segments (shard.go:163-212).  numpy arrays
+        with where == II2_HOST, DeviceArrays with II2_DEVICE.  Returns (Segment, BuildStats)."""
+        if where == II2_HOST:
+            list_ids = _np(list_ids, np.uint32)
+            values = _np(values, np.uint32)
+            n = list_ids.size
+            if values.size != n:
+                raise ValueError("build_segment: list_ids and values differ in length")
+        else:
+            n = list_ids.count
+            if values.count != n:
+                raise ValueError("build_segment: list_ids and values differ in length")
+        s, st = C.c_void_p(), BuildStats()
+        self._ck(self.lib.ii2_seg_build(self.h, int(n_lists), n, _ptr(list_ids) if n else None, _ptr(values) if n else None, where,
+                                        C.byref(s), C.byref(st)))
+        return Segment(self, s), st
 
     def import_dv1(self, n_postings: int, blk_off, skip, payload) -> "Segment":
         blk_off = _np(blk_off, np.uint32)

@@ -56,6 +56,7 @@ def _lib_typed():
         lib.ii2h_last_error.restype = C.c_char_p
         lib.ii2h_last_error.argtypes = [vp]
         lib.ii2h_put.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32]
+        lib.ii2h_put_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64]
         lib.ii2h_remove.argtypes = [vp, vp, C.c_uint64]
         lib.ii2h_merge.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         lib.ii2h_read.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64, C.c_int, u64p]
@@ -69,7 +70,7 @@ def _lib_typed():
             getattr(lib, f).argtypes = [vp, C.c_uint64]
         lib.ii2h_result_copy.argtypes = [vp, C.c_uint64, vp, vp]
         lib.ii2h_ids_copy.argtypes = [vp, vp]
-        for f in ("ii2h_segment_count", "ii2h_shard_count"):
+        for f in ("ii2h_segment_count", "ii2h_index_segment_count", "ii2h_shard_count"):
             getattr(lib, f).restype = C.c_uint64
             getattr(lib, f).argtypes = [vp]
         _typed = True
@@ -124,6 +125,17 @@ class _Target:
     def put(self, terms: List[bytes], val: int) -> None:
         blob, off = _pack(list(terms))
         self._ck(self.lib.ii2h_put(self.h, blob.ctypes.data, off.ctypes.data, len(terms), val))
+
+    def put_batch(self, docs: List[Tuple[List[bytes], int]]) -> None:
+        """Many puts at once, docs = [(terms, val), ...]: one merged-quality segment per shard that receives a term (PutBatch:
+        one ii2_seg_build call each) instead of one direct segment per put."""
+        docs = [(list(terms), int(val)) for terms, val in docs]
+        blob, off = _pack([t for terms, _ in docs for t in terms])
+        doc_first = np.zeros(len(docs) + 1, np.uint64)
+        if docs:
+            doc_first[1:] = np.cumsum([len(terms) for terms, _ in docs])
+        vals = np.array([val for _, val in docs] + [0], np.uint32)
+        self._ck(self.lib.ii2h_put_batch(self.h, blob.ctypes.data, off.ctypes.data, doc_first.ctypes.data, vals.ctypes.data, len(docs)))
 
     def _results(self, n: int) -> List[Tuple[bytes, List[int]]]:
         out = []
@@ -231,6 +243,11 @@ class InvertedIndex(_Target):
     @property
     def n_shards(self) -> int:
         return self.lib.ii2h_shard_count(self.h)
+
+    @property
+    def n_segments(self) -> int:
+        """Segments of all shards together (a shard exists once it has received a term)."""
+        return self.lib.ii2h_index_segment_count(self.h)
 
 
 class SegmentFiles(_Target):

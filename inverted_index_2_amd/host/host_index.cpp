@@ -8,6 +8,7 @@
 // package's Writer / Reader / RemoveSegment and the removed.list persistence).
 //
 //   Shard.Put / Read / Remove / Merge / MinMax      shard.go:33-298
+//   Shard.PutBatch / InvertedIndex.PutBatch          additive: many Puts as ONE merged-quality segment per shard (ii2_seg_build)
 //   NewShard (load existing files, removed.list)     shard.go:300-358
 //   file.Writer / Reader / RemoveSegment             file/writer.go, file/reader.go
 //   Segments.add ordering                            segments.go:56-64
@@ -268,6 +269,33 @@ class Shard {
         add(std::move(seg));       // make the new segment visible (shard.go:64)
     }
 
+    // additive: many Puts at once.  What N calls of Put (shard.go:33-67) and the merges that fold their N direct segments
+    // (shard.go:163-212) leave behind, made directly: the dictionary is the sorted, duplicate-free terms of all docs, every
+    // (doc, term) is one (index of the term, val) pair, and ONE ii2_seg_build call sorts and encodes them into one ordinary
+    // (non-direct) segment.  No tombstone filter, as in Put.  No docs or no terms: no segment.
+    void PutBatch(const std::vector<std::pair<std::vector<Term>, uint32_t>> &docs) {
+        std::vector<Term> terms;
+        for (auto &d : docs) terms.insert(terms.end(), d.first.begin(), d.first.end());
+        std::sort(terms.begin(), terms.end(), term_less);
+        terms.erase(std::unique(terms.begin(), terms.end()), terms.end());
+        if (terms.empty()) return;
+        std::vector<uint32_t> list_id, vals;
+        for (auto &d : docs)
+            for (auto &t : d.first) {
+                list_id.push_back((uint32_t)(std::lower_bound(terms.begin(), terms.end(), t, term_less) - terms.begin()));
+                vals.push_back(d.second);
+            }
+        ii2_seg *s = nullptr;
+        ck(ctx_, ii2_seg_build(ctx_, terms.size(), list_id.size(), list_id.data(), vals.data(), II2_HOST, &s, nullptr), "s: put batch");
+        Segment seg{now_ns(), std::move(terms), std::make_shared<SegHandle>(s)};
+        if (!basedir_.empty()) {   // written like a merged segment: term file + value file
+            try { write_segment(ctx_, seg); }
+            catch (const std::exception &e) { throw Error(std::string("index put batch: ") + e.what()); }
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        add(std::move(seg));
+    }
+
     // shard.go:72-75 + makeIterator :253-278 — merged view of all segments, [min,max] inclusive, no tombstones
     // The snapshot of shared pointers plays the part of the reference's per-segment read locks (segments.go:32-46):
     // a merge may detach and unlink these segments meanwhile, their device arrays live until the last reader lets go.
@@ -325,15 +353,8 @@ class Shard {
         Segment out;
         const bool any = merged_segment(ctx, segs, removed, &out);
         if (any && !basedir_.empty()) {            // file.NewWriter + Close: both files, renamed when complete
-            const std::string key = std::to_string(out.key);
-            try {
-                file::TermFile tf;
-                tf.terms = out.terms;
-                file::write_terms(basedir_, key, tf);
-                file::write_dv1(basedir_, key, Writer::export_dv1(ctx, out.seg->h));
-                file::commit(file::dv1_path(basedir_, key));
-                file::commit(file::tdx_path(basedir_, key));
-            } catch (const std::exception &e) { throw Error(std::string("s: merge: writer close: ") + e.what()); }
+            try { write_segment(ctx, out); }
+            catch (const std::exception &e) { throw Error(std::string("s: merge: writer close: ") + e.what()); }
         }
         {
             std::lock_guard<std::mutex> g(mu_);
@@ -373,6 +394,17 @@ class Shard {
     std::vector<std::shared_ptr<Segment>> snapshot() const { std::lock_guard<std::mutex> g(mu_); return segments_; }
 
    private:
+
+    // file.NewWriter + Close for a device-resident segment: both files, under their final names only when complete
+    void write_segment(ii2_ctx *ctx, const Segment &s) const {
+        const std::string key = std::to_string(s.key);
+        file::TermFile tf;
+        tf.terms = s.terms;
+        file::write_terms(basedir_, key, tf);
+        file::write_dv1(basedir_, key, Writer::export_dv1(ctx, s.seg->h));
+        file::commit(file::dv1_path(basedir_, key));
+        file::commit(file::tdx_path(basedir_, key));
+    }
 
     // segments.go:56-64 — insert before the first segment with terms >= new.terms (mu_ held, or the constructor)
     void add(Segment s) {
@@ -652,6 +684,16 @@ class InvertedIndex {
         std::map<uint32_t, std::vector<Term>> groups;
         for (auto &t : terms) groups[shard_key(t)].push_back(t);
         for (auto &g : groups) shard(g.first).Put(g.second, val);
+    }
+    // additive: every doc's terms grouped by shard as Put groups them, one Shard.PutBatch per shard that receives something
+    void PutBatch(const std::vector<std::pair<std::vector<Term>, uint32_t>> &docs) {
+        std::map<uint32_t, std::vector<std::pair<std::vector<Term>, uint32_t>>> groups;
+        for (auto &d : docs) {
+            std::map<uint32_t, std::vector<Term>> mine;
+            for (auto &t : d.first) mine[shard_key(t)].push_back(t);
+            for (auto &m : mine) groups[m.first].emplace_back(std::move(m.second), d.second);
+        }
+        for (auto &g : groups) shard(g.first).PutBatch(g.second);
     }
     void PutRemoved(const std::vector<uint32_t> &values) {                    // inverted_index.go:41-55
         for (auto &s : shard_list()) s.second->Remove(values);
@@ -1015,6 +1057,7 @@ class InvertedIndex {
         return out;
     }
     size_t ShardCount() const { std::lock_guard<std::mutex> g(mu_); return shards_.size(); }
+    size_t SegmentCount() const { size_t n = 0; for (auto &s : shard_list()) n += s.second->SegmentCount(); return n; }      // over all shards
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
 
    private:
@@ -1184,6 +1227,18 @@ const char *ii2h_last_error(const ii2h_target *t) { return t->err.c_str(); }
 int ii2h_put(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint32_t val) {
     H_TRY(t, { auto terms = unpack_terms(bytes, off, n); if (t->index) t->index->Put(terms, val); else t->shard->Put(terms, val); })
 }
+// n_docs docs, flat: doc d owns the terms doc_first[d] .. doc_first[d + 1] - 1 of (bytes, off) and the value vals[d]
+int ii2h_put_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *doc_first, const uint32_t *vals, uint64_t n_docs) {
+    H_TRY(t, {
+        const std::vector<Term> terms = unpack_terms(bytes, off, n_docs ? doc_first[n_docs] : 0);
+        std::vector<std::pair<std::vector<Term>, uint32_t>> docs(n_docs);
+        for (uint64_t d = 0; d < n_docs; d++) {
+            docs[d].first.assign(terms.begin() + doc_first[d], terms.begin() + doc_first[d + 1]);
+            docs[d].second = vals[d];
+        }
+        if (t->index) t->index->PutBatch(docs); else t->shard->PutBatch(docs);
+    })
+}
 int ii2h_remove(ii2h_target *t, const uint32_t *vals, uint64_t n) {
     H_TRY(t, { std::vector<uint32_t> v(vals, vals + n); if (t->index) t->index->PutRemoved(v); else t->shard->Remove(v); })
 }
@@ -1243,6 +1298,7 @@ void ii2h_ids_copy(const ii2h_target *t, uint32_t *out) {
     if (!t->ids.empty()) std::memcpy(out, t->ids.data(), t->ids.size() * 4);
 }
 uint64_t ii2h_segment_count(const ii2h_target *t) { return t->shard ? t->shard->SegmentCount() : 0; }
+uint64_t ii2h_index_segment_count(const ii2h_target *t) { return t->index ? t->index->SegmentCount() : 0; }      // the segments of all its shards
 uint64_t ii2h_shard_count(const ii2h_target *t) { return t->index ? t->index->ShardCount() : 1; }
 
 }  // extern "C"
