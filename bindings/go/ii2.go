@@ -515,6 +515,41 @@ func (c *Ctx) AndNotRangesHost(groupFirst []uint64, groupNot []uint8, segs []*Se
 	}
 }
 
+// CountStats mirrors ii2_count_stats.
+type CountStats struct {
+	Lists, Blocks, Decoded, Hits uint64
+	Windows                      uint32
+}
+
+// CountRanges is the facet count (ii2_count_ranges): per list named by the ranges - lists [listFirst[i], listEnd[i]) of
+// segs[i], in range order - the number of its ids that lie in the doc set, one pass over the encoded lists whatever their
+// number.  set is a device buffer of nSet ascending, duplicate-free ids, what every query entry point writes (AndNotRanges,
+// QueryBatch ...); set == nil means every doc: the lists' lengths.  A list named twice is counted twice; an empty list gets 0.
+func (c *Ctx) CountRanges(segs []*Segment, listFirst, listEnd []uint64, set unsafe.Pointer, nSet uint64) ([]uint64, CountStats, error) {
+	if len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return nil, CountStats{}, fmt.Errorf("count ranges: array lengths disagree")
+	}
+	var named uint64
+	for i := range segs {
+		if listEnd[i] < listFirst[i] {
+			return nil, CountStats{}, fmt.Errorf("count ranges: range %d ends before it begins", i)
+		}
+		named += listEnd[i] - listFirst[i]
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	counts := make([]uint64, named)
+	var st C.ii2_count_stats
+	rc := C.ii2_count_ranges(c.h, C.uint64_t(len(segs)), (**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd),
+		(*C.uint32_t)(set), C.uint64_t(nSet), nil, u64ptr(counts), C.uint64_t(named), &st)
+	if rc != 0 {
+		return nil, CountStats{}, c.err("count ranges", rc)
+	}
+	return counts, CountStats{uint64(st.n_lists), uint64(st.n_blocks), uint64(st.n_decoded), uint64(st.n_hits), uint32(st.n_windows)}, nil
+}
+
 // Union replaces PrefixSearch's append + slices.Sort + slices.Compact (inverted_index.go:274-292).
 func (c *Ctx) Union(listOff []uint64, values, removed []uint32) ([]uint32, error) {
 	return c.lists(true, listOff, values, removed)

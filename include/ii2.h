@@ -383,6 +383,37 @@ int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *que
                            const uint8_t *group_not, const ii2_seg *const *segs, const uint64_t *list_first,
                            const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap, uint64_t *out_off);
 
+/* Hits per list against a doc set - facet counts ("of the docs matching the query, how many per level=*, per host=*?") and,
+ * with the set "every doc", the document frequency of every term under a prefix.  The lists are named by n ranges exactly as
+ * ii2_union_ranges takes them (segments and views alike; a list may appear in several ranges; empty ranges and empty lists are
+ * allowed).  counts (host memory) receives one entry per list named, in range order - the lists list_first[0] .. list_end[0] - 1
+ * of range 0, then those of range 1, and so on: counts[k] = the ids of that list that lie in the set and are not in tomb (tomb
+ * may be NULL).  An empty list gets 0; a list named twice is counted twice.
+ *   - the set: d_set[n_set], a device array of this context's device, ascending and duplicate-free - what every query entry
+ *     point writes to d_out.  n_set == 0 with d_set != NULL: all counts are 0, nothing is launched.  d_set == NULL means "every
+ *     doc": the counts are the lists' lengths minus their removed ids (tomb == NULL: from the segments' host mirrors, without a
+ *     launch).  A set that is not ascending gives unspecified counts, never an access outside the call's buffers.
+ *   - counts_cap smaller than the number of lists named (the sum of list_end[i] - list_first[i]): II2_ECAPACITY, nothing is
+ *     launched and nothing written.  Bad ranges are rejected as ii2_union_ranges rejects them, under this entry point's name;
+ *     counts == NULL with lists named, or more than 2^32 set ids: II2_EINVAL.  II2_ERANGE at 2^32 - 2 blocks or ranges, or
+ *     2^31 lists named.
+ *   - all-or-nothing: every argument is checked before anything is launched; counts and stats are written only on success.
+ * One pass over the encoded lists, whatever their number: the set is marked once into the per-context doc bitmap of
+ * ii2_union_ranges (window by window over the doc span that the set and the lists share: option union.many_window_log2), then
+ * every block of the lists that can hold a set doc is decoded and each of its ids tested.  Blocks outside that span are not
+ * read, and neither are those that meet no marked 2048-doc chunk of the bitmap's summary (option count.summary_skip).  The call
+ * waits at most twice.  It is not a set operation: it takes no kernel path (ii2_ctx_paths). */
+typedef struct {
+    uint64_t n_lists;    /* lists named by the ranges = counts written */
+    uint64_t n_blocks;   /* DV1 blocks those lists own */
+    uint64_t n_decoded;  /* blocks decoded, summed over the windows (the others were skipped unread) */
+    uint64_t n_hits;     /* sum of the counts */
+    uint32_t n_windows;  /* doc windows processed (0: nothing was marked) */
+} ii2_count_stats;       /* 40 bytes */
+int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
+                     const uint64_t *list_end, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb,
+                     uint64_t *counts, uint64_t counts_cap, ii2_count_stats *stats /* may be NULL */);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -463,6 +494,8 @@ int ii2_selftest(ii2_ctx *ctx);
  *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)
+ *   count.summary_skip                      ii2_count_ranges: 1 (default) a block whose docs meet no marked 2048-doc chunk of the set's
+ *                                           bitmap is not decoded; 0 (tests, measuring) every block that meets the window is
  *   intersect.ranges                        ii2_intersect_ranges: 1 = the group path even for single-list groups (default 0: they go to
  *                                           ii2_intersect's paths when the result surely fits)
  *   intersect.ranges_mark                   its filters mark a group into the doc bitmap when the group holds at most N postings per

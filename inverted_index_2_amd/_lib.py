@@ -30,6 +30,11 @@ class BuildStats(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_postings", C.c_uint64), ("n_nonempty", C.c_uint64), ("n_passes", C.c_uint32)]
 
 
+class CountStats(C.Structure):
+    _fields_ = [("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64),
+                ("n_windows", C.c_uint32)]
+
+
 vp = C.c_void_p
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
@@ -81,6 +86,7 @@ PROTOTYPES = {
     "ii2_andnot_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_query_batch": (C.c_int, [vp, C.c_uint64, u8p, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_query_batch_groups": (C.c_int, [vp, C.c_uint64, u64p, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
+    "ii2_count_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, C.c_uint64, vp, u64p, C.c_uint64, C.POINTER(CountStats)]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

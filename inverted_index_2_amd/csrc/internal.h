@@ -108,6 +108,7 @@ struct ii2_ctx {
     bool um_dirty = false;              // a call stopped between mark and compact: scratch and staging are cleared / waited for first
     void *h_um = nullptr;               // pinned staging of its range descriptors (grow-only)
     size_t h_um_cap = 0;
+    int64_t opt_count_summary_skip = 1; // ii2_count_ranges: blocks whose docs meet no marked chunk of the bitmap's summary are not decoded (0: tests, measuring)
     int64_t opt_intersect_ranges = 0;   // 1: ii2_intersect_ranges takes the group path even where ii2_intersect's paths would do
     int64_t opt_ir_mark = 64;           // ... whose filters mark a group with at most this many postings per (list x 256 candidates), or
                                         //     fewer than 4 runs of 256 candidates per CU (0: always probe)
@@ -521,6 +522,35 @@ hipError_t launch_ir_probe(const IrParams &p, hipStream_t s, hipEvent_t ev0 = nu
 hipError_t launch_ir_test(const IrParams &p, hipStream_t s);
 hipError_t launch_ir_clear(const IrParams &p, uint32_t grid, hipStream_t s);
 hipError_t launch_ir_compact(const IrParams &p, hipStream_t s);
+
+// hits per list against a doc set (count_ranges.hip): the ranges' blocks as the block-wise OR walks them, one counter per list named
+constexpr uint32_t CR_DECODED_SLOTS = 64;       // words the waves' decoded-block counts are spread over (one word takes ~90 atomics / us)
+struct CountParams {
+    const UmRange *ranges;       // [n_ranges], none without blocks
+    const uint32_t *pre;         // [n_ranges + 1] exclusive prefix of the ranges' blocks
+    const uint32_t *out_first;   // [n_ranges] counter of each range's first list
+    uint32_t n_ranges;
+    uint32_t n_blocks;           // pre[n_ranges]
+    uint32_t per_wave;           // query blocks per wave of the count kernel
+    uint32_t summary_skip;       // 1: a block whose docs meet no marked 2048-doc chunk is not decoded (option count.summary_skip)
+    uint32_t win_lo;             // first doc of the window (a multiple of 32: word i <-> tombstone word win_lo / 32 + i)
+    uint32_t win_docs;           // docs of the window (<= 2^30)
+    uint32_t doc_lo, doc_hi;     // the docs of the window that can hit: it clipped to the set's and the lists' span (inclusive)
+    uint32_t n_sum;              // summary words of the window
+    uint32_t *bitmap;            // [n_sum * 2048] the per-context doc bitmap (UnionManyParams) ...
+    uint32_t *summary;           // [n_sum] ... and its summary
+    const uint32_t *set;         // [n_set] the doc set, ascending
+    uint64_t n_set;
+    const uint32_t *tomb;        // may be null
+    uint32_t tomb_nwords;
+    uint32_t pad;
+    uint32_t *counts;            // [lists named] hits per list, accumulated over the windows
+    uint32_t *decoded;           // [CR_DECODED_SLOTS] blocks decoded
+    uint32_t *edges;             // [2] k_cr_edges: the set's first and last id
+};
+hipError_t launch_cr_edges(const CountParams &p, hipStream_t s);
+hipError_t launch_cr_mark(const CountParams &p, hipStream_t s);
+hipError_t launch_cr_count(const CountParams &p, bool every_doc, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 }  // namespace ii2
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held

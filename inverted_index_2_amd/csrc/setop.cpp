@@ -809,6 +809,193 @@ extern "C" int ii2_union_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *
     return union_ranges_unlocked(ctx, n, segs, list_first, list_end, tomb, d_out, cap, count);
 }
 
+// ---- hits per list against a doc set ------------------------------------------------------------
+// what a call found out before its first launch: the checked ranges that own blocks, the counter of each one's first list, and
+// the totals
+struct CountIn {
+    std::vector<RangeIn> rs;
+    std::vector<uint32_t> out_first;
+    uint64_t n_named = 0, n_blocks = 0;
+};
+
+// counts and stats of a call that succeeded with nothing to count: every count 0
+static int count_done(const CountIn &in, uint64_t *counts, ii2_count_stats *stats) {
+    if (in.n_named) std::memset(counts, 0, in.n_named * sizeof(uint64_t));
+    if (stats) *stats = ii2_count_stats{in.n_named, in.n_blocks, 0, 0, 0};
+    return II2_OK;
+}
+
+// The block-wise count (count_ranges.hip) of the ranges' blocks against d_set - per window of the doc span that the set and the
+// lists share mark, count, clear - or, with d_set == NULL, against "every doc" minus the tombstones in one launch.  At most two
+// waits: the span fetch and the final read.
+static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts,
+                      ii2_count_stats *stats) {
+    hipStream_t st = ctx->stream;
+    const std::vector<RangeIn> &rs = in.rs;
+    const size_t nr = rs.size();
+    const bool every_doc = !d_set;
+    if (int rc = um_scratch_clean(ctx)) return rc;
+    // staging: range descriptors + block prefix, the ranges' first counters, and room for the counters on their way back
+    const size_t n_words = (size_t)in.n_named + CR_DECODED_SLOTS;
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), up_bytes = um_bytes + align_up(nr * sizeof(uint32_t));
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + n_words * sizeof(uint32_t), false, "ii2_count_ranges: staging allocation failed"))
+        return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    um_desc_fill(rs, 0, nr, h);
+    std::memcpy(h + um_bytes, in.out_first.data(), nr * sizeof(uint32_t));
+    uint32_t *h_words = (uint32_t *)(h + up_bytes);
+    // the lists' doc span: from the mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    bool mirrored = true;
+    if (!every_doc)
+        for (const RangeIn &q : rs) {
+            const ii2_seg *s = q.seg;
+            if (!spans_mirrored(s)) { mirrored = false; break; }
+            for (uint64_t j = q.l0; j < q.l1; j++) {
+                if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
+                lo = std::min(lo, s->h_spans[3 * j]);
+                hi = std::max(hi, s->h_spans[3 * j + 2]);
+            }
+        }
+    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_words * sizeof(uint32_t)) + 2 * 256 + 4096)) return rc;
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
+    uint32_t *d_words = ws_take<uint32_t>(ctx, n_words);
+    uint32_t *d_span = ws_take<uint32_t>(ctx, 4);                // {lists' first doc, lists' last doc, set's first id, set's last id}
+    UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
+    std::memset(&bp, 0, sizeof bp);
+    bp.ranges = (const UmRange *)d_stage;
+    bp.pre = (const uint32_t *)(d_stage + desc_bytes);
+    bp.n_ranges = (uint32_t)nr;
+    bp.n_blocks = (uint32_t)in.n_blocks;
+    bp.bounds = d_span;
+    CountParams p;
+    std::memset(&p, 0, sizeof p);
+    p.ranges = bp.ranges;
+    p.pre = bp.pre;
+    p.out_first = (const uint32_t *)(d_stage + um_bytes);
+    p.n_ranges = bp.n_ranges;
+    p.n_blocks = bp.n_blocks;
+    p.per_wave = um_per_wave(ctx, in.n_blocks);
+    p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
+    p.set = d_set;
+    p.n_set = n_set;
+    set_tomb(p, tomb);
+    p.counts = d_words;
+    p.decoded = d_words + in.n_named;
+    p.edges = d_span + 2;
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_words, 0, n_words * sizeof(uint32_t), st));
+    uint32_t n_win = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    if (every_doc) {
+        HIP_TRY(ctx, launch_cr_count(p, true, st, e0, e1));
+    } else {
+        if (!mirrored) {
+            HIP_TRY(ctx, hipMemsetAsync(d_span, 0xFF, sizeof(uint32_t), st));
+            HIP_TRY(ctx, hipMemsetAsync(d_span + 1, 0, sizeof(uint32_t), st));
+            HIP_TRY(ctx, launch_union_many_bounds(bp, st));
+        }
+        HIP_TRY(ctx, launch_cr_edges(p, st));
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (!mirrored) {
+            lo = hb[0];
+            hi = hb[1];
+        }
+        if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_count_ranges: inconsistent list bounds");
+        // the docs that can hit: the lists' span clipped to the set's
+        lo = std::max(lo, hb[2]);
+        hi = std::min(hi, hb[3]);
+        if (lo > hi) {                                          // no overlap: nothing was marked, the staging copy has been waited for
+            ctx->um_dirty = false;
+            return count_done(in, counts, stats);
+        }
+        const uint64_t W = um_window(ctx);
+        const uint32_t base = lo & ~2047u;                      // the summary's bits are the docs' 2048-doc chunks: doc >> 11
+        const uint64_t span = (uint64_t)hi - base + 1;
+        if (int rc = um_scratch_reserve(ctx, "ii2_count_ranges", span, W)) return rc;
+        for (uint64_t wlo = base; wlo <= hi; wlo += W, n_win++) {
+            UnionManyParams wp;
+            um_set_window(ctx, wp, wlo, std::min<uint64_t>(W, (uint64_t)hi - wlo + 1));
+            p.win_lo = wp.win_lo;
+            p.win_docs = wp.win_docs;
+            p.n_sum = wp.n_sum;
+            p.bitmap = wp.bitmap;
+            p.summary = wp.summary;
+            p.doc_lo = std::max(lo, p.win_lo);
+            p.doc_hi = (uint32_t)std::min<uint64_t>(hi, wlo + p.win_docs - 1);
+            IrParams ip;
+            std::memset(&ip, 0, sizeof ip);
+            ip.n_sum = p.n_sum;
+            ip.bitmap = p.bitmap;
+            ip.summary = p.summary;
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+            HIP_TRY(ctx, launch_cr_mark(p, st));
+            HIP_TRY(ctx, launch_cr_count(p, false, st, e0, e1));
+            HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
+            e0 = e1 = nullptr;
+        }
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->um_dirty = false;
+    uint64_t hits = 0, decoded = 0;
+    for (uint64_t k = 0; k < in.n_named; k++) {
+        counts[k] = h_words[k];
+        hits += h_words[k];
+    }
+    for (uint32_t k = 0; k < CR_DECODED_SLOTS; k++) decoded += h_words[in.n_named + k];
+    if (stats) *stats = ii2_count_stats{in.n_named, in.n_blocks, decoded, hits, n_win};
+    return II2_OK;
+}
+
+static int count_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts, uint64_t counts_cap,
+                                 ii2_count_stats *stats) {
+    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_count_ranges: bad argument");
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_count_ranges: tombstones live on another device");
+    if (n_set > (1ull << 32)) return fail(ctx, II2_EINVAL, "ii2_count_ranges: more than 2^32 set ids");
+    // the ranges one by one: those that own blocks keep the index of their first list's count
+    CountIn in;
+    uint64_t n_nonempty = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const size_t before = in.rs.size();
+        if (int rc = collect_ranges(ctx, "ii2_count_ranges", 1, segs + i, list_first + i, list_end + i, in.rs, &in.n_blocks, &n_nonempty)) return rc;
+        if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_count_ranges: 2^31 lists or more in one call");
+        if (in.rs.size() > before) in.out_first.push_back((uint32_t)in.n_named);
+        in.n_named += list_end[i] - list_first[i];
+    }
+    if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_count_ranges: 2^31 lists or more in one call");
+    if (in.n_blocks >= 0xFFFFFFFFull || in.rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_count_ranges: more than 2^32 - 2 blocks in one call");
+    if (in.n_named && !counts) return fail(ctx, II2_EINVAL, "ii2_count_ranges: counts is NULL");
+    if (counts_cap < in.n_named) return fail(ctx, II2_ECAPACITY, "ii2_count_ranges: counts holds fewer entries than lists are named (nothing written)");
+    if (!in.n_blocks || (d_set && !n_set)) return count_done(in, counts, stats);
+    if (!d_set && !tomb) {
+        // every doc, nothing removed: the lists' lengths, from the segments' host mirrors
+        for (const RangeIn &q : in.rs)
+            if (int rc = ii2_seg_host_cnt(ctx, q.seg)) return rc;
+        count_done(in, counts, stats);
+        uint64_t hits = 0;
+        for (size_t r = 0; r < in.rs.size(); r++)
+            for (uint64_t j = in.rs[r].l0; j < in.rs[r].l1; j++) hits += counts[in.out_first[r] + (j - in.rs[r].l0)] = in.rs[r].seg->h_cnt[j];
+        if (stats) stats->n_hits = hits;
+        return II2_OK;
+    }
+    return count_many(ctx, in, d_set, n_set, tomb, counts, stats);
+}
+
+extern "C" int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts, uint64_t counts_cap,
+                                ii2_count_stats *stats) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return count_ranges_unlocked(ctx, n, segs, list_first, list_end, d_set, n_set, tomb, counts, counts_cap, stats);
+}
+
 // ---- AND of ORs over list ranges ----------------------------------------------------------------
 // one group of a call: its checked ranges rs[r0, r1), their blocks, non-empty lists and postings, and its doc span
 struct GroupIn {

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, BuildStats, MergeStats, SegInfo
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, BuildStats, CountStats, MergeStats, SegInfo
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -498,6 +498,27 @@ class Context:
                                                  end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None, _ptr(out), out.count,
                                                  off.ctypes.data_as(_lib.u64p)))
         return out, off
+
+    def count_ranges(self, ranges, dset: Optional[DeviceArray] = None, n_set: Optional[int] = None,
+                     tomb: Optional["Tombstones"] = None):
+        """Hits per list against a doc set (ii2_count_ranges: facet counts): ranges = [(Segment, first, end), ...] as union_ranges
+        takes them; dset is a DeviceArray of ascending, duplicate-free ids - what every query returns - of which the first n_set
+        count (default: all of it), or None for "every doc".  Returns (uint64 counts, one per list named in range order: its ids
+        that lie in the set and not in tomb; CountStats)."""
+        ranges = [(s, int(a), int(b)) for s, a, b in ranges]
+        n = len(ranges)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s, _, _ in ranges])
+        first = (C.c_uint64 * max(n, 1))(*[a for _, a, _ in ranges])
+        end = (C.c_uint64 * max(n, 1))(*[b for _, _, b in ranges])
+        if dset is None:
+            n_set = 0
+        elif n_set is None:
+            n_set = dset.count
+        counts = np.zeros(sum(max(b - a, 0) for _, a, b in ranges), np.uint64)
+        st = CountStats()
+        self._ck(self.lib.ii2_count_ranges(self.h, n, segs, first, end, _ptr(dset), int(n_set), tomb.h if tomb else None,
+                                           counts.ctypes.data_as(_lib.u64p), counts.size, C.byref(st)))
+        return counts, st
 
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):

@@ -65,6 +65,10 @@ def _lib_typed():
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
+        lib.ii2h_term_counts.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_count_term_len.restype = C.c_uint64
+        lib.ii2h_count_term_len.argtypes = [vp, C.c_uint64]
+        lib.ii2h_count_copy.argtypes = [vp, C.c_uint64, vp, u64p]
         for f in ("ii2h_result_term_len", "ii2h_result_values_len"):
             getattr(lib, f).restype = C.c_uint64
             getattr(lib, f).argtypes = [vp, C.c_uint64]
@@ -190,7 +194,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectMany)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectMany, TermCounts)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -239,6 +243,26 @@ class InvertedIndex(_Target):
         self._ck(self.lib.ii2h_intersect_batch(self.h, blob.ctypes.data, off.ctypes.data, q_first.ctypes.data, q_req.ctypes.data, len(queries),
                                                C.byref(n)))
         return [vals for _, vals in self._results(n.value)]
+
+    def term_counts(self, prefix: bytes, terms: List[bytes] = (), exclude: List[bytes] = ()) -> Dict[bytes, int]:
+        """Facet counts (TermCounts: the filter stays on the device, one ii2_count_ranges call over the prefix's run of every
+        segment): for every term that starts with `prefix`, the number of distinct docs under it among
+        intersect_except(terms, exclude); terms with count 0 are left out.  Without `terms` the doc set is every doc: the
+        document frequency of each term under the prefix."""
+        blob, off = _pack(list(terms))
+        x_blob, x_off = _pack(list(exclude))
+        pre = np.frombuffer(bytes(prefix) + b"\0", dtype=np.uint8).copy()
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_term_counts(self.h, pre.ctypes.data, len(prefix), blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data,
+                                           x_off.ctypes.data, len(exclude), C.byref(n)))
+        out = {}
+        for i in range(n.value):
+            tl = self.lib.ii2h_count_term_len(self.h, i)
+            tb = np.zeros(max(tl, 1), np.uint8)
+            c = C.c_uint64()
+            self.lib.ii2h_count_copy(self.h, i, tb.ctypes.data, C.byref(c))
+            out[tb[:tl].tobytes()] = c.value
+        return out
 
     @property
     def n_shards(self) -> int:

@@ -18,6 +18,7 @@
 //   Intersect(terms)                                 additive
 //   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
+//   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //
 // Built as its own library (libii2_host.so) that only sees include/ii2.h and links libii2_hip.so:
 // the product library exports the C ABI and nothing else.  A small C facade (ii2h_*) at the bottom
@@ -914,12 +915,28 @@ class InvertedIndex {
     // second download, no set difference on the host.  An excluded term found in no segment is dropped; a required one gives the
     // empty result.  Like Intersect and Read, no tombstone filter.
     std::vector<uint32_t> IntersectExcept(const std::vector<Term> &terms, const std::vector<Term> &except) const {
-        if (terms.empty()) return {};
+        Filter f;
+        if (!filter_build(terms, except, f)) return {};
+        DevMem d_out(ctx_);
+        const uint64_t n = filter_run(f, d_out, "intersect except");
+        std::vector<uint32_t> ids(n);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
+        return ids;
+    }
+   private:
+    // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
+    // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
+    struct Filter {
         std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
         std::vector<uint64_t> group_first{0};
         std::vector<uint8_t> group_not;
         std::vector<const ii2_seg *> segs;
         std::vector<uint64_t> first, end;
+        uint64_t bound = ~0ull;
+    };
+    // false: a required term is in no segment (or there is none) - nothing is under every term
+    bool filter_build(const std::vector<Term> &terms, const std::vector<Term> &except, Filter &f) const {
+        if (terms.empty()) return false;
         // one one-list range per segment that holds the term; returns the term's postings bound (see Intersect), 0: in no segment
         auto gather = [&](const Term &t) {
             uint64_t post = 0;
@@ -930,47 +947,170 @@ class InvertedIndex {
                     if (j == T.size() || T[j] != t) continue;
                     ii2_seg_info info;
                     ii2_seg_get_info(sg->seg->h, &info);
-                    held.push_back(sg);
-                    segs.push_back(sg->seg->h);
-                    first.push_back(j);
-                    end.push_back(j + 1);
+                    f.held.push_back(sg);
+                    f.segs.push_back(sg->seg->h);
+                    f.first.push_back(j);
+                    f.end.push_back(j + 1);
                     post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
                 }
             }
             return post;
         };
         // the output's size: the smallest REQUIRED term's bound, as in Intersect (an exclusion only removes ids)
-        constexpr uint64_t FIRST_CAP = 1u << 22;
-        uint64_t bound = ~0ull;
         for (auto &t : terms) {
             const uint64_t post = gather(t);
-            if (!post) return {};                                // a required term in no segment: nothing is under every term
-            group_first.push_back(segs.size());
-            group_not.push_back(0);
-            bound = std::min(bound, post);
+            if (!post) return false;                             // a required term in no segment: nothing is under every term
+            f.group_first.push_back(f.segs.size());
+            f.group_not.push_back(0);
+            f.bound = std::min(f.bound, post);
         }
         for (auto &t : except) {
             if (!gather(t)) continue;                            // an excluded term in no segment removes nothing
-            group_first.push_back(segs.size());
-            group_not.push_back(1);
+            f.group_first.push_back(f.segs.size());
+            f.group_not.push_back(1);
         }
-        uint64_t cap = std::min(bound, FIRST_CAP), n = 0;
-        DevMem d_out(ctx_);
+        return true;
+    }
+    // ONE ii2_andnot_ranges call into d_out, which stays on the device; returns the result's size.  Past FIRST_CAP ids the first
+    // call tries FIRST_CAP, and a result that does not fit is written by a second call with the size the first one reported
+    uint64_t filter_run(const Filter &f, DevMem &d_out, const char *what) const {
+        constexpr uint64_t FIRST_CAP = 1u << 22;
+        uint64_t cap = std::min(f.bound, FIRST_CAP), n = 0;
         for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect except");
-            const int rc = ii2_andnot_ranges(ctx_, group_not.size(), group_first.data(), group_not.data(), segs.data(), first.data(), end.data(),
-                                             nullptr, (uint32_t *)d_out.p, cap + 1, &n);
+            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), what);
+            const int rc = ii2_andnot_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), f.segs.data(), f.first.data(),
+                                             f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n);
             if (rc != II2_ECAPACITY || attempt) {
-                ck(ctx_, rc, "intersect except");
+                ck(ctx_, rc, what);
                 break;
             }
-            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect except");
+            ck(ctx_, ii2_dev_free(ctx_, d_out.p), what);
             d_out.p = nullptr;
             cap = n;
         }
-        std::vector<uint32_t> ids(n);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
-        return ids;
+        return n;
+    }
+
+   public:
+    // additive: facet counts - for every term that starts with `prefix` the number of distinct docs under it that
+    // IntersectExcept(terms, except) returns; terms with count 0 are omitted.  With `terms` empty the doc set is "every doc" and
+    // the result is the document frequency of each term under the prefix (`except` must then be empty too: there is no doc
+    // universe to take it from).  The filter result stays on the device, and ONE ii2_count_ranges call counts the prefix's run
+    // of every segment of every shard against it - the runs are found as PrefixSearch finds them.  Per term the per-segment
+    // counts are summed.  Nothing stops a (term, doc) pair from being Put again, so a term whose hits come from two or more
+    // segments may hold the same doc twice: those terms alone are counted again exactly, all of them in ONE
+    // ii2_query_batch_groups call - the query's groups plus the term's group, no output buffer, the sizes read from the offsets it
+    // fills under II2_ECAPACITY.  Like Read and Intersect, no tombstone filter.
+    std::map<Term, uint64_t> TermCounts(const Term &prefix, const std::vector<Term> &terms, const std::vector<Term> &except) const {
+        std::map<Term, uint64_t> out;
+        if (terms.empty() && !except.empty()) throw Error("term counts: an exclusion needs a required term");
+        Filter f;
+        DevMem d_set(ctx_);
+        uint64_t n_set = 0;
+        if (!terms.empty()) {
+            if (!filter_build(terms, except, f)) return out;
+            n_set = filter_run(f, d_set, "term counts");
+            if (!n_set) return out;
+        }
+        // the prefix's run in every segment of every shard
+        std::vector<std::shared_ptr<Segment>> held;
+        std::vector<const ii2_seg *> segs;
+        std::vector<uint64_t> first, end;
+        uint64_t n_named = 0;
+        for (auto &s : shard_list()) {
+            Term mn, mx;
+            if (!s.second->MinMax(&mn, &mx)) continue;
+            size_t l = std::min(prefix.size(), mn.size());
+            if (prefix.compare(0, l, mn, 0, l) < 0) continue;
+            l = std::min(prefix.size(), mx.size());
+            if (prefix.compare(0, l, mx, 0, l) > 0) continue;
+            for (auto &sg : s.second->snapshot()) {
+                const std::vector<Term> &T = sg->terms;
+                const size_t j0 = std::lower_bound(T.begin(), T.end(), prefix, term_less) - T.begin();
+                const size_t j1 = prefix_end(T, prefix);
+                if (j0 >= j1) continue;
+                held.push_back(sg);
+                segs.push_back(sg->seg->h);
+                first.push_back(j0);
+                end.push_back(j1);
+                n_named += j1 - j0;
+            }
+        }
+        if (segs.empty()) return out;
+        std::vector<uint64_t> counts(n_named);
+        ck(ctx_, ii2_count_ranges(ctx_, segs.size(), segs.data(), first.data(), end.data(), terms.empty() ? nullptr : (const uint32_t *)d_set.p, n_set,
+                                  nullptr, counts.data(), counts.size(), nullptr),
+           "term counts");
+        // per term: the sum over its segments, and the lists that hit
+        struct Hit {
+            uint64_t sum = 0;
+            std::vector<std::pair<const ii2_seg *, uint64_t>> lists;      // (segment, list) of every segment with a hit
+        };
+        std::map<Term, Hit> hits;
+        size_t k = 0;
+        for (size_t r = 0; r < segs.size(); r++)
+            for (uint64_t j = first[r]; j < end[r]; j++, k++) {
+                if (!counts[k]) continue;
+                Hit &h = hits[held[r]->terms[j]];
+                h.sum += counts[k];
+                h.lists.emplace_back(segs[r], j);
+            }
+        std::vector<const Term *> again;
+        for (auto &kv : hits) {
+            out[kv.first] = kv.second.sum;
+            if (kv.second.lists.size() > 1) again.push_back(&kv.first);
+        }
+        // the exact re-count: per term one query of the filter's groups plus the term's own (for "every doc" that group alone),
+        // in calls of at most 2^20 queries whose result bounds stay below 2^32 ids
+        constexpr size_t CALL_QUERIES = 1u << 20;
+        constexpr uint64_t CALL_IDS = 0xFFFFFFFFull;
+        size_t at = 0;
+        while (at < again.size()) {
+            std::vector<uint64_t> query_first{0}, group_first{0}, qfirst, qend;
+            std::vector<uint8_t> group_not;
+            std::vector<const ii2_seg *> qsegs;
+            uint64_t bound = 0;
+            const size_t q0 = at;
+            for (; at < again.size() && at - q0 < CALL_QUERIES; at++) {
+                const Hit &h = hits[*again[at]];
+                if (at > q0 && bound + h.sum >= CALL_IDS) break;
+                bound += h.sum;                                  // (the term's group holds at least its hits; the result is no longer)
+                // the required groups first - the filter's, then the term's own - and the excluded ones last, as the packers lay a query out
+                auto filter_groups = [&](uint8_t flag) {
+                    for (size_t g = 0; g < f.group_not.size(); g++) {
+                        if (f.group_not[g] != flag) continue;
+                        for (uint64_t i = f.group_first[g]; i < f.group_first[g + 1]; i++) {
+                            qsegs.push_back(f.segs[i]);
+                            qfirst.push_back(f.first[i]);
+                            qend.push_back(f.end[i]);
+                        }
+                        group_first.push_back(qsegs.size());
+                        group_not.push_back(flag);
+                    }
+                };
+                filter_groups(0);
+                for (auto &sl : h.lists) {
+                    qsegs.push_back(sl.first);
+                    qfirst.push_back(sl.second);
+                    qend.push_back(sl.second + 1);
+                }
+                group_first.push_back(qsegs.size());
+                group_not.push_back(0);
+                filter_groups(1);
+                query_first.push_back(group_not.size());
+            }
+            const size_t nq = at - q0;
+            std::vector<uint64_t> off(nq + 1, 0);
+            const int rc = ii2_query_batch_groups(ctx_, nq, query_first.data(), group_first.data(), group_not.data(), qsegs.data(), qfirst.data(),
+                                                  qend.data(), nullptr, nullptr, 0, off.data());
+            if (rc != II2_ECAPACITY) ck(ctx_, rc, "term counts");
+            for (size_t q = 0; q < nq; q++) {
+                const uint64_t c = off[q + 1] - off[q];
+                if (c) out[*again[q0 + q]] = c;
+                else out.erase(*again[q0 + q]);
+            }
+        }
+        return out;
     }
     // additive: MANY IntersectExcept queries, queries[q] = (terms, except), in one ii2_query_batch_groups call - with a second one
     // when the results exceed FIRST_CAP ids, see below - one wait and one download.  Per term the groups are built exactly as IntersectExcept builds them - one one-list range per segment of the
@@ -1111,6 +1251,7 @@ struct ii2h_target {
     std::string err;
     std::vector<TermValues> result;     // last Read / PrefixSearch result
     std::vector<uint32_t> ids;          // last Intersect / RemovedValues result
+    std::vector<std::pair<Term, uint64_t>> counts;      // last TermCounts result
 };
 
 static std::vector<Term> unpack_terms(const uint8_t *bytes, const uint64_t *off, uint64_t n) {
@@ -1284,6 +1425,19 @@ int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *o
         for (auto &ids : t->index->IntersectMany(queries)) t->result.push_back(TermValues{Term(), std::move(ids)});
         *n_results = t->result.size();
     })
+}
+int ii2h_term_counts(ii2h_target *t, const uint8_t *prefix, uint64_t prefix_len, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                     const uint8_t *x_bytes, const uint64_t *x_off, uint64_t n_x, uint64_t *n_found) {
+    H_TRY(t, {
+        auto m = t->index->TermCounts(Term((const char *)prefix, prefix_len), unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x));
+        t->counts.assign(m.begin(), m.end());
+        *n_found = t->counts.size();
+    })
+}
+uint64_t ii2h_count_term_len(const ii2h_target *t, uint64_t i) { return t->counts[i].first.size(); }
+void ii2h_count_copy(const ii2h_target *t, uint64_t i, uint8_t *term, uint64_t *count) {
+    std::memcpy(term, t->counts[i].first.data(), t->counts[i].first.size());
+    *count = t->counts[i].second;
 }
 int ii2h_removed_values(ii2h_target *t, uint64_t *n_ids) {
     H_TRY(t, { Shard *s = t->shard ? t->shard.get() : t->index->OnlyShard(); t->ids = s ? s->RemovedValues() : std::vector<uint32_t>(); *n_ids = t->ids.size(); })
