@@ -555,6 +555,15 @@ int ii2_profile_region_ms(ii2_ctx *ctx, double *ms);
 int ii2_ctx_paths(ii2_ctx *ctx, uint64_t *out, uint32_t n);
 /* Name of path i ("and.small", "or.rank", ...), NULL beyond the last id.  Needs no context and no GPU. */
 const char *ii2_path_name(uint32_t i);
+/* How often the merge tile kernel left its ordinary path on this context since it was created: out[i] = count of event i.  n = words
+ * `out` holds (at most that many are written); returns the number of event ids the library knows.  The events are the kernel's
+ * recoveries (DESIGN.md has the list): a batch of small terms redone term by term, a doc range bisected because it held more
+ * postings than a tile sorts or because a bucket of its sort overflowed, and the leaves of such a bisection, by the way they were
+ * merged.  Every merge counts - ii2_merge_segments*, ii2_merge_host and the merge passes of the unions.  The counters live on the
+ * device and are never cleared by a call; the read waits for the context's stream. */
+int ii2_merge_events(ii2_ctx *ctx, uint64_t *out, uint32_t n);
+/* Name of event i ("batch_redo", "range_overfull", ...), NULL beyond the last id.  Needs no context and no GPU. */
+const char *ii2_merge_event_name(uint32_t i);
 
 #ifdef __cplusplus
 }

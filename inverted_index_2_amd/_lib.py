@@ -107,6 +107,8 @@ PROTOTYPES = {
     "ii2_profile_region_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "ii2_ctx_paths": (C.c_int, [vp, u64p, C.c_uint32]),
     "ii2_path_name": (C.c_char_p, [C.c_uint32]),
+    "ii2_merge_events": (C.c_int, [vp, u64p, C.c_uint32]),
+    "ii2_merge_event_name": (C.c_char_p, [C.c_uint32]),
 }
 
 _lib = None

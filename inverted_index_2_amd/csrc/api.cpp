@@ -129,6 +129,13 @@ int ii2_ctx_create(int device, uint32_t flags, ii2_ctx **out) {
         ii2_ctx_destroy(ctx);
         return II2_EHIP;
     }
+    // the merge tile kernel's event counters: zeroed here, on the context's stream (ahead of every launch), and never again
+    if (ii2::dm_malloc_retry((void **)&ctx->d_merge_events, ii2::ME_COUNT * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemsetAsync(ctx->d_merge_events, 0, ii2::ME_COUNT * sizeof(unsigned long long), ctx->stream) != hipSuccess) {
+        g_create_err = "context resource allocation failed";
+        ii2_ctx_destroy(ctx);
+        return II2_EHIP;
+    }
     *out = ctx;
     return II2_OK;
 }
@@ -158,6 +165,7 @@ void ii2_ctx_destroy(ii2_ctx *ctx) {
     if (ctx->d_an) (void)hipFree(ctx->d_an);
     if (ctx->d_batch) (void)hipFree(ctx->d_batch);
     if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+    if (ctx->d_merge_events) (void)hipFree(ctx->d_merge_events);
     if (ctx->d_mail) (void)hipFree(ctx->d_mail);
     if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
     for (hipEvent_t e : ctx->region_ev) if (e) (void)hipEventDestroy(e);
@@ -991,6 +999,23 @@ int ii2_ctx_paths(ii2_ctx *ctx, uint64_t *out, uint32_t n) {
 }
 
 const char *ii2_path_name(uint32_t i) { return i < ii2::P_COUNT ? PATH_NAMES[i] : nullptr; }
+
+// the names of ii2::MergeEvent, in the enum's order
+static const char *const MERGE_EVENT_NAMES[] = {"batch_redo", "range_overfull", "range_bucket_overflow", "leaf_bitmap", "leaf_sorted"};
+static_assert(sizeof MERGE_EVENT_NAMES / sizeof MERGE_EVENT_NAMES[0] == ii2::ME_COUNT, "one name per ii2::MergeEvent");
+
+int ii2_merge_events(ii2_ctx *ctx, uint64_t *out, uint32_t n) {
+    if (!ctx || (!out && n)) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    unsigned long long ev[ii2::ME_COUNT];
+    HIP_TRY(ctx, hipMemcpyAsync(ev, ctx->d_merge_events, sizeof ev, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < n && i < ii2::ME_COUNT; i++) out[i] = ev[i];
+    return (int)ii2::ME_COUNT;
+}
+
+const char *ii2_merge_event_name(uint32_t i) { return i < ii2::ME_COUNT ? MERGE_EVENT_NAMES[i] : nullptr; }
 
 int ii2_debug_read(ii2_ctx *ctx, uint64_t *out, uint64_t n_words) {
     if (!ctx || !out || !ctx->d_debug) return II2_EINVAL;

@@ -27,6 +27,9 @@ enum Path : uint32_t {
     P_SPAN_FETCH, P_SPAN_BOUNDS,
     P_COUNT
 };
+// The events of the merge tile kernel's recovery (ii2_merge_events / ii2_merge_event_name): one id per cold site of
+// k_merge_tiles (merge.hip) where a tile leaves the ordinary path.  The names live in api.cpp (MERGE_EVENT_NAMES), in this order.
+enum MergeEvent : uint32_t { ME_BATCH_REDO, ME_RANGE_OVERFULL, ME_RANGE_BUCKET_OVERFLOW, ME_LEAF_BITMAP, ME_LEAF_SORTED, ME_COUNT };
 }  // namespace ii2
 
 // mailbox layout (u64 words; h_mail and d_mail both hold II2_MAIL_WORDS)
@@ -52,7 +55,7 @@ struct ii2_ctx {
     // options
     int64_t opt_intersect_g = 0;        // 0 = auto
     int64_t opt_intersect_wgs = 0;      // tile-kernel workgroups per CU (0 = default)
-    int64_t opt_merge_large_tile = 0;   // 0 = default (MERGE_CAP / 2)
+    int64_t opt_merge_large_tile = 0;   // 0 = default (MERGE_CAP / 20 * 19 = 3401 input postings per range tile)
     int64_t opt_merge_direct = 1;       // tiles place their survivors themselves when the output buffer surely fits (0: always park + pack)
     int64_t opt_merge_spin = 0;         // bounded waits of the direct placement: polls (0 = default; tests shorten it)
     uint64_t merge_fallbacks = 0;       // merges repeated through the parking + packing pass after a bounded wait ran out
@@ -130,6 +133,8 @@ struct ii2_ctx {
     int world = 1, rank = 0;
     uint64_t comm_syncs = 0;            // host waits inside the exchange entry points (what a chunked exchange pays per chunk)
     int cu_count = 256;
+    unsigned long long *d_merge_events = nullptr;   // [ii2::ME_COUNT] counted by k_merge_tiles on the device (ii2_merge_events): allocated and zeroed with the
+                                        //     context, never cleared by a call
     uint64_t paths[ii2::P_COUNT] = {};  // how often each kernel path was taken (ii2_ctx_paths): host words, bumped under mu where the launch is decided
 };
 static inline void took(ii2_ctx *ctx, ii2::Path p) { ctx->paths[p]++; }
@@ -614,7 +619,7 @@ constexpr uint32_t MERGE_THREADS = 256;     // threads per workgroup of the tile
 constexpr uint32_t MERGE_CAP = 3584;        // postings a tile sorts in LDS (14 per thread)
 constexpr uint32_t MERGE_NT_MAX = 256;      // terms per batch tile (one thread per term)
 constexpr uint32_t MERGE_BM_WORDS = 2 * MERGE_CAP;          // LDS bitmap of a bitmap tile: the sort arrays' 56 KB
-constexpr uint32_t MERGE_BM_DOCS = MERGE_BM_WORDS * 32u;    // docs a bitmap tile covers (458752)
+constexpr uint32_t MERGE_BM_DOCS = MERGE_BM_WORDS * 32u;    // docs a bitmap tile covers (229376)
 // the k term-aligned inputs, by value in the kernel arguments
 struct MergeSegs {
     SegView segs[MAX_LISTS];
@@ -668,6 +673,7 @@ struct MergeParams {
     uint64_t out_cap;
     uint64_t *d_total;            // total survivors
     unsigned long long *debug;    // optional diagnostics words
+    unsigned long long *events;   // [ME_COUNT] the context's event counters: every workgroup adds what it met, once, at its end
 };
 constexpr uint32_t MERGE_DESC_LARGE = 1u << 30;   // desc.y: the tile belongs to a large term (its count goes through tile_count)
 constexpr uint32_t MERGE_DESC_BITMAP = 1u << 31;  // desc.y: bitmap tile

@@ -683,6 +683,7 @@ struct __align__(16) MergeSmem {
     uint32_t pq_tile[MERGE_PQ], pq_cnt[MERGE_PQ];
     unsigned long long pq_slot[MERGE_PQ];
     unsigned long long pq_off;              // output offset of the queue's first tile
+    uint32_t evc[8];                        // this workgroup's events (MergeEvent), bumped by thread 0 and added to the context's counters at the kernel's end
     uint32_t stk[36][2];                    // bisection stack of doc ranges (<= 32 levels, two pushes per pop)
 };
 
@@ -865,6 +866,7 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
             __builtin_amdgcn_s_sleep(20);
         }
     };
+    if (tid < 8) sm.evc[tid] = 0u;
     if (tid == 0) { sm.pq_n = 0u; sm.abort = 0u; sm.tk = p.direct ? atomicAdd(&sy->ticket, 1u) : blockIdx.x; }
     lds_barrier();
     const uint32_t n_workers = p.direct ? gridDim.x - 1u : gridDim.x;
@@ -1202,6 +1204,7 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
                 // word by word (coalesced loads of exactly the range's words), count, extract
                 uint32_t *bm = sm.u.bm;
                 if (tid == 0) {     // a sub-range need not start or end at a word
+                    if (!was_root) sm.evc[ME_LEAF_BITMAP]++;
                     if (lo & 31u) bm[0] &= ~((1u << (lo & 31u)) - 1u);
                     if ((hi & 31u) != 31u) bm[bm_nw - 1u] &= (2u << (hi & 31u)) - 1u;
                 }
@@ -1432,7 +1435,7 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
                     if ((uint32_t)tid <= nw) sm.x.f.DP[tid] = ex;       // (DP[nw] = all of them)
                 }
                 const uint32_t nout = n - totdead;
-                if (!allocated && tid == 0) sm.ab = ab_reg;
+                if (tid == 0) { if (!allocated) sm.ab = ab_reg; if (!was_root) sm.evc[ME_LEAF_SORTED]++; }
                 lds_barrier();
                 if (!allocated) { slot = p.npre[t0] + sm.ab; dst = p.tmp + slot; allocated = true; }
                 uint32_t *out = dst + acc;
@@ -1454,6 +1457,7 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
             }
             // ---- the range does not fit LDS, or its ids are clustered so that a bucket overflowed
             if (cur_batch) {
+                if (tid == 0) sm.evc[ME_BATCH_REDO]++;
                 fb_next = cur_t0;                  // the batch again, term by term (nothing of it was written)
                 fb_end = cur_t0 + cur_nt;
                 acc = 0;
@@ -1466,6 +1470,7 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
             if (tid == 0) {
                 sm.stk[sp][0] = mid + 1u; sm.stk[sp][1] = hi;
                 sm.stk[sp + 1u][0] = lo;  sm.stk[sp + 1u][1] = mid;
+                sm.evc[sm.fill > MCAP ? ME_RANGE_OVERFULL : ME_RANGE_BUCKET_OVERFLOW]++;
             }
             sp += 2u;
             II2_STAMP(7)
@@ -1494,6 +1499,10 @@ __global__ __launch_bounds__(MERGE_THREADS, 4) void k_merge_tiles(const MergeSeg
         II2_STAMP(7)
     }
     if (p.direct) drain(true, ~0ull, 0xFFFFFFFFu);
+    // the events this workgroup met (normally none).  They are counted in LDS where they happen and reach the context's counters
+    // here: an atomic on global memory at any of those sites costs the tile loop a spilled register
+    lds_barrier();
+    if ((uint32_t)tid < ME_COUNT && sm.evc[tid]) atomicAdd(&p.events[tid], (unsigned long long)sm.evc[tid]);
     if (stamps && tid == 0)
         for (int i = 0; i < 8; i++) p.debug[(uint64_t)blockIdx.x * 8u + i] = tacc[i];
 #undef II2_STAMP

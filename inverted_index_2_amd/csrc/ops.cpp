@@ -51,8 +51,8 @@ int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n_terms,
     const uint32_t cap = MERGE_CAP;
     // batches: small terms are packed in term order; a batch ends when its weight passes a multiple of batch_q, so it holds
     // less than batch_q + small_max <= cap postings and, every term weighing at least wmin, at most MERGE_NT_MAX terms
-    p.small_max = (cap * 5u) / 14u;         // 2560
-    p.batch_q = cap - p.small_max;          // 4608
+    p.small_max = (cap * 5u) / 14u;         // 1280
+    p.batch_q = cap - p.small_max;          // 2304
     p.wmin = (cap + MERGE_NT_MAX - 1u) / MERGE_NT_MAX;
     p.range_target = ctx->opt_merge_large_tile > 0 ? std::min<uint32_t>((uint32_t)ctx->opt_merge_large_tile, cap) : (cap / 20u) * 19u;
     p.bitmap_tiles = ctx->opt_merge_bitmap ? 1u : 0u;
@@ -141,6 +141,7 @@ int merge_core(ii2_ctx *ctx, uint32_t k, const SegView *views, uint64_t n_terms,
     p.out_cap = out_cap;
     p.d_total = ctx->d_mail;                    // [0] total, [2] surviving terms
     p.debug = nullptr;
+    p.events = ctx->d_merge_events;
     if (ctx->opt_debug_stamps) {
         if (int rcd = ensure_debug(ctx, false)) return rcd;
         p.debug = ctx->d_debug;

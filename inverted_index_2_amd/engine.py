@@ -127,6 +127,17 @@ def path_names():
         names.append(name.decode())
 
 
+def merge_event_names():
+    """The names of the events the merge tile kernel counts (ii2_merge_event_name), in id order.  Needs no context and no GPU."""
+    lib = _lib.load()
+    names = []
+    while True:
+        name = lib.ii2_merge_event_name(len(names))
+        if name is None:
+            return names
+        names.append(name.decode())
+
+
 class DeviceArray:
     """A raw HBM buffer owned by a Context."""
 
@@ -221,6 +232,20 @@ class Context:
         n = self.lib.ii2_ctx_paths(self.h, out, len(names))
         if n != len(names):
             raise II2Error(-1, "ii2_ctx_paths: the library knows another number of paths than ii2_path_name")
+        return {name: int(out[i]) for i, name in enumerate(names)}
+
+    def merge_events(self):
+        """{event name: how often the merge tile kernel left its ordinary path that way on this context since it was created}
+        (ii2_merge_events; the names come from ii2_merge_event_name).  Counted on the device by every merge, the unions' merge
+        passes included; the read waits for the context's stream.  The difference between two reads is what the calls in between
+        met."""
+        names = merge_event_names()
+        out = (C.c_uint64 * len(names))()
+        n = self.lib.ii2_merge_events(self.h, out, len(names))
+        if n < 0:
+            self._ck(n)
+        if n != len(names):
+            raise II2Error(-1, "ii2_merge_events: the library knows another number of events than ii2_merge_event_name")
         return {name: int(out[i]) for i, name in enumerate(names)}
 
     def profile_read(self):

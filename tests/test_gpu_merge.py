@@ -5,6 +5,7 @@ import pytest
 
 from inverted_index_2_amd import synth
 from oracle import oracle as orc
+from tests import merge_cases as mc
 from tests.gpu_util import ctx, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +25,21 @@ def _check_merge(ctx, offs, vals, removed=None):
     h_off, h_vals, hst = ctx.merge_host(offs, vals, removed if removed is not None else ())
     assert np.array_equal(h_off, w_off) and np.array_equal(h_vals, w_vals) and hst.n_terms_out == w_terms
     return st
+
+
+def _check_merge_events(ctx, offs, vals, removed=None):
+    """_check_merge, and the events of its two merges (ii2_merge_segments, ii2_merge_host) are exactly what the model of
+    tests/merge_cases.py counts for these lists, twice.  Returns the events of one merge."""
+    host = list(zip(offs, vals))
+    model = mc.simulate(host, mc.plan(host))
+    before = ctx.merge_events()
+    st = _check_merge(ctx, offs, vals, removed)
+    after = ctx.merge_events()
+    delta = {k: after[k] - before[k] for k in after if after[k] != before[k]}
+    print("tiles", st.n_tiles, "events of two merges", delta)
+    assert st.n_tiles == mc.plan(host).n_tiles
+    assert delta == {k: 2 * v for k, v in model.items()}
+    return model
 
 
 def _rand_segments(rng, k, T, max_len, universe, p_empty=0.3):
@@ -98,7 +114,10 @@ def test_clustered_large_term_replans(ctx):
     c = np.concatenate([sorted_unique(rng, 100, 1 << 20), np.arange(1_010_000, 1_050_000, dtype=np.uint32)])
     c = np.unique(c).astype(np.uint32)
     offs = [np.array([0, x.size], np.uint64) for x in (a, b, c)]
-    _check_merge(ctx, offs, [a, b, c])
+    ev = _check_merge_events(ctx, offs, [a, b, c])
+    # what the test was written for: tiles cut by the sparse list's blocks hold far more of the clustered lists than a tile sorts
+    # (bisected), and the cluster's ranges end as bitmap leaves
+    assert ev.get("range_overfull", 0) > 0 and ev.get("leaf_bitmap", 0) > 0 and ev.get("leaf_sorted", 0) > 0
 
 
 def test_zipf_workload_miniature(ctx):
@@ -286,8 +305,11 @@ def test_bucket_fold_fallbacks_on_clustered_ids(ctx):
     removed = np.unique(np.concatenate([rng.integers(0, 6000, 500), (1 << 19) + rng.integers(0, 1 << 19, 2000)])).astype(np.uint32)
     offs = [np.concatenate([[0], np.cumsum([x.size for x in lists])]).astype(np.uint64) for lists in segs]
     vals = [np.concatenate(lists).astype(np.uint32) for lists in segs]
-    _check_merge(ctx, offs, vals, removed)
-    _check_merge(ctx, offs, vals, None)
+    ev = _check_merge_events(ctx, offs, vals, removed)
+    assert _check_merge_events(ctx, offs, vals, None) == ev                    # (tombstoned ids fill buckets like any other)
+    # what the test was written for: batches whose sort overflows and are redone term by term, range tiles of the large term whose
+    # cluster overflows a bucket, and the bisection down to bitmap leaves
+    assert ev.get("batch_redo", 0) > 0 and ev.get("range_bucket_overflow", 0) > 0 and ev.get("leaf_bitmap", 0) > 0
 
 
 def _check_union(ctx, lists, removed=None):
