@@ -3,82 +3,16 @@ expected delta of Context.paths() - the kernels, template instantiations and ker
 numpy reference bit for bit; with the lists in one segment, spread over two, and (where the case says so) in a segment of 65537
 lists, whose doc spans the host does not mirror: there the delta also names the span fetches and bounds reductions, and a repeat
 of the call fetches no span again."""
-import numpy as np
 import pytest
 
 from tests import path_cases as pc
-from tests.gpu_util import ctx  # noqa: F401
+from tests.gpu_util import ctx, run_path_case  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0xDEADBEEF
-
-
-def _delta(before, after):
-    return {k: after[k] - before[k] for k in after if after[k] != before[k]}
-
-
-def _run(c, case, segs, lay, tomb, want):
-    """One call of the case; returns its results, one array per query."""
-    kind, *args = case.call
-    total = int(sum(w.size for w in want))
-    # (the capacity is part of the choice - the paths that may write part of a result want one that surely fits, a union over
-    # several windows counts first below 256 ids per block: every block of the case's lists fits unless the case says "exact")
-    cap = total if case.cap == "exact" else 256 * int(sum((l.size + 255) // 256 for s in lay.segments for l in s)) + 64
-    out = c.empty(cap + 64).upload(np.full(cap + 64, SENTINEL, np.uint32))
-    out.count = cap                                       # (what the entry points take as the capacity)
-    R = lambda rs: [(segs[s], a, b) for s, a, b in lay.ranges(rs)]
-    off = None
-    if kind == "intersect":
-        _, n = c.intersect([(segs[s], i) for s, i in lay.pairs(args[0])], tomb=tomb, out=out)
-    elif kind == "union":
-        _, n = c.union([(segs[s], i) for s, i in lay.pairs(args[0])], tomb=tomb, out=out)
-    elif kind == "union_ranges":
-        _, n = c.union_ranges(R(args[0]), tomb=tomb, out=out)
-    elif kind == "intersect_ranges":
-        _, n = c.intersect_ranges([R(g) for g in args[0]], tomb=tomb, out=out)
-    elif kind == "andnot":
-        _, n = c.andnot_ranges([R(g) for g in args[0]], [R(g) for g in args[1]], tomb=tomb, out=out)
-    elif kind == "batch":
-        _, off = c.query_batch([(op, R(rs)) for op, rs in args[0]], tomb=tomb, out=out)
-    else:
-        _, off = c.query_batch_groups([([R(g) for g in groups], [R(g) for g in exclude]) for groups, exclude in args[0]], tomb=tomb, out=out)
-    if off is None:
-        off = np.array([0, n], np.uint64)
-    out.count = cap + 64
-    got = out.download()
-    assert np.all(got[int(off[-1]):] == SENTINEL), "ids written behind the result"
-    return [got[int(a):int(b)] for a, b in zip(off[:-1], off[1:])], off
-
 
 CASE_LAYOUTS = [pytest.param(case, layout, id=f"{case.name}-{layout}") for case in pc.CASES for layout in case.layouts()]
 
 
 @pytest.mark.parametrize("case,layout", CASE_LAYOUTS)
 def test_path_and_result(ctx, case, layout):
-    lists = case.lists()
-    lay = pc.Layout(layout, lists)
-    removed = pc.removed_ids(case, lists) if case.tomb else None
-    want = pc.reference(case, lists, removed)
-    segs = [ctx.encode(*lay.flat(s)) for s in range(len(lay.segments))]
-    assert [s.info.n_lists for s in segs] == lay.n_lists
-    tomb = ctx.tombstones(removed) if case.tomb else None
-    try:
-        for name, value in case.options.items():
-            ctx.set_option(name, value)
-        for repeat in (False, True) if layout == "big" else (False,):
-            before = ctx.paths()
-            got, off = _run(ctx, case, segs, lay, tomb, want)
-            delta = _delta(before, ctx.paths())
-            print(case.name, layout, "repeat" if repeat else "first", delta)
-            assert delta == case.expect_in(layout, repeat)
-            assert list(off) == list(np.cumsum([0] + [w.size for w in want]))              # (a batch's out_off; else [0, count])
-            for q, (g, w) in enumerate(zip(got, want)):
-                assert g.dtype == np.uint32 and np.array_equal(g.astype(np.uint64), w), q
-    finally:
-        for name in case.options:
-            ctx.set_option(name, pc.DEFAULTS[name])
-        for s in segs:
-            s.free()
-        if tomb is not None:
-            tomb.free()
+    run_path_case(ctx, case, layout, pc.DEFAULTS)
