@@ -1328,105 +1328,70 @@ extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint6
 }
 
 // ---- AND of ORs minus excluded groups -----------------------------------------------------------------
-// The one-launch form (setop_groups.hip): the non-empty lists of the required groups, group by group, then the excluded lists
-// that count, when they are at most MAX_LISTS lists of SMALL_SET_POSTINGS postings in SMALL_SET_BLOCKS blocks and the result
-// surely fits.  *taken = false when the query is too large (or option andnot.small is 0).
-static int andnot_small(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std::vector<GroupIn> &req, const std::vector<RangeIn> &rx,
-                        const IrPass &ex, uint64_t shortest, const SetOut &o, bool *taken) {
-    *taken = false;
-    if (!ctx->opt_andnot_small || o.cap < shortest || req.size() > MAX_LISTS) return II2_OK;
-    GroupSetParams gp;
-    std::memset(&gp, 0, sizeof gp);
-    uint32_t m = 0, nb = 0;
-    uint64_t sum = 0;
-    bool fits = true;
-    auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
-        const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1], c = s->h_cnt[j];
-        if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || !blocks_full(b1 - b0, c)) {
-            fits = false;
-            return;
+// A grouped query as ii2_andnot_ranges and every query of ii2_query_batch_groups plan it (plan_groups, then size_exclusions): the
+// two entry points agree on what is empty and on which excluded lists count because this is the only place that decides it.
+struct GroupQuery {
+    std::vector<RangeIn> rs, rx;            // the ranges of all groups; those of the excluded groups, back to back: ONE logical group
+    std::vector<GroupIn> all, req;          // every group; the required ones, sized (group_sizes)
+    IrPass ex;                              // the exclusion over rx
+    uint64_t shortest;                      // the postings of the smallest required group: no result is longer
+    bool req_known;                         // the host mirrors every required group's doc span
+    bool empty;                             // no group, a required group without blocks, or required spans that do not overlap
+};
+
+// Everything checked before anything is launched or written; `who` names the entry point in the messages, `per` what its block
+// limit counts over ("call" | "query").  group_not == NULL: every group is required.  Q's vectors keep their storage between calls.
+// (Inlined into its two callers, like the walk below: out of line they cost the batch 6 ns per query, 3 % at six lists a query.)
+__attribute__((always_inline)) static inline int plan_groups(ii2_ctx *ctx, const char *who, const char *per, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                       const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q) {
+    Q.rs.clear();
+    Q.rx.clear();
+    Q.all.clear();
+    Q.req.clear();
+    Q.ex = IrPass{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
+    Q.shortest = ~0ull;
+    Q.req_known = true;
+    Q.empty = true;
+    if (n_groups == 0) return II2_OK;
+    uint64_t n_req = 0;
+    for (uint64_t g = 0; g < n_groups; g++) {
+        if (group_not && group_not[g] > 1) return fail(ctx, II2_EINVAL, (std::string(who) + ": a group_not flag is neither 0 nor 1").c_str());
+        n_req += group_not && group_not[g] ? 0u : 1u;
+    }
+    if (!n_req) return fail(ctx, II2_EINVAL, (std::string(who) + ": no required group (the library has no doc universe to complement)").c_str());
+    uint64_t n_blocks = 0;
+    if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, Q.rs, Q.all, &n_blocks)) return rc;
+    if (n_blocks >= 0xFFFFFFFFull || Q.rs.size() >= 0xFFFFFFFFull)
+        return fail(ctx, II2_ERANGE, (std::string(who) + ": more than 2^32 - 2 blocks in one " + per).c_str());
+    for (uint64_t g = 0; g < n_groups; g++) {
+        const GroupIn &G = Q.all[g];
+        if (!group_not || !group_not[g]) {
+            if (!G.n_blocks) return II2_OK;                             // a required group without postings
+            Q.req.push_back(G);
+        } else {                                                        // (an excluded group without postings adds nothing)
+            Q.rx.insert(Q.rx.end(), Q.rs.begin() + G.r0, Q.rs.begin() + G.r1);
+            Q.ex.n_blocks += G.n_blocks;
         }
-        gp.lists[m] = list_view(s, j);
-        gp.blk_base[m] = nb;
-        gp.lpre[m] = (uint32_t)sum;
-        gp.tag[m] = (uint8_t)tag;
-        m++;
-        nb += b1 - b0;
-        sum += c;
-    };
-    for (size_t g = 0; g < req.size() && fits; g++)
-        for (size_t r = req[g].r0; r < req[g].r1 && fits; r++)
-            for (uint64_t j = rs[r].l0; j < rs[r].l1 && fits; j++)
-                if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) add(rs[r].seg, j, (uint32_t)g);
-    for (size_t r = ex.r0; r < ex.r1 && fits && ex.n_nonempty; r++)
-        for (uint64_t j = rx[r].l0; j < rx[r].l1 && fits; j++)
-            if (ir_list_counts(ex, rx[r].seg, j)) add(rx[r].seg, j, (uint32_t)req.size());
-    if (!fits) return II2_OK;
-    // The kernel ranks every id by one bisection per other list: its time grows with postings x lists, the general form's with
-    // the number of groups.  Measured (DESIGN.md §4.1h, scripts/andnot_probe.py): at the kernel's capacity, 64 lists x 8000
-    // postings, 410 us against the general form's 165 - 180 (four groups).  Sweep, 2 required + 1 excluded group, 4 - 64 lists:
-    // ~60 us + 0.68 ns per posting x list against 133 - 145 us - the one-launch form wins every point up to postings x lists =
-    // 65 536 (1.3 - 2.2x), ties at ~130 000 and loses beyond.  The limit is deliberately below that crossover: the general
-    // form's wait was half as long on another machine of the same kind (63 - 68 us for three groups).
-    // (option andnot.small = 2 lifts the limit to the kernel's capacity: tests, measurements)
-    if (ctx->opt_andnot_small == 1 && sum * m > ANDNOT_SMALL_WORK) return II2_OK;
-    gp.blk_base[m] = nb;
-    gp.lpre[m] = (uint32_t)sum;
-    gp.n_lists = m;
-    gp.n_blocks = nb;
-    gp.n_req = (uint32_t)req.size();
-    set_out(gp, o);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    took(ctx, P_ANDNOT_SMALL);
-    HIP_TRY(ctx, launch_setop_groups(gp, ctx->stream, e0, e1));
-    *taken = true;
+    }
+    Q.ex.r1 = Q.rx.size();
+    if (int rc = group_sizes(ctx, Q.rs, Q.req)) return rc;
+    // the common span of the REQUIRED groups only: an excluded group never narrows it
+    common_span(Q.req, &Q.ex.lo, &Q.ex.hi);
+    if (Q.ex.lo > Q.ex.hi) return II2_OK;
+    for (const GroupIn &G : Q.req) { Q.shortest = std::min(Q.shortest, G.n_post); Q.req_known = Q.req_known && G.span_known; }
+    Q.empty = false;
     return II2_OK;
 }
 
-static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
-                                  const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
-                                  uint32_t *d_out, uint64_t cap, uint64_t *count) {
-    if (!group_not) return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
-    if (n_groups == 0) { *count = 0; return II2_OK; }
-    // 1. everything checked before anything is launched or written
-    uint64_t n_req = 0;
-    for (uint64_t g = 0; g < n_groups; g++) {
-        if (group_not[g] > 1) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: a group_not flag is neither 0 nor 1");
-        n_req += group_not[g] ? 0u : 1u;
-    }
-    if (!n_req) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: no required group (the library has no doc universe to complement)");
-    std::vector<RangeIn> rs, rx;               // the ranges of all groups; those of the excluded groups, back to back: ONE logical group
-    std::vector<GroupIn> all, req;
-    uint64_t n_blocks = 0;
-    if (int rc = collect_groups(ctx, "ii2_andnot_ranges", n_groups, group_first, segs, list_first, list_end, rs, all, &n_blocks)) return rc;
-    if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_andnot_ranges: more than 2^32 - 2 blocks in one call");
-    IrPass ex{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
-    for (uint64_t g = 0; g < n_groups; g++) {
-        if (!group_not[g]) {
-            if (!all[g].n_blocks) { *count = 0; return II2_OK; }       // a required group without postings
-            req.push_back(all[g]);
-        } else {                                                        // (an excluded group without postings adds nothing)
-            rx.insert(rx.end(), rs.begin() + all[g].r0, rs.begin() + all[g].r1);
-            ex.n_blocks += all[g].n_blocks;
-        }
-    }
-    ex.r1 = rx.size();
-    if (int rc = group_sizes(ctx, rs, req)) return rc;
-    // the common span of the REQUIRED groups only: an excluded group never narrows it
-    uint32_t clo, chi;
-    common_span(req, &clo, &chi);
-    if (clo > chi) { *count = 0; return II2_OK; }
-    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: output buffer is NULL");
-    uint64_t shortest = ~0ull;
-    bool req_known = true;
-    for (const GroupIn &G : req) { shortest = std::min(shortest, G.n_post); req_known = req_known && G.span_known; }
-    // 2. the excluded lists that count: non-empty, their doc span (where the host mirrors it) meeting the common span
-    ex.lo = clo;
-    ex.hi = chi;
+// The excluded lists of a planned query that count - non-empty, their doc span (where the host mirrors it) meeting the required
+// groups' common span - sized for the general form; ex.lo / ex.hi shrink to their span where every one is mirrored.  That
+// changes nothing about which lists count: a list that meets the common span lies inside the span of all such lists, so it
+// meets the narrowed span too, and no other list does - the walk below may run before or after this.
+static int size_exclusions(ii2_ctx *ctx, GroupQuery &Q) {
+    IrPass &ex = Q.ex;
     uint32_t elo = 0xFFFFFFFFu, ehi = 0;
     bool ex_known = true;
-    for (const RangeIn &q : rx) {
+    for (const RangeIn &q : Q.rx) {
         const ii2_seg *s = q.seg;
         if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
         const bool mirrored = spans_mirrored(s);
@@ -1440,13 +1405,93 @@ static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_
             ehi = std::max(ehi, s->h_spans[3 * j + 2]);
         }
     }
-    if (ex.n_nonempty && ex_known) { ex.lo = std::max(clo, elo); ex.hi = std::min(chi, ehi); }     // (lo <= hi: every list that counts meets [clo, chi])
+    if (ex.n_nonempty && ex_known) { ex.lo = std::max(ex.lo, elo); ex.hi = std::min(ex.hi, ehi); }   // (lo <= hi: every list that counts meets the common span)
+    return II2_OK;
+}
+
+// the lists, blocks and postings a walk has taken, whether every list it met fitted, and the error that ended it (rc != II2_OK)
+struct Counted { uint32_t m, nb; uint64_t sum; bool fits; int rc; };
+
+// The lists of a planned query that count, in the order the one-workgroup kernels want them (setop_groups.hip,
+// setop_groups_batch.hip; `mirror`: the context that mirrors the excluded segments' counts on the way, NULL after size_exclusions): the non-empty lists of the required groups, group by group, tag = the group's number; then the
+// excluded lists that count, tag = the number of required groups.  put(segment, list, tag, the totals before it) sees each one
+// while they fit one workgroup - at most MAX_LISTS regular lists (blocks_full) of SMALL_SET_POSTINGS postings in SMALL_SET_BLOCKS
+// blocks; the walk ends at the first list that does not.
+template <class F> __attribute__((always_inline)) static inline Counted for_each_counted_list(ii2_ctx *mirror, const GroupQuery &Q, F &&put) {
+    Counted t{0, 0, 0, true, II2_OK};
+    auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
+        const uint32_t nb = s->h_blk_off[j + 1] - s->h_blk_off[j], c = s->h_cnt[j];
+        if (t.m == MAX_LISTS || nb > SMALL_SET_BLOCKS - t.nb || t.sum + c > SMALL_SET_POSTINGS || !blocks_full(nb, c)) { t.fits = false; return; }
+        put(s, j, tag, t);
+        t.m++;
+        t.nb += nb;
+        t.sum += c;
+    };
+    for (size_t g = 0; g < Q.req.size() && t.fits; g++)
+        for (size_t r = Q.req[g].r0; r < Q.req[g].r1 && t.fits; r++)
+            for (uint64_t j = Q.rs[r].l0; j < Q.rs[r].l1 && t.fits; j++)
+                if (Q.rs[r].seg->h_blk_off[j + 1] > Q.rs[r].seg->h_blk_off[j]) add(Q.rs[r].seg, j, (uint32_t)g);
+    // (not skipped on ex.n_nonempty == 0: the batch walks without size_exclusions, which fills it; no list counts then anyway)
+    for (size_t r = Q.ex.r0; r < Q.ex.r1 && t.fits; r++) {
+        if (mirror && (t.rc = ii2_seg_host_cnt(mirror, Q.rx[r].seg))) return t;
+        for (uint64_t j = Q.rx[r].l0; j < Q.rx[r].l1 && t.fits; j++)
+            if (ir_list_counts(Q.ex, Q.rx[r].seg, j)) add(Q.rx[r].seg, j, (uint32_t)Q.req.size());
+    }
+    return t;
+}
+
+// The one-launch form (setop_groups.hip): the lists that count, when they fit one workgroup and the result surely fits.
+// *taken = false when the query is too large (or option andnot.small is 0).
+static int andnot_small(ii2_ctx *ctx, const GroupQuery &Q, const SetOut &o, bool *taken) {
+    *taken = false;
+    if (!ctx->opt_andnot_small || o.cap < Q.shortest || Q.req.size() > MAX_LISTS) return II2_OK;
+    GroupSetParams gp;
+    std::memset(&gp, 0, sizeof gp);
+    const Counted t = for_each_counted_list(nullptr, Q, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &at) {
+        gp.lists[at.m] = list_view(s, j);
+        gp.blk_base[at.m] = at.nb;
+        gp.lpre[at.m] = (uint32_t)at.sum;
+        gp.tag[at.m] = (uint8_t)tag;
+    });
+    if (!t.fits) return II2_OK;
+    // The kernel ranks every id by one bisection per other list: its time grows with postings x lists, the general form's with
+    // the number of groups.  Measured (DESIGN.md §4.1h, scripts/andnot_probe.py): at the kernel's capacity, 64 lists x 8000
+    // postings, 410 us against the general form's 165 - 180 (four groups).  Sweep, 2 required + 1 excluded group, 4 - 64 lists:
+    // ~60 us + 0.68 ns per posting x list against 133 - 145 us - the one-launch form wins every point up to postings x lists =
+    // 65 536 (1.3 - 2.2x), ties at ~130 000 and loses beyond.  The limit is deliberately below that crossover: the general
+    // form's wait was half as long on another machine of the same kind (63 - 68 us for three groups).
+    // (option andnot.small = 2 lifts the limit to the kernel's capacity: tests, measurements)
+    if (ctx->opt_andnot_small == 1 && t.sum * t.m > ANDNOT_SMALL_WORK) return II2_OK;
+    gp.blk_base[t.m] = t.nb;
+    gp.lpre[t.m] = (uint32_t)t.sum;
+    gp.n_lists = t.m;
+    gp.n_blocks = t.nb;
+    gp.n_req = (uint32_t)Q.req.size();
+    set_out(gp, o);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    took(ctx, P_ANDNOT_SMALL);
+    HIP_TRY(ctx, launch_setop_groups(gp, ctx->stream, e0, e1));
+    *taken = true;
+    return II2_OK;
+}
+
+static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                                  const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                                  uint32_t *d_out, uint64_t cap, uint64_t *count) {
+    if (!group_not) return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
+    // 1. the plan; 2. the excluded lists that count
+    GroupQuery Q;
+    if (int rc = plan_groups(ctx, "ii2_andnot_ranges", "call", n_groups, group_first, group_not, segs, list_first, list_end, Q)) return rc;
+    if (Q.empty) { *count = 0; return II2_OK; }
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_andnot_ranges: output buffer is NULL");
+    if (int rc = size_exclusions(ctx, Q)) return rc;
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
     // 3. short lists: one launch
     {
         const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
         bool taken = false;
-        if (int rc = andnot_small(ctx, rs, req, rx, ex, shortest, o, &taken)) return rc;
+        if (int rc = andnot_small(ctx, Q, o, &taken)) return rc;
         if (taken) {
             if (int rc = read_count(ctx, o.d_count, count)) return rc;
             if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_andnot_ranges: result does not fit the output buffer (nothing written)");
@@ -1457,26 +1502,26 @@ static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_
     // else into the candidate array, which holds the shortest required group: neither a capacity error nor a partly written
     // result can occur there (tombstones are applied here, once)
     took(ctx, P_ANDNOT_GENERAL);
-    if (!ex.n_nonempty && cap >= shortest) return intersect_sized(ctx, rs, req, tomb, d_out, cap, count);
-    if (int rc = grow_device(ctx, &ctx->d_an, &ctx->an_words, shortest + 1, (size_t)((shortest + 1 + (shortest + 1) / 4 + 63) & ~63ull), sizeof(uint32_t),
+    if (!Q.ex.n_nonempty && cap >= Q.shortest) return intersect_sized(ctx, Q.rs, Q.req, tomb, d_out, cap, count);
+    if (int rc = grow_device(ctx, &ctx->d_an, &ctx->an_words, Q.shortest + 1, (size_t)((Q.shortest + 1 + (Q.shortest + 1) / 4 + 63) & ~63ull), sizeof(uint32_t),
                              "ii2_andnot_ranges: candidate allocation failed"))
         return rc;
     uint64_t nc = 0;
-    if (int rc = intersect_sized(ctx, rs, req, tomb, ctx->d_an, shortest, &nc)) return rc;
+    if (int rc = intersect_sized(ctx, Q.rs, Q.req, tomb, ctx->d_an, Q.shortest, &nc)) return rc;
     // 5. one exclusion pass over the candidates into d_out, written only when all survivors fit
-    bool pass = nc && ex.n_nonempty;
-    if (pass && !req_known) {
+    bool pass = nc && Q.ex.n_nonempty;
+    if (pass && !Q.req_known) {
         // the candidates' span is not known from the host mirrors: their first and last id bound the mark's windows
         uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
         HIP_TRY(ctx, hipMemcpyAsync(hb, ctx->d_an, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(hb + 1, ctx->d_an + (nc - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ex.lo = std::max(ex.lo, hb[0]);
-        ex.hi = std::min(ex.hi, hb[1]);
-        pass = ex.lo <= ex.hi;                      // (else no excluded list reaches a candidate)
+        Q.ex.lo = std::max(Q.ex.lo, hb[0]);
+        Q.ex.hi = std::min(Q.ex.hi, hb[1]);
+        pass = Q.ex.lo <= Q.ex.hi;                      // (else no excluded list reaches a candidate)
     }
     if (pass) {
-        if (int rc = ir_filter_pass(ctx, "ii2_andnot_ranges", rx, ex, ctx->d_an, nc, d_out, cap, &nc)) return rc;
+        if (int rc = ir_filter_pass(ctx, "ii2_andnot_ranges", Q.rx, Q.ex, ctx->d_an, nc, d_out, cap, &nc)) return rc;
         *count = nc;
         if (nc > cap) return fail(ctx, II2_ECAPACITY, "ii2_andnot_ranges: result does not fit the output buffer (nothing written)");
         return II2_OK;
@@ -1741,8 +1786,8 @@ extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *
 
 // ---- many AND-of-ORs / NOT queries in one call ------------------------------------------------------
 // Query q owns the groups query_first[q] .. query_first[q + 1] - 1 of an ii2_andnot_ranges call; its result is that call's.
-// The plan of a query follows andnot_ranges_unlocked step by step - same helpers, same order of the checks - so that the two
-// agree on what is empty and on which excluded lists count; what differs is where a short query runs.
+// Every query is planned as that call plans it (plan_groups, size_exclusions, for_each_counted_list); what differs is where a
+// short query runs.
 static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_first, const uint64_t *group_first, const uint8_t *group_not,
                                        const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
                                        uint32_t *d_out, uint64_t cap, uint64_t *out_off) {
@@ -1768,8 +1813,7 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
     std::vector<BatchPlan> plan(nq);
     std::vector<BatchList> tl;             // the table's lists and their tags, the queries in batch order (tiny and small ones alike)
     std::vector<uint8_t> tt;
-    std::vector<RangeIn> rs, rx;
-    std::vector<GroupIn> all, req;
+    GroupQuery gq;                          // (one for the call: its vectors keep their storage from query to query)
     uint64_t stage_ids = 0, max_bound = 0;
     uint32_t n_kind[4] = {0, 0, 0, 0};
     for (uint64_t q = 0; q < nq; q++) {
@@ -1777,77 +1821,29 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
         BatchPlan &pl = plan[q];
         pl = BatchPlan{0, stage_ids, tl.size(), 0, 0, BP_EMPTY, 0, 0};
         auto planned = [&]() { n_kind[pl.kind]++; };
-        if (ng == 0) { planned(); continue; }                              // no group: an empty result
-        uint64_t n_req = 0;
-        for (uint64_t g = g0; g < g0 + ng; g++) {
-            if (group_not && group_not[g] > 1) return bad(q, "a group_not flag is neither 0 nor 1");
-            n_req += group_not && group_not[g] ? 0u : 1u;
-        }
-        if (!n_req) return bad(q, "no required group (the library has no doc universe to complement)");
-        rs.clear();
-        rx.clear();
-        all.clear();
-        req.clear();
-        uint64_t n_blocks = 0;
-        if (int rc = collect_groups(ctx, who, ng, group_first + g0, segs, list_first, list_end, rs, all, &n_blocks)) return named(q, rc);
-        if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull)
-            return fail(ctx, II2_ERANGE, (w + ": query " + std::to_string(q) + ": more than 2^32 - 2 blocks in one query").c_str());
-        IrPass ex{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
-        bool empty = false;
-        for (uint64_t g = 0; g < ng; g++) {
-            if (!group_not || !group_not[g0 + g]) {
-                if (!all[g].n_blocks) empty = true;                          // a required group without postings
-                req.push_back(all[g]);
-            } else {
-                rx.insert(rx.end(), rs.begin() + all[g].r0, rs.begin() + all[g].r1);
-            }
-        }
-        if (empty) { planned(); continue; }
-        ex.r1 = rx.size();
-        if (int rc = group_sizes(ctx, rs, req)) return named(q, rc);
-        uint32_t clo, chi;
-        common_span(req, &clo, &chi);
-        if (clo > chi) { planned(); continue; }                            // the required spans do not overlap
-        uint64_t shortest = ~0ull;
-        for (const GroupIn &G : req) shortest = std::min(shortest, G.n_post);
-        pl.bound = shortest;
+        if (int rc = plan_groups(ctx, who, "query", ng, group_first + g0, group_not ? group_not + g0 : nullptr, segs, list_first, list_end, gq))
+            return named(q, rc);
+        if (gq.empty) { planned(); continue; }
+        pl.bound = gq.shortest;
         pl.kind = BP_LARGE;
-        // A query fits the batch kernel when its non-empty required lists and the excluded lists that count are at most MAX_LISTS
-        // lists of SMALL_SET_POSTINGS postings in SMALL_SET_BLOCKS blocks.  ANDNOT_SMALL_WORK is NOT applied: that bound prices one
-        // workgroup against the general form's waits inside a single call; in a batch the alternative is those waits once per
-        // query, one after the other, while the other CUs sit idle (DESIGN.md §4.1i has the case at the kernel's capacity).
-        if (ctx->opt_batch_groups && req.size() <= MAX_LISTS) {
-            ex.lo = clo;
-            ex.hi = chi;
-            uint32_t m = 0, nb = 0;
-            uint64_t sum = 0;
-            bool fits = true;
-            auto add = [&](const ii2_seg *s, uint64_t j, uint32_t tag) {
-                const uint32_t b0 = s->h_blk_off[j], b1 = s->h_blk_off[j + 1], c = s->h_cnt[j];
-                if (m == MAX_LISTS || b1 - b0 > SMALL_SET_BLOCKS - nb || sum + c > SMALL_SET_POSTINGS || !blocks_full(b1 - b0, c)) {
-                    fits = false;
-                    return;
-                }
-                tl.push_back(BatchList{s->d_skip + b0, s->d_payload, b1 - b0, c});
+        // A query fits the batch kernel when the lists that count fit one workgroup (for_each_counted_list).  ANDNOT_SMALL_WORK is
+        // NOT applied: that bound prices one workgroup against the general form's waits inside a single call; in a batch the
+        // alternative is those waits once per query, one after the other, while the other CUs sit idle (DESIGN.md §4.1i has the
+        // case at the kernel's capacity).
+        if (ctx->opt_batch_groups && gq.req.size() <= MAX_LISTS) {
+            // (size_exclusions' totals and narrowed span, a second pass over the excluded lists, are for the general form: the walk
+            // mirrors their counts itself, and the lists that count are the same under either span)
+            const Counted t = for_each_counted_list(ctx, gq, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &) {
+                const uint32_t b0 = s->h_blk_off[j];
+                tl.push_back(BatchList{s->d_skip + b0, s->d_payload, s->h_blk_off[j + 1] - b0, s->h_cnt[j]});
                 tt.push_back((uint8_t)tag);
-                m++;
-                nb += b1 - b0;
-                sum += c;
-            };
-            for (size_t g = 0; g < req.size() && fits; g++)
-                for (size_t r = req[g].r0; r < req[g].r1 && fits; r++)
-                    for (uint64_t j = rs[r].l0; j < rs[r].l1 && fits; j++)
-                        if (rs[r].seg->h_blk_off[j + 1] > rs[r].seg->h_blk_off[j]) add(rs[r].seg, j, (uint32_t)g);
-            for (size_t r = 0; r < rx.size() && fits; r++) {
-                if (int rc = ii2_seg_host_cnt(ctx, rx[r].seg)) return rc;
-                for (uint64_t j = rx[r].l0; j < rx[r].l1 && fits; j++)
-                    if (ir_list_counts(ex, rx[r].seg, j)) add(rx[r].seg, j, (uint32_t)req.size());
-            }
-            if (fits) {
-                pl.nl = m;
-                pl.n_blocks = nb;
-                pl.kind = ctx->opt_batch_tiny && nb <= BATCH_TINY_BLOCKS && sum <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
-                pl.n_req = (uint8_t)req.size();
+            });
+            if (t.rc) return t.rc;
+            if (t.fits) {
+                pl.nl = t.m;
+                pl.n_blocks = t.nb;
+                pl.kind = ctx->opt_batch_tiny && t.nb <= BATCH_TINY_BLOCKS && t.sum <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
+                pl.n_req = (uint8_t)gq.req.size();
             } else {
                 tl.resize(pl.l0);
                 tt.resize(pl.l0);

@@ -12,7 +12,9 @@ term), --puts of them (default 100: a term is ~16 one-posting lists), plus one s
 Modes:
   single  the Q queries one after the other through ii2_andnot_ranges (it returns its count: a launch and a wait per query) -
           the yardstick.  With --lib it runs on THAT library (one built from the commit to compare against), loaded next to the
-          package's own in the same process, with a context and segments of its own;
+          package's own in the same process, with a context and segments of its own; the same loop then also times the
+          one-by-one calls on the package's library (`single_own`) and the batch on THAT library (`batch_yardstick`), so that
+          a change of the host code shows as each call's median against the other library's min - max;
   batch   the same Q queries in one ii2_query_batch_groups call of the package's library; plus, for s and m, the device time of
           the batch kernel and of the pack kernel alone (option profile.events; of the batch without its large queries - an (s)
           query whose three terms hold more than 64 lists is one, `large_queries` counts them) - wall time minus these two is what the call
@@ -42,6 +44,7 @@ ap.add_argument("--qs", default="1,64,4096")
 ap.add_argument("--runs", type=int, default=15)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--puts", type=int, default=100)
+ap.add_argument("--note", default=None, help="copied into every row (which build is which, say)")
 args = ap.parse_args()
 
 from inverted_index_2_amd import Context, _lib  # noqa: E402
@@ -205,6 +208,8 @@ for case in args.cases.split(","):
     for nq in (int(x) for x in args.qs.split(",")):
         qs = make_queries(case, nq)
         row = {"case": case, "Q": nq, "lists": sum(n_lists(q) for q in qs), "yardstick_lib": args.lib or "own"}
+        if args.note:
+            row["note"] = args.note
         batch, off, row["pack_group_batch_python_us_per_query"], _keep = batch_call(ctx, index, qs, cap, d_out)
         batch()                                          # the results that are being timed are the right ones
         ids = d_out.download(int(off[-1]))
@@ -218,12 +223,17 @@ for case in args.cases.split(","):
             single(record=True)
             assert counts == np.diff(off.astype(np.int64)).tolist(), (case, nq)
             fns = [single, batch]
+            if args.lib:                                 # ... and each call on the OTHER library, in the same loop
+                y_batch = batch_call(yctx, yindex, qs, cap, yd_out)
+                fns += [single_calls(ctx, index, qs, cap, d_out)[0], y_batch[0]]
         res = timed_alternating(fns, nq)
-        row["batch"] = res[-1]
-        row["batch_wall_us_per_call"] = round(res[-1]["median_us_per_query"] * nq, 1)
+        row["batch"] = res[1 if yctx is not None else 0]
+        row["batch_wall_us_per_call"] = round(row["batch"]["median_us_per_query"] * nq, 1)
         if yctx is not None:
             row["single"] = res[0]
-            row["batch_over_single_qps"] = round(res[0]["median_us_per_query"] / res[-1]["median_us_per_query"], 2)
+            row["batch_over_single_qps"] = round(res[0]["median_us_per_query"] / row["batch"]["median_us_per_query"], 2)
+        if len(fns) == 4:
+            row["single_own"], row["batch_yardstick"] = res[2], res[3]
         # an (s) query whose three terms hold more than 64 lists is beyond one workgroup: a large query with passes and waits of
         # its own.  The device times and the host time are those of the batch WITHOUT them (`fit_only` when there are any)
         fit = [q for q in qs if q[0] != "s" or n_lists(q) <= 64]

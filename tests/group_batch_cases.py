@@ -138,6 +138,43 @@ def query_class(pool, groups, exclude):
     return "tiny" if post <= TINY_POSTINGS and blocks <= TINY_BLOCKS else "small"
 
 
+# ---- the capacity table: queries at, and one past, every limit of the one-workgroup kernels --------------------------------
+# A pool of one segment per entry: 33 lists of 256 postings (one full block each), 33 lists of 64 postings, two one-posting
+# lists, 80 short lists, and a one-posting list far outside every other span.
+CAPACITY_LISTS = [
+    [np.arange(i, 256 * 64 + i, 64, dtype=np.uint32) for i in range(33)],
+    [np.arange(i, 64 * 100 + i, 100, dtype=np.uint32) for i in range(33)],
+    [np.array([77], np.uint32), np.array([64], np.uint32)],
+    [np.arange(i % 7, 2000, 17 + i % 5, dtype=np.uint32) for i in range(80)],
+    [np.array([1_000_000], np.uint32)],
+]
+CAPACITY_QUERIES = [
+    # the excluded lists are counted in: 20 + 12 lists, 2048 postings in 32 blocks - exactly the 256-thread form's capacity
+    ([[(1, 0, 10)], [(1, 10, 20)]], [[(1, 20, 32)]]),
+    ([[(1, 0, 10)], [(1, 10, 20)]], [[(1, 20, 33)]]),           # 33 blocks: one past it -> the 1024-thread form
+    ([[(1, 0, 32)]], []),                                       # 32 blocks in one group
+    ([[(1, 0, 33)]], []),
+    ([[(0, 0, 4)], [(0, 2, 6)]], []),                           # 2048 postings in 8 full blocks
+    ([[(0, 0, 4)], [(0, 2, 6)]], [[(2, 0, 1)]]),                # 2049 postings
+    ([[(0, 0, 16)], [(0, 8, 16)]], [[(0, 16, 24)]]),            # 8192 postings in 32 blocks: exactly the 1024-thread form's capacity
+    ([[(0, 0, 16)], [(0, 8, 16)]], [[(0, 16, 24)], [(2, 1, 2)]]),   # 8193 postings: a large query
+    ([[(0, 0, 16)], [(0, 8, 16), (2, 1, 2)]], [[(0, 16, 24)]]),     # ... with the extra posting on the required side
+    ([[(0, 0, 33)]], []),
+    ([[(3, 0, 30)], [(3, 30, 50)]], [[(3, 50, 64)]]),           # 64 lists
+    ([[(3, 0, 30)], [(3, 30, 50)]], [[(3, 50, 65)]]),           # 65 lists: a large query
+    ([[(3, 0, 30), (3, 64, 65)], [(3, 30, 50)]], [[(3, 50, 64)]]),
+    ([[(3, 0, 64)]], []),
+    ([[(3, 0, 65)]], []),
+    ([[(3, 0, 40), (3, 20, 80), (1, 0, 33)]], [[(3, 1, 2)]]),
+    # 64 lists that count plus the far list.  Excluded, its span misses the required groups' common span: it does not count and
+    # the query stays small.  Required in a group of its own, the required spans do not overlap: the query is empty.
+    ([[(3, 0, 30)], [(3, 30, 50)]], [[(3, 50, 64)], [(4, 0, 1)]]),
+    ([[(3, 0, 30)], [(3, 30, 50)], [(4, 0, 1)]], [[(3, 50, 64)]]),
+]
+CAPACITY_CLASSES = ["tiny", "small", "tiny", "small", "tiny", "small", "small", "large", "large", "large", "small", "large", "large",
+                    "small", "large", "large", "small", "empty"]
+
+
 def random_batch(universe, with_tomb, seed):
     """(pool, queries, removed or None, expectations) of one entry of RANDOM_BATCHES"""
     rng = np.random.default_rng(seed)

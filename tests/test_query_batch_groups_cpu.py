@@ -154,3 +154,20 @@ def test_random_batches_hold_every_class_of_query(universe, with_tomb, seed):
     assert all(1 <= count(grp) <= 24 for _, x in queries for grp in x)    # (a range both required and excluded adds up to four)
     if universe > 1_000_000:
         assert any(w.size and w[0] == 0 for w in wants) or removed is not None
+
+
+def test_capacity_table_holds_both_outcomes_with_and_without_exclusions():
+    lists, queries = cases.CAPACITY_LISTS, cases.CAPACITY_QUERIES
+    assert [len(ls) for ls in lists] == [33, 33, 2, 80, 1]
+    assert all(l.size == 256 for l in lists[0]) and all(l.size == 64 for l in lists[1]) and all(l.size == 1 for l in lists[2])
+    assert lists[4][0].tolist() == [1_000_000] and all(int(l[-1]) < 1_000_000 for ls in lists[:4] for l in ls)
+    klass = [cases.query_class(lists, g, x) for g, x in queries]
+    assert klass == cases.CAPACITY_CLASSES and len(klass) == 18
+    with_x = [k for k, (_, x) in zip(klass, queries) if x]              # what the single call's one-launch form is asked about
+    assert sum(k in ("tiny", "small") for k in with_x) >= 4 and with_x.count("large") >= 4
+    # the far list: 64 lists count either way; excluded it is not one of them, required it empties the query
+    counted = lambda g, x: sum(l.size > 0 for grp in g + x for l in cases.lists_of(lists, grp))      # noqa: E731
+    for (g, x), k in zip(queries[16:], ("small", "empty")):
+        assert counted(g, x) == 65 and any((4, 0, 1) in grp for grp in g + x)
+        assert cases.query_class(lists, g, x) == k
+    assert klass[10] == "small" and klass[11] == "large"                # ... and a 65th list that does count makes it large
