@@ -515,6 +515,88 @@ func (c *Ctx) AndNotRangesHost(groupFirst []uint64, groupNot []uint8, segs []*Se
 	}
 }
 
+// AtLeastStats mirrors ii2_atleast_stats.
+type AtLeastStats struct {
+	Counted, Bound                uint64
+	Form, Planes, Windows, NLate uint32
+}
+
+// The forms of AtLeastRanges (II2_ATLEAST_*).
+const (
+	AtLeastNone  = uint32(C.II2_ATLEAST_NONE)
+	AtLeastSmall = uint32(C.II2_ATLEAST_SMALL)
+	AtLeastCount = uint32(C.II2_ATLEAST_COUNT)
+	AtLeastAnd   = uint32(C.II2_ATLEAST_AND)
+	AtLeastOr    = uint32(C.II2_ATLEAST_OR)
+)
+
+// AtLeastRanges answers one threshold query over resident segments (ii2_atleast_ranges): the ids that lie in at least one list
+// of AT LEAST minMatch required groups and in NO list of ANY excluded group.  Groups, ranges and groupNot are those of
+// AndNotRanges; a required group without postings matches no doc.  The ids go to the device buffer out (capacity capIDs ids;
+// the postings of the n' - minMatch + 1 smallest required groups are always enough) and their number is returned.
+// All-or-nothing: on ErrCapacity nothing was written and the returned count is the capacity to call again with.
+func (c *Ctx) AtLeastRanges(groupFirst []uint64, groupNot []uint8, minMatch uint32, segs []*Segment, listFirst, listEnd []uint64, out unsafe.Pointer, capIDs uint64) (uint64, AtLeastStats, error) {
+	nGroups := len(groupFirst) - 1
+	if nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return 0, AtLeastStats{}, fmt.Errorf("atleast ranges: array lengths disagree")
+	}
+	if groupFirst[nGroups] != uint64(len(segs)) { // the C side reads the range arrays up to groupFirst's last element
+		return 0, AtLeastStats{}, fmt.Errorf("atleast ranges: groupFirst does not end at the number of ranges")
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if groupNot != nil && nGroups > 0 {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	var n C.uint64_t
+	var st C.ii2_atleast_stats
+	rc := C.ii2_atleast_ranges(c.h, C.uint64_t(nGroups), u64ptr(groupFirst), flags, C.uint32_t(minMatch), (**C.ii2_seg)(unsafe.Pointer(&hs[0])),
+		u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(out), C.uint64_t(capIDs), &n, &st)
+	stats := AtLeastStats{uint64(st.n_counted), uint64(st.bound), uint32(st.form), uint32(st.n_planes), uint32(st.n_windows), uint32(st.n_late)}
+	if rc == C.II2_ECAPACITY {
+		return uint64(n), stats, ErrCapacity
+	}
+	if rc != 0 {
+		return 0, AtLeastStats{}, c.err("atleast ranges", rc)
+	}
+	return uint64(n), stats, nil
+}
+
+// AtLeastRangesHost is AtLeastRanges with the result in host memory, in the shape of AndNotRangesHost: a device buffer of firstCap
+// ids, a second call with the size the first one reported when the result did not fit, one download.
+func (c *Ctx) AtLeastRangesHost(groupFirst []uint64, groupNot []uint8, minMatch uint32, segs []*Segment, listFirst, listEnd []uint64, firstCap uint64) ([]uint32, error) {
+	capIDs := firstCap
+	for attempt := 0; ; attempt++ {
+		var d unsafe.Pointer
+		if rc := C.ii2_dev_alloc(c.h, C.size_t((capIDs+1)*4), &d); rc != 0 {
+			return nil, c.err("atleast ranges", rc)
+		}
+		n, _, err := c.AtLeastRanges(groupFirst, groupNot, minMatch, segs, listFirst, listEnd, d, capIDs+1)
+		if err == ErrCapacity && attempt == 0 {
+			C.ii2_dev_free(c.h, d)
+			capIDs = n
+			continue
+		}
+		if err != nil {
+			C.ii2_dev_free(c.h, d)
+			return nil, err
+		}
+		ids := make([]uint32, n)
+		var rc C.int
+		if n > 0 {
+			rc = C.ii2_copy_d2h(c.h, unsafe.Pointer(&ids[0]), d, C.size_t(n*4))
+		}
+		C.ii2_dev_free(c.h, d)
+		if rc != 0 {
+			return nil, c.err("atleast ranges", rc)
+		}
+		return ids, nil
+	}
+}
+
 // CountStats mirrors ii2_count_stats.
 type CountStats struct {
 	Lists, Blocks, Decoded, Hits uint64

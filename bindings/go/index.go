@@ -316,6 +316,69 @@ type ResidentIndex interface {
 	Release()
 }
 
+// IntersectAtLeast (additive): the ids under at least minMatch of terms and under none of except - minimum-should-match, "any two
+// of these tags".  One group per term as IntersectExcept builds them, but a required term found in no segment is a group without
+// ranges (it matches no doc), not an empty result; ONE Ctx.AtLeastRanges call with one download - what the C++ host mirror's
+// InvertedIndex::IntersectAtLeast does (host/host_index.cpp).  Like Read, no tombstone filter.
+func IntersectAtLeast(c *Ctx, ix ResidentIndex, terms [][]byte, minMatch uint32, except [][]byte) ([]uint32, error) {
+	if minMatch == 0 {
+		return nil, fmt.Errorf("intersect at least: minMatch is 0")
+	}
+	defer ix.Release()
+	const firstCap = uint64(1) << 22
+	groupFirst := []uint64{0}
+	var groupNot []uint8
+	var segs []*Segment
+	var first, end []uint64
+	var posts []uint64 // the postings bounds of the terms that some segment holds
+	for _, t := range terms {
+		s, l, post := ix.TermLists(t)
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 0)
+		if len(s) > 0 {
+			if post == 0 {
+				post = 1
+			}
+			posts = append(posts, post)
+		}
+	}
+	if uint64(len(posts)) < uint64(minMatch) {
+		return nil, nil
+	}
+	for _, t := range except {
+		s, l, _ := ix.TermLists(t)
+		if len(s) == 0 {
+			continue // (in no segment: it removes nothing)
+		}
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 1)
+	}
+	// a result id lies in at least one of any n' - minMatch + 1 terms: those with the smallest bounds
+	sort.Slice(posts, func(a, b int) bool { return posts[a] < posts[b] })
+	bound := uint64(0)
+	for k := 0; k+int(minMatch) <= len(posts); k++ {
+		bound += posts[k]
+	}
+	if bound > firstCap {
+		bound = firstCap
+	}
+	ids, err := c.AtLeastRangesHost(groupFirst, groupNot, minMatch, segs, first, end, bound)
+	if err != nil {
+		return nil, fmt.Errorf("intersect at least: %w", err)
+	}
+	return ids, nil
+}
+
 // IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
 // "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
 // flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does

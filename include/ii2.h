@@ -414,6 +414,75 @@ int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const
                      const uint64_t *list_end, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb,
                      uint64_t *counts, uint64_t counts_cap, ii2_count_stats *stats /* may be NULL */);
 
+/* THRESHOLD query - "docs that lie in at least min_match of these n groups" (minimum-should-match, n-gram / fuzzy term matching,
+ * "any two of these tags"): the ascending, duplicate-free ids that lie in at least one list of AT LEAST min_match required groups
+ * and in NO list of ANY excluded group, minus the tombstones when tomb != NULL.  An id that sits in several lists of one group
+ * counts once for that group.  Groups, ranges and group_not are exactly those of ii2_andnot_ranges (segments and views alike; a
+ * list may appear in any number of ranges and groups; ranges may overlap; group_not == NULL: every group is required).
+ * ii2_union_ranges is min_match = 1, ii2_andnot_ranges is min_match = the number of required groups.
+ *   - min_match == 0: II2_EINVAL.  n_groups > 0 and no required group: II2_EINVAL, for the reason ii2_andnot_ranges gives.  A
+ *     flag other than 0 / 1: II2_EINVAL.  Bad ranges are rejected as ii2_andnot_ranges rejects them, under this entry point's
+ *     name.  Every check happens before anything is launched or written.
+ *   - a required group without postings does NOT fail the query: it matches no doc.  With n' the number of required groups
+ *     that have postings: min_match > n', or n_groups == 0: *count = 0, nothing is launched, d_out may be NULL.  An excluded
+ *     group without postings is ignored, and so is any excluded list whose doc span misses the required groups' span.
+ *   - a result doc lies in at least one of any n' - min_match + 1 groups, so cap >= the postings of the n' - min_match + 1
+ *     required groups with the fewest postings is always enough (ii2_andnot_ranges' bound at min_match = n', ii2_union_ranges'
+ *     at 1).  All-or-nothing on EVERY form: on II2_ECAPACITY nothing is written to d_out and *count holds the size needed.
+ *   - the counting form holds its counters in at most 8 bit planes: 1 < min_match < n' with min_match > 255 is II2_ERANGE.
+ *     II2_ERANGE also at 2^32 - 2 blocks or ranges.
+ *   - stats and *count are written only on success and on II2_ECAPACITY.
+ * The forms, tried in this order (stats->form tells which one ran; the call counts no kernel path of its own in ii2_ctx_paths -
+ * the two hand-offs run existing code and count its paths):
+ *   II2_ATLEAST_NONE   nothing to do (count 0, nothing launched).
+ *   II2_ATLEAST_AND    min_match = n': the call is ii2_andnot_ranges on the required groups that have postings plus the
+ *   II2_ATLEAST_OR     excluded ones; min_match = 1 with no excluded list that counts: the call is ii2_union_ranges on the
+ *                      required ranges.  Same results, same errors as those entry points (option atleast.handoff, default 1;
+ *                      min_match = n' > 255 is handed off whatever the option says: the counters cannot hold it).
+ *   II2_ATLEAST_SMALL  the lists that count fit one workgroup (at most II2_MAX_LISTS non-empty lists, required and excluded
+ *                      together, 8192 postings in 128 blocks, by default postings x lists <= 32768): ONE launch and one wait,
+ *                      the kernel of ii2_andnot_ranges' one-launch form with "at least min_match required tags" as the rule for a
+ *                      run of equal ids (option atleast.small: 1 default, 2 up to the kernel's capacity, 0 never).
+ *   II2_ATLEAST_COUNT  any number of groups and lists: per window of the doc span, the groups in ascending order of postings
+ *                      are marked one after the other into the per-context doc bitmap of ii2_union_ranges (the union is what
+ *                      counts an id once per group) and added into a bit-sliced counter per doc - B = bit_width(min_match)
+ *                      bitmaps, saturating, a second grow-only per-context allocation of at most 128 MiB kept until
+ *                      ii2_ctx_destroy.  A doc absent from the first n' - min_match + 1 groups cannot reach min_match: the
+ *                      groups behind them ("late") only add into 2048-doc chunks that already hold a counter.  Then the
+ *                      excluded lists are marked, the counters compared with min_match, and the union's count / scan / compact
+ *                      kernels produce the ids (tombstones, several windows, count-first when they may not fit).  The window
+ *                      is min(1 << union.many_window_log2, 2^30 / B rounded down to a power of two) docs. */
+#define II2_ATLEAST_NONE 0u
+#define II2_ATLEAST_SMALL 1u
+#define II2_ATLEAST_COUNT 2u
+#define II2_ATLEAST_AND 3u
+#define II2_ATLEAST_OR 4u
+typedef struct {
+    uint64_t n_counted;   /* required groups with postings (n') */
+    uint64_t bound;       /* the result bound the call used: the postings of the n' - min_match + 1 smallest of them (0: min_match > n') */
+    uint32_t form;        /* II2_ATLEAST_NONE / _SMALL / _COUNT / _AND / _OR: what ran */
+    uint32_t n_planes;    /* counter bitmaps of the counting form (0 otherwise) */
+    uint32_t n_windows;   /* doc windows of the counting form */
+    uint32_t n_late;      /* groups added in "late" mode */
+} ii2_atleast_stats;      /* 32 bytes */
+int ii2_atleast_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first,
+                       const uint8_t *group_not, uint32_t min_match,
+                       const ii2_seg *const *segs, const uint64_t *list_first,
+                       const uint64_t *list_end, const ii2_tomb *tomb,
+                       uint32_t *d_out, uint64_t cap, uint64_t *count,
+                       ii2_atleast_stats *stats /* may be NULL */);
+/* The counting form's arithmetic, host only (no GPU needed).  For a query of n_counted required groups with postings:
+ * *n_planes = bit_width(min_match), *window_docs = the docs per window at option union.many_window_log2 = window_log2 (see above;
+ * n_planes x window_docs / 8 <= 128 MiB), *first_late = n_counted - min_match + 1 - the groups from that index on, in ascending
+ * order of postings, are added in late mode.  min_match == 0: II2_EINVAL.  1 < min_match < n_counted with min_match > 255:
+ * II2_ERANGE.  min_match > n_counted (nothing runs), or min_match = n_counted > 255 (always handed off): all three are 0. */
+int ii2_atleast_plan(uint64_t n_counted, uint32_t min_match, uint32_t window_log2,
+                     uint32_t *n_planes, uint64_t *window_docs, uint64_t *first_late);
+/* *mask = the docs of one bitmap word whose counter is >= min_match after the words adds[0 .. n_adds) have been added into
+ * n_planes zero planes, by the functions the kernels run (saturating: a counter never wraps).  n_planes outside 1 .. 8,
+ * min_match == 0 or min_match >= 2^n_planes: II2_EINVAL. */
+int ii2_atleast_word(uint32_t n_planes, uint32_t min_match, const uint32_t *adds, uint32_t n_adds, uint32_t *mask);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -504,6 +573,9 @@ int ii2_selftest(ii2_ctx *ctx);
  *   andnot.small                            ii2_andnot_ranges: 1 (default) queries of at most II2_MAX_LISTS non-empty lists, 8192 postings and
  *                                           128 blocks with postings x lists <= 32768 whose result surely fits run as one launch; 2 the
  *                                           same up to the kernel's capacity (no postings x lists bound); 0 never (always the general form)
+ *   atleast.small                           ii2_atleast_ranges: its one-launch form, with andnot.small's values and limits (default 1)
+ *   atleast.handoff                         ii2_atleast_ranges: 1 (default) min_match = n' runs ii2_andnot_ranges' paths and min_match = 1
+ *                                           without exclusion ii2_union_ranges'; 0 (tests, measuring) they take the forms of its own
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel

@@ -159,6 +159,7 @@ void ii2_ctx_destroy(ii2_ctx *ctx) {
     if (ctx->d_lb) (void)hipFree(ctx->d_lb);
     if (ctx->d_small) (void)hipFree(ctx->d_small);
     if (ctx->d_um_bits) (void)hipFree(ctx->d_um_bits);
+    if (ctx->d_thr) (void)hipFree(ctx->d_thr);
     if (ctx->h_um) (void)hipHostFree(ctx->h_um);
     if (ctx->d_ir) (void)hipFree(ctx->d_ir);
     if (ctx->h_ir) (void)hipHostFree(ctx->h_ir);
@@ -1056,6 +1057,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "intersect.ranges") ctx->opt_intersect_ranges = value;
     else if (k == "intersect.ranges_mark") ctx->opt_ir_mark = value;
     else if (k == "andnot.small") ctx->opt_andnot_small = value;
+    else if (k == "atleast.small") ctx->opt_atleast_small = value;
+    else if (k == "atleast.handoff") ctx->opt_atleast_handoff = value;
     else if (k == "union.sparsity") ctx->opt_union_sparsity = value > 0 ? value : 2048;
     else if (k == "intersect.map_docs") ctx->opt_intersect_map_docs = value;
     else if (k == "intersect.dense") ctx->opt_intersect_dense = value;

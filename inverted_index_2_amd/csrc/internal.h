@@ -122,6 +122,10 @@ struct ii2_ctx {
     int64_t opt_andnot_small = 1;       // ii2_andnot_ranges: short queries in one launch (setop_groups.hip); 0: never, 2: up to the kernel's capacity
     uint32_t *d_an = nullptr;           // its required part's result, the candidates of the exclusion pass (grow-only; neither d_ir, which the
     size_t an_words = 0;                //     group path ping-pongs in, nor workspace, which the driver's union reserves itself)
+    int64_t opt_atleast_small = 1;      // ii2_atleast_ranges: short queries in one launch (setop_groups.hip), as andnot.small; 0: never, 2: up to the kernel's capacity
+    int64_t opt_atleast_handoff = 1;    // ... min_match = n' through ii2_andnot_ranges' paths, min_match = 1 without exclusion through the union's (0: tests, measuring)
+    uint32_t *d_thr = nullptr;          // its counting form's counter planes + accumulated summary: all-zero between calls like d_um_bits and
+    size_t thr_words = 0;               //     cleaned with it (grow-only, <= 128 MiB + 64 KiB)
     int64_t opt_batch_small = 1;        // ii2_query_batch: small queries share the batch kernel (0: every query through the single-query paths)
     int64_t opt_batch_tiny = 1;         // ... of both entry points: those of <= 2048 postings in <= 32 blocks in the 256-thread form (0: all in the 1024-thread one)
     int64_t opt_batch_groups = 1;       // ii2_query_batch_groups: queries that fit share its batch kernel (0: every query through ii2_andnot_ranges' paths)
@@ -379,8 +383,11 @@ struct GroupSetParams {
     uint32_t *out;
     uint64_t out_cap;            // nothing is written when the result is longer
     uint64_t *d_count;
+    uint32_t min_match;          // the threshold instantiation (ii2_atleast_ranges): required groups an id must lie in, 1 .. n_req
 };
 hipError_t launch_setop_groups(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the same kernel with the survive rule "in at least min_match required groups" instead of "in every one"
+hipError_t launch_setop_groups_atleast(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_batch_pack(const BatchPackParams &p, uint64_t max_bound, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // many short AND-of-ORs / NOT queries in one launch (setop_groups_batch.hip): the batch kernel's table (is_union unused), every
@@ -497,6 +504,21 @@ hipError_t launch_union_many_bounds(const UnionManyParams &p, hipStream_t s);
 hipError_t launch_union_many_mark(const UnionManyParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_union_many_count(const UnionManyParams &p, uint32_t grid, hipStream_t s);
 hipError_t launch_union_many_compact(const UnionManyParams &p, uint32_t grid, hipStream_t s);
+
+// docs in at least m of n groups, counting form (atleast.hip): the bit-sliced counters behind the union's mark kernel
+struct ThrParams {
+    uint32_t *bitmap;            // the window's doc bitmap G [n_sum * 2048] and ...
+    uint32_t *summary;           // ... its summary [n_sum], as UnionManyParams has them
+    uint32_t *planes;            // [n_planes][plane_words]: plane b holds bit b of every doc's counter, laid out as the bitmap
+    uint32_t *acc;               // [n_sum] the accumulated summary S_acc: the chunks some counter of which may be non-zero
+    uint32_t plane_words;        // n_sum * 2048
+    uint32_t n_sum;
+    uint32_t n_planes;           // 1 .. THR_MAX_PLANES (atleast_count.h)
+    uint32_t min_match;          // < 2^n_planes
+    uint32_t late;               // k_thr_add: 1 = chunks that S_acc does not name are cleared, not added
+};
+hipError_t launch_thr_add(const ThrParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_thr_select(const ThrParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // AND of ORs over list ranges: the filters of the group path (intersect_ranges.hip)
 constexpr uint32_t IR_PROBE_RUN = 256;          // consecutive candidates per wave of the probe

@@ -15,6 +15,11 @@
 //        postings in 128 blocks, a result that surely fits: one launch (setop_groups.hip); otherwise the required groups through
 //        the chooser above into a candidate array, then ONE exclusion pass over the excluded lists that reach the candidates'
 //        span - the probe / mark filter with the flag turned round - or, without such a list, a copy.
+//   At least m of n groups (ii2_atleast_ranges): no group or m above the n' required groups that have postings (count 0, no launch);
+//        m = n': the call above on those groups, m = 1 without exclusion: the OR of list ranges (the hand-offs); the lists that
+//        count fit one workgroup: one launch (setop_groups.hip, the threshold rule); otherwise the counting form - per window the
+//        groups marked one by one (union_many.hip) and added into bit-sliced counters, compared with m (atleast.hip), then the
+//        OR of list ranges' count, scan and compact.
 //   Many AND / OR queries in one call (ii2_query_batch): the small ones in one launch per size class (setop_batch.hip), the
 //        others one by one through the choosers above; all of them staged, then packed in query order.
 //   Many AND-of-ORs / NOT queries in one call (ii2_query_batch_groups): every query an ii2_andnot_ranges call - those that fit
@@ -27,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "atleast_count.h"
 #include "internal.h"
 
 using namespace ii2;
@@ -596,12 +602,13 @@ static uint64_t um_window(const ii2_ctx *ctx) {
     return 1ull << std::min<int64_t>(std::max<int64_t>(ctx->opt_union_many_window_log2, 11), 30);
 }
 
-// the per-context doc bitmap is all-zero between calls: a call that stopped half-way (its copy from the staging block may still be
-// pending, its marks are still set) is cleaned up by the next one
+// the per-context doc bitmap - and the counter planes of ii2_atleast_ranges - are all-zero between calls: a call that stopped
+// half-way (its copy from the staging block may still be pending, its marks are still set) is cleaned up by the next one
 static int um_scratch_clean(ii2_ctx *ctx) {
     if (!ctx->um_dirty) return II2_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->d_um_bits) HIP_TRY(ctx, hipMemsetAsync(ctx->d_um_bits, 0, ctx->um_bits_words * sizeof(uint32_t), ctx->stream));
+    if (ctx->d_thr) HIP_TRY(ctx, hipMemsetAsync(ctx->d_thr, 0, ctx->thr_words * sizeof(uint32_t), ctx->stream));
     ctx->um_dirty = false;
     return II2_OK;
 }
@@ -1440,11 +1447,13 @@ template <class F> __attribute__((always_inline)) static inline Counted for_each
     return t;
 }
 
-// The one-launch form (setop_groups.hip): the lists that count, when they fit one workgroup and the result surely fits.
-// *taken = false when the query is too large (or option andnot.small is 0).
-static int andnot_small(ii2_ctx *ctx, const GroupQuery &Q, const SetOut &o, bool *taken) {
+// The one-launch form (setop_groups.hip) of a planned query: the lists that count, when they fit one workgroup.  opt: the
+// entry point's option (1: up to ANDNOT_SMALL_WORK postings x lists, 2: up to the kernel's capacity); min_match == 0: an id
+// survives in every required group (ii2_andnot_ranges, counted as its path), else in at least min_match of them
+// (ii2_atleast_ranges).  *taken = false when the query is too large.
+static int groups_one_launch(ii2_ctx *ctx, const GroupQuery &Q, const SetOut &o, int64_t opt, uint32_t min_match, bool *taken) {
     *taken = false;
-    if (!ctx->opt_andnot_small || o.cap < Q.shortest || Q.req.size() > MAX_LISTS) return II2_OK;
+    if (Q.req.size() > MAX_LISTS) return II2_OK;
     GroupSetParams gp;
     std::memset(&gp, 0, sizeof gp);
     const Counted t = for_each_counted_list(nullptr, Q, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &at) {
@@ -1460,20 +1469,28 @@ static int andnot_small(ii2_ctx *ctx, const GroupQuery &Q, const SetOut &o, bool
     // ~60 us + 0.68 ns per posting x list against 133 - 145 us - the one-launch form wins every point up to postings x lists =
     // 65 536 (1.3 - 2.2x), ties at ~130 000 and loses beyond.  The limit is deliberately below that crossover: the general
     // form's wait was half as long on another machine of the same kind (63 - 68 us for three groups).
-    // (option andnot.small = 2 lifts the limit to the kernel's capacity: tests, measurements)
-    if (ctx->opt_andnot_small == 1 && t.sum * t.m > ANDNOT_SMALL_WORK) return II2_OK;
+    // (option value 2 lifts the limit to the kernel's capacity: tests, measurements)
+    if (opt == 1 && t.sum * t.m > ANDNOT_SMALL_WORK) return II2_OK;
     gp.blk_base[t.m] = t.nb;
     gp.lpre[t.m] = (uint32_t)t.sum;
     gp.n_lists = t.m;
     gp.n_blocks = t.nb;
     gp.n_req = (uint32_t)Q.req.size();
+    gp.min_match = min_match;
     set_out(gp, o);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
-    took(ctx, P_ANDNOT_SMALL);
-    HIP_TRY(ctx, launch_setop_groups(gp, ctx->stream, e0, e1));
+    if (!min_match) took(ctx, P_ANDNOT_SMALL);
+    HIP_TRY(ctx, min_match ? launch_setop_groups_atleast(gp, ctx->stream, e0, e1) : launch_setop_groups(gp, ctx->stream, e0, e1));
     *taken = true;
     return II2_OK;
+}
+
+// ... of ii2_andnot_ranges: when the result surely fits, too.  *taken = false when the query is too large (or option andnot.small is 0).
+static int andnot_small(ii2_ctx *ctx, const GroupQuery &Q, const SetOut &o, bool *taken) {
+    *taken = false;
+    if (!ctx->opt_andnot_small || o.cap < Q.shortest) return II2_OK;
+    return groups_one_launch(ctx, Q, o, ctx->opt_andnot_small, 0u, taken);
 }
 
 static int andnot_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
@@ -1544,6 +1561,315 @@ extern "C" int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return andnot_ranges_unlocked(ctx, n_groups, group_first, group_not, segs, list_first, list_end, tomb, d_out, cap, count);
 }
+
+// ---- at least m of n groups -------------------------------------------------------------------------
+// The plan of ii2_atleast_ranges, plan_groups' sibling: the same checks under this entry point's name and the same helpers, but a
+// required group without postings is dropped, not fatal (Q.req: the n' required groups that have postings, tags 0 .. n' - 1
+// in for_each_counted_list), and the span the excluded lists must meet is the required groups' whole span, not their common
+// one - a result doc need not lie in every group.  kept: the groups of the call that are left (the AND hand-off's arguments).
+static int plan_atleast(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                        const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q, std::vector<uint64_t> &kept) {
+    Q.ex = IrPass{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
+    Q.shortest = ~0ull;
+    Q.req_known = true;
+    Q.empty = true;
+    if (n_groups == 0) return II2_OK;
+    uint64_t n_req = 0;
+    for (uint64_t g = 0; g < n_groups; g++) {
+        if (group_not && group_not[g] > 1) return fail(ctx, II2_EINVAL, (std::string(who) + ": a group_not flag is neither 0 nor 1").c_str());
+        n_req += group_not && group_not[g] ? 0u : 1u;
+    }
+    if (!n_req) return fail(ctx, II2_EINVAL, (std::string(who) + ": no required group (the library has no doc universe to complement)").c_str());
+    uint64_t n_blocks = 0;
+    if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, Q.rs, Q.all, &n_blocks)) return rc;
+    if (n_blocks >= 0xFFFFFFFFull || Q.rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, (std::string(who) + ": more than 2^32 - 2 blocks in one call").c_str());
+    for (uint64_t g = 0; g < n_groups; g++) {
+        const GroupIn &G = Q.all[g];
+        if (!group_not || !group_not[g]) {
+            if (!G.n_blocks) continue;                                  // a required group without postings matches no doc
+            Q.req.push_back(G);
+        } else {                                                        // (an excluded group without postings adds nothing)
+            Q.rx.insert(Q.rx.end(), Q.rs.begin() + G.r0, Q.rs.begin() + G.r1);
+            Q.ex.n_blocks += G.n_blocks;
+        }
+        kept.push_back(g);
+    }
+    Q.ex.r1 = Q.rx.size();
+    if (Q.req.empty()) return II2_OK;
+    if (int rc = group_sizes(ctx, Q.rs, Q.req)) return rc;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (const GroupIn &G : Q.req) {
+        Q.shortest = std::min(Q.shortest, G.n_post);
+        Q.req_known = Q.req_known && G.span_known;
+        lo = std::min(lo, G.lo);
+        hi = std::max(hi, G.hi);
+    }
+    if (Q.req_known) { Q.ex.lo = lo; Q.ex.hi = hi; }                   // (else every excluded list counts)
+    Q.empty = false;
+    return II2_OK;
+}
+
+// the counter planes + accumulated summary of the largest window of a doc span (grow-only, zeroed when they grow)
+static int thr_scratch_reserve(ii2_ctx *ctx, uint32_t n_planes, uint64_t span, uint64_t W) {
+    const uint64_t n_sum_call = (std::min(span, W) + 65535) / 65536;
+    const size_t words = (size_t)n_planes * n_sum_call * 2048 + n_sum_call;
+    if (ctx->thr_words >= words) return II2_OK;
+    if (int rc = grow_device(ctx, &ctx->d_thr, &ctx->thr_words, words, words, sizeof(uint32_t), "ii2_atleast_ranges: counter allocation failed")) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_thr, 0, words * sizeof(uint32_t), ctx->stream));
+    return II2_OK;
+}
+
+// The counting form (atleast.hip) of a planned query, order: its required groups in ascending order of postings.  Per window of
+// the doc span and group: mark (union_many.hip), add; then the excluded lists' mark, select, and the block-wise OR's count, scan
+// and compact.  The descriptors of all groups are staged once.  At most two waits: the bounds of spans the host does not mirror,
+// and the count.
+static int atleast_count(ii2_ctx *ctx, GroupQuery &Q, const std::vector<size_t> &order, uint32_t min_match, const ii2_tomb *tomb, uint32_t *d_out,
+                         uint64_t cap, uint64_t *count, ii2_atleast_stats &stats) {
+    hipStream_t st = ctx->stream;
+    const size_t n1 = order.size();
+    const bool excl = Q.ex.n_nonempty > 0;
+    const uint32_t B = thr_bit_width(min_match);
+    const size_t first_late = n1 - min_match + 1;
+    if (int rc = um_scratch_clean(ctx)) return rc;
+    // staging: one descriptor block (ranges + block prefix) per group in `order`, then one for all excluded ranges
+    std::vector<size_t> at(n1 + 1);
+    size_t stage_bytes = 0;
+    for (size_t k = 0; k < n1; k++) {
+        at[k] = stage_bytes;
+        stage_bytes += um_desc_bytes(Q.req[order[k]].r1 - Q.req[order[k]].r0);
+    }
+    at[n1] = stage_bytes;
+    if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes, false, "ii2_atleast_ranges: staging allocation failed")) return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    for (size_t k = 0; k < n1; k++) um_desc_fill(Q.rs, Q.req[order[k]].r0, Q.req[order[k]].r1, h + at[k]);
+    if (excl) um_desc_fill(Q.rx, 0, Q.rx.size(), h + at[n1]);
+    const uint64_t W = thr_window_docs(B, ctx->opt_union_many_window_log2);
+    const uint64_t n_sum_max = (W + 65535) / 65536;
+    UnionManyParams p;
+    std::memset(&p, 0, sizeof p);
+    const size_t scan_tmp = scan_temp_bytes(n_sum_max + 1);
+    if (int rc = ii2_ws_reserve(ctx, stage_bytes + 2 * align_up((n_sum_max + 1) * sizeof(uint64_t)) + scan_tmp + 2 * 256 + 4096)) return rc;
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, stage_bytes);
+    p.cnt = ws_take<uint32_t>(ctx, n_sum_max + 1);
+    p.off = ws_take<uint64_t>(ctx, n_sum_max + 1);
+    void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
+    p.run = ws_take<uint64_t>(ctx, 2);
+    p.bounds = ws_take<uint32_t>(ctx, 2);
+    // the descriptors of group k of `order` (n1: the excluded ranges) in a copy of p
+    auto group_params = [&](size_t k, size_t nr, uint64_t n_blocks) {
+        UnionManyParams g = p;
+        g.ranges = (const UmRange *)(d_stage + at[k]);
+        g.pre = (const uint32_t *)(d_stage + at[k] + align_up(nr * sizeof(UmRange)));
+        g.n_ranges = (uint32_t)nr;
+        g.n_blocks = (uint32_t)n_blocks;
+        g.per_wave = um_per_wave(ctx, n_blocks);
+        return g;
+    };
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, stage_bytes, hipMemcpyHostToDevice, st));
+    // the doc span of the required groups: from the mirrored spans, else one reduction over the group's blocks
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (const GroupIn &G : Q.req)
+        if (G.span_known) { lo = std::min(lo, G.lo); hi = std::max(hi, G.hi); }
+    if (!Q.req_known) {
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
+        for (size_t k = 0; k < n1; k++) {
+            const GroupIn &G = Q.req[order[k]];
+            if (!G.span_known) HIP_TRY(ctx, launch_union_many_bounds(group_params(k, G.r1 - G.r0, G.n_blocks), st));
+        }
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        lo = std::min(lo, hb[0]);
+        hi = std::max(hi, hb[1]);
+    }
+    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_atleast_ranges: inconsistent list bounds");
+    const uint32_t base = lo & ~31u;
+    const uint64_t span = (uint64_t)hi - base + 1;
+    const uint64_t n_win = (span + W - 1) / W;
+    // the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero
+    if (int rc = um_scratch_reserve(ctx, "ii2_atleast_ranges", span, W)) return rc;
+    if (int rc = thr_scratch_reserve(ctx, B, span, W)) return rc;
+    uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+    p.d_count = d_cnt ? d_cnt : ctx->d_mail;
+    set_tomb(p, tomb);
+    p.out = d_out;
+    p.out_cap = cap;
+    p.check_window = n_win > 1 ? 1u : 0u;
+    stats.form = II2_ATLEAST_COUNT;
+    stats.n_planes = B;
+    stats.n_windows = (uint32_t)n_win;
+    stats.n_late = (uint32_t)(n1 - first_late);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    // several windows whose result may not fit: count first (nothing written), then write
+    const bool count_first = n_win > 1 && cap < stats.bound;
+    for (int pass = count_first ? 0 : 1; pass < 2; pass++) {
+        p.write = (uint32_t)pass;
+        for (uint64_t w = 0; w < n_win; w++) {
+            const uint64_t wlo = base + w * W, docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1), whi = wlo + docs - 1;
+            p.window = (uint32_t)w;
+            um_set_window(ctx, p, wlo, docs);
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 1 + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+            ThrParams t;
+            std::memset(&t, 0, sizeof t);
+            t.bitmap = p.bitmap;
+            t.summary = p.summary;
+            t.plane_words = p.n_sum * 2048u;
+            t.planes = ctx->d_thr;
+            t.acc = ctx->d_thr + (size_t)B * t.plane_words;
+            t.n_sum = p.n_sum;
+            t.n_planes = B;
+            t.min_match = min_match;
+            for (size_t k = 0; k < n1; k++) {
+                const GroupIn &G = Q.req[order[k]];
+                if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;      // none of the group's docs lies in this window
+                HIP_TRY(ctx, launch_union_many_mark(group_params(k, G.r1 - G.r0, G.n_blocks), st));
+                t.late = k >= first_late ? 1u : 0u;
+                HIP_TRY(ctx, launch_thr_add(t, grid, st, e0, e1));
+                e0 = e1 = nullptr;
+            }
+            if (excl) {
+                UnionManyParams x = group_params(n1, Q.rx.size(), Q.ex.n_blocks);
+                x.check_window = 1u;                                        // blocks outside the required groups' span are not decoded
+                HIP_TRY(ctx, launch_union_many_mark(x, st));
+            }
+            HIP_TRY(ctx, launch_thr_select(t, grid, st));
+            HIP_TRY(ctx, launch_union_many_count(p, grid, st));
+            HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, p.cnt, p.off, p.n_sum + 1, st));
+            HIP_TRY(ctx, launch_union_many_compact(p, grid, st));
+        }
+        if (int rc = read_count(ctx, p.d_count, count)) return rc;
+        ctx->um_dirty = false;
+        if (*count > cap) return fail(ctx, II2_ECAPACITY, "ii2_atleast_ranges: result does not fit the output buffer (nothing written)");
+        if (pass == 0) ctx->um_dirty = true;
+    }
+    return II2_OK;
+}
+
+static int atleast_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, uint32_t min_match,
+                                   const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                                   uint32_t *d_out, uint64_t cap, uint64_t *count, ii2_atleast_stats *stats) {
+    if (!min_match) return fail(ctx, II2_EINVAL, "ii2_atleast_ranges: min_match is 0");
+    // 1. the plan: n' required groups with postings, in ascending order of postings; the bound
+    GroupQuery Q;
+    std::vector<uint64_t> kept;
+    if (int rc = plan_atleast(ctx, "ii2_atleast_ranges", n_groups, group_first, group_not, segs, list_first, list_end, Q, kept)) return rc;
+    const size_t n1 = Q.req.size();
+    ii2_atleast_stats st{n1, 0, II2_ATLEAST_NONE, 0, 0, 0};
+    if (Q.empty || min_match > n1) {
+        *count = 0;
+        if (stats) *stats = st;
+        return II2_OK;
+    }
+    std::vector<size_t> order(n1);
+    for (size_t g = 0; g < n1; g++) order[g] = g;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return Q.req[a].n_post < Q.req[b].n_post; });
+    for (size_t k = 0; k + min_match <= n1; k++) st.bound += Q.req[order[k]].n_post;
+    const bool is_and = min_match == n1;
+    if (!is_and && min_match > 255) return fail(ctx, II2_ERANGE, "ii2_atleast_ranges: min_match above 255 and below the number of required groups with postings");
+    if (!d_out) return fail(ctx, II2_EINVAL, "ii2_atleast_ranges: output buffer is NULL");
+    // 2. the excluded lists that count
+    if (int rc = size_exclusions(ctx, Q)) return rc;
+    auto done = [&](int rc) {
+        if (stats && (rc == II2_OK || rc == II2_ECAPACITY)) *stats = st;
+        return rc;
+    };
+    // 3. the hand-offs: every group - ii2_andnot_ranges on the groups that are left; any group, nothing excluded - the OR
+    if (is_and && (ctx->opt_atleast_handoff || min_match > 255)) {
+        st.form = II2_ATLEAST_AND;
+        if (kept.size() == n_groups) return done(andnot_ranges_unlocked(ctx, n_groups, group_first, group_not, segs, list_first, list_end, tomb, d_out, cap, count));
+        std::vector<uint64_t> gf{0}, lf, le;
+        std::vector<uint8_t> gn;
+        std::vector<const ii2_seg *> gsegs;
+        for (uint64_t g : kept) {
+            gsegs.insert(gsegs.end(), segs + group_first[g], segs + group_first[g + 1]);
+            lf.insert(lf.end(), list_first + group_first[g], list_first + group_first[g + 1]);
+            le.insert(le.end(), list_end + group_first[g], list_end + group_first[g + 1]);
+            gf.push_back(gsegs.size());
+            gn.push_back(group_not ? group_not[g] : 0);
+        }
+        return done(andnot_ranges_unlocked(ctx, kept.size(), gf.data(), group_not ? gn.data() : nullptr, gsegs.data(), lf.data(), le.data(), tomb, d_out, cap, count));
+    }
+    if (min_match == 1 && !Q.ex.n_nonempty && ctx->opt_atleast_handoff) {
+        st.form = II2_ATLEAST_OR;
+        std::vector<RangeIn> rr;
+        uint64_t n_blocks = 0, n_nonempty = 0;
+        for (const GroupIn &G : Q.req) {
+            rr.insert(rr.end(), Q.rs.begin() + G.r0, Q.rs.begin() + G.r1);
+            n_blocks += G.n_blocks;
+            n_nonempty += G.n_nonempty;
+        }
+        return done(union_collected(ctx, rr, n_blocks, n_nonempty, tomb, d_out, cap, count));
+    }
+    // 4. short lists: one launch
+    if (ctx->opt_atleast_small) {
+        uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
+        const SetOut o{tomb, d_out, cap, d_cnt ? d_cnt : ctx->d_mail};
+        bool taken = false;
+        if (int rc = groups_one_launch(ctx, Q, o, ctx->opt_atleast_small, min_match, &taken)) return rc;
+        if (taken) {
+            if (int rc = read_count(ctx, o.d_count, count)) return rc;
+            st.form = II2_ATLEAST_SMALL;
+            if (*count > cap) return done(fail(ctx, II2_ECAPACITY, "ii2_atleast_ranges: result does not fit the output buffer (nothing written)"));
+            return done(II2_OK);
+        }
+    }
+    // 5. the counting form
+    return done(atleast_count(ctx, Q, order, min_match, tomb, d_out, cap, count, st));
+}
+
+// the >= min_match mask after adding adds[0, n_adds) into B zero planes (ii2_atleast_word)
+template <uint32_t B> static uint32_t thr_word_mask(uint32_t min_match, const uint32_t *adds, uint32_t n_adds) {
+    uint32_t pl[B] = {};
+    for (uint32_t i = 0; i < n_adds; i++) thr_add_word<B>(pl, adds[i]);
+    return thr_ge_word<B>(pl, min_match);
+}
+
+extern "C" {
+
+int ii2_atleast_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, uint32_t min_match,
+                       const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out,
+                       uint64_t cap, uint64_t *count, ii2_atleast_stats *stats) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return atleast_ranges_unlocked(ctx, n_groups, group_first, group_not, min_match, segs, list_first, list_end, tomb, d_out, cap, count, stats);
+}
+
+// host only: what the counting form would use for a query of n_counted required groups with postings
+int ii2_atleast_plan(uint64_t n_counted, uint32_t min_match, uint32_t window_log2, uint32_t *n_planes, uint64_t *window_docs, uint64_t *first_late) {
+    if (!n_planes || !window_docs || !first_late || !min_match) return II2_EINVAL;
+    *n_planes = 0;
+    *window_docs = 0;
+    *first_late = 0;
+    if (min_match > n_counted) return II2_OK;
+    if (min_match > 255) return min_match < n_counted ? II2_ERANGE : II2_OK;
+    *n_planes = thr_bit_width(min_match);
+    *window_docs = thr_window_docs(*n_planes, window_log2);
+    *first_late = n_counted - min_match + 1;
+    return II2_OK;
+}
+
+// host only: the kernels' word arithmetic
+int ii2_atleast_word(uint32_t n_planes, uint32_t min_match, const uint32_t *adds, uint32_t n_adds, uint32_t *mask) {
+    if (!mask || (n_adds && !adds) || n_planes < 1 || n_planes > THR_MAX_PLANES || !min_match || (min_match >> n_planes)) return II2_EINVAL;
+    switch (n_planes) {
+        case 1: *mask = thr_word_mask<1>(min_match, adds, n_adds); break;
+        case 2: *mask = thr_word_mask<2>(min_match, adds, n_adds); break;
+        case 3: *mask = thr_word_mask<3>(min_match, adds, n_adds); break;
+        case 4: *mask = thr_word_mask<4>(min_match, adds, n_adds); break;
+        case 5: *mask = thr_word_mask<5>(min_match, adds, n_adds); break;
+        case 6: *mask = thr_word_mask<6>(min_match, adds, n_adds); break;
+        case 7: *mask = thr_word_mask<7>(min_match, adds, n_adds); break;
+        default: *mask = thr_word_mask<8>(min_match, adds, n_adds); break;
+    }
+    return II2_OK;
+}
+
+}  // extern "C"
 
 // ---- many queries in one call ---------------------------------------------------------------------
 // one query of a batch as the host plans it

@@ -13,6 +13,8 @@
 //     when every required tag occurs and the run's last tag is not the excluded one.  The same id in two lists of one group -
 //     or the same list twice - repeats a tag and is counted once.  Then the tombstone test, the block scan, the write-out -
 //     only when the whole result fits out_cap - and the count.
+//   - the threshold query (ii2_atleast_ranges) is the same kernel with "at least min_match required tags" as the rule of the run
+//     walk: a second instantiation, launched by that entry point only.
 // The kernel waits for no other workgroup.
 #include <hip/hip_runtime.h>
 
@@ -27,7 +29,7 @@ constexpr uint32_t GS_PER_WAVE = SMALL_SET_BLOCKS / GS_WAVES;          // blocks
 constexpr uint32_t GS_PER_THREAD = SMALL_SET_POSTINGS / GS_THREADS;    // ids a thread ranks
 static_assert(GS_PER_WAVE * GS_WAVES == SMALL_SET_BLOCKS && GS_PER_THREAD == 8u, "a wave takes 8 blocks, a thread 8 ids");
 
-__global__ __launch_bounds__(GS_THREADS) void k_setop_groups(GroupSetParams p) {
+template <bool AT_LEAST> __global__ __launch_bounds__(GS_THREADS) void k_setop_groups(GroupSetParams p) {
     __shared__ uint32_t raw[SMALL_SET_POSTINGS];                    // list j decoded at raw[lpre[j] ...]; then every id at its rank
     __shared__ uint8_t tags[SMALL_SET_POSTINGS];                    // the group tag of the id at that rank
     __shared__ uint32_t lcnt[MAX_LISTS], lpre[MAX_LISTS + 1];       // postings of every list (the host knows them), their prefix
@@ -82,7 +84,11 @@ __global__ __launch_bounds__(GS_THREADS) void k_setop_groups(GroupSetParams p) {
             kept[q] = v;
             bool keep = i == 0u || prev != v;                             // first of its run
             prev = v;
-            if (keep) keep = ss_group_run_kept(raw, tags, i, n_total, n_req);
+            if constexpr (AT_LEAST) {
+                if (keep) keep = ss_group_run_reaches(raw, tags, i, n_total, n_req, p.min_match);
+            } else {
+                if (keep) keep = ss_group_run_kept(raw, tags, i, n_total, n_req);
+            }
             if (keep && tomb_has(p.tomb, p.tomb_nwords, v)) keep = false;
             if (keep) { keepmask |= 1u << q; cnt++; }
         }
@@ -99,7 +105,14 @@ __global__ __launch_bounds__(GS_THREADS) void k_setop_groups(GroupSetParams p) {
 
 hipError_t launch_setop_groups(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
     if (ev0) (void)hipEventRecord(ev0, s);
-    hipLaunchKernelGGL(k_setop_groups, dim3(1), dim3(GS_THREADS), 0, s, p);
+    hipLaunchKernelGGL(k_setop_groups<false>, dim3(1), dim3(GS_THREADS), 0, s, p);
+    if (ev1) (void)hipEventRecord(ev1, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_setop_groups_atleast(const GroupSetParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (ev0) (void)hipEventRecord(ev0, s);
+    hipLaunchKernelGGL(k_setop_groups<true>, dim3(1), dim3(GS_THREADS), 0, s, p);
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();
 }

@@ -137,8 +137,10 @@ __device__ __forceinline__ uint32_t ss_block_scan(uint32_t cnt, uint32_t *wsum, 
 // The survive rule of the group kernels.  raw[0, n_total): every id at its rank; tags[]: the group tag of the id at that rank -
 // the required groups are tags 0 .. n_req - 1, the excluded lists tag n_req; lists are in tag order, so the tags inside a run of
 // equal ids ascend.  i is the head of a run (at most MAX_LISTS long: a list holds an id once): the id survives when every
-// required tag occurs in the run and its last tag is not the excluded one.  A repeated tag is counted once.
-__device__ __forceinline__ bool ss_group_run_kept(const uint32_t *raw, const uint8_t *tags, uint32_t i, uint32_t n_total, uint32_t n_req) {
+// required tag occurs in the run (AT_LEAST: at least min_match of them) and its last tag is not the excluded one.  A repeated tag
+// is counted once.
+template <bool AT_LEAST>
+__device__ __forceinline__ bool ss_group_run(const uint32_t *raw, const uint8_t *tags, uint32_t i, uint32_t n_total, uint32_t n_req, uint32_t min_match) {
     const uint32_t v = raw[i];
     uint32_t seen = 0, last = 0xFFFFFFFFu;
     for (uint32_t k = i; k < n_total && raw[k] == v; k++) {
@@ -146,7 +148,16 @@ __device__ __forceinline__ bool ss_group_run_kept(const uint32_t *raw, const uin
         seen += (t != last && t < n_req) ? 1u : 0u;
         last = t;
     }
-    return seen == n_req && last < n_req;
+    return (AT_LEAST ? seen >= min_match : seen == n_req) && last < n_req;
+}
+// in every required group (ii2_andnot_ranges, ii2_query_batch_groups) ...
+__device__ __forceinline__ bool ss_group_run_kept(const uint32_t *raw, const uint8_t *tags, uint32_t i, uint32_t n_total, uint32_t n_req) {
+    return ss_group_run<false>(raw, tags, i, n_total, n_req, 0u);
+}
+// ... or in at least min_match of them (ii2_atleast_ranges)
+__device__ __forceinline__ bool ss_group_run_reaches(const uint32_t *raw, const uint8_t *tags, uint32_t i, uint32_t n_total, uint32_t n_req,
+                                                     uint32_t min_match) {
+    return ss_group_run<true>(raw, tags, i, n_total, n_req, min_match);
 }
 
 }  // namespace ii2

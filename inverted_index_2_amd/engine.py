@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, BuildStats, CountStats, MergeStats, SegInfo
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -480,6 +480,26 @@ class Context:
                                             segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None,
                                             _ptr(out), out.count, C.byref(cnt)))
         return out, cnt.value
+
+    def atleast_ranges(self, groups, min_match: int, exclude=(), tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None,
+                       stats: bool = False):
+        """Threshold query (ii2_atleast_ranges): groups and exclude are lists of groups as andnot_ranges takes them; the ids found
+        in at least one list of at least `min_match` groups of `groups` and in no list of any group of `exclude`.  A group without
+        postings matches no doc.  Returns (DeviceArray ids, count), with stats=True (DeviceArray ids, count, AtleastStats); the
+        default `out` holds 256 ids per block of the n' - min_match + 1 groups with the fewest blocks, n' the groups that have blocks."""
+        groups = [list(g) for g in groups]
+        group_first, group_not, gsegs, first, end = pack_andnot(groups, exclude)
+        n = len(gsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in gsegs])
+        if out is None:
+            blocks = sorted(b for b in (sum(s.range_blocks(int(a), int(b), self) for s, a, b in g) for g in groups) if b)
+            out = self.empty(max(sum(blocks[:max(len(blocks) - int(min_match) + 1, 0)]) * 256, 1))
+        cnt = C.c_uint64()
+        st = AtleastStats()
+        self._ck(self.lib.ii2_atleast_ranges(self.h, len(group_not), group_first.ctypes.data_as(_lib.u64p), group_not.ctypes.data_as(_lib.u8p),
+                                             int(min_match), segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p),
+                                             tomb.h if tomb else None, _ptr(out), out.count, C.byref(cnt), C.byref(st)))
+        return (out, cnt.value, st) if stats else (out, cnt.value)
 
     def query_batch(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
         """Many AND / OR queries in one call (ii2_query_batch): queries = [("and" | "or", [(Segment, first, end), ...]), ...] -

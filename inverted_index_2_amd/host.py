@@ -63,6 +63,7 @@ def _lib_typed():
         lib.ii2h_prefix_search.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         lib.ii2h_term_counts.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
@@ -194,7 +195,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectMany, TermCounts)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectMany, TermCounts)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -226,6 +227,18 @@ class InvertedIndex(_Target):
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_except(self.h, blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data, x_off.ctypes.data,
                                                 len(exclude), C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint32)
+        self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
+        return out[: n.value].tolist()
+
+    def intersect_at_least(self, terms: List[bytes], min_match: int, exclude: List[bytes] = ()) -> List[int]:
+        """ids under at least `min_match` of `terms` and under no term of `exclude` (IntersectAtLeast: one ii2_atleast_ranges call);
+        a term found in no segment matches no doc."""
+        blob, off = _pack(list(terms))
+        x_blob, x_off = _pack(list(exclude))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_at_least(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(min_match), x_blob.ctypes.data,
+                                                  x_off.ctypes.data, len(exclude), C.byref(n)))
         out = np.zeros(max(n.value, 1), np.uint32)
         self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
         return out[: n.value].tolist()

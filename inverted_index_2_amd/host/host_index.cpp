@@ -17,6 +17,7 @@
 //   shardKey                                         shard.go:362-378
 //   Intersect(terms)                                 additive
 //   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
+//   IntersectAtLeast(terms, min_match, except)       additive: the ids under at least min_match of the terms, minus the excluded terms
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //
@@ -923,6 +924,25 @@ class InvertedIndex {
         if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
         return ids;
     }
+    // additive: ids present under AT LEAST min_match of `terms` and under none of `except` (minimum-should-match, "any two of
+    // these tags").  One group per term as IntersectExcept builds them - but a required term found in no segment is an empty group,
+    // not an empty result - and ONE ii2_atleast_ranges call and one download.  Like Intersect and Read, no tombstone filter.
+    std::vector<uint32_t> IntersectAtLeast(const std::vector<Term> &terms, uint32_t min_match, const std::vector<Term> &except) const {
+        if (!min_match) throw std::runtime_error("intersect at least: min_match is 0");
+        Filter f;
+        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
+        filter_build(terms, except, f, &posts);
+        if (posts.size() < min_match) return {};
+        // the output's size: a result id lies in at least one of any n' - min_match + 1 terms, so those with the smallest bounds
+        std::sort(posts.begin(), posts.end());
+        f.bound = 0;
+        for (size_t k = 0; k + min_match <= posts.size(); k++) f.bound += posts[k];
+        DevMem d_out(ctx_);
+        const uint64_t n = filter_run(f, d_out, "intersect at least", min_match);
+        std::vector<uint32_t> ids(n);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect at least");
+        return ids;
+    }
    private:
     // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
     // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
@@ -934,8 +954,9 @@ class InvertedIndex {
         std::vector<uint64_t> first, end;
         uint64_t bound = ~0ull;
     };
-    // false: a required term is in no segment (or there is none) - nothing is under every term
-    bool filter_build(const std::vector<Term> &terms, const std::vector<Term> &except, Filter &f) const {
+    // false: a required term is in no segment (or there is none) - nothing is under every term.  posts != NULL (IntersectAtLeast):
+    // such a term is a group without ranges instead, and *posts receives the bounds of the others
+    bool filter_build(const std::vector<Term> &terms, const std::vector<Term> &except, Filter &f, std::vector<uint64_t> *posts = nullptr) const {
         if (terms.empty()) return false;
         // one one-list range per segment that holds the term; returns the term's postings bound (see Intersect), 0: in no segment
         auto gather = [&](const Term &t) {
@@ -959,7 +980,8 @@ class InvertedIndex {
         // the output's size: the smallest REQUIRED term's bound, as in Intersect (an exclusion only removes ids)
         for (auto &t : terms) {
             const uint64_t post = gather(t);
-            if (!post) return false;                             // a required term in no segment: nothing is under every term
+            if (!post && !posts) return false;                   // a required term in no segment: nothing is under every term
+            if (post && posts) posts->push_back(post);
             f.group_first.push_back(f.segs.size());
             f.group_not.push_back(0);
             f.bound = std::min(f.bound, post);
@@ -971,15 +993,18 @@ class InvertedIndex {
         }
         return true;
     }
-    // ONE ii2_andnot_ranges call into d_out, which stays on the device; returns the result's size.  Past FIRST_CAP ids the first
-    // call tries FIRST_CAP, and a result that does not fit is written by a second call with the size the first one reported
-    uint64_t filter_run(const Filter &f, DevMem &d_out, const char *what) const {
+    // ONE ii2_andnot_ranges call - min_match > 0: ONE ii2_atleast_ranges call - into d_out, which stays on the device; returns the
+    // result's size.  Past FIRST_CAP ids the first call tries FIRST_CAP, and a result that does not fit is written by a second call
+    // with the size the first one reported
+    uint64_t filter_run(const Filter &f, DevMem &d_out, const char *what, uint32_t min_match = 0) const {
         constexpr uint64_t FIRST_CAP = 1u << 22;
         uint64_t cap = std::min(f.bound, FIRST_CAP), n = 0;
         for (int attempt = 0;; attempt++) {
             ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), what);
-            const int rc = ii2_andnot_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), f.segs.data(), f.first.data(),
-                                             f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n);
+            const int rc = min_match ? ii2_atleast_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), min_match, f.segs.data(),
+                                                          f.first.data(), f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n, nullptr)
+                                     : ii2_andnot_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), f.segs.data(), f.first.data(),
+                                                         f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n);
             if (rc != II2_ECAPACITY || attempt) {
                 ck(ctx_, rc, what);
                 break;
@@ -1404,6 +1429,10 @@ int ii2h_prefix_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off
 }
 int ii2h_intersect(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->Intersect(unpack_terms(bytes, off, n)); *n_ids = t->ids.size(); })
+}
+int ii2h_intersect_at_least(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint32_t min_match, const uint8_t *x_bytes,
+                            const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
+    H_TRY(t, { t->ids = t->index->IntersectAtLeast(unpack_terms(bytes, off, n), min_match, unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
 }
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
