@@ -597,6 +597,80 @@ func (c *Ctx) AtLeastRangesHost(groupFirst []uint64, groupNot []uint8, minMatch 
 	}
 }
 
+// TopKStats mirrors ii2_topk_stats.
+type TopKStats struct {
+	Counted, Eligible, NCut                       uint64
+	MaxScore, CutScore, Planes, Windows, NMarks uint32
+}
+
+// TopKMax is the largest k of TopKRanges (II2_TOPK_MAX).
+const TopKMax = uint64(C.II2_TOPK_MAX)
+
+// TopKRanges answers one ranked query over resident segments (ii2_topk_ranges): the k docs that lie in the most required groups - at
+// least minMatch of them, in NO list of ANY excluded group - ordered by score descending, then id ascending.  Groups, ranges and
+// groupNot are those of AtLeastRanges; a required group without postings matches no doc.  The ids go to the device buffer ids and
+// their scores to scores (k entries each; scores may be nil); the number written, min(k, eligible docs), is returned together with
+// the score histogram (eligible docs per score).  k == 0 returns the histogram and stats only.  There is no ErrCapacity.
+func (c *Ctx) TopKRanges(groupFirst []uint64, groupNot []uint8, minMatch uint32, k uint64, segs []*Segment, listFirst, listEnd []uint64, ids, scores unsafe.Pointer) (uint64, [256]uint64, TopKStats, error) {
+	var hist [256]uint64
+	nGroups := len(groupFirst) - 1
+	if nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return 0, hist, TopKStats{}, fmt.Errorf("topk ranges: array lengths disagree")
+	}
+	if groupFirst[nGroups] != uint64(len(segs)) { // the C side reads the range arrays up to groupFirst's last element
+		return 0, hist, TopKStats{}, fmt.Errorf("topk ranges: groupFirst does not end at the number of ranges")
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if groupNot != nil && nGroups > 0 {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	var n C.uint64_t
+	var st C.ii2_topk_stats
+	rc := C.ii2_topk_ranges(c.h, C.uint64_t(nGroups), u64ptr(groupFirst), flags, C.uint32_t(minMatch), C.uint64_t(k), (**C.ii2_seg)(unsafe.Pointer(&hs[0])),
+		u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(ids), (*C.uint32_t)(scores), &n, (*C.uint64_t)(unsafe.Pointer(&hist[0])), &st)
+	if rc != 0 {
+		return 0, hist, TopKStats{}, c.err("topk ranges", rc)
+	}
+	stats := TopKStats{uint64(st.n_counted), uint64(st.n_eligible), uint64(st.n_cut), uint32(st.max_score), uint32(st.cut_score), uint32(st.n_planes),
+		uint32(st.n_windows), uint32(st.n_marks)}
+	return uint64(n), hist, stats, nil
+}
+
+// Scored is one entry of a ranked result: a doc id and the number of groups it lies in.
+type Scored struct {
+	ID, Score uint32
+}
+
+// TopKRangesHost is TopKRanges with the result in host memory: one device buffer of 2k words (the ids, then the scores), one call,
+// one download.
+func (c *Ctx) TopKRangesHost(groupFirst []uint64, groupNot []uint8, minMatch uint32, k uint64, segs []*Segment, listFirst, listEnd []uint64) ([]Scored, error) {
+	if k == 0 {
+		return nil, nil
+	}
+	var d unsafe.Pointer
+	if rc := C.ii2_dev_alloc(c.h, C.size_t(2*k*4), &d); rc != 0 {
+		return nil, c.err("topk ranges", rc)
+	}
+	defer C.ii2_dev_free(c.h, d)
+	n, _, _, err := c.TopKRanges(groupFirst, groupNot, minMatch, k, segs, listFirst, listEnd, d, unsafe.Add(d, int(k*4)))
+	if err != nil || n == 0 {
+		return nil, err
+	}
+	raw := make([]uint32, k+n)
+	if rc := C.ii2_copy_d2h(c.h, unsafe.Pointer(&raw[0]), d, C.size_t((k+n)*4)); rc != 0 {
+		return nil, c.err("topk ranges", rc)
+	}
+	out := make([]Scored, n)
+	for i := range out {
+		out[i] = Scored{raw[i], raw[k+uint64(i)]}
+	}
+	return out, nil
+}
+
 // CountStats mirrors ii2_count_stats.
 type CountStats struct {
 	Lists, Blocks, Decoded, Hits uint64

@@ -379,6 +379,60 @@ func IntersectAtLeast(c *Ctx, ix ResidentIndex, terms [][]byte, minMatch uint32,
 	return ids, nil
 }
 
+// IntersectTop (additive): the k ids under the most of terms - at least minMatch of them, under none of except - with the number of
+// terms each lies under, score descending, then id ascending: a ranked page of a search.  One group per term as IntersectAtLeast
+// builds them (a required term found in no segment is a group without ranges), ONE Ctx.TopKRanges call with one download of the k
+// (id, score) pairs - what the C++ host mirror's InvertedIndex::IntersectTop does (host/host_index.cpp).  Like Read, no tombstone
+// filter.
+func IntersectTop(c *Ctx, ix ResidentIndex, terms [][]byte, k uint64, minMatch uint32, except [][]byte) ([]Scored, error) {
+	if minMatch == 0 {
+		return nil, fmt.Errorf("intersect top: minMatch is 0")
+	}
+	if k > TopKMax {
+		return nil, fmt.Errorf("intersect top: k above TopKMax")
+	}
+	defer ix.Release()
+	groupFirst := []uint64{0}
+	var groupNot []uint8
+	var segs []*Segment
+	var first, end []uint64
+	held := uint32(0) // the terms that some segment holds
+	for _, t := range terms {
+		s, l, _ := ix.TermLists(t)
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 0)
+		if len(s) > 0 {
+			held++
+		}
+	}
+	if held < minMatch || k == 0 {
+		return nil, nil
+	}
+	for _, t := range except {
+		s, l, _ := ix.TermLists(t)
+		if len(s) == 0 {
+			continue // (in no segment: it removes nothing)
+		}
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 1)
+	}
+	top, err := c.TopKRangesHost(groupFirst, groupNot, minMatch, k, segs, first, end)
+	if err != nil {
+		return nil, fmt.Errorf("intersect top: %w", err)
+	}
+	return top, nil
+}
+
 // IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
 // "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
 // flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does

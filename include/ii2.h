@@ -27,6 +27,7 @@
  *     The one-launch form of ii2_andnot_ranges takes queries whose non-empty lists - required
  *     and excluded - are at most II2_MAX_LISTS and hold at most 8192 postings in at most 128 blocks, by default only while
  *     postings x lists <= 32768 (what the form costs; beyond it, or beyond the kernel, a query takes the general form: no error).
+ *     ii2_topk_ranges takes at most 255 required groups that have postings and k <= II2_TOPK_MAX = 2^20.
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
  *     internal mutex, so a ctx may be shared by goroutines / threads (InvertedIndex.Merge
  *     fans Shard.Merge over `concurrency` goroutines, inverted_index.go:83-103); use one
@@ -482,6 +483,70 @@ int ii2_atleast_plan(uint64_t n_counted, uint32_t min_match, uint32_t window_log
  * n_planes zero planes, by the functions the kernels run (saturating: a counter never wraps).  n_planes outside 1 .. 8,
  * min_match == 0 or min_match >= 2^n_planes: II2_EINVAL. */
 int ii2_atleast_word(uint32_t n_planes, uint32_t min_match, const uint32_t *adds, uint32_t n_adds, uint32_t *mask);
+
+/* RANKED query - "the k docs that match the most of these groups, and how many each matched": what a search front end asks of
+ * a posting-list engine most often.  Groups, ranges and group_not are exactly those of ii2_atleast_ranges / ii2_andnot_ranges
+ * (segments and views alike; a list may appear in any number of ranges and groups; ranges may overlap; group_not == NULL: every
+ * group is required).  score(d) = the number of REQUIRED groups that hold d in at least one list (an id in several lists of one
+ * group counts once).  d is eligible when score(d) >= min_match, d lies in no list of any excluded group, and d is not in tomb
+ * (when tomb != NULL).  The result is the k eligible docs that come first in the order SCORE DESCENDING, THEN DOC ID ASCENDING -
+ * ties at the cut go to the smallest ids - written in that order to d_ids[0 .. *count), d_scores[i] = score(d_ids[i]);
+ * *count = min(k, eligible docs).  It replaces a loop of ii2_atleast_ranges calls with min_match = n', n' - 1, ... until k ids
+ * have come back (n' marks and adds per round, and no score per doc), or n ii2_union_ranges calls, n downloads and a count on
+ * the host.
+ *   - a required group without postings matches no doc, as in ii2_atleast_ranges.  With n' the required groups that have
+ *     postings: min_match > n', or n_groups == 0: *count = 0, hist all zero, nothing is launched, the device pointers may be
+ *     NULL.  An excluded group without postings is ignored, and so is any excluded list whose doc span misses the required
+ *     groups' span.
+ *   - II2_EINVAL: min_match == 0; n_groups > 0 and no required group; a flag other than 0 / 1; a bad range (rejected as
+ *     ii2_andnot_ranges rejects it, under this entry point's name); d_ids == NULL with k > 0 and something to return.
+ *     II2_ERANGE: n' > 255 (the scores are exact 8-bit counters and must not saturate); k > II2_TOPK_MAX (a ranked page, not a
+ *     dump: whoever wants every doc calls ii2_atleast_ranges); 2^32 - 2 blocks or ranges.  Every check happens before anything is
+ *     launched or written.
+ *   - k == 0 is allowed: only hist and stats are produced (the score distribution), nothing is emitted, d_ids may be NULL.
+ *   - *count <= k always: there is no II2_ECAPACITY.  d_ids and d_scores hold k entries; d_scores may be NULL; the entries
+ *     [*count, k) are not written.  All-or-nothing: on any error d_ids, d_scores, hist, stats and *count are untouched.
+ *   - hist (host, 256 entries, may be NULL): hist[s] = the eligible docs whose score is exactly s - 0 for s < min_match and for
+ *     s > n'.
+ * How it runs (the call counts no kernel path in ii2_ctx_paths): per window of the doc span - min(1 << union.many_window_log2,
+ * 2^30 / B rounded down to a power of two) docs, B = bit_width(n') - every required group is marked into the per-context doc
+ * bitmap and added into B counter bitmaps as ii2_atleast_ranges' counting form does it, the excluded lists are marked, and
+ * pass 1 tallies the eligible docs by score.  The host reads the histogram and cuts it for k (ii2_topk_cut).  Pass 2 counts the
+ * docs of every score from the cut up per 65536-doc stretch, scans that class-major table once and places every doc directly:
+ * rank order without a sort, the cut class filled by its smallest ids up to its quota.  With one window the counters stay
+ * between the passes and every group is marked once; with several, pass 2 marks and adds again.  A one-window call waits twice
+ * (a third time for the bounds of spans the host does not mirror).  The call leaves the per-context scratch - doc bitmap,
+ * counter planes and their summaries - all zero, as every call that uses them does; its temporaries are workspace. */
+#define II2_TOPK_MAX (1u << 20)
+typedef struct {
+    uint64_t n_counted;   /* required groups with postings (n') */
+    uint64_t n_eligible;  /* eligible docs = sum of hist */
+    uint64_t n_cut;       /* docs of score cut_score returned: the smallest ids of that score */
+    uint32_t max_score;   /* highest score of an eligible doc (0: none) */
+    uint32_t cut_score;   /* lowest score returned (0: nothing returned) */
+    uint32_t n_planes;    /* counter bitmaps: bit_width(n'); 0 when nothing ran */
+    uint32_t n_windows;   /* doc windows */
+    uint32_t n_marks;     /* mark launches for required groups, over the whole call */
+    uint32_t pad;
+} ii2_topk_stats;         /* 48 bytes */
+int ii2_topk_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first,
+                    const uint8_t *group_not, uint32_t min_match, uint64_t k,
+                    const ii2_seg *const *segs, const uint64_t *list_first,
+                    const uint64_t *list_end, const ii2_tomb *tomb,
+                    uint32_t *d_ids, uint32_t *d_scores /* may be NULL */, uint64_t *count,
+                    uint64_t *hist /* host, 256 entries, may be NULL */,
+                    ii2_topk_stats *stats /* may be NULL */);
+/* The ranked query's arithmetic, host only (no GPU needed).  ii2_topk_cut: for a histogram of 256 entries (hist[s] = docs of
+ * score s) and k, *cut_score = the largest s with sum(hist[t], t >= s) >= k - the smallest s with hist[s] > 0 when fewer than k
+ * docs are there -, *n_above = sum(hist[t], t > cut_score), *n_cut = min(hist[cut_score], k - n_above), *max_score = the largest s
+ * with hist[s] > 0.  k == 0 or an all-zero hist: all four are 0.  A NULL argument: II2_EINVAL. */
+int ii2_topk_cut(const uint64_t *hist, uint64_t k, uint32_t *max_score, uint32_t *cut_score,
+                 uint64_t *n_above, uint64_t *n_cut);
+/* scores[i] = the counter of the doc at bit i of one bitmap word after the words adds[0 .. n_adds) have been added into n_planes
+ * zero planes, read back by the function the kernels use to extract a score; docs outside mask get 0.  (The adds saturate at
+ * 2^n_planes - 1, which the ranked query never reaches.)  n_planes outside 1 .. 8, a NULL scores, or a NULL adds with
+ * n_adds > 0: II2_EINVAL. */
+int ii2_topk_word(uint32_t n_planes, const uint32_t *adds, uint32_t n_adds, uint32_t mask, uint32_t *scores /* 32 */);
 
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that

@@ -40,6 +40,12 @@ class AtleastStats(C.Structure):
                 ("n_windows", C.c_uint32), ("n_late", C.c_uint32)]
 
 
+class TopkStats(C.Structure):
+    _fields_ = [("n_counted", C.c_uint64), ("n_eligible", C.c_uint64), ("n_cut", C.c_uint64), ("max_score", C.c_uint32),
+                ("cut_score", C.c_uint32), ("n_planes", C.c_uint32), ("n_windows", C.c_uint32), ("n_marks", C.c_uint32), ("pad", C.c_uint32)]
+
+
+II2_TOPK_MAX = 1 << 20
 II2_ATLEAST_NONE, II2_ATLEAST_SMALL, II2_ATLEAST_COUNT, II2_ATLEAST_AND, II2_ATLEAST_OR = range(5)
 
 vp = C.c_void_p
@@ -97,6 +103,9 @@ PROTOTYPES = {
     "ii2_atleast_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, C.c_uint32, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p, C.POINTER(AtleastStats)]),
     "ii2_atleast_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, u32p, u64p, u64p]),
     "ii2_atleast_word": (C.c_int, [C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]),
+    "ii2_topk_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, C.c_uint32, C.c_uint64, vpp, u64p, u64p, vp, vp, vp, u64p, u64p, C.POINTER(TopkStats)]),
+    "ii2_topk_cut": (C.c_int, [u64p, C.c_uint64, u32p, u32p, u64p, u64p]),
+    "ii2_topk_word": (C.c_int, [C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

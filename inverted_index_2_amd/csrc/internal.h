@@ -520,6 +520,39 @@ struct ThrParams {
 hipError_t launch_thr_add(const ThrParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_thr_select(const ThrParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
+// the k docs in the most groups (topk.hip): the counting form's planes read as scores.  G, its summary, the planes and S_acc are
+// ThrParams'; the classes of pass 2 are the scores cut_score .. cut_score + n_cls - 1
+struct TopParams {
+    uint32_t *bitmap;            // the window's doc bitmap G [n_sum * 2048]: the excluded docs
+    uint32_t *summary;           // [n_sum] its summary
+    uint32_t *planes;            // [n_planes][plane_words] the counters
+    uint32_t *acc;               // [n_sum] S_acc: the chunks that hold a counter
+    uint32_t plane_words;        // n_sum * 2048
+    uint32_t n_sum;
+    uint32_t n_planes;           // 1 .. THR_MAX_PLANES
+    uint32_t min_match;          // k_top_hist: the lowest eligible score
+    uint32_t clear;              // k_top_hist: 1 = it zeroes what it read (no pass 2 follows on these planes)
+    uint32_t win_lo;             // first doc of the window (a multiple of 32: word i <-> tombstone word win_lo / 32 + i)
+    uint32_t window;             // index of the window: run[window & 1] = docs per class before it
+    uint32_t tomb_nwords;
+    const uint32_t *tomb;        // may be null
+    uint64_t *hist;              // [256] eligible docs per score, summed over the windows
+    uint64_t *base;              // [256] k_top_base: eligible docs of a higher score
+    uint32_t cut_score;          // pass 2: the lowest score returned ...
+    uint32_t n_cls;              // ... and the number of classes from there up to the highest (0: k_top_emit only cleans up)
+    uint64_t n_cut;              // docs of score cut_score returned
+    uint64_t k;                  // entries of ids / scores
+    uint32_t *cnt;               // [n_cls * n_sum + 1] docs per (class, summary word), class-major
+    uint64_t *off;               // [n_cls * n_sum + 1] their exclusive prefix
+    uint64_t *run;               // [2][256]
+    uint32_t *ids;               // [k] the result, score descending, then id ascending
+    uint32_t *scores;            // [k], may be null
+};
+hipError_t launch_top_hist(const TopParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t launch_top_base(const TopParams &p, hipStream_t s);
+hipError_t launch_top_count(const TopParams &p, uint32_t grid, hipStream_t s);
+hipError_t launch_top_emit(const TopParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
 // AND of ORs over list ranges: the filters of the group path (intersect_ranges.hip)
 constexpr uint32_t IR_PROBE_RUN = 256;          // consecutive candidates per wave of the probe
 struct IrList {

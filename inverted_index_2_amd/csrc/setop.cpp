@@ -34,6 +34,7 @@
 
 #include "atleast_count.h"
 #include "internal.h"
+#include "topk_count.h"
 
 using namespace ii2;
 
@@ -1821,6 +1822,214 @@ static int atleast_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64
     return done(atleast_count(ctx, Q, order, min_match, tomb, d_out, cap, count, st));
 }
 
+// ---- the k docs in the most groups --------------------------------------------------------------------
+// The ranked form (topk.hip) of a planned query: atleast_count's marks and adds with B = bit_width(n') planes - an exact counter per
+// doc - and then, instead of the select, pass 1 (the score histogram; read back and cut for k on the host) and pass 2 (count
+// table, scan, emit in rank order).  One window: the planes stay between the passes and every group is marked once.  Several:
+// pass 1 cleans up behind each window and pass 2 marks and adds again.  Waits: the bounds of spans the host does not mirror, the
+// histogram, the end of pass 2.  Everything the caller sees is written after the last of them.
+static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t k, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores,
+                      uint64_t *count, uint64_t *hist, ii2_topk_stats &stats) {
+    hipStream_t st = ctx->stream;
+    const size_t n1 = Q.req.size();
+    const bool excl = Q.ex.n_nonempty > 0;
+    const uint32_t B = thr_bit_width(n1);
+    if (int rc = um_scratch_clean(ctx)) return rc;
+    // staging: one descriptor block (ranges + block prefix) per required group, one for all excluded ranges, then the histogram on
+    // its way down
+    std::vector<size_t> at(n1 + 1);
+    size_t stage_bytes = 0;
+    for (size_t g = 0; g < n1; g++) {
+        at[g] = stage_bytes;
+        stage_bytes += um_desc_bytes(Q.req[g].r1 - Q.req[g].r0);
+    }
+    at[n1] = stage_bytes;
+    if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes + TOPK_SCORES * sizeof(uint64_t), false, "ii2_topk_ranges: staging allocation failed")) return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    uint64_t *h_hist = (uint64_t *)(h + stage_bytes);
+    for (size_t g = 0; g < n1; g++) um_desc_fill(Q.rs, Q.req[g].r0, Q.req[g].r1, h + at[g]);
+    if (excl) um_desc_fill(Q.rx, 0, Q.rx.size(), h + at[n1]);
+    const uint64_t W = thr_window_docs(B, ctx->opt_union_many_window_log2);
+    // the doc span of the required groups: from the mirrored spans, else one reduction over the group's blocks (below)
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (const GroupIn &G : Q.req)
+        if (G.span_known) { lo = std::min(lo, G.lo); hi = std::max(hi, G.hi); }
+    // workspace, sized before the bounds are known: the count table holds a class per score min_match .. n' and a column per
+    // summary word of the largest window
+    uint64_t n_sum_max = (W + 65535) / 65536;
+    if (Q.req_known && lo <= hi) n_sum_max = std::min<uint64_t>(n_sum_max, (std::min<uint64_t>((uint64_t)hi - (lo & ~31u) + 1, W) + 65535) / 65536);
+    const size_t table_max = (size_t)(n1 - min_match + 1) * n_sum_max + 1;
+    const size_t scan_tmp = scan_temp_bytes(table_max);
+    if (int rc = ii2_ws_reserve(ctx, stage_bytes + align_up(table_max * sizeof(uint32_t)) + align_up(table_max * sizeof(uint64_t)) + scan_tmp +
+                                         4 * align_up(TOPK_SCORES * sizeof(uint64_t)) + 256 + 4096))
+        return rc;
+    UnionManyParams p;
+    std::memset(&p, 0, sizeof p);
+    TopParams t;
+    std::memset(&t, 0, sizeof t);
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, stage_bytes);
+    t.cnt = ws_take<uint32_t>(ctx, table_max);
+    t.off = ws_take<uint64_t>(ctx, table_max);
+    void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
+    t.hist = ws_take<uint64_t>(ctx, TOPK_SCORES);
+    t.base = ws_take<uint64_t>(ctx, TOPK_SCORES);
+    t.run = ws_take<uint64_t>(ctx, 2 * TOPK_SCORES);
+    p.bounds = ws_take<uint32_t>(ctx, 2);
+    // the descriptors of required group g (n1: the excluded ranges) in a copy of p
+    auto group_params = [&](size_t g, size_t nr, uint64_t n_blocks) {
+        UnionManyParams q = p;
+        q.ranges = (const UmRange *)(d_stage + at[g]);
+        q.pre = (const uint32_t *)(d_stage + at[g] + align_up(nr * sizeof(UmRange)));
+        q.n_ranges = (uint32_t)nr;
+        q.n_blocks = (uint32_t)n_blocks;
+        q.per_wave = um_per_wave(ctx, n_blocks);
+        return q;
+    };
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, stage_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(t.hist, 0, TOPK_SCORES * sizeof(uint64_t), st));
+    if (!Q.req_known) {
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
+        HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
+        for (size_t g = 0; g < n1; g++) {
+            const GroupIn &G = Q.req[g];
+            if (!G.span_known) HIP_TRY(ctx, launch_union_many_bounds(group_params(g, G.r1 - G.r0, G.n_blocks), st));
+        }
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        lo = std::min(lo, hb[0]);
+        hi = std::max(hi, hb[1]);
+    }
+    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: inconsistent list bounds");
+    const uint32_t base = lo & ~31u;
+    const uint64_t span = (uint64_t)hi - base + 1;
+    const uint64_t n_win = (span + W - 1) / W;
+    // the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero
+    if (int rc = um_scratch_reserve(ctx, "ii2_topk_ranges", span, W)) return rc;
+    if (int rc = thr_scratch_reserve(ctx, B, span, W)) return rc;
+    p.check_window = n_win > 1 ? 1u : 0u;
+    set_tomb(t, tomb);
+    t.planes = ctx->d_thr;
+    t.n_planes = B;
+    t.min_match = min_match;
+    t.k = k;
+    t.ids = d_ids;
+    t.scores = d_scores;
+    uint32_t n_marks = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr, f0 = nullptr, f1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    // window w of the doc span in p and t; every required group that can meet it marked and added, the excluded lists left in G
+    uint32_t grid = 0;
+    auto count_window = [&](uint64_t w) -> int {
+        const uint64_t wlo = base + w * W, docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1), whi = wlo + docs - 1;
+        p.window = (uint32_t)w;
+        um_set_window(ctx, p, wlo, docs);
+        grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+        ThrParams a;
+        std::memset(&a, 0, sizeof a);
+        a.bitmap = t.bitmap = p.bitmap;
+        a.summary = t.summary = p.summary;
+        a.plane_words = t.plane_words = p.n_sum * 2048u;
+        a.planes = ctx->d_thr;
+        a.acc = t.acc = ctx->d_thr + (size_t)B * a.plane_words;
+        a.n_sum = t.n_sum = p.n_sum;
+        a.n_planes = B;
+        a.min_match = min_match;
+        t.win_lo = p.win_lo;
+        t.window = p.window;
+        for (size_t g = 0; g < n1; g++) {
+            const GroupIn &G = Q.req[g];
+            if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;          // none of the group's docs lies in this window
+            HIP_TRY(ctx, launch_union_many_mark(group_params(g, G.r1 - G.r0, G.n_blocks), st));
+            HIP_TRY(ctx, launch_thr_add(a, grid, st));
+            n_marks++;
+        }
+        if (excl) {
+            UnionManyParams x = group_params(n1, Q.rx.size(), Q.ex.n_blocks);
+            x.check_window = 1u;                                            // blocks outside the required groups' span are not decoded
+            HIP_TRY(ctx, launch_union_many_mark(x, st));
+        }
+        return II2_OK;
+    };
+    // pass 1: the histogram of the eligible docs' scores
+    for (uint64_t w = 0; w < n_win; w++) {
+        if (int rc = count_window(w)) return rc;
+        t.clear = n_win > 1 || !k ? 1u : 0u;
+        HIP_TRY(ctx, launch_top_hist(t, std::min<uint32_t>(grid, (uint32_t)ctx->cu_count * 2u), st, e0, e1));
+        e0 = e1 = nullptr;
+    }
+    if (k) HIP_TRY(ctx, launch_top_base(t, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h_hist, t.hist, TOPK_SCORES * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    uint64_t n_eligible = 0, n_above = 0;
+    for (uint32_t s = 0; s < TOPK_SCORES; s++) n_eligible += h_hist[s];
+    top_cut(h_hist, k, &stats.max_score, &stats.cut_score, &n_above, &stats.n_cut);
+    // pass 2: the classes cut_score .. max_score, counted per summary word, scanned and placed
+    const bool emit = k && n_eligible;
+    t.cut_score = stats.cut_score;
+    t.n_cls = emit ? stats.max_score - stats.cut_score + 1u : 0u;
+    t.n_cut = stats.n_cut;
+    if (emit || (n_win == 1 && k)) {                                        // (nothing eligible behind one window: its planes are still set)
+        ii2_profile_pair(ctx, &f0, &f1);
+        for (uint64_t w = 0; w < (emit ? n_win : 1); w++) {
+            if (n_win > 1) {
+                if (int rc = count_window(w)) return rc;
+            }
+            if (emit) {
+                if ((size_t)t.n_cls * p.n_sum + 1 > table_max) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: inconsistent count table");
+                HIP_TRY(ctx, launch_top_count(t, grid, st));
+                HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, t.cnt, t.off, (size_t)t.n_cls * p.n_sum + 1, st));
+            }
+            HIP_TRY(ctx, launch_top_emit(t, grid, st, f0, f1));
+            f0 = f1 = nullptr;
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    ctx->um_dirty = false;
+    stats.n_eligible = n_eligible;
+    stats.n_planes = B;
+    stats.n_windows = (uint32_t)n_win;
+    stats.n_marks = n_marks;
+    if (hist) std::memcpy(hist, h_hist, TOPK_SCORES * sizeof(uint64_t));
+    *count = std::min(k, n_eligible);
+    return II2_OK;
+}
+
+static int topk_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, uint32_t min_match, uint64_t k,
+                                const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_ids,
+                                uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topk_stats *stats) {
+    if (!min_match) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: min_match is 0");
+    if (k > II2_TOPK_MAX) return fail(ctx, II2_ERANGE, "ii2_topk_ranges: k above II2_TOPK_MAX (ii2_atleast_ranges returns every doc)");
+    GroupQuery Q;
+    std::vector<uint64_t> kept;
+    if (int rc = plan_atleast(ctx, "ii2_topk_ranges", n_groups, group_first, group_not, segs, list_first, list_end, Q, kept)) return rc;
+    const size_t n1 = Q.req.size();
+    if (n1 > 255) return fail(ctx, II2_ERANGE, "ii2_topk_ranges: more than 255 required groups with postings (the scores are exact 8-bit counters)");
+    ii2_topk_stats st;
+    std::memset(&st, 0, sizeof st);
+    st.n_counted = n1;
+    if (Q.empty || min_match > n1) {
+        *count = 0;
+        if (hist) std::memset(hist, 0, TOPK_SCORES * sizeof(uint64_t));
+        if (stats) *stats = st;
+        return II2_OK;
+    }
+    if (k && !d_ids) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: output buffer is NULL");
+    if (int rc = size_exclusions(ctx, Q)) return rc;
+    if (int rc = topk_count(ctx, Q, min_match, k, tomb, d_ids, d_scores, count, hist, st)) return rc;
+    if (stats) *stats = st;
+    return II2_OK;
+}
+
+// the counters of the 32 docs of a word after adding adds[0, n_adds) into B zero planes, read back as the kernels read a score
+template <uint32_t B> static void top_word_scores(const uint32_t *adds, uint32_t n_adds, uint32_t mask, uint32_t *scores) {
+    uint32_t pl[B] = {};
+    for (uint32_t i = 0; i < n_adds; i++) thr_add_word<B>(pl, adds[i]);
+    for (uint32_t bit = 0; bit < 32; bit++) scores[bit] = (mask >> bit) & 1u ? top_score<B>(pl, bit) : 0u;
+}
+
 // the >= min_match mask after adding adds[0, n_adds) into B zero planes (ii2_atleast_word)
 template <uint32_t B> static uint32_t thr_word_mask(uint32_t min_match, const uint32_t *adds, uint32_t n_adds) {
     uint32_t pl[B] = {};
@@ -1865,6 +2074,38 @@ int ii2_atleast_word(uint32_t n_planes, uint32_t min_match, const uint32_t *adds
         case 6: *mask = thr_word_mask<6>(min_match, adds, n_adds); break;
         case 7: *mask = thr_word_mask<7>(min_match, adds, n_adds); break;
         default: *mask = thr_word_mask<8>(min_match, adds, n_adds); break;
+    }
+    return II2_OK;
+}
+
+int ii2_topk_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, uint32_t min_match, uint64_t k,
+                    const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_ids,
+                    uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topk_stats *stats) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return topk_ranges_unlocked(ctx, n_groups, group_first, group_not, min_match, k, segs, list_first, list_end, tomb, d_ids, d_scores, count, hist, stats);
+}
+
+// host only: the cut of a score histogram for k
+int ii2_topk_cut(const uint64_t *hist, uint64_t k, uint32_t *max_score, uint32_t *cut_score, uint64_t *n_above, uint64_t *n_cut) {
+    if (!hist || !max_score || !cut_score || !n_above || !n_cut) return II2_EINVAL;
+    top_cut(hist, k, max_score, cut_score, n_above, n_cut);
+    return II2_OK;
+}
+
+// host only: the kernels' score extraction
+int ii2_topk_word(uint32_t n_planes, const uint32_t *adds, uint32_t n_adds, uint32_t mask, uint32_t *scores) {
+    if (!scores || (n_adds && !adds) || n_planes < 1 || n_planes > THR_MAX_PLANES) return II2_EINVAL;
+    switch (n_planes) {
+        case 1: top_word_scores<1>(adds, n_adds, mask, scores); break;
+        case 2: top_word_scores<2>(adds, n_adds, mask, scores); break;
+        case 3: top_word_scores<3>(adds, n_adds, mask, scores); break;
+        case 4: top_word_scores<4>(adds, n_adds, mask, scores); break;
+        case 5: top_word_scores<5>(adds, n_adds, mask, scores); break;
+        case 6: top_word_scores<6>(adds, n_adds, mask, scores); break;
+        case 7: top_word_scores<7>(adds, n_adds, mask, scores); break;
+        default: top_word_scores<8>(adds, n_adds, mask, scores); break;
     }
     return II2_OK;
 }

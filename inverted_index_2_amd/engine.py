@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -500,6 +500,28 @@ class Context:
                                              int(min_match), segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p),
                                              tomb.h if tomb else None, _ptr(out), out.count, C.byref(cnt), C.byref(st)))
         return (out, cnt.value, st) if stats else (out, cnt.value)
+
+    def topk_ranges(self, groups, k: int, min_match: int = 1, exclude=(), tomb: Optional["Tombstones"] = None, stats: bool = False,
+                    out: Optional[tuple] = None):
+        """Ranked query (ii2_topk_ranges): groups and exclude as atleast_ranges takes them; the `k` docs that lie in the most groups
+        of `groups` - at least `min_match` of them, in no list of any group of `exclude`, not in `tomb` - ordered by score
+        descending, then id ascending.  Returns (DeviceArray ids, DeviceArray scores, count), with stats=True also the score
+        histogram (ndarray[256]: eligible docs per score) and TopkStats.  k = 0: the histogram and stats only.  `out`: (ids, scores)
+        DeviceArrays of at least k entries to write into instead of fresh ones."""
+        groups = [list(g) for g in groups]
+        group_first, group_not, gsegs, first, end = pack_andnot(groups, exclude)
+        n = len(gsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in gsegs])
+        ids, scores = out if out is not None else (self.empty(max(int(k), 1)), self.empty(max(int(k), 1)))
+        if ids.count < int(k) or scores.count < int(k):
+            raise ValueError("topk_ranges: out holds fewer than k entries")
+        cnt = C.c_uint64()
+        st = TopkStats()
+        hist = np.zeros(256, np.uint64)
+        self._ck(self.lib.ii2_topk_ranges(self.h, len(group_not), group_first.ctypes.data_as(_lib.u64p), group_not.ctypes.data_as(_lib.u8p),
+                                          int(min_match), int(k), segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p),
+                                          tomb.h if tomb else None, _ptr(ids), _ptr(scores), C.byref(cnt), hist.ctypes.data_as(_lib.u64p), C.byref(st)))
+        return (ids, scores, cnt.value, hist, st) if stats else (ids, scores, cnt.value)
 
     def query_batch(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):
         """Many AND / OR queries in one call (ii2_query_batch): queries = [("and" | "or", [(Segment, first, end), ...]), ...] -

@@ -64,6 +64,7 @@ def _lib_typed():
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         lib.ii2h_term_counts.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
@@ -75,6 +76,7 @@ def _lib_typed():
             getattr(lib, f).argtypes = [vp, C.c_uint64]
         lib.ii2h_result_copy.argtypes = [vp, C.c_uint64, vp, vp]
         lib.ii2h_ids_copy.argtypes = [vp, vp]
+        lib.ii2h_scores_copy.argtypes = [vp, vp]
         for f in ("ii2h_segment_count", "ii2h_index_segment_count", "ii2h_shard_count"):
             getattr(lib, f).restype = C.c_uint64
             getattr(lib, f).argtypes = [vp]
@@ -195,7 +197,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectMany, TermCounts)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectMany, TermCounts)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -242,6 +244,19 @@ class InvertedIndex(_Target):
         out = np.zeros(max(n.value, 1), np.uint32)
         self.lib.ii2h_ids_copy(self.h, out.ctypes.data)
         return out[: n.value].tolist()
+
+    def intersect_top(self, terms: List[bytes], k: int, min_match: int = 1, exclude: List[bytes] = ()) -> List[Tuple[int, int]]:
+        """the `k` ids under the most of `terms` - at least `min_match` of them, under no term of `exclude` - as (id, score) pairs,
+        score descending, then id ascending (IntersectTop: one ii2_topk_ranges call); a term found in no segment matches no doc."""
+        blob, off = _pack(list(terms))
+        x_blob, x_off = _pack(list(exclude))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_top(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(k), int(min_match), x_blob.ctypes.data,
+                                             x_off.ctypes.data, len(exclude), C.byref(n)))
+        ids, scores = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        self.lib.ii2h_ids_copy(self.h, ids.ctypes.data)
+        self.lib.ii2h_scores_copy(self.h, scores.ctypes.data)
+        return list(zip(ids[: n.value].tolist(), scores[: n.value].tolist()))
 
     def intersect_batch(self, queries) -> List[List[int]]:
         """Many intersect_except queries, queries = [(terms, exclude), ...], in one device call (IntersectMany: one

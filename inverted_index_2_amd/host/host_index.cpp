@@ -18,6 +18,7 @@
 //   Intersect(terms)                                 additive
 //   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
 //   IntersectAtLeast(terms, min_match, except)       additive: the ids under at least min_match of the terms, minus the excluded terms
+//   IntersectTop(terms, k, min_match, except)        additive: the k ids under the most of the terms, with their scores, in rank order
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //
@@ -943,6 +944,28 @@ class InvertedIndex {
         if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect at least");
         return ids;
     }
+    // additive: the k ids under the MOST of `terms` - at least min_match of them, under none of `except` - with the number of terms each
+    // lies under, ordered by that score descending, then id ascending (a ranked page of a search).  One group per term as
+    // IntersectAtLeast builds them (a term found in no segment is an empty group), ONE ii2_topk_ranges call and one download of the k
+    // (id, score) pairs.  Like IntersectAtLeast, no tombstone filter.
+    std::vector<std::pair<uint32_t, uint32_t>> IntersectTop(const std::vector<Term> &terms, uint64_t k, uint32_t min_match, const std::vector<Term> &except) const {
+        if (!min_match) throw std::runtime_error("intersect top: min_match is 0");
+        if (k > II2_TOPK_MAX) throw std::runtime_error("intersect top: k above II2_TOPK_MAX");
+        Filter f;
+        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
+        filter_build(terms, except, f, &posts);
+        if (posts.size() < min_match || !k) return {};
+        DevMem d_out(ctx_);                                      // ids [0, k), then scores [k, 2k)
+        ck(ctx_, ii2_dev_alloc(ctx_, 2 * k * sizeof(uint32_t), &d_out.p), "intersect top");
+        uint64_t n = 0;
+        ck(ctx_, ii2_topk_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), min_match, k, f.segs.data(), f.first.data(),
+                                 f.end.data(), nullptr, (uint32_t *)d_out.p, (uint32_t *)d_out.p + k, &n, nullptr, nullptr), "intersect top");
+        std::vector<uint32_t> raw(n ? k + n : 0);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top");
+        std::vector<std::pair<uint32_t, uint32_t>> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
+        return out;
+    }
    private:
     // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
     // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
@@ -1276,6 +1299,7 @@ struct ii2h_target {
     std::string err;
     std::vector<TermValues> result;     // last Read / PrefixSearch result
     std::vector<uint32_t> ids;          // last Intersect / RemovedValues result
+    std::vector<uint32_t> scores;       // last IntersectTop result: the score of each of ids
     std::vector<std::pair<Term, uint64_t>> counts;      // last TermCounts result
 };
 
@@ -1434,6 +1458,16 @@ int ii2h_intersect_at_least(ii2h_target *t, const uint8_t *bytes, const uint64_t
                             const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->IntersectAtLeast(unpack_terms(bytes, off, n), min_match, unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
 }
+int ii2h_intersect_top(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t k, uint32_t min_match, const uint8_t *x_bytes,
+                       const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
+    H_TRY(t, {
+        const auto top = t->index->IntersectTop(unpack_terms(bytes, off, n), k, min_match, unpack_terms(x_bytes, x_off, n_x));
+        t->ids.resize(top.size());
+        t->scores.resize(top.size());
+        for (size_t i = 0; i < top.size(); i++) { t->ids[i] = top[i].first; t->scores[i] = top[i].second; }
+        *n_ids = top.size();
+    })
+}
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->IntersectExcept(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
@@ -1479,6 +1513,9 @@ void ii2h_result_copy(const ii2h_target *t, uint64_t i, uint8_t *term, uint32_t 
 }
 void ii2h_ids_copy(const ii2h_target *t, uint32_t *out) {
     if (!t->ids.empty()) std::memcpy(out, t->ids.data(), t->ids.size() * 4);
+}
+void ii2h_scores_copy(const ii2h_target *t, uint32_t *out) {
+    if (!t->scores.empty()) std::memcpy(out, t->scores.data(), t->scores.size() * 4);
 }
 uint64_t ii2h_segment_count(const ii2h_target *t) { return t->shard ? t->shard->SegmentCount() : 0; }
 uint64_t ii2h_index_segment_count(const ii2h_target *t) { return t->index ? t->index->SegmentCount() : 0; }      // the segments of all its shards
