@@ -640,7 +640,7 @@ func (c *Ctx) TopKRanges(groupFirst []uint64, groupNot []uint8, minMatch uint32,
 	return uint64(n), hist, stats, nil
 }
 
-// Scored is one entry of a ranked result: a doc id and the number of groups it lies in.
+// Scored is one entry of a ranked result: a doc id and its score - the number of groups it lies in, or the sum of their weights.
 type Scored struct {
 	ID, Score uint32
 }
@@ -663,6 +663,75 @@ func (c *Ctx) TopKRangesHost(groupFirst []uint64, groupNot []uint8, minMatch uin
 	raw := make([]uint32, k+n)
 	if rc := C.ii2_copy_d2h(c.h, unsafe.Pointer(&raw[0]), d, C.size_t((k+n)*4)); rc != 0 {
 		return nil, c.err("topk ranges", rc)
+	}
+	out := make([]Scored, n)
+	for i := range out {
+		out[i] = Scored{raw[i], raw[k+uint64(i)]}
+	}
+	return out, nil
+}
+
+// TopKWStats mirrors ii2_topkw_stats.
+type TopKWStats struct {
+	Counted, Eligible, NCut                                         uint64
+	TotalWeight, MaxScore, CutScore, Planes, Windows, NMarks, NLate uint32
+}
+
+// TopKWeightedRanges is TopKRanges with a weight per group (ii2_topk_weighted_ranges): a doc's score is the sum of groupWeight[g]
+// over the required groups g it lies in - weights 1 .. 255 that sum to at most 255 over the groups with postings - and it is
+// eligible from minScore up.  groupWeight holds one entry per group (an excluded group's is ignored); nil: every weight is 1.
+// Everything else - groups, ranges, groupNot, the order, the buffers, k == 0 - is TopKRanges'.
+func (c *Ctx) TopKWeightedRanges(groupFirst []uint64, groupNot []uint8, groupWeight []uint32, minScore uint32, k uint64, segs []*Segment, listFirst, listEnd []uint64, ids, scores unsafe.Pointer) (uint64, [256]uint64, TopKWStats, error) {
+	var hist [256]uint64
+	nGroups := len(groupFirst) - 1
+	if nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || (groupWeight != nil && len(groupWeight) != nGroups) || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return 0, hist, TopKWStats{}, fmt.Errorf("topk weighted ranges: array lengths disagree")
+	}
+	if groupFirst[nGroups] != uint64(len(segs)) { // the C side reads the range arrays up to groupFirst's last element
+		return 0, hist, TopKWStats{}, fmt.Errorf("topk weighted ranges: groupFirst does not end at the number of ranges")
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if groupNot != nil && nGroups > 0 {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	var weights *C.uint32_t
+	if groupWeight != nil && nGroups > 0 {
+		weights = (*C.uint32_t)(unsafe.Pointer(&groupWeight[0]))
+	}
+	var n C.uint64_t
+	var st C.ii2_topkw_stats
+	rc := C.ii2_topk_weighted_ranges(c.h, C.uint64_t(nGroups), u64ptr(groupFirst), flags, weights, C.uint32_t(minScore), C.uint64_t(k),
+		(**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(ids), (*C.uint32_t)(scores), &n,
+		(*C.uint64_t)(unsafe.Pointer(&hist[0])), &st)
+	if rc != 0 {
+		return 0, hist, TopKWStats{}, c.err("topk weighted ranges", rc)
+	}
+	stats := TopKWStats{uint64(st.n_counted), uint64(st.n_eligible), uint64(st.n_cut), uint32(st.total_weight), uint32(st.max_score), uint32(st.cut_score),
+		uint32(st.n_planes), uint32(st.n_windows), uint32(st.n_marks), uint32(st.n_late)}
+	return uint64(n), hist, stats, nil
+}
+
+// TopKWeightedRangesHost is TopKWeightedRanges with the result in host memory, as TopKRangesHost is TopKRanges'.
+func (c *Ctx) TopKWeightedRangesHost(groupFirst []uint64, groupNot []uint8, groupWeight []uint32, minScore uint32, k uint64, segs []*Segment, listFirst, listEnd []uint64) ([]Scored, error) {
+	if k == 0 {
+		return nil, nil
+	}
+	var d unsafe.Pointer
+	if rc := C.ii2_dev_alloc(c.h, C.size_t(2*k*4), &d); rc != 0 {
+		return nil, c.err("topk weighted ranges", rc)
+	}
+	defer C.ii2_dev_free(c.h, d)
+	n, _, _, err := c.TopKWeightedRanges(groupFirst, groupNot, groupWeight, minScore, k, segs, listFirst, listEnd, d, unsafe.Add(d, int(k*4)))
+	if err != nil || n == 0 {
+		return nil, err
+	}
+	raw := make([]uint32, k+n)
+	if rc := C.ii2_copy_d2h(c.h, unsafe.Pointer(&raw[0]), d, C.size_t((k+n)*4)); rc != 0 {
+		return nil, c.err("topk weighted ranges", rc)
 	}
 	out := make([]Scored, n)
 	for i := range out {

@@ -433,6 +433,64 @@ func IntersectTop(c *Ctx, ix ResidentIndex, terms [][]byte, k uint64, minMatch u
 	return top, nil
 }
 
+// IntersectTopWeighted (additive): IntersectTop with a weight per term - an idf tier, a field boost.  A doc's score is the sum of
+// weights[i] over the terms[i] it lies under (1 .. 255 each, at most 255 together), at least minScore.  The groups are IntersectTop's:
+// a term found in no segment keeps its slot, and its weight, and matches nothing.  ONE Ctx.TopKWeightedRanges call with one download
+// - what the C++ host mirror's InvertedIndex::IntersectTopWeighted does (host/host_index.cpp).
+func IntersectTopWeighted(c *Ctx, ix ResidentIndex, terms [][]byte, weights []uint32, k uint64, minScore uint32, except [][]byte) ([]Scored, error) {
+	if minScore == 0 {
+		return nil, fmt.Errorf("intersect top weighted: minScore is 0")
+	}
+	if len(weights) != len(terms) {
+		return nil, fmt.Errorf("intersect top weighted: one weight per term")
+	}
+	if k > TopKMax {
+		return nil, fmt.Errorf("intersect top weighted: k above TopKMax")
+	}
+	defer ix.Release()
+	groupFirst := []uint64{0}
+	var groupNot []uint8
+	var segs []*Segment
+	var first, end []uint64
+	groupWeight := append([]uint32(nil), weights...)
+	held := 0 // the terms that some segment holds
+	for _, t := range terms {
+		s, l, _ := ix.TermLists(t)
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 0)
+		if len(s) > 0 {
+			held++
+		}
+	}
+	if held == 0 || k == 0 {
+		return nil, nil
+	}
+	for _, t := range except {
+		s, l, _ := ix.TermLists(t)
+		if len(s) == 0 {
+			continue // (in no segment: it removes nothing)
+		}
+		segs = append(segs, s...)
+		for _, j := range l {
+			first = append(first, j)
+			end = append(end, j+1)
+		}
+		groupFirst = append(groupFirst, uint64(len(segs)))
+		groupNot = append(groupNot, 1)
+		groupWeight = append(groupWeight, 0) // (ignored)
+	}
+	top, err := c.TopKWeightedRangesHost(groupFirst, groupNot, groupWeight, minScore, k, segs, first, end)
+	if err != nil {
+		return nil, fmt.Errorf("intersect top weighted: %w", err)
+	}
+	return top, nil
+}
+
 // IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
 // "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
 // flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does

@@ -28,6 +28,7 @@
  *     and excluded - are at most II2_MAX_LISTS and hold at most 8192 postings in at most 128 blocks, by default only while
  *     postings x lists <= 32768 (what the form costs; beyond it, or beyond the kernel, a query takes the general form: no error).
  *     ii2_topk_ranges takes at most 255 required groups that have postings and k <= II2_TOPK_MAX = 2^20.
+ *     ii2_topk_weighted_ranges takes group weights 1 .. 255 whose sum over those groups is at most 255.
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
  *     internal mutex, so a ctx may be shared by goroutines / threads (InvertedIndex.Merge
  *     fans Shard.Merge over `concurrency` goroutines, inverted_index.go:83-103); use one
@@ -548,6 +549,56 @@ int ii2_topk_cut(const uint64_t *hist, uint64_t k, uint32_t *max_score, uint32_t
  * n_adds > 0: II2_EINVAL. */
 int ii2_topk_word(uint32_t n_planes, const uint32_t *adds, uint32_t n_adds, uint32_t mask, uint32_t *scores /* 32 */);
 
+/* ---- the ranked query with a weight per group ---------------------------------------------- */
+/* ii2_topk_ranges ranks by the number of groups a doc lies in; here every required group carries a weight - an idf tier, a field
+ * boost (title:error^4 body:error^1 host:db*^2) - and score(d) = the sum of group_weight[g] over the REQUIRED groups g that hold
+ * d in at least one list.  d is eligible when score(d) >= min_score, d lies in no list of any excluded group, and d is not in
+ * tomb.  Everything not stated here is ii2_topk_ranges' contract word for word: groups, ranges, group_not, the tombstones, the
+ * order (score descending, then doc id ascending), *count <= k, k == 0, d_scores == NULL, all-or-nothing on every error, the
+ * scratch left all zero, and the message prefix, which is this entry point's name.
+ *   - group_weight (host, n_groups entries): the weight of each group; an excluded group's entry is ignored.  NULL: every weight
+ *     is 1, and the call returns what ii2_topk_ranges returns for min_match = min_score.
+ *   - W' = the weights summed over the n' required groups that have postings.  min_score > W', n_groups == 0, or no required
+ *     group with postings: *count = 0, hist all zero, nothing is launched, stats holds only n_counted and total_weight.
+ *   - II2_EINVAL: min_score == 0; a required group of weight 0 (drop the group instead); everything ii2_topk_ranges rejects as
+ *     II2_EINVAL.  II2_ERANGE: a required group's weight above 255; W' above 255 (the scores are exact 8-bit values that never
+ *     saturate, so ii2_topk_ranges' kernels serve unchanged); k > II2_TOPK_MAX; the block and range limits.
+ *   - hist[s] = the eligible docs whose score is exactly s.
+ * How it runs (no kernel path is counted): as ii2_topk_ranges with B = bit_width(W') counter bitmaps, but behind every mark the
+ * group's weight is added to its docs' counters by a ripple-carry add that starts at bit ctz(weight) - the bitmaps below are
+ * neither read nor written.  Late mode (option topk.late, default 1): take the counted groups in descending order of postings,
+ * ties by index; the longest prefix whose weights sum to at most min_score - 1 is marked after all other groups, and its adds
+ * skip every 2048-doc chunk that no earlier group touched - a doc that lies only in those groups scores below min_score.  Every
+ * eligible doc's score stays exact; the big low-weight groups (the stop-words) touch only the chunks the rare terms named. */
+typedef struct {
+    uint64_t n_counted;     /* required groups with postings (n') */
+    uint64_t n_eligible;    /* eligible docs = sum of hist */
+    uint64_t n_cut;         /* docs of score cut_score returned */
+    uint32_t total_weight;  /* W' = sum of the weights of the n' counted groups */
+    uint32_t max_score, cut_score;
+    uint32_t n_planes;      /* bit_width(W'); 0 when nothing ran */
+    uint32_t n_windows, n_marks;
+    uint32_t n_late;        /* counted groups added in late mode */
+    uint32_t pad;
+} ii2_topkw_stats;          /* 56 bytes */
+int ii2_topk_weighted_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                             const uint32_t *group_weight /* host, n_groups entries; NULL: every weight 1 */,
+                             uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first,
+                             const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores,
+                             uint64_t *count, uint64_t *hist /* host, 256, may be NULL */, ii2_topkw_stats *stats);
+/* The weighted query's arithmetic, host only (no GPU needed).  ii2_topkw_word: ii2_topk_word with a weight per add - scores[i] =
+ * the sum of weights[j] over the words adds[j] that hold bit i, as the kernels' add leaves it in n_planes planes (saturating at
+ * 2^n_planes - 1, never wrapping); docs outside mask get 0.  n_planes outside 1 .. 8, a weight of 0 or above 255, a NULL scores,
+ * or NULL adds / weights with n_adds > 0: II2_EINVAL. */
+int ii2_topkw_word(uint32_t n_planes, const uint32_t *adds, const uint32_t *weights, uint32_t n_adds, uint32_t mask, uint32_t *scores /* 32 */);
+/* What ii2_topk_weighted_ranges would use for n_counted required groups with postings, of these weights and posting counts:
+ * *total_weight = W', *n_planes = bit_width(W'), *window_docs as ii2_atleast_plan gives it for that many planes, late[g] = 1 for
+ * the groups added in late mode (option topk.late 1) and *n_late their number.  min_score > W': every output is 0, as
+ * ii2_atleast_plan's are when nothing would run.  II2_EINVAL: a NULL output, NULL weights / postings with n_counted > 0, min_score == 0, a weight of 0.
+ * II2_ERANGE: a weight above 255, W' above 255. */
+int ii2_topkw_plan(uint64_t n_counted, const uint32_t *weights, const uint64_t *postings, uint32_t min_score, uint32_t window_log2,
+                   uint32_t *total_weight, uint32_t *n_planes, uint64_t *window_docs, uint8_t *late /* n_counted */, uint32_t *n_late);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -641,6 +692,8 @@ int ii2_selftest(ii2_ctx *ctx);
  *   atleast.small                           ii2_atleast_ranges: its one-launch form, with andnot.small's values and limits (default 1)
  *   atleast.handoff                         ii2_atleast_ranges: 1 (default) min_match = n' runs ii2_andnot_ranges' paths and min_match = 1
  *                                           without exclusion ii2_union_ranges'; 0 (tests, measuring) they take the forms of its own
+ *   topk.late                               ii2_topk_weighted_ranges: 1 (default) the largest groups whose weights sum to less than
+ *                                           min_score are added in late mode; 0 (tests, measuring) no group is.  Same results
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel

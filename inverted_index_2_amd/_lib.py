@@ -45,6 +45,12 @@ class TopkStats(C.Structure):
                 ("cut_score", C.c_uint32), ("n_planes", C.c_uint32), ("n_windows", C.c_uint32), ("n_marks", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class TopkwStats(C.Structure):
+    _fields_ = [("n_counted", C.c_uint64), ("n_eligible", C.c_uint64), ("n_cut", C.c_uint64), ("total_weight", C.c_uint32),
+                ("max_score", C.c_uint32), ("cut_score", C.c_uint32), ("n_planes", C.c_uint32), ("n_windows", C.c_uint32),
+                ("n_marks", C.c_uint32), ("n_late", C.c_uint32), ("pad", C.c_uint32)]
+
+
 II2_TOPK_MAX = 1 << 20
 II2_ATLEAST_NONE, II2_ATLEAST_SMALL, II2_ATLEAST_COUNT, II2_ATLEAST_AND, II2_ATLEAST_OR = range(5)
 
@@ -106,6 +112,10 @@ PROTOTYPES = {
     "ii2_topk_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, C.c_uint32, C.c_uint64, vpp, u64p, u64p, vp, vp, vp, u64p, u64p, C.POINTER(TopkStats)]),
     "ii2_topk_cut": (C.c_int, [u64p, C.c_uint64, u32p, u32p, u64p, u64p]),
     "ii2_topk_word": (C.c_int, [C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p]),
+    "ii2_topk_weighted_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, u32p, C.c_uint32, C.c_uint64, vpp, u64p, u64p, vp, vp, vp, u64p, u64p,
+                                           C.POINTER(TopkwStats)]),
+    "ii2_topkw_word": (C.c_int, [C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, u32p]),
+    "ii2_topkw_plan": (C.c_int, [C.c_uint64, u32p, u64p, C.c_uint32, C.c_uint32, u32p, u32p, u64p, u8p, u32p]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

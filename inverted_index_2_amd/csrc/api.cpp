@@ -1059,6 +1059,7 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "andnot.small") ctx->opt_andnot_small = value;
     else if (k == "atleast.small") ctx->opt_atleast_small = value;
     else if (k == "atleast.handoff") ctx->opt_atleast_handoff = value;
+    else if (k == "topk.late") ctx->opt_topk_late = value;
     else if (k == "union.sparsity") ctx->opt_union_sparsity = value > 0 ? value : 2048;
     else if (k == "intersect.map_docs") ctx->opt_intersect_map_docs = value;
     else if (k == "intersect.dense") ctx->opt_intersect_dense = value;

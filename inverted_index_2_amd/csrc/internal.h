@@ -123,6 +123,7 @@ struct ii2_ctx {
     uint32_t *d_an = nullptr;           // its required part's result, the candidates of the exclusion pass (grow-only; neither d_ir, which the
     size_t an_words = 0;                //     group path ping-pongs in, nor workspace, which the driver's union reserves itself)
     int64_t opt_atleast_small = 1;      // ii2_atleast_ranges: short queries in one launch (setop_groups.hip), as andnot.small; 0: never, 2: up to the kernel's capacity
+    int64_t opt_topk_late = 1;          // ii2_topk_weighted_ranges: 1 the big low-weight groups are added in late mode; 0 none is (tests, measuring)
     int64_t opt_atleast_handoff = 1;    // ... min_match = n' through ii2_andnot_ranges' paths, min_match = 1 without exclusion through the union's (0: tests, measuring)
     uint32_t *d_thr = nullptr;          // its counting form's counter planes + accumulated summary: all-zero between calls like d_um_bits and
     size_t thr_words = 0;               //     cleaned with it (grow-only, <= 128 MiB + 64 KiB)
@@ -548,6 +549,19 @@ struct TopParams {
     uint32_t *ids;               // [k] the result, score descending, then id ascending
     uint32_t *scores;            // [k], may be null
 };
+// the weighted query's add (topk.hip: k_top_add): ThrParams' scratch, and the weight of the group just marked
+struct TopAddParams {
+    uint32_t *bitmap;            // the window's doc bitmap G [n_sum * 2048] and ...
+    uint32_t *summary;           // ... its summary [n_sum]
+    uint32_t *planes;            // [n_planes][plane_words] the counters
+    uint32_t *acc;               // [n_sum] S_acc
+    uint32_t plane_words;        // n_sum * 2048
+    uint32_t n_sum;
+    uint32_t n_planes;           // 1 .. THR_MAX_PLANES
+    uint32_t weight;             // 1 .. 2^n_planes - 1: added to the counter of every doc in G
+    uint32_t late;               // 1 = chunks that S_acc does not name are cleared, not added
+};
+hipError_t launch_top_add(const TopAddParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_top_hist(const TopParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t launch_top_base(const TopParams &p, hipStream_t s);
 hipError_t launch_top_count(const TopParams &p, uint32_t grid, hipStream_t s);

@@ -1568,8 +1568,10 @@ extern "C" int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t
 // required group without postings is dropped, not fatal (Q.req: the n' required groups that have postings, tags 0 .. n' - 1
 // in for_each_counted_list), and the span the excluded lists must meet is the required groups' whole span, not their common
 // one - a result doc need not lie in every group.  kept: the groups of the call that are left (the AND hand-off's arguments).
+// req_weight (the weighted ranked query): the weight of each group of Q.req, group_weight's entry or 1 without one.
 static int plan_atleast(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
-                        const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q, std::vector<uint64_t> &kept) {
+                        const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q, std::vector<uint64_t> &kept,
+                        const uint32_t *group_weight = nullptr, std::vector<uint32_t> *req_weight = nullptr) {
     Q.ex = IrPass{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
     Q.shortest = ~0ull;
     Q.req_known = true;
@@ -1589,6 +1591,7 @@ static int plan_atleast(ii2_ctx *ctx, const char *who, uint64_t n_groups, const 
         if (!group_not || !group_not[g]) {
             if (!G.n_blocks) continue;                                  // a required group without postings matches no doc
             Q.req.push_back(G);
+            if (req_weight) req_weight->push_back(group_weight ? group_weight[g] : 1u);
         } else {                                                        // (an excluded group without postings adds nothing)
             Q.rx.insert(Q.rx.end(), Q.rs.begin() + G.r0, Q.rs.begin() + G.r1);
             Q.ex.n_blocks += G.n_blocks;
@@ -1828,12 +1831,27 @@ static int atleast_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64
 // table, scan, emit in rank order).  One window: the planes stay between the passes and every group is marked once.  Several:
 // pass 1 cleans up behind each window and pass 2 marks and adds again.  Waits: the bounds of spans the host does not mirror, the
 // histogram, the end of pass 2.  Everything the caller sees is written after the last of them.
-static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t k, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores,
-                      uint64_t *count, uint64_t *hist, ii2_topk_stats &stats) {
+// weights == NULL: ii2_topk_ranges - a doc's score is the number of its groups, every add is atleast.hip's.  Else (`who` is
+// ii2_topk_weighted_ranges) weights[g] is the weight of Q.req[g] and late[g] whether it is added in late mode: B = bit_width(W'),
+// the early groups come first and the late ones after them, every mark is followed by topk.hip's weighted add, and *n_late counts
+// the late groups.  min_match is the lowest eligible score in both.
+static int topk_count(ii2_ctx *ctx, const char *who, GroupQuery &Q, uint32_t min_match, uint64_t k, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores,
+                      uint64_t *count, uint64_t *hist, ii2_topk_stats &stats, const uint32_t *weights = nullptr, const uint8_t *late = nullptr,
+                      uint32_t *n_late = nullptr) {
     hipStream_t st = ctx->stream;
     const size_t n1 = Q.req.size();
     const bool excl = Q.ex.n_nonempty > 0;
-    const uint32_t B = thr_bit_width(n1);
+    const std::string name(who);
+    uint64_t top = n1;                                                      // the highest score a doc can reach
+    std::vector<size_t> order(n1);
+    for (size_t g = 0; g < n1; g++) order[g] = g;
+    if (weights) {
+        top = 0;
+        for (size_t g = 0; g < n1; g++) top += weights[g];
+        std::stable_partition(order.begin(), order.end(), [&](size_t g) { return !late[g]; });
+        *n_late = (uint32_t)std::count(late, late + n1, (uint8_t)1);
+    }
+    const uint32_t B = thr_bit_width(top);
     if (int rc = um_scratch_clean(ctx)) return rc;
     // staging: one descriptor block (ranges + block prefix) per required group, one for all excluded ranges, then the histogram on
     // its way down
@@ -1845,7 +1863,7 @@ static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t 
     }
     at[n1] = stage_bytes;
     if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes + TOPK_SCORES * sizeof(uint64_t), false, "ii2_topk_ranges: staging allocation failed")) return rc;
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes + TOPK_SCORES * sizeof(uint64_t), false, (name + ": staging allocation failed").c_str())) return rc;
     uint8_t *h = (uint8_t *)ctx->h_um;
     uint64_t *h_hist = (uint64_t *)(h + stage_bytes);
     for (size_t g = 0; g < n1; g++) um_desc_fill(Q.rs, Q.req[g].r0, Q.req[g].r1, h + at[g]);
@@ -1859,7 +1877,7 @@ static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t 
     // summary word of the largest window
     uint64_t n_sum_max = (W + 65535) / 65536;
     if (Q.req_known && lo <= hi) n_sum_max = std::min<uint64_t>(n_sum_max, (std::min<uint64_t>((uint64_t)hi - (lo & ~31u) + 1, W) + 65535) / 65536);
-    const size_t table_max = (size_t)(n1 - min_match + 1) * n_sum_max + 1;
+    const size_t table_max = (size_t)(top - min_match + 1) * n_sum_max + 1;
     const size_t scan_tmp = scan_temp_bytes(table_max);
     if (int rc = ii2_ws_reserve(ctx, stage_bytes + align_up(table_max * sizeof(uint32_t)) + align_up(table_max * sizeof(uint64_t)) + scan_tmp +
                                          4 * align_up(TOPK_SCORES * sizeof(uint64_t)) + 256 + 4096))
@@ -1902,12 +1920,12 @@ static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t 
         lo = std::min(lo, hb[0]);
         hi = std::max(hi, hb[1]);
     }
-    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: inconsistent list bounds");
+    if (lo > hi) return fail(ctx, II2_EINVAL, (name + ": inconsistent list bounds").c_str());
     const uint32_t base = lo & ~31u;
     const uint64_t span = (uint64_t)hi - base + 1;
     const uint64_t n_win = (span + W - 1) / W;
     // the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero
-    if (int rc = um_scratch_reserve(ctx, "ii2_topk_ranges", span, W)) return rc;
+    if (int rc = um_scratch_reserve(ctx, who, span, W)) return rc;
     if (int rc = thr_scratch_reserve(ctx, B, span, W)) return rc;
     p.check_window = n_win > 1 ? 1u : 0u;
     set_tomb(t, tomb);
@@ -1937,13 +1955,28 @@ static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t 
         a.n_sum = t.n_sum = p.n_sum;
         a.n_planes = B;
         a.min_match = min_match;
+        TopAddParams wa;
+        std::memset(&wa, 0, sizeof wa);
+        wa.bitmap = a.bitmap;
+        wa.summary = a.summary;
+        wa.planes = a.planes;
+        wa.acc = a.acc;
+        wa.plane_words = a.plane_words;
+        wa.n_sum = a.n_sum;
+        wa.n_planes = B;
         t.win_lo = p.win_lo;
         t.window = p.window;
-        for (size_t g = 0; g < n1; g++) {
+        for (size_t g : order) {
             const GroupIn &G = Q.req[g];
             if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;          // none of the group's docs lies in this window
             HIP_TRY(ctx, launch_union_many_mark(group_params(g, G.r1 - G.r0, G.n_blocks), st));
-            HIP_TRY(ctx, launch_thr_add(a, grid, st));
+            if (weights) {
+                wa.weight = weights[g];
+                wa.late = late[g];
+                HIP_TRY(ctx, launch_top_add(wa, grid, st));
+            } else {
+                HIP_TRY(ctx, launch_thr_add(a, grid, st));
+            }
             n_marks++;
         }
         if (excl) {
@@ -1978,7 +2011,7 @@ static int topk_count(ii2_ctx *ctx, GroupQuery &Q, uint32_t min_match, uint64_t 
                 if (int rc = count_window(w)) return rc;
             }
             if (emit) {
-                if ((size_t)t.n_cls * p.n_sum + 1 > table_max) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: inconsistent count table");
+                if ((size_t)t.n_cls * p.n_sum + 1 > table_max) return fail(ctx, II2_EINVAL, (name + ": inconsistent count table").c_str());
                 HIP_TRY(ctx, launch_top_count(t, grid, st));
                 HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, t.cnt, t.off, (size_t)t.n_cls * p.n_sum + 1, st));
             }
@@ -2018,7 +2051,58 @@ static int topk_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t 
     }
     if (k && !d_ids) return fail(ctx, II2_EINVAL, "ii2_topk_ranges: output buffer is NULL");
     if (int rc = size_exclusions(ctx, Q)) return rc;
-    if (int rc = topk_count(ctx, Q, min_match, k, tomb, d_ids, d_scores, count, hist, st)) return rc;
+    if (int rc = topk_count(ctx, "ii2_topk_ranges", Q, min_match, k, tomb, d_ids, d_scores, count, hist, st)) return rc;
+    if (stats) *stats = st;
+    return II2_OK;
+}
+
+// ii2_topk_weighted_ranges: ii2_topk_ranges' checks and plan with a weight per counted group, then the same ranked form
+static int topkw_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, const uint32_t *group_weight,
+                                 uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topkw_stats *stats) {
+    static const char who[] = "ii2_topk_weighted_ranges";
+    const std::string name(who);
+    if (!min_score) return fail(ctx, II2_EINVAL, (name + ": min_score is 0").c_str());
+    if (k > II2_TOPK_MAX) return fail(ctx, II2_ERANGE, (name + ": k above II2_TOPK_MAX (ii2_atleast_ranges returns every doc)").c_str());
+    GroupQuery Q;
+    std::vector<uint64_t> kept;
+    std::vector<uint32_t> weights;
+    if (int rc = plan_atleast(ctx, who, n_groups, group_first, group_not, segs, list_first, list_end, Q, kept, group_weight, &weights)) return rc;
+    for (uint64_t g = 0; group_weight && g < n_groups; g++) {
+        if (group_not && group_not[g]) continue;                            // an excluded group's weight is ignored
+        if (!group_weight[g]) return fail(ctx, II2_EINVAL, (name + ": required group " + std::to_string(g) + " has weight 0 (drop the group instead)").c_str());
+        if (group_weight[g] > 255) return fail(ctx, II2_ERANGE, (name + ": the weight of required group " + std::to_string(g) + " is above 255").c_str());
+    }
+    const size_t n1 = Q.req.size();
+    uint64_t total = 0;
+    for (uint32_t w : weights) total += w;
+    if (total > 255) return fail(ctx, II2_ERANGE, (name + ": the weights of the required groups with postings sum to more than 255 (the scores are exact 8-bit values)").c_str());
+    ii2_topkw_stats st;
+    std::memset(&st, 0, sizeof st);
+    st.n_counted = n1;
+    st.total_weight = (uint32_t)total;
+    if (Q.empty || min_score > total) {
+        *count = 0;
+        if (hist) std::memset(hist, 0, TOPK_SCORES * sizeof(uint64_t));
+        if (stats) *stats = st;
+        return II2_OK;
+    }
+    if (k && !d_ids) return fail(ctx, II2_EINVAL, (name + ": output buffer is NULL").c_str());
+    if (int rc = size_exclusions(ctx, Q)) return rc;
+    std::vector<uint64_t> postings(n1);
+    for (size_t g = 0; g < n1; g++) postings[g] = Q.req[g].n_post;
+    std::vector<uint8_t> late(n1, 0);
+    if (ctx->opt_topk_late) top_late_set(n1, weights.data(), postings.data(), min_score, late.data());
+    ii2_topk_stats ts;
+    std::memset(&ts, 0, sizeof ts);
+    if (int rc = topk_count(ctx, who, Q, min_score, k, tomb, d_ids, d_scores, count, hist, ts, weights.data(), late.data(), &st.n_late)) return rc;
+    st.n_eligible = ts.n_eligible;
+    st.n_cut = ts.n_cut;
+    st.max_score = ts.max_score;
+    st.cut_score = ts.cut_score;
+    st.n_planes = ts.n_planes;
+    st.n_windows = ts.n_windows;
+    st.n_marks = ts.n_marks;
     if (stats) *stats = st;
     return II2_OK;
 }
@@ -2027,6 +2111,13 @@ static int topk_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t 
 template <uint32_t B> static void top_word_scores(const uint32_t *adds, uint32_t n_adds, uint32_t mask, uint32_t *scores) {
     uint32_t pl[B] = {};
     for (uint32_t i = 0; i < n_adds; i++) thr_add_word<B>(pl, adds[i]);
+    for (uint32_t bit = 0; bit < 32; bit++) scores[bit] = (mask >> bit) & 1u ? top_score<B>(pl, bit) : 0u;
+}
+
+// ... after adding weights[i] to the docs of adds[i], as the weighted form's kernel does (ii2_topkw_word)
+template <uint32_t B> static void topw_word_scores(const uint32_t *adds, const uint32_t *weights, uint32_t n_adds, uint32_t mask, uint32_t *scores) {
+    uint32_t pl[B] = {};
+    for (uint32_t i = 0; i < n_adds; i++) top_add_weighted<B>(pl, adds[i], weights[i]);
     for (uint32_t bit = 0; bit < 32; bit++) scores[bit] = (mask >> bit) & 1u ? top_score<B>(pl, bit) : 0u;
 }
 
@@ -2107,6 +2198,54 @@ int ii2_topk_word(uint32_t n_planes, const uint32_t *adds, uint32_t n_adds, uint
         case 7: top_word_scores<7>(adds, n_adds, mask, scores); break;
         default: top_word_scores<8>(adds, n_adds, mask, scores); break;
     }
+    return II2_OK;
+}
+
+int ii2_topk_weighted_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, const uint32_t *group_weight,
+                             uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                             const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topkw_stats *stats) {
+    if (!ctx || !count) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return topkw_ranges_unlocked(ctx, n_groups, group_first, group_not, group_weight, min_score, k, segs, list_first, list_end, tomb, d_ids, d_scores, count,
+                                 hist, stats);
+}
+
+// host only: the weighted add and the score extraction of the kernels
+int ii2_topkw_word(uint32_t n_planes, const uint32_t *adds, const uint32_t *weights, uint32_t n_adds, uint32_t mask, uint32_t *scores) {
+    if (!scores || (n_adds && (!adds || !weights)) || n_planes < 1 || n_planes > THR_MAX_PLANES) return II2_EINVAL;
+    for (uint32_t i = 0; i < n_adds; i++)
+        if (!weights[i] || weights[i] > 255) return II2_EINVAL;
+    switch (n_planes) {
+        case 1: topw_word_scores<1>(adds, weights, n_adds, mask, scores); break;
+        case 2: topw_word_scores<2>(adds, weights, n_adds, mask, scores); break;
+        case 3: topw_word_scores<3>(adds, weights, n_adds, mask, scores); break;
+        case 4: topw_word_scores<4>(adds, weights, n_adds, mask, scores); break;
+        case 5: topw_word_scores<5>(adds, weights, n_adds, mask, scores); break;
+        case 6: topw_word_scores<6>(adds, weights, n_adds, mask, scores); break;
+        case 7: topw_word_scores<7>(adds, weights, n_adds, mask, scores); break;
+        default: topw_word_scores<8>(adds, weights, n_adds, mask, scores); break;
+    }
+    return II2_OK;
+}
+
+// host only: what the weighted ranked query would use for these counted groups
+int ii2_topkw_plan(uint64_t n_counted, const uint32_t *weights, const uint64_t *postings, uint32_t min_score, uint32_t window_log2, uint32_t *total_weight,
+                   uint32_t *n_planes, uint64_t *window_docs, uint8_t *late, uint32_t *n_late) {
+    if (!total_weight || !n_planes || !window_docs || !n_late || !min_score || (n_counted && (!weights || !postings || !late))) return II2_EINVAL;
+    uint64_t total = 0;
+    for (uint64_t g = 0; g < n_counted; g++) {
+        if (!weights[g]) return II2_EINVAL;
+        if (weights[g] > 255 || (total += weights[g]) > 255) return II2_ERANGE;
+    }
+    *total_weight = *n_planes = *n_late = 0u;
+    *window_docs = 0;
+    for (uint64_t g = 0; g < n_counted; g++) late[g] = 0;
+    if (min_score > total) return II2_OK;
+    *total_weight = (uint32_t)total;
+    *n_planes = thr_bit_width(total);
+    *window_docs = thr_window_docs(*n_planes, window_log2);
+    *n_late = top_late_set(n_counted, weights, postings, min_score, late);
     return II2_OK;
 }
 

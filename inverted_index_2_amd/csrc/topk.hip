@@ -16,6 +16,10 @@
 // A word's docs are tallied class by class: the class of the lowest doc left is read from the planes (top_score), an equality
 // mask names every doc of that class in the wave's 64 words (top_eq_word), they are counted / placed by one wave scan, and the
 // loop goes on with what is left - as many rounds as the 2048 docs hold distinct scores, whatever n' is.
+// The weighted form (ii2_topk_weighted_ranges) puts its own add behind every mark, k_top_add: the walk of the counting form's add
+// kernel (atleast.hip), but the group's weight w is added to its docs' counters (topk_count.h: top_add_weighted), and only the
+// planes ctz(w) .. B - 1 are loaded and stored - an even weight moves fewer bytes (the kernel is instantiated on their number).  Late mode is the counting form's: a chunk
+// that S_acc does not name is cleared, not added (topk_count.h: top_late_set says for which groups that loses no eligible doc).
 // A summary word and its 2048 x 32 docs belong to one wave; no kernel waits for another workgroup.
 #include <hip/hip_runtime.h>
 
@@ -207,6 +211,68 @@ template <uint32_t B> __global__ __launch_bounds__(256) void k_top_emit(TopParam
             if (marked) p.summary[sw] = 0u;
         }
     }
+}
+
+// behind a group's mark: w added to the counters of the docs in G, G and its summary zeroed, the chunks named in S_acc.  One wave
+// per summary word; every access is 64 lanes x one dword, consecutive; the weight and late are wave-uniform.  NP = B - ctz(w) planes
+// take part: the launch hands the kernel plane ctz(w) as its plane 0 and w >> ctz(w), an odd weight, so the loads and stores of
+// the NP planes stand side by side without a branch between them.
+template <uint32_t NP> __global__ __launch_bounds__(256) void k_top_add(TopAddParams p) {
+    const uint32_t l = threadIdx.x & 63u;
+    const uint32_t n_waves = gridDim.x * 4u;
+    const uint32_t w = p.weight | 1u;                                     // (odd already: the add is known to start at plane 0)
+    for (uint32_t sw = blockIdx.x * 4u + (threadIdx.x >> 6); sw < p.n_sum; sw += n_waves) {
+        const uint32_t set = p.summary[sw];
+        if (!set) continue;                                               // (wave-uniform)
+        const uint32_t acc = p.acc[sw];
+        uint32_t bits = set;
+        while (bits) {
+            const uint32_t chunk = (uint32_t)__builtin_ctz(bits);
+            bits &= bits - 1u;
+            const uint32_t wi = (sw * 32u + chunk) * 64u + l;
+            const uint32_t g = p.bitmap[wi];
+            if (!g) continue;
+            p.bitmap[wi] = 0u;
+            if (p.late && !((acc >> chunk) & 1u)) continue;               // no doc of this chunk was seen in an early group
+            uint32_t pl[NP];
+#pragma unroll
+            for (uint32_t b = 0; b < NP; b++) pl[b] = p.planes[(size_t)b * p.plane_words + wi];
+            top_add_weighted<NP>(pl, g, w);
+#pragma unroll
+            for (uint32_t b = 0; b < NP; b++) p.planes[(size_t)b * p.plane_words + wi] = pl[b];
+        }
+        if (l == 0) {
+            if (!p.late) p.acc[sw] = acc | set;
+            p.summary[sw] = 0u;
+        }
+    }
+}
+
+template <uint32_t NP> static void top_add_launch(const TopAddParams &p, uint32_t grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_top_add<NP>, dim3(grid), dim3(256), 0, s, p);
+}
+
+hipError_t launch_top_add(const TopAddParams &p, uint32_t grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+    if (p.n_planes < 1u || p.n_planes > THR_MAX_PLANES || !grid || !p.weight || (p.weight >> p.n_planes)) return hipErrorInvalidValue;
+    // the planes below ctz(weight) are neither read nor written: the kernel sees the others as planes 0 .. NP - 1
+    const uint32_t z = (uint32_t)__builtin_ctz(p.weight);
+    TopAddParams q = p;
+    q.planes = p.planes + (size_t)z * p.plane_words;
+    q.n_planes = p.n_planes - z;
+    q.weight = p.weight >> z;
+    if (ev0) (void)hipEventRecord(ev0, s);
+    switch (q.n_planes) {
+        case 1: top_add_launch<1>(q, grid, s); break;
+        case 2: top_add_launch<2>(q, grid, s); break;
+        case 3: top_add_launch<3>(q, grid, s); break;
+        case 4: top_add_launch<4>(q, grid, s); break;
+        case 5: top_add_launch<5>(q, grid, s); break;
+        case 6: top_add_launch<6>(q, grid, s); break;
+        case 7: top_add_launch<7>(q, grid, s); break;
+        default: top_add_launch<8>(q, grid, s); break;
+    }
+    if (ev1) (void)hipEventRecord(ev1, s);
+    return hipGetLastError();
 }
 
 enum TopKernel { TOP_HIST, TOP_COUNT, TOP_EMIT };

@@ -2,6 +2,8 @@
 // counter of atleast_count.h (B = bit_width(n') planes, so it never saturates); here are the three things the ranking adds: a
 // doc's score read back from the planes, the docs of a word whose score equals / exceeds a value, and the cut of a score
 // histogram for k.  The device kernels and the host-only exports (ii2_topk_word, ii2_topk_cut) run the same code.
+// The weighted form (ii2_topk_weighted_ranges) adds two: a constant added to the counters of a word's docs, and the choice of the
+// groups that may be added in late mode (ii2_topkw_word, ii2_topkw_plan).
 #pragma once
 #include <stdint.h>
 
@@ -37,6 +39,45 @@ template <uint32_t B> II2_HD uint32_t top_eq_word(const uint32_t (&pl)[B], uint3
     uint32_t eq, gt;
     top_cmp_word<B>(pl, s, &eq, &gt);
     return eq;
+}
+
+// add the constant w (0 < w < 2^B) to the counters of the docs in word g: a full-adder ripple per plane from plane ctz(w) up - a
+// multiple of 2^ctz(w) leaves the planes below alone.  A carry out of the top plane saturates as thr_add_word does.
+template <uint32_t B> II2_HD void top_add_weighted(uint32_t (&pl)[B], uint32_t g, uint32_t w) {
+    const uint32_t z = w ? (uint32_t)__builtin_ctz(w) : B;
+    uint32_t carry = 0u;
+#pragma unroll
+    for (uint32_t b = 0; b < B; b++) {
+        if (b < z) continue;
+        const uint32_t a = ((w >> b) & 1u) ? g : 0u;
+        const uint32_t x = pl[b];
+        pl[b] = x ^ a ^ carry;
+        carry = (x & a) | (carry & (x ^ a));
+    }
+    carry |= (w >> B) ? g : 0u;                            // (a weight the planes cannot hold: saturate)
+#pragma unroll
+    for (uint32_t b = 0; b < B; b++) pl[b] |= carry;       // the carry left the top plane: all ones
+}
+
+// The late set of a weighted query.  The counted groups in descending order of postings, ties by index; the late groups are the
+// longest prefix of that order whose weights sum to at most min_score - 1: a doc that lies in late groups only scores below
+// min_score, so a late group's add may skip every 2048-doc chunk that no early group touched.  late[g] = 1 for those groups;
+// returns their number.  min_score > the sum of all weights: nothing is late (nothing runs).
+II2_HD uint32_t top_late_set(uint64_t n, const uint32_t *weights, const uint64_t *postings, uint32_t min_score, uint8_t *late) {
+    uint64_t total = 0;
+    for (uint64_t g = 0; g < n; g++) { late[g] = 0; total += weights[g]; }
+    if (min_score > total) return 0u;
+    uint64_t sum = 0;
+    uint32_t n_late = 0;
+    for (;;) {
+        uint64_t best = n;                                 // the largest group not yet taken, the lowest index among equals
+        for (uint64_t g = 0; g < n; g++)
+            if (!late[g] && (best == n || postings[g] > postings[best])) best = g;
+        if (best == n || sum + weights[best] + 1u > min_score) return n_late;
+        sum += weights[best];
+        late[best] = 1;
+        n_late++;
+    }
 }
 
 // The cut of a score histogram (hist[s] = docs of score s, TOPK_SCORES entries) for the k best docs: *cut_score = the largest s

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkStats
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -521,6 +521,33 @@ class Context:
         self._ck(self.lib.ii2_topk_ranges(self.h, len(group_not), group_first.ctypes.data_as(_lib.u64p), group_not.ctypes.data_as(_lib.u8p),
                                           int(min_match), int(k), segs, first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p),
                                           tomb.h if tomb else None, _ptr(ids), _ptr(scores), C.byref(cnt), hist.ctypes.data_as(_lib.u64p), C.byref(st)))
+        return (ids, scores, cnt.value, hist, st) if stats else (ids, scores, cnt.value)
+
+    def topk_weighted_ranges(self, groups, weights, k: int, min_score: int = 1, exclude=(), tomb: Optional["Tombstones"] = None,
+                             stats: bool = False, out: Optional[tuple] = None):
+        """Ranked query with a weight per group (ii2_topk_weighted_ranges): groups, exclude, k, tomb and out as topk_ranges takes
+        them; `weights` holds one integer 1 .. 255 per group of `groups` (None: every weight is 1) and a doc's score is the sum of
+        the weights of the groups it lies in - at least `min_score`, at most 255.  Returns (DeviceArray ids, DeviceArray scores,
+        count), with stats=True also the score histogram (ndarray[256]) and TopkwStats."""
+        groups = [list(g) for g in groups]
+        group_first, group_not, gsegs, first, end = pack_andnot(groups, exclude)
+        n = len(gsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in gsegs])
+        c_weights = None
+        if weights is not None:
+            if len(weights) != len(groups):
+                raise ValueError("topk_weighted_ranges: one weight per group")
+            c_weights = (C.c_uint32 * max(len(group_not), 1))(*[int(w) for w in weights])      # (an excluded group's entry is ignored)
+        ids, scores = out if out is not None else (self.empty(max(int(k), 1)), self.empty(max(int(k), 1)))
+        if ids.count < int(k) or scores.count < int(k):
+            raise ValueError("topk_weighted_ranges: out holds fewer than k entries")
+        cnt = C.c_uint64()
+        st = TopkwStats()
+        hist = np.zeros(256, np.uint64)
+        self._ck(self.lib.ii2_topk_weighted_ranges(self.h, len(group_not), group_first.ctypes.data_as(_lib.u64p), group_not.ctypes.data_as(_lib.u8p),
+                                                   c_weights, int(min_score), int(k), segs, first.ctypes.data_as(_lib.u64p),
+                                                   end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None, _ptr(ids), _ptr(scores), C.byref(cnt),
+                                                   hist.ctypes.data_as(_lib.u64p), C.byref(st)))
         return (ids, scores, cnt.value, hist, st) if stats else (ids, scores, cnt.value)
 
     def query_batch(self, queries, tomb: Optional["Tombstones"] = None, out: Optional[DeviceArray] = None):

@@ -65,6 +65,7 @@ def _lib_typed():
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         lib.ii2h_term_counts.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
@@ -197,7 +198,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectMany, TermCounts)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectMany, TermCounts)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -253,6 +254,24 @@ class InvertedIndex(_Target):
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_top(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(k), int(min_match), x_blob.ctypes.data,
                                              x_off.ctypes.data, len(exclude), C.byref(n)))
+        ids, scores = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        self.lib.ii2h_ids_copy(self.h, ids.ctypes.data)
+        self.lib.ii2h_scores_copy(self.h, scores.ctypes.data)
+        return list(zip(ids[: n.value].tolist(), scores[: n.value].tolist()))
+
+    def intersect_top_weighted(self, terms: List[bytes], weights: List[int], k: int, min_score: int = 1,
+                               exclude: List[bytes] = ()) -> List[Tuple[int, int]]:
+        """intersect_top with a weight per term: a doc's score is the sum of `weights[i]` (1 .. 255 each, at most 255 together) over
+        the `terms[i]` it lies under, at least `min_score` (IntersectTopWeighted: one ii2_topk_weighted_ranges call); a term found
+        in no segment keeps its slot and matches no doc."""
+        if len(weights) != len(terms):
+            raise ValueError("intersect_top_weighted: one weight per term")
+        blob, off = _pack(list(terms))
+        x_blob, x_off = _pack(list(exclude))
+        w = np.asarray(list(weights) + [0], np.uint32)
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_top_weighted(self.h, blob.ctypes.data, off.ctypes.data, len(terms), w.ctypes.data, int(k), int(min_score),
+                                                      x_blob.ctypes.data, x_off.ctypes.data, len(exclude), C.byref(n)))
         ids, scores = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
         self.lib.ii2h_ids_copy(self.h, ids.ctypes.data)
         self.lib.ii2h_scores_copy(self.h, scores.ctypes.data)

@@ -19,6 +19,7 @@
 //   IntersectExcept(terms, except)                   additive: Intersect minus the ids under any excluded term
 //   IntersectAtLeast(terms, min_match, except)       additive: the ids under at least min_match of the terms, minus the excluded terms
 //   IntersectTop(terms, k, min_match, except)        additive: the k ids under the most of the terms, with their scores, in rank order
+//   IntersectTopWeighted(terms, weights, k, min_score, except)   additive: the same with a weight per term, the score their sum
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //
@@ -966,6 +967,32 @@ class InvertedIndex {
         for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
         return out;
     }
+    // additive: IntersectTop with a weight per term (an idf tier, a field boost): a doc's score is the sum of the weights of the terms it
+    // lies under, 1 .. 255 each and at most 255 together; at least min_score.  The groups are IntersectTop's - a term found in no
+    // segment keeps its slot, and its weight, and matches nothing - and the call is ONE ii2_topk_weighted_ranges.
+    std::vector<std::pair<uint32_t, uint32_t>> IntersectTopWeighted(const std::vector<Term> &terms, const std::vector<uint32_t> &weights, uint64_t k,
+                                                                    uint32_t min_score, const std::vector<Term> &except) const {
+        if (!min_score) throw std::runtime_error("intersect top weighted: min_score is 0");
+        if (weights.size() != terms.size()) throw std::runtime_error("intersect top weighted: one weight per term");
+        if (k > II2_TOPK_MAX) throw std::runtime_error("intersect top weighted: k above II2_TOPK_MAX");
+        Filter f;
+        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
+        filter_build(terms, except, f, &posts);
+        if (posts.empty() || !k) return {};
+        std::vector<uint32_t> group_weight(weights);
+        group_weight.resize(f.group_not.size(), 0u);             // (the excluded groups follow the terms: their weights are ignored)
+        DevMem d_out(ctx_);                                      // ids [0, k), then scores [k, 2k)
+        ck(ctx_, ii2_dev_alloc(ctx_, 2 * k * sizeof(uint32_t), &d_out.p), "intersect top weighted");
+        uint64_t n = 0;
+        ck(ctx_, ii2_topk_weighted_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), group_weight.data(), min_score, k,
+                                          f.segs.data(), f.first.data(), f.end.data(), nullptr, (uint32_t *)d_out.p, (uint32_t *)d_out.p + k, &n, nullptr,
+                                          nullptr), "intersect top weighted");
+        std::vector<uint32_t> raw(n ? k + n : 0);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top weighted");
+        std::vector<std::pair<uint32_t, uint32_t>> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
+        return out;
+    }
    private:
     // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
     // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
@@ -1462,6 +1489,17 @@ int ii2h_intersect_top(ii2h_target *t, const uint8_t *bytes, const uint64_t *off
                        const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, {
         const auto top = t->index->IntersectTop(unpack_terms(bytes, off, n), k, min_match, unpack_terms(x_bytes, x_off, n_x));
+        t->ids.resize(top.size());
+        t->scores.resize(top.size());
+        for (size_t i = 0; i < top.size(); i++) { t->ids[i] = top[i].first; t->scores[i] = top[i].second; }
+        *n_ids = top.size();
+    })
+}
+int ii2h_intersect_top_weighted(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint32_t *weights, uint64_t k,
+                                uint32_t min_score, const uint8_t *x_bytes, const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
+    H_TRY(t, {
+        const auto top = t->index->IntersectTopWeighted(unpack_terms(bytes, off, n), std::vector<uint32_t>(weights, weights + n), k, min_score,
+                                                        unpack_terms(x_bytes, x_off, n_x));
         t->ids.resize(top.size());
         t->scores.resize(top.size());
         for (size_t i = 0; i < top.size(); i++) { t->ids[i] = top[i].first; t->scores[i] = top[i].second; }
