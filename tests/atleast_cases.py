@@ -1,7 +1,9 @@
 """The case table of ii2_atleast_ranges ("docs in at least m of n groups"), shared by tests/test_atleast_cases_cpu.py (every
 reference is non-trivial) and tests/test_gpu_atleast_ranges.py (every case under every form).  Pure numpy: a case is its lists,
 its groups as lists of list indices, the threshold and the removed ids; reference() is the plain count over np.unique'd groups.
-All ids stay below 2^18 (at most 128 windows of 2048 docs) and a case holds at most a few thousand postings."""
+All ids stay below 2^18 (at most 128 windows of 2048 docs) and a case holds at most a few thousand postings: every kernel of the
+counting form runs as one workgroup here.  The wide regimes - several workgroups, a second grid-stride step, the windows of the default
+union.many_window_log2, ids up to 0xFFFFFFFF - live in tests/wide_cases.py."""
 from dataclasses import dataclass, field
 from typing import List, Sequence
 

@@ -4,7 +4,9 @@ every k, one window and many, one segment and two, with and without tombstones).
 lists, groups as lists of list indices, excluded groups, removed ids - plus the values of k and min_match it runs at.
 reference() is the plain count over np.unique'd groups and one lexsort.  It holds every case of atleast_cases.CASES with at most
 255 groups that have postings, at min_match 1 and at the case's own m, and the cases written for the ranking below.  All ids stay
-below 2^18 except in high_ids, and a case holds at most a few ten thousand postings."""
+below 2^18 except in high_ids (a span of 32 docs), and a case holds at most a few ten thousand postings: every kernel of the ranked
+query runs as one workgroup here and its count table fits one scan tile.  The wide regimes - several workgroups, a second grid-stride
+step, a table of two scan tiles, the windows of the default union.many_window_log2 - live in tests/wide_cases.py."""
 from dataclasses import dataclass
 from typing import List
 
