@@ -740,6 +740,103 @@ func (c *Ctx) TopKWeightedRangesHost(groupFirst []uint64, groupNot []uint8, grou
 	return out, nil
 }
 
+// TopKBatchStats mirrors ii2_topk_batch_stats.
+type TopKBatchStats struct {
+	Tiny, Small, Single, Empty uint32
+	Staged                     uint64
+}
+
+// TopKBatch answers MANY ranked queries over resident segments in one call (ii2_topk_batch): query q owns the groups
+// queryFirst[q] .. queryFirst[q+1]-1 - groupFirst, groupNot and the range arrays are those of QueryBatchGroups, groupWeight holds
+// one entry per group of the batch (nil: every weight is 1) - and its result is what TopKWeightedRanges returns for those groups
+// with minScore[q] (nil: every one is 1) and k[q]: the same ids in the same order, the same scores.  The results are packed back
+// to back in query order into the device buffers ids and scores (capEntries entries each; scores may be nil; the sum of the k[q]
+// is always enough); the returned offsets (len(queryFirst)) delimit them and eligible[q] is query q's number of eligible docs.
+// All-or-nothing: on ErrCapacity nothing was written and the last offset is the capacity to call again with.
+func (c *Ctx) TopKBatch(queryFirst, groupFirst []uint64, groupNot []uint8, groupWeight, minScore, k []uint32, segs []*Segment, listFirst, listEnd []uint64, ids, scores unsafe.Pointer, capEntries uint64) ([]uint64, []uint64, TopKBatchStats, error) {
+	nQueries := len(queryFirst) - 1
+	nGroups := len(groupFirst) - 1
+	if nQueries < 0 || nGroups < 0 || (groupNot != nil && len(groupNot) != nGroups) || (groupWeight != nil && len(groupWeight) != nGroups) ||
+		(minScore != nil && len(minScore) != nQueries) || len(k) != nQueries || len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return nil, nil, TopKBatchStats{}, fmt.Errorf("topk batch: array lengths disagree")
+	}
+	// the C side reads groupFirst[0 .. queryFirst[nQueries]] and the range arrays up to groupFirst's last element
+	if queryFirst[nQueries] != uint64(nGroups) || groupFirst[nGroups] != uint64(len(segs)) {
+		return nil, nil, TopKBatchStats{}, fmt.Errorf("topk batch: queryFirst / groupFirst do not end at the lengths of the arrays they index")
+	}
+	offsets := make([]uint64, nQueries+1)
+	eligible := make([]uint64, nQueries+1)
+	if nQueries == 0 {
+		return offsets, eligible[:0], TopKBatchStats{}, nil
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	var flags *C.uint8_t
+	if len(groupNot) != 0 {
+		flags = (*C.uint8_t)(unsafe.Pointer(&groupNot[0]))
+	}
+	var weights, mins *C.uint32_t
+	if len(groupWeight) != 0 {
+		weights = (*C.uint32_t)(unsafe.Pointer(&groupWeight[0]))
+	}
+	if len(minScore) != 0 {
+		mins = (*C.uint32_t)(unsafe.Pointer(&minScore[0]))
+	}
+	var st C.ii2_topk_batch_stats
+	rc := C.ii2_topk_batch(c.h, C.uint64_t(nQueries), u64ptr(queryFirst), u64ptr(groupFirst), flags, weights, mins,
+		(*C.uint32_t)(unsafe.Pointer(&k[0])), (**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd), nil, (*C.uint32_t)(ids),
+		(*C.uint32_t)(scores), C.uint64_t(capEntries), u64ptr(offsets), u64ptr(eligible), &st)
+	stats := TopKBatchStats{uint32(st.n_tiny), uint32(st.n_small), uint32(st.n_single), uint32(st.n_empty), uint64(st.n_staged)}
+	if rc == C.II2_ECAPACITY {
+		return offsets, eligible[:nQueries], stats, ErrCapacity
+	}
+	if rc != 0 {
+		return nil, nil, TopKBatchStats{}, c.err("topk batch", rc)
+	}
+	return offsets, eligible[:nQueries], stats, nil
+}
+
+// TopKBatchHost is TopKBatch with the results in host memory, one slice per query: a first call with capEntries entries, a second
+// one with the size the first reported when they did not fit, and one download.
+func (c *Ctx) TopKBatchHost(queryFirst, groupFirst []uint64, groupNot []uint8, groupWeight, minScore, k []uint32, segs []*Segment, listFirst, listEnd []uint64, capEntries uint64) ([][]Scored, error) {
+	out := make([][]Scored, len(k))
+	if capEntries == 0 {
+		capEntries = 1
+	}
+	for attempt := 0; ; attempt++ {
+		var d unsafe.Pointer
+		if rc := C.ii2_dev_alloc(c.h, C.size_t(2*capEntries*4), &d); rc != 0 {
+			return nil, c.err("topk batch", rc)
+		}
+		off, _, _, err := c.TopKBatch(queryFirst, groupFirst, groupNot, groupWeight, minScore, k, segs, listFirst, listEnd, d, unsafe.Add(d, int(capEntries*4)), capEntries)
+		if err == ErrCapacity && attempt == 0 {
+			C.ii2_dev_free(c.h, d)
+			capEntries = off[len(off)-1]
+			continue
+		}
+		if err != nil {
+			C.ii2_dev_free(c.h, d)
+			return nil, err
+		}
+		if n := off[len(off)-1]; n != 0 {
+			raw := make([]uint32, capEntries+n)
+			if rc := C.ii2_copy_d2h(c.h, unsafe.Pointer(&raw[0]), d, C.size_t((capEntries+n)*4)); rc != 0 {
+				C.ii2_dev_free(c.h, d)
+				return nil, c.err("topk batch", rc)
+			}
+			for q := range out {
+				for i := off[q]; i < off[q+1]; i++ {
+					out[q] = append(out[q], Scored{raw[i], raw[capEntries+i]})
+				}
+			}
+		}
+		C.ii2_dev_free(c.h, d)
+		return out, nil
+	}
+}
+
 // CountStats mirrors ii2_count_stats.
 type CountStats struct {
 	Lists, Blocks, Decoded, Hits uint64

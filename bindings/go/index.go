@@ -491,6 +491,97 @@ func IntersectTopWeighted(c *Ctx, ix ResidentIndex, terms [][]byte, weights []ui
 	return top, nil
 }
 
+// TopQuery is one query of IntersectTopBatch: IntersectTopWeighted's arguments.
+type TopQuery struct {
+	Terms    [][]byte
+	Weights  []uint32
+	K        uint64
+	MinScore uint32
+	Except   [][]byte
+}
+
+// IntersectTopBatch (additive): MANY IntersectTopWeighted queries in one device call; result q is that of IntersectTopWeighted for
+// queries[q].  Per query the groups are built exactly as IntersectTopWeighted builds them; a query none of whose terms is in a
+// segment, or with K == 0, keeps its place without a group - its result is empty.  ONE Ctx.TopKBatch call, a second one when the
+// results exceed the first buffer of at most 4M entries, and one download - what the C++ host mirror's
+// InvertedIndex::IntersectTopBatch does (host/host_index.cpp).
+func IntersectTopBatch(c *Ctx, ix ResidentIndex, queries []TopQuery) ([][]Scored, error) {
+	if len(queries) == 0 {
+		return nil, nil
+	}
+	defer ix.Release()
+	const firstCap = uint64(1) << 22
+	queryFirst, groupFirst := []uint64{0}, []uint64{0}
+	var groupNot []uint8
+	var groupWeight, minScore, ks []uint32
+	var segs []*Segment
+	var first, end []uint64
+	total := uint64(0)
+	for q, Q := range queries {
+		if Q.MinScore == 0 {
+			return nil, fmt.Errorf("intersect top batch: query %d: minScore is 0", q)
+		}
+		if len(Q.Weights) != len(Q.Terms) {
+			return nil, fmt.Errorf("intersect top batch: query %d: one weight per term", q)
+		}
+		if Q.K > TopKMax {
+			return nil, fmt.Errorf("intersect top batch: query %d: k above TopKMax", q)
+		}
+		minScore = append(minScore, Q.MinScore)
+		ks = append(ks, uint32(Q.K))
+		gMark, rMark := len(groupNot), len(segs)
+		posts := uint64(0)
+		add := func(t []byte, not uint8, w uint32) {
+			s, l, post := ix.TermLists(t)
+			if len(s) == 0 && not == 1 {
+				return // (an excluded term in no segment removes nothing)
+			}
+			segs = append(segs, s...)
+			for _, j := range l {
+				first = append(first, j)
+				end = append(end, j+1)
+			}
+			groupFirst = append(groupFirst, uint64(len(segs)))
+			groupNot = append(groupNot, not)
+			groupWeight = append(groupWeight, w)
+			if not == 0 && len(s) > 0 {
+				if post == 0 {
+					post = 1
+				}
+				posts += post
+			}
+		}
+		for i, t := range Q.Terms {
+			add(t, 0, Q.Weights[i])
+		}
+		if posts != 0 && Q.K != 0 {
+			for _, t := range Q.Except {
+				add(t, 1, 0)
+			}
+			if Q.K < posts {
+				posts = Q.K
+			}
+			total += posts
+		} else { // the query keeps its place, without a group
+			groupFirst, groupNot, groupWeight = groupFirst[:gMark+1], groupNot[:gMark], groupWeight[:gMark]
+			segs, first, end = segs[:rMark], first[:rMark], end[:rMark]
+		}
+		queryFirst = append(queryFirst, uint64(len(groupNot)))
+	}
+	capEntries := total
+	if capEntries > firstCap {
+		capEntries = firstCap
+	}
+	if capEntries == 0 {
+		capEntries = 1
+	}
+	out, err := c.TopKBatchHost(queryFirst, groupFirst, groupNot, groupWeight, minScore, ks, segs, first, end, capEntries)
+	if err != nil {
+		return nil, fmt.Errorf("intersect top batch: %w", err)
+	}
+	return out, nil
+}
+
 // IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
 // "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
 // flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does

@@ -29,6 +29,9 @@
  *     postings x lists <= 32768 (what the form costs; beyond it, or beyond the kernel, a query takes the general form: no error).
  *     ii2_topk_ranges takes at most 255 required groups that have postings and k <= II2_TOPK_MAX = 2^20.
  *     ii2_topk_weighted_ranges takes group weights 1 .. 255 whose sum over those groups is at most 255.
+ *     ii2_topk_batch takes <= 2^20 such queries whose result bounds (min(k, the postings of the query's required groups)) add up
+ *     to < 2^32 ids; a query of at most II2_MAX_LISTS counted lists that hold at most 8192 postings in at most 128 blocks shares
+ *     the batch's launch (larger ones run one by one: no error).
  *   - a ctx is bound to one GPU and one HIP stream; calls on one ctx are serialised by an
  *     internal mutex, so a ctx may be shared by goroutines / threads (InvertedIndex.Merge
  *     fans Shard.Merge over `concurrency` goroutines, inverted_index.go:83-103); use one
@@ -599,6 +602,63 @@ int ii2_topkw_word(uint32_t n_planes, const uint32_t *adds, const uint32_t *weig
 int ii2_topkw_plan(uint64_t n_counted, const uint32_t *weights, const uint64_t *postings, uint32_t min_score, uint32_t window_log2,
                    uint32_t *total_weight, uint32_t *n_planes, uint64_t *window_docs, uint8_t *late /* n_counted */, uint32_t *n_late);
 
+/* ---- many ranked queries in one call --------------------------------------------------------- */
+/* Query q is an ii2_topk_weighted_ranges call over the groups query_first[q] .. query_first[q + 1] - 1 with min_score[q] and k[q];
+ * query_first, group_first, group_not and the range arrays are exactly those of ii2_query_batch_groups.  group_weight (host) covers
+ * all G = query_first[n_queries] groups of the batch, an excluded group's entry is ignored, NULL: every weight is 1.  min_score
+ * (host, n_queries; NULL: every one is 1) and k (host, n_queries).
+ *   - Result q is bit for bit what ii2_topk_weighted_ranges writes for that query: the same ids in the same order (score descending,
+ *     then doc id ascending) and the same scores; its *count is out_off[q + 1] - out_off[q], its stats.n_eligible is eligible[q].
+ *     The results are packed back to back in query order into d_ids and, when given, into d_scores at the same offsets.
+ *   - The per-query rules are that call's, word for word: a required group without postings matches no doc; min_score[q] above W',
+ *     a query without groups, or k[q] == 0 gives an empty result (eligible[q] is still exact for k[q] == 0); an excluded group
+ *     without postings is ignored; tomb applies to every query.
+ *   - All-or-nothing: every query is checked before anything is launched or written, and everything that call rejects is rejected
+ *     with the same code - min_score 0, a weight of 0 or above 255 on a required group, W' above 255 (so n' above 255), k above
+ *     II2_TOPK_MAX, no required group, a bad flag, a bad range, a segment or tombstones of another device - under the message
+ *     "ii2_topk_batch: query N: ...".  More than 2^20 queries, or bounds that add up to 2^32 ids or more: II2_ERANGE.
+ *   - The bound of query q is min(k[q], the postings of its required groups that have postings), 0 when nothing runs.  cap (in
+ *     entries, for d_ids and d_scores each) >= the sum of the bounds is always enough.  When the packed results exceed cap:
+ *     II2_ECAPACITY, d_ids and d_scores untouched, out_off completely filled, eligible and stats written.  n_queries == 0 sets
+ *     out_off[0] = 0.
+ * How it runs (no kernel path is counted, like the rest of the ranked family; stats tells what ran): a query whose counted lists -
+ * the non-empty lists of its required groups and the excluded lists that count - are at most II2_MAX_LISTS and hold at most 8192
+ * postings in at most 128 blocks, with at most II2_MAX_LISTS required groups that have postings, is answered by one workgroup of
+ * the batch kernel (option batch.topk; option batch.tiny picks the 256- or the 1024-thread form): every list decoded into LDS,
+ * every id ranked with its group's tag, the head of every run of equal ids sums the weights of the run's distinct required
+ * groups, and the eligible (id, score) pairs are put in rank order by one stable counting sort on 255 - score.  No per-context
+ * scratch is touched and the whole batch has one wait.  The other queries run one after the other through
+ * ii2_topk_weighted_ranges' form, each with that form's own waits. */
+typedef struct {
+    uint32_t n_tiny, n_small;   /* queries answered by the batch kernel, per size class */
+    uint32_t n_single;          /* queries run one by one through ii2_topk_weighted_ranges' form */
+    uint32_t n_empty;           /* queries for which nothing ran */
+    uint64_t n_staged;          /* sum of the queries' result bounds */
+} ii2_topk_batch_stats;         /* 24 bytes */
+int ii2_topk_batch(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,
+                   const uint8_t *group_not, const uint32_t *group_weight /* NULL: every weight 1 */,
+                   const uint32_t *min_score /* [n_queries]; NULL: every one 1 */, const uint32_t *k /* [n_queries] */,
+                   const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb,
+                   uint32_t *d_ids, uint32_t *d_scores /* may be NULL */, uint64_t cap, uint64_t *out_off /* host, n_queries + 1 */,
+                   uint64_t *eligible /* host, n_queries, may be NULL */, ii2_topk_batch_stats *stats /* may be NULL */);
+/* The batch kernel's rule and the host's choice of form, host only (no GPU needed).  ii2_topk_batch_run: tags[0 .. n_tags) are the
+ * group tags of one run of equal ids, ascending (required groups 0 .. n_req - 1, the excluded lists n_req), weights[t] the weight
+ * of tag t < n_req; *score = the sum of the weights of the run's distinct required tags, *excluded = 1 when the run's last tag is
+ * the excluded one, computed by the function the kernel calls.  A NULL argument, n_tags == 0 or above II2_MAX_LISTS + 1, n_req
+ * above II2_MAX_LISTS, or a tag above n_req: II2_EINVAL. */
+int ii2_topk_batch_run(const uint8_t *tags, uint32_t n_tags, uint32_t n_req, const uint8_t *weights /* n_req */,
+                       uint32_t *score, uint32_t *excluded);
+/* ii2_topk_batch_plan: a query whose n_lists counted lists hold n_postings postings in n_blocks blocks, n_counted required
+ * groups with postings that hold req_postings of them, and k, under the values batch_topk / batch_tiny of the two options:
+ * *form = the II2_TOPK_BATCH_* the host planner picks with the same function, *bound = min(k, req_postings), 0 for an empty one
+ * (n_counted == 0).  A NULL output: II2_EINVAL. */
+#define II2_TOPK_BATCH_EMPTY 0
+#define II2_TOPK_BATCH_TINY 1
+#define II2_TOPK_BATCH_SMALL 2
+#define II2_TOPK_BATCH_SINGLE 3
+int ii2_topk_batch_plan(uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_counted, uint64_t req_postings,
+                        uint64_t k, int64_t batch_topk, int64_t batch_tiny, uint32_t *form, uint64_t *bound);
+
 /* ---- host-buffer convenience (what the cgo binding calls) ------------------------------- */
 /* k term-aligned segments, flat: seg_off[k*(n_terms+1)] (per segment, offsets into that
  * segment's own slice), seg_base[k+1] (where each segment's slice starts in values).
@@ -676,7 +736,10 @@ int ii2_selftest(ii2_ctx *ctx);
  *   batch.groups                            ii2_query_batch_groups: 1 (default) the queries that fit one workgroup share the batch kernel
  *                                           (batch.tiny picks its form as above), 0 every query of a batch goes through the paths of
  *                                           ii2_andnot_ranges one after the other
- *   union.many                              ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
+ *   batch.topk                              ii2_topk_batch: 1 (default) the queries that fit one workgroup share the batch kernel
+ *                                           (batch.tiny picks its form as above), 0 every query of a batch goes through
+ *                                           ii2_topk_weighted_ranges' form one after the other
+ *   union.many                             ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)
  *   count.summary_skip                      ii2_count_ranges: 1 (default) a block whose docs meet no marked 2048-doc chunk of the set's

@@ -51,7 +51,12 @@ class TopkwStats(C.Structure):
                 ("n_marks", C.c_uint32), ("n_late", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class TopkBatchStats(C.Structure):
+    _fields_ = [("n_tiny", C.c_uint32), ("n_small", C.c_uint32), ("n_single", C.c_uint32), ("n_empty", C.c_uint32), ("n_staged", C.c_uint64)]
+
+
 II2_TOPK_MAX = 1 << 20
+II2_TOPK_BATCH_EMPTY, II2_TOPK_BATCH_TINY, II2_TOPK_BATCH_SMALL, II2_TOPK_BATCH_SINGLE = range(4)
 II2_ATLEAST_NONE, II2_ATLEAST_SMALL, II2_ATLEAST_COUNT, II2_ATLEAST_AND, II2_ATLEAST_OR = range(5)
 
 vp = C.c_void_p
@@ -116,6 +121,10 @@ PROTOTYPES = {
                                            C.POINTER(TopkwStats)]),
     "ii2_topkw_word": (C.c_int, [C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32, u32p]),
     "ii2_topkw_plan": (C.c_int, [C.c_uint64, u32p, u64p, C.c_uint32, C.c_uint32, u32p, u32p, u64p, u8p, u32p]),
+    "ii2_topk_batch": (C.c_int, [vp, C.c_uint64, u64p, u64p, u8p, u32p, u32p, u32p, vpp, u64p, u64p, vp, vp, vp, C.c_uint64, u64p, u64p,
+                                 C.POINTER(TopkBatchStats)]),
+    "ii2_topk_batch_run": (C.c_int, [u8p, C.c_uint32, C.c_uint32, u8p, u32p, u32p]),
+    "ii2_topk_batch_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, u32p, u64p]),
     "ii2_merge_host": (C.c_int, [vp, C.c_uint32, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(MergeStats)]),
     "ii2_intersect_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "ii2_union_host": (C.c_int, [vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]),

@@ -130,6 +130,7 @@ struct ii2_ctx {
     int64_t opt_batch_small = 1;        // ii2_query_batch: small queries share the batch kernel (0: every query through the single-query paths)
     int64_t opt_batch_tiny = 1;         // ... of both entry points: those of <= 2048 postings in <= 32 blocks in the 256-thread form (0: all in the 1024-thread one)
     int64_t opt_batch_groups = 1;       // ii2_query_batch_groups: queries that fit share its batch kernel (0: every query through ii2_andnot_ranges' paths)
+    int64_t opt_batch_topk = 1;         // ii2_topk_batch: queries that fit share its batch kernel (0: every query through ii2_topk_weighted_ranges' form)
     uint8_t *d_batch = nullptr;         // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
     size_t batch_cap = 0;
     void *h_batch = nullptr;            // pinned: the descriptor table on its way up, the offsets on their way down (grow-only)
@@ -400,6 +401,19 @@ struct GroupBatchParams {
 };
 hipError_t launch_setop_groups_batch(const GroupBatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 uint32_t setop_groups_batch_forms(const GroupBatchParams &p);      // the forms of its kernel that launch runs (BATCH_FORM_*)
+
+// many short ranked queries in one launch (topk_batch.hip): the grouped batch's table - n_req the required groups with postings,
+// bound = min(k, their postings) - plus, parallel to it, one weight byte per list (its group's; an excluded list's is unused)
+// and min_score per query of the table.  The ranked ids go to stage + stage_off, their scores to stage_scores + stage_off, the
+// count (at most bound) to cnt[slot] and the number of eligible docs to eligible[slot].
+struct TopkBatchParams {
+    GroupBatchParams g;
+    const uint8_t *weight;       // [lists of the table]
+    const uint32_t *min_score;   // [n_tiny + n_small], in the table's order
+    uint32_t *stage_scores;
+    uint32_t *eligible;          // [queries of the batch]
+};
+hipError_t launch_topk_batch(const TopkBatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // OR of a few medium-size lists by ranking (union_rank.hip)
 constexpr uint32_t UNION_RANK_MAXL = 8;

@@ -25,6 +25,9 @@
 //   Many AND-of-ORs / NOT queries in one call (ii2_query_batch_groups): every query an ii2_andnot_ranges call - those that fit
 //        one workgroup in one launch per size class (setop_groups_batch.hip), the others one by one through that entry point's
 //        paths; staged and packed by the same code as the flat batch.
+//   Many ranked queries in one call (ii2_topk_batch): every query an ii2_topk_weighted_ranges call - those that fit one workgroup
+//        in one launch per size class (topk_batch.hip), the others one by one through that entry point's form; ids and scores
+//        staged and packed by the same code as the flat batch.
 // The file is in that order, every section closed by its entry points (those of the AND and the OR chooser together, behind the
 // OR section: each of the two is also called by the sections below), the helpers that several sections share in front.
 #include <algorithm>
@@ -34,6 +37,7 @@
 
 #include "atleast_count.h"
 #include "internal.h"
+#include "topk_batch_run.h"
 #include "topk_count.h"
 
 using namespace ii2;
@@ -2056,27 +2060,39 @@ static int topk_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t 
     return II2_OK;
 }
 
-// ii2_topk_weighted_ranges: ii2_topk_ranges' checks and plan with a weight per counted group, then the same ranked form
-static int topkw_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, const uint32_t *group_weight,
-                                 uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
-                                 const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topkw_stats *stats) {
-    static const char who[] = "ii2_topk_weighted_ranges";
+// The checks and the plan of the weighted ranked query - ii2_topk_ranges' with a weight per counted group - under the name `who`:
+// ii2_topk_weighted_ranges and every query of ii2_topk_batch go through here, so the two entry points reject the same things
+// with the same codes.  weights: those of Q.req (plan_atleast), *total their sum W'.
+static int topkw_plan(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, const uint32_t *group_weight,
+                      uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q,
+                      std::vector<uint64_t> &kept, std::vector<uint32_t> &weights, uint64_t *total) {
     const std::string name(who);
     if (!min_score) return fail(ctx, II2_EINVAL, (name + ": min_score is 0").c_str());
     if (k > II2_TOPK_MAX) return fail(ctx, II2_ERANGE, (name + ": k above II2_TOPK_MAX (ii2_atleast_ranges returns every doc)").c_str());
-    GroupQuery Q;
-    std::vector<uint64_t> kept;
-    std::vector<uint32_t> weights;
     if (int rc = plan_atleast(ctx, who, n_groups, group_first, group_not, segs, list_first, list_end, Q, kept, group_weight, &weights)) return rc;
     for (uint64_t g = 0; group_weight && g < n_groups; g++) {
         if (group_not && group_not[g]) continue;                            // an excluded group's weight is ignored
         if (!group_weight[g]) return fail(ctx, II2_EINVAL, (name + ": required group " + std::to_string(g) + " has weight 0 (drop the group instead)").c_str());
         if (group_weight[g] > 255) return fail(ctx, II2_ERANGE, (name + ": the weight of required group " + std::to_string(g) + " is above 255").c_str());
     }
-    const size_t n1 = Q.req.size();
+    *total = 0;
+    for (uint32_t w : weights) *total += w;
+    if (*total > 255) return fail(ctx, II2_ERANGE, (name + ": the weights of the required groups with postings sum to more than 255 (the scores are exact 8-bit values)").c_str());
+    return II2_OK;
+}
+
+// ii2_topk_weighted_ranges: the plan above, then ii2_topk_ranges' ranked form
+static int topkw_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not, const uint32_t *group_weight,
+                                 uint32_t min_score, uint64_t k, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t *count, uint64_t *hist, ii2_topkw_stats *stats) {
+    static const char who[] = "ii2_topk_weighted_ranges";
+    const std::string name(who);
+    GroupQuery Q;
+    std::vector<uint64_t> kept;
+    std::vector<uint32_t> weights;
     uint64_t total = 0;
-    for (uint32_t w : weights) total += w;
-    if (total > 255) return fail(ctx, II2_ERANGE, (name + ": the weights of the required groups with postings sum to more than 255 (the scores are exact 8-bit values)").c_str());
+    if (int rc = topkw_plan(ctx, who, n_groups, group_first, group_not, group_weight, min_score, k, segs, list_first, list_end, Q, kept, weights, &total)) return rc;
+    const size_t n1 = Q.req.size();
     ii2_topkw_stats st;
     std::memset(&st, 0, sizeof st);
     st.n_counted = n1;
@@ -2284,30 +2300,44 @@ struct BatchMem {
     uint32_t *d_stage;
     uint64_t *h_soff;            // [nq] every query's staging slot
     uint32_t *h_cnt;             // [nq + 1] the counts of the queries that no batch kernel answers (theirs: 0); [nq] = 0
+    // ranked (ii2_topk_batch) only: the eligible words [nq] close the block that travels up, so they sit right in front of the
+    // offsets and come down with them in one copy; the scores are staged in a second region of the staging's size
+    size_t o_elig;
+    uint32_t *d_stage_scores;
+    uint32_t *h_elig;            // [nq] filled like h_cnt
 };
 }  // namespace
-static int batch_blocks(ii2_ctx *ctx, size_t table_bytes, uint64_t nq, uint64_t stage_ids, BatchMem *m) {
+static int batch_blocks(ii2_ctx *ctx, size_t table_bytes, uint64_t nq, uint64_t stage_ids, BatchMem *m, bool ranked = false) {
     m->o_soff = table_bytes;
     m->o_cnt = m->o_soff + align_up(nq * sizeof(uint64_t));
-    m->up_bytes = m->o_cnt + align_up((nq + 1) * sizeof(uint32_t));
+    m->o_elig = m->o_cnt + align_up((nq + 1) * sizeof(uint32_t));
+    m->up_bytes = m->o_elig + (ranked ? align_up(nq * sizeof(uint32_t)) : 0);
     const size_t off_bytes = align_up((nq + 1) * sizeof(uint64_t));
     m->scan_tmp = scan_temp_bytes(nq + 1);
     m->o_off = m->up_bytes;
     m->o_scan = m->o_off + off_bytes;
     m->o_stage = m->o_scan + m->scan_tmp;
-    if (int rc = batch_reserve(ctx, m->o_stage + align_up((stage_ids + 4) * sizeof(uint32_t)), m->up_bytes + off_bytes)) return rc;
+    const size_t stage_bytes = align_up((stage_ids + 4) * sizeof(uint32_t));
+    if (int rc = batch_reserve(ctx, m->o_stage + (ranked ? 2 : 1) * stage_bytes, m->up_bytes + off_bytes)) return rc;
     m->h = (uint8_t *)ctx->h_batch;
     m->d = ctx->d_batch;
     m->d_stage = (uint32_t *)(m->d + m->o_stage);
+    m->d_stage_scores = ranked ? (uint32_t *)(m->d + m->o_stage + stage_bytes) : nullptr;
     m->h_soff = (uint64_t *)(m->h + m->o_soff);
     m->h_cnt = (uint32_t *)(m->h + m->o_cnt);
+    m->h_elig = ranked ? (uint32_t *)(m->h + m->o_elig) : nullptr;
     return II2_OK;
 }
 
 // The end of a batch call, behind its batch kernels: counts -> offsets, pack (tests the capacity on the device), offsets down;
 // the call's one wait.  `who` names the entry point in the message.
+// ranked (ii2_topk_batch; blocks made with batch_blocks' ranked = true, no path counted): a second pack moves the staged scores
+// to d_scores (may be NULL) at the same offsets, and the eligible words come down with the offsets into eligible (may be NULL).
+namespace {
+struct BatchRanked { uint32_t *d_scores; uint64_t *eligible; };
+}  // namespace
 static int batch_finish(ii2_ctx *ctx, const char *who, Path pack, const BatchMem &m, uint64_t nq, uint64_t max_bound, uint32_t *d_out, uint64_t cap,
-                        uint64_t *out_off) {
+                        uint64_t *out_off, const BatchRanked *ranked = nullptr) {
     hipStream_t st = ctx->stream;
     uint8_t *d = m.d;
     HIP_TRY(ctx, scan_excl_u32_to_u64(d + m.o_scan, m.scan_tmp, (const uint32_t *)(d + m.o_cnt), (uint64_t *)(d + m.o_off), nq + 1, st));
@@ -2322,13 +2352,21 @@ static int batch_finish(ii2_ctx *ctx, const char *who, Path pack, const BatchMem
     {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
-        took(ctx, pack);
+        if (!ranked) took(ctx, pack);
         HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st, e0, e1));
     }
+    if (ranked && ranked->d_scores) {
+        pp.stage = m.d_stage_scores;
+        pp.out = ranked->d_scores;
+        HIP_TRY(ctx, launch_batch_pack(pp, max_bound, st));
+    }
     uint64_t *h_off = (uint64_t *)(m.h + m.up_bytes);
-    HIP_TRY(ctx, hipMemcpyAsync(h_off, d + m.o_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (ranked) HIP_TRY(ctx, hipMemcpyAsync(m.h + m.o_elig, d + m.o_elig, m.o_off - m.o_elig + (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    else HIP_TRY(ctx, hipMemcpyAsync(h_off, d + m.o_off, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     std::memcpy(out_off, h_off, (nq + 1) * sizeof(uint64_t));
+    if (ranked && ranked->eligible)
+        for (uint64_t q = 0; q < nq; q++) ranked->eligible[q] = m.h_elig[q];
     if (out_off[nq] > cap)
         return fail(ctx, II2_ECAPACITY, (std::string(who) + ": the results do not fit the output buffer (nothing written; out_off holds the sizes)").c_str());
     return II2_OK;
@@ -2628,6 +2666,205 @@ extern "C" int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const ui
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return query_batch_groups_unlocked(ctx, n_queries, query_first, group_first, group_not, segs, list_first, list_end, tomb, d_out, cap, out_off);
+}
+
+// ---- many ranked queries in one call ------------------------------------------------------------
+// The form a planned ranked query takes in a batch: n_lists counted lists (for_each_counted_list; `fits`: the walk saw every one)
+// of n_post postings in n_blocks blocks, n_counted required groups with postings.  The host planner and ii2_topk_batch_plan call it.
+static_assert(BP_EMPTY == II2_TOPK_BATCH_EMPTY && BP_TINY == II2_TOPK_BATCH_TINY && BP_SMALL == II2_TOPK_BATCH_SMALL && BP_LARGE == II2_TOPK_BATCH_SINGLE,
+              "ii2_topk_batch_plan reports the planner's kinds");
+static uint8_t topk_batch_form(bool fits, uint64_t n_lists, uint64_t n_post, uint64_t n_blocks, uint64_t n_counted, int64_t opt_topk, int64_t opt_tiny) {
+    if (!n_counted) return BP_EMPTY;
+    if (!opt_topk || !fits || n_counted > MAX_LISTS || n_lists > MAX_LISTS || n_post > SMALL_SET_POSTINGS || n_blocks > SMALL_SET_BLOCKS) return BP_LARGE;
+    return opt_tiny && n_blocks <= BATCH_TINY_BLOCKS && n_post <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
+}
+static uint64_t topk_batch_bound(uint64_t n_counted, uint64_t req_post, uint64_t k) { return n_counted ? std::min(k, req_post) : 0; }
+
+// Query q owns the groups query_first[q] .. query_first[q + 1] - 1 of an ii2_topk_weighted_ranges call; its result is that call's.
+// Every query is planned as that call plans it (topkw_plan, for_each_counted_list); what differs is where a short query runs.
+static int topk_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_first, const uint64_t *group_first, const uint8_t *group_not,
+                               const uint32_t *group_weight, const uint32_t *min_score, const uint32_t *k, const ii2_seg *const *segs,
+                               const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t cap,
+                               uint64_t *out_off, uint64_t *eligible, ii2_topk_batch_stats *stats) {
+    const char *const who = "ii2_topk_batch";
+    const std::string w(who);
+    if (nq == 0) {
+        out_off[0] = 0;
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return II2_OK;
+    }
+    if (!query_first || !k) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
+    if (!d_ids && cap) return fail(ctx, II2_EINVAL, (w + ": output buffer is NULL").c_str());
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": the tombstones live on another device").c_str());
+    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, (w + ": query " + std::to_string(q) + ": " + what).c_str()); };
+    // a helper's message "<entry point>: ..." gets the query's index behind the name (built on the error path only)
+    auto named = [&](uint64_t q, int rc) {
+        if (ctx->err.compare(0, w.size() + 2, w + ": ") == 0) ctx->err.insert(w.size(), ": query " + std::to_string(q));
+        return rc;
+    };
+    if (query_first[0] != 0) return bad(0, "query_first does not ascend from 0");
+    for (uint64_t q = 0; q < nq; q++)
+        if (query_first[q + 1] < query_first[q]) return bad(q, "query_first does not ascend from 0");
+    if (query_first[nq] && !group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (query_first[nq] && group_first[0] != 0) return bad(0, "group_first does not ascend from 0");
+    // 1. every query checked and sized before anything is launched
+    std::vector<BatchPlan> plan(nq);
+    std::vector<BatchList> tl;             // the table's lists, their tags and their groups' weights, the queries in batch order
+    std::vector<uint8_t> tt, tw;
+    GroupQuery gq;
+    std::vector<uint64_t> kept;
+    std::vector<uint32_t> weights;
+    uint64_t stage_ids = 0, max_bound = 0;
+    uint32_t n_kind[4] = {0, 0, 0, 0};
+    for (uint64_t q = 0; q < nq; q++) {
+        const uint64_t g0 = query_first[q], ng = query_first[q + 1] - g0;
+        const uint32_t ms = min_score ? min_score[q] : 1u;
+        BatchPlan &pl = plan[q];
+        pl = BatchPlan{0, stage_ids, tl.size(), 0, 0, BP_EMPTY, 0, 0};
+        gq.rs.clear();                      // (plan_atleast appends)
+        gq.rx.clear();
+        gq.all.clear();
+        gq.req.clear();
+        kept.clear();
+        weights.clear();
+        uint64_t total = 0;
+        if (int rc = topkw_plan(ctx, who, ng, group_first + g0, group_not ? group_not + g0 : nullptr, group_weight ? group_weight + g0 : nullptr, ms, k[q],
+                                segs, list_first, list_end, gq, kept, weights, &total))
+            return named(q, rc);
+        if (gq.empty || ms > total) { n_kind[BP_EMPTY]++; continue; }
+        uint64_t req_post = 0;
+        for (const GroupIn &G : gq.req) req_post += G.n_post;
+        pl.bound = topk_batch_bound(gq.req.size(), req_post, k[q]);
+        // A query takes the batch kernel when the lists that count fit one workgroup (for_each_counted_list), with at most
+        // MAX_LISTS tags for its required groups.  As in ii2_query_batch_groups the walk mirrors the excluded segments' counts
+        // itself, and no postings x lists bound applies: the alternative is the single form's waits once per query.
+        Counted t{0, 0, 0, false, II2_OK};
+        if (ctx->opt_batch_topk && gq.req.size() <= MAX_LISTS) {
+            t = for_each_counted_list(ctx, gq, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &) {
+                const uint32_t b0 = s->h_blk_off[j];
+                tl.push_back(BatchList{s->d_skip + b0, s->d_payload, s->h_blk_off[j + 1] - b0, s->h_cnt[j]});
+                tt.push_back((uint8_t)tag);
+                tw.push_back(tag < weights.size() ? (uint8_t)weights[tag] : (uint8_t)0);
+            });
+            if (t.rc) return t.rc;
+        }
+        pl.kind = topk_batch_form(t.fits, t.m, t.sum, t.nb, gq.req.size(), ctx->opt_batch_topk, ctx->opt_batch_tiny);
+        if (pl.kind == BP_LARGE) {
+            tl.resize(pl.l0);
+            tt.resize(pl.l0);
+            tw.resize(pl.l0);
+        } else {
+            pl.nl = t.m;
+            pl.n_blocks = t.nb;
+            pl.n_req = (uint8_t)gq.req.size();
+        }
+        n_kind[pl.kind]++;
+        stage_ids += pl.bound;
+        max_bound = std::max(max_bound, pl.bound);
+        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": the result bounds of the queries add up to 2^32 ids or more").c_str());
+    }
+    const ii2_topk_batch_stats bst{n_kind[BP_TINY], n_kind[BP_SMALL], n_kind[BP_LARGE], n_kind[BP_EMPTY], stage_ids};
+    // 2. the blocks: [queries | lists | tags | weights | min_scores | staging offsets | counts | eligible] travel up in one copy
+    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
+    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
+    const size_t o_weights = o_tags + align_up(tt.size()), o_ms = o_weights + align_up(tw.size());
+    BatchMem m;
+    if (int rc = batch_blocks(ctx, o_ms + align_up((size_t)n_table * sizeof(uint32_t)), nq, stage_ids, &m, true)) return rc;
+    BatchQuery *hq = (BatchQuery *)m.h;
+    uint32_t *hms = (uint32_t *)(m.h + o_ms);
+    if (!tl.empty()) {
+        std::memcpy(m.h + o_lists, tl.data(), tl.size() * sizeof(BatchList));
+        std::memcpy(m.h + o_tags, tt.data(), tt.size());
+        std::memcpy(m.h + o_weights, tw.data(), tw.size());
+    }
+    // 3. the queries that do not fit, one after the other through ii2_topk_weighted_ranges' form, ids and scores straight into their
+    // staging slots (each with that form's own waits)
+    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY];
+    for (uint64_t q = 0; q < nq; q++) {
+        const BatchPlan &pl = plan[q];
+        const uint32_t ms = min_score ? min_score[q] : 1u;
+        m.h_soff[q] = pl.stage_off;
+        m.h_cnt[q] = 0;
+        m.h_elig[q] = 0;
+        if (pl.kind == BP_EMPTY) continue;
+        if (pl.kind == BP_LARGE) {
+            const uint64_t g0 = query_first[q];
+            uint64_t count = 0;
+            ii2_topkw_stats ws;
+            const int rc = topkw_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr,
+                                                 group_weight ? group_weight + g0 : nullptr, ms, k[q], segs, list_first, list_end, tomb,
+                                                 m.d_stage + pl.stage_off, m.d_stage_scores + pl.stage_off, &count, nullptr, &ws);
+            if (rc) {
+                ctx->err = w + ": query " + std::to_string(q) + ": " + ctx->err;
+                return rc;
+            }
+            m.h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
+            m.h_elig[q] = (uint32_t)std::min<uint64_t>(ws.n_eligible, 0xFFFFFFFFull);
+            continue;
+        }
+        const uint32_t at = pl.kind == BP_TINY ? at_tiny++ : at_small++;
+        hq[at] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
+        hms[at] = ms;
+    }
+    m.h_cnt[nq] = 0;
+    // 4. table up, the queries that fit in one launch per size class, then the flat batch's scan, pack (ids, then scores) and wait
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemcpyAsync(m.d, m.h, m.up_bytes, hipMemcpyHostToDevice, st));
+    if (n_table) {
+        TopkBatchParams tp;
+        std::memset(&tp, 0, sizeof tp);
+        tp.g.b.queries = (const BatchQuery *)m.d;
+        tp.g.b.lists = (const BatchList *)(m.d + o_lists);
+        tp.g.tag = m.d + o_tags;
+        tp.weight = m.d + o_weights;
+        tp.min_score = (const uint32_t *)(m.d + o_ms);
+        set_tomb(tp.g.b, tomb);
+        tp.g.b.n_tiny = n_kind[BP_TINY];
+        tp.g.b.n_small = n_kind[BP_SMALL];
+        tp.g.b.stage = m.d_stage;
+        tp.g.b.cnt = (uint32_t *)(m.d + m.o_cnt);
+        tp.stage_scores = m.d_stage_scores;
+        tp.eligible = (uint32_t *)(m.d + m.o_elig);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_topk_batch(tp, st, e0, e1));
+    }
+    const BatchRanked ranked{d_scores, eligible};
+    const int rc = batch_finish(ctx, who, P_COUNT, m, nq, max_bound, d_ids, cap, out_off, &ranked);
+    if (stats && (rc == II2_OK || rc == II2_ECAPACITY)) *stats = bst;
+    return rc;
+}
+
+extern "C" int ii2_topk_batch(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first, const uint8_t *group_not,
+                              const uint32_t *group_weight, const uint32_t *min_score, const uint32_t *k, const ii2_seg *const *segs,
+                              const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_ids, uint32_t *d_scores, uint64_t cap,
+                              uint64_t *out_off, uint64_t *eligible, ii2_topk_batch_stats *stats) {
+    if (!ctx || !out_off) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return topk_batch_unlocked(ctx, n_queries, query_first, group_first, group_not, group_weight, min_score, k, segs, list_first, list_end, tomb, d_ids,
+                               d_scores, cap, out_off, eligible, stats);
+}
+
+// host only: the batch kernel's run rule
+extern "C" int ii2_topk_batch_run(const uint8_t *tags, uint32_t n_tags, uint32_t n_req, const uint8_t *weights, uint32_t *score, uint32_t *excluded) {
+    if (!tags || !weights || !score || !excluded || !n_tags || n_tags > MAX_LISTS + 1 || n_req > MAX_LISTS) return II2_EINVAL;
+    for (uint32_t i = 0; i < n_tags; i++)
+        if (tags[i] > n_req) return II2_EINVAL;
+    bool ex = false;
+    *score = tb_run_score([&](uint32_t i) { return i < n_tags ? (uint32_t)tags[i] : TB_RUN_END; }, [&](uint32_t t) { return (uint32_t)weights[t]; }, n_req, &ex);
+    *excluded = ex ? 1u : 0u;
+    return II2_OK;
+}
+
+// host only: the form and the bound the planner above gives a query
+extern "C" int ii2_topk_batch_plan(uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_counted, uint64_t req_postings, uint64_t k,
+                                   int64_t batch_topk, int64_t batch_tiny, uint32_t *form, uint64_t *bound) {
+    if (!form || !bound) return II2_EINVAL;
+    *form = topk_batch_form(true, n_lists, n_postings, n_blocks, n_counted, batch_topk, batch_tiny);
+    *bound = topk_batch_bound(n_counted, req_postings, k);
+    return II2_OK;
 }
 
 extern "C" {

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -114,6 +114,23 @@ def pack_group_batch(queries):
         query_first[q + 1] = len(group_not)
     return (query_first, np.array(group_first, np.uint64), np.array(group_not, np.uint8), segs, np.array(first, np.uint64),
             np.array(end, np.uint64))
+
+
+def pack_topk_batch(queries):
+    """The flat arrays ii2_topk_batch takes, from queries = [(groups, weights | None, k, min_score, exclude), ...] with groups /
+    exclude as pack_andnot takes them and one weight per group of `groups`: pack_group_batch's six arrays for [(groups, exclude),
+    ...], then (group_weight u32 [G] - None when no query has weights, else 1 for the groups of a query without and for every
+    excluded group, whose entry the library ignores -, min_score u32 [Q], k u32 [Q]).  Pure host code."""
+    packed = pack_group_batch([(groups, exclude) for groups, _, _, _, exclude in queries])
+    weight = []
+    for q, (groups, weights, _, _, exclude) in enumerate(queries):
+        groups = list(groups)
+        if weights is not None and len(weights) != len(groups):
+            raise ValueError(f"query {q}: one weight per group")
+        weight += [int(w) for w in weights] if weights is not None else [1] * len(groups)
+        weight += [1] * len(list(exclude))
+    group_weight = None if all(w is None for _, w, _, _, _ in queries) else np.array(weight, np.uint32)
+    return packed + (group_weight, np.array([int(m) for _, _, _, m, _ in queries], np.uint32), np.array([int(k) for _, _, k, _, _ in queries], np.uint32))
 
 
 def path_names():
@@ -592,6 +609,30 @@ class Context:
                                                  end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None, _ptr(out), out.count,
                                                  off.ctypes.data_as(_lib.u64p)))
         return out, off
+
+    def topk_batch(self, queries, tomb: Optional["Tombstones"] = None, stats: bool = False, out: Optional[tuple] = None):
+        """Many ranked queries in one call (ii2_topk_batch): queries = [(groups, weights | None, k, min_score, exclude), ...], each
+        as topk_weighted_ranges takes it.  Returns (DeviceArray ids, DeviceArray scores, offsets, eligible), with stats=True also
+        TopkBatchStats: result q is ids / scores[offsets[q] : offsets[q + 1]], eligible[q] its number of eligible docs.  The default
+        `out` holds sum(k) entries each; `out` = (ids, scores) DeviceArrays to write into instead, scores may be None."""
+        query_first, group_first, group_not, qsegs, first, end, weight, min_score, k = pack_topk_batch(queries)
+        n = len(qsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in qsegs])
+        if out is None:
+            cap = max(int(k.sum(dtype=np.uint64)), 1)
+            out = (self.empty(cap), self.empty(cap))
+        ids, scores = out
+        if scores is not None and scores.count < ids.count:
+            raise ValueError("topk_batch: scores holds fewer entries than ids")
+        off = np.zeros(len(queries) + 1, np.uint64)
+        eligible = np.zeros(len(queries), np.uint64)
+        st = TopkBatchStats()
+        self._ck(self.lib.ii2_topk_batch(self.h, len(queries), query_first.ctypes.data_as(_lib.u64p), group_first.ctypes.data_as(_lib.u64p),
+                                         group_not.ctypes.data_as(_lib.u8p), None if weight is None else weight.ctypes.data_as(_lib.u32p),
+                                         min_score.ctypes.data_as(_lib.u32p), k.ctypes.data_as(_lib.u32p), segs, first.ctypes.data_as(_lib.u64p),
+                                         end.ctypes.data_as(_lib.u64p), tomb.h if tomb else None, _ptr(ids), _ptr(scores), ids.count,
+                                         off.ctypes.data_as(_lib.u64p), eligible.ctypes.data_as(_lib.u64p), C.byref(st)))
+        return (ids, scores, off, eligible, st) if stats else (ids, scores, off, eligible)
 
     def count_ranges(self, ranges, dset: Optional[DeviceArray] = None, n_set: Optional[int] = None,
                      tomb: Optional["Tombstones"] = None):

@@ -67,6 +67,7 @@ def _lib_typed():
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_intersect_top_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
         lib.ii2h_term_counts.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_count_term_len.restype = C.c_uint64
@@ -198,7 +199,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectMany, TermCounts)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -290,6 +291,33 @@ class InvertedIndex(_Target):
         self._ck(self.lib.ii2h_intersect_batch(self.h, blob.ctypes.data, off.ctypes.data, q_first.ctypes.data, q_req.ctypes.data, len(queries),
                                                C.byref(n)))
         return [vals for _, vals in self._results(n.value)]
+
+    def intersect_top_batch(self, queries) -> List[List[Tuple[int, int]]]:
+        """Many intersect_top_weighted queries, queries = [(terms, weights, k, min_score, exclude), ...], in one device call
+        (IntersectTopBatch: one ii2_topk_batch call - a second one when the results exceed its first buffer - and one download);
+        result q is that of intersect_top_weighted(*queries[q])."""
+        queries = [(list(t), list(w), int(k), int(m), list(x)) for t, w, k, m, x in queries]
+        for q, (t, w, _, _, _) in enumerate(queries):
+            if len(w) != len(t):
+                raise ValueError(f"intersect_top_batch: query {q}: one weight per term")
+        blob, off = _pack([term for t, _, _, _, x in queries for term in t + x])
+        q_first = np.zeros(len(queries) + 1, np.uint64)
+        q_first[1:] = np.cumsum([len(t) + len(x) for t, _, _, _, x in queries], dtype=np.uint64) if queries else []
+        q_req = np.array([len(t) for t, _, _, _, _ in queries], np.uint64)
+        w = np.asarray([x for _, ws, _, _, _ in queries for x in ws] + [0], np.uint32)
+        k = np.asarray([k for _, _, k, _, _ in queries] + [0], np.uint64)
+        m = np.asarray([m for _, _, _, m, _ in queries] + [0], np.uint32)
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_intersect_top_batch(self.h, blob.ctypes.data, off.ctypes.data, q_first.ctypes.data, q_req.ctypes.data, w.ctypes.data,
+                                                   k.ctypes.data, m.ctypes.data, len(queries), C.byref(n)))
+        ids = [vals for _, vals in self._results(n.value)]
+        scores = np.zeros(max(sum(len(v) for v in ids), 1), np.uint32)
+        self.lib.ii2h_scores_copy(self.h, scores.ctypes.data)
+        out, at = [], 0
+        for v in ids:
+            out.append(list(zip(v, scores[at:at + len(v)].tolist())))
+            at += len(v)
+        return out
 
     def term_counts(self, prefix: bytes, terms: List[bytes] = (), exclude: List[bytes] = ()) -> Dict[bytes, int]:
         """Facet counts (TermCounts: the filter stays on the device, one ii2_count_ranges call over the prefix's run of every

@@ -20,6 +20,7 @@
 //   IntersectAtLeast(terms, min_match, except)       additive: the ids under at least min_match of the terms, minus the excluded terms
 //   IntersectTop(terms, k, min_match, except)        additive: the k ids under the most of the terms, with their scores, in rank order
 //   IntersectTopWeighted(terms, weights, k, min_score, except)   additive: the same with a weight per term, the score their sum
+//   IntersectTopBatch(queries)                       additive: many IntersectTopWeighted queries in one device call
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //
@@ -993,6 +994,78 @@ class InvertedIndex {
         for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
         return out;
     }
+    // additive: MANY IntersectTopWeighted queries in one ii2_topk_batch call - a second one when the results exceed FIRST_CAP
+    // entries - and one download; result q is that of IntersectTopWeighted(queries[q]...).  Per query the groups are built exactly
+    // as IntersectTopWeighted builds them; a query none of whose terms is in a segment keeps its place without a group - its
+    // result is empty, the call goes on.  The library takes result bounds below 2^32 ids per call (II2_ERANGE beyond).
+    struct TopQuery {
+        std::vector<Term> terms;
+        std::vector<uint32_t> weights;
+        uint64_t k;
+        uint32_t min_score;
+        std::vector<Term> except;
+    };
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> IntersectTopBatch(const std::vector<TopQuery> &queries) const {
+        std::vector<std::vector<std::pair<uint32_t, uint32_t>>> out(queries.size());
+        if (queries.empty()) return out;
+        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
+        std::vector<uint64_t> query_first{0}, group_first{0}, first, end;
+        std::vector<uint8_t> group_not;
+        std::vector<uint32_t> group_weight, min_score, ks;
+        std::vector<const ii2_seg *> segs;
+        constexpr uint64_t FIRST_CAP = 1u << 22;
+        uint64_t total = 0;
+        for (size_t q = 0; q < queries.size(); q++) {
+            const TopQuery &Q = queries[q];
+            const std::string who = "intersect top batch: query " + std::to_string(q);
+            if (!Q.min_score) throw std::runtime_error(who + ": min_score is 0");
+            if (Q.weights.size() != Q.terms.size()) throw std::runtime_error(who + ": one weight per term");
+            if (Q.k > II2_TOPK_MAX) throw std::runtime_error(who + ": k above II2_TOPK_MAX");
+            Filter f;
+            std::vector<uint64_t> posts;                         // the postings bounds of the terms that some segment holds
+            filter_build(Q.terms, Q.except, f, &posts);
+            min_score.push_back(Q.min_score);
+            ks.push_back((uint32_t)Q.k);
+            if (!posts.empty() && Q.k) {
+                const uint64_t r0 = segs.size();
+                held.insert(held.end(), f.held.begin(), f.held.end());
+                segs.insert(segs.end(), f.segs.begin(), f.segs.end());
+                first.insert(first.end(), f.first.begin(), f.first.end());
+                end.insert(end.end(), f.end.begin(), f.end.end());
+                for (size_t g = 0; g < f.group_not.size(); g++) {
+                    group_first.push_back(r0 + f.group_first[g + 1]);
+                    group_not.push_back(f.group_not[g]);
+                    group_weight.push_back(g < Q.weights.size() ? Q.weights[g] : 0u);    // (the excluded groups follow the terms)
+                }
+                uint64_t post = 0;
+                for (uint64_t p : posts) post += p;
+                total += std::min(Q.k, post);
+            }
+            query_first.push_back(group_not.size());
+        }
+        std::vector<uint64_t> off(queries.size() + 1, 0);
+        uint64_t cap = std::max<uint64_t>(std::min(total, FIRST_CAP), 1);
+        DevMem d_out(ctx_);                                      // ids [0, cap), then scores [cap, 2 cap)
+        for (int attempt = 0;; attempt++) {
+            ck(ctx_, ii2_dev_alloc(ctx_, 2 * cap * sizeof(uint32_t), &d_out.p), "intersect top batch");
+            const int rc = ii2_topk_batch(ctx_, queries.size(), query_first.data(), group_first.data(), group_not.data(), group_weight.data(),
+                                          min_score.data(), ks.data(), segs.data(), first.data(), end.data(), nullptr, (uint32_t *)d_out.p,
+                                          (uint32_t *)d_out.p + cap, cap, off.data(), nullptr, nullptr);
+            if (rc != II2_ECAPACITY || attempt) {
+                ck(ctx_, rc, "intersect top batch");
+                break;
+            }
+            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect top batch");
+            d_out.p = nullptr;
+            cap = off.back();
+        }
+        const uint64_t n = off.back();
+        std::vector<uint32_t> raw(n ? cap + n : 0);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top batch");
+        for (size_t q = 0; q < queries.size(); q++)
+            for (uint64_t i = off[q]; i < off[q + 1]; i++) out[q].push_back({raw[i], raw[cap + i]});
+        return out;
+    }
    private:
     // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
     // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
@@ -1524,6 +1597,34 @@ int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *o
         }
         t->result.clear();
         for (auto &ids : t->index->IntersectMany(queries)) t->result.push_back(TermValues{Term(), std::move(ids)});
+        *n_results = t->result.size();
+    })
+}
+// n_q ranked queries over the terms (bytes, off), owned and split as ii2h_intersect_batch's; weights: one per REQUIRED term, query after
+// query; k and min_score: one per query.  Result q: the ids in the values of the target's result q (its term is empty), the scores of
+// all results back to back in the target's scores
+int ii2h_intersect_top_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req,
+                             const uint32_t *weights, const uint64_t *k, const uint32_t *min_score, uint64_t n_q, uint64_t *n_results) {
+    H_TRY(t, {
+        const std::vector<Term> terms = unpack_terms(bytes, off, n_q ? q_first[n_q] : 0);
+        std::vector<InvertedIndex::TopQuery> queries(n_q);
+        uint64_t w0 = 0;
+        for (uint64_t q = 0; q < n_q; q++) {
+            const uint64_t a = q_first[q], m = std::min(a + q_req[q], q_first[q + 1]);
+            queries[q].terms.assign(terms.begin() + a, terms.begin() + m);
+            queries[q].except.assign(terms.begin() + m, terms.begin() + q_first[q + 1]);
+            queries[q].weights.assign(weights + w0, weights + w0 + (m - a));
+            w0 += m - a;
+            queries[q].k = k[q];
+            queries[q].min_score = min_score[q];
+        }
+        t->result.clear();
+        t->scores.clear();
+        for (auto &top : t->index->IntersectTopBatch(queries)) {
+            TermValues tv{Term(), {}};
+            for (auto &p : top) { tv.values.push_back(p.first); t->scores.push_back(p.second); }
+            t->result.push_back(std::move(tv));
+        }
         *n_results = t->result.size();
     })
 }
