@@ -1351,10 +1351,12 @@ struct GroupQuery {
     bool empty;                             // no group, a required group without blocks, or required spans that do not overlap
 };
 
-// Everything checked before anything is launched or written; `who` names the entry point in the messages, `per` what its block
-// limit counts over ("call" | "query").  group_not == NULL: every group is required.  Q's vectors keep their storage between calls.
-// (Inlined into its two callers, like the walk below: out of line they cost the batch 6 ns per query, 3 % at six lists a query.)
-__attribute__((always_inline)) static inline int plan_groups(ii2_ctx *ctx, const char *who, const char *per, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+// The opening of every plan (plan_groups, plan_atleast): Q reset, then everything that is checked before anything is launched or
+// written, and the groups collected into Q.rs / Q.all.  `who` names the entry point in the messages, `per` what its block limit
+// counts over ("call" | "query").  group_not == NULL: every group is required.  Q's vectors keep their storage between calls.
+// (Inlined into its callers, and they into theirs, like the walk below: out of line they cost the batch 6 ns per query, 3 % at six
+// lists a query.)
+__attribute__((always_inline)) static inline int plan_open(ii2_ctx *ctx, const char *who, const char *per, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
                        const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q) {
     Q.rs.clear();
     Q.rx.clear();
@@ -1375,6 +1377,14 @@ __attribute__((always_inline)) static inline int plan_groups(ii2_ctx *ctx, const
     if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, Q.rs, Q.all, &n_blocks)) return rc;
     if (n_blocks >= 0xFFFFFFFFull || Q.rs.size() >= 0xFFFFFFFFull)
         return fail(ctx, II2_ERANGE, (std::string(who) + ": more than 2^32 - 2 blocks in one " + per).c_str());
+    return II2_OK;
+}
+
+// The plan of an AND of ORs minus excluded groups: a required group without postings, or required spans that do not overlap, end
+// it (Q.empty); the span the excluded lists must meet is the required groups' common one.
+__attribute__((always_inline)) static inline int plan_groups(ii2_ctx *ctx, const char *who, const char *per, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
+                       const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q) {
+    if (int rc = plan_open(ctx, who, per, n_groups, group_first, group_not, segs, list_first, list_end, Q); rc || !n_groups) return rc;
     for (uint64_t g = 0; g < n_groups; g++) {
         const GroupIn &G = Q.all[g];
         if (!group_not || !group_not[g]) {
@@ -1568,7 +1578,7 @@ extern "C" int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t
 }
 
 // ---- at least m of n groups -------------------------------------------------------------------------
-// The plan of ii2_atleast_ranges, plan_groups' sibling: the same checks under this entry point's name and the same helpers, but a
+// The plan of ii2_atleast_ranges, plan_groups' sibling: the same opening under this entry point's name and the same helpers, but a
 // required group without postings is dropped, not fatal (Q.req: the n' required groups that have postings, tags 0 .. n' - 1
 // in for_each_counted_list), and the span the excluded lists must meet is the required groups' whole span, not their common
 // one - a result doc need not lie in every group.  kept: the groups of the call that are left (the AND hand-off's arguments).
@@ -1576,20 +1586,9 @@ extern "C" int ii2_andnot_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t
 static int plan_atleast(ii2_ctx *ctx, const char *who, uint64_t n_groups, const uint64_t *group_first, const uint8_t *group_not,
                         const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end, GroupQuery &Q, std::vector<uint64_t> &kept,
                         const uint32_t *group_weight = nullptr, std::vector<uint32_t> *req_weight = nullptr) {
-    Q.ex = IrPass{0, 0, 0, 0, 0, 0u, 0xFFFFFFFFu, true};
-    Q.shortest = ~0ull;
-    Q.req_known = true;
-    Q.empty = true;
-    if (n_groups == 0) return II2_OK;
-    uint64_t n_req = 0;
-    for (uint64_t g = 0; g < n_groups; g++) {
-        if (group_not && group_not[g] > 1) return fail(ctx, II2_EINVAL, (std::string(who) + ": a group_not flag is neither 0 nor 1").c_str());
-        n_req += group_not && group_not[g] ? 0u : 1u;
-    }
-    if (!n_req) return fail(ctx, II2_EINVAL, (std::string(who) + ": no required group (the library has no doc universe to complement)").c_str());
-    uint64_t n_blocks = 0;
-    if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, Q.rs, Q.all, &n_blocks)) return rc;
-    if (n_blocks >= 0xFFFFFFFFull || Q.rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, (std::string(who) + ": more than 2^32 - 2 blocks in one call").c_str());
+    kept.clear();
+    if (req_weight) req_weight->clear();
+    if (int rc = plan_open(ctx, who, "call", n_groups, group_first, group_not, segs, list_first, list_end, Q); rc || !n_groups) return rc;
     for (uint64_t g = 0; g < n_groups; g++) {
         const GroupIn &G = Q.all[g];
         if (!group_not || !group_not[g]) {
@@ -1627,6 +1626,129 @@ static int thr_scratch_reserve(ii2_ctx *ctx, uint32_t n_planes, uint64_t span, u
     return II2_OK;
 }
 
+// What the counting form and the ranked form (atleast_count, topk_count) share: the descriptors of every required group and of
+// the excluded ranges, staged once by group index; the doc span, its windows and the scratch they need; the marks of one window.
+// Each form keeps its workspace, the order of its groups, its adds and its passes.
+namespace {
+struct CountCore {
+    ii2_ctx *const ctx;
+    const char *const who;                  // the entry point in the messages
+    const GroupQuery &Q;
+    const size_t n1;                        // required groups
+    const bool excl;
+    const uint32_t B;                       // counter planes
+    const uint64_t W;                       // docs per window
+    std::vector<size_t> at;                 // the descriptor block of required group g in the staging; [n1]: the excluded ranges'
+    size_t stage_bytes = 0;
+    uint8_t *d_stage = nullptr;
+    UnionManyParams p;                      // what every mark shares: bounds, the window (set_window), what the form adds
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;      // the doc span: what the host mirrors of it (stage), then all of it (resolve)
+    uint32_t base = 0;
+    uint64_t span = 0, n_win = 0, wlo = 0, whi = 0;
+    uint32_t n_marks = 0;                   // the required groups' marks so far
+
+    CountCore(ii2_ctx *c, const char *w, const GroupQuery &q, uint32_t planes)
+        : ctx(c), who(w), Q(q), n1(q.req.size()), excl(q.ex.n_nonempty > 0), B(planes), W(thr_window_docs(planes, c->opt_union_many_window_log2)), at(n1 + 1) {
+        std::memset(&p, 0, sizeof p);
+    }
+
+    // staging: one descriptor block (ranges + block prefix) per required group, then one for all excluded ranges, in the pinned
+    // block with `extra` bytes behind them
+    int stage(size_t extra) {
+        for (size_t g = 0; g < n1; g++) {
+            at[g] = stage_bytes;
+            stage_bytes += um_desc_bytes(Q.req[g].r1 - Q.req[g].r0);
+            if (Q.req[g].span_known) { lo = std::min(lo, Q.req[g].lo); hi = std::max(hi, Q.req[g].hi); }
+        }
+        at[n1] = stage_bytes;
+        if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
+        if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes + extra, false, (std::string(who) + ": staging allocation failed").c_str())) return rc;
+        uint8_t *h = (uint8_t *)ctx->h_um;
+        for (size_t g = 0; g < n1; g++) um_desc_fill(Q.rs, Q.req[g].r0, Q.req[g].r1, h + at[g]);
+        if (excl) um_desc_fill(Q.rx, 0, Q.rx.size(), h + at[n1]);
+        return II2_OK;
+    }
+    // ... and up, into the workspace the form has reserved (stage_bytes + 256 of it are the core's)
+    int upload() {
+        d_stage = ws_take<uint8_t>(ctx, stage_bytes);
+        p.bounds = ws_take<uint32_t>(ctx, 2);
+        HIP_TRY(ctx, hipMemcpyAsync(d_stage, ctx->h_um, stage_bytes, hipMemcpyHostToDevice, ctx->stream));
+        return II2_OK;
+    }
+    // the descriptors of required group g (n1: the excluded ranges) in a copy of p
+    UnionManyParams group_params(size_t g) const {
+        const size_t nr = g < n1 ? Q.req[g].r1 - Q.req[g].r0 : Q.rx.size();
+        const uint64_t n_blocks = g < n1 ? Q.req[g].n_blocks : Q.ex.n_blocks;
+        UnionManyParams q = p;
+        q.ranges = (const UmRange *)(d_stage + at[g]);
+        q.pre = (const uint32_t *)(d_stage + at[g] + align_up(nr * sizeof(UmRange)));
+        q.n_ranges = (uint32_t)nr;
+        q.n_blocks = (uint32_t)n_blocks;
+        q.per_wave = um_per_wave(ctx, n_blocks);
+        return q;
+    }
+    // The doc span of the required groups: from the mirrored spans, else one reduction over the group's blocks and a wait.  Then
+    // its windows and the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero.
+    int resolve() {
+        hipStream_t st = ctx->stream;
+        if (!Q.req_known) {
+            HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
+            HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
+            for (size_t g = 0; g < n1; g++)
+                if (!Q.req[g].span_known) HIP_TRY(ctx, launch_union_many_bounds(group_params(g), st));
+            uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+            HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            lo = std::min(lo, hb[0]);
+            hi = std::max(hi, hb[1]);
+        }
+        if (lo > hi) return fail(ctx, II2_EINVAL, (std::string(who) + ": inconsistent list bounds").c_str());
+        base = lo & ~31u;
+        span = (uint64_t)hi - base + 1;
+        n_win = (span + W - 1) / W;
+        p.check_window = n_win > 1 ? 1u : 0u;
+        if (int rc = um_scratch_reserve(ctx, who, span, W)) return rc;
+        return thr_scratch_reserve(ctx, B, span, W);
+    }
+    // window w of the doc span in p
+    void set_window(uint64_t w) {
+        wlo = base + w * W;
+        const uint64_t docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1);
+        whi = wlo + docs - 1;
+        p.window = (uint32_t)w;
+        um_set_window(ctx, p, wlo, docs);
+    }
+    // ... marked: every required group that can meet it, in the form's order, each followed by add(its place in the order, the
+    // group); then the excluded lists, left in the bitmap
+    template <class Add> int mark_window(const std::vector<size_t> &order, Add &&add) {
+        for (size_t k = 0; k < order.size(); k++) {
+            const GroupIn &G = Q.req[order[k]];
+            if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;          // none of the group's docs lies in this window
+            HIP_TRY(ctx, launch_union_many_mark(group_params(order[k]), ctx->stream));
+            if (int rc = add(k, order[k])) return rc;
+            n_marks++;
+        }
+        if (excl) {
+            UnionManyParams x = group_params(n1);
+            x.check_window = 1u;                                            // blocks outside the required groups' span are not decoded
+            HIP_TRY(ctx, launch_union_many_mark(x, ctx->stream));
+        }
+        return II2_OK;
+    }
+};
+}  // namespace
+
+// the window of p in the params of a counting kernel: G and its summary, the B planes and the accumulated summary behind them
+template <class P> static void set_planes(P &t, const UnionManyParams &p, uint32_t *planes, uint32_t B) {
+    t.bitmap = p.bitmap;
+    t.summary = p.summary;
+    t.plane_words = p.n_sum * 2048u;
+    t.planes = planes;
+    t.acc = planes + (size_t)B * t.plane_words;
+    t.n_sum = p.n_sum;
+    t.n_planes = B;
+}
+
 // The counting form (atleast.hip) of a planned query, order: its required groups in ascending order of postings.  Per window of
 // the doc span and group: mark (union_many.hip), add; then the excluded lists' mark, select, and the block-wise OR's count, scan
 // and compact.  The descriptors of all groups are staged once.  At most two waits: the bounds of spans the host does not mirror,
@@ -1635,115 +1757,51 @@ static int atleast_count(ii2_ctx *ctx, GroupQuery &Q, const std::vector<size_t> 
                          uint64_t cap, uint64_t *count, ii2_atleast_stats &stats) {
     hipStream_t st = ctx->stream;
     const size_t n1 = order.size();
-    const bool excl = Q.ex.n_nonempty > 0;
     const uint32_t B = thr_bit_width(min_match);
     const size_t first_late = n1 - min_match + 1;
     if (int rc = um_scratch_clean(ctx)) return rc;
-    // staging: one descriptor block (ranges + block prefix) per group in `order`, then one for all excluded ranges
-    std::vector<size_t> at(n1 + 1);
-    size_t stage_bytes = 0;
-    for (size_t k = 0; k < n1; k++) {
-        at[k] = stage_bytes;
-        stage_bytes += um_desc_bytes(Q.req[order[k]].r1 - Q.req[order[k]].r0);
-    }
-    at[n1] = stage_bytes;
-    if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes, false, "ii2_atleast_ranges: staging allocation failed")) return rc;
-    uint8_t *h = (uint8_t *)ctx->h_um;
-    for (size_t k = 0; k < n1; k++) um_desc_fill(Q.rs, Q.req[order[k]].r0, Q.req[order[k]].r1, h + at[k]);
-    if (excl) um_desc_fill(Q.rx, 0, Q.rx.size(), h + at[n1]);
-    const uint64_t W = thr_window_docs(B, ctx->opt_union_many_window_log2);
-    const uint64_t n_sum_max = (W + 65535) / 65536;
-    UnionManyParams p;
-    std::memset(&p, 0, sizeof p);
+    CountCore C(ctx, "ii2_atleast_ranges", Q, B);
+    if (int rc = C.stage(0)) return rc;
+    const uint64_t n_sum_max = (C.W + 65535) / 65536;
+    UnionManyParams &p = C.p;
     const size_t scan_tmp = scan_temp_bytes(n_sum_max + 1);
-    if (int rc = ii2_ws_reserve(ctx, stage_bytes + 2 * align_up((n_sum_max + 1) * sizeof(uint64_t)) + scan_tmp + 2 * 256 + 4096)) return rc;
-    uint8_t *d_stage = ws_take<uint8_t>(ctx, stage_bytes);
+    if (int rc = ii2_ws_reserve(ctx, C.stage_bytes + 2 * align_up((n_sum_max + 1) * sizeof(uint64_t)) + scan_tmp + 2 * 256 + 4096)) return rc;
     p.cnt = ws_take<uint32_t>(ctx, n_sum_max + 1);
     p.off = ws_take<uint64_t>(ctx, n_sum_max + 1);
     void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
     p.run = ws_take<uint64_t>(ctx, 2);
-    p.bounds = ws_take<uint32_t>(ctx, 2);
-    // the descriptors of group k of `order` (n1: the excluded ranges) in a copy of p
-    auto group_params = [&](size_t k, size_t nr, uint64_t n_blocks) {
-        UnionManyParams g = p;
-        g.ranges = (const UmRange *)(d_stage + at[k]);
-        g.pre = (const uint32_t *)(d_stage + at[k] + align_up(nr * sizeof(UmRange)));
-        g.n_ranges = (uint32_t)nr;
-        g.n_blocks = (uint32_t)n_blocks;
-        g.per_wave = um_per_wave(ctx, n_blocks);
-        return g;
-    };
     ctx->um_dirty = true;
-    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, stage_bytes, hipMemcpyHostToDevice, st));
-    // the doc span of the required groups: from the mirrored spans, else one reduction over the group's blocks
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (const GroupIn &G : Q.req)
-        if (G.span_known) { lo = std::min(lo, G.lo); hi = std::max(hi, G.hi); }
-    if (!Q.req_known) {
-        HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
-        HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
-        for (size_t k = 0; k < n1; k++) {
-            const GroupIn &G = Q.req[order[k]];
-            if (!G.span_known) HIP_TRY(ctx, launch_union_many_bounds(group_params(k, G.r1 - G.r0, G.n_blocks), st));
-        }
-        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        lo = std::min(lo, hb[0]);
-        hi = std::max(hi, hb[1]);
-    }
-    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_atleast_ranges: inconsistent list bounds");
-    const uint32_t base = lo & ~31u;
-    const uint64_t span = (uint64_t)hi - base + 1;
-    const uint64_t n_win = (span + W - 1) / W;
-    // the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero
-    if (int rc = um_scratch_reserve(ctx, "ii2_atleast_ranges", span, W)) return rc;
-    if (int rc = thr_scratch_reserve(ctx, B, span, W)) return rc;
+    if (int rc = C.upload()) return rc;
+    if (int rc = C.resolve()) return rc;
     uint64_t *d_cnt = ii2_mapped_mail(ctx, II2_MAIL_COUNT);
     p.d_count = d_cnt ? d_cnt : ctx->d_mail;
     set_tomb(p, tomb);
     p.out = d_out;
     p.out_cap = cap;
-    p.check_window = n_win > 1 ? 1u : 0u;
     stats.form = II2_ATLEAST_COUNT;
     stats.n_planes = B;
-    stats.n_windows = (uint32_t)n_win;
+    stats.n_windows = (uint32_t)C.n_win;
     stats.n_late = (uint32_t)(n1 - first_late);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
     // several windows whose result may not fit: count first (nothing written), then write
-    const bool count_first = n_win > 1 && cap < stats.bound;
+    const bool count_first = C.n_win > 1 && cap < stats.bound;
     for (int pass = count_first ? 0 : 1; pass < 2; pass++) {
         p.write = (uint32_t)pass;
-        for (uint64_t w = 0; w < n_win; w++) {
-            const uint64_t wlo = base + w * W, docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1), whi = wlo + docs - 1;
-            p.window = (uint32_t)w;
-            um_set_window(ctx, p, wlo, docs);
+        for (uint64_t w = 0; w < C.n_win; w++) {
+            C.set_window(w);
             const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 1 + 3) / 4, (uint64_t)ctx->cu_count * 8u);
             ThrParams t;
             std::memset(&t, 0, sizeof t);
-            t.bitmap = p.bitmap;
-            t.summary = p.summary;
-            t.plane_words = p.n_sum * 2048u;
-            t.planes = ctx->d_thr;
-            t.acc = ctx->d_thr + (size_t)B * t.plane_words;
-            t.n_sum = p.n_sum;
-            t.n_planes = B;
+            set_planes(t, p, ctx->d_thr, B);
             t.min_match = min_match;
-            for (size_t k = 0; k < n1; k++) {
-                const GroupIn &G = Q.req[order[k]];
-                if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;      // none of the group's docs lies in this window
-                HIP_TRY(ctx, launch_union_many_mark(group_params(k, G.r1 - G.r0, G.n_blocks), st));
-                t.late = k >= first_late ? 1u : 0u;
-                HIP_TRY(ctx, launch_thr_add(t, grid, st, e0, e1));
-                e0 = e1 = nullptr;
-            }
-            if (excl) {
-                UnionManyParams x = group_params(n1, Q.rx.size(), Q.ex.n_blocks);
-                x.check_window = 1u;                                        // blocks outside the required groups' span are not decoded
-                HIP_TRY(ctx, launch_union_many_mark(x, st));
-            }
+            if (int rc = C.mark_window(order, [&](size_t k, size_t) -> int {
+                    t.late = k >= first_late ? 1u : 0u;
+                    HIP_TRY(ctx, launch_thr_add(t, grid, st, e0, e1));
+                    e0 = e1 = nullptr;
+                    return II2_OK;
+                }))
+                return rc;
             HIP_TRY(ctx, launch_thr_select(t, grid, st));
             HIP_TRY(ctx, launch_union_many_count(p, grid, st));
             HIP_TRY(ctx, scan_excl_u32_to_u64(d_scan, scan_tmp, p.cnt, p.off, p.n_sum + 1, st));
@@ -1844,7 +1902,6 @@ static int topk_count(ii2_ctx *ctx, const char *who, GroupQuery &Q, uint32_t min
                       uint32_t *n_late = nullptr) {
     hipStream_t st = ctx->stream;
     const size_t n1 = Q.req.size();
-    const bool excl = Q.ex.n_nonempty > 0;
     const std::string name(who);
     uint64_t top = n1;                                                      // the highest score a doc can reach
     std::vector<size_t> order(n1);
@@ -1857,123 +1914,56 @@ static int topk_count(ii2_ctx *ctx, const char *who, GroupQuery &Q, uint32_t min
     }
     const uint32_t B = thr_bit_width(top);
     if (int rc = um_scratch_clean(ctx)) return rc;
-    // staging: one descriptor block (ranges + block prefix) per required group, one for all excluded ranges, then the histogram on
-    // its way down
-    std::vector<size_t> at(n1 + 1);
-    size_t stage_bytes = 0;
-    for (size_t g = 0; g < n1; g++) {
-        at[g] = stage_bytes;
-        stage_bytes += um_desc_bytes(Q.req[g].r1 - Q.req[g].r0);
-    }
-    at[n1] = stage_bytes;
-    if (excl) stage_bytes += um_desc_bytes(Q.rx.size());
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, stage_bytes + TOPK_SCORES * sizeof(uint64_t), false, (name + ": staging allocation failed").c_str())) return rc;
-    uint8_t *h = (uint8_t *)ctx->h_um;
-    uint64_t *h_hist = (uint64_t *)(h + stage_bytes);
-    for (size_t g = 0; g < n1; g++) um_desc_fill(Q.rs, Q.req[g].r0, Q.req[g].r1, h + at[g]);
-    if (excl) um_desc_fill(Q.rx, 0, Q.rx.size(), h + at[n1]);
-    const uint64_t W = thr_window_docs(B, ctx->opt_union_many_window_log2);
-    // the doc span of the required groups: from the mirrored spans, else one reduction over the group's blocks (below)
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    for (const GroupIn &G : Q.req)
-        if (G.span_known) { lo = std::min(lo, G.lo); hi = std::max(hi, G.hi); }
+    // staging: the descriptors, then the histogram on its way down
+    CountCore C(ctx, who, Q, B);
+    if (int rc = C.stage(TOPK_SCORES * sizeof(uint64_t))) return rc;
+    uint64_t *h_hist = (uint64_t *)((uint8_t *)ctx->h_um + C.stage_bytes);
     // workspace, sized before the bounds are known: the count table holds a class per score min_match .. n' and a column per
     // summary word of the largest window
-    uint64_t n_sum_max = (W + 65535) / 65536;
-    if (Q.req_known && lo <= hi) n_sum_max = std::min<uint64_t>(n_sum_max, (std::min<uint64_t>((uint64_t)hi - (lo & ~31u) + 1, W) + 65535) / 65536);
+    uint64_t n_sum_max = (C.W + 65535) / 65536;
+    if (Q.req_known && C.lo <= C.hi) n_sum_max = std::min<uint64_t>(n_sum_max, (std::min<uint64_t>((uint64_t)C.hi - (C.lo & ~31u) + 1, C.W) + 65535) / 65536);
     const size_t table_max = (size_t)(top - min_match + 1) * n_sum_max + 1;
     const size_t scan_tmp = scan_temp_bytes(table_max);
-    if (int rc = ii2_ws_reserve(ctx, stage_bytes + align_up(table_max * sizeof(uint32_t)) + align_up(table_max * sizeof(uint64_t)) + scan_tmp +
+    if (int rc = ii2_ws_reserve(ctx, C.stage_bytes + align_up(table_max * sizeof(uint32_t)) + align_up(table_max * sizeof(uint64_t)) + scan_tmp +
                                          4 * align_up(TOPK_SCORES * sizeof(uint64_t)) + 256 + 4096))
         return rc;
-    UnionManyParams p;
-    std::memset(&p, 0, sizeof p);
+    UnionManyParams &p = C.p;
     TopParams t;
     std::memset(&t, 0, sizeof t);
-    uint8_t *d_stage = ws_take<uint8_t>(ctx, stage_bytes);
     t.cnt = ws_take<uint32_t>(ctx, table_max);
     t.off = ws_take<uint64_t>(ctx, table_max);
     void *d_scan = ws_take<uint8_t>(ctx, scan_tmp);
     t.hist = ws_take<uint64_t>(ctx, TOPK_SCORES);
     t.base = ws_take<uint64_t>(ctx, TOPK_SCORES);
     t.run = ws_take<uint64_t>(ctx, 2 * TOPK_SCORES);
-    p.bounds = ws_take<uint32_t>(ctx, 2);
-    // the descriptors of required group g (n1: the excluded ranges) in a copy of p
-    auto group_params = [&](size_t g, size_t nr, uint64_t n_blocks) {
-        UnionManyParams q = p;
-        q.ranges = (const UmRange *)(d_stage + at[g]);
-        q.pre = (const uint32_t *)(d_stage + at[g] + align_up(nr * sizeof(UmRange)));
-        q.n_ranges = (uint32_t)nr;
-        q.n_blocks = (uint32_t)n_blocks;
-        q.per_wave = um_per_wave(ctx, n_blocks);
-        return q;
-    };
     ctx->um_dirty = true;
-    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, stage_bytes, hipMemcpyHostToDevice, st));
+    if (int rc = C.upload()) return rc;
     HIP_TRY(ctx, hipMemsetAsync(t.hist, 0, TOPK_SCORES * sizeof(uint64_t), st));
-    if (!Q.req_known) {
-        HIP_TRY(ctx, hipMemsetAsync(p.bounds, 0xFF, sizeof(uint32_t), st));
-        HIP_TRY(ctx, hipMemsetAsync(p.bounds + 1, 0, sizeof(uint32_t), st));
-        for (size_t g = 0; g < n1; g++) {
-            const GroupIn &G = Q.req[g];
-            if (!G.span_known) HIP_TRY(ctx, launch_union_many_bounds(group_params(g, G.r1 - G.r0, G.n_blocks), st));
-        }
-        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(hb, p.bounds, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        lo = std::min(lo, hb[0]);
-        hi = std::max(hi, hb[1]);
-    }
-    if (lo > hi) return fail(ctx, II2_EINVAL, (name + ": inconsistent list bounds").c_str());
-    const uint32_t base = lo & ~31u;
-    const uint64_t span = (uint64_t)hi - base + 1;
-    const uint64_t n_win = (span + W - 1) / W;
-    // the scratch: bitmap + summary and planes + accumulated summary of the largest window, zero
-    if (int rc = um_scratch_reserve(ctx, who, span, W)) return rc;
-    if (int rc = thr_scratch_reserve(ctx, B, span, W)) return rc;
-    p.check_window = n_win > 1 ? 1u : 0u;
+    if (int rc = C.resolve()) return rc;
+    const uint64_t n_win = C.n_win;
     set_tomb(t, tomb);
-    t.planes = ctx->d_thr;
-    t.n_planes = B;
     t.min_match = min_match;
     t.k = k;
     t.ids = d_ids;
     t.scores = d_scores;
-    uint32_t n_marks = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr, f0 = nullptr, f1 = nullptr;
     ii2_profile_pair(ctx, &e0, &e1);
     // window w of the doc span in p and t; every required group that can meet it marked and added, the excluded lists left in G
     uint32_t grid = 0;
     auto count_window = [&](uint64_t w) -> int {
-        const uint64_t wlo = base + w * W, docs = std::min<uint64_t>(W, (uint64_t)hi - wlo + 1), whi = wlo + docs - 1;
-        p.window = (uint32_t)w;
-        um_set_window(ctx, p, wlo, docs);
+        C.set_window(w);
         grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
         ThrParams a;
         std::memset(&a, 0, sizeof a);
-        a.bitmap = t.bitmap = p.bitmap;
-        a.summary = t.summary = p.summary;
-        a.plane_words = t.plane_words = p.n_sum * 2048u;
-        a.planes = ctx->d_thr;
-        a.acc = t.acc = ctx->d_thr + (size_t)B * a.plane_words;
-        a.n_sum = t.n_sum = p.n_sum;
-        a.n_planes = B;
-        a.min_match = min_match;
         TopAddParams wa;
         std::memset(&wa, 0, sizeof wa);
-        wa.bitmap = a.bitmap;
-        wa.summary = a.summary;
-        wa.planes = a.planes;
-        wa.acc = a.acc;
-        wa.plane_words = a.plane_words;
-        wa.n_sum = a.n_sum;
-        wa.n_planes = B;
+        set_planes(a, p, ctx->d_thr, B);
+        set_planes(wa, p, ctx->d_thr, B);
+        set_planes(t, p, ctx->d_thr, B);
+        a.min_match = min_match;
         t.win_lo = p.win_lo;
         t.window = p.window;
-        for (size_t g : order) {
-            const GroupIn &G = Q.req[g];
-            if (G.span_known && (G.hi < wlo || G.lo > whi)) continue;          // none of the group's docs lies in this window
-            HIP_TRY(ctx, launch_union_many_mark(group_params(g, G.r1 - G.r0, G.n_blocks), st));
+        return C.mark_window(order, [&](size_t, size_t g) -> int {
             if (weights) {
                 wa.weight = weights[g];
                 wa.late = late[g];
@@ -1981,14 +1971,8 @@ static int topk_count(ii2_ctx *ctx, const char *who, GroupQuery &Q, uint32_t min
             } else {
                 HIP_TRY(ctx, launch_thr_add(a, grid, st));
             }
-            n_marks++;
-        }
-        if (excl) {
-            UnionManyParams x = group_params(n1, Q.rx.size(), Q.ex.n_blocks);
-            x.check_window = 1u;                                            // blocks outside the required groups' span are not decoded
-            HIP_TRY(ctx, launch_union_many_mark(x, st));
-        }
-        return II2_OK;
+            return II2_OK;
+        });
     };
     // pass 1: the histogram of the eligible docs' scores
     for (uint64_t w = 0; w < n_win; w++) {
@@ -2028,7 +2012,7 @@ static int topk_count(ii2_ctx *ctx, const char *who, GroupQuery &Q, uint32_t min
     stats.n_eligible = n_eligible;
     stats.n_planes = B;
     stats.n_windows = (uint32_t)n_win;
-    stats.n_marks = n_marks;
+    stats.n_marks = C.n_marks;
     if (hist) std::memcpy(hist, h_hist, TOPK_SCORES * sizeof(uint64_t));
     *count = std::min(k, n_eligible);
     return II2_OK;
@@ -2372,22 +2356,116 @@ static int batch_finish(ii2_ctx *ctx, const char *who, Path pack, const BatchMem
     return II2_OK;
 }
 
+// The argument checks every batch call makes, under its name w; have: the arrays the entry point cannot do without are there.
+static int batch_args(ii2_ctx *ctx, const std::string &w, bool have, uint64_t nq, const uint32_t *d_out, uint64_t cap, const ii2_tomb *tomb) {
+    if (!have) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
+    if (!d_out && cap) return fail(ctx, II2_EINVAL, (w + ": output buffer is NULL").c_str());
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": the tombstones live on another device").c_str());
+    return II2_OK;
+}
+static int batch_bad(ii2_ctx *ctx, const std::string &w, uint64_t q, const char *what) {
+    return fail(ctx, II2_EINVAL, (w + ": query " + std::to_string(q) + ": " + what).c_str());
+}
+// a helper's message "<entry point>: ..." gets the query's index behind the name (built on the error path only)
+static int batch_named(ii2_ctx *ctx, const std::string &w, uint64_t q, int rc) {
+    if (ctx->err.compare(0, w.size() + 2, w + ": ") == 0) ctx->err.insert(w.size(), ": query " + std::to_string(q));
+    return rc;
+}
+// ... and of the grouped ones: query q owns the groups query_first[q] .. query_first[q + 1] - 1
+static int batch_group_args(ii2_ctx *ctx, const std::string &w, uint64_t nq, const uint64_t *query_first, const uint64_t *group_first) {
+    if (query_first[0] != 0) return batch_bad(ctx, w, 0, "query_first does not ascend from 0");
+    for (uint64_t q = 0; q < nq; q++)
+        if (query_first[q + 1] < query_first[q]) return batch_bad(ctx, w, q, "query_first does not ascend from 0");
+    if (query_first[nq] && !group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (query_first[nq] && group_first[0] != 0) return batch_bad(ctx, w, 0, "group_first does not ascend from 0");
+    return II2_OK;
+}
+
+// what the planned queries of a batch add up to: the ids their staging slots hold, the largest slot, the queries of each kind
+namespace {
+struct BatchTally {
+    uint64_t stage_ids = 0, max_bound = 0;
+    uint32_t n_kind[4] = {0, 0, 0, 0};
+    uint32_t n_table() const { return n_kind[BP_TINY] + n_kind[BP_SMALL]; }              // the queries the batch kernel answers ...
+    size_t o_lists() const { return align_up((size_t)n_table() * sizeof(BatchQuery)); }   // ... open the table; their lists follow
+};
+}  // namespace
+// a query is planned (kind, bound): its staging slot follows those before it
+// (per-query work, inlined like plan_groups: its cold message keeps the compiler from doing it by itself, +1 - 2 ns a query)
+__attribute__((always_inline)) static inline int batch_planned(ii2_ctx *ctx, const std::string &w, BatchPlan &pl, BatchTally &T) {
+    T.n_kind[pl.kind]++;
+    pl.stage_off = T.stage_ids;
+    T.stage_ids += pl.bound;
+    T.max_bound = std::max(T.max_bound, pl.bound);
+    if (T.stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": the result bounds of the queries add up to 2^32 ids or more").c_str());
+    return II2_OK;
+}
+
+// two-list ANDs in the two-kernel form while it lives: nothing of a batch waits between workgroups
+namespace {
+struct And2Split {
+    ii2_ctx *ctx;
+    const int64_t keep;
+    explicit And2Split(ii2_ctx *c) : ctx(c), keep(c->opt_intersect_and2) { if (keep == 1) ctx->opt_intersect_and2 = 2; }
+    ~And2Split() { ctx->opt_intersect_and2 = keep; }
+};
+}  // namespace
+
+// The pinned block behind the entry point's table, filled and sent up: every query's staging slot and a count of 0 (batch_blocks).
+// On the way the large queries run one after the other, run(q, its plan, &count) writing into their staging slots with the waits
+// of the single call - an error gets "<entry point>: query <q>: " in front - and each query the batch kernel answers is given its
+// row: put(q, its plan, the row), the tiny ones first.
+template <class Run, class Put> __attribute__((always_inline)) static inline int batch_fill(ii2_ctx *ctx, const std::string &w, const std::vector<BatchPlan> &plan, const BatchTally &T, const BatchMem &m,
+                                                      Run &&run, Put &&put) {
+    const uint64_t nq = plan.size();
+    uint32_t at_tiny = 0, at_small = T.n_kind[BP_TINY];
+    for (uint64_t q = 0; q < nq; q++) {
+        const BatchPlan &pl = plan[q];
+        m.h_soff[q] = pl.stage_off;
+        m.h_cnt[q] = 0;
+        if (m.h_elig) m.h_elig[q] = 0;
+        if (pl.kind == BP_EMPTY) continue;
+        if (pl.kind == BP_LARGE) {
+            uint64_t count = 0;
+            if (int rc = run(q, pl, &count)) {
+                ctx->err = w + ": query " + std::to_string(q) + ": " + ctx->err;
+                return rc;
+            }
+            m.h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
+            continue;
+        }
+        put(q, pl, pl.kind == BP_TINY ? at_tiny++ : at_small++);
+    }
+    m.h_cnt[nq] = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(m.d, m.h, m.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return II2_OK;
+}
+
+// the table's head, the staging and the counts in a batch kernel's params
+static void batch_params(BatchParams &b, const BatchMem &m, size_t o_lists, const BatchTally &T, const ii2_tomb *tomb) {
+    b.queries = (const BatchQuery *)m.d;
+    b.lists = (const BatchList *)(m.d + o_lists);
+    set_tomb(b, tomb);
+    b.n_tiny = T.n_kind[BP_TINY];
+    b.n_small = T.n_kind[BP_SMALL];
+    b.stage = m.d_stage;
+    b.cnt = (uint32_t *)(m.d + m.o_cnt);
+}
+
 static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
                                 const uint64_t *list_first, const uint64_t *list_end, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                                 uint64_t *out_off) {
+    const std::string w("ii2_query_batch");
     if (nq == 0) { out_off[0] = 0; return II2_OK; }
-    if (!op || !query_first) return fail(ctx, II2_EINVAL, "ii2_query_batch: bad argument");
-    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, "ii2_query_batch: more than 2^20 queries in one call");
-    if (!d_out && cap) return fail(ctx, II2_EINVAL, "ii2_query_batch: output buffer is NULL");
-    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_query_batch: the tombstones live on another device");
-    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, ("ii2_query_batch: query " + std::to_string(q) + ": " + what).c_str()); };
+    if (int rc = batch_args(ctx, w, op && query_first, nq, d_out, cap, tomb)) return rc;
+    auto bad = [&](uint64_t q, const char *what) { return batch_bad(ctx, w, q, what); };
     if (query_first[nq] && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_query_batch: bad argument");
     // 1. every query checked and sized before anything is launched
     std::vector<BatchPlan> plan(nq);
     std::vector<SetList> lists;
     lists.reserve(2 * nq);
-    uint64_t stage_ids = 0, max_bound = 0;
-    uint32_t n_kind[4] = {0, 0, 0, 0};
+    BatchTally T;
     size_t n_table_lists = 0;
     const ii2_seg *mirrored = nullptr;     // the segment whose host mirrors were looked at last
     for (uint64_t q = 0; q < nq; q++) {
@@ -2435,88 +2513,54 @@ static int query_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint8_t *op, co
         if (pl.bound == 0 || blocks == 0) { pl.bound = 0; pl.kind = BP_EMPTY; }       // an empty operand / no posting: an empty result, no launch
         else if (!ctx->opt_batch_small || !regular || pl.nl > MAX_LISTS || blocks > SMALL_SET_BLOCKS || post > SMALL_SET_POSTINGS) pl.kind = BP_LARGE;
         else pl.kind = ctx->opt_batch_tiny && blocks <= BATCH_TINY_BLOCKS && post <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
-        n_kind[pl.kind]++;
         if (pl.kind == BP_TINY || pl.kind == BP_SMALL) n_table_lists += pl.nl;
-        pl.stage_off = stage_ids;
-        stage_ids += pl.bound;
-        max_bound = std::max(max_bound, pl.bound);
-        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, "ii2_query_batch: the result bounds of the queries add up to 2^32 ids or more");
+        if (int rc = batch_planned(ctx, w, pl, T)) return rc;
     }
     // 2. the blocks: [queries | lists | staging offsets | counts] travel up in one copy; offsets, scan temp and staged ids stay below
-    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
-    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery));
+    const size_t o_lists = T.o_lists();
     BatchMem m;
-    if (int rc = batch_blocks(ctx, o_lists + align_up(n_table_lists * sizeof(BatchList)), nq, stage_ids, &m)) return rc;
-    uint8_t *h = m.h, *d = m.d;
-    uint32_t *d_stage = m.d_stage;
-    BatchQuery *hq = (BatchQuery *)h;
-    BatchList *hl = (BatchList *)(h + o_lists);
-    uint64_t *h_soff = m.h_soff;
-    uint32_t *h_cnt = m.h_cnt;
+    if (int rc = batch_blocks(ctx, o_lists + align_up(n_table_lists * sizeof(BatchList)), nq, T.stage_ids, &m)) return rc;
+    BatchQuery *hq = (BatchQuery *)m.h;
+    BatchList *hl = (BatchList *)(m.h + o_lists);
     // 3. the large queries, one after the other through the single-query paths, into their staging slots (each with its own wait);
-    // two-list ANDs in the two-kernel form: nothing of a batch waits between workgroups
+    // two-list ANDs in the two-kernel form: nothing of a batch waits between workgroups; the table up
     std::vector<const ii2_seg *> one_segs;
     std::vector<uint64_t> one_idx;
-    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY], at_list = 0;
-    for (uint64_t q = 0; q < nq; q++) {
-        const BatchPlan &pl = plan[q];
-        h_soff[q] = pl.stage_off;
-        h_cnt[q] = 0;
-        if (pl.kind == BP_EMPTY) continue;
-        if (pl.kind == BP_LARGE) {
-            took(ctx, P_BATCH_SINGLE);
-            uint64_t count = 0;
-            uint32_t *slot = d_stage + pl.stage_off;
-            int rc;
-            if (pl.is_union) {
+    uint32_t at_list = 0;
+    if (int rc = batch_fill(ctx, w, plan, T, m,
+            [&](uint64_t q, const BatchPlan &pl, uint64_t *count) -> int {
+                took(ctx, P_BATCH_SINGLE);
+                uint32_t *slot = m.d_stage + pl.stage_off;
                 const uint64_t r0 = query_first[q];
-                rc = union_ranges_unlocked(ctx, query_first[q + 1] - r0, segs + r0, list_first + r0, list_end + r0, tomb, slot, pl.bound, &count);
-            } else {
+                if (pl.is_union) return union_ranges_unlocked(ctx, query_first[q + 1] - r0, segs + r0, list_first + r0, list_end + r0, tomb, slot, pl.bound, count);
                 one_segs.clear();
                 one_idx.clear();
                 for (uint32_t i = 0; i < pl.nl; i++) { one_segs.push_back(lists[pl.l0 + i].seg); one_idx.push_back(lists[pl.l0 + i].idx); }
-                const int64_t keep = ctx->opt_intersect_and2;
-                if (keep == 1) ctx->opt_intersect_and2 = 2;
-                rc = intersect_sync(ctx, pl.nl, one_segs.data(), one_idx.data(), tomb, slot, pl.bound, &count);
-                ctx->opt_intersect_and2 = keep;
-            }
-            if (rc) {
-                ctx->err = "ii2_query_batch: query " + std::to_string(q) + ": " + ctx->err;
-                return rc;
-            }
-            h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
-            continue;
-        }
-        BatchQuery &bq = hq[pl.kind == BP_TINY ? at_tiny++ : at_small++];
-        bq = BatchQuery{pl.stage_off, (uint32_t)pl.bound, at_list, pl.nl, pl.is_union, (uint32_t)q, 0u};
-        for (uint32_t i = 0; i < pl.nl; i++) {
-            const SetList &sl = lists[pl.l0 + i];
-            hl[at_list++] = BatchList{sl.v.skip, sl.v.payload, sl.v.nblk, sl.seg->h_cnt[sl.idx]};
-        }
-    }
-    h_cnt[nq] = 0;
-    // 4. table up, the small queries in one launch per size class, counts -> offsets, pack (tests the capacity on the device),
-    // offsets down: one wait
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(d, h, m.up_bytes, hipMemcpyHostToDevice, st));
-    if (n_table) {
+                const And2Split split(ctx);
+                return intersect_sync(ctx, pl.nl, one_segs.data(), one_idx.data(), tomb, slot, pl.bound, count);
+            },
+            [&](uint64_t q, const BatchPlan &pl, uint32_t at) {
+                hq[at] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, at_list, pl.nl, pl.is_union, (uint32_t)q, 0u};
+                for (uint32_t i = 0; i < pl.nl; i++) {
+                    const SetList &sl = lists[pl.l0 + i];
+                    hl[at_list++] = BatchList{sl.v.skip, sl.v.payload, sl.v.nblk, sl.seg->h_cnt[sl.idx]};
+                }
+            }))
+        return rc;
+    // 4. the small queries in one launch per size class, counts -> offsets, pack (tests the capacity on the device), offsets down:
+    // one wait
+    if (T.n_table()) {
         BatchParams bp;
         std::memset(&bp, 0, sizeof bp);
-        bp.queries = (const BatchQuery *)d;
-        bp.lists = (const BatchList *)(d + o_lists);
-        set_tomb(bp, tomb);
-        bp.n_tiny = n_kind[BP_TINY];
-        bp.n_small = n_kind[BP_SMALL];
-        bp.stage = d_stage;
-        bp.cnt = (uint32_t *)(d + m.o_cnt);
+        batch_params(bp, m, o_lists, T, tomb);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
         const uint32_t forms = setop_batch_forms(bp);
         if (forms & BATCH_FORM_TINY) took(ctx, P_BATCH_TINY);
         if (forms & BATCH_FORM_SMALL) took(ctx, P_BATCH_SMALL);
-        HIP_TRY(ctx, launch_setop_batch(bp, st, e0, e1));
+        HIP_TRY(ctx, launch_setop_batch(bp, ctx->stream, e0, e1));
     }
-    return batch_finish(ctx, "ii2_query_batch", P_BATCH_PACK, m, nq, max_bound, d_out, cap, out_off);
+    return batch_finish(ctx, "ii2_query_batch", P_BATCH_PACK, m, nq, T.max_bound, d_out, cap, out_off);
 }
 
 extern "C" int ii2_query_batch(ii2_ctx *ctx, uint64_t n_queries, const uint8_t *op, const uint64_t *query_first, const ii2_seg *const *segs,
@@ -2538,43 +2582,29 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
     const char *const who = "ii2_query_batch_groups";
     const std::string w(who);
     if (nq == 0) { out_off[0] = 0; return II2_OK; }
-    if (!query_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
-    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
-    if (!d_out && cap) return fail(ctx, II2_EINVAL, (w + ": output buffer is NULL").c_str());
-    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": the tombstones live on another device").c_str());
-    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, (w + ": query " + std::to_string(q) + ": " + what).c_str()); };
-    // a helper's message "<entry point>: ..." gets the query's index behind the name (built on the error path only)
-    auto named = [&](uint64_t q, int rc) {
-        if (ctx->err.compare(0, w.size() + 2, w + ": ") == 0) ctx->err.insert(w.size(), ": query " + std::to_string(q));
-        return rc;
-    };
-    if (query_first[0] != 0) return bad(0, "query_first does not ascend from 0");
-    for (uint64_t q = 0; q < nq; q++)
-        if (query_first[q + 1] < query_first[q]) return bad(q, "query_first does not ascend from 0");
-    if (query_first[nq] && !group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
-    if (query_first[nq] && group_first[0] != 0) return bad(0, "group_first does not ascend from 0");
+    if (int rc = batch_args(ctx, w, query_first, nq, d_out, cap, tomb)) return rc;
+    if (int rc = batch_group_args(ctx, w, nq, query_first, group_first)) return rc;
     // 1. every query checked and sized before anything is launched
     std::vector<BatchPlan> plan(nq);
     std::vector<BatchList> tl;             // the table's lists and their tags, the queries in batch order (tiny and small ones alike)
     std::vector<uint8_t> tt;
     GroupQuery gq;                          // (one for the call: its vectors keep their storage from query to query)
-    uint64_t stage_ids = 0, max_bound = 0;
-    uint32_t n_kind[4] = {0, 0, 0, 0};
+    BatchTally T;
     for (uint64_t q = 0; q < nq; q++) {
         const uint64_t g0 = query_first[q], ng = query_first[q + 1] - g0;
         BatchPlan &pl = plan[q];
-        pl = BatchPlan{0, stage_ids, tl.size(), 0, 0, BP_EMPTY, 0, 0};
-        auto planned = [&]() { n_kind[pl.kind]++; };
+        pl = BatchPlan{0, 0, tl.size(), 0, 0, BP_EMPTY, 0, 0};
         if (int rc = plan_groups(ctx, who, "query", ng, group_first + g0, group_not ? group_not + g0 : nullptr, segs, list_first, list_end, gq))
-            return named(q, rc);
-        if (gq.empty) { planned(); continue; }
-        pl.bound = gq.shortest;
-        pl.kind = BP_LARGE;
+            return batch_named(ctx, w, q, rc);
+        if (!gq.empty) {
+            pl.bound = gq.shortest;
+            pl.kind = BP_LARGE;
+        }
         // A query fits the batch kernel when the lists that count fit one workgroup (for_each_counted_list).  ANDNOT_SMALL_WORK is
         // NOT applied: that bound prices one workgroup against the general form's waits inside a single call; in a batch the
         // alternative is those waits once per query, one after the other, while the other CUs sit idle (DESIGN.md §4.1i has the
         // case at the kernel's capacity).
-        if (ctx->opt_batch_groups && gq.req.size() <= MAX_LISTS) {
+        if (pl.kind == BP_LARGE && ctx->opt_batch_groups && gq.req.size() <= MAX_LISTS) {
             // (size_exclusions' totals and narrowed span, a second pass over the excluded lists, are for the general form: the walk
             // mirrors their counts itself, and the lists that count are the same under either span)
             const Counted t = for_each_counted_list(ctx, gq, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &) {
@@ -2593,70 +2623,45 @@ static int query_batch_groups_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t
                 tt.resize(pl.l0);
             }
         }
-        planned();
-        stage_ids += pl.bound;
-        max_bound = std::max(max_bound, pl.bound);
-        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": the result bounds of the queries add up to 2^32 ids or more").c_str());
+        if (int rc = batch_planned(ctx, w, pl, T)) return rc;
     }
     // 2. the blocks: [queries | lists | tags | staging offsets | counts] travel up in one copy (batch_blocks)
-    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
-    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
+    const size_t o_lists = T.o_lists(), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
     BatchMem m;
-    if (int rc = batch_blocks(ctx, o_tags + align_up(tt.size()), nq, stage_ids, &m)) return rc;
+    if (int rc = batch_blocks(ctx, o_tags + align_up(tt.size()), nq, T.stage_ids, &m)) return rc;
     BatchQuery *hq = (BatchQuery *)m.h;
     if (!tl.empty()) {
         std::memcpy(m.h + o_lists, tl.data(), tl.size() * sizeof(BatchList));
         std::memcpy(m.h + o_tags, tt.data(), tt.size());
     }
     // 3. the large queries, one after the other through ii2_andnot_ranges' paths, into their staging slots (each with its own
-    // waits); two-list ANDs in the two-kernel form for the duration: nothing of a batch waits between workgroups
-    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY];
-    for (uint64_t q = 0; q < nq; q++) {
-        const BatchPlan &pl = plan[q];
-        m.h_soff[q] = pl.stage_off;
-        m.h_cnt[q] = 0;
-        if (pl.kind == BP_EMPTY) continue;
-        if (pl.kind == BP_LARGE) {
-            took(ctx, P_GBATCH_SINGLE);
-            const uint64_t g0 = query_first[q];
-            uint64_t count = 0;
-            const int64_t keep = ctx->opt_intersect_and2;
-            if (keep == 1) ctx->opt_intersect_and2 = 2;
-            const int rc = andnot_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr, segs, list_first,
-                                                  list_end, tomb, m.d_stage + pl.stage_off, pl.bound, &count);
-            ctx->opt_intersect_and2 = keep;
-            if (rc) {
-                ctx->err = w + ": query " + std::to_string(q) + ": " + ctx->err;
-                return rc;
-            }
-            m.h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
-            continue;
-        }
-        hq[pl.kind == BP_TINY ? at_tiny++ : at_small++] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
-    }
-    m.h_cnt[nq] = 0;
-    // 4. table up, the queries that fit in one launch per size class, then the flat batch's scan, pack and wait (batch_finish)
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(m.d, m.h, m.up_bytes, hipMemcpyHostToDevice, st));
-    if (n_table) {
+    // waits); two-list ANDs in the two-kernel form for the duration: nothing of a batch waits between workgroups; the table up
+    if (int rc = batch_fill(ctx, w, plan, T, m,
+            [&](uint64_t q, const BatchPlan &pl, uint64_t *count) -> int {
+                took(ctx, P_GBATCH_SINGLE);
+                const uint64_t g0 = query_first[q];
+                const And2Split split(ctx);
+                return andnot_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr, segs, list_first,
+                                              list_end, tomb, m.d_stage + pl.stage_off, pl.bound, count);
+            },
+            [&](uint64_t q, const BatchPlan &pl, uint32_t at) {
+                hq[at] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
+            }))
+        return rc;
+    // 4. the queries that fit in one launch per size class, then the flat batch's scan, pack and wait (batch_finish)
+    if (T.n_table()) {
         GroupBatchParams gp;
         std::memset(&gp, 0, sizeof gp);
-        gp.b.queries = (const BatchQuery *)m.d;
-        gp.b.lists = (const BatchList *)(m.d + o_lists);
+        batch_params(gp.b, m, o_lists, T, tomb);
         gp.tag = m.d + o_tags;
-        set_tomb(gp.b, tomb);
-        gp.b.n_tiny = n_kind[BP_TINY];
-        gp.b.n_small = n_kind[BP_SMALL];
-        gp.b.stage = m.d_stage;
-        gp.b.cnt = (uint32_t *)(m.d + m.o_cnt);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
         const uint32_t forms = setop_groups_batch_forms(gp);
         if (forms & BATCH_FORM_TINY) took(ctx, P_GBATCH_TINY);
         if (forms & BATCH_FORM_SMALL) took(ctx, P_GBATCH_SMALL);
-        HIP_TRY(ctx, launch_setop_groups_batch(gp, st, e0, e1));
+        HIP_TRY(ctx, launch_setop_groups_batch(gp, ctx->stream, e0, e1));
     }
-    return batch_finish(ctx, who, P_GBATCH_PACK, m, nq, max_bound, d_out, cap, out_off);
+    return batch_finish(ctx, who, P_GBATCH_PACK, m, nq, T.max_bound, d_out, cap, out_off);
 }
 
 extern "C" int ii2_query_batch_groups(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,
@@ -2693,21 +2698,8 @@ static int topk_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_
         if (stats) std::memset(stats, 0, sizeof *stats);
         return II2_OK;
     }
-    if (!query_first || !k) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
-    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
-    if (!d_ids && cap) return fail(ctx, II2_EINVAL, (w + ": output buffer is NULL").c_str());
-    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": the tombstones live on another device").c_str());
-    auto bad = [&](uint64_t q, const char *what) { return fail(ctx, II2_EINVAL, (w + ": query " + std::to_string(q) + ": " + what).c_str()); };
-    // a helper's message "<entry point>: ..." gets the query's index behind the name (built on the error path only)
-    auto named = [&](uint64_t q, int rc) {
-        if (ctx->err.compare(0, w.size() + 2, w + ": ") == 0) ctx->err.insert(w.size(), ": query " + std::to_string(q));
-        return rc;
-    };
-    if (query_first[0] != 0) return bad(0, "query_first does not ascend from 0");
-    for (uint64_t q = 0; q < nq; q++)
-        if (query_first[q + 1] < query_first[q]) return bad(q, "query_first does not ascend from 0");
-    if (query_first[nq] && !group_first) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
-    if (query_first[nq] && group_first[0] != 0) return bad(0, "group_first does not ascend from 0");
+    if (int rc = batch_args(ctx, w, query_first && k, nq, d_ids, cap, tomb)) return rc;
+    if (int rc = batch_group_args(ctx, w, nq, query_first, group_first)) return rc;
     // 1. every query checked and sized before anything is launched
     std::vector<BatchPlan> plan(nq);
     std::vector<BatchList> tl;             // the table's lists, their tags and their groups' weights, the queries in batch order
@@ -2715,62 +2707,52 @@ static int topk_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_
     GroupQuery gq;
     std::vector<uint64_t> kept;
     std::vector<uint32_t> weights;
-    uint64_t stage_ids = 0, max_bound = 0;
-    uint32_t n_kind[4] = {0, 0, 0, 0};
+    BatchTally T;
     for (uint64_t q = 0; q < nq; q++) {
         const uint64_t g0 = query_first[q], ng = query_first[q + 1] - g0;
         const uint32_t ms = min_score ? min_score[q] : 1u;
         BatchPlan &pl = plan[q];
-        pl = BatchPlan{0, stage_ids, tl.size(), 0, 0, BP_EMPTY, 0, 0};
-        gq.rs.clear();                      // (plan_atleast appends)
-        gq.rx.clear();
-        gq.all.clear();
-        gq.req.clear();
-        kept.clear();
-        weights.clear();
+        pl = BatchPlan{0, 0, tl.size(), 0, 0, BP_EMPTY, 0, 0};
         uint64_t total = 0;
         if (int rc = topkw_plan(ctx, who, ng, group_first + g0, group_not ? group_not + g0 : nullptr, group_weight ? group_weight + g0 : nullptr, ms, k[q],
                                 segs, list_first, list_end, gq, kept, weights, &total))
-            return named(q, rc);
-        if (gq.empty || ms > total) { n_kind[BP_EMPTY]++; continue; }
-        uint64_t req_post = 0;
-        for (const GroupIn &G : gq.req) req_post += G.n_post;
-        pl.bound = topk_batch_bound(gq.req.size(), req_post, k[q]);
-        // A query takes the batch kernel when the lists that count fit one workgroup (for_each_counted_list), with at most
-        // MAX_LISTS tags for its required groups.  As in ii2_query_batch_groups the walk mirrors the excluded segments' counts
-        // itself, and no postings x lists bound applies: the alternative is the single form's waits once per query.
-        Counted t{0, 0, 0, false, II2_OK};
-        if (ctx->opt_batch_topk && gq.req.size() <= MAX_LISTS) {
-            t = for_each_counted_list(ctx, gq, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &) {
-                const uint32_t b0 = s->h_blk_off[j];
-                tl.push_back(BatchList{s->d_skip + b0, s->d_payload, s->h_blk_off[j + 1] - b0, s->h_cnt[j]});
-                tt.push_back((uint8_t)tag);
-                tw.push_back(tag < weights.size() ? (uint8_t)weights[tag] : (uint8_t)0);
-            });
-            if (t.rc) return t.rc;
+            return batch_named(ctx, w, q, rc);
+        if (!gq.empty && ms <= total) {
+            uint64_t req_post = 0;
+            for (const GroupIn &G : gq.req) req_post += G.n_post;
+            pl.bound = topk_batch_bound(gq.req.size(), req_post, k[q]);
+            // A query takes the batch kernel when the lists that count fit one workgroup (for_each_counted_list), with at most
+            // MAX_LISTS tags for its required groups.  As in ii2_query_batch_groups the walk mirrors the excluded segments' counts
+            // itself, and no postings x lists bound applies: the alternative is the single form's waits once per query.
+            Counted t{0, 0, 0, false, II2_OK};
+            if (ctx->opt_batch_topk && gq.req.size() <= MAX_LISTS) {
+                t = for_each_counted_list(ctx, gq, [&](const ii2_seg *s, uint64_t j, uint32_t tag, const Counted &) {
+                    const uint32_t b0 = s->h_blk_off[j];
+                    tl.push_back(BatchList{s->d_skip + b0, s->d_payload, s->h_blk_off[j + 1] - b0, s->h_cnt[j]});
+                    tt.push_back((uint8_t)tag);
+                    tw.push_back(tag < weights.size() ? (uint8_t)weights[tag] : (uint8_t)0);
+                });
+                if (t.rc) return t.rc;
+            }
+            pl.kind = topk_batch_form(t.fits, t.m, t.sum, t.nb, gq.req.size(), ctx->opt_batch_topk, ctx->opt_batch_tiny);
+            if (pl.kind == BP_LARGE) {
+                tl.resize(pl.l0);
+                tt.resize(pl.l0);
+                tw.resize(pl.l0);
+            } else {
+                pl.nl = t.m;
+                pl.n_blocks = t.nb;
+                pl.n_req = (uint8_t)gq.req.size();
+            }
         }
-        pl.kind = topk_batch_form(t.fits, t.m, t.sum, t.nb, gq.req.size(), ctx->opt_batch_topk, ctx->opt_batch_tiny);
-        if (pl.kind == BP_LARGE) {
-            tl.resize(pl.l0);
-            tt.resize(pl.l0);
-            tw.resize(pl.l0);
-        } else {
-            pl.nl = t.m;
-            pl.n_blocks = t.nb;
-            pl.n_req = (uint8_t)gq.req.size();
-        }
-        n_kind[pl.kind]++;
-        stage_ids += pl.bound;
-        max_bound = std::max(max_bound, pl.bound);
-        if (stage_ids >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": the result bounds of the queries add up to 2^32 ids or more").c_str());
+        if (int rc = batch_planned(ctx, w, pl, T)) return rc;
     }
-    const ii2_topk_batch_stats bst{n_kind[BP_TINY], n_kind[BP_SMALL], n_kind[BP_LARGE], n_kind[BP_EMPTY], stage_ids};
+    const ii2_topk_batch_stats bst{T.n_kind[BP_TINY], T.n_kind[BP_SMALL], T.n_kind[BP_LARGE], T.n_kind[BP_EMPTY], T.stage_ids};
     // 2. the blocks: [queries | lists | tags | weights | min_scores | staging offsets | counts | eligible] travel up in one copy
-    const uint32_t n_table = n_kind[BP_TINY] + n_kind[BP_SMALL];
-    const size_t o_lists = align_up((size_t)n_table * sizeof(BatchQuery)), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
+    const size_t o_lists = T.o_lists(), o_tags = o_lists + align_up(tl.size() * sizeof(BatchList));
     const size_t o_weights = o_tags + align_up(tt.size()), o_ms = o_weights + align_up(tw.size());
     BatchMem m;
-    if (int rc = batch_blocks(ctx, o_ms + align_up((size_t)n_table * sizeof(uint32_t)), nq, stage_ids, &m, true)) return rc;
+    if (int rc = batch_blocks(ctx, o_ms + align_up((size_t)T.n_table() * sizeof(uint32_t)), nq, T.stage_ids, &m, true)) return rc;
     BatchQuery *hq = (BatchQuery *)m.h;
     uint32_t *hms = (uint32_t *)(m.h + o_ms);
     if (!tl.empty()) {
@@ -2779,59 +2761,39 @@ static int topk_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_
         std::memcpy(m.h + o_weights, tw.data(), tw.size());
     }
     // 3. the queries that do not fit, one after the other through ii2_topk_weighted_ranges' form, ids and scores straight into their
-    // staging slots (each with that form's own waits)
-    uint32_t at_tiny = 0, at_small = n_kind[BP_TINY];
-    for (uint64_t q = 0; q < nq; q++) {
-        const BatchPlan &pl = plan[q];
-        const uint32_t ms = min_score ? min_score[q] : 1u;
-        m.h_soff[q] = pl.stage_off;
-        m.h_cnt[q] = 0;
-        m.h_elig[q] = 0;
-        if (pl.kind == BP_EMPTY) continue;
-        if (pl.kind == BP_LARGE) {
-            const uint64_t g0 = query_first[q];
-            uint64_t count = 0;
-            ii2_topkw_stats ws;
-            const int rc = topkw_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr,
-                                                 group_weight ? group_weight + g0 : nullptr, ms, k[q], segs, list_first, list_end, tomb,
-                                                 m.d_stage + pl.stage_off, m.d_stage_scores + pl.stage_off, &count, nullptr, &ws);
-            if (rc) {
-                ctx->err = w + ": query " + std::to_string(q) + ": " + ctx->err;
-                return rc;
-            }
-            m.h_cnt[q] = (uint32_t)std::min<uint64_t>(count, pl.bound);
-            m.h_elig[q] = (uint32_t)std::min<uint64_t>(ws.n_eligible, 0xFFFFFFFFull);
-            continue;
-        }
-        const uint32_t at = pl.kind == BP_TINY ? at_tiny++ : at_small++;
-        hq[at] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
-        hms[at] = ms;
-    }
-    m.h_cnt[nq] = 0;
-    // 4. table up, the queries that fit in one launch per size class, then the flat batch's scan, pack (ids, then scores) and wait
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipMemcpyAsync(m.d, m.h, m.up_bytes, hipMemcpyHostToDevice, st));
-    if (n_table) {
+    // staging slots (each with that form's own waits); the table up
+    if (int rc = batch_fill(ctx, w, plan, T, m,
+            [&](uint64_t q, const BatchPlan &pl, uint64_t *count) -> int {
+                const uint64_t g0 = query_first[q];
+                ii2_topkw_stats ws;
+                if (int rc = topkw_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, group_not ? group_not + g0 : nullptr,
+                                                   group_weight ? group_weight + g0 : nullptr, min_score ? min_score[q] : 1u, k[q], segs, list_first, list_end,
+                                                   tomb, m.d_stage + pl.stage_off, m.d_stage_scores + pl.stage_off, count, nullptr, &ws))
+                    return rc;
+                m.h_elig[q] = (uint32_t)std::min<uint64_t>(ws.n_eligible, 0xFFFFFFFFull);
+                return II2_OK;
+            },
+            [&](uint64_t q, const BatchPlan &pl, uint32_t at) {
+                hq[at] = BatchQuery{pl.stage_off, (uint32_t)pl.bound, (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, pl.n_req};
+                hms[at] = min_score ? min_score[q] : 1u;
+            }))
+        return rc;
+    // 4. the queries that fit in one launch per size class, then the flat batch's scan, pack (ids, then scores) and wait
+    if (T.n_table()) {
         TopkBatchParams tp;
         std::memset(&tp, 0, sizeof tp);
-        tp.g.b.queries = (const BatchQuery *)m.d;
-        tp.g.b.lists = (const BatchList *)(m.d + o_lists);
+        batch_params(tp.g.b, m, o_lists, T, tomb);
         tp.g.tag = m.d + o_tags;
         tp.weight = m.d + o_weights;
         tp.min_score = (const uint32_t *)(m.d + o_ms);
-        set_tomb(tp.g.b, tomb);
-        tp.g.b.n_tiny = n_kind[BP_TINY];
-        tp.g.b.n_small = n_kind[BP_SMALL];
-        tp.g.b.stage = m.d_stage;
-        tp.g.b.cnt = (uint32_t *)(m.d + m.o_cnt);
         tp.stage_scores = m.d_stage_scores;
         tp.eligible = (uint32_t *)(m.d + m.o_elig);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         ii2_profile_pair(ctx, &e0, &e1);
-        HIP_TRY(ctx, launch_topk_batch(tp, st, e0, e1));
+        HIP_TRY(ctx, launch_topk_batch(tp, ctx->stream, e0, e1));
     }
     const BatchRanked ranked{d_scores, eligible};
-    const int rc = batch_finish(ctx, who, P_COUNT, m, nq, max_bound, d_ids, cap, out_off, &ranked);
+    const int rc = batch_finish(ctx, who, P_COUNT, m, nq, T.max_bound, d_ids, cap, out_off, &ranked);
     if (stats && (rc == II2_OK || rc == II2_ECAPACITY)) *stats = bst;
     return rc;
 }
