@@ -221,6 +221,43 @@ func (c *Ctx) NewDictionary(termBytes []byte, termOff []uint64) (*Dictionary, er
 
 func (d *Dictionary) Free() { C.ii2_dict_free(d.h); d.h = nil }
 
+// DictFind looks terms up in k resident dictionaries on the device (ii2_dict_find): the step from a query's terms to the list
+// ranges every range call takes.  prefix == nil: every probe is a term - [j, j+1) where dictionary s holds it as list j, the
+// empty [j, j) at its insertion point where it does not; prefix[p] == 1: the run of the terms that start with probe p
+// (PrefixSearch, inverted_index.go:274-292).  Entry p*k + s of first / end answers probe p in dicts[s]: the k ranges of one probe
+// are one group of the range calls, with the k segments repeated.  found is the number of non-empty ranges.
+func (c *Ctx) DictFind(dicts []*Dictionary, probes [][]byte, prefix []uint8) (first, end []uint64, found uint64, err error) {
+	if len(dicts) == 0 {
+		return nil, nil, 0, fmt.Errorf("dict find: no dictionaries")
+	}
+	if prefix != nil && len(prefix) != len(probes) {
+		return nil, nil, 0, fmt.Errorf("dict find: one prefix flag per probe")
+	}
+	hs := make([]*C.ii2_dict, len(dicts))
+	for i, d := range dicts {
+		hs[i] = d.h
+	}
+	off := make([]uint64, len(probes)+1)
+	var blob []byte
+	for i, p := range probes {
+		blob = append(blob, p...)
+		off[i+1] = uint64(len(blob))
+	}
+	blob = append(blob, 0) // never an empty array
+	first = make([]uint64, len(probes)*len(dicts)+1)
+	end = make([]uint64, len(probes)*len(dicts)+1)
+	var pf *C.uint8_t
+	if len(prefix) > 0 {
+		pf = (*C.uint8_t)(unsafe.Pointer(&prefix[0]))
+	}
+	var n C.uint64_t
+	if rc := C.ii2_dict_find(c.h, C.uint32_t(len(hs)), (**C.ii2_dict)(unsafe.Pointer(&hs[0])), C.uint64_t(len(probes)),
+		(*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off), pf, C.II2_HOST, u64ptr(first), u64ptr(end), &n); rc != 0 {
+		return nil, nil, 0, c.err("dict find", rc)
+	}
+	return first[:len(probes)*len(dicts)], end[:len(probes)*len(dicts)], uint64(n), nil
+}
+
 // AlignDicts is AlignTerms on resident dictionaries (ii2_align_dicts): nothing is uploaded, nothing is sorted.
 func (c *Ctx) AlignDicts(dicts []*Dictionary) (*Alignment, error) {
 	hs := make([]*C.ii2_dict, len(dicts))

@@ -167,6 +167,34 @@ typedef struct ii2_align ii2_align;
 typedef struct ii2_dict ii2_dict;
 int ii2_dict_create(ii2_ctx *ctx, const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, int where, ii2_dict **out);
 void ii2_dict_free(ii2_dict *dict);
+/* Term and prefix lookup in k resident dictionaries: the step in front of every range entry point, which take list indices where
+ * callers have terms (replaces one dictionary bisection per (term, segment): the FST lookups of Intersect and PrefixSearch,
+ * inverted_index.go:274-292; order = bytes.Compare, file/types.go:24-26).  Probe p is probe_bytes[probe_off[p] ..
+ * probe_off[p + 1]); entry p * k + s of list_first / list_end answers it in dicts[s]:
+ *   - exact probe (probe_prefix == NULL or probe_prefix[p] == 0): with j the index of the first term >= the probe, [j, j + 1)
+ *     when term j is the probe and [j, j) - empty, at the insertion point - when it is not;
+ *   - prefix probe (probe_prefix[p] == 1): [j, the first term at or after j that does not start with the probe) - the run
+ *     PrefixSearch reads.  The empty prefix is the whole dictionary.
+ * The k ranges of one probe are adjacent: they are one group of ii2_intersect_ranges / ii2_andnot_ranges / ii2_atleast_ranges /
+ * the ranked calls / ii2_query_batch_groups / ii2_topk_batch with group_first[g] = g * k and the k segments repeated per group
+ * (every range entry point takes empty ranges).  An empty dictionary gives [0, 0).
+ * `where` says where probe_bytes, probe_off[n_probes + 1], probe_prefix[n_probes], list_first and list_end [n_probes * k each]
+ * live, all five together.  *n_found (host, may be NULL) = the number of non-empty ranges.
+ * All-or-nothing, every check before anything is launched: II2_EINVAL for a NULL array with n_probes > 0 (probe_prefix
+ * excepted), k == 0 or k > II2_MAX_LISTS, a dictionary that is NULL or of another device, probe_off that does not start at 0 or
+ * descends, a flag other than 0 / 1 (arrays on the device are checked there, in front of the lookup, which then writes nothing);
+ * II2_ERANGE for n_probes * k >= 2^32.  n_probes == 0 writes nothing and sets *n_found = 0.
+ * One wait per call.  Not a set operation: it takes no kernel path of ii2_ctx_paths.  One thread per (probe, dictionary), a
+ * workgroup per 256 consecutive probes of one dictionary; the bisection compares 8-byte keys and goes to the bytes on ties
+ * (dict_find.hip). */
+int ii2_dict_find(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint64_t n_probes, const uint8_t *probe_bytes,
+                  const uint64_t *probe_off /* n_probes + 1 */, const uint8_t *probe_prefix /* n_probes; NULL: all exact */, int where,
+                  uint64_t *list_first, uint64_t *list_end /* n_probes * k each */, uint64_t *n_found /* host, may be NULL */);
+/* The lookup's arithmetic, host only (no GPU needed): one probe against one host dictionary (term_off[n_terms + 1] from 0, as
+ * ii2_dict_create takes it) by the functions the kernel runs - the 8-byte keys, the comparison, the bisection, the prefix rule.  [*first, *end) as above.  II2_EINVAL: a NULL output, NULL term_off with n_terms > 0, NULL probe with probe_len > 0,
+ * term_off not ascending from 0, prefix other than 0 / 1.  II2_ERANGE: 2^31 or more terms. */
+int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, const uint8_t *probe, uint64_t probe_len,
+                    int prefix, uint64_t *first, uint64_t *end);
 /* The alignment of k resident dictionaries: no upload, no host pass over the terms, no sort — every term finds its place
  * in the k-way merge by bounded bisections in the other dictionaries (align.hip). */
 int ii2_align_dicts(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, ii2_align **out);

@@ -86,6 +86,8 @@ PROTOTYPES = {
     "ii2_seg_select": (C.c_int, [vp, vp, C.c_uint64, vp, vpp]),
     "ii2_dict_create": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, vpp]),
     "ii2_dict_free": (None, [vp]),
+    "ii2_dict_find": (C.c_int, [vp, C.c_uint32, vpp, C.c_uint64, vp, vp, vp, C.c_int, vp, vp, u64p]),
+    "ii2_term_bounds": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, u64p, u64p]),
     "ii2_align_dicts": (C.c_int, [vp, C.c_uint32, vpp, vpp]),
     "ii2_align_terms": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vpp]),
     "ii2_align_info": (C.c_int, [vp, u64p, C.POINTER(C.c_uint32)]),

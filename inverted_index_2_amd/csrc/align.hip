@@ -21,21 +21,7 @@
 
 #include "dv1_device.h"
 #include "internal.h"
-
-// a term dictionary resident in HBM: sorted, duplicate-free terms of one segment
-struct ii2_dict {
-    int device = 0;
-    uint64_t n = 0, n_bytes = 0;
-    uint8_t *d_bytes = nullptr;           // [n_bytes + 16]
-    uint64_t *d_off = nullptr;            // [n + 1] byte offsets
-    uint64_t *d_key = nullptr;            // [n] first 8 bytes, big-endian, zero padded
-    uint32_t long_terms = 0;              // 1: some term is longer than 8 bytes (a tie of the keys does not decide)
-    ~ii2_dict() {
-        if (d_bytes) (void)hipFree(d_bytes);
-        if (d_off) (void)hipFree(d_off);
-        if (d_key) (void)hipFree(d_key);
-    }
-};
+#include "term_device.h"
 
 namespace ii2 {
 
@@ -71,33 +57,11 @@ __global__ void k_dict_keys(const uint8_t *__restrict__ bytes, const uint64_t *_
     if (len > 8) atomicOr(bad, 4u);
 }
 
-// bytes.Compare of term (ka, bytes a[0 .. la)) with term (kb, b[0 .. lb)): -1 / 0 / 1.  The keys decide unless they tie.
-__device__ __forceinline__ int term_cmp(uint64_t ka, const uint8_t *__restrict__ a, uint64_t la, uint64_t kb, const uint8_t *__restrict__ b, uint64_t lb, bool long_terms) {
-    if (ka != kb) return ka < kb ? -1 : 1;
-    if (long_terms) {
-        const uint64_t m = la < lb ? la : lb;
-        for (uint64_t j = 8; j < m; j++) {
-            const uint8_t x = a[j], y = b[j];
-            if (x != y) return x < y ? -1 : 1;
-        }
-    }
-    return la == lb ? 0 : (la < lb ? -1 : 1);      // (equal keys, one a prefix of the other — also decides the zero padding)
-}
-
-struct TermRef { uint64_t key; const uint8_t *p; uint64_t len; };
-__device__ __forceinline__ TermRef term_of(const AlignDicts &d, uint32_t s, uint32_t i) {
-    const uint64_t b = d.off[s][i];
-    return TermRef{d.key[s][i], d.bytes[s] + b, d.off[s][i + 1] - b};
-}
+// the comparison (term_cmp), TermRef and the bisection (term_bound) are term_device.h's
+__device__ __forceinline__ TermRef term_of(const AlignDicts &d, uint32_t s, uint32_t i) { return term_at(TermDict{d.key[s], d.off[s], d.bytes[s]}, i); }
 // first index in [lo, hi) of dictionary s whose term is > x (upper = true) or >= x (upper = false)
 __device__ __forceinline__ uint32_t bound_in(const AlignDicts &d, uint32_t s, uint32_t lo, uint32_t hi, const TermRef &x, bool upper) {
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const TermRef y = term_of(d, s, mid);
-        const int c = term_cmp(y.key, y.p, y.len, x.key, x.p, x.len, d.long_terms != 0u);
-        if (c < 0 || (upper && c == 0)) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
+    return term_bound(TermDict{d.key[s], d.off[s], d.bytes[s]}, lo, hi, x, upper, d.long_terms != 0u);
 }
 
 // pos[g] = place of input term g in the k-way merge; head[place] = 1 when the term opens a run of equal terms.

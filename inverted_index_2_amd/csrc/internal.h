@@ -208,6 +208,21 @@ struct ii2_tomb {
     uint64_t n_words = 0;   // bitmap covers doc ids [0, 32*n_words)
 };
 
+// a term dictionary resident in HBM: sorted, duplicate-free terms of one segment (made by align.hip, looked up by dict_find.hip)
+struct ii2_dict {
+    int device = 0;
+    uint64_t n = 0, n_bytes = 0;
+    uint8_t *d_bytes = nullptr;           // [n_bytes + 16]
+    uint64_t *d_off = nullptr;            // [n + 1] byte offsets
+    uint64_t *d_key = nullptr;            // [n] first 8 bytes, big-endian, zero padded
+    uint32_t long_terms = 0;              // 1: some term is longer than 8 bytes (a tie of the keys does not decide)
+    ~ii2_dict() {
+        if (d_bytes) (void)hipFree(d_bytes);
+        if (d_off) (void)hipFree(d_off);
+        if (d_key) (void)hipFree(d_key);
+    }
+};
+
 void ii2_comm_destroy_internal(ii2_ctx *ctx);
 int ii2_seg_alloc_internal(ii2_ctx *ctx, uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_bytes, ii2_seg **out, bool with_meta = false);   // ctx->mu held
 int ii2_seg_rebase_internal(ii2_ctx *ctx, ii2_seg *seg, int world, const uint64_t *lo, const uint64_t *bo, const uint64_t *qo);            // ctx->mu held

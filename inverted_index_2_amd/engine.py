@@ -386,6 +386,43 @@ class Context:
         self._ck(self.lib.ii2_dict_create(self.h, _ptr(blob), _ptr(off), off.size - 1, II2_HOST, C.byref(h)))
         return Dictionary(self, h, terms)
 
+    def dict_find(self, dicts, terms, prefix=False):
+        """Term and prefix lookup on the device (ii2_dict_find): every term of `terms` (bytes) in every one of the k resident
+        dictionaries.  prefix: one flag for all the probes or one per probe - False: the term itself, [j, j + 1) where it is
+        list j and the empty [j, j) at its insertion point where it is absent; True: the run of the terms that start with it.
+        Returns (list_first, list_end, n_found): u64 arrays of shape (len(terms), k) and the number of non-empty ranges.  Row p,
+        flattened with the k segments repeated, is one group of the range entry points."""
+        terms = list(terms)
+        off = np.zeros(len(terms) + 1, np.uint64)
+        if terms:
+            off[1:] = np.cumsum([len(t) for t in terms])
+        blob = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
+        flags = np.full(len(terms), 1 if prefix else 0, np.uint8) if isinstance(prefix, (bool, int)) else _np(prefix, np.uint8)
+        if flags.size != len(terms):
+            raise ValueError("dict_find: one prefix flag per term")
+        first, end, found = self.dict_find_flat(dicts, blob, off, flags, II2_HOST)
+        return first.reshape(len(terms), len(dicts)), end.reshape(len(terms), len(dicts)), found
+
+    def dict_find_flat(self, dicts, probe_bytes, probe_off, probe_prefix=None, where: int = II2_HOST, list_first=None, list_end=None):
+        """The same from flat arrays, as the ABI takes them: numpy arrays with where == II2_HOST, DeviceArrays (the outputs
+        included: list_first / list_end of n_probes * k u64 each) with II2_DEVICE.  Returns (list_first, list_end, n_found)."""
+        arr = (C.c_void_p * len(dicts))(*[d.h for d in dicts])
+        if where == II2_HOST:
+            probe_bytes, probe_off = _np(probe_bytes, np.uint8), _np(probe_off, np.uint64)
+            n = probe_off.size - 1
+            if probe_prefix is not None:
+                probe_prefix = _np(probe_prefix, np.uint8)
+            list_first = np.zeros(max(n * len(dicts), 1), np.uint64)
+            list_end = np.zeros(max(n * len(dicts), 1), np.uint64)
+        else:
+            n = probe_off.count - 1
+        found = C.c_uint64()
+        self._ck(self.lib.ii2_dict_find(self.h, len(dicts), arr, n, _ptr(probe_bytes), _ptr(probe_off), _ptr(probe_prefix), where,
+                                        _ptr(list_first), _ptr(list_end), C.byref(found)))
+        if where == II2_HOST:
+            list_first, list_end = list_first[: n * len(dicts)], list_end[: n * len(dicts)]
+        return list_first, list_end, found.value
+
     def align_dicts(self, dicts) -> "Alignment":
         """The union of k resident dictionaries and every dictionary's place in it (ii2_align_dicts): no upload, no sort."""
         arr = (C.c_void_p * len(dicts))(*[d.h for d in dicts])
@@ -871,6 +908,11 @@ class Dictionary:
 
     def __init__(self, ctx: Context, h: C.c_void_p, terms=None):
         self.ctx, self.h, self.terms = ctx, h, terms
+
+    def find(self, terms, prefix=False):
+        """(list_first, list_end) u64 [len(terms)] of every term of `terms` in this dictionary (Context.dict_find with k = 1)."""
+        first, end, _ = self.ctx.dict_find([self], terms, prefix)
+        return first[:, 0].copy(), end[:, 0].copy()
 
     def free(self) -> None:
         if self.h:

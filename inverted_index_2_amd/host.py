@@ -66,6 +66,7 @@ def _lib_typed():
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_set_resolve.argtypes = [vp, C.c_int]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
@@ -209,6 +210,12 @@ class InvertedIndex(_Target):
 
     def put_removed(self, values) -> None:
         self._remove(values)
+
+    def set_resolve(self, mode: int) -> None:
+        """How intersect_many and intersect_top_batch turn their terms into lists (SetResolve): 0 bisects the host dictionaries,
+        1 probes resident dictionaries on the device (ii2_dict_find), -1 (the default) decides by the call's size.  The results
+        are the same in every mode."""
+        self._ck(self.lib.ii2h_set_resolve(self.h, int(mode)))
 
     def prefix_search(self, prefixes: List[bytes]) -> Dict[bytes, List[int]]:
         blob, off = _pack(list(prefixes))
