@@ -221,6 +221,57 @@ func (c *Ctx) NewDictionary(termBytes []byte, termOff []uint64) (*Dictionary, er
 
 func (d *Dictionary) Free() { C.ii2_dict_free(d.h); d.h = nil }
 
+// DictBuildStats mirrors ii2_dict_build_stats.
+type DictBuildStats struct {
+	Terms, Unique, Bytes uint64
+	MinLen, MaxLen       uint32
+	Passes               uint32
+}
+
+// DictBuild sorts and deduplicates terms on the device (ii2_dict_build): terms in any order, repeats allowed, at most 256 bytes
+// each.  The dictionary holds the sorted distinct terms (bytes.Compare order, file/types.go:24-26) and termID[i] is the index of
+// terms[i] in it - the listID of SegBuild for the occurrences' values.
+func (c *Ctx) DictBuild(terms [][]byte) (*Dictionary, []uint32, DictBuildStats, error) {
+	off := make([]uint64, len(terms)+1)
+	var blob []byte
+	for i, t := range terms {
+		blob = append(blob, t...)
+		off[i+1] = uint64(len(blob))
+	}
+	blob = append(blob, 0) // never an empty array
+	ids := make([]uint32, len(terms)+1)
+	var d *C.ii2_dict
+	var st C.ii2_dict_build_stats
+	if rc := C.ii2_dict_build(c.h, C.uint64_t(len(terms)), (*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off), C.II2_HOST, &d,
+		(*C.uint32_t)(unsafe.Pointer(&ids[0])), &st); rc != 0 {
+		return nil, nil, DictBuildStats{}, c.err("dict build", rc)
+	}
+	return &Dictionary{d}, ids[:len(terms)], DictBuildStats{uint64(st.n_terms), uint64(st.n_unique), uint64(st.n_bytes), uint32(st.min_len),
+		uint32(st.max_len), uint32(st.n_passes)}, nil
+}
+
+// DictInfo returns the number of terms of a dictionary and the bytes they take (ii2_dict_info).
+func (d *Dictionary) DictInfo() (nTerms, nBytes uint64) {
+	var n, b C.uint64_t
+	C.ii2_dict_info(d.h, &n, &b)
+	return uint64(n), uint64(b)
+}
+
+// DictExport copies a dictionary's terms to the host, in its order (ii2_dict_export).
+func (c *Ctx) DictExport(d *Dictionary) ([][]byte, error) {
+	n, nb := d.DictInfo()
+	blob := make([]byte, nb+1)
+	off := make([]uint64, n+1)
+	if rc := C.ii2_dict_export(c.h, d.h, (*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off)); rc != 0 {
+		return nil, c.err("dict export", rc)
+	}
+	terms := make([][]byte, n)
+	for i := range terms {
+		terms[i] = blob[off[i]:off[i+1]]
+	}
+	return terms, nil
+}
+
 // DictFind looks terms up in k resident dictionaries on the device (ii2_dict_find): the step from a query's terms to the list
 // ranges every range call takes.  prefix == nil: every probe is a term - [j, j+1) where dictionary s holds it as list j, the
 // empty [j, j) at its insertion point where it does not; prefix[p] == 1: the run of the terms that start with probe p

@@ -20,6 +20,7 @@
  *     blocks and < 2^30 term slots; ii2_align_terms takes < 2^31 terms; one segment holds < 2^31
  *     lists, < 2^31 blocks and < 4 GiB of payload (split larger inputs into several segments / calls);
  *     ii2_seg_build takes < 2^32 pairs for < 2^31 lists (the encoder's limits on the segment it makes apply unchanged);
+ *     ii2_dict_build takes < 2^31 terms of at most II2_DICT_BUILD_MAX_TERM = 256 bytes each (longer terms: sort on the host, ii2_dict_create);
  *     ii2_query_batch takes <= 2^20 queries whose result bounds (AND: the shortest operand, OR: the postings of
  *     its ranges) add up to < 2^32 ids; ii2_query_batch_groups takes <= 2^20 queries whose result bounds (the postings of each query's
  *     smallest required group) add up to < 2^32 ids, a query of at most II2_MAX_LISTS non-empty lists - required and excluded -
@@ -195,6 +196,50 @@ int ii2_dict_find(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint64
  * term_off not ascending from 0, prefix other than 0 / 1.  II2_ERANGE: 2^31 or more terms. */
 int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, const uint8_t *probe, uint64_t probe_len,
                     int prefix, uint64_t *first, uint64_t *end);
+/* Dictionary build step (bulk Put, in front of ii2_seg_build).  Replaces the std::sort over every term occurrence, the
+ * std::unique and the string bisection per occurrence that a bulk Put does on the host before ii2_seg_build (order = bytes.Compare,
+ * file/types.go:24-26).  Input: n_terms terms in any order, repeats allowed, any bytes, the empty term included - term i is
+ * term_bytes[term_off[i] .. term_off[i + 1]).  *out is a dictionary like the one ii2_dict_create makes from the sorted,
+ * duplicate-free terms: the same offsets, bytes, 8-byte keys and long-terms flag, usable by ii2_dict_find, ii2_align_dicts,
+ * ii2_seg_select_aligned* and ii2_dict_free.  term_id[i] (may be NULL) is the index of input term i in it.
+ * `where` says where term_bytes, term_off and term_id live, all three together; with II2_DEVICE term_id is directly the list_id
+ * of ii2_seg_build(ctx, n_unique, n_terms, term_id, values, II2_DEVICE, ...).  n_terms == 0: the empty dictionary and all-zero
+ * stats (the arrays may be NULL).
+ * Every check happens before anything the caller sees is written, and *out stays NULL on any error: II2_EINVAL for a NULL
+ * array with n_terms > 0 or a term_off that does not start at 0 or descends (arrays on the device are checked there, in the
+ * first kernel); II2_ERANGE for 2^31 or more terms or a term longer than II2_DICT_BUILD_MAX_TERM.  After an error nothing stays
+ * allocated.  The library never reads beyond term_bytes[term_off[n_terms]): the caller's arrays carry no padding.
+ * On the device (dict_build.hip): bytes.Compare order is the order of (chunk 0, chunk 1, ..., length) with chunk c = bytes
+ * [8c, 8c + 8) big-endian, zero padded, so the terms are sorted by a stable least-significant-digit radix sort of (64-bit key,
+ * 32-bit index) pairs, 8-bit digits, the length first and then the chunks from the last to the first.  Only the bytes that can
+ * differ get a pass: one kernel reduces OR and AND of every chunk and of the lengths, stats->n_passes is what
+ * ii2_dict_build_plan returns for the same terms (terms behind a common prefix skip its passes, identical terms run none).
+ * Then equal neighbours are numbered and the dictionary is gathered.  The call waits three times, whatever n_terms and the
+ * number of passes: for the plan, for the dictionary's sizes, and at the end.  No workgroup of it waits for another.  Not a
+ * set operation: it takes no kernel path of ii2_ctx_paths. */
+#define II2_DICT_BUILD_MAX_TERM 256u     /* bytes per term; longer: II2_ERANGE (sort on the host, ii2_dict_create) */
+typedef struct {
+    uint64_t n_terms;    /* terms read */
+    uint64_t n_unique;   /* distinct terms = terms of the dictionary */
+    uint64_t n_bytes;    /* bytes of the dictionary */
+    uint32_t min_len, max_len;
+    uint32_t n_passes;   /* radix passes run */
+    uint32_t pad;
+} ii2_dict_build_stats;  /* 40 bytes */
+int ii2_dict_build(ii2_ctx *ctx, uint64_t n_terms, const uint8_t *term_bytes, const uint64_t *term_off /* n_terms + 1, from 0 */,
+                   int where, ii2_dict **out, uint32_t *term_id /* n_terms, may be NULL */, ii2_dict_build_stats *stats /* may be NULL */);
+/* The sizes of a dictionary (either output may be NULL) and its arrays copied to the host: term_bytes[n_bytes], term_off[n_terms + 1]
+ * (either may be NULL). */
+int ii2_dict_info(const ii2_dict *dict, uint64_t *n_terms, uint64_t *n_bytes);
+int ii2_dict_export(ii2_ctx *ctx, const ii2_dict *dict, uint8_t *term_bytes, uint64_t *term_off);
+/* The build's arithmetic, host only (no GPU needed), by the very functions the driver and the kernels use.
+ * ii2_term_chunk: the key of chunk c of a term - bytes [8c, 8c + 8) big-endian, zero padded (chunk 0 is the dictionary's key).
+ * ii2_dict_build_plan: the passes ii2_dict_build would run for these terms (host arrays) - pos_pass[p] = 1 when byte position p
+ * (0 .. 255) gets a radix pass, len_pass[b] = 1 when byte b (0, 1) of the lengths gets one, *n_passes their number, the least and
+ * the greatest length.  Same errors as the call (and II2_EINVAL for a NULL output). */
+int ii2_term_chunk(const uint8_t *term, uint64_t len, uint32_t c, uint64_t *key);
+int ii2_dict_build_plan(const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, uint8_t *pos_pass /* 256 */,
+                        uint8_t *len_pass /* 2 */, uint32_t *n_passes, uint32_t *min_len, uint32_t *max_len);
 /* The alignment of k resident dictionaries: no upload, no host pass over the terms, no sort — every term finds its place
  * in the k-way merge by bounded bisections in the other dictionaries (align.hip). */
 int ii2_align_dicts(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, ii2_align **out);

@@ -30,6 +30,11 @@ class BuildStats(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("n_postings", C.c_uint64), ("n_nonempty", C.c_uint64), ("n_passes", C.c_uint32)]
 
 
+class DictBuildStats(C.Structure):
+    _fields_ = [("n_terms", C.c_uint64), ("n_unique", C.c_uint64), ("n_bytes", C.c_uint64), ("min_len", C.c_uint32), ("max_len", C.c_uint32),
+                ("n_passes", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class CountStats(C.Structure):
     _fields_ = [("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64),
                 ("n_windows", C.c_uint32)]
@@ -88,6 +93,11 @@ PROTOTYPES = {
     "ii2_dict_free": (None, [vp]),
     "ii2_dict_find": (C.c_int, [vp, C.c_uint32, vpp, C.c_uint64, vp, vp, vp, C.c_int, vp, vp, u64p]),
     "ii2_term_bounds": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, u64p, u64p]),
+    "ii2_dict_build": (C.c_int, [vp, C.c_uint64, vp, vp, C.c_int, vpp, vp, C.POINTER(DictBuildStats)]),
+    "ii2_dict_info": (C.c_int, [vp, u64p, u64p]),
+    "ii2_dict_export": (C.c_int, [vp, vp, vp, vp]),
+    "ii2_term_chunk": (C.c_int, [vp, C.c_uint64, C.c_uint32, u64p]),
+    "ii2_dict_build_plan": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ii2_align_dicts": (C.c_int, [vp, C.c_uint32, vpp, vpp]),
     "ii2_align_terms": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vpp]),
     "ii2_align_info": (C.c_int, [vp, u64p, C.POINTER(C.c_uint32)]),

@@ -38,6 +38,7 @@ constexpr size_t II2_MAIL_COUNT = 200;     // word of h_mail that receives the r
 constexpr size_t II2_MAIL_LB_OWN = 24;     // the look-back error word behind a synchronous call's own launch ...
 constexpr size_t II2_MAIL_LB_PENDING = 25; // ... and in front of it, as the asynchronous launches before it left it
 constexpr size_t II2_MAIL_BUILD = 32;      // ii2_seg_build: {unique keys, non-empty lists, bad-id word} (seg_build.hip)
+constexpr size_t II2_MAIL_DICT_BUILD = 40; // ii2_dict_build: the plan's reduction words, then the dictionary's byte count (dict_build.hip: 70 words)
 constexpr size_t II2_MAIL_COMM = 256;      // all-gatherv: {count, cap} of this rank, then of every rank (2 + 2 * II2_MAX_RANKS words)
 
 struct ii2_ctx {

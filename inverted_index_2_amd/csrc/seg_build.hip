@@ -5,7 +5,8 @@
 // least-significant-digit radix sort (8-bit digits, only the digits that can differ), equal neighbours are dropped, the
 // list offsets are looked up and the two-pass DV1 encoder of api.cpp writes the segment.  No library (scan.hip is the
 // precedent), and NO WORKGROUP EVER WAITS FOR ANOTHER: each radix pass is the classic three steps on the context's
-// stream, ordered by the stream alone.
+// stream, ordered by the stream alone.  The parts of a pass that ii2_dict_build's sort of (key, index) pairs runs as well - the
+// digit counting, the wave's ballot ranking, the digit scan of the tile, the staging slot - live in radix_device.h.
 //
 //   k_sb_hist      one workgroup per tile of SB_TILE keys: per-wave digit counts in LDS, the tile's 256 counts stored
 //                  digit-major (count[digit * n_tiles + tile]), so ONE exclusive scan of the table (scan_excl_u32) gives
@@ -26,35 +27,12 @@
 // One readback (unique keys, non-empty lists, the bad-id word) and with it one wait, then the encoder.
 #include <algorithm>
 
-#include "dv1_device.h"
-#include "internal.h"
+#include "radix_device.h"
 
 namespace ii2 {
 
-constexpr uint32_t SB_THREADS = 256;
-constexpr uint32_t SB_WAVES = SB_THREADS / 64;
-constexpr uint32_t SB_ITEMS = 16;                           // keys per thread
-constexpr uint32_t SB_TILE = SB_THREADS * SB_ITEMS;         // 4096 keys per workgroup
-constexpr uint32_t SB_WAVE_KEYS = 64 * SB_ITEMS;            // consecutive keys of the tile one wave owns
-constexpr uint32_t SB_DIGITS = 256;
-static_assert(SB_DIGITS == SB_THREADS, "one thread per digit where the tile's counts are combined");
-
 // control words of one call in the context's mailbox (u64 each)
 constexpr uint32_t SB_CTL_UNIQUE = 0, SB_CTL_NONEMPTY = 1, SB_CTL_BAD = 2, SB_CTL_WORDS = 3;
-
-__device__ __forceinline__ uint32_t sb_digit(uint64_t key, uint32_t shift) { return (uint32_t)(key >> shift) & (SB_DIGITS - 1u); }
-
-// exclusive scan of one u32 per thread over the 256 threads of a workgroup (wsum: SB_WAVES words of LDS)
-__device__ __forceinline__ uint32_t sb_wg_excl_scan(uint32_t v, uint32_t *wsum) {
-    const int l = lane_id(), w = (int)threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan(v);
-    if (l == 63) wsum[w] = incl;
-    __syncthreads();
-    uint32_t pre = 0;
-    for (int k = 0; k < (int)SB_WAVES; k++)
-        if (k < w) pre += wsum[k];
-    return pre + incl - v;
-}
 
 // PACK (first pass): key[i] = list_id[i] << 32 | values[i] is formed, stored and counted; a list_id >= n_lists leaves
 // n - i in ctl[SB_CTL_BAD] (the largest wins: the first bad pair).  Otherwise the keys are read.
@@ -82,21 +60,10 @@ __global__ __launch_bounds__(SB_THREADS) void k_sb_hist(const uint32_t *__restri
                 key = keys[i];
             }
         }
-        const uint32_t d = sb_digit(key, shift);
-        // valid lanes are a prefix of the wave; a wave whose keys share the digit (high digits mostly do) adds once
-        const uint64_t vm = __ballot(valid);
-        if (vm == 0) continue;
-        const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
-        if (__ballot(valid && d != d0) == 0) {
-            if (lane_id() == 0) atomicAdd(&wcnt[w][d0], (uint32_t)__popcll(vm));
-        } else if (valid) {
-            atomicAdd(&wcnt[w][d], 1u);
-        }
+        sb_hist_count(wcnt[w], sb_digit(key, shift), valid);
     }
     __syncthreads();
-    uint32_t c = 0;
-    for (uint32_t k = 0; k < SB_WAVES; k++) c += wcnt[k][tid];
-    count[(size_t)tid * n_tiles + blockIdx.x] = c;
+    sb_hist_store(wcnt, n_tiles, count);
 }
 
 __global__ __launch_bounds__(SB_THREADS) void k_sb_scatter(const uint64_t *__restrict__ in, uint64_t *__restrict__ out, uint64_t n, uint32_t n_tiles,
@@ -117,43 +84,16 @@ __global__ __launch_bounds__(SB_THREADS) void k_sb_scatter(const uint64_t *__res
         key[j] = loc < nv ? in[tile0 + loc] : 0ull;
     }
     __syncthreads();
-    volatile uint32_t *my_cnt = wcnt[w];
     const uint64_t lt = (1ull << l) - 1ull;
 #pragma unroll
-    for (uint32_t j = 0; j < SB_ITEMS; j++) {
-        const bool valid = w * SB_WAVE_KEYS + j * 64u + l < nv;
-        const uint32_t d = sb_digit(key[j], shift);
-        uint64_t m = __ballot(valid);
-#pragma unroll
-        for (uint32_t b = 0; b < 8; b++) {
-            const bool bit = (d >> b) & 1u;
-            const uint64_t bal = __ballot(bit);
-            m &= bit ? bal : ~bal;
-        }
-        // m: the valid lanes whose key has this lane's digit; the lowest of them keeps the wave's counter
-        const int leader = m ? __ffsll((unsigned long long)m) - 1 : 0;
-        uint32_t old = 0;
-        if (valid && (int)l == leader) {
-            old = my_cnt[d];
-            my_cnt[d] = old + (uint32_t)__popcll(m);
-        }
-        old = (uint32_t)__shfl((int)old, leader, 64);
-        rank[j] = old + (uint32_t)__popcll(m & lt);
-        __builtin_amdgcn_wave_barrier();      // (the next item's leaders read what this item's leaders stored)
-    }
+    for (uint32_t j = 0; j < SB_ITEMS; j++) rank[j] = sb_wave_rank(sb_digit(key[j], shift), w * SB_WAVE_KEYS + j * 64u + l < nv, wcnt[w], l, lt);
     __syncthreads();
-    {   // thread d: where digit d starts in the tile (exclusive scan of the digit totals) and, from it, every wave's first slot
-        uint32_t c[SB_WAVES], tot = 0;
-        for (uint32_t k = 0; k < SB_WAVES; k++) { c[k] = wcnt[k][tid]; tot += c[k]; }
-        uint32_t at = sb_wg_excl_scan(tot, wsum);
-        goff[tid] = base[(size_t)tid * n_tiles + blockIdx.x] - at;      // (u32 arithmetic: every index below is < n < 2^32)
-        for (uint32_t k = 0; k < SB_WAVES; k++) { wcnt[k][tid] = at; at += c[k]; }
-    }
+    sb_tile_bases(wcnt, goff, wsum, base, n_tiles);
     __syncthreads();
 #pragma unroll
     for (uint32_t j = 0; j < SB_ITEMS; j++) {
         const bool valid = w * SB_WAVE_KEYS + j * 64u + l < nv;
-        if (valid) stage[wcnt[w][sb_digit(key[j], shift)] + rank[j]] = key[j];
+        if (valid) stage[sb_stage_slot(wcnt, w, sb_digit(key[j], shift), rank[j])] = key[j];
     }
     __syncthreads();
     for (uint32_t s = tid; s < nv; s += SB_THREADS) {
@@ -236,19 +176,6 @@ __global__ __launch_bounds__(SB_THREADS) void k_sb_offsets(const uint32_t *__res
 using namespace ii2;
 
 namespace {
-// the call's device block: handed back on every exit path, after the stream has passed whatever still reads or writes it
-struct BuildBlock {
-    hipStream_t stream;
-    void *p = nullptr;
-    explicit BuildBlock(hipStream_t s) : stream(s) {}
-    ~BuildBlock() {
-        if (!p) return;
-        (void)hipStreamSynchronize(stream);
-        dm_free(p);
-    }
-    BuildBlock(const BuildBlock &) = delete;
-};
-
 uint32_t bit_width64(uint64_t x) { return x ? 64u - (uint32_t)__builtin_clzll((unsigned long long)x) : 0u; }
 }  // namespace
 

@@ -31,6 +31,13 @@ __host__ __device__ __forceinline__ uint64_t term_key(const uint8_t *__restrict_
     return kk;
 }
 
+// the key of chunk c of the term: bytes [8c, 8c + 8) big-endian, zero padded (chunk 0 is term_key).  bytes.Compare order is the
+// order of the tuple (chunk 0, chunk 1, ..., length): a zero byte past a term's end ties with a real one, the length decides.
+__host__ __device__ __forceinline__ uint64_t term_chunk(const uint8_t *__restrict__ p, uint64_t len, uint32_t c) {
+    const uint64_t at = 8ull * c;
+    return at < len ? term_key(p + at, len - at) : 0ull;
+}
+
 // bytes.Compare of term (ka, bytes a[0 .. la)) with term (kb, b[0 .. lb)): -1 / 0 / 1.  The keys decide unless they tie.
 __host__ __device__ __forceinline__ int term_cmp(uint64_t ka, const uint8_t *__restrict__ a, uint64_t la, uint64_t kb, const uint8_t *__restrict__ b, uint64_t lb, bool long_terms) {
     if (ka != kb) return ka < kb ? -1 : 1;

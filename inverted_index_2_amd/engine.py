@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -385,6 +385,33 @@ class Context:
         h = C.c_void_p()
         self._ck(self.lib.ii2_dict_create(self.h, _ptr(blob), _ptr(off), off.size - 1, II2_HOST, C.byref(h)))
         return Dictionary(self, h, terms)
+
+    def build_dictionary(self, terms, term_off=None, where: int = II2_HOST, want_ids: bool = True):
+        """Dictionary build step (ii2_dict_build): terms in any order, repeats allowed -> the resident dictionary of the sorted,
+        duplicate-free terms and every input term's index in it, sorted and deduplicated on the device.  `terms` is a list of
+        bytes, or - with term_off, u64 [n + 1] from 0 - the flat u8 bytes: numpy arrays with where == II2_HOST, DeviceArrays
+        with II2_DEVICE.  Returns (Dictionary, term_id, DictBuildStats): term_id is a u32 numpy array, or with II2_DEVICE a
+        DeviceArray that ii2_seg_build takes as its list_id (None with want_ids=False)."""
+        if term_off is None:
+            terms = list(terms)
+            term_off = np.zeros(len(terms) + 1, np.uint64)
+            if terms:
+                term_off[1:] = np.cumsum([len(t) for t in terms])
+            terms = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
+            where = II2_HOST
+        if where == II2_HOST:
+            terms, term_off = _np(terms, np.uint8), _np(term_off, np.uint64)
+            n = term_off.size - 1
+            ids = np.zeros(max(n, 1), np.uint32) if want_ids else None
+        else:
+            n = term_off.count - 1
+            ids = DeviceArray(self, max(n, 1), np.uint32) if want_ids else None
+        h, st = C.c_void_p(), DictBuildStats()
+        self._ck(self.lib.ii2_dict_build(self.h, n, _ptr(terms) if n else None, _ptr(term_off) if n else None, where, C.byref(h),
+                                         _ptr(ids) if ids is not None else None, C.byref(st)))
+        if where == II2_HOST and ids is not None:
+            ids = ids[:n]
+        return Dictionary(self, h), ids, st
 
     def dict_find(self, dicts, terms, prefix=False):
         """Term and prefix lookup on the device (ii2_dict_find): every term of `terms` (bytes) in every one of the k resident
@@ -913,6 +940,25 @@ class Dictionary:
         """(list_first, list_end) u64 [len(terms)] of every term of `terms` in this dictionary (Context.dict_find with k = 1)."""
         first, end, _ = self.ctx.dict_find([self], terms, prefix)
         return first[:, 0].copy(), end[:, 0].copy()
+
+    def info(self):
+        """(number of terms, bytes of the terms) - ii2_dict_info"""
+        n, b = C.c_uint64(), C.c_uint64()
+        self.ctx._ck(self.ctx.lib.ii2_dict_info(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def export_flat(self):
+        """(u8 bytes [n_bytes], u64 offsets [n + 1]) copied to the host - ii2_dict_export"""
+        n, nb = self.info()
+        blob, off = np.zeros(max(nb, 1), np.uint8), np.zeros(n + 1, np.uint64)
+        self.ctx._ck(self.ctx.lib.ii2_dict_export(self.ctx.h, self.h, _ptr(blob), _ptr(off)))
+        return blob[:nb], off
+
+    def export(self):
+        """the terms as a list of bytes, in the dictionary's order"""
+        blob, off = self.export_flat()
+        raw = blob.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(off.size - 1)]
 
     def free(self) -> None:
         if self.h:

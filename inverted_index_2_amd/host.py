@@ -67,6 +67,7 @@ def _lib_typed():
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_set_resolve.argtypes = [vp, C.c_int]
+        lib.ii2h_set_build.argtypes = [vp, C.c_int]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
@@ -135,6 +136,12 @@ class _Target:
     def put(self, terms: List[bytes], val: int) -> None:
         blob, off = _pack(list(terms))
         self._ck(self.lib.ii2h_put(self.h, blob.ctypes.data, off.ctypes.data, len(terms), val))
+
+    def set_build(self, mode: int) -> None:
+        """Where put_batch sorts, deduplicates and looks up its terms (SetBuild): 0 on the host, 1 on the device (ii2_dict_build;
+        the built dictionary stays resident with the segment), -1 (the default) decides by the batch's size.  A batch with a term
+        above 256 bytes takes the host route under every mode.  The segment and its files are the same either way."""
+        self._ck(self.lib.ii2h_set_build(self.h, int(mode)))
 
     def put_batch(self, docs: List[Tuple[List[bytes], int]]) -> None:
         """Many puts at once, docs = [(terms, val), ...]: one merged-quality segment per shard that receives a term (PutBatch:

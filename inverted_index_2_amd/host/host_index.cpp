@@ -24,6 +24,7 @@
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //   SetResolve(mode)                                 additive: the two bulk calls look their terms up on the host or on the device (ii2_dict_find)
+//   SetBuild(mode)                                   additive: PutBatch sorts and looks up its terms on the host or on the device (ii2_dict_build)
 //
 // Built as its own library (libii2_host.so) that only sees include/ii2.h and links libii2_hip.so:
 // the product library exports the C ABI and nothing else.  A small C facade (ii2h_*) at the bottom
@@ -305,6 +306,7 @@ class Shard {
     // (doc, term) is one (index of the term, val) pair, and ONE ii2_seg_build call sorts and encodes them into one ordinary
     // (non-direct) segment.  No tombstone filter, as in Put.  No docs or no terms: no segment.
     void PutBatch(const std::vector<std::pair<std::vector<Term>, uint32_t>> &docs) {
+        if (build_on_device(docs)) { put_batch_device(docs); return; }
         std::vector<Term> terms;
         for (auto &d : docs) terms.insert(terms.end(), d.first.begin(), d.first.end());
         std::sort(terms.begin(), terms.end(), term_less);
@@ -325,6 +327,18 @@ class Shard {
         }
         std::lock_guard<std::mutex> g(mu_);
         add(std::move(seg));
+    }
+
+    // additive: where PutBatch sorts, deduplicates and looks up its terms - 0: on the host (std::sort, std::unique and one
+    // bisection per occurrence), 1: on the device (ii2_dict_build; the occurrences' indices never leave it), -1 (the default):
+    // the device from BUILD_MIN_TERMS term occurrences per batch - the smallest probed size from which the device route's
+    // [min - max] lies wholly below the host route's (scripts/dict_build_probe.py case r).  A batch with a term
+    // above II2_DICT_BUILD_MAX_TERM takes the host route under every mode.  The segment, its files and every later answer are
+    // the same on both routes.
+    static constexpr uint64_t BUILD_MIN_TERMS = 8192;
+    void SetBuild(int mode) {
+        if (mode < -1 || mode > 1) throw Error("set build: mode is -1, 0 or 1");
+        build_mode_.store(mode);
     }
 
     // shard.go:72-75 + makeIterator :253-278 — merged view of all segments, [min,max] inclusive, no tombstones
@@ -427,6 +441,60 @@ class Shard {
    private:
 
     // file.NewWriter + Close for a device-resident segment: both files, under their final names only when complete
+    bool build_on_device(const std::vector<std::pair<std::vector<Term>, uint32_t>> &docs) const {
+        const int mode = build_mode_.load();
+        if (mode == 0) return false;
+        uint64_t n = 0;
+        for (auto &d : docs)
+            for (auto &t : d.first) {
+                if (t.size() > II2_DICT_BUILD_MAX_TERM) return false;
+                n++;
+            }
+        return n > 0 && (mode == 1 || n >= BUILD_MIN_TERMS);
+    }
+    // PutBatch's device route: every term occurrence flat -> ii2_dict_build (the arrays staged in device buffers, so that the
+    // occurrences' indices stay there) -> ii2_seg_build on those indices -> ii2_dict_export for Segment::terms and the term
+    // file.  The built dictionary becomes the segment's resident one: its first device lookup uploads nothing.
+    void put_batch_device(const std::vector<std::pair<std::vector<Term>, uint32_t>> &docs) {
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> off{0};
+        std::vector<uint32_t> vals;
+        for (auto &d : docs)
+            for (auto &t : d.first) {
+                bytes.insert(bytes.end(), t.begin(), t.end());
+                off.push_back(bytes.size());
+                vals.push_back(d.second);
+            }
+        const uint64_t n = vals.size();
+        DevMem d_bytes(ctx_), d_off(ctx_), d_ids(ctx_), d_vals(ctx_);
+        ck(ctx_, ii2_dev_alloc(ctx_, bytes.size() + 16, &d_bytes.p), "s: put batch");
+        ck(ctx_, ii2_dev_alloc(ctx_, off.size() * sizeof(uint64_t), &d_off.p), "s: put batch");
+        ck(ctx_, ii2_dev_alloc(ctx_, n * sizeof(uint32_t), &d_ids.p), "s: put batch");
+        ck(ctx_, ii2_dev_alloc(ctx_, n * sizeof(uint32_t), &d_vals.p), "s: put batch");
+        if (!bytes.empty()) ck(ctx_, ii2_copy_h2d(ctx_, d_bytes.p, bytes.data(), bytes.size()), "s: put batch");
+        ck(ctx_, ii2_copy_h2d(ctx_, d_off.p, off.data(), off.size() * sizeof(uint64_t)), "s: put batch");
+        ck(ctx_, ii2_copy_h2d(ctx_, d_vals.p, vals.data(), n * sizeof(uint32_t)), "s: put batch");
+        auto dict = std::make_unique<DictHandle>();
+        ck(ctx_, ii2_dict_build(ctx_, n, (const uint8_t *)d_bytes.p, (const uint64_t *)d_off.p, II2_DEVICE, &dict->h, (uint32_t *)d_ids.p, nullptr), "s: put batch: dictionary");
+        uint64_t n_unique = 0, n_bytes = 0;
+        ii2_dict_info(dict->h, &n_unique, &n_bytes);
+        ii2_seg *s = nullptr;
+        ck(ctx_, ii2_seg_build(ctx_, n_unique, n, (const uint32_t *)d_ids.p, (const uint32_t *)d_vals.p, II2_DEVICE, &s, nullptr), "s: put batch");
+        auto handle = std::make_shared<SegHandle>(s);
+        std::vector<uint8_t> tb(n_bytes + 1);
+        std::vector<uint64_t> to(n_unique + 1);
+        ck(ctx_, ii2_dict_export(ctx_, dict->h, tb.data(), to.data()), "s: put batch: dictionary");
+        std::vector<Term> terms(n_unique);
+        for (uint64_t i = 0; i < n_unique; i++) terms[i].assign((const char *)tb.data() + to[i], to[i + 1] - to[i]);
+        Segment seg{now_ns(), std::move(terms), std::move(handle)};
+        seg.dict = std::move(dict);
+        if (!basedir_.empty()) {   // written like a merged segment: term file + value file
+            try { write_segment(ctx_, seg); }
+            catch (const std::exception &e) { throw Error(std::string("index put batch: ") + e.what()); }
+        }
+        std::lock_guard<std::mutex> g(mu_);
+        add(std::move(seg));
+    }
     void write_segment(ii2_ctx *ctx, const Segment &s) const {
         const std::string key = std::to_string(s.key);
         file::TermFile tf;
@@ -680,6 +748,7 @@ class Shard {
     }
 
     ii2_ctx *ctx_;
+    std::atomic<int> build_mode_{-1};                      // SetBuild
     std::string basedir_;                                  // empty: no files
     mutable std::mutex mu_;                                // Segments.m and RemovedLists.m in one: guards the two members below
     std::vector<std::shared_ptr<Segment>> segments_;       // sorted by term count
@@ -1438,6 +1507,13 @@ class InvertedIndex {
         if (mode < -1 || mode > 1) throw Error("set resolve: mode is -1, 0 or 1");
         resolve_mode_.store(mode);
     }
+    // additive: where every shard's PutBatch sorts and looks up its terms (Shard::SetBuild), for the shards there are and the ones to come
+    void SetBuild(int mode) {
+        if (mode < -1 || mode > 1) throw Error("set build: mode is -1, 0 or 1");
+        std::lock_guard<std::mutex> g(mu_);
+        build_mode_ = mode;
+        for (auto &s : shards_) s.second->SetBuild(mode);
+    }
     size_t ShardCount() const { std::lock_guard<std::mutex> g(mu_); return shards_.size(); }
     size_t SegmentCount() const { size_t n = 0; for (auto &s : shard_list()) n += s.second->SegmentCount(); return n; }      // over all shards
     Shard *OnlyShard() { std::lock_guard<std::mutex> g(mu_); return shards_.empty() ? nullptr : shards_.begin()->second.get(); }
@@ -1472,11 +1548,13 @@ class InvertedIndex {
                 if (!file::fs::create_directory(dir, ec) && ec) throw Error("new shard: " + dir + ": " + ec.message());
             }
             it = shards_.emplace(key, std::make_unique<Shard>(ctx_, dir)).first;
+            it->second->SetBuild(build_mode_);
         }
         return *it->second;
     }
     ii2_ctx *ctx_;
     std::atomic<int> resolve_mode_{-1};                    // SetResolve
+    int build_mode_ = -1;                                  // SetBuild (guarded by mu_)
     std::string basedir_;
     mutable std::mutex mu_;                                // guards shards_ (the map, not the shards) and workers_
     std::vector<ii2_ctx *> workers_;                       // contexts of Merge's workers 1..n-1 (created on demand)
@@ -1685,6 +1763,9 @@ int ii2h_set_resolve(ii2h_target *t, int mode) {
         if (!t->index) throw Error("set resolve: not an index");
         t->index->SetResolve(mode);
     });
+}
+int ii2h_set_build(ii2h_target *t, int mode) {
+    H_TRY(t, { if (t->index) t->index->SetBuild(mode); else t->shard->SetBuild(mode); });
 }
 int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req, uint64_t n_q,
                          uint64_t *n_results) {
