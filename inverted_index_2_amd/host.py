@@ -68,6 +68,9 @@ def _lib_typed():
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_set_resolve.argtypes = [vp, C.c_int]
         lib.ii2h_set_build.argtypes = [vp, C.c_int]
+        lib.ii2h_set_first_cap.argtypes = [vp, C.c_uint64]
+        lib.ii2h_second_calls.restype = C.c_uint64
+        lib.ii2h_second_calls.argtypes = [vp]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
@@ -223,6 +226,16 @@ class InvertedIndex(_Target):
         1 probes resident dictionaries on the device (ii2_dict_find), -1 (the default) decides by the call's size.  The results
         are the same in every mode."""
         self._ck(self.lib.ii2h_set_resolve(self.h, int(mode)))
+
+    def set_first_cap(self, ids: int) -> None:
+        """For the tests: the first buffer of every call that may need a second one holds at most `ids` ids (SetFirstCap: 1 to
+        2**22, the default), so that a small index reaches the second call."""
+        self._ck(self.lib.ii2h_set_first_cap(self.h, int(ids)))
+
+    @property
+    def second_calls(self) -> int:
+        """How many calls on this index have been made a second time because the first buffer was too small."""
+        return self.lib.ii2h_second_calls(self.h)
 
     def prefix_search(self, prefixes: List[bytes]) -> Dict[bytes, List[int]]:
         blob, off = _pack(list(prefixes))

@@ -24,6 +24,7 @@
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //   SetResolve(mode)                                 additive: the two bulk calls look their terms up on the host or on the device (ii2_dict_find)
+//   SetFirstCap(ids) / SecondCalls()                 additive, for the tests: the first buffer of the calls that may need a second one (two_call)
 //   SetBuild(mode)                                   additive: PutBatch sorts and looks up its terms on the host or on the device (ii2_dict_build)
 //
 // Built as its own library (libii2_host.so) that only sees include/ii2.h and links libii2_hip.so:
@@ -81,7 +82,8 @@ struct DevMem {                // device buffer freed at scope exit
     void *p = nullptr;
     explicit DevMem(ii2_ctx *c) : ctx(c) {}
     ~DevMem() { if (p) ii2_dev_free(ctx, p); }
-    DevMem(const DevMem &) = delete;
+    DevMem(DevMem &&o) : ctx(o.ctx), p(o.p) { o.p = nullptr; }
+    DevMem &operator=(DevMem &&o) { std::swap(ctx, o.ctx); std::swap(p, o.p); return *this; }
 };
 struct TombHandle {
     ii2_tomb *h = nullptr;
@@ -850,10 +852,9 @@ class InvertedIndex {
         return out;
     }
     // The reference reads each selected shard from its smallest prefix on (the merged terms of all its segments), keeps the
-    // terms that start with a prefix, stops at the first term past the greatest prefix (its first len(greatest) bytes compare
-    // greater), then sorts and compacts the collected lists.  Here no list leaves the device: in every segment the lists of
-    // a prefix are one run of consecutive terms, [lower_bound(prefix), end of the prefix's run) cut at the end of the greatest
-    // prefix's run, and ONE ii2_query_batch call - an OR query per prefix - unions the runs of every segment of every shard.
+    // terms that start with a prefix, stops at the first term past the greatest prefix, then sorts and compacts the collected
+    // lists.  Here no list leaves the device: in every segment the lists of a prefix are one run of consecutive terms
+    // (prefix_runs), and ONE ii2_query_batch call - an OR query per prefix - unions the runs of every segment of every shard.
     std::map<Term, std::vector<uint32_t>> PrefixSearch(std::vector<Term> prefixes) const {   // inverted_index.go:192-295
         std::sort(prefixes.begin(), prefixes.end(), term_less);
         prefixes.erase(std::unique(prefixes.begin(), prefixes.end()), prefixes.end());
@@ -863,43 +864,19 @@ class InvertedIndex {
         };
         std::map<Term, Ranges> found;
         std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the unions are done
-        for (auto &s : shard_list()) {
-            Term mn, mx;
-            if (!s.second->MinMax(&mn, &mx)) continue;
-            std::vector<Term> mine;
-            for (auto &p : prefixes) {
-                size_t l = std::min(p.size(), mn.size());
-                if (p.compare(0, l, mn, 0, l) < 0) continue;
-                l = std::min(p.size(), mx.size());
-                if (p.compare(0, l, mx, 0, l) > 0) continue;
-                mine.push_back(p);
-            }
-            if (mine.empty()) continue;
-            for (auto &sg : s.second->snapshot()) {
-                const std::vector<Term> &T = sg->terms;
-                const size_t stop = prefix_end(T, mine.back());
-                bool used = false;
-                for (auto &p : mine) {
-                    const size_t j0 = std::lower_bound(T.begin(), T.end(), p, term_less) - T.begin();
-                    const size_t j1 = std::min(prefix_end(T, p), stop);
-                    if (j0 >= j1) continue;
-                    Ranges &r = found[p];
-                    r.segs.push_back(sg->seg->h);
-                    r.first.push_back(j0);
-                    r.end.push_back(j1);
-                    used = true;
-                }
-                if (used) held.push_back(sg);
-            }
-        }
+        prefix_runs(prefixes, [&](const Term &p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+            Ranges &r = found[p];
+            r.segs.push_back(sg->seg->h);
+            r.first.push_back(j0);
+            r.end.push_back(j1);
+            held.push_back(sg);
+        });
         std::map<Term, std::vector<uint32_t>> out;
-        if (found.empty()) return out;
-        // ONE ii2_query_batch call, one wait and one download for all the prefixes (an OR query each).  The output's size: the C
-        // ABI gives no per-list counts, so a prefix is bounded by the postings of the segments its runs lie in; past FIRST_CAP
-        // ids the first call tries FIRST_CAP, and results that do not fit are written by a second call with the size the first
-        // one reported (II2_ECAPACITY writes nothing and fills the offsets).  Prefixes whose bounds add up to the call's limit
-        // of 2^32 ids go in several calls; one that reaches it alone goes through ii2_union_ranges.
-        constexpr uint64_t FIRST_CAP = 1u << 22, CALL_IDS = 0xFFFFFFFFull;
+        // ONE ii2_query_batch call, one wait and one download for all the prefixes (an OR query each), through two_call.  The
+        // output's size: the C ABI gives no per-list counts, so a prefix is bounded by the postings of the segments its runs lie
+        // in.  Prefixes whose bounds add up to the call's limit of 2^32 ids go in several calls; one that reaches it alone goes
+        // through ii2_union_ranges.
+        constexpr uint64_t CALL_IDS = 0xFFFFFFFFull;
         auto it = found.begin();
         while (it != found.end()) {
             std::vector<const Term *> names;
@@ -924,122 +901,69 @@ class InvertedIndex {
                 end.insert(end.end(), r.end.begin(), r.end.end());
                 query_first.push_back(segs.size());
             }
-            DevMem d_out(ctx_);
             if (bound >= CALL_IDS) {                                          // (one prefix, alone in its call)
+                DevMem d_out(ctx_);
                 uint64_t n = 0;
                 ck(ctx_, ii2_dev_alloc(ctx_, (bound + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
                 ck(ctx_, ii2_union_ranges(ctx_, segs.size(), segs.data(), first.data(), end.data(), nullptr, (uint32_t *)d_out.p, bound + 1, &n),
                    "prefix search");
-                std::vector<uint32_t> ids(n);
-                if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "prefix search");
-                out[*names[0]] = std::move(ids);
+                out[*names[0]] = download(d_out, n, "prefix search");
                 continue;
             }
             std::vector<uint64_t> off(names.size() + 1, 0);
-            uint64_t cap = std::min(bound, FIRST_CAP);
-            for (int attempt = 0;; attempt++) {
-                ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "prefix search");
-                const int rc = ii2_query_batch(ctx_, names.size(), op.data(), query_first.data(), segs.data(), first.data(), end.data(), nullptr,
-                                               (uint32_t *)d_out.p, cap + 1, off.data());
-                if (rc != II2_ECAPACITY || attempt) {
-                    ck(ctx_, rc, "prefix search");
-                    break;
-                }
-                ck(ctx_, ii2_dev_free(ctx_, d_out.p), "prefix search");
-                d_out.p = nullptr;
-                cap = off.back();
-            }
-            std::vector<uint32_t> all(off.back());                            // :288-292 sort + compact, on the GPU
-            if (!all.empty()) ck(ctx_, ii2_copy_d2h(ctx_, all.data(), d_out.p, all.size() * sizeof(uint32_t)), "prefix search");
+            const Output o = two_call(bound, 1, "prefix search", [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+                const int rc = ii2_query_batch(ctx_, names.size(), op.data(), query_first.data(), segs.data(), first.data(), end.data(), nullptr, d_ids,
+                                               cap, off.data());
+                *n = off.back();
+                return rc;
+            });
+            const std::vector<uint32_t> all = download(o.mem, o.n, "prefix search");      // :288-292 sort + compact, on the GPU
             for (size_t q = 0; q < names.size(); q++) out[*names[q]] = std::vector<uint32_t>(all.begin() + off[q], all.begin() + off[q + 1]);
         }
         return out;
     }
     // additive: ids present under every term.  A term's postings are spread over the segments of its shard (every Put writes
-    // one): one group per term, one one-list range per segment that holds it, and ONE ii2_intersect_ranges call - no list is
-    // merged, downloaded or uploaded again.  Like Read, no tombstone filter.
+    // one): one group per term, one one-list range per segment that holds it (Plan::add), and ONE ii2_intersect_ranges call - no
+    // list is merged, downloaded or uploaded again.  The output's size: the smallest term's bound.  Like Read, no tombstone filter.
     std::vector<uint32_t> Intersect(const std::vector<Term> &terms) const {
-        if (terms.empty()) return {};
-        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
-        std::vector<uint64_t> group_first{0};
-        std::vector<const ii2_seg *> segs;
-        std::vector<uint64_t> first, end;
-        // The output's size: the C ABI gives no per-list counts, so each term is bounded by its segments - a list of a segment
-        // holds at most its postings minus one per other list (every list a shard's segment holds is non-empty: a Put writes one
-        // posting per term, a merge drops empty terms), exact for Put segments, loose for merged ones.  The smallest term's bound
-        // is enough, but it may be a whole merged segment: past FIRST_CAP ids the first call tries FIRST_CAP, and a result that
-        // does not fit is written by a second call with the size the first one reported (II2_ECAPACITY writes nothing).
-        constexpr uint64_t FIRST_CAP = 1u << 22;
-        uint64_t bound = ~0ull;
-        for (auto &t : terms) {
-            uint64_t post = 0;
-            if (Shard *sh = find_shard(shard_key(t))) {
-                for (auto &sg : sh->snapshot()) {
-                    const std::vector<Term> &T = sg->terms;
-                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
-                    if (j == T.size() || T[j] != t) continue;
-                    ii2_seg_info info;
-                    ii2_seg_get_info(sg->seg->h, &info);
-                    held.push_back(sg);
-                    segs.push_back(sg->seg->h);
-                    first.push_back(j);
-                    end.push_back(j + 1);
-                    post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
-                }
-            }
-            if (segs.size() == group_first.back()) return {};    // a term in no segment: nothing is under every term
-            group_first.push_back(segs.size());
-            bound = std::min(bound, post);
-        }
-        uint64_t cap = std::min(bound, FIRST_CAP), n = 0;
-        DevMem d_out(ctx_);
-        for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect");
-            const int rc = ii2_intersect_ranges(ctx_, terms.size(), group_first.data(), segs.data(), first.data(), end.data(), nullptr,
-                                                (uint32_t *)d_out.p, cap + 1, &n);
-            if (rc != II2_ECAPACITY || attempt) {
-                ck(ctx_, rc, "intersect");
-                break;
-            }
-            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect");
-            d_out.p = nullptr;
-            cap = n;
-        }
-        std::vector<uint32_t> ids(n);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect");
-        return ids;
+        Resolver where(*this);
+        Plan plan;
+        const uint64_t bound = smallest(plan.add(where, terms, {}, Absent::EmptyQuery));
+        if (!bound) return {};                               // no term, or a term in no segment: nothing is under every term
+        const Output o = two_call(bound, 1, "intersect", [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+            return ii2_intersect_ranges(ctx_, plan.n_groups(), plan.group_first.data(), plan.segs.data(), plan.first.data(), plan.end.data(), nullptr,
+                                        d_ids, cap, n);
+        });
+        return download(o.mem, o.n, "intersect");
     }
     // additive: ids present under every term of `terms` and under none of `except` ("error AND db NOT healthcheck").  One group
     // per term as Intersect builds them, the excluded terms' groups flagged, and ONE ii2_andnot_ranges call: no second query, no
     // second download, no set difference on the host.  An excluded term found in no segment is dropped; a required one gives the
-    // empty result.  Like Intersect and Read, no tombstone filter.
+    // empty result.  The output's size: the smallest REQUIRED term's bound (an exclusion only removes ids).  Like Intersect and
+    // Read, no tombstone filter.
     std::vector<uint32_t> IntersectExcept(const std::vector<Term> &terms, const std::vector<Term> &except) const {
-        Filter f;
-        if (!filter_build(terms, except, f)) return {};
-        DevMem d_out(ctx_);
-        const uint64_t n = filter_run(f, d_out, "intersect except");
-        std::vector<uint32_t> ids(n);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect except");
-        return ids;
+        Resolver where(*this);
+        Plan plan;
+        const uint64_t bound = smallest(plan.add(where, terms, except, Absent::EmptyQuery));
+        if (!bound) return {};
+        const Output o = filter_run(plan, bound, "intersect except");
+        return download(o.mem, o.n, "intersect except");
     }
     // additive: ids present under AT LEAST min_match of `terms` and under none of `except` (minimum-should-match, "any two of
     // these tags").  One group per term as IntersectExcept builds them - but a required term found in no segment is an empty group,
     // not an empty result - and ONE ii2_atleast_ranges call and one download.  Like Intersect and Read, no tombstone filter.
     std::vector<uint32_t> IntersectAtLeast(const std::vector<Term> &terms, uint32_t min_match, const std::vector<Term> &except) const {
         if (!min_match) throw std::runtime_error("intersect at least: min_match is 0");
-        Filter f;
-        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
-        filter_build(terms, except, f, &posts);
+        Resolver where(*this);
+        Plan plan;
+        std::vector<uint64_t> posts = plan.add(where, terms, except, Absent::EmptyGroup);
         if (posts.size() < min_match) return {};
         // the output's size: a result id lies in at least one of any n' - min_match + 1 terms, so those with the smallest bounds
         std::sort(posts.begin(), posts.end());
-        f.bound = 0;
-        for (size_t k = 0; k + min_match <= posts.size(); k++) f.bound += posts[k];
-        DevMem d_out(ctx_);
-        const uint64_t n = filter_run(f, d_out, "intersect at least", min_match);
-        std::vector<uint32_t> ids(n);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, ids.data(), d_out.p, n * sizeof(uint32_t)), "intersect at least");
-        return ids;
+        uint64_t bound = 0;
+        for (size_t k = 0; k + min_match <= posts.size(); k++) bound += posts[k];
+        const Output o = filter_run(plan, bound, "intersect at least", min_match);
+        return download(o.mem, o.n, "intersect at least");
     }
     // additive: the k ids under the MOST of `terms` - at least min_match of them, under none of `except` - with the number of terms each
     // lies under, ordered by that score descending, then id ascending (a ranked page of a search).  One group per term as
@@ -1048,20 +972,13 @@ class InvertedIndex {
     std::vector<std::pair<uint32_t, uint32_t>> IntersectTop(const std::vector<Term> &terms, uint64_t k, uint32_t min_match, const std::vector<Term> &except) const {
         if (!min_match) throw std::runtime_error("intersect top: min_match is 0");
         if (k > II2_TOPK_MAX) throw std::runtime_error("intersect top: k above II2_TOPK_MAX");
-        Filter f;
-        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
-        filter_build(terms, except, f, &posts);
-        if (posts.size() < min_match || !k) return {};
-        DevMem d_out(ctx_);                                      // ids [0, k), then scores [k, 2k)
-        ck(ctx_, ii2_dev_alloc(ctx_, 2 * k * sizeof(uint32_t), &d_out.p), "intersect top");
-        uint64_t n = 0;
-        ck(ctx_, ii2_topk_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), min_match, k, f.segs.data(), f.first.data(),
-                                 f.end.data(), nullptr, (uint32_t *)d_out.p, (uint32_t *)d_out.p + k, &n, nullptr, nullptr), "intersect top");
-        std::vector<uint32_t> raw(n ? k + n : 0);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top");
-        std::vector<std::pair<uint32_t, uint32_t>> out(n);
-        for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
-        return out;
+        Resolver where(*this);
+        Plan plan;
+        if (plan.add(where, terms, except, Absent::EmptyGroup).size() < min_match || !k) return {};
+        return ranked(k, "intersect top", [&](uint32_t *d_ids, uint32_t *d_scores, uint64_t *n) {
+            return ii2_topk_ranges(ctx_, plan.n_groups(), plan.group_first.data(), plan.group_not.data(), min_match, k, plan.segs.data(),
+                                   plan.first.data(), plan.end.data(), nullptr, d_ids, d_scores, n, nullptr, nullptr);
+        });
     }
     // additive: IntersectTop with a weight per term (an idf tier, a field boost): a doc's score is the sum of the weights of the terms it
     // lies under, 1 .. 255 each and at most 255 together; at least min_score.  The groups are IntersectTop's - a term found in no
@@ -1071,28 +988,19 @@ class InvertedIndex {
         if (!min_score) throw std::runtime_error("intersect top weighted: min_score is 0");
         if (weights.size() != terms.size()) throw std::runtime_error("intersect top weighted: one weight per term");
         if (k > II2_TOPK_MAX) throw std::runtime_error("intersect top weighted: k above II2_TOPK_MAX");
-        Filter f;
-        std::vector<uint64_t> posts;                             // the postings bounds of the terms that some segment holds
-        filter_build(terms, except, f, &posts);
-        if (posts.empty() || !k) return {};
-        std::vector<uint32_t> group_weight(weights);
-        group_weight.resize(f.group_not.size(), 0u);             // (the excluded groups follow the terms: their weights are ignored)
-        DevMem d_out(ctx_);                                      // ids [0, k), then scores [k, 2k)
-        ck(ctx_, ii2_dev_alloc(ctx_, 2 * k * sizeof(uint32_t), &d_out.p), "intersect top weighted");
-        uint64_t n = 0;
-        ck(ctx_, ii2_topk_weighted_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), group_weight.data(), min_score, k,
-                                          f.segs.data(), f.first.data(), f.end.data(), nullptr, (uint32_t *)d_out.p, (uint32_t *)d_out.p + k, &n, nullptr,
-                                          nullptr), "intersect top weighted");
-        std::vector<uint32_t> raw(n ? k + n : 0);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top weighted");
-        std::vector<std::pair<uint32_t, uint32_t>> out(n);
-        for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
-        return out;
+        Resolver where(*this);
+        Plan plan;
+        if (plan.add(where, terms, except, Absent::EmptyGroup, &weights).empty() || !k) return {};
+        return ranked(k, "intersect top weighted", [&](uint32_t *d_ids, uint32_t *d_scores, uint64_t *n) {
+            return ii2_topk_weighted_ranges(ctx_, plan.n_groups(), plan.group_first.data(), plan.group_not.data(), plan.group_weight.data(), min_score,
+                                            k, plan.segs.data(), plan.first.data(), plan.end.data(), nullptr, d_ids, d_scores, n, nullptr, nullptr);
+        });
     }
-    // additive: MANY IntersectTopWeighted queries in one ii2_topk_batch call - a second one when the results exceed FIRST_CAP
-    // entries - and one download; result q is that of IntersectTopWeighted(queries[q]...).  Per query the groups are built exactly
-    // as IntersectTopWeighted builds them; a query none of whose terms is in a segment keeps its place without a group - its
-    // result is empty, the call goes on.  The library takes result bounds below 2^32 ids per call (II2_ERANGE beyond).
+    // additive: MANY IntersectTopWeighted queries in one ii2_topk_batch call (through two_call) and one download; result q is that
+    // of IntersectTopWeighted(queries[q]...).  Per query the groups are built exactly as IntersectTopWeighted builds them; a query
+    // none of whose terms is in a segment keeps its place without a group - its result is empty, the call goes on.  The output's
+    // size: per query min(k, the postings bounds of its terms).  The library takes result bounds below 2^32 ids per call
+    // (II2_ERANGE beyond).
     struct TopQuery {
         std::vector<Term> terms;
         std::vector<uint32_t> weights;
@@ -1103,64 +1011,35 @@ class InvertedIndex {
     std::vector<std::vector<std::pair<uint32_t, uint32_t>>> IntersectTopBatch(const std::vector<TopQuery> &queries) const {
         std::vector<std::vector<std::pair<uint32_t, uint32_t>>> out(queries.size());
         if (queries.empty()) return out;
-        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
-        std::vector<uint64_t> query_first{0}, group_first{0}, first, end;
-        std::vector<uint8_t> group_not;
-        std::vector<uint32_t> group_weight, min_score, ks;
-        std::vector<const ii2_seg *> segs;
-        constexpr uint64_t FIRST_CAP = 1u << 22;
-        uint64_t total = 0;
         Resolver where(*this);
         where.prepare(queries.size(), [&](size_t q, bool ex) -> const std::vector<Term> & { return ex ? queries[q].except : queries[q].terms; });
+        Plan plan;
+        std::vector<uint32_t> min_score, ks;
+        uint64_t total = 0;
+        const std::vector<Term> none;
         for (size_t q = 0; q < queries.size(); q++) {
             const TopQuery &Q = queries[q];
             const std::string who = "intersect top batch: query " + std::to_string(q);
             if (!Q.min_score) throw std::runtime_error(who + ": min_score is 0");
             if (Q.weights.size() != Q.terms.size()) throw std::runtime_error(who + ": one weight per term");
             if (Q.k > II2_TOPK_MAX) throw std::runtime_error(who + ": k above II2_TOPK_MAX");
-            Filter f;
-            std::vector<uint64_t> posts;                         // the postings bounds of the terms that some segment holds
-            filter_build(Q.terms, Q.except, f, &posts, &where);
             min_score.push_back(Q.min_score);
             ks.push_back((uint32_t)Q.k);
-            if (!posts.empty() && Q.k) {
-                const uint64_t r0 = segs.size();
-                held.insert(held.end(), f.held.begin(), f.held.end());
-                segs.insert(segs.end(), f.segs.begin(), f.segs.end());
-                first.insert(first.end(), f.first.begin(), f.first.end());
-                end.insert(end.end(), f.end.begin(), f.end.end());
-                for (size_t g = 0; g < f.group_not.size(); g++) {
-                    group_first.push_back(r0 + f.group_first[g + 1]);
-                    group_not.push_back(f.group_not[g]);
-                    group_weight.push_back(g < Q.weights.size() ? Q.weights[g] : 0u);    // (the excluded groups follow the terms)
-                }
-                uint64_t post = 0;
-                for (uint64_t p : posts) post += p;
-                total += std::min(Q.k, post);
-            }
-            query_first.push_back(group_not.size());
+            uint64_t post = 0;                                   // (k = 0 asks for nothing: a query without terms)
+            for (uint64_t p : plan.add(where, Q.k ? Q.terms : none, Q.except, Absent::EmptyGroup, &Q.weights)) post += p;
+            total += std::min(Q.k, post);
         }
         std::vector<uint64_t> off(queries.size() + 1, 0);
-        uint64_t cap = std::max<uint64_t>(std::min(total, FIRST_CAP), 1);
-        DevMem d_out(ctx_);                                      // ids [0, cap), then scores [cap, 2 cap)
-        for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, 2 * cap * sizeof(uint32_t), &d_out.p), "intersect top batch");
-            const int rc = ii2_topk_batch(ctx_, queries.size(), query_first.data(), group_first.data(), group_not.data(), group_weight.data(),
-                                          min_score.data(), ks.data(), segs.data(), first.data(), end.data(), nullptr, (uint32_t *)d_out.p,
-                                          (uint32_t *)d_out.p + cap, cap, off.data(), nullptr, nullptr);
-            if (rc != II2_ECAPACITY || attempt) {
-                ck(ctx_, rc, "intersect top batch");
-                break;
-            }
-            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect top batch");
-            d_out.p = nullptr;
-            cap = off.back();
-        }
-        const uint64_t n = off.back();
-        std::vector<uint32_t> raw(n ? cap + n : 0);
-        if (n) ck(ctx_, ii2_copy_d2h(ctx_, raw.data(), d_out.p, raw.size() * sizeof(uint32_t)), "intersect top batch");
+        const Output o = two_call(total, 2, "intersect top batch", [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {      // ids [0, cap), then scores [cap, 2 cap)
+            const int rc = ii2_topk_batch(ctx_, queries.size(), plan.query_first.data(), plan.group_first.data(), plan.group_not.data(),
+                                          plan.group_weight.data(), min_score.data(), ks.data(), plan.segs.data(), plan.first.data(), plan.end.data(),
+                                          nullptr, d_ids, d_ids + cap, cap, off.data(), nullptr, nullptr);
+            *n = off.back();
+            return rc;
+        });
+        const std::vector<uint32_t> raw = download(o.mem, o.n ? o.cap + o.n : 0, "intersect top batch");
         for (size_t q = 0; q < queries.size(); q++)
-            for (uint64_t i = off[q]; i < off[q + 1]; i++) out[q].push_back({raw[i], raw[cap + i]});
+            for (uint64_t i = off[q]; i < off[q + 1]; i++) out[q].push_back({raw[i], raw[o.cap + i]});
         return out;
     }
    private:
@@ -1175,9 +1054,11 @@ class InvertedIndex {
     // prepare() - the bulk calls - may move the whole call's lookups to the device instead (ii2h_set_resolve): per shard the
     // call's distinct terms that hash to it are probed against all segments of ONE snapshot by ii2_dict_find, at most
     // II2_MAX_LISTS dictionaries per call, and append() then only reads the answers.  The ranges are the same either way.
+    // `remember`: the host bisection keeps its answers too, so a term asked for again gets the same lists without a second
+    // lookup (TermCounts lays its filter out once more per re-counted term).
     class Resolver {
        public:
-        explicit Resolver(const InvertedIndex &ix) : ix_(ix) {}
+        explicit Resolver(const InvertedIndex &ix, bool remember = false) : ix_(ix), remember_(remember) {}
         // terms_of(q, false / true): the required / excluded terms of query q
         template <class TermsOf> void prepare(size_t n_queries, TermsOf terms_of) {
             const int mode = ix_.resolve_mode_.load();
@@ -1224,9 +1105,12 @@ class InvertedIndex {
                 }
             }
         }
-        // one one-list range per segment that holds the term; returns the term's postings bound (see Intersect), 0: in no segment
+        // One one-list range per segment that holds the term; returns the term's postings bound, 0: in no segment.  The bound:
+        // the C ABI gives no per-list counts, so a term is bounded by its segments - a list of a segment holds at most its
+        // postings minus one per other list (every list a shard's segment holds is non-empty: a Put writes one posting per term,
+        // a merge drops empty terms), exact for Put segments, loose for merged ones.
         uint64_t append(const Term &t, std::vector<std::shared_ptr<Segment>> &held, std::vector<const ii2_seg *> &segs, std::vector<uint64_t> &first,
-                        std::vector<uint64_t> &end) const {
+                        std::vector<uint64_t> &end) {
             uint64_t post = 0;
             auto take = [&](const std::shared_ptr<Segment> &sg, uint64_t j) {
                 ii2_seg_info info;
@@ -1237,78 +1121,180 @@ class InvertedIndex {
                 end.push_back(j + 1);
                 post += info.n_postings > info.n_lists ? info.n_postings - (info.n_lists - 1) : 1;
             };
-            if (device_) {
+            if (remember_ && !found_.count(t)) bisect(t, [&, &hits = found_[t]](const std::shared_ptr<Segment> &sg, uint64_t j) { hits.emplace_back(sg, j); });
+            if (device_ || remember_) {
                 for (auto &hit : found_.at(t)) take(hit.first, hit.second);
-            } else if (Shard *sh = ix_.find_shard(shard_key(t))) {
-                for (auto &sg : sh->snapshot()) {
-                    const std::vector<Term> &T = sg->terms;
-                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
-                    if (j != T.size() && T[j] == t) take(sg, j);
-                }
+            } else {
+                bisect(t, take);
             }
             return post;
         }
 
        private:
+        // the host lookup: fn(segment, list) for every segment of the term's shard that holds it, in the order of the shard's snapshot
+        template <class Fn> void bisect(const Term &t, Fn fn) const {
+            if (Shard *sh = ix_.find_shard(shard_key(t))) {
+                for (auto &sg : sh->snapshot()) {
+                    const std::vector<Term> &T = sg->terms;
+                    const size_t j = std::lower_bound(T.begin(), T.end(), t, term_less) - T.begin();
+                    if (j != T.size() && T[j] == t) fn(sg, j);
+                }
+            }
+        }
         const InvertedIndex &ix_;
+        const bool remember_;
         bool device_ = false;
         std::unordered_map<Term, TermHits> found_;
     };
-    // an IntersectExcept query as the range entry points take it: one group per term - one one-list range per segment of the term's
-    // shard that holds it - the excluded terms' groups flagged, and the bound of the result's size
-    struct Filter {
+    // ---- the query plan: what the range and batch entry points take ----
+    // What a required term found in no segment does to its query: the AND forms have nothing under every term, the at-least and
+    // ranked forms keep the term as a group without ranges (it matches no doc and keeps its slot and weight).
+    enum class Absent { EmptyQuery, EmptyGroup };
+    using Lists = std::vector<std::pair<const ii2_seg *, uint64_t>>;      // (segment, list)
+    // Queries as flat arrays: query q owns the groups query_first[q] .. query_first[q + 1] - 1, group g the ranges group_first[g] ..
+    // group_first[g + 1] - 1 - one one-list range per segment of the term's shard that holds the term.  A single query is a plan of
+    // one query (the range entry points take group_first on and ignore query_first).
+    struct Plan {
         std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
-        std::vector<uint64_t> group_first{0};
+        std::vector<uint64_t> query_first{0}, group_first{0}, first, end;
         std::vector<uint8_t> group_not;
+        std::vector<uint32_t> group_weight;                  // filled for the queries added with weights
         std::vector<const ii2_seg *> segs;
-        std::vector<uint64_t> first, end;
-        uint64_t bound = ~0ull;
+        size_t n_groups() const { return group_not.size(); }
+        // Appends one query: a group per required term, then `extra` - lists given directly - as one more required group, then a
+        // flagged group per excluded term (the packers lay a query out that way: the required groups first, the excluded ones
+        // last; an excluded group's weight is 0 and ignored).  An excluded term found in no segment removes nothing and is dropped.
+        // A query that turns out empty - `rule` says what an absent required term means; no required term and no `extra`, or under
+        // EmptyGroup no required term found - is undone: it keeps its place, without a group.  Returns the postings bounds of the
+        // required terms found, in their order (none for an empty query), valid until the next add: each caller derives its
+        // output bound from them.
+        const std::vector<uint64_t> &add(Resolver &where, const std::vector<Term> &terms, const std::vector<Term> &except, Absent rule,
+                                         const std::vector<uint32_t> *weights = nullptr, const Lists *extra = nullptr) {
+            const size_t g_mark = group_not.size(), r_mark = segs.size();
+            auto close_group = [&](uint8_t flag, uint32_t weight) {
+                group_first.push_back(segs.size());
+                group_not.push_back(flag);
+                if (weights) group_weight.push_back(weight);
+            };
+            posts_.clear();
+            bool nothing = false;                                // under EmptyQuery: a required term in no segment, the others are not looked up
+            for (size_t i = 0; i < terms.size() && !nothing; i++) {
+                const uint64_t post = where.append(terms[i], held, segs, first, end);
+                if (post) posts_.push_back(post);
+                nothing = !post && rule == Absent::EmptyQuery;
+                close_group(0, weights ? (*weights)[i] : 0u);
+            }
+            if (extra) {
+                for (auto &sl : *extra) {
+                    segs.push_back(sl.first);
+                    first.push_back(sl.second);
+                    end.push_back(sl.second + 1);
+                }
+                close_group(0, 0u);
+            }
+            if (nothing || (posts_.empty() && !extra)) {
+                posts_.clear();
+                group_first.resize(g_mark + 1);
+                group_not.resize(g_mark);
+                if (weights) group_weight.resize(g_mark);
+                segs.resize(r_mark);
+                first.resize(r_mark);
+                end.resize(r_mark);
+            } else {
+                for (auto &t : except)
+                    if (where.append(t, held, segs, first, end)) close_group(1, 0u);
+            }
+            query_first.push_back(group_not.size());
+            return posts_;
+        }
+
+       private:
+        std::vector<uint64_t> posts_;
     };
-    // false: a required term is in no segment (or there is none) - nothing is under every term.  posts != NULL (IntersectAtLeast):
-    // such a term is a group without ranges instead, and *posts receives the bounds of the others
-    bool filter_build(const std::vector<Term> &terms, const std::vector<Term> &except, Filter &f, std::vector<uint64_t> *posts = nullptr,
-                      Resolver *batch = nullptr) const {
-        if (terms.empty()) return false;
-        Resolver own(*this);                                     // a single query bisects on the host
-        Resolver &where = batch ? *batch : own;
-        auto gather = [&](const Term &t) { return where.append(t, f.held, f.segs, f.first, f.end); };
-        // the output's size: the smallest REQUIRED term's bound, as in Intersect (an exclusion only removes ids)
-        for (auto &t : terms) {
-            const uint64_t post = gather(t);
-            if (!post && !posts) return false;                   // a required term in no segment: nothing is under every term
-            if (post && posts) posts->push_back(post);
-            f.group_first.push_back(f.segs.size());
-            f.group_not.push_back(0);
-            f.bound = std::min(f.bound, post);
-        }
-        for (auto &t : except) {
-            if (!gather(t)) continue;                            // an excluded term in no segment removes nothing
-            f.group_first.push_back(f.segs.size());
-            f.group_not.push_back(1);
-        }
-        return true;
-    }
-    // ONE ii2_andnot_ranges call - min_match > 0: ONE ii2_atleast_ranges call - into d_out, which stays on the device; returns the
-    // result's size.  Past FIRST_CAP ids the first call tries FIRST_CAP, and a result that does not fit is written by a second call
-    // with the size the first one reported
-    uint64_t filter_run(const Filter &f, DevMem &d_out, const char *what, uint32_t min_match = 0) const {
-        constexpr uint64_t FIRST_CAP = 1u << 22;
-        uint64_t cap = std::min(f.bound, FIRST_CAP), n = 0;
+    // the output bound of an AND query: its smallest term's (0: the query is empty)
+    static uint64_t smallest(const std::vector<uint64_t> &posts) { return posts.empty() ? 0 : *std::min_element(posts.begin(), posts.end()); }
+
+    // ---- the two-call output protocol ----
+    // The bounds above may be a whole merged segment, so no call allocates more than FIRST_CAP ids at first: a result that does not
+    // fit is written by a second call with the size the first one reported (II2_ECAPACITY writes nothing; the batch calls fill
+    // their offsets under it).  Either call passes one entry more than it needs.  `arrays`: the uint32 arrays of `cap` entries the output holds, back to back (1: ids, 2: ids then
+    // scores).  call(d_out, cap, &n) makes the library call and returns its rc, n = the size it reported.
+    static constexpr uint64_t FIRST_CAP = 1ull << 22;
+    struct Output {
+        DevMem mem;
+        uint64_t cap, n;           // entries per array, entries written
+    };
+    template <class Call> Output two_call(uint64_t bound, unsigned arrays, const char *what, Call call) const {
+        Output o{DevMem(ctx_), std::min(bound, first_cap_.load()) + 1, 0};
         for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), what);
-            const int rc = min_match ? ii2_atleast_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), min_match, f.segs.data(),
-                                                          f.first.data(), f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n, nullptr)
-                                     : ii2_andnot_ranges(ctx_, f.group_not.size(), f.group_first.data(), f.group_not.data(), f.segs.data(), f.first.data(),
-                                                         f.end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, &n);
+            ck(ctx_, ii2_dev_alloc(ctx_, arrays * o.cap * sizeof(uint32_t), &o.mem.p), what);
+            const int rc = call((uint32_t *)o.mem.p, o.cap, &o.n);
             if (rc != II2_ECAPACITY || attempt) {
                 ck(ctx_, rc, what);
-                break;
+                return o;
             }
-            ck(ctx_, ii2_dev_free(ctx_, d_out.p), what);
-            d_out.p = nullptr;
-            cap = n;
+            second_calls_++;
+            ck(ctx_, ii2_dev_free(ctx_, o.mem.p), what);
+            o.mem.p = nullptr;
+            o.cap = o.n + 1;
         }
-        return n;
+    }
+    std::vector<uint32_t> download(const DevMem &d, uint64_t n, const char *what) const {
+        std::vector<uint32_t> v(n);
+        if (n) ck(ctx_, ii2_copy_d2h(ctx_, v.data(), d.p, n * sizeof(uint32_t)), what);
+        return v;
+    }
+    // ONE ii2_andnot_ranges call - min_match > 0: ONE ii2_atleast_ranges call - over a plan of one query; the result stays on the device
+    Output filter_run(const Plan &f, uint64_t bound, const char *what, uint32_t min_match = 0) const {
+        return two_call(bound, 1, what, [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+            return min_match ? ii2_atleast_ranges(ctx_, f.n_groups(), f.group_first.data(), f.group_not.data(), min_match, f.segs.data(), f.first.data(),
+                                                  f.end.data(), nullptr, d_ids, cap, n, nullptr)
+                             : ii2_andnot_ranges(ctx_, f.n_groups(), f.group_first.data(), f.group_not.data(), f.segs.data(), f.first.data(),
+                                                 f.end.data(), nullptr, d_ids, cap, n);
+        });
+    }
+    // the tail of the two single ranked methods: exactly 2k entries - ids [0, k), then scores [k, 2k); a ranked result never
+    // exceeds k, so there is no second call - one call, one download, the (id, score) pairs
+    template <class Call> std::vector<std::pair<uint32_t, uint32_t>> ranked(uint64_t k, const char *what, Call call) const {
+        DevMem d_out(ctx_);
+        ck(ctx_, ii2_dev_alloc(ctx_, 2 * k * sizeof(uint32_t), &d_out.p), what);
+        uint64_t n = 0;
+        ck(ctx_, call((uint32_t *)d_out.p, (uint32_t *)d_out.p + k, &n), what);
+        const std::vector<uint32_t> raw = download(d_out, n ? k + n : 0, what);
+        std::vector<std::pair<uint32_t, uint32_t>> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = {raw[i], raw[k + i]};
+        return out;
+    }
+    // ---- a prefix's lists ----
+    // fn(prefix, segment, j0, j1) for every non-empty run of lists of every prefix (sorted, distinct) in every segment of every
+    // shard, shard by shard in key order.  A shard whose MinMax excludes a prefix is not read for it.  In a segment the terms that
+    // start with a prefix are one run, [lower_bound(prefix), the first term after it that does not start with it), and every run is
+    // cut at the end of the GREATEST prefix's run: the reference stops reading a shard at the first term past the greatest prefix
+    // (its first len(greatest) bytes compare greater; inverted_index.go:192-295), so with prefixes a and ab the run of a ends
+    // where the run of ab ends.
+    template <class Fn> void prefix_runs(const std::vector<Term> &prefixes, Fn fn) const {
+        for (auto &s : shard_list()) {
+            Term mn, mx;
+            if (!s.second->MinMax(&mn, &mx)) continue;
+            std::vector<const Term *> mine;
+            for (auto &p : prefixes) {
+                size_t l = std::min(p.size(), mn.size());
+                if (p.compare(0, l, mn, 0, l) < 0) continue;
+                l = std::min(p.size(), mx.size());
+                if (p.compare(0, l, mx, 0, l) > 0) continue;
+                mine.push_back(&p);
+            }
+            if (mine.empty()) continue;
+            for (auto &sg : s.second->snapshot()) {
+                const std::vector<Term> &T = sg->terms;
+                const size_t stop = prefix_end(T, *mine.back());
+                for (const Term *p : mine) {
+                    const size_t j0 = std::lower_bound(T.begin(), T.end(), *p, term_less) - T.begin();
+                    const size_t j1 = std::min(prefix_end(T, *p), stop);
+                    if (j0 < j1) fn(*p, sg, j0, j1);
+                }
+            }
+        }
     }
 
    public:
@@ -1324,47 +1310,36 @@ class InvertedIndex {
     std::map<Term, uint64_t> TermCounts(const Term &prefix, const std::vector<Term> &terms, const std::vector<Term> &except) const {
         std::map<Term, uint64_t> out;
         if (terms.empty() && !except.empty()) throw Error("term counts: an exclusion needs a required term");
-        Filter f;
-        DevMem d_set(ctx_);
-        uint64_t n_set = 0;
+        Resolver where(*this, true);                             // (the re-count lays the filter's terms out again: the same lists)
+        Output set{DevMem(ctx_), 0, 0};
         if (!terms.empty()) {
-            if (!filter_build(terms, except, f)) return out;
-            n_set = filter_run(f, d_set, "term counts");
-            if (!n_set) return out;
+            Plan filter;
+            const uint64_t bound = smallest(filter.add(where, terms, except, Absent::EmptyQuery));
+            if (!bound) return out;
+            set = filter_run(filter, bound, "term counts");
+            if (!set.n) return out;
         }
         // the prefix's run in every segment of every shard
         std::vector<std::shared_ptr<Segment>> held;
         std::vector<const ii2_seg *> segs;
         std::vector<uint64_t> first, end;
         uint64_t n_named = 0;
-        for (auto &s : shard_list()) {
-            Term mn, mx;
-            if (!s.second->MinMax(&mn, &mx)) continue;
-            size_t l = std::min(prefix.size(), mn.size());
-            if (prefix.compare(0, l, mn, 0, l) < 0) continue;
-            l = std::min(prefix.size(), mx.size());
-            if (prefix.compare(0, l, mx, 0, l) > 0) continue;
-            for (auto &sg : s.second->snapshot()) {
-                const std::vector<Term> &T = sg->terms;
-                const size_t j0 = std::lower_bound(T.begin(), T.end(), prefix, term_less) - T.begin();
-                const size_t j1 = prefix_end(T, prefix);
-                if (j0 >= j1) continue;
-                held.push_back(sg);
-                segs.push_back(sg->seg->h);
-                first.push_back(j0);
-                end.push_back(j1);
-                n_named += j1 - j0;
-            }
-        }
+        prefix_runs({prefix}, [&](const Term &, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+            held.push_back(sg);
+            segs.push_back(sg->seg->h);
+            first.push_back(j0);
+            end.push_back(j1);
+            n_named += j1 - j0;
+        });
         if (segs.empty()) return out;
         std::vector<uint64_t> counts(n_named);
-        ck(ctx_, ii2_count_ranges(ctx_, segs.size(), segs.data(), first.data(), end.data(), terms.empty() ? nullptr : (const uint32_t *)d_set.p, n_set,
+        ck(ctx_, ii2_count_ranges(ctx_, segs.size(), segs.data(), first.data(), end.data(), terms.empty() ? nullptr : (const uint32_t *)set.mem.p, set.n,
                                   nullptr, counts.data(), counts.size(), nullptr),
            "term counts");
         // per term: the sum over its segments, and the lists that hit
         struct Hit {
             uint64_t sum = 0;
-            std::vector<std::pair<const ii2_seg *, uint64_t>> lists;      // (segment, list) of every segment with a hit
+            Lists lists;                                         // (segment, list) of every segment with a hit
         };
         std::map<Term, Hit> hits;
         size_t k = 0;
@@ -1386,43 +1361,19 @@ class InvertedIndex {
         constexpr uint64_t CALL_IDS = 0xFFFFFFFFull;
         size_t at = 0;
         while (at < again.size()) {
-            std::vector<uint64_t> query_first{0}, group_first{0}, qfirst, qend;
-            std::vector<uint8_t> group_not;
-            std::vector<const ii2_seg *> qsegs;
+            Plan plan;
             uint64_t bound = 0;
             const size_t q0 = at;
             for (; at < again.size() && at - q0 < CALL_QUERIES; at++) {
                 const Hit &h = hits[*again[at]];
                 if (at > q0 && bound + h.sum >= CALL_IDS) break;
                 bound += h.sum;                                  // (the term's group holds at least its hits; the result is no longer)
-                // the required groups first - the filter's, then the term's own - and the excluded ones last, as the packers lay a query out
-                auto filter_groups = [&](uint8_t flag) {
-                    for (size_t g = 0; g < f.group_not.size(); g++) {
-                        if (f.group_not[g] != flag) continue;
-                        for (uint64_t i = f.group_first[g]; i < f.group_first[g + 1]; i++) {
-                            qsegs.push_back(f.segs[i]);
-                            qfirst.push_back(f.first[i]);
-                            qend.push_back(f.end[i]);
-                        }
-                        group_first.push_back(qsegs.size());
-                        group_not.push_back(flag);
-                    }
-                };
-                filter_groups(0);
-                for (auto &sl : h.lists) {
-                    qsegs.push_back(sl.first);
-                    qfirst.push_back(sl.second);
-                    qend.push_back(sl.second + 1);
-                }
-                group_first.push_back(qsegs.size());
-                group_not.push_back(0);
-                filter_groups(1);
-                query_first.push_back(group_not.size());
+                plan.add(where, terms, except, Absent::EmptyQuery, nullptr, &h.lists);
             }
             const size_t nq = at - q0;
             std::vector<uint64_t> off(nq + 1, 0);
-            const int rc = ii2_query_batch_groups(ctx_, nq, query_first.data(), group_first.data(), group_not.data(), qsegs.data(), qfirst.data(),
-                                                  qend.data(), nullptr, nullptr, 0, off.data());
+            const int rc = ii2_query_batch_groups(ctx_, nq, plan.query_first.data(), plan.group_first.data(), plan.group_not.data(), plan.segs.data(),
+                                                  plan.first.data(), plan.end.data(), nullptr, nullptr, 0, off.data());
             if (rc != II2_ECAPACITY) ck(ctx_, rc, "term counts");
             for (size_t q = 0; q < nq; q++) {
                 const uint64_t c = off[q + 1] - off[q];
@@ -1432,74 +1383,38 @@ class InvertedIndex {
         }
         return out;
     }
-    // additive: MANY IntersectExcept queries, queries[q] = (terms, except), in one ii2_query_batch_groups call - with a second one
-    // when the results exceed FIRST_CAP ids, see below - one wait and one download.  Per term the groups are built exactly as IntersectExcept builds them - one one-list range per segment of the
-    // term's shard that holds it, the excluded terms' groups flagged, an excluded term found in no segment dropped.  A required
-    // term found in no segment (or no term at all) makes that query one without groups - its result is empty, the call goes
-    // on.  The library takes result bounds below 2^32 ids per call (II2_ERANGE beyond: send such a bulk in parts).  Like
-    // Intersect and Read, no tombstone filter.
+    // additive: MANY IntersectExcept queries, queries[q] = (terms, except), in one ii2_query_batch_groups call (through two_call),
+    // one wait and one download.  Per term the groups are built exactly as IntersectExcept builds them.  A required term found in
+    // no segment (or no term at all) makes that query one without groups - its result is empty, the call goes on.  The output's
+    // size: per query the smallest REQUIRED term's bound.  The library takes result bounds below 2^32 ids per call (II2_ERANGE
+    // beyond: send such a bulk in parts).  Like Intersect and Read, no tombstone filter.
     std::vector<std::vector<uint32_t>> IntersectMany(const std::vector<std::pair<std::vector<Term>, std::vector<Term>>> &queries) const {
         std::vector<std::vector<uint32_t>> out(queries.size());
         if (queries.empty()) return out;
-        std::vector<std::shared_ptr<Segment>> held;          // the segments read, alive until the call is done
-        std::vector<uint64_t> query_first{0}, group_first{0};
-        std::vector<uint8_t> group_not;
-        std::vector<const ii2_seg *> segs;
-        std::vector<uint64_t> first, end;
         Resolver where(*this);
         where.prepare(queries.size(), [&](size_t q, bool ex) -> const std::vector<Term> & { return ex ? queries[q].second : queries[q].first; });
-        auto gather = [&](const Term &t) { return where.append(t, held, segs, first, end); };
-        // the output's size: per query the smallest REQUIRED term's bound, as in Intersect; past FIRST_CAP ids in all the first
-        // call tries FIRST_CAP, and results that do not fit are written by a second call with the size the first one reported
-        // (II2_ECAPACITY writes nothing and fills the offsets)
-        constexpr uint64_t FIRST_CAP = 1u << 22;
+        Plan plan;
         uint64_t total = 0;
-        for (auto &qe : queries) {
-            const size_t g_mark = group_first.size(), n_mark = group_not.size(), r_mark = segs.size();
-            uint64_t bound = qe.first.empty() ? 0 : ~0ull;
-            for (auto &t : qe.first) {
-                const uint64_t post = gather(t);
-                bound = std::min(bound, post);
-                if (!post) break;                                // a required term in no segment: nothing is under every term
-                group_first.push_back(segs.size());
-                group_not.push_back(0);
-            }
-            if (bound) {
-                for (auto &t : qe.second) {
-                    if (!gather(t)) continue;                    // an excluded term in no segment removes nothing
-                    group_first.push_back(segs.size());
-                    group_not.push_back(1);
-                }
-            } else {                                             // the query keeps its place, without a group
-                group_first.resize(g_mark);
-                group_not.resize(n_mark);
-                segs.resize(r_mark);
-                first.resize(r_mark);
-                end.resize(r_mark);
-            }
-            query_first.push_back(group_not.size());
-            total += bound;
-        }
+        for (auto &qe : queries) total += smallest(plan.add(where, qe.first, qe.second, Absent::EmptyQuery));
         std::vector<uint64_t> off(queries.size() + 1, 0);
-        uint64_t cap = std::min(total, FIRST_CAP);
-        DevMem d_out(ctx_);
-        for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, (cap + 1) * sizeof(uint32_t), &d_out.p), "intersect batch");
-            const int rc = ii2_query_batch_groups(ctx_, queries.size(), query_first.data(), group_first.data(), group_not.data(), segs.data(),
-                                                  first.data(), end.data(), nullptr, (uint32_t *)d_out.p, cap + 1, off.data());
-            if (rc != II2_ECAPACITY || attempt) {
-                ck(ctx_, rc, "intersect batch");
-                break;
-            }
-            ck(ctx_, ii2_dev_free(ctx_, d_out.p), "intersect batch");
-            d_out.p = nullptr;
-            cap = off.back();
-        }
-        std::vector<uint32_t> all(off.back());
-        if (!all.empty()) ck(ctx_, ii2_copy_d2h(ctx_, all.data(), d_out.p, all.size() * sizeof(uint32_t)), "intersect batch");
+        const Output o = two_call(total, 1, "intersect batch", [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+            const int rc = ii2_query_batch_groups(ctx_, queries.size(), plan.query_first.data(), plan.group_first.data(), plan.group_not.data(),
+                                                  plan.segs.data(), plan.first.data(), plan.end.data(), nullptr, d_ids, cap, off.data());
+            *n = off.back();
+            return rc;
+        });
+        std::vector<uint32_t> all(o.n);
+        if (o.n) ck(ctx_, ii2_copy_d2h(ctx_, all.data(), o.mem.p, o.n * sizeof(uint32_t)), "intersect batch");
         for (size_t q = 0; q < queries.size(); q++) out[q].assign(all.begin() + off[q], all.begin() + off[q + 1]);
         return out;
     }
+    // tests: the first call of two_call allocates at most `ids` ids (1 .. FIRST_CAP, the default), so that a small index reaches the
+    // second call; SecondCalls counts those
+    void SetFirstCap(uint64_t ids) {
+        if (ids < 1 || ids > FIRST_CAP) throw Error("set first cap: 1 to 2^22 ids");
+        first_cap_.store(ids);
+    }
+    uint64_t SecondCalls() const { return second_calls_.load(); }
     // additive: how IntersectMany and IntersectTopBatch turn their terms into lists - 0: bisections of the host dictionaries, 1:
     // ii2_dict_find on resident dictionaries, -1 (the default): the device from RESOLVE_MIN_PAIRS (term, segment) pairs per call.
     // The results are the same in every mode.
@@ -1554,6 +1469,8 @@ class InvertedIndex {
     }
     ii2_ctx *ctx_;
     std::atomic<int> resolve_mode_{-1};                    // SetResolve
+    std::atomic<uint64_t> first_cap_{FIRST_CAP};           // SetFirstCap
+    mutable std::atomic<uint64_t> second_calls_{0};        // two_call's retries
     int build_mode_ = -1;                                  // SetBuild (guarded by mu_)
     std::string basedir_;
     mutable std::mutex mu_;                                // guards shards_ (the map, not the shards) and workers_
@@ -1580,6 +1497,20 @@ static std::vector<Term> unpack_terms(const uint8_t *bytes, const uint64_t *off,
     std::vector<Term> t(n);
     for (uint64_t i = 0; i < n; i++) t[i].assign((const char *)bytes + off[i], off[i + 1] - off[i]);
     return t;
+}
+
+// (id, score) pairs into ids / scores, after what these hold
+static void split_pairs(const std::vector<std::pair<uint32_t, uint32_t>> &top, std::vector<uint32_t> &ids, std::vector<uint32_t> &scores) {
+    for (auto &p : top) { ids.push_back(p.first); scores.push_back(p.second); }
+}
+// The queries of a bulk call: n_q queries over the terms (bytes, off), query q owns terms q_first[q] .. q_first[q + 1] - 1, the first
+// q_req[q] of them required, the others excluded.  fn(q, a, m, e) per query, in order: its required terms are [a, m), its excluded ones [m, e).
+template <class Fn> static void split_queries(const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req, uint64_t n_q, Fn fn) {
+    const std::vector<Term> terms = unpack_terms(bytes, off, n_q ? q_first[n_q] : 0);
+    for (uint64_t q = 0; q < n_q; q++) {
+        const uint64_t a = q_first[q], m = std::min(a + q_req[q], q_first[q + 1]);
+        fn(q, terms.begin() + a, terms.begin() + m, terms.begin() + q_first[q + 1]);
+    }
 }
 
 #define H_TRY(t, ...)                                   \
@@ -1734,30 +1665,26 @@ int ii2h_intersect_at_least(ii2h_target *t, const uint8_t *bytes, const uint64_t
 int ii2h_intersect_top(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t k, uint32_t min_match, const uint8_t *x_bytes,
                        const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, {
-        const auto top = t->index->IntersectTop(unpack_terms(bytes, off, n), k, min_match, unpack_terms(x_bytes, x_off, n_x));
-        t->ids.resize(top.size());
-        t->scores.resize(top.size());
-        for (size_t i = 0; i < top.size(); i++) { t->ids[i] = top[i].first; t->scores[i] = top[i].second; }
-        *n_ids = top.size();
+        t->ids.clear();
+        t->scores.clear();
+        split_pairs(t->index->IntersectTop(unpack_terms(bytes, off, n), k, min_match, unpack_terms(x_bytes, x_off, n_x)), t->ids, t->scores);
+        *n_ids = t->ids.size();
     })
 }
 int ii2h_intersect_top_weighted(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint32_t *weights, uint64_t k,
                                 uint32_t min_score, const uint8_t *x_bytes, const uint64_t *x_off, uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, {
-        const auto top = t->index->IntersectTopWeighted(unpack_terms(bytes, off, n), std::vector<uint32_t>(weights, weights + n), k, min_score,
-                                                        unpack_terms(x_bytes, x_off, n_x));
-        t->ids.resize(top.size());
-        t->scores.resize(top.size());
-        for (size_t i = 0; i < top.size(); i++) { t->ids[i] = top[i].first; t->scores[i] = top[i].second; }
-        *n_ids = top.size();
+        t->ids.clear();
+        t->scores.clear();
+        split_pairs(t->index->IntersectTopWeighted(unpack_terms(bytes, off, n), std::vector<uint32_t>(weights, weights + n), k, min_score,
+                                                   unpack_terms(x_bytes, x_off, n_x)), t->ids, t->scores);
+        *n_ids = t->ids.size();
     })
 }
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->IntersectExcept(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
 }
-// n_q queries over the terms (bytes, off): query q owns terms q_first[q] .. q_first[q + 1] - 1, the first q_req[q] of them required, the
-// others excluded.  Result q: the values of the target's result q (its term is empty)
 int ii2h_set_resolve(ii2h_target *t, int mode) {
     H_TRY(t, {
         if (!t->index) throw Error("set resolve: not an index");
@@ -1767,16 +1694,23 @@ int ii2h_set_resolve(ii2h_target *t, int mode) {
 int ii2h_set_build(ii2h_target *t, int mode) {
     H_TRY(t, { if (t->index) t->index->SetBuild(mode); else t->shard->SetBuild(mode); });
 }
+// tests: the first buffer of the calls that may need a second one, and how many second calls there were (InvertedIndex::SetFirstCap)
+int ii2h_set_first_cap(ii2h_target *t, uint64_t ids) {
+    H_TRY(t, {
+        if (!t->index) throw Error("set first cap: not an index");
+        t->index->SetFirstCap(ids);
+    });
+}
+uint64_t ii2h_second_calls(const ii2h_target *t) { return t->index ? t->index->SecondCalls() : 0; }
+// n_q queries laid out as split_queries takes them.  Result q: the values of the target's result q (its term is empty)
 int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req, uint64_t n_q,
                          uint64_t *n_results) {
     H_TRY(t, {
-        const std::vector<Term> terms = unpack_terms(bytes, off, n_q ? q_first[n_q] : 0);
         std::vector<std::pair<std::vector<Term>, std::vector<Term>>> queries(n_q);
-        for (uint64_t q = 0; q < n_q; q++) {
-            const uint64_t a = q_first[q], m = std::min(a + q_req[q], q_first[q + 1]);
-            queries[q].first.assign(terms.begin() + a, terms.begin() + m);
-            queries[q].second.assign(terms.begin() + m, terms.begin() + q_first[q + 1]);
-        }
+        split_queries(bytes, off, q_first, q_req, n_q, [&](uint64_t q, auto a, auto m, auto e) {
+            queries[q].first.assign(a, m);
+            queries[q].second.assign(m, e);
+        });
         t->result.clear();
         for (auto &ids : t->index->IntersectMany(queries)) t->result.push_back(TermValues{Term(), std::move(ids)});
         *n_results = t->result.size();
@@ -1788,24 +1722,21 @@ int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *o
 int ii2h_intersect_top_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req,
                              const uint32_t *weights, const uint64_t *k, const uint32_t *min_score, uint64_t n_q, uint64_t *n_results) {
     H_TRY(t, {
-        const std::vector<Term> terms = unpack_terms(bytes, off, n_q ? q_first[n_q] : 0);
         std::vector<InvertedIndex::TopQuery> queries(n_q);
-        uint64_t w0 = 0;
-        for (uint64_t q = 0; q < n_q; q++) {
-            const uint64_t a = q_first[q], m = std::min(a + q_req[q], q_first[q + 1]);
-            queries[q].terms.assign(terms.begin() + a, terms.begin() + m);
-            queries[q].except.assign(terms.begin() + m, terms.begin() + q_first[q + 1]);
+        uint64_t w0 = 0;                                         // (one weight per required term, query after query)
+        split_queries(bytes, off, q_first, q_req, n_q, [&](uint64_t q, auto a, auto m, auto e) {
+            queries[q].terms.assign(a, m);
+            queries[q].except.assign(m, e);
             queries[q].weights.assign(weights + w0, weights + w0 + (m - a));
             w0 += m - a;
             queries[q].k = k[q];
             queries[q].min_score = min_score[q];
-        }
+        });
         t->result.clear();
         t->scores.clear();
         for (auto &top : t->index->IntersectTopBatch(queries)) {
-            TermValues tv{Term(), {}};
-            for (auto &p : top) { tv.values.push_back(p.first); t->scores.push_back(p.second); }
-            t->result.push_back(std::move(tv));
+            t->result.push_back(TermValues{Term(), {}});
+            split_pairs(top, t->result.back().values, t->scores);
         }
         *n_results = t->result.size();
     })

@@ -48,8 +48,9 @@ if args.libdir:
 from inverted_index_2_amd import Context, host, synth  # noqa: E402
 if args.libdir:      # a host library from before the switch: the binding types every export it knows, so the absent one gets a stand-in
     host._host = C.CDLL(host.HOST_LIB_PATH)
-    if not hasattr(host._host, "ii2h_set_resolve"):
-        host._host.ii2h_set_resolve = type("Absent", (), {})()
+    for name in ("ii2h_set_resolve", "ii2h_set_first_cap", "ii2h_second_calls"):
+        if not hasattr(host._host, name):
+            setattr(host._host, name, type("Absent", (), {})())
 from inverted_index_2_amd._lib import II2_DEVICE  # noqa: E402
 from inverted_index_2_amd.engine import DeviceArray, II2Error  # noqa: E402
 
