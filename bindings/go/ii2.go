@@ -206,7 +206,8 @@ func (a *Alignment) Free() { C.ii2_align_free(a.h); a.h = nil }
 // segment is written or loaded, so that alignments read it in place (no upload per merge).
 type Dictionary struct{ h *C.ii2_dict }
 
-// NewDictionary uploads a dictionary given flat (termBytes, termOff[n+1], termOff[0] == 0).
+// NewDictionary uploads a dictionary given flat (termBytes, termOff[n+1], termOff[0] == 0).  Terms that do not ascend
+// strictly in bytes.Compare order are an error (II2_EINVAL).
 func (c *Ctx) NewDictionary(termBytes []byte, termOff []uint64) (*Dictionary, error) {
 	var tb *C.uint8_t
 	if len(termBytes) > 0 {

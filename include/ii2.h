@@ -164,7 +164,10 @@ int ii2_seg_select(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, const int64
 typedef struct ii2_align ii2_align;
 /* A segment's term dictionary resident in HBM (sorted, duplicate-free terms: term_off[n_terms + 1] byte offsets into
  * term_bytes, term_off[0] = 0; `where` says where the two arrays live).  Made once, when the segment is created or
- * loaded; alignments then read it in place. */
+ * loaded; alignments then read it in place.  II2_EINVAL, with nothing left allocated and *out NULL: term_off that does not
+ * start at 0, descends or ends past the bytes, and terms that do not ascend strictly in bytes.Compare order - term i > 0 must
+ * be greater than term i - 1 (an equal or a smaller neighbour is refused; checked on the device, next to the keys).  The
+ * alignment ranks by bisection and relies on that order: ii2_align_terms makes its dictionaries by this call and refuses alike. */
 typedef struct ii2_dict ii2_dict;
 int ii2_dict_create(ii2_ctx *ctx, const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, int where, ii2_dict **out);
 void ii2_dict_free(ii2_dict *dict);
@@ -246,6 +249,28 @@ int ii2_align_dicts(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, ii2_
 /* The same from flat host arrays (k temporary dictionaries are made and freed inside the call): */
 int ii2_align_terms(ii2_ctx *ctx, uint32_t k, const uint8_t *term_bytes, const uint64_t *term_off,
                     const uint64_t *seg_first, ii2_align **out);
+/* The alignment's arithmetic, host only (no GPU needed): what the ranking kernel of ii2_align_terms / ii2_align_dicts would do
+ * for these dictionaries (host arrays as ii2_align_terms takes them), by the constants and functions the kernel uses.  A
+ * workgroup takes terms_per_workgroup consecutive terms of one dictionary (n_workgroups in all); for every other dictionary it
+ * finds the bracket of terms its stretch can meet, and bisects there - in LDS when the bracket has at most staged_cap entries
+ * (brackets_staged), in global memory when it has more (brackets_global), not at all when it is empty (brackets_empty).
+ * max_bracket is the largest bracket; long_terms is 1 when some term of any dictionary is longer than 8 bytes (a tie of the
+ * 8-byte keys is then decided by the bytes, else by the lengths alone).  Same checks and codes as ii2_align_terms - II2_EINVAL:
+ * k == 0 or k > II2_MAX_LISTS, a NULL array, seg_first that does not start at 0 or descends, term_off that descends, terms of a
+ * dictionary that do not ascend strictly; II2_ERANGE: 2^31 or more terms - and II2_EINVAL for a NULL plan.  *plan is written
+ * only on success. */
+typedef struct {
+    uint64_t n_terms, n_workgroups;
+    uint64_t brackets_staged;   /* 0 < size <= staged_cap: bisected in LDS        */
+    uint64_t brackets_global;   /* size > staged_cap: bisected in global memory   */
+    uint64_t brackets_empty;    /* size == 0                                      */
+    uint64_t max_bracket;
+    uint32_t long_terms;        /* some term is longer than 8 bytes               */
+    uint32_t terms_per_workgroup, staged_cap;
+    uint32_t pad;
+} ii2_align_plan_info;          /* 64 bytes */
+int ii2_align_plan(uint32_t k, const uint8_t *term_bytes, const uint64_t *term_off, const uint64_t *seg_first,
+                   ii2_align_plan_info *plan);
 int ii2_align_info(const ii2_align *a, uint64_t *n_union, uint32_t *k);
 /* rep[n_union]: index (into term_off) of one input term equal to union term u, in union order;
  * src_list[k * n_union]: row s = for every union term the term of dictionary s equal to it (index

@@ -35,6 +35,12 @@ class DictBuildStats(C.Structure):
                 ("n_passes", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class AlignPlan(C.Structure):
+    _fields_ = [("n_terms", C.c_uint64), ("n_workgroups", C.c_uint64), ("brackets_staged", C.c_uint64), ("brackets_global", C.c_uint64),
+                ("brackets_empty", C.c_uint64), ("max_bracket", C.c_uint64), ("long_terms", C.c_uint32), ("terms_per_workgroup", C.c_uint32),
+                ("staged_cap", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class CountStats(C.Structure):
     _fields_ = [("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64),
                 ("n_windows", C.c_uint32)]
@@ -100,6 +106,7 @@ PROTOTYPES = {
     "ii2_dict_build_plan": (C.c_int, [vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ii2_align_dicts": (C.c_int, [vp, C.c_uint32, vpp, vpp]),
     "ii2_align_terms": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vpp]),
+    "ii2_align_plan": (C.c_int, [C.c_uint32, vp, vp, vp, C.POINTER(AlignPlan)]),
     "ii2_align_info": (C.c_int, [vp, u64p, C.POINTER(C.c_uint32)]),
     "ii2_align_export": (C.c_int, [vp, vp, vp, vp]),
     "ii2_seg_select_aligned": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, vpp]),

@@ -19,14 +19,14 @@
 #include <cstring>
 #include <new>
 
+#include "align_plan.h"
 #include "dv1_device.h"
 #include "internal.h"
 #include "term_device.h"
 
 namespace ii2 {
 
-constexpr uint32_t AL_THREADS = 256;      // threads per workgroup of the ranking kernel
-constexpr uint32_t AL_T = 1024;           // terms per workgroup (the brackets in the other dictionaries are searched once per workgroup)
+// AL_THREADS, AL_T (terms per workgroup) and AL_LCAP (bracket entries staged in LDS) are align_plan.h's, shared with ii2_align_plan
 
 struct AlignDicts {
     const uint64_t *key[MAX_LISTS];
@@ -39,7 +39,8 @@ struct AlignDicts {
     uint32_t long_terms;                  // some dictionary has terms longer than 8 bytes
 };
 
-// keys of a dictionary + checks: offsets non-decreasing, terms strictly ascending (bad |= 1 / 2), any term longer than 8 bytes (bad |= 4)
+// keys of a dictionary + checks: offsets non-decreasing, terms strictly ascending (bad |= 1 / 2), any term longer than 8 bytes (bad |= 4).
+// Every thread compares its term with the one before it (whose key it derives from the bytes: key[i - 1] is another thread's to write).
 __global__ void k_dict_keys(const uint8_t *__restrict__ bytes, const uint64_t *__restrict__ off, uint64_t n, uint64_t n_bytes, uint64_t *__restrict__ key,
                             uint32_t *__restrict__ bad) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,6 +56,13 @@ __global__ void k_dict_keys(const uint8_t *__restrict__ bytes, const uint64_t *_
     }
     key[i] = kk;
     if (len > 8) atomicOr(bad, 4u);
+    if (i > 0) {
+        const uint64_t pb = off[i - 1];
+        if (pb <= b) {                      // (else thread i - 1 reports the offsets; [pb, b) lies inside the bytes: b <= e <= n_bytes)
+            const uint64_t plen = b - pb;
+            if (term_cmp(term_key(bytes + pb, plen), bytes + pb, plen, kk, bytes + b, len, true) >= 0) atomicOr(bad, 2u);
+        }
+    }
 }
 
 // the comparison (term_cmp), TermRef and the bisection (term_bound) are term_device.h's
@@ -69,7 +77,6 @@ __device__ __forceinline__ uint32_t bound_in(const AlignDicts &d, uint32_t s, ui
 // is staged in LDS with coalesced loads — bisecting in global memory would cost one cache line per lane and step — and
 // a thread bisects there once, for its first term, then walks on for the following ones (they ascend).
 constexpr uint32_t AL_PER = AL_T / AL_THREADS;        // 4
-constexpr uint32_t AL_LCAP = 2048;                    // bracket entries staged per dictionary (larger brackets: bisection in global memory)
 __global__ __launch_bounds__(AL_THREADS) void k_align_rank(AlignDicts d, uint32_t *__restrict__ pos, uint32_t *__restrict__ head) {
     __shared__ uint32_t br[2][MAX_LISTS];       // where the workgroup's stretch of terms begins / ends in every dictionary
     __shared__ uint64_t SK[AL_LCAP];
@@ -87,7 +94,7 @@ __global__ __launch_bounds__(AL_THREADS) void k_align_rank(AlignDicts d, uint32_
         const uint32_t sp = threadIdx.x >> 1, which = threadIdx.x & 1u;
         // lower bracket: terms of sp before the stretch's first term; upper bracket: up to and including its last term
         const TermRef x = term_of(d, s, which ? i1 - 1u : i0);
-        br[which][sp] = bound_in(d, sp, 0u, d.n[sp], x, which != 0u);
+        br[which][sp] = align_bracket(TermDict{d.key[sp], d.off[sp], d.bytes[sp]}, d.n[sp], x, which != 0u, lt);
     }
     // my terms
     TermRef x[AL_PER];
@@ -259,6 +266,7 @@ static int dict_create_unlocked(ii2_ctx *ctx, const uint8_t *term_bytes, const u
     HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (bad & 1u) return fail(ctx, II2_EINVAL, "ii2_dict_create: term_off must be non-decreasing and end at the bytes' length");
+    if (bad & 2u) return fail(ctx, II2_EINVAL, "ii2_dict_create: the terms must ascend strictly in byte order (sorted, no duplicates)");
     d->long_terms = (bad & 4u) ? 1u : 0u;
     *out = d.release();
     return II2_OK;
@@ -284,7 +292,7 @@ static int align_dicts_unlocked(ii2_ctx *ctx, uint32_t k, const ii2_dict *const 
         ad.long_terms |= dicts[s]->long_terms;
         a->seg_first[s] = n;
         n += dicts[s]->n;
-        wgs += (dicts[s]->n + AL_T - 1) / AL_T;
+        wgs += align_workgroups(dicts[s]->n);
     }
     if (n >= (1ull << 31) || wgs >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_align_dicts: 2^31 or more terms");
     ad.first[k] = (uint32_t)n;
@@ -368,6 +376,61 @@ int ii2_align_terms(ii2_ctx *ctx, uint32_t k, const uint8_t *term_bytes, const u
     if (!rc) rc = align_dicts_unlocked(ctx, k, dicts.data(), out);
     for (ii2_dict *d : dicts) delete d;
     return rc;
+}
+
+// host only: the brackets k_align_rank would bisect for these dictionaries, by align_plan.h's constants and function and
+// term_device.h's comparison - the checks of ii2_align_terms (ii2_dict_create's among them) come first, nothing is written on error
+int ii2_align_plan(uint32_t k, const uint8_t *term_bytes, const uint64_t *term_off, const uint64_t *seg_first, ii2_align_plan_info *plan) {
+    if (!plan || !term_off || !seg_first || k == 0 || k > II2_MAX_LISTS) return II2_EINVAL;
+    if (seg_first[0] != 0) return II2_EINVAL;
+    for (uint32_t s = 0; s < k; s++)
+        if (seg_first[s + 1] < seg_first[s]) return II2_EINVAL;
+    if (seg_first[k] >= (1ull << 31)) return II2_ERANGE;
+    const uint64_t n_all = seg_first[k];
+    for (uint64_t i = 0; i < n_all; i++)
+        if (term_off[i + 1] < term_off[i]) return II2_EINVAL;
+    if (term_off[n_all] > term_off[0] && !term_bytes) return II2_EINVAL;
+    std::vector<uint64_t> key(n_all);
+    bool lt = false;
+    for (uint64_t i = 0; i < n_all; i++) {
+        const uint64_t len = term_off[i + 1] - term_off[i];
+        key[i] = term_key(term_bytes + term_off[i], len);
+        lt |= len > 8;
+    }
+    std::vector<TermDict> td(k);
+    for (uint32_t s = 0; s < k; s++) {
+        td[s] = TermDict{key.data() + seg_first[s], term_off + seg_first[s], term_bytes};
+        for (uint64_t i = seg_first[s] + 1; i < seg_first[s + 1]; i++) {       // what k_dict_keys refuses (bad & 2)
+            const uint8_t *a = term_bytes + term_off[i - 1], *b = term_bytes + term_off[i];
+            if (term_cmp(key[i - 1], a, term_off[i] - term_off[i - 1], key[i], b, term_off[i + 1] - term_off[i], true) >= 0) return II2_EINVAL;
+        }
+    }
+    ii2_align_plan_info p;
+    std::memset(&p, 0, sizeof p);
+    p.n_terms = n_all;
+    p.long_terms = lt ? 1u : 0u;
+    p.terms_per_workgroup = AL_T;
+    p.staged_cap = AL_LCAP;
+    for (uint32_t s = 0; s < k; s++) {
+        const uint32_t n = (uint32_t)(seg_first[s + 1] - seg_first[s]);
+        const uint64_t wgs = align_workgroups(n);
+        p.n_workgroups += wgs;
+        for (uint64_t w = 0; w < wgs; w++) {
+            const uint32_t i0 = (uint32_t)w * AL_T, i1 = i0 + AL_T < n ? i0 + AL_T : n;       // the stretch, as k_align_rank cuts it
+            const TermRef x0 = term_at(td[s], i0), x1 = term_at(td[s], i1 - 1u);
+            for (uint32_t sp = 0; sp < k; sp++) {
+                if (sp == s) continue;
+                const uint32_t np = (uint32_t)(seg_first[sp + 1] - seg_first[sp]);
+                const uint64_t nb = (uint64_t)align_bracket(td[sp], np, x1, true, lt) - align_bracket(td[sp], np, x0, false, lt);
+                if (nb == 0) p.brackets_empty++;
+                else if (nb <= AL_LCAP) p.brackets_staged++;
+                else p.brackets_global++;
+                if (nb > p.max_bracket) p.max_bracket = nb;
+            }
+        }
+    }
+    *plan = p;
+    return II2_OK;
 }
 
 int ii2_align_info(const ii2_align *a, uint64_t *n_union, uint32_t *k) {

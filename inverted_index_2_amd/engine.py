@@ -869,6 +869,23 @@ def seg_gather_plan(shapes):
     return rc, list(lo), list(bo), list(qo)
 
 
+def align_plan(dictionaries) -> _lib.AlignPlan:
+    """Host arithmetic of the alignment (ii2_align_plan, no GPU): the brackets the ranking kernel would bisect for these k sorted,
+    duplicate-free dictionaries (lists of bytes) - how many in LDS, in global memory and empty - and its constants."""
+    flat = [t for d in dictionaries for t in d]
+    off = np.zeros(len(flat) + 1, np.uint64)
+    if flat:
+        off[1:] = np.cumsum([len(t) for t in flat])
+    blob = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
+    first = np.zeros(len(dictionaries) + 1, np.uint64)
+    first[1:] = np.cumsum([len(d) for d in dictionaries])
+    plan = _lib.AlignPlan()
+    rc = _lib.load().ii2_align_plan(len(dictionaries), _ptr(blob), _ptr(off), _ptr(first), C.byref(plan))
+    if rc:
+        raise II2Error(rc, "ii2_align_plan refused the dictionaries")
+    return plan
+
+
 def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(_lib.II2_UNIQUE_ID_BYTES)
     rc = _lib.load().ii2_comm_unique_id(buf)

@@ -153,3 +153,17 @@ def test_malformed_dictionary_is_refused(ctx):
         ctx.dictionary_flat(np.zeros(4, np.uint8), np.array([0, 3, 2, 4], np.uint64))      # offsets not monotone
     with pytest.raises(II2Error):
         ctx.dictionary_flat(np.zeros(4, np.uint8), np.array([1, 2, 4], np.uint64))         # does not start at 0
+    # terms that do not ascend strictly are refused when the dictionary is made, so that no alignment ever ranks them (places
+    # would collide there): an equal neighbour, a swapped pair, a swap that only the ninth byte shows, "a\0" before "a" - at
+    # the front, in the middle and at the end of a dictionary, and on both entry points that make dictionaries
+    for pair in ([b"m", b"m"], [b"n", b"m"], [b"tiebreakb", b"tiebreaka"], [b"m\0", b"m"]):
+        for terms in (pair, [b"a", b"b"] + pair + [b"z"], [b"a%03d" % i for i in range(600)] + pair):
+            with pytest.raises(II2Error) as e:
+                ctx.dictionary(terms)
+            assert e.value.code == -1 and "ascend" in str(e.value), terms
+        with pytest.raises(II2Error) as e:
+            ctx.align_terms([[b"a", b"b"], pair])          # refused at the dictionary's creation, inside the call
+        assert e.value.code == -1 and "ascend" in str(e.value)
+    # the same neighbours in ascending order are taken
+    for pair in ([b"m", b"n"], [b"tiebreaka", b"tiebreakb"], [b"m", b"m\0"]):
+        ctx.dictionary(pair).free()
