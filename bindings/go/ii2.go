@@ -109,6 +109,34 @@ func (c *Ctx) Decode(s *Segment) (postOff []uint64, values []uint32, err error) 
 	return postOff, values, nil
 }
 
+// SegMeta holds the arrays the library derives when a segment is made (ii2_seg_export_meta): postings and last doc per list,
+// the owner of every block (0xFFFFFFFF: none of a view's lists, and the entry past the last block) and - when the segment has
+// the host mirror - {first doc, first doc of the last block, last doc} per list as the path choice reads it.
+type SegMeta struct {
+	Cnt, LastDoc, BlkList, Spans []uint32 // Spans is nil when SpansMirrored is false
+	IsView, SpansMirrored        bool
+	MergeBlocks, MergeBytes      uint64
+	Postings                     uint64
+}
+
+// Meta copies a segment's derived arrays to the host (one wait, no kernel).
+func (c *Ctx) Meta(s *Segment) (*SegMeta, error) {
+	var info C.ii2_seg_info
+	C.ii2_seg_get_info(s.h, &info)
+	m := &SegMeta{Cnt: make([]uint32, uint64(info.n_lists)), LastDoc: make([]uint32, uint64(info.n_lists)),
+		BlkList: make([]uint32, uint64(info.n_blocks)+1), Spans: make([]uint32, 3*uint64(info.n_lists))}
+	var mi C.ii2_seg_meta_info
+	if rc := C.ii2_seg_export_meta(c.h, s.h, u32ptr(m.Cnt), u32ptr(m.LastDoc), u32ptr(m.BlkList), u32ptr(m.Spans), &mi); rc != 0 {
+		return nil, c.err("export meta", rc)
+	}
+	m.IsView, m.SpansMirrored = mi.is_view != 0, mi.spans_mirrored != 0
+	m.MergeBlocks, m.MergeBytes, m.Postings = uint64(mi.merge_blocks), uint64(mi.merge_bytes), uint64(mi.n_postings)
+	if !m.SpansMirrored {
+		m.Spans = nil
+	}
+	return m, nil
+}
+
 func (s *Segment) Free() { C.ii2_seg_free(s.h); s.h = nil }
 
 // MergeAligned replaces the loop of Shard.Merge (shard.go:163-212) for k term-aligned segments

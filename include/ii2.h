@@ -289,6 +289,32 @@ int ii2_seg_select_aligned_all(ii2_ctx *ctx, const ii2_seg *const *srcs, const i
 void ii2_align_free(ii2_align *a);
 
 int ii2_seg_get_info(const ii2_seg *seg, ii2_seg_info *info);
+/* Introspection: the arrays the library DERIVES when a segment is made and every query and merge kernel reads next to the DV1
+ * bytes, copied to host buffers (any output may be NULL).  With n_lists / n_blocks as ii2_seg_get_info reports them (a view's
+ * n_blocks is its store's):
+ *   cnt[n_lists]            postings per list;
+ *   last_doc[n_lists]       last doc per list, 0 for an empty list;
+ *   blk_list[n_blocks + 1]  the list that owns each block, in the segment's own numbering; 0xFFFFFFFF for a block that none of a
+ *                           view's lists owns and, for every segment, in the entry past the last block;
+ *   spans[3 * n_lists]      {first doc, first doc of the last block, last doc} per list, zeros for an empty list: the host mirror
+ *                           exactly as the path choice reads it.  Written only when the segment has the mirror
+ *                           (info->spans_mirrored; segments of more than 65536 lists and the views of ii2_seg_select_aligned*
+ *                           have none: their spans are fetched when a query first asks);
+ *   info                    is_view: made by ii2_seg_select*; merge_blocks / merge_bytes: what a merge of the segment can at
+ *                           most read - the totals, or for a view of ii2_seg_select the blocks and payload bytes of its window of
+ *                           the store; n_postings: exact for whole segments and the views of ii2_seg_select, for the views of
+ *                           ii2_seg_select_aligned* the store's total (an upper bound).
+ * II2_EINVAL for a NULL ctx or seg and for a segment of another device.  One wait, no kernel.  Not a set operation: it takes no
+ * kernel path of ii2_ctx_paths. */
+typedef struct {
+    uint64_t n_postings;
+    uint64_t merge_blocks;
+    uint64_t merge_bytes;
+    uint32_t is_view;
+    uint32_t spans_mirrored;
+} ii2_seg_meta_info;    /* 32 bytes */
+int ii2_seg_export_meta(ii2_ctx *ctx, const ii2_seg *seg, uint32_t *cnt, uint32_t *last_doc, uint32_t *blk_list, uint32_t *spans,
+                        ii2_seg_meta_info *info /* may be NULL */);
 /* Frees a segment.  As with any free, no call that reads the segment may still be running (the library's calls are
  * synchronous: that is "after they returned"; a query started with ii2_intersect_async is waited for first).  The
  * segment's device arrays go back to a size-class cache and are handed out again by the next segment that is made — a

@@ -22,6 +22,11 @@ class SegInfo(C.Structure):
     _fields_ = [("n_lists", C.c_uint64), ("n_postings", C.c_uint64), ("n_blocks", C.c_uint64), ("n_bytes", C.c_uint64)]
 
 
+class SegMetaInfo(C.Structure):
+    _fields_ = [("n_postings", C.c_uint64), ("merge_blocks", C.c_uint64), ("merge_bytes", C.c_uint64), ("is_view", C.c_uint32),
+                ("spans_mirrored", C.c_uint32)]
+
+
 class MergeStats(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("n_terms_out", C.c_uint64), ("n_tiles", C.c_uint64)]
 
@@ -113,6 +118,7 @@ PROTOTYPES = {
     "ii2_seg_select_aligned_all": (C.c_int, [vp, vpp, vp, vp, vpp]),
     "ii2_align_free": (None, [vp]),
     "ii2_seg_get_info": (C.c_int, [vp, C.POINTER(SegInfo)]),
+    "ii2_seg_export_meta": (C.c_int, [vp, vp, vp, vp, vp, vp, C.POINTER(SegMetaInfo)]),
     "ii2_seg_free": (None, [vp]),
     "ii2_tomb_create": (C.c_int, [vp, vp, C.c_uint64, C.c_int, vpp]),
     "ii2_tomb_free": (None, [vp]),

@@ -204,7 +204,8 @@ __global__ void k_align_view(const int32_t *__restrict__ sel_row, const uint32_t
 __global__ void k_align_blk_list(const uint32_t *__restrict__ src_blk_list, uint64_t n_blocks, uint64_t first_list, uint64_t n_dict,
                                  const uint32_t *__restrict__ uidx_seg, uint32_t *__restrict__ blk_list) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_blocks) return;
+    if (b > n_blocks) return;
+    if (b == n_blocks) { blk_list[b] = 0xFFFFFFFFu; return; }       // the entry past the last block, as every maker leaves it
     const uint32_t li = src_blk_list[b];
     uint32_t v = 0xFFFFFFFFu;
     if (li != 0xFFFFFFFFu && li >= first_list && (uint64_t)li - first_list < n_dict) v = uidx_seg[(uint64_t)li - first_list];
@@ -491,9 +492,8 @@ static int select_aligned_one(ii2_ctx *ctx, const ii2_seg *src, const ii2_align 
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_align_view, dim3(grid_for(nu + 1)), dim3(256), 0, st, sel_row, (const uint32_t *)d_before, nu, first_list,
                            (const uint32_t *)src->d_blk_off, (const uint32_t *)src->d_cnt, (const uint32_t *)src->d_last_doc, d_blk_off, d_cnt, d_last);
-        if (src->n_blocks)
-            hipLaunchKernelGGL(k_align_blk_list, dim3(grid_for(src->n_blocks)), dim3(256), 0, st, (const uint32_t *)src->d_blk_list, src->n_blocks, first_list, n_dict,
-                               (const uint32_t *)(a->d_uidx + a->seg_first[s]), d_blk_list);
+        hipLaunchKernelGGL(k_align_blk_list, dim3(grid_for(src->n_blocks + 1)), dim3(256), 0, st, (const uint32_t *)src->d_blk_list, src->n_blocks, first_list, n_dict,
+                           (const uint32_t *)(a->d_uidx + a->seg_first[s]), d_blk_list);
         e = hipGetLastError();
     }
     if (e == hipSuccess && wait) e = hipStreamSynchronize(st);

@@ -590,6 +590,29 @@ int ii2_seg_get_info(const ii2_seg *seg, ii2_seg_info *info) {
     return II2_OK;
 }
 
+// the derived arrays as the kernels and the path choice read them: copies only (one wait, no kernel)
+int ii2_seg_export_meta(ii2_ctx *ctx, const ii2_seg *seg, uint32_t *cnt, uint32_t *last_doc, uint32_t *blk_list, uint32_t *spans,
+                        ii2_seg_meta_info *info) {
+    if (!ctx || !seg || seg->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_seg_export_meta: bad argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nl = (size_t)seg->n_lists * sizeof(uint32_t);
+    if (cnt && nl) HIP_TRY(ctx, hipMemcpyAsync(cnt, seg->d_cnt, nl, hipMemcpyDeviceToHost, ctx->stream));
+    if (last_doc && nl) HIP_TRY(ctx, hipMemcpyAsync(last_doc, seg->d_last_doc, nl, hipMemcpyDeviceToHost, ctx->stream));
+    if (blk_list) HIP_TRY(ctx, hipMemcpyAsync(blk_list, seg->d_blk_list, (seg->n_blocks + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const bool mirrored = seg->h_spans.size() == 3 * seg->n_lists;       // (what setop.cpp asks before it reads the mirror)
+    if (spans && mirrored && nl) std::memcpy(spans, seg->h_spans.data(), 3 * nl);
+    if (info) {
+        info->n_postings = seg->n_postings;
+        info->merge_blocks = seg->merge_blocks();
+        info->merge_bytes = seg->merge_bytes();
+        info->is_view = seg->is_view ? 1u : 0u;
+        info->spans_mirrored = mirrored ? 1u : 0u;
+    }
+    return II2_OK;
+}
+
 int ii2_seg_select(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, const int64_t *src_list, ii2_seg **out) {
     if (!ctx || !src || !out || (n_out && !src_list) || src->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_seg_select: bad argument");
     std::lock_guard<std::mutex> g(ctx->mu);

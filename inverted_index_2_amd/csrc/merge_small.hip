@@ -342,6 +342,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_merge_small(SmallParams p) {
         o->blk_off[T2] = bo_tot;
         p.o_skip[bo_tot].first_doc = n_out ? sm.E[n_out - 1u] : 0u;
         p.o_skip[bo_tot].byte_off = n_bytes;
+        p.o_blk_list[bo_tot] = 0xFFFFFFFFu;              // the entry past the last block, as every maker leaves it
         for (uint32_t z = 0; z < 16u; z++) p.o_payload[n_bytes + z] = 0;
         o->n_terms_out = T2; o->n_out = n_out; o->n_blocks = bo_tot; o->n_bytes = n_bytes; o->n_in = n; o->error = 0;
     }

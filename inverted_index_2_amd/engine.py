@@ -934,6 +934,23 @@ class Segment:
         self.ctx._ck(self.ctx.lib.ii2_seg_export(self.ctx.h, self.h, _ptr(blk), _ptr(skip), _ptr(payload)))
         return blk, skip, payload[: self.info.n_bytes]
 
+    def meta(self, ctx: Optional["Context"] = None):
+        """The arrays the library derives when the segment is made (ii2_seg_export_meta), as a dict: cnt, last_doc (u32
+        [n_lists]), blk_list (u32 [n_blocks + 1], a view's n_blocks being its store's), spans (u32 [n_lists, 3]: the host mirror
+        the path choice reads, None when the segment has none), and is_view, spans_mirrored, merge_blocks, merge_bytes,
+        n_postings."""
+        c = ctx if ctx is not None and ctx.h else self.ctx
+        nl, nb = self.info.n_lists, self.info.n_blocks
+        cnt, last = np.zeros(max(nl, 1), np.uint32), np.zeros(max(nl, 1), np.uint32)
+        blk_list = np.zeros(nb + 1, np.uint32)
+        spans = np.zeros(max(3 * nl, 1), np.uint32)
+        info = _lib.SegMetaInfo()
+        c._ck(c.lib.ii2_seg_export_meta(c.h, self.h, _ptr(cnt), _ptr(last), _ptr(blk_list), _ptr(spans), C.byref(info)))
+        return {"cnt": cnt[:nl], "last_doc": last[:nl], "blk_list": blk_list,
+                "spans": spans[: 3 * nl].reshape(nl, 3) if info.spans_mirrored else None,
+                "is_view": bool(info.is_view), "spans_mirrored": bool(info.spans_mirrored), "merge_blocks": int(info.merge_blocks),
+                "merge_bytes": int(info.merge_bytes), "n_postings": int(info.n_postings)}
+
     def free(self) -> None:
         if self.h:
             self.ctx.lib.ii2_seg_free(self.h)      # needs no context: the segment knows its device

@@ -190,7 +190,13 @@ def test_segments_concatenate_like_the_exchange_would(ctx):
     a = flat_all[int(po_all[li]):int(po_all[li + 1])]
     out, n = ctx.intersect([(cat, li), (cat, li)])
     assert n == a.size and np.array_equal(out.download(n), a)
-    merged, _ = ctx.merge_to_segment([cat, cat])                # and the merge reads it like any other segment
+    # (that query reads no block owner: the derived arrays themselves, against the concatenated lists)
+    m = cat.meta()
+    lens = np.diff(po_all.astype(np.int64))
+    assert np.array_equal(m["cnt"], lens)
+    assert np.array_equal(m["blk_list"], np.append(np.repeat(np.arange(lens.size), (lens + 255) // 256), 0xFFFFFFFF))
+    assert np.array_equal(m["last_doc"], [flat_all[int(po_all[i + 1]) - 1] if lens[i] else 0 for i in range(lens.size)])
+    merged, _ = ctx.merge_to_segment([cat, cat])               # and the merge reads it like any other segment
     mpo, mv = merged.decode()
     assert np.array_equal(mpo, po_all) and np.array_equal(mv, flat_all)
     from inverted_index_2_amd.engine import II2Error

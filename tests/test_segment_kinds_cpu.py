@@ -1,0 +1,151 @@
+"""CPU: the table of segment kinds itself (tests/segment_kinds.py) - every maker is there, every edge the derived arrays can go
+wrong at occurs in some shape, every plan has the structure its kind is about, and the numpy reference agrees with the block table
+of the oracle's encoding of the store."""
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from tests import segment_kinds as sk
+
+
+def test_every_maker_has_a_kind():
+    assert set(sk.KINDS) == {"encode_host", "encode_device", "build_pairs", "import_oracle", "merge_stream", "merge_two_pass",
+                             "merge_tomb_stream", "merge_tomb_two_pass", "select", "select_aligned", "select_aligned_all",
+                             "merge_small", "concat", "allgather", "big"}
+    assert len(sk.CASES) == len(sk.KINDS) * len(sk.SHAPES)
+    for k, (plan, make, is_view, aligned) in sk.KINDS.items():
+        assert is_view == k.startswith("select") and aligned == k.startswith("select_aligned"), k
+
+
+def test_the_shapes_hold_every_edge():
+    shapes = {n: sk.shape(n) for n in sk.SHAPES}
+    every = [l for s in shapes.values() for l in s]
+    lens = {len(l) for l in every}
+    assert {0, 1, 255, 256, 257, 511, 512, 513, 16384} <= lens
+    assert any(l.tolist() == [0] for l in every)
+    assert any(len(l) > 1 and l[-1] == 0xFFFFFFFF for l in every) and any(l.tolist() == [0xFFFFFFFF] for l in every)
+    assert any(len(l) > 1 and l[0] == 0 for l in every)
+    assert any(len(l) > 256 and len(l) % 256 == 1 for l in every)                   # a last block of one posting
+    for name, s in shapes.items():
+        assert sum(len(l) for l in s) < 60_000, name
+        assert all(l.dtype == np.uint32 and np.all(np.diff(l.astype(np.int64)) > 0) for l in s), name
+        span = max(int(l[-1]) for l in s if len(l)) - min(int(l[0]) for l in s if len(l))
+        assert 2048 < span < (1 << 19), name                                         # several 2048-doc windows, not thousands
+    s = shapes["lengths"]
+    assert len(s[0]) == 0 and len(s[-1]) == 0                                        # empty first and last ...
+    assert any(len(a) == 0 and len(b) == 0 for a, b in zip(s, s[1:]))                # ... and in a run
+    a, b, c = s[2], s[3], s[4]
+    assert b[0] == a[-1] and b[1] > a[-1] and c[0] > b[-1]
+    crowd = shapes["crowd"]
+    n = np.array([len(l) for l in crowd])
+    assert n.size > 3000 and n.max() == 20000 and np.sum(n > 3) == 1 and set(n[n <= 3]) == {0, 1, 2, 3}
+    start = np.concatenate([[0], np.cumsum(n)])[:-1]
+    big = int(np.argmax(n))
+    assert start[big] % 1024 != 0 and (start[big] + 20000) // 8192 - start[big] // 8192 >= 2      # inside a partition, across workgroups
+    assert np.max(np.bincount(start[n > 0] // 1024)) > 64                             # more than 64 list starts in one 1024-id tile
+    assert np.all(n[:3] == 0) and np.all(n[-2:] == 0) and 0 < big < n.size - 1
+
+
+@pytest.mark.parametrize("kind,shape", sk.CASES)
+def test_reference_agrees_with_the_oracles_block_table(kind, shape):
+    p = sk.plan(kind, shape)
+    r = sk.reference(p)
+    store = [l for l, _ in p.store]
+    po, flat = sk.csr(store)
+    blk, skip, payload = orc.dv1_encode(po, flat)
+    assert np.array_equal(np.diff(blk.astype(np.int64)), [sk.nblk(l) for l in store])
+    assert r.n_blocks == int(blk[-1]) and r.n_bytes == payload.size and r.blk_list.size == r.n_blocks + 1
+    assert r.blk_list[-1] == sk.NONE
+    seen = set()
+    for j, (l, slot) in enumerate(p.store):
+        b0, b1 = int(blk[j]), int(blk[j + 1])
+        assert np.all(r.blk_list[b0:b1] == (sk.NONE if slot is None else slot))
+        if slot is None:
+            continue
+        assert slot not in seen and np.array_equal(p.slots[slot], l)
+        seen.add(slot)
+        assert r.cnt[slot] == len(l)
+        if b1 > b0:
+            assert tuple(r.spans[slot]) == (skip["first_doc"][b0], skip["first_doc"][b1 - 1], l[-1]) and r.last_doc[slot] == l[-1]
+    for i, l in enumerate(p.slots):                       # slots no list of the store stands behind are empty
+        if i not in seen:
+            assert len(l) == 0
+        if len(l) == 0:
+            assert r.cnt[i] == 0 and r.last_doc[i] == 0 and not r.spans[i].any()
+    owned = [j for j, (_, slot) in enumerate(p.store) if slot is not None]
+    assert owned == list(range(owned[0], owned[-1] + 1))                              # a window: consecutive lists of the store
+    b0, b1 = int(blk[owned[0]]), int(blk[owned[-1] + 1])
+    assert r.win_blocks == b1 - b0 and r.win_bytes == int(skip["byte_off"][b1]) - int(skip["byte_off"][b0])
+    if not p.is_view:
+        assert (r.win_blocks, r.win_bytes, r.sum_cnt) == (r.n_blocks, r.n_bytes, r.store_postings)
+    assert p.mirrored == (not p.aligned and kind != "big")
+
+
+@pytest.mark.parametrize("shape", sk.SHAPES)
+def test_every_plan_has_the_structure_its_kind_is_about(shape):
+    lists = sk.shape(shape)
+    same = lambda a, b: len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+    for kind in ("encode_host", "encode_device", "import_oracle", "allgather", "build_pairs", "merge_stream", "merge_two_pass"):
+        assert same(sk.plan(kind, shape).slots, lists), kind
+    p = sk.plan("build_pairs", shape).inputs
+    assert p.list_ids.size > sum(len(l) for l in lists) and np.any(np.diff(p.list_ids.astype(np.int64)) < 0)      # repeats, shuffled
+    pairs = np.unique(np.stack([p.list_ids, p.values]), axis=1)
+    assert pairs.shape[1] == sum(len(l) for l in lists)
+    for kind in ("merge_stream", "merge_tomb_stream"):
+        p = sk.plan(kind, shape)
+        a, b = p.inputs.segs
+        rem = p.inputs.removed if p.inputs.removed is not None else sk.E
+        assert same(p.slots, [np.setdiff1d(np.union1d(x, y), rem).astype(np.uint32) for x, y in zip(a, b)])
+        assert any(len(np.intersect1d(x, y)) and len(np.setdiff1d(x, y)) and len(np.setdiff1d(y, x)) for x, y in zip(a, b))
+    p = sk.plan("merge_tomb_two_pass", shape)
+    n = len(p.slots)
+    assert p.inputs.emptied[0] == 0 and 0 < p.inputs.emptied[1] < n - 1 and p.inputs.emptied[2] == n - 1
+    for s in p.inputs.emptied:                                                       # whole lists emptied by the tombstones
+        assert len(np.union1d(p.inputs.segs[0][s], p.inputs.segs[1][s])) > 0 and len(p.slots[s]) == 0
+    assert sum(len(l) for l in p.slots) < sum(len(l) for l in lists)                 # ... and docs inside other lists
+    p = sk.plan("select", shape)
+    src = p.inputs.src_list
+    assert src[0] == -1 and src[-1] == -1 and np.any(src[1:-1][1:-1] == -1) and np.any(src >= 0)
+    first, last = np.flatnonzero(src >= 0)[[0, -1]]
+    assert np.any(src[first:last] == -1)                                             # an inner empty slot
+    assert p.store[0][1] is None and len(p.store[0][0]) > 256 and p.store[-1][1] is None and len(p.store[-1][0]) > 0      # the window lies in the middle
+    assert same([p.slots[i] for i in np.flatnonzero(src >= 0)], lists)
+    for kind, fl in (("select_aligned", 0), ("select_aligned_all", len(sk.JUNK_BEFORE))):
+        p = sk.plan(kind, shape)
+        assert p.inputs.first_list == fl and len(p.slots[0]) == 0 and p.inputs.union[0] not in p.inputs.dicts[0]
+        assert same([l for l, t in zip(p.slots, p.inputs.union) if t in set(p.inputs.dicts[0])], lists)
+        assert len(p.slots) > len(lists) and p.inputs.union[-1] not in p.inputs.dicts[0]
+    assert sk.plan("select_aligned_all", shape).store[0][1] is None
+    p = sk.plan("merge_small", shape)
+    assert sum(len(d) for d in p.inputs.dicts) <= sk.SMALL_MERGE_TERMS and p.inputs.removed.size <= 4096
+    assert sum(len(l) for s in p.inputs.segs for l in s) <= sk.SMALL_MERGE_POSTINGS
+    assert all(len(l) for l in p.slots) and len(p.slots) == len(p.inputs.dicts[0]) - (1 if p.inputs.dropped else 0)
+    assert shape == "crowd" or any(len(l) > 256 for l in p.slots)      # (the crowd's one long list is beyond the small merge)
+    p = sk.plan("concat", shape)
+    parts = p.inputs.parts
+    assert len(parts) == 4 and len(parts[1]) == 0 and len(parts[2]) == 3 and all(len(l) == 0 for l in parts[2])
+    assert all(sum(len(l) for l in parts[i]) > 0 for i in (0, 3))
+    p = sk.plan("big", shape)
+    assert len(p.slots) == 65537 and same(p.slots[:len(lists)], lists) and all(len(l) == 0 for l in p.slots[len(lists):])
+
+
+@pytest.mark.parametrize("kind", list(sk.KINDS))
+def test_the_readers_questions_are_not_trivial(kind):
+    """What tests/test_gpu_segment_kinds.py asks of every kind has an answer worth comparing."""
+    p, q = sk.plan(kind, sk.READER_SHAPE), sk.queries(kind)
+    s = p.slots
+    assert 0 < q.union_tomb.size < q.union.size
+    assert (max(int(l[-1]) for l in s if len(l)) - min(int(l[0]) for l in s if len(l))) > 4 * 2048                # several windows
+    assert 0 < q.counts.sum() < q.lens.sum() and np.any(~np.isin(q.dset, q.all))
+    assert all(b > a for a, b in q.groups) and q.groups[0][1] <= q.groups[1][0] and q.groups[1][1] <= q.groups[2][0]
+    assert 0 < q.atleast2.size < q.union.size and q.top_scores[0] >= 2 and q.top_ids.size == 10
+    assert sk.nblk(s[q.pair[1]]) >= 2 and sk.nblk(s[q.pair[0]]) >= 2 and 0 < q.pair_and.size < len(s[q.pair[0]])
+    if kind != "merge_small":                             # (whose limits leave the 16384-posting list out)
+        assert len(s[q.pair[1]]) > 8192
+        assert "tomb" in kind or (len(s[q.pair[0]]), len(s[q.pair[1]])) == (513, 16384)      # (tombstones take some of their docs)
+    assert q.miss is not None and q.touch is not None
+    r, e = q.touch
+    assert np.intersect1d(s[r], s[e]).tolist() == [s[r][-1]] and s[e][0] == s[r][-1]
+    r, e = q.miss
+    assert s[e][0] > s[r][-1]
+    assert any(len(m) > len(a) > 0 for m, a in zip(q.merged, s))
