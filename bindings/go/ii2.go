@@ -137,6 +137,16 @@ func (c *Ctx) Meta(s *Segment) (*SegMeta, error) {
 	return m, nil
 }
 
+// DenseForm reports the bitmap a two-list AND has cached for list i (ii2_seg_dense_form): present, its origin and word count,
+// and the bytes held by all forms of the segment's store.  It builds nothing.
+func (c *Ctx) DenseForm(s *Segment, i uint64) (present bool, origin, nWords, storeBytes uint64, err error) {
+	var info [4]C.uint64_t
+	if rc := C.ii2_seg_dense_form(c.h, s.h, C.uint64_t(i), &info[0], nil, 0); rc != 0 {
+		return false, 0, 0, 0, c.err("dense form", rc)
+	}
+	return info[0] != 0, uint64(info[1]), uint64(info[2]), uint64(info[3]), nil
+}
+
 func (s *Segment) Free() { C.ii2_seg_free(s.h); s.h = nil }
 
 // MergeAligned replaces the loop of Shard.Merge (shard.go:163-212) for k term-aligned segments

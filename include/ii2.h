@@ -315,6 +315,15 @@ typedef struct {
 } ii2_seg_meta_info;    /* 32 bytes */
 int ii2_seg_export_meta(ii2_ctx *ctx, const ii2_seg *seg, uint32_t *cnt, uint32_t *last_doc, uint32_t *blk_list, uint32_t *spans,
                         ii2_seg_meta_info *info /* may be NULL */);
+/* The dense form of list list_idx, if a query has cached one: an array of 32-bit words in which bit d - origin is set when doc d is
+ * in the list (origin = the list's first doc & ~31, n_words = ((last doc - origin) >> 5) + 1).  The one-launch two-list AND makes
+ * it the first time it is about to mark the list - its longer one - and option intersect.dense_form allows it; later calls on
+ * that list read the words instead of marking.  The forms belong to the segment's store: a view made by ii2_seg_select* and its
+ * parent share them, they are counted by ii2_devmem_stats and freed with the segment.
+ *   info = {present (0 / 1), origin, n_words, bytes held by this store's forms in all};
+ *   words (may be NULL): the n_words words; II2_ECAPACITY when cap < n_words.
+ * Builds nothing.  Not a set operation: it takes no kernel path of ii2_ctx_paths. */
+int ii2_seg_dense_form(ii2_ctx *ctx, const ii2_seg *seg, uint64_t list_idx, uint64_t info[4], uint32_t *words /* may be NULL */, uint64_t cap);
 /* Frees a segment.  As with any free, no call that reads the segment may still be running (the library's calls are
  * synchronous: that is "after they returned"; a query started with ii2_intersect_async is waited for first).  The
  * segment's device arrays go back to a size-class cache and are handed out again by the next segment that is made — a
@@ -884,6 +893,10 @@ int ii2_selftest(ii2_ctx *ctx);
  *   merge.bitmap_tiles, merge.large_tile    bitmap tiles for dense terms (1: terms with >= 1 posting per 80 docs; N > 1: per N docs; 0: off)
  *                                           / input postings a doc-range tile of a large term aims at
  *   intersect.and2                          dense 2-list ANDs: 1 one launch (look-back for the output offsets), 2 two kernels, 0 the n-list kernel
+ *   intersect.dense_form                    the one-launch 2-list AND reads its longer list as a cached bitmap (ii2_seg_dense_form) instead of
+ *                                           marking it: 1 (default) for a list whose bitmap is at most half its payload bytes, made by
+ *                                           the first such query on the list, which waits for the build once (ii2_intersect_async
+ *                                           too); 0 never (no form is made or used); 2 (tests) for any list
  *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0);
  *                                           tests: -1 / -2 force a give-up of the one-pass encoder's look-back (see below)
  *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters).

@@ -613,6 +613,31 @@ int ii2_seg_export_meta(ii2_ctx *ctx, const ii2_seg *seg, uint32_t *cnt, uint32_
     return II2_OK;
 }
 
+// what a query has cached for a list: nothing is built here (one wait when the words are copied, no kernel)
+int ii2_seg_dense_form(ii2_ctx *ctx, const ii2_seg *seg, uint64_t list_idx, uint64_t info[4], uint32_t *words, uint64_t cap) {
+    if (!ctx || !seg || !info || seg->device != ctx->device || list_idx >= seg->n_lists) return fail(ctx, II2_EINVAL, "ii2_seg_dense_form: bad argument");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc0 = ii2_seg_host_blk_off(ctx, seg)) return rc0;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    ii2_seg_store *store = seg->store.get();
+    if (!store) return II2_OK;
+    std::lock_guard<std::mutex> fg(store->form_mu);
+    info[3] = store->form_bytes;
+    if (seg->h_blk_off[list_idx] == seg->h_blk_off[list_idx + 1]) return II2_OK;       // (an empty list shares its block number with the next one)
+    auto it = store->forms.find(seg->h_blk_off[list_idx]);
+    if (it == store->forms.end() || !it->second.d_words) return II2_OK;
+    info[0] = 1;
+    info[1] = it->second.origin;
+    info[2] = it->second.n_words;
+    if (words) {
+        if (cap < it->second.n_words) return fail(ctx, II2_ECAPACITY, "ii2_seg_dense_form: the form does not fit the buffer");
+        HIP_TRY(ctx, hipMemcpyAsync(words, it->second.d_words, (size_t)it->second.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return II2_OK;
+}
+
 int ii2_seg_select(ii2_ctx *ctx, const ii2_seg *src, uint64_t n_out, const int64_t *src_list, ii2_seg **out) {
     if (!ctx || !src || !out || (n_out && !src_list) || src->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_seg_select: bad argument");
     std::lock_guard<std::mutex> g(ctx->mu);
@@ -1092,6 +1117,7 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "intersect.submax") ctx->opt_intersect_submax = value;
     else if (k == "intersect.and2") ctx->opt_intersect_and2 = value;      // 0: n-list kernel, 1: one launch (look-back), 2: two kernels
     else if (k == "intersect.and2_spin") ctx->opt_and2_spin = value;
+    else if (k == "intersect.dense_form") ctx->opt_dense_form = value;    // 0: never, 1: where the form is <= half the list's payload, 2: always (tests)
     else if (k == "encode.stream") ctx->opt_encode_stream = value;        // 1: one-pass encoder behind a merge (default), 0: two-pass, -1: forced fallback (tests)
     else return fail(ctx, II2_EINVAL, "unknown option");
     return II2_OK;

@@ -96,6 +96,7 @@ struct ii2_ctx {
     bool lb_async_failed = false;       // one of those gave up: ii2_ctx_sync reports it
     uint64_t lb_waits = 0;              // stream waits ii2_lookback_launch put in front of this context's launches (per-device order)
     int64_t opt_intersect_and2 = 1;     // dense 2-list ANDs: the shorter list's postings are tested against the longer one's bitmap (intersect_and2.hip)
+    int64_t opt_dense_form = 1;         // ... against the longer list's cached dense form instead of marking it: 0 never, 1 where the form is <= half the list's payload, 2 always
     int64_t opt_profile_events = 0;     // N > 0: bracket the dominant kernel of every Nth call with HIP events
     uint64_t prof_calls = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;   // recorded pairs since the last read
@@ -161,7 +162,19 @@ struct ii2_seg_store {
     ii2_skip *d_skip = nullptr;
     uint8_t *d_payload = nullptr;
     void *slab = nullptr;            // one allocation that holds ALL arrays of a small segment (ii2_merge_small): freed as a whole
+    // The dense form of a list: bit d - origin of `d_words` is set when doc d is in the list (origin = first doc & ~31).  Made by the
+    // first one-launch two-list AND that is about to mark the list (setop.cpp: dense_form_get), read by every later one instead of
+    // marking.  Keyed by the list's first block number in the store: a view and its parent find the same entry.
+    struct DenseForm {
+        uint32_t *d_words = nullptr; // nullptr: the list was looked at and has no form (so far)
+        uint32_t origin = 0, n_words = 0;
+        uint64_t payload_bytes = 0;  // of the list: what criterion (b) compares the form's bytes with
+    };
+    std::mutex form_mu;              // contexts on different threads share the cache; held while a form is built: nobody reads a half-made one
+    std::unordered_map<uint64_t, DenseForm> forms;
+    uint64_t form_bytes = 0;         // held by the forms in all
     ~ii2_seg_store() {
+        for (auto &f : forms) ii2::dm_free(f.second.d_words);
         ii2::dm_free(d_skip);
         ii2::dm_free(d_payload);
         ii2::dm_free(slab);
@@ -489,6 +502,9 @@ struct DenseParams {
     LookBack lb;                 // ... in one launch (k_and2_fused): the output offsets come from a look-back; lb.agg == nullptr selects the two-kernel form
     float a_scale;               // blocks of lists[1] per doc and ...
     float b_dpb;                 // ... docs per block of lists[0]: where a wave's first probe of lists[1]'s skip table goes
+    const uint32_t *a_bits;      // k_and2_fused: lists[1]'s dense form (bit d - a_origin <=> doc d), or null: the list is marked
+    uint32_t a_origin;           // a multiple of 32
+    uint32_t a_nwords;
 };
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})
@@ -496,6 +512,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
 // the kernel (sequence) those two launchers run for p: what they switch on and what setop.cpp records
 Path intersect_dense_path(const DenseParams &p);
 Path intersect_and2_path(const DenseParams &p);
+// the dense form of list L: bits[0, n_words) (all zero before) get bit d - origin for every doc d of the list
+hipError_t launch_dense_form_build(const ListView &L, uint32_t origin, uint32_t n_words, uint32_t *bits, hipStream_t s);
 
 // OR of any number of lists, block by block (union_many.hip)
 struct UmRange {

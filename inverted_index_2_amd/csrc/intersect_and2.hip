@@ -274,6 +274,33 @@ __device__ __forceinline__ unsigned long long a2_test_lane(const uint32_t *lds_a
     return (((unsigned long long)hhi << 32) | hlo) & L.valid;
 }
 
+// the hard rows of B (multi-byte gaps, a short last block): decoded by the whole wave, every posting inside the window probes the
+// bitmap bm and answers by its index in its block (hs: 256 bits per row)
+__device__ __forceinline__ void a2_test_hard(const ListView &LB, const uint4 &EB, unsigned long long hm, const uint32_t *bm, uint32_t *hs, uint32_t wlo,
+                                             uint32_t wspan) {
+#pragma unroll 1
+    for (uint32_t r = 0; r < A2_ROWS; r++) {
+        if (((hm >> (4u * r)) & 0xFull) == 0ull) continue;
+        const uint32_t fq = (uint32_t)__builtin_amdgcn_readlane((int)EB.x, (int)(4u * r)), q0r = (uint32_t)__builtin_amdgcn_readlane((int)EB.y, (int)(4u * r)),
+                       q1r = (uint32_t)__builtin_amdgcn_readlane((int)EB.w, (int)(4u * r));
+        uint32_t *hr = hs + 8u * r;
+        auto probe = [&](uint32_t ix, uint32_t id) {
+            const uint32_t d = id - wlo;
+            if (d <= wspan && ix < 256u) {
+                const uint32_t u = d + A2_GU;
+                if ((bm[u >> 5] >> (u & 31u)) & 1u) atomicOr(&hr[ix >> 5], 1u << (ix & 31u));
+            }
+        };
+        decode_block_wave4(GlobalBytes{LB.payload}, q0r, q1r, fq,
+                           [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
+                               if (mask & 1u) { probe(ix, id0); ix++; }
+                               if (mask & 2u) { probe(ix, id1); ix++; }
+                               if (mask & 4u) { probe(ix, id2); ix++; }
+                               if (mask & 8u) { probe(ix, id3); ix++; }
+                           });
+    }
+}
+
 // ---- kernel 1: mark A, test B, one answer bit per B posting -------------------------------------------------------
 __device__ __forceinline__ void and2_tiles_body(const DenseParams &p) {
     __shared__ __align__(16) uint32_t lds[4][A2_WAVE_LDS];
@@ -600,6 +627,11 @@ constexpr uint32_t A2F_STAGE_W = (A2_STAGE + 1u) / 2u;            // stage in wo
 constexpr uint32_t A2F_WAVE_LDS = (A2F_STAGE_W > A2_NW ? A2F_STAGE_W : A2_NW) + A2_HS;
 static_assert(A2F_STAGE_W % 4u == 0u, "16-byte alignment of the per-wave LDS regions");
 
+//
+// ABM: lists[1] has a dense form (p.a_bits: one bit per doc, made once per list and cached with the segment's store).  The
+// window's words of it ARE the bitmap the marking passes would build: the wave copies them into LDS - no probe of A's skip
+// table, none of A's entries or payload, no marking, no clear - and everything from the test of B's postings on is the same code.
+template <bool ABM>
 __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
     __shared__ __align__(16) uint32_t lds[4][A2F_WAVE_LDS];
     __shared__ uint32_t wcnt[4];
@@ -637,7 +669,60 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
     const uint32_t nvB = work ? b1 - b0 : 0u;
     const bool rvB = row < nvB;
 
-    if (work) {
+    if (ABM && work) {
+        EB = a2_ent_load(LB, b0, row);
+        const uint32_t b_last = a2_uni(*LB.last_doc);
+        lo = a2_uni(EB.x);                                                      // (row 0 = block b0)
+        const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)EB.z, (int)(4u * (nvB - 1u)));
+        hi = b1 < LB.nblk ? nf - 1u : b_last;
+        II2_STAMP(0)          // prologue: B's entries
+        uint32_t wlo = lo & ~31u;
+        bool first_window = true;
+        A2Bytes X;
+        for (;;) {
+            const uint32_t wspan = hi - wlo < A2_CAPW ? hi - wlo : A2_CAPW - 1u;
+            const uint32_t nw = (wspan >> 5) + 1u;
+            // ---- one round trip: the window's words of A's form (<= 512: eight per lane, coalesced), its tombstone words and -
+            // for the first window - B's payload.  wlo and a_origin are multiples of 32: a window maps onto whole words; B's
+            // docs may start before A's, end after them or miss them altogether: words outside [0, a_nwords) are 0
+            const int32_t aw0 = (int32_t)(wlo >> 5) - (int32_t)(p.a_origin >> 5);
+            const uint32_t tw0 = wlo >> 5;
+            uint32_t aw[8], tw[8];
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; k++) {
+                const uint32_t i = 64u * k + (uint32_t)l;
+                const int32_t ai = aw0 + (int32_t)i;
+                aw[k] = (i < nw && ai >= 0 && (uint32_t)ai < p.a_nwords) ? p.a_bits[ai] : 0u;
+                tw[k] = (p.tomb && i < nw && tw0 + i < p.tomb_nwords) ? p.tomb[tw0 + i] : 0u;
+            }
+            if (first_window) X = a2_fetch(LB.payload, rvB, EB.y, EB.w, rl);
+            II2_STAMP(1)      // requests: A's words, tombstones, B's payload
+            // removed docs are absent from A (no B posting finds them).  The test reads the words [GU/32, GU/32 + nw) only: a live
+            // lane's postings lie in [lo, hi], the others' answers are masked - the guards need no clearing
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; k++)
+                if (64u * k < nw) bmA[A2_GU / 32u + 64u * k + (uint32_t)l] = aw[k] & ~tw[k];
+            II2_STAMP(2)      // A's words into LDS
+            if (first_window) {
+                a2_lane_setup(LN, X, rvB, EB, rl, row);
+                hm_any = LN.hm;
+                if (LN.hm != 0ull) { hs[2 * l] = 0u; hs[2 * l + 1] = 0u; }      // answers of the hard rows are collected in LDS
+            }
+            const bool single = first_window && hi - wlo < A2_CAPW;
+            if (single) H |= a2_test_lane<false>(lds_all, bmbits, LN, wlo, wspan);
+            else H |= a2_test_lane<true>(lds_all, bmbits, LN, wlo, wspan);
+            if (LN.hm != 0ull) a2_test_hard(LB, EB, LN.hm, bmA, hs, wlo, wspan);
+            II2_STAMP(3)      // test B
+            if (hi - wlo < A2_CAPW) break;
+            wlo += A2_CAPW;
+            first_window = false;
+        }
+        if (hm_any != 0ull) {
+            const bool rowhard = ((hm_any >> (4u * row)) & 0xFull) != 0ull;
+            if (rowhard) H = ((unsigned long long)hs[8u * row + 2u * rl + 1u] << 32) | hs[8u * row + 2u * rl];
+        }
+    }
+    if (!ABM && work) {
         // ---- first round trip: B's entries and, beside them, a 128-entry window of A's skip table around the place where a
         // uniform list would have this wave's first doc (B's docs-per-block and A's blocks-per-doc from the host: a guess that
         // the entries themselves confirm or refute)
@@ -944,6 +1029,52 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
 #undef II2_STAMP
 }
 
+// ---- the dense form of a list: its marking, done once ---------------------------------------------------------------
+// A wave takes sixteen blocks of the list; its docs are [first doc of its first block, first doc of the next wave's first block)
+// (the list's last doc for the last wave).  That range is cut into windows of A2_CAPW docs from its first doc & ~31 on (a sparse
+// stretch makes many); per window the sixteen blocks are marked into the wave's LDS bitmap by a2_mark_rows - which takes any
+// block and leaves out what lies outside the window - and the window's non-zero words are OR-ed into the global array.  The
+// first and the last word of a wave's range are shared with its neighbours: every word goes out as a vector atomic (a one-off
+// per list: exactness before speed).
+__global__ __launch_bounds__(256) void k_dense_form_build(ListView LA, uint32_t origin, uint32_t n_words, uint32_t *bits) {
+    __shared__ __align__(16) uint32_t lds[4][A2_NW];
+    const int l = lane_id();
+    const uint32_t wv = a2_uni(threadIdx.x >> 6);
+    const uint32_t rl = (uint32_t)l & 3u, row = (uint32_t)l >> 2;
+    const uint32_t a0 = (blockIdx.x * 4u + wv) * A2_ROWS;
+    if (a0 >= LA.nblk) return;                               // wave-uniform; no barrier below
+    uint32_t *lds_all = &lds[0][0];
+    uint32_t *bm = lds[wv];
+    const uint32_t nv = LA.nblk - a0 < A2_ROWS ? LA.nblk - a0 : A2_ROWS;
+    const bool rv = row < nv;
+    const uint4 E = a2_ent_load(LA, a0, row);
+    const A2Bytes B = a2_fetch(LA.payload, rv, E.y, E.w, rl);
+    const uint32_t lo = a2_uni(E.x);
+    const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)E.z, (int)(4u * (nv - 1u)));
+    const uint32_t hi = a0 + A2_ROWS < LA.nblk ? nf - 1u : a2_uni(*LA.last_doc);
+    uint32_t wlo = lo & ~31u;
+    for (;;) {
+        const uint32_t wspan = hi - wlo < A2_CAPW ? hi - wlo : A2_CAPW - 1u;
+        const uint32_t nw = (wspan >> 5) + 1u;
+        const uint32_t ncl = nw + 2u * (A2_GU / 32u) + 2u;       // <= A2_NW - 2; cleared in 4-word steps
+        for (uint32_t i = 4u * (uint32_t)l; i < ncl; i += 256u) *reinterpret_cast<uint4 *>(&bm[i]) = make_uint4(0, 0, 0, 0);
+        a2_mark_rows(lds_all, bm, LA.payload, rv, E.x, E.y, E.w, B, wlo, wspan, rl, row);
+        const uint32_t g0 = (wlo - origin) >> 5;                // (wlo >= origin: the list's first doc & ~31)
+        for (uint32_t i = (uint32_t)l; i < nw; i += 64u) {
+            const uint32_t wd = bm[A2_GU / 32u + i];
+            if (wd != 0u && g0 + i < n_words) atomicOr(&bits[g0 + i], wd);
+        }
+        if (hi - wlo < A2_CAPW) break;
+        wlo += A2_CAPW;
+    }
+}
+
+hipError_t launch_dense_form_build(const ListView &L, uint32_t origin, uint32_t n_words, uint32_t *bits, hipStream_t s) {
+    const uint32_t waves = (L.nblk + A2_ROWS - 1u) / A2_ROWS;
+    hipLaunchKernelGGL(k_dense_form_build, dim3((waves + 3u) / 4u), dim3(256), 0, s, L, origin, n_words, bits);
+    return hipGetLastError();
+}
+
 // one launch (the look-back records are set) or two kernels
 Path intersect_and2_path(const DenseParams &p) { return p.lb.agg != nullptr ? P_AND_AND2_FUSED : P_AND_AND2_SPLIT; }
 
@@ -951,7 +1082,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
     if (ev0) (void)hipEventRecord(ev0, s);
     const uint32_t grid = (p.n_waves + 3u) / 4u;
     if (intersect_and2_path(p) == P_AND_AND2_FUSED) {
-        hipLaunchKernelGGL(k_and2_fused, dim3(grid), dim3(256), 0, s, p);
+        if (p.a_bits) hipLaunchKernelGGL(k_and2_fused<true>, dim3(grid), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(k_and2_fused<false>, dim3(grid), dim3(256), 0, s, p);
         if (ev1) (void)hipEventRecord(ev1, s);
         return hipGetLastError();
     }

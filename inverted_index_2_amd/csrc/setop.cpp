@@ -269,6 +269,52 @@ static int tiles_setup(ii2_ctx *ctx, IntersectParams &p, uint32_t G, const SetOu
 }
 
 // ---- AND ------------------------------------------------------------------------------------
+// The dense form of l - lists[1] of a one-launch two-list AND, whose docs are sp - into dp (a_bits stays null: the call marks the
+// list as before).  Found in the store's cache, or made now when option intersect.dense_form allows it: 1 = the form's bytes are
+// at most half the list's payload bytes (it must be clearly smaller than what it replaces), 2 = always (tests).  The store's mutex
+// is held from the look-up until the build kernel has FINISHED: a context on another thread that asks for the same list
+// waits here and then reads a complete form, whatever its stream.  An allocation failure is not the query's: no form.
+static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpan &sp, DenseParams &dp) {
+    ii2_seg_store *store = l.seg->store.get();
+    if (!store || !ctx->opt_dense_form || sp.last_doc < sp.first_doc) return II2_OK;
+    hipStream_t st = ctx->stream;
+    std::lock_guard<std::mutex> fg(store->form_mu);
+    const uint64_t key = l.seg->h_blk_off[l.idx];
+    auto it = store->forms.find(key);
+    if (it == store->forms.end()) {
+        ii2_skip e[2];                                      // payload bytes: between the skip entries of the first and the one-past-last block
+        HIP_TRY(ctx, hipMemcpyAsync(&e[0], l.v.skip, sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&e[1], l.v.skip + l.v.nblk, sizeof(ii2_skip), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        ii2_seg_store::DenseForm f;
+        f.origin = sp.first_doc & ~31u;
+        f.n_words = ((sp.last_doc - f.origin) >> 5) + 1u;
+        f.payload_bytes = (uint64_t)(e[1].byte_off - e[0].byte_off);
+        it = store->forms.emplace(key, f).first;
+    }
+    ii2_seg_store::DenseForm &f = it->second;
+    if (!f.d_words) {
+        const uint64_t bytes = (uint64_t)f.n_words * sizeof(uint32_t);
+        if (ctx->opt_dense_form != 2 && 2 * bytes > f.payload_bytes) return II2_OK;
+        uint32_t *w = nullptr;
+        if (dm_alloc((void **)&w, bytes + 16) != hipSuccess) { (void)hipGetLastError(); return II2_OK; }      // (16-byte loads of the last words are legal)
+        hipError_t e = hipMemsetAsync(w, 0, bytes + 16, st);
+        if (e == hipSuccess) e = launch_dense_form_build(l.v, f.origin, f.n_words, w, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            dm_free(w);
+            ctx->err = std::string("dense form: ") + hipGetErrorString(e);
+            return II2_EHIP;
+        }
+        f.d_words = w;
+        store->form_bytes += bytes + 16;
+    }
+    dp.a_bits = f.d_words;
+    dp.a_origin = f.origin;
+    dp.a_nwords = f.n_words;
+    return II2_OK;
+}
+
 // Lists that are dense together (the headline 2-term query): every wave streams through its own run of driver blocks, no
 // partition pass, no workgroup barriers (intersect_dense.hip).  L is sorted by blocks; per_block: docs per driver block.
 static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double per_block, const SetOut &o) {
@@ -299,6 +345,8 @@ static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double pe
         const double spanA = (double)dp.last_doc[1] - (double)dp.first_doc[1] + 1.0;
         dp.a_scale = (float)((double)L[1].v.nblk / spanA);
         dp.b_dpb = (float)per_block;
+        // the longer list as a cached bitmap where it has (or now gets) one: that instance of the kernel marks nothing
+        if (int rcf = dense_form_get(ctx, L[1], ii2_seg::ListSpan{dp.first_doc[1], 0u, dp.last_doc[1]}, dp)) return rcf;
     }
     if (ctx->opt_debug_stamps) {
         if (int rcd = ensure_debug(ctx, true)) return rcd;

@@ -951,6 +951,28 @@ class Segment:
                 "is_view": bool(info.is_view), "spans_mirrored": bool(info.spans_mirrored), "merge_blocks": int(info.merge_blocks),
                 "merge_bytes": int(info.merge_bytes), "n_postings": int(info.n_postings)}
 
+    def dense_form(self, i: int, ctx: Optional["Context"] = None, words: bool = True):
+        """The dense form a two-list AND has cached for list i (ii2_seg_dense_form), or None: a dict of origin, n_words, the
+        words (u32 [n_words]; None with words=False) and store_bytes, the bytes of all forms of this segment's store.  Builds
+        nothing."""
+        c = ctx if ctx is not None and ctx.h else self.ctx
+        info = np.zeros(4, np.uint64)
+        c._ck(c.lib.ii2_seg_dense_form(c.h, self.h, int(i), _ptr(info), None, 0))
+        if not info[0]:
+            return None
+        w = None
+        if words:
+            w = np.zeros(int(info[2]), np.uint32)
+            c._ck(c.lib.ii2_seg_dense_form(c.h, self.h, int(i), _ptr(info), _ptr(w), len(w)))
+        return {"origin": int(info[1]), "n_words": int(info[2]), "words": w, "store_bytes": int(info[3])}
+
+    def dense_form_bytes(self, ctx: Optional["Context"] = None) -> int:
+        """Bytes held by the dense forms of this segment's store."""
+        c = ctx if ctx is not None and ctx.h else self.ctx
+        info = np.zeros(4, np.uint64)
+        c._ck(c.lib.ii2_seg_dense_form(c.h, self.h, 0, _ptr(info), None, 0))
+        return int(info[3])
+
     def free(self) -> None:
         if self.h:
             self.ctx.lib.ii2_seg_free(self.h)      # needs no context: the segment knows its device

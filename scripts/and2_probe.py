@@ -55,6 +55,7 @@ for and2 in (1, 2, 0, 1):
 
 if want_stamps:
     ctx.set_option("intersect.and2", 1)
+    # (with A's dense form - intersect.dense_form=0 turns it off - phase 1 is the requests and phase 2 the form's words into LDS)
     names = {1: ["prologue", "clear+fetch", "mark A", "tomb+test B", "count+publish", "stage", "look-back", "flush"]}
     for mode in (1,):
         ctx.set_option("debug.stamps", mode)
