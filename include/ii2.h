@@ -897,6 +897,11 @@ int ii2_selftest(ii2_ctx *ctx);
  *                                           marking it: 1 (default) for a list whose bitmap is at most half its payload bytes, made by
  *                                           the first such query on the list, which waits for the build once (ii2_intersect_async
  *                                           too); 0 never (no form is made or used); 2 (tests) for any list
+ *   intersect.and2_tiles                    ... with such a bitmap, runs of 16 blocks of the shorter list a wave owns: 1, 2 (half as many
+ *                                           workgroups, each paying its waits - skip entries, loads, look-back - once for two runs), or
+ *                                           0 (default) 2 exactly when the grid at 1 is larger than the device holds at once
+ *   intersect.and2_slots                    ... the workgroups "the device holds at once" of that rule: 0 (default) CUs x the runtime's
+ *                                           occupancy answer for the kernel; N > 0 (tests) N
  *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0);
  *                                           tests: -1 / -2 force a give-up of the one-pass encoder's look-back (see below)
  *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters).

@@ -1117,6 +1117,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "intersect.submax") ctx->opt_intersect_submax = value;
     else if (k == "intersect.and2") ctx->opt_intersect_and2 = value;      // 0: n-list kernel, 1: one launch (look-back), 2: two kernels
     else if (k == "intersect.and2_spin") ctx->opt_and2_spin = value;
+    else if (k == "intersect.and2_tiles") ctx->opt_and2_tiles = value;    // 0: auto (setop.cpp and2_tiles_pick), 1, 2: tiles per wave where the longer list has a dense form
+    else if (k == "intersect.and2_slots") ctx->opt_and2_slots = value;    // auto's "workgroups the device holds at once" (0: asked of the runtime)
     else if (k == "intersect.dense_form") ctx->opt_dense_form = value;    // 0: never, 1: where the form is <= half the list's payload, 2: always (tests)
     else if (k == "encode.stream") ctx->opt_encode_stream = value;        // 1: one-pass encoder behind a merge (default), 0: two-pass, -1: forced fallback (tests)
     else return fail(ctx, II2_EINVAL, "unknown option");

@@ -86,6 +86,9 @@ struct ii2_ctx {
     int64_t opt_dense_bpw = 0;          // driver blocks per wave there (0 = default)
     int64_t opt_encode_stream = 1;      // merged segments are encoded in one pass over the ids (encode_stream.hip)
     int64_t opt_and2_spin = 0;          // bounded waits of its look-back: polls (0 = default; 1 forces the fallback in tests)
+    int64_t opt_and2_tiles = 0;         // tiles a wave of the one-launch two-list AND owns where the longer list has a dense form: 0 auto, 1, 2
+    int64_t opt_and2_slots = 0;         // ... auto: workgroups of the one-tile instance the device holds at once (0 = CUs x the occupancy query; tests inject one)
+    int and2_wgs_per_cu = -1;           // the occupancy query's answer, asked once (-1: not yet)
     unsigned long long *d_lb = nullptr; // look-back records of the fused two-list AND: [0] error word, then agg[], grp[]
     size_t lb_cap = 0;                  // workgroups the records hold
     uint32_t lb_epoch = 0;              // launches so far
@@ -505,6 +508,7 @@ struct DenseParams {
     const uint32_t *a_bits;      // k_and2_fused: lists[1]'s dense form (bit d - a_origin <=> doc d), or null: the list is marked
     uint32_t a_origin;           // a multiple of 32
     uint32_t a_nwords;
+    uint32_t and2_tiles;         // k_and2_fused with a dense form: tiles of sixteen lists[0] blocks a wave owns (2: the grid is half as many workgroups; else 1)
 };
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})
@@ -512,6 +516,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
 // the kernel (sequence) those two launchers run for p: what they switch on and what setop.cpp records
 Path intersect_dense_path(const DenseParams &p);
 Path intersect_and2_path(const DenseParams &p);
+// workgroups of the one-tile dense-form instance of k_and2_fused that a CU holds at once (occupancy query; 0: unknown)
+uint32_t and2_fused_wgs_per_cu();
 // the dense form of list L: bits[0, n_words) (all zero before) get bit d - origin for every doc d of the list
 hipError_t launch_dense_form_build(const ListView &L, uint32_t origin, uint32_t n_words, uint32_t *bits, hipStream_t s);
 

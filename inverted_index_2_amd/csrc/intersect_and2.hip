@@ -274,6 +274,38 @@ __device__ __forceinline__ unsigned long long a2_test_lane(const uint32_t *lds_a
     return (((unsigned long long)hhi << 32) | hlo) & L.valid;
 }
 
+// a2_test_lane<true> as a loop of sixteen rounds of four postings - the lane's words rotate through ww[0] and are back in place at
+// the end.  For a caller short of registers (unrolled, the compiler starts all 64 reads and keeps 64 conditions beside them) on a
+// path it rarely takes: a tile wider than one window
+__device__ __forceinline__ unsigned long long a2_test_lane_rolled(const uint32_t *lds_all, uint32_t bmbits, A2Lane &L, uint32_t wlo, uint32_t wspan) {
+    const uint32_t org = A2_GU + bmbits;
+    uint32_t u = (L.live ? L.base - wlo : 0u) + org;
+    unsigned long long h = 0ull;
+    auto probe = [&](uint32_t j) {
+        const bool in = u - org <= wspan;
+        const uint32_t uu = in ? u : org;
+        const uint32_t wd = lds_all[uu >> 5];
+        const uint32_t hit = in ? __builtin_amdgcn_ubfe(wd, uu, 1u) : 0u;           // (the offset operand is taken mod 32)
+        h |= (unsigned long long)hit << j;
+    };
+    probe(0u);
+#pragma unroll 1
+    for (uint32_t r = 0; r < 16u; r++) {
+        const uint32_t x = L.ww[0];
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++) {
+            if (4u * r + b < 63u) {                                   // (63 gap bytes: the row's last lane has zeroed its 64th)
+                u += (x >> (8u * b)) & 0xFFu;
+                probe(4u * r + b + 1u);
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 15u; k++) L.ww[k] = L.ww[k + 1u];
+        L.ww[15] = x;
+    }
+    return h & L.valid;
+}
+
 // the hard rows of B (multi-byte gaps, a short last block): decoded by the whole wave, every posting inside the window probes the
 // bitmap bm and answers by its index in its block (hs: 256 bits per row)
 __device__ __forceinline__ void a2_test_hard(const ListView &LB, const uint4 &EB, unsigned long long hm, const uint32_t *bm, uint32_t *hs, uint32_t wlo,
@@ -627,6 +659,14 @@ constexpr uint32_t A2F_STAGE_W = (A2_STAGE + 1u) / 2u;            // stage in wo
 constexpr uint32_t A2F_WAVE_LDS = (A2F_STAGE_W > A2_NW ? A2F_STAGE_W : A2_NW) + A2_HS;
 static_assert(A2F_STAGE_W % 4u == 0u, "16-byte alignment of the per-wave LDS regions");
 
+// What every instance does with a tile's answers (below the kernels): H = one bit per posting of the lane, hs = the hard rows'
+// answers by posting index, q0 = the lane's first id's place among the wave's `count` ids, off = the wave's place in the output.
+__device__ __forceinline__ void a2f_stage(uint16_t *st, const uint32_t *hs, const ListView &LB, const uint4 &EB, const A2Lane &LN, unsigned long long H,
+                                          unsigned long long hm_any, uint32_t lo, uint32_t q0);
+__device__ __forceinline__ void a2f_flush(const DenseParams &p, const uint16_t *st, const uint32_t *hs, const ListView &LB, const uint4 &EB, const A2Lane &LN,
+                                          unsigned long long H, unsigned long long hm_any, uint32_t lo, uint32_t q0, uint32_t count, bool wide,
+                                          unsigned long long off);
+
 //
 // ABM: lists[1] has a dense form (p.a_bits: one bit per doc, made once per list and cached with the segment's store).  The
 // window's words of it ARE the bitmap the marking passes would build: the wave copies them into LDS - no probe of A's skip
@@ -881,72 +921,8 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
         if (!lb_group_publish(p.lb, g, total) && l == 0) { wg_err = 1u; lb_fail(p.lb); }
     }
     // ---- stage the ids of my postings whose answer bit is set: 16-bit offsets from the round's first doc, in output order
-    const bool wide = work && hi - lo > 0xFFFFu;             // (a sparse stretch: ids go out one by one, below)
-    if (work && !wide && count != 0u) {
-        const unsigned long long He = LN.live ? H : 0ull;
-        // 64 steps, the same for every lane: the running id advances by the gap byte (SDWA picks it), the answer word is
-        // shifted left by adding it to itself — the bit that falls out is the step's write mask — and the lanes whose bit
-        // was set store the id's 16-bit offset at their place and move on: 3 vector + 1 LDS + 2 scalar instructions a posting
-        // (s_and_saveexec writes SCC: the clobber list says so — the compiler keeps branch conditions there across statements).
-        // (The compiler's form of `if (bit) st[q++] = v` is 7 + 1 + 2.)
-        uint32_t qa = (uint32_t)(uintptr_t)st + 2u * q0;        // (low 32 bits of an LDS pointer = its offset)
-        uint32_t v = LN.base - lo;
-        uint32_t h = __builtin_bitreverse32((uint32_t)He);
-        unsigned long long sx;
-        asm volatile("v_add_co_u32 %1, vcc, %1, %1\n\t"
-                     "s_and_saveexec_b64 %3, vcc\n\t"
-                     "ds_write_b16 %2, %0\n\t"
-                     "v_add_u32 %2, 2, %2\n\t"
-                     "s_mov_b64 exec, %3"
-                     : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : : "vcc", "scc", "memory");
-#define A2_STEP_TXT(SEL)                                                                                               \
-        "v_add_u32_sdwa %0, %0, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" SEL "\n\t"           \
-        "v_add_co_u32 %1, vcc, %1, %1\n\t"                                                                            \
-        "s_and_saveexec_b64 %3, vcc\n\t"                                                                              \
-        "ds_write_b16 %2, %0\n\t"                                                                                     \
-        "v_add_u32 %2, 2, %2\n\t"                                                                                     \
-        "s_mov_b64 exec, %3\n\t"
-#define A2_STAGE_STEP(W, SEL) asm volatile(A2_STEP_TXT(SEL) : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
-#define A2_STAGE_3(W) asm volatile(A2_STEP_TXT("BYTE_0") A2_STEP_TXT("BYTE_1") A2_STEP_TXT("BYTE_2") : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
-#define A2_STAGE_WORD(W) asm volatile(A2_STEP_TXT("BYTE_0") A2_STEP_TXT("BYTE_1") A2_STEP_TXT("BYTE_2") A2_STEP_TXT("BYTE_3") : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
-        A2_STAGE_WORD(LN.ww[0]) A2_STAGE_WORD(LN.ww[1]) A2_STAGE_WORD(LN.ww[2]) A2_STAGE_WORD(LN.ww[3])
-        A2_STAGE_WORD(LN.ww[4]) A2_STAGE_WORD(LN.ww[5]) A2_STAGE_WORD(LN.ww[6])
-        A2_STAGE_3(LN.ww[7])                                                                                        // postings 1..31
-        h = __builtin_bitreverse32((uint32_t)(He >> 32));
-        A2_STAGE_STEP(LN.ww[7], "BYTE_3")
-        A2_STAGE_WORD(LN.ww[8]) A2_STAGE_WORD(LN.ww[9]) A2_STAGE_WORD(LN.ww[10]) A2_STAGE_WORD(LN.ww[11])
-        A2_STAGE_WORD(LN.ww[12]) A2_STAGE_WORD(LN.ww[13]) A2_STAGE_WORD(LN.ww[14])
-        A2_STAGE_3(LN.ww[15])                                                                                       // postings 33..63
-#undef A2_STAGE_WORD
-#undef A2_STAGE_3
-#undef A2_STAGE_STEP
-#undef A2_STEP_TXT
-        if (hm_any != 0ull) {                   // rows with multi-byte gaps: decoded again, every hit ranks itself among its row's answers
-#pragma unroll 1
-            for (uint32_t r = 0; r < A2_ROWS; r++) {
-                if (((hm_any >> (4u * r)) & 0xFull) == 0ull) continue;
-                const uint32_t fq = (uint32_t)__builtin_amdgcn_readlane((int)EB.x, (int)(4u * r)), q0r = (uint32_t)__builtin_amdgcn_readlane((int)EB.y, (int)(4u * r)),
-                               q1r = (uint32_t)__builtin_amdgcn_readlane((int)EB.w, (int)(4u * r));
-                const uint32_t qrow = (uint32_t)__builtin_amdgcn_readlane((int)q0, (int)(4u * r));
-                const uint32_t *hr = hs + 8u * r;
-                auto place = [&](uint32_t ix, uint32_t id) {
-                    if (ix >= 256u) return;
-                    const uint32_t wd = hr[ix >> 5];
-                    if (!((wd >> (ix & 31u)) & 1u)) return;
-                    uint32_t rk = (uint32_t)__popc(wd & ((1u << (ix & 31u)) - 1u));
-                    for (uint32_t j = 0; j < (ix >> 5); j++) rk += (uint32_t)__popc(hr[j]);
-                    st[qrow + rk] = (uint16_t)(id - lo);
-                };
-                decode_block_wave4(GlobalBytes{LB.payload}, q0r, q1r, fq,
-                                   [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
-                                       if (mask & 1u) { place(ix, id0); ix++; }
-                                       if (mask & 2u) { place(ix, id1); ix++; }
-                                       if (mask & 4u) { place(ix, id2); ix++; }
-                                       if (mask & 8u) { place(ix, id3); ix++; }
-                                   });
-            }
-        }
-    }
+    const bool wide = work && hi - lo > 0xFFFFu;             // (a sparse stretch: ids go out one by one, by the flush)
+    if (work && !wide && count != 0u) a2f_stage(st, hs, LB, EB, LN, H, hm_any, lo, q0);
     II2_STAMP(5)              // stage
     // ---- the ids of all workgroups before mine (wave 0)
     if (wv == 0u) {
@@ -968,65 +944,418 @@ __global__ __launch_bounds__(256, 3) void k_and2_fused(DenseParams p) {
         *p.d_count = anyerr ? ~0ull : wg_off + total;
         if (p.lb.spin == LB_SPIN_LATE) lb_late_done(p.lb);
     }
-    if (work && !err && count != 0u) {
-        if (!wide) {
-            const bool fits = off + count <= p.out_cap;
-            for (uint32_t c = 4u * (uint32_t)l; c < count; c += 256u) {        // 16 bytes per lane (wave-private LDS: program order is enough)
-                const uint2 pk = *reinterpret_cast<const uint2 *>(&st[c]);
-                const uint4 ids = make_uint4(lo + (pk.x & 0xFFFFu), lo + (pk.x >> 16), lo + (pk.y & 0xFFFFu), lo + (pk.y >> 16));
-                if (c + 4u <= count && fits) {
-                    uint32_t *dst = p.out + off + c;
-                    __builtin_memcpy(dst, &ids, 16);                // one 16-byte store, any 4-byte alignment
-                } else {
-                    const uint32_t vv[4] = {ids.x, ids.y, ids.z, ids.w};
-                    for (uint32_t k = 0; k < 4u; k++)
-                        if (c + k < count && off + c + k < p.out_cap) p.out[off + c + k] = vv[k];
-                }
-            }
-        } else {
-            const unsigned long long He = LN.live ? H : 0ull;
-            uint32_t q = q0;
-            uint32_t v = LN.base;
-            if ((He & 1ull) && off + q < p.out_cap) p.out[off + q] = v;
-            q += (uint32_t)(He & 1ull);
-#pragma unroll
-            for (uint32_t k = 0; k < 63u; k++) {
-                v += (LN.ww[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
-                const uint32_t hit = (uint32_t)((He >> (k + 1u)) & 1ull);
-                if (hit && off + q < p.out_cap) p.out[off + q] = v;
-                q += hit;
-            }
-            if (hm_any != 0ull) {
-#pragma unroll 1
-                for (uint32_t r = 0; r < A2_ROWS; r++) {
-                    if (((hm_any >> (4u * r)) & 0xFull) == 0ull) continue;
-                    const uint32_t fq = (uint32_t)__builtin_amdgcn_readlane((int)EB.x, (int)(4u * r)), q0r = (uint32_t)__builtin_amdgcn_readlane((int)EB.y, (int)(4u * r)),
-                                   q1r = (uint32_t)__builtin_amdgcn_readlane((int)EB.w, (int)(4u * r));
-                    const uint32_t qrow = (uint32_t)__builtin_amdgcn_readlane((int)q0, (int)(4u * r));
-                    const uint32_t *hr = hs + 8u * r;
-                    auto place = [&](uint32_t ix, uint32_t id) {
-                        if (ix >= 256u) return;
-                        const uint32_t wd = hr[ix >> 5];
-                        if (!((wd >> (ix & 31u)) & 1u)) return;
-                        uint32_t rk = (uint32_t)__popc(wd & ((1u << (ix & 31u)) - 1u));
-                        for (uint32_t j = 0; j < (ix >> 5); j++) rk += (uint32_t)__popc(hr[j]);
-                        if (off + qrow + rk < p.out_cap) p.out[off + qrow + rk] = id;
-                    };
-                    decode_block_wave4(GlobalBytes{LB.payload}, q0r, q1r, fq,
-                                       [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
-                                           if (mask & 1u) { place(ix, id0); ix++; }
-                                           if (mask & 2u) { place(ix, id1); ix++; }
-                                           if (mask & 4u) { place(ix, id2); ix++; }
-                                           if (mask & 8u) { place(ix, id3); ix++; }
-                                       });
-                }
-            }
-        }
-    }
+    if (work && !err && count != 0u) a2f_flush(p, st, hs, LB, EB, LN, H, hm_any, lo, q0, count, wide, off);
     II2_STAMP(7)              // flush
     if (stamps && l == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&p.debug[(uint64_t)(blockIdx.x % 2048u) * 8u + i], tacc[i]);
 #undef II2_STAMP
+}
+
+// ---- the dense-form instance with TWO tiles per wave ------------------------------------------------------------------
+// The life of a wave of k_and2_fused<true> is a chain of waits - B's entries, then A's words and B's payload, then the look-back -
+// around little work, and a grid that the device does not hold at once pays that chain once per round of workgroups.  Here
+// workgroup g owns the blocks [128 g, 128 g + 128) of B; tile s of wave wv is the sixteen blocks from 128 g + 64 s + 16 wv on
+// (output order = doc order: tile 0 of waves 0..3, then tile 1 of waves 0..3), and the chain is paid once for both tiles:
+//   * the skip entries of both come in one round trip, and so does everything else: tile 1's requests go out right behind
+//     tile 0's, and what they bring waits in LDS - the stage area is dead until both tiles are tested - while tile 0 is tested;
+//   * ONE look-back record per workgroup carries the ids of both tiles, published once both are tested (a record per tile would
+//     chain the grid: workgroup g - 1 would publish its tile 1 only after its tile 0 had waited for workgroup g - 2);
+//   * tile 1's place is the workgroup's plus tile 0's ids - no second look-back - and it is staged while tile 0's stores travel.
+// Half the workgroups, each 1.7 times as long (DESIGN.md 4.1a'): launch_intersect_and2 takes this instance when setop.cpp found
+// that the one-tile grid does not fit the device at once (DenseParams::and2_tiles).
+constexpr uint32_t A2F2_WAVE_LDS = A2F_WAVE_LDS + A2_HS;          // a second answer area: tile 0's hard rows answer until they are staged, after tile 1's test
+constexpr uint32_t A2F2_WIN = A2_GU / 32u + A2_CAPW / 32u;        // words of a window of the dense form: the lower guard's place, then <= 512 words (no guard is read)
+constexpr uint32_t A2F2_PARK = 2u * A2F2_WIN;                      // tile 1's payload, 64 bytes a lane, waits behind the two windows
+static_assert(A2F2_WIN % 4u == 0u && A2F2_PARK + 64u * 16u <= A2F2_WAVE_LDS - A2_HS, "two windows and the parked payload end before tile 0's answer area");
+
+// Words [w0, w0 + nw) of a bit array of n_words (>= 1) words, eight per lane (coalesced), in two steps.  a2f_words_request: every
+// lane loads, from an index clamped into the window and into the array - a load under a per-element condition gets a branch of
+// its own, behind which the compiler may wait for everything in flight, and a select kept from before the load costs a register
+// per word for as long as the load travels.  a2f_words_settle, once they have landed: the words outside the array are zero (B's
+// docs may start before A's, end after them or miss them altogether); words past the window are whatever was loaded - nobody
+// reads them.  w0 is made opaque in between (A2F_OPAQUE), so that the second step's conditions are worked out there.
+#define A2F_OPAQUE(x) asm volatile("" : "+s"(x))
+__device__ __forceinline__ void a2f_words_request(const uint32_t *__restrict__ bits, int32_t w0, uint32_t n_words, uint32_t nw, uint32_t (&out)[8]) {
+    const uint32_t l = (uint32_t)lane_id();
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) {
+        const uint32_t i = 64u * k + l;
+        const int32_t wi = w0 + (int32_t)(i < nw ? i : nw - 1u);
+        const uint32_t at = wi < 0 ? 0u : (uint32_t)wi < n_words ? (uint32_t)wi : n_words - 1u;
+        // (a 32-bit byte offset from the uniform base - one address register a load, not two: n_words <= 2^27, one bit per doc id)
+        out[k] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(bits) + 4u * at);
+    }
+}
+__device__ __forceinline__ void a2f_words_settle(int32_t w0, uint32_t n_words, uint32_t (&out)[8]) {
+    const uint32_t l = (uint32_t)lane_id();
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) out[k] = (uint32_t)(w0 + (int32_t)(64u * k + l)) < n_words ? out[k] : 0u;      // (below the array: a huge unsigned index)
+}
+
+// a2_fetch in the same two steps: every lane loads its four 16-byte pieces - a piece past the block's end from the block's first
+// bytes instead, which can always be read (a block ends at or before the payload's end, and segments carry 16 bytes of padding) -
+// and zeroes those pieces afterwards (q1 made opaque in between)
+__device__ __forceinline__ A2Bytes a2f_fetch_request(const uint8_t *payload, bool rv, uint32_t q0, uint32_t q1, uint32_t rl) {
+    const uint32_t len = rv ? q1 - q0 : 0u;
+    A2Bytes B;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        const uint32_t off = 64u * rl + 16u * k;
+        __builtin_memcpy(&B.g[k], payload + (q0 + (len > off ? off : 0u)), 16);      // (a 32-bit offset from the uniform base)
+    }
+    return B;
+}
+__device__ __forceinline__ void a2f_fetch_settle(A2Bytes &B, bool rv, uint32_t q0, uint32_t q1, uint32_t rl) {
+    const uint32_t len = rv ? q1 - q0 : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++)
+        if (!(len > 64u * rl + 16u * k)) B.g[k] = make_uint4(0, 0, 0, 0);
+}
+
+// A's words of a window - the removed docs are out of them already (absent from A: no B posting finds them) - into the wave's LDS
+// window.  The test reads the words [GU/32, GU/32 + nw) only: a live lane's postings lie in [lo, hi], the others' answers are masked
+__device__ __forceinline__ void a2f_window_store(uint32_t *bmA, const uint32_t (&aw)[8], uint32_t nw) {
+    const uint32_t l = (uint32_t)lane_id();
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++)
+        if (64u * k < nw) bmA[A2_GU / 32u + 64u * k + l] = aw[k];
+}
+
+// a tile's postings against A's words, window by window (the first window is in LDS already; windows behind it - a tile wider
+// than A2_CAPW docs - are loaded here, one round trip each): one answer bit per posting of the lane
+__device__ __forceinline__ unsigned long long a2f_probe(const DenseParams &p, const ListView &LB, uint32_t *lds_all, uint32_t *bmA, uint32_t *hs,
+                                                        A2Lane &LN, const uint4 &EB, uint32_t lo, uint32_t hi, uint32_t rl, uint32_t row) {
+    const uint32_t bmbits = (uint32_t)(bmA - lds_all) * 32u;
+    uint32_t wlo = lo & ~31u;
+    unsigned long long H = 0ull;
+    if (hi - wlo < A2_CAPW) {
+        H = a2_test_lane<false>(lds_all, bmbits, LN, wlo, hi - wlo);
+        if (LN.hm != 0ull) a2_test_hard(LB, EB, LN.hm, bmA, hs, wlo, hi - wlo);
+    } else {
+#pragma unroll 1
+        for (;;) {
+            const uint32_t wspan = hi - wlo < A2_CAPW ? hi - wlo : A2_CAPW - 1u;
+            H |= a2_test_lane_rolled(lds_all, bmbits, LN, wlo, wspan);
+            if (LN.hm != 0ull) a2_test_hard(LB, EB, LN.hm, bmA, hs, wlo, wspan);
+            if (hi - wlo < A2_CAPW) break;
+            wlo += A2_CAPW;
+            const uint32_t nw = ((hi - wlo < A2_CAPW ? hi - wlo : A2_CAPW - 1u) >> 5) + 1u;
+            const int32_t wa = (int32_t)(wlo >> 5) - (int32_t)(p.a_origin >> 5), wt = (int32_t)(wlo >> 5);
+            uint32_t aw[8];
+            a2f_words_request(p.a_bits, wa, p.a_nwords, nw, aw);
+            a2f_words_settle(wa, p.a_nwords, aw);
+            if (p.tomb && p.tomb_nwords) {
+                uint32_t tw[8];
+                a2f_words_request(p.tomb, wt, p.tomb_nwords, nw, tw);
+                a2f_words_settle(wt, p.tomb_nwords, tw);
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; k++) aw[k] &= ~tw[k];
+            }
+            a2f_window_store(bmA, aw, nw);
+        }
+    }
+    if (LN.hm != 0ull) {
+        const bool rowhard = ((LN.hm >> (4u * row)) & 0xFull) != 0ull;
+        if (rowhard) H = ((unsigned long long)hs[8u * row + 2u * rl + 1u] << 32) | hs[8u * row + 2u * rl];
+    }
+    return H;
+}
+
+__global__ __launch_bounds__(256, 4) void k_and2_fused_x2(DenseParams p) {
+    __shared__ __align__(16) uint32_t lds[4][A2F2_WAVE_LDS];
+    __shared__ uint32_t wcnt[2][4];
+    __shared__ unsigned long long wg_off;
+    __shared__ uint32_t wg_err;
+    const int l = lane_id();
+    const uint32_t wv = a2_uni(threadIdx.x >> 6);
+    const uint32_t rl = (uint32_t)l & 3u, row = (uint32_t)l >> 2;
+    const uint32_t g = blockIdx.x;
+    uint32_t *lds_all = &lds[0][0];
+    // a wave's LDS: [tile 0's window | tile 1's window | tile 1's parked payload ...) until both tiles are tested, the stage
+    // after that; behind them the hard rows' answers of tile 1 - the parked payload ends in there, and is gone before they are
+    // cleared - and of tile 0
+    uint32_t *bmA = lds[wv], *bmA1 = bmA + A2F2_WIN, *park = bmA + A2F2_PARK;
+    uint32_t *hs1 = bmA + (A2F2_WAVE_LDS - 2u * A2_HS), *hs0 = hs1 + A2_HS;
+    uint16_t *st = reinterpret_cast<uint16_t *>(bmA);
+    const ListView LB = p.lists[0];
+    // tile 0 / tile 1 of this wave: first block, valid rows
+    const uint32_t b0 = (g * 8u + wv) * A2_ROWS, b1 = b0 + 4u * A2_ROWS;
+    const uint32_t nv0 = b0 < LB.nblk ? (LB.nblk - b0 < A2_ROWS ? LB.nblk - b0 : A2_ROWS) : 0u;
+    const uint32_t nv1 = b1 < LB.nblk ? (LB.nblk - b1 < A2_ROWS ? LB.nblk - b1 : A2_ROWS) : 0u;
+    const bool work0 = nv0 != 0u, work1 = nv1 != 0u;         // wave-uniform; tile 1 has work only where tile 0 has
+    const bool rv0 = row < nv0, rv1 = row < nv1;
+    uint32_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+    unsigned long long H0 = 0ull, H1 = 0ull;
+    A2Lane LN0, LN1;
+    uint4 E0 = make_uint4(0, 0, 0, 0), E1 = make_uint4(0, 0, 0, 0);
+    unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long tprev = 0;
+    const bool stamps = p.debug != nullptr;
+#define II2_STAMP(i)                                                    \
+    if (stamps) {                                                       \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              \
+        const unsigned long long tn_ = __builtin_amdgcn_s_memtime();    \
+        tacc[i] += tn_ - tprev;                                         \
+        tprev = tn_;                                                    \
+    }
+    if (stamps) tprev = __builtin_amdgcn_s_memtime();
+    if (threadIdx.x == 0) wg_err = 0u;
+
+    if (work0) {
+        // ---- one round trip: the skip entries of both tiles (they depend on the wave's number only; a tile without blocks reads
+        // the list's end entry)
+        E0 = a2_ent_load(LB, b0, row);
+        E1 = a2_ent_load(LB, b1, row);
+        const uint32_t b_last = a2_uni(*LB.last_doc);
+        lo0 = a2_uni(E0.x);                                                     // (row 0 = the tile's first block)
+        hi0 = b0 + A2_ROWS < LB.nblk ? (uint32_t)__builtin_amdgcn_readlane((int)E0.z, (int)(4u * (nv0 - 1u))) - 1u : b_last;
+        if (work1) {
+            lo1 = a2_uni(E1.x);
+            hi1 = b1 + A2_ROWS < LB.nblk ? (uint32_t)__builtin_amdgcn_readlane((int)E1.z, (int)(4u * (nv1 - 1u))) - 1u : b_last;
+        }
+        asm volatile("" : : "v"(E0.y), "v"(E0.w), "v"(E1.y), "v"(E1.w));       // (every entry is waited for here: no such wait is left to fall among the requests)
+        II2_STAMP(0)          // prologue: B's entries, both tiles
+        // ---- one go: the first window's words of A's form and the tombstone words, of tile 0 and of tile 1, then B's payload of
+        // tile 0 and of tile 1 - forty loads a lane, one round trip
+        const bool tombs = p.tomb != nullptr && p.tomb_nwords != 0u;
+        const uint32_t wl0 = lo0 & ~31u, wl1 = lo1 & ~31u;
+        const uint32_t nw0 = ((hi0 - wl0 < A2_CAPW ? hi0 - wl0 : A2_CAPW - 1u) >> 5) + 1u;
+        const uint32_t nw1 = ((hi1 - wl1 < A2_CAPW ? hi1 - wl1 : A2_CAPW - 1u) >> 5) + 1u;
+        int32_t wa0 = (int32_t)(wl0 >> 5) - (int32_t)(p.a_origin >> 5), wa1 = (int32_t)(wl1 >> 5) - (int32_t)(p.a_origin >> 5);
+        int32_t wt0 = (int32_t)(wl0 >> 5), wt1 = (int32_t)(wl1 >> 5);
+        uint32_t aw0[8], aw1[8], tw0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tw1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        a2f_words_request(p.a_bits, wa0, p.a_nwords, nw0, aw0);
+        a2f_words_request(p.a_bits, wa1, p.a_nwords, nw1, aw1);
+        if (tombs) {
+            a2f_words_request(p.tomb, wt0, p.tomb_nwords, nw0, tw0);
+            a2f_words_request(p.tomb, wt1, p.tomb_nwords, nw1, tw1);
+        }
+        A2Bytes X0 = a2f_fetch_request(LB.payload, rv0, E0.y, E0.w, rl);
+        {
+            A2Bytes X1 = a2f_fetch_request(LB.payload, rv1, E1.y, E1.w, rl);
+            II2_STAMP(1)      // requests, both tiles
+            // ---- landed.  Everything of tile 1 goes into LDS at once - its words into a window of its own, its payload behind
+            // that - and waits there, not in twenty-four registers, while tile 0 is tested: the test keeps as many LDS reads in
+            // flight as it has registers for, and four waves a SIMD leave it 128.  (Loads come back in the order they went out,
+            // within a few hundred cycles of each other: waiting for the last of them here costs little.)
+            uint32_t tombs2 = a2_uni(tombs ? 1u : 0u), qe0 = E0.w, qe1 = E1.w;
+            A2F_OPAQUE(wa0); A2F_OPAQUE(wa1); A2F_OPAQUE(wt0); A2F_OPAQUE(wt1); A2F_OPAQUE(tombs2);
+            asm volatile("" : "+v"(qe0), "+v"(qe1));
+            a2f_words_settle(wa0, p.a_nwords, aw0);
+            a2f_words_settle(wa1, p.a_nwords, aw1);
+            if (tombs2) {                                              // (opaque too, and the words: their complement is not taken - and waited for - among the requests)
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; k++) asm volatile("" : "+v"(tw0[k]), "+v"(tw1[k]));
+                a2f_words_settle(wt0, p.tomb_nwords, tw0);
+                a2f_words_settle(wt1, p.tomb_nwords, tw1);
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; k++) { aw0[k] &= ~tw0[k]; aw1[k] &= ~tw1[k]; }
+            }
+            a2f_window_store(bmA, aw0, nw0);
+            a2f_window_store(bmA1, aw1, nw1);
+            a2f_fetch_settle(X0, rv0, E0.y, qe0, rl);
+            a2f_fetch_settle(X1, rv1, E1.y, qe1, rl);
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) *reinterpret_cast<uint4 *>(&park[256u * k + 4u * (uint32_t)l]) = X1.g[k];
+        }
+        a2_lane_setup(LN0, X0, rv0, E0, rl, row);
+        if (LN0.hm != 0ull) { hs0[2 * l] = 0u; hs0[2 * l + 1] = 0u; }           // answers of the hard rows are collected in LDS
+        II2_STAMP(2)          // A's words and tile 1's payload into LDS
+        H0 = a2f_probe(p, LB, lds_all, bmA, hs0, LN0, E0, lo0, hi0, rl, row);
+        II2_STAMP(3)          // test B, tile 0
+        if (work1) {
+            A2Bytes X1;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) X1.g[k] = *reinterpret_cast<const uint4 *>(&park[256u * k + 4u * (uint32_t)l]);
+            a2_lane_setup(LN1, X1, rv1, E1, rl, row);
+            if (LN1.hm != 0ull) { hs1[2 * l] = 0u; hs1[2 * l + 1] = 0u; }       // (over the end of the parked payload, which is in registers by now)
+            II2_STAMP(2)      // tile 1's payload out of LDS
+            H1 = a2f_probe(p, LB, lds_all, bmA1, hs1, LN1, E1, lo1, hi1, rl, row);
+            II2_STAMP(3)      // test B, tile 1
+        }
+    }
+    // ---- the ids of both tiles; one record for the workgroup
+    const uint32_t pc0 = (uint32_t)__popcll(H0), pc1 = (uint32_t)__popcll(H1);
+    const uint32_t in0 = wave_incl_scan(pc0), in1 = wave_incl_scan(pc1);
+    const uint32_t count0 = wave_bcast(in0, 63), count1 = wave_bcast(in1, 63);
+    const uint32_t q0 = in0 - pc0, q1 = in1 - pc1;          // my first id's place among the wave's ids of the tile
+    if (l == 0) { wcnt[0][wv] = count0; wcnt[1][wv] = count1; }
+    lds_barrier();
+    uint32_t total0 = 0, total1 = 0, before0 = 0, before1 = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < 4u; v++) {
+        const uint32_t c0 = wcnt[0][v], c1 = wcnt[1][v];
+        before0 += v < wv ? c0 : 0u; before1 += v < wv ? c1 : 0u;
+        total0 += c0; total1 += c1;
+    }
+    const uint32_t total = total0 + total1;
+    if (threadIdx.x == 0) lb_publish(p.lb, g, total);
+    II2_STAMP(4)              // count, barrier, publish
+    if (wv == 1u && lb_is_leader(g, gridDim.x)) {            // the group's ids, as soon as its other members have published theirs
+        if (!lb_group_publish(p.lb, g, total) && l == 0) { wg_err = 1u; lb_fail(p.lb); }
+    }
+    const bool wide0 = work0 && hi0 - lo0 > 0xFFFFu, wide1 = work1 && hi1 - lo1 > 0xFFFFu;
+    if (work0 && !wide0 && count0 != 0u) a2f_stage(st, hs0, LB, E0, LN0, H0, LN0.hm, lo0, q0);
+    II2_STAMP(5)              // stage, tile 0
+    // ---- the ids of all workgroups before mine (wave 0)
+    if (wv == 0u) {
+        unsigned long long pre = 0ull;
+        const bool ok = lb_prefix(p.lb, g, gridDim.x, total, &pre);
+        bool late = false;                  // (tests: a give-up after the last workgroup has stored the count - lookback.h)
+        if (p.lb.spin == LB_SPIN_LATE && ok && total != 0u && lb_late_pick(g, gridDim.x)) late = lb_late_wait(p.lb);
+        if (l == 0) {
+            wg_off = ok ? pre : 0ull;
+            if (!ok || late) { wg_err = 1u; lb_fail(p.lb); }
+        }
+    }
+    II2_STAMP(6)              // look-back
+    lds_barrier();
+    const bool err = wg_err != 0u;
+    if (g == gridDim.x - 1u && threadIdx.x == 0) {          // the last workgroup: the total, or all ones when some workgroup gave up
+        const bool anyerr = err || lb_failed(p.lb);
+        *p.d_count = anyerr ? ~0ull : wg_off + total;
+        if (p.lb.spin == LB_SPIN_LATE) lb_late_done(p.lb);
+    }
+    // ---- tile 0 out; tile 1 into the same stage while those stores travel (wave-private LDS: program order is enough), and out
+    if (work0 && !err && count0 != 0u) a2f_flush(p, st, hs0, LB, E0, LN0, H0, LN0.hm, lo0, q0, count0, wide0, wg_off + before0);
+    II2_STAMP(7)              // flush, tile 0
+    if (work1 && !err && count1 != 0u) {
+        if (!wide1) a2f_stage(st, hs1, LB, E1, LN1, H1, LN1.hm, lo1, q1);
+        II2_STAMP(5)          // stage, tile 1
+        a2f_flush(p, st, hs1, LB, E1, LN1, H1, LN1.hm, lo1, q1, count1, wide1, wg_off + total0 + before1);
+        II2_STAMP(7)          // flush, tile 1
+    }
+    if (stamps && l == 0)
+        for (int i = 0; i < 8; i++) atomicAdd(&p.debug[(uint64_t)(blockIdx.x % 2048u) * 8u + i], tacc[i]);
+#undef II2_STAMP
+}
+
+// the ids of a tile's postings whose answer bit is set, into the wave's stage: 16-bit offsets from the tile's first doc, in output order
+__device__ __forceinline__ void a2f_stage(uint16_t *st, const uint32_t *hs, const ListView &LB, const uint4 &EB, const A2Lane &LN, unsigned long long H,
+                                          unsigned long long hm_any, uint32_t lo, uint32_t q0) {
+    const unsigned long long He = LN.live ? H : 0ull;
+    // 64 steps, the same for every lane: the running id advances by the gap byte (SDWA picks it), the answer word is
+    // shifted left by adding it to itself — the bit that falls out is the step's write mask — and the lanes whose bit
+    // was set store the id's 16-bit offset at their place and move on: 3 vector + 1 LDS + 2 scalar instructions a posting
+    // (s_and_saveexec writes SCC: the clobber list says so — the compiler keeps branch conditions there across statements).
+    // (The compiler's form of `if (bit) st[q++] = v` is 7 + 1 + 2.)
+    uint32_t qa = (uint32_t)(uintptr_t)st + 2u * q0;        // (low 32 bits of an LDS pointer = its offset)
+    uint32_t v = LN.base - lo;
+    uint32_t h = __builtin_bitreverse32((uint32_t)He);
+    unsigned long long sx;
+    asm volatile("v_add_co_u32 %1, vcc, %1, %1\n\t"
+                 "s_and_saveexec_b64 %3, vcc\n\t"
+                 "ds_write_b16 %2, %0\n\t"
+                 "v_add_u32 %2, 2, %2\n\t"
+                 "s_mov_b64 exec, %3"
+                 : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : : "vcc", "scc", "memory");
+#define A2_STEP_TXT(SEL)                                                                                               \
+    "v_add_u32_sdwa %0, %0, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" SEL "\n\t"           \
+    "v_add_co_u32 %1, vcc, %1, %1\n\t"                                                                            \
+    "s_and_saveexec_b64 %3, vcc\n\t"                                                                              \
+    "ds_write_b16 %2, %0\n\t"                                                                                     \
+    "v_add_u32 %2, 2, %2\n\t"                                                                                     \
+    "s_mov_b64 exec, %3\n\t"
+#define A2_STAGE_STEP(W, SEL) asm volatile(A2_STEP_TXT(SEL) : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
+#define A2_STAGE_3(W) asm volatile(A2_STEP_TXT("BYTE_0") A2_STEP_TXT("BYTE_1") A2_STEP_TXT("BYTE_2") : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
+#define A2_STAGE_WORD(W) asm volatile(A2_STEP_TXT("BYTE_0") A2_STEP_TXT("BYTE_1") A2_STEP_TXT("BYTE_2") A2_STEP_TXT("BYTE_3") : "+v"(v), "+v"(h), "+v"(qa), "=&s"(sx) : "v"(W) : "vcc", "scc", "memory");
+    A2_STAGE_WORD(LN.ww[0]) A2_STAGE_WORD(LN.ww[1]) A2_STAGE_WORD(LN.ww[2]) A2_STAGE_WORD(LN.ww[3])
+    A2_STAGE_WORD(LN.ww[4]) A2_STAGE_WORD(LN.ww[5]) A2_STAGE_WORD(LN.ww[6])
+    A2_STAGE_3(LN.ww[7])                                                                                        // postings 1..31
+    h = __builtin_bitreverse32((uint32_t)(He >> 32));
+    A2_STAGE_STEP(LN.ww[7], "BYTE_3")
+    A2_STAGE_WORD(LN.ww[8]) A2_STAGE_WORD(LN.ww[9]) A2_STAGE_WORD(LN.ww[10]) A2_STAGE_WORD(LN.ww[11])
+    A2_STAGE_WORD(LN.ww[12]) A2_STAGE_WORD(LN.ww[13]) A2_STAGE_WORD(LN.ww[14])
+    A2_STAGE_3(LN.ww[15])                                                                                       // postings 33..63
+#undef A2_STAGE_WORD
+#undef A2_STAGE_3
+#undef A2_STAGE_STEP
+#undef A2_STEP_TXT
+    if (hm_any != 0ull) {                   // rows with multi-byte gaps: decoded again, every hit ranks itself among its row's answers
+#pragma unroll 1
+        for (uint32_t r = 0; r < A2_ROWS; r++) {
+            if (((hm_any >> (4u * r)) & 0xFull) == 0ull) continue;
+            const uint32_t fq = (uint32_t)__builtin_amdgcn_readlane((int)EB.x, (int)(4u * r)), q0r = (uint32_t)__builtin_amdgcn_readlane((int)EB.y, (int)(4u * r)),
+                           q1r = (uint32_t)__builtin_amdgcn_readlane((int)EB.w, (int)(4u * r));
+            const uint32_t qrow = (uint32_t)__builtin_amdgcn_readlane((int)q0, (int)(4u * r));
+            const uint32_t *hr = hs + 8u * r;
+            auto place = [&](uint32_t ix, uint32_t id) {
+                if (ix >= 256u) return;
+                const uint32_t wd = hr[ix >> 5];
+                if (!((wd >> (ix & 31u)) & 1u)) return;
+                uint32_t rk = (uint32_t)__popc(wd & ((1u << (ix & 31u)) - 1u));
+                for (uint32_t j = 0; j < (ix >> 5); j++) rk += (uint32_t)__popc(hr[j]);
+                st[qrow + rk] = (uint16_t)(id - lo);
+            };
+            decode_block_wave4(GlobalBytes{LB.payload}, q0r, q1r, fq,
+                               [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
+                                   if (mask & 1u) { place(ix, id0); ix++; }
+                                   if (mask & 2u) { place(ix, id1); ix++; }
+                                   if (mask & 4u) { place(ix, id2); ix++; }
+                                   if (mask & 8u) { place(ix, id3); ix++; }
+                               });
+        }
+    }
+}
+
+// a tile's staged ids out to their place (16 bytes per lane); a tile wider than 64 k docs has none staged: its ids go out one by one
+__device__ __forceinline__ void a2f_flush(const DenseParams &p, const uint16_t *st, const uint32_t *hs, const ListView &LB, const uint4 &EB, const A2Lane &LN,
+                                          unsigned long long H, unsigned long long hm_any, uint32_t lo, uint32_t q0, uint32_t count, bool wide,
+                                          unsigned long long off) {
+    const int l = lane_id();
+    if (!wide) {
+        const bool fits = off + count <= p.out_cap;
+        for (uint32_t c = 4u * (uint32_t)l; c < count; c += 256u) {        // 16 bytes per lane (wave-private LDS: program order is enough)
+            const uint2 pk = *reinterpret_cast<const uint2 *>(&st[c]);
+            const uint4 ids = make_uint4(lo + (pk.x & 0xFFFFu), lo + (pk.x >> 16), lo + (pk.y & 0xFFFFu), lo + (pk.y >> 16));
+            if (c + 4u <= count && fits) {
+                uint32_t *dst = p.out + off + c;
+                __builtin_memcpy(dst, &ids, 16);                // one 16-byte store, any 4-byte alignment
+            } else {
+                const uint32_t vv[4] = {ids.x, ids.y, ids.z, ids.w};
+                for (uint32_t k = 0; k < 4u; k++)
+                    if (c + k < count && off + c + k < p.out_cap) p.out[off + c + k] = vv[k];
+            }
+        }
+    } else {
+        const unsigned long long He = LN.live ? H : 0ull;
+        uint32_t q = q0;
+        uint32_t v = LN.base;
+        if ((He & 1ull) && off + q < p.out_cap) p.out[off + q] = v;
+        q += (uint32_t)(He & 1ull);
+#pragma unroll
+        for (uint32_t k = 0; k < 63u; k++) {
+            v += (LN.ww[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
+            const uint32_t hit = (uint32_t)((He >> (k + 1u)) & 1ull);
+            if (hit && off + q < p.out_cap) p.out[off + q] = v;
+            q += hit;
+        }
+        if (hm_any != 0ull) {
+#pragma unroll 1
+            for (uint32_t r = 0; r < A2_ROWS; r++) {
+                if (((hm_any >> (4u * r)) & 0xFull) == 0ull) continue;
+                const uint32_t fq = (uint32_t)__builtin_amdgcn_readlane((int)EB.x, (int)(4u * r)), q0r = (uint32_t)__builtin_amdgcn_readlane((int)EB.y, (int)(4u * r)),
+                               q1r = (uint32_t)__builtin_amdgcn_readlane((int)EB.w, (int)(4u * r));
+                const uint32_t qrow = (uint32_t)__builtin_amdgcn_readlane((int)q0, (int)(4u * r));
+                const uint32_t *hr = hs + 8u * r;
+                auto place = [&](uint32_t ix, uint32_t id) {
+                    if (ix >= 256u) return;
+                    const uint32_t wd = hr[ix >> 5];
+                    if (!((wd >> (ix & 31u)) & 1u)) return;
+                    uint32_t rk = (uint32_t)__popc(wd & ((1u << (ix & 31u)) - 1u));
+                    for (uint32_t j = 0; j < (ix >> 5); j++) rk += (uint32_t)__popc(hr[j]);
+                    if (off + qrow + rk < p.out_cap) p.out[off + qrow + rk] = id;
+                };
+                decode_block_wave4(GlobalBytes{LB.payload}, q0r, q1r, fq,
+                                   [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
+                                       if (mask & 1u) { place(ix, id0); ix++; }
+                                       if (mask & 2u) { place(ix, id1); ix++; }
+                                       if (mask & 4u) { place(ix, id2); ix++; }
+                                       if (mask & 8u) { place(ix, id3); ix++; }
+                                   });
+            }
+        }
+    }
 }
 
 // ---- the dense form of a list: its marking, done once ---------------------------------------------------------------
@@ -1075,6 +1404,16 @@ hipError_t launch_dense_form_build(const ListView &L, uint32_t origin, uint32_t 
     return hipGetLastError();
 }
 
+// workgroups of the one-tile dense-form instance that a CU holds at once, by the occupancy query (0: the query failed)
+uint32_t and2_fused_wgs_per_cu() {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_and2_fused<true>, 256, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0u;
+    }
+    return n > 0 ? (uint32_t)n : 0u;
+}
+
 // one launch (the look-back records are set) or two kernels
 Path intersect_and2_path(const DenseParams &p) { return p.lb.agg != nullptr ? P_AND_AND2_FUSED : P_AND_AND2_SPLIT; }
 
@@ -1082,7 +1421,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
     if (ev0) (void)hipEventRecord(ev0, s);
     const uint32_t grid = (p.n_waves + 3u) / 4u;
     if (intersect_and2_path(p) == P_AND_AND2_FUSED) {
-        if (p.a_bits) hipLaunchKernelGGL(k_and2_fused<true>, dim3(grid), dim3(256), 0, s, p);
+        if (p.a_bits && p.and2_tiles == 2u) hipLaunchKernelGGL(k_and2_fused_x2, dim3((grid + 1u) / 2u), dim3(256), 0, s, p);
+        else if (p.a_bits) hipLaunchKernelGGL(k_and2_fused<true>, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_and2_fused<false>, dim3(grid), dim3(256), 0, s, p);
         if (ev1) (void)hipEventRecord(ev1, s);
         return hipGetLastError();

@@ -315,6 +315,22 @@ static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpa
     return II2_OK;
 }
 
+// Tiles a wave of the one-launch two-list AND owns when the longer list has a dense form (option intersect.and2_tiles: 1, 2, or
+// 0 = this rule).  A workgroup's life there is a chain of waits that a second tile shares (intersect_and2.hip, k_and2_fused_x2):
+// two tiles a wave halve the grid, each workgroup 1.7 times as long.  That pays when the one-tile grid - wgs
+// workgroups - does not fit the device at once and so runs in rounds; a grid the device holds at once is one round already, and
+// pairing its tiles would only halve the waves that hide each other's waits.  The device holds CUs x (workgroups of the one-tile
+// instance per CU, by the occupancy query); option intersect.and2_slots puts a number in its place (tests).
+static uint32_t and2_tiles_pick(ii2_ctx *ctx, uint32_t wgs) {
+    if (ctx->opt_and2_tiles == 1 || ctx->opt_and2_tiles == 2) return (uint32_t)ctx->opt_and2_tiles;
+    uint64_t slots = ctx->opt_and2_slots > 0 ? (uint64_t)ctx->opt_and2_slots : 0u;
+    if (!slots) {
+        if (ctx->and2_wgs_per_cu < 0) ctx->and2_wgs_per_cu = (int)and2_fused_wgs_per_cu();
+        slots = (uint64_t)ctx->cu_count * (uint64_t)ctx->and2_wgs_per_cu;
+    }
+    return slots != 0u && wgs > slots ? 2u : 1u;
+}
+
 // Lists that are dense together (the headline 2-term query): every wave streams through its own run of driver blocks, no
 // partition pass, no workgroup barriers (intersect_dense.hip).  L is sorted by blocks; per_block: docs per driver block.
 static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double per_block, const SetOut &o) {
@@ -347,6 +363,7 @@ static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double pe
         dp.b_dpb = (float)per_block;
         // the longer list as a cached bitmap where it has (or now gets) one: that instance of the kernel marks nothing
         if (int rcf = dense_form_get(ctx, L[1], ii2_seg::ListSpan{dp.first_doc[1], 0u, dp.last_doc[1]}, dp)) return rcf;
+        dp.and2_tiles = dp.a_bits ? and2_tiles_pick(ctx, dp.n_meta / 4u) : 1u;
     }
     if (ctx->opt_debug_stamps) {
         if (int rcd = ensure_debug(ctx, true)) return rcd;

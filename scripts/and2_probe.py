@@ -55,7 +55,9 @@ for and2 in (1, 2, 0, 1):
 
 if want_stamps:
     ctx.set_option("intersect.and2", 1)
-    # (with A's dense form - intersect.dense_form=0 turns it off - phase 1 is the requests and phase 2 the form's words into LDS)
+    # (with A's dense form - intersect.dense_form=0 turns it off - phase 1 is the requests and phase 2 the form's words into LDS;
+    # at two tiles a wave - intersect.and2_tiles=1 turns that off - a row is a workgroup of half the grid and every phase is the
+    # sum over both tiles: the entries and the requests happen once, the landing, test, stage and flush once per tile)
     names = {1: ["prologue", "clear+fetch", "mark A", "tomb+test B", "count+publish", "stage", "look-back", "flush"]}
     for mode in (1,):
         ctx.set_option("debug.stamps", mode)
