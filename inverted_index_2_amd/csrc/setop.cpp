@@ -618,7 +618,10 @@ static int union_lists(ii2_ctx *ctx, const SetList *L, uint32_t n, uint64_t bloc
     ii2_merge_stats st;
     std::memset(&st, 0, sizeof st);
     took(ctx, P_OR_MERGE);
-    if (int rc = merge_core(ctx, n, views, 1, blocks_ub, blocks_ub * II2_DV1_BLOCK, tomb, nullptr, d_out, cap, &st)) return rc;
+    if (int rc = merge_core(ctx, n, views, 1, blocks_ub, blocks_ub * II2_DV1_BLOCK, tomb, nullptr, d_out, cap, &st)) {
+        if (rc == II2_ECAPACITY) *count = ctx->h_mail[0];      // the size needed, as on the chooser's paths (merge_core has just read it)
+        return rc;
+    }
     *count = st.n_out;
     return II2_OK;
 }

@@ -67,6 +67,55 @@ def call_case(c, case, segs, lay, tomb, want):
     return [got[int(a):int(b)] for a, b in zip(off[:-1], off[1:])], off
 
 
+def case_capacity(case, lay):
+    """The generous capacity call_case gives a case that does not ask for an exact one: 256 ids per block of its lists, and 64."""
+    return 256 * int(sum((l.size + 255) // 256 for s in lay.segments for l in s)) + 64
+
+
+def raw_call_case(c, case, segs, lay, out, cap, tomb=None):
+    """One call of the case straight through the C ABI, with `cap` as the capacity whatever `out` holds: (return code, *count - a
+    batch's out_off[-1] -, out_off).  *count and out_off start at zero, so what comes back is what the library wrote."""
+    import ctypes as C
+
+    from inverted_index_2_amd import _lib
+    from inverted_index_2_amd.engine import pack_andnot, pack_batch, pack_group_batch
+    kind, *args = case.call
+    lib, t = c.lib, (tomb.h if tomb else None)
+    R = lambda rs: [(segs[s], a, b) for s, a, b in lay.ranges(rs)]
+    handles = lambda ss: (C.c_void_p * max(len(ss), 1))(*[s.h for s in ss])
+    u64 = lambda a: a.ctypes.data_as(_lib.u64p)
+    cnt = C.c_uint64(0)
+    if kind in ("intersect", "union"):
+        sa, idx = c._listargs([(segs[s], i) for s, i in lay.pairs(args[0])])
+        fn = lib.ii2_intersect if kind == "intersect" else lib.ii2_union
+        rc = fn(c.h, len(args[0]), sa, idx, t, out.data_ptr(), cap, C.byref(cnt))
+    elif kind == "union_ranges":
+        gf, _, gs, first, end = pack_andnot([R(args[0])], [])
+        rc = lib.ii2_union_ranges(c.h, len(gs), handles(gs), u64(first), u64(end), t, out.data_ptr(), cap, C.byref(cnt))
+    elif kind in ("intersect_ranges", "andnot"):
+        groups, exclude = [R(g) for g in args[0]], [R(g) for g in args[1]] if kind == "andnot" else []
+        gf, gn, gs, first, end = pack_andnot(groups, exclude)
+        if kind == "andnot":
+            rc = lib.ii2_andnot_ranges(c.h, len(gn), u64(gf), gn.ctypes.data_as(_lib.u8p), handles(gs), u64(first), u64(end), t, out.data_ptr(), cap,
+                                       C.byref(cnt))
+        else:
+            rc = lib.ii2_intersect_ranges(c.h, len(gn), u64(gf), handles(gs), u64(first), u64(end), t, out.data_ptr(), cap, C.byref(cnt))
+    elif kind == "batch":
+        op, qf, qs, first, end = pack_batch([(o, R(rs)) for o, rs in args[0]])
+        off = np.zeros(len(args[0]) + 1, np.uint64)
+        rc = lib.ii2_query_batch(c.h, len(args[0]), op.ctypes.data_as(_lib.u8p), u64(qf), handles(qs), u64(first), u64(end), t, out.data_ptr(), cap, u64(off))
+        return rc, int(off[-1]), off
+    elif kind == "gbatch":
+        qf, gf, gn, qs, first, end = pack_group_batch([([R(g) for g in groups], [R(g) for g in exclude]) for groups, exclude in args[0]])
+        off = np.zeros(len(args[0]) + 1, np.uint64)
+        rc = lib.ii2_query_batch_groups(c.h, len(args[0]), u64(qf), u64(gf), gn.ctypes.data_as(_lib.u8p), handles(qs), u64(first), u64(end), t,
+                                        out.data_ptr(), cap, u64(off))
+        return rc, int(off[-1]), off
+    else:
+        raise ValueError(kind)
+    return rc, cnt.value, np.array([0, cnt.value], np.uint64)
+
+
 def run_path_case(ctx, case, layout, defaults):
     """The case's call with its lists laid out as `layout` says: the exact delta of Context.paths() it must show and the plain
     numpy reference bit for bit; defaults: the value every option the case sets goes back to."""
