@@ -913,6 +913,10 @@ int ii2_selftest(ii2_ctx *ctx);
  *   debug.no_chain                          experiments: the kernels that wait between workgroups (one-launch AND, one-pass encoder,
  *                                           direct placement) are NOT ordered per device across contexts (they may
  *                                           then hold each other's slots until their bounded waits run out)
+ *   debug.lb_epoch                          tests: waits for the stream and sets the number of the context's last look-back launch to N
+ *                                           (0 .. 2^24 - 1), nothing else: the next such launch - one-launch AND, one-pass encoder,
+ *                                           ii2_lookback_check - takes N + 1, or, at N = 2^24 - 1, clears the records and starts again at 1.
+ *                                           Set it while no ii2_intersect_async launch waits for its ii2_ctx_sync
  *   debug.stamps, profile.events            see ii2_debug_read / ii2_profile_read below
  * Every combination returns the same results; the tests run the kernels with the alternatives switched on and off. */
 int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value);
@@ -959,6 +963,38 @@ const char *ii2_path_name(uint32_t i);
 int ii2_merge_events(ii2_ctx *ctx, uint64_t *out, uint32_t n);
 /* Name of event i ("batch_redo", "range_overfull", ...), NULL beyond the last id.  Needs no context and no GPU. */
 const char *ii2_merge_event_name(uint32_t i);
+/* A test and diagnostic facility, no part of any query: runs the protocol that orders the output of the one-launch two-list AND
+ * and of the one-pass encoder - a workgroup publishes an amount and asks for the sum of the amounts of the workgroups before it
+ * (see ii2_ctx_counters) - WITHOUT a payload, on this context's own records and launch numbers (epochs), which it shares with
+ * those kernels; the kernel calls the very functions they call.  A logical grid of n_wg workgroups (1 .. II2_LB_CHECK_MAX_WG)
+ * of which g_base .. n_wg - 1 are launched (g_base a multiple of 64, < n_wg); workgroup g publishes amount[g] (amount: n_wg
+ * host words, each and their sum below 2^40; those before g_base are checked and not used) after delay[g] units of waiting (delay: NULL or n_wg host words, each at most
+ * II2_LB_CHECK_MAX_DELAY; a unit is about half a microsecond).  spin = polls a wait may take, 1 .. II2_LB_CHECK_MAX_SPIN.
+ * The records of what is NOT launched - the amounts of workgroups 0 .. g_base - 1, then, for each of the g_base / 64 groups
+ * before, its amount and its inclusive prefix - are written before the launch as the caller says: seed_state[i] (II2_LB_SEED_*)
+ * and seed_value[i] (< 2^40; any value: it need not be the sum it stands for), g_base + 2 * (g_base / 64) host entries each
+ * in that order (NULL when g_base = 0).
+ * Outputs, host arrays, one entry per launched workgroup g - g_base: out_prefix = the amounts before g as the protocol found
+ * them (0 when it gave up); out_state = 0 or II2_LB_GAVE_UP_* bits; out_walk = the windows of 32 group records the workgroup
+ * looked at | (the place 0 .. 31 in the last of them of the prefix record it used, or II2_LB_NO_PREFIX) << 24; out_polls = the
+ * rounds of loads it took.  out_agg [n_wg - g_base] and out_grp [2 x the launched groups] receive the raw records
+ * {epoch : 24 | value : 40} of the launched workgroups and groups as the kernel left them.  out_info[0] = the epoch of this
+ * launch, [1] = the records' error word afterwards (= that epoch exactly when a workgroup gave up), [2] = the workgroups the
+ * records hold now.  A give-up is reported here alone, never by ii2_ctx_sync.
+ * II2_EINVAL for any argument outside the above, before anything is launched, counted or written. */
+#define II2_LB_CHECK_MAX_WG (1u << 24)
+#define II2_LB_CHECK_MAX_SPIN 65536u
+#define II2_LB_CHECK_MAX_DELAY 256u
+#define II2_LB_SEED_MISSING 0u /* all zero */
+#define II2_LB_SEED_READY 1u   /* tagged with this launch's epoch */
+#define II2_LB_SEED_STALE 2u   /* ... with the epoch before it */
+#define II2_LB_SEED_LATER 3u   /* ... with the epoch after it (what a launch before a wrap of the epochs leaves) */
+#define II2_LB_GAVE_UP_PREFIX 1u /* the wait for the amounts before it ran out */
+#define II2_LB_GAVE_UP_GROUP 2u  /* a group's last workgroup: the wait for its group's amounts ran out */
+#define II2_LB_NO_PREFIX 0xFFu
+int ii2_lookback_check(ii2_ctx *ctx, uint32_t n_wg, uint32_t g_base, const uint64_t *amount, uint32_t spin, const uint8_t *seed_state,
+                       const uint64_t *seed_value, const uint16_t *delay, uint64_t *out_prefix, uint32_t *out_state, uint32_t *out_walk,
+                       uint32_t *out_polls, uint64_t *out_agg, uint64_t *out_grp, uint64_t *out_info);
 
 #ifdef __cplusplus
 }

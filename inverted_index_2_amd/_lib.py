@@ -73,6 +73,8 @@ class TopkBatchStats(C.Structure):
 
 II2_TOPK_MAX = 1 << 20
 II2_TOPK_BATCH_EMPTY, II2_TOPK_BATCH_TINY, II2_TOPK_BATCH_SMALL, II2_TOPK_BATCH_SINGLE = range(4)
+II2_LB_SEED_MISSING, II2_LB_SEED_READY, II2_LB_SEED_STALE, II2_LB_SEED_LATER = range(4)
+II2_LB_GAVE_UP_PREFIX, II2_LB_GAVE_UP_GROUP, II2_LB_NO_PREFIX = 1, 2, 0xFF
 II2_ATLEAST_NONE, II2_ATLEAST_SMALL, II2_ATLEAST_COUNT, II2_ATLEAST_AND, II2_ATLEAST_OR = range(5)
 
 vp = C.c_void_p
@@ -173,6 +175,7 @@ PROTOTYPES = {
     "ii2_path_name": (C.c_char_p, [C.c_uint32]),
     "ii2_merge_events": (C.c_int, [vp, u64p, C.c_uint32]),
     "ii2_merge_event_name": (C.c_char_p, [C.c_uint32]),
+    "ii2_lookback_check": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

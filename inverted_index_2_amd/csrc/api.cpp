@@ -994,6 +994,71 @@ int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb) {
 
 extern "C" {
 
+// The protocol alone, on this context's records and epoch (ii2.h; lookback_check.hip): prepared and launched like the kernels
+// that use it, so what it leaves in the records and what they leave is the same state.
+int ii2_lookback_check(ii2_ctx *ctx, uint32_t n_wg, uint32_t g_base, const uint64_t *amount, uint32_t spin, const uint8_t *seed_state,
+                       const uint64_t *seed_value, const uint16_t *delay, uint64_t *out_prefix, uint32_t *out_state, uint32_t *out_walk,
+                       uint32_t *out_polls, uint64_t *out_agg, uint64_t *out_grp, uint64_t *out_info) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    if (n_wg == 0 || n_wg > II2_LB_CHECK_MAX_WG || g_base >= n_wg || g_base % LB_GROUP != 0 || !amount || spin == 0 || spin > II2_LB_CHECK_MAX_SPIN ||
+        !out_prefix || !out_state || !out_walk || !out_polls || !out_agg || !out_grp || !out_info || (g_base && (!seed_state || !seed_value)))
+        return fail(ctx, II2_EINVAL, "ii2_lookback_check: bad argument");
+    const uint32_t n_launched = n_wg - g_base, grp_base = g_base / LB_GROUP, n_grp = (n_wg + LB_GROUP - 1u) / LB_GROUP - grp_base;
+    const size_t n_seed = (size_t)g_base + 2u * grp_base;
+    unsigned long long total = 0;
+    for (uint32_t i = 0; i < n_wg; i++) {
+        if (amount[i] > LB_VALUE_MASK || (total += amount[i]) > LB_VALUE_MASK) return fail(ctx, II2_EINVAL, "ii2_lookback_check: the amounts and their sum are below 2^40");
+        if (delay && delay[i] > II2_LB_CHECK_MAX_DELAY) return fail(ctx, II2_EINVAL, "ii2_lookback_check: a delay is at most II2_LB_CHECK_MAX_DELAY");
+    }
+    for (size_t i = 0; i < n_seed; i++)
+        if (seed_state[i] > II2_LB_SEED_LATER || seed_value[i] > LB_VALUE_MASK) return fail(ctx, II2_EINVAL, "ii2_lookback_check: bad seed");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (int rcw = ii2_ws_reserve(ctx, align_up((size_t)n_wg * sizeof(uint64_t)) + align_up((size_t)n_wg * sizeof(uint16_t)) +
+                                          align_up((size_t)n_launched * sizeof(uint64_t)) + 3 * align_up((size_t)n_launched * sizeof(uint32_t)) + 4096))
+        return rcw;
+    LbCheckParams p;
+    unsigned long long *d_amount = ws_take<unsigned long long>(ctx, n_wg);
+    uint16_t *d_delay = ws_take<uint16_t>(ctx, n_wg);
+    p.n_wg = n_wg; p.g_base = g_base; p.amount = d_amount; p.delay = delay ? d_delay : nullptr;
+    p.prefix = ws_take<unsigned long long>(ctx, n_launched);
+    p.state = ws_take<uint32_t>(ctx, n_launched);
+    p.walk = ws_take<uint32_t>(ctx, n_launched);
+    p.polls = ws_take<uint32_t>(ctx, n_launched);
+    if (int rcn = lb_note_pending(ctx)) return rcn;       // (the give-ups of asynchronous launches before this one stay reported)
+    if (int rcl = ii2_lookback_prepare(ctx, n_wg, &p.lb)) return rcl;
+    ctx->lb_pending = 0;                           // (this call reports its own give-up, below)
+    p.lb.spin = spin;
+    // the records of the workgroups and groups before the launched ones, as the caller wants them found
+    std::vector<unsigned long long> seed(n_seed);
+    for (size_t i = 0; i < n_seed; i++) {
+        const uint32_t tag = seed_state[i] == II2_LB_SEED_READY ? p.lb.epoch : seed_state[i] == II2_LB_SEED_STALE ? p.lb.epoch - 1u : p.lb.epoch + 1u;
+        seed[i] = seed_state[i] == II2_LB_SEED_MISSING ? 0ull : ((unsigned long long)(tag & LB_EPOCH_MAX) << LB_VALUE_BITS) | seed_value[i];
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_amount, amount, (size_t)n_wg * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (delay) HIP_TRY(ctx, hipMemcpyAsync(d_delay, delay, (size_t)n_wg * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    if (g_base) {
+        HIP_TRY(ctx, hipMemcpyAsync(p.lb.agg, seed.data(), (size_t)g_base * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(p.lb.grp, seed.data() + g_base, 2 * (size_t)grp_base * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    if (int rcq = ii2_lookback_launch(ctx, true, [&] { return launch_lb_check(p, st); })) return rcq;
+    uint64_t err_word = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(out_prefix, p.prefix, (size_t)n_launched * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_state, p.state, (size_t)n_launched * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_walk, p.walk, (size_t)n_launched * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_polls, p.polls, (size_t)n_launched * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_agg, p.lb.agg + g_base, (size_t)n_launched * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out_grp, p.lb.grp + 2 * (size_t)grp_base, 2 * (size_t)n_grp * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(&err_word, p.lb.err, sizeof err_word, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    lb_fold_pending(ctx);
+    out_info[0] = p.lb.epoch;
+    out_info[1] = err_word;
+    out_info[2] = ctx->lb_cap;
+    return II2_OK;
+}
+
 int ii2_selftest(ii2_ctx *ctx) {
     if (!ctx) return II2_EINVAL;
     std::lock_guard<std::mutex> g(ctx->mu);
@@ -1089,6 +1154,11 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "debug.stamps") ctx->opt_debug_stamps = value;
     else if (k == "merge.alone") ctx->opt_merge_alone = value;
     else if (k == "debug.no_chain") ctx->opt_debug_no_chain = value;
+    else if (k == "debug.lb_epoch") {       // tests: the number of the last look-back launch (the next one takes value + 1, or wraps)
+        if (value < 0 || value > (int64_t)LB_EPOCH_MAX) return fail(ctx, II2_EINVAL, "debug.lb_epoch: 0 .. 2^24 - 1");
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->lb_epoch = (uint32_t)value;
+    }
     else if (k == "profile.events") ctx->opt_profile_events = value;
     else if (k == "intersect.bitmap") ctx->opt_intersect_bitmap = value;
     else if (k == "union.dense") ctx->opt_union_dense = value;

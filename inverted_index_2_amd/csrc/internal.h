@@ -475,8 +475,28 @@ struct LookBack {
     uint32_t epoch;              // this launch's number, 1 .. 2^24 - 1
     uint32_t spin;               // polls a wait may take (0: default; or one of the two test values below)
 };
+constexpr uint32_t LB_GROUP = 64;                    // workgroups per group record
+constexpr uint32_t LB_VALUE_BITS = 40;
+constexpr unsigned long long LB_VALUE_MASK = (1ull << LB_VALUE_BITS) - 1ull;
+constexpr uint32_t LB_EPOCH_MAX = (1u << (64u - LB_VALUE_BITS)) - 1u;
 constexpr uint32_t LB_SPIN_EARLY = 0xFFFFFFFFu;     // tests: workgroup 1 gives up at once
 constexpr uint32_t LB_SPIN_LATE = 0xFFFFFFFEu;      // tests: one workgroup gives up after the last one has stored the count (lookback.h)
+// the protocol without a payload (lookback_check.hip: ii2_lookback_check).  Arrays indexed by g hold n_wg entries, the outputs one
+// per launched workgroup (g - g_base)
+constexpr uint32_t LB_CHECK_THREADS = 128;
+constexpr uint32_t LB_CHECK_GAVE_UP_PREFIX = II2_LB_GAVE_UP_PREFIX, LB_CHECK_GAVE_UP_GROUP = II2_LB_GAVE_UP_GROUP;      // bits of state[]
+constexpr uint32_t LB_CHECK_NO_PREFIX = II2_LB_NO_PREFIX;      // walk[] >> 24 when no prefix record ended the walk
+struct LbCheckParams {
+    LookBack lb;
+    uint32_t n_wg, g_base;
+    const unsigned long long *amount;   // [n_wg]
+    const uint16_t *delay;              // [n_wg] or nullptr: units of s_sleep(16) before the publish
+    unsigned long long *prefix;         // amounts before the workgroup (0 when its wait ran out)
+    uint32_t *state;                    // 0, or which of its waits ran out
+    uint32_t *walk;                     // windows of group records looked at | place of the prefix record used << 24
+    uint32_t *polls;                    // rounds of loads lb_prefix took
+};
+hipError_t launch_lb_check(const LbCheckParams &p, hipStream_t s);
 
 // dense streaming intersection (intersect_dense.hip)
 constexpr uint32_t DENSE_MAXL = 4;             // lists it takes

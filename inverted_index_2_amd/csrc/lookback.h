@@ -26,11 +26,7 @@
 
 namespace ii2 {
 
-constexpr uint32_t LB_GROUP = 64;
 constexpr uint32_t LB_SPIN = 1u << 21;                       // polls (each >= ~1 us): seconds in all
-constexpr uint32_t LB_VALUE_BITS = 40;
-constexpr unsigned long long LB_VALUE_MASK = (1ull << LB_VALUE_BITS) - 1ull;
-constexpr uint32_t LB_EPOCH_MAX = (1u << (64u - LB_VALUE_BITS)) - 1u;
 
 __device__ __forceinline__ unsigned long long lb_ld(const unsigned long long *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lb_st(unsigned long long *q, unsigned long long v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -76,9 +72,12 @@ __device__ __forceinline__ bool lb_group_publish(const LookBack &lb, uint32_t g,
 // that has been seen ready is not read again, and the groups are looked at 32 at a time (the nearest one that carries a prefix
 // is normally one or two groups back) - the first version read 64 + 2 x 64 records per poll and its polls alone were as much
 // traffic as the payload of k_enc_stream.
+// (diagnostics, lookback_check.hip: *windows counts the windows of group records looked at, *dist receives the place 0 ..
+// LB_WINDOW - 1, within the last of them, of the prefix record that ended the walk - untouched when none did)
 constexpr uint32_t LB_WINDOW = 32;
 __device__ __forceinline__ bool lb_prefix(const LookBack &lb, uint32_t g, uint32_t n_wg, unsigned long long own, unsigned long long *prefix,
-                                          uint32_t *polls = nullptr, uint32_t *polls_members = nullptr) {
+                                          uint32_t *polls = nullptr, uint32_t *polls_members = nullptr, uint32_t *windows = nullptr,
+                                          uint32_t *dist = nullptr) {
     const uint32_t l = (uint32_t)lane_id(), G = g / LB_GROUP, gi = g % LB_GROUP;
     const uint32_t limit = lb_limit(lb);
     if (lb.spin == LB_SPIN_EARLY && g == 1u) return false;
@@ -100,6 +99,7 @@ __device__ __forceinline__ bool lb_prefix(const LookBack &lb, uint32_t g, uint32
         unsigned long long ga = lb_tag(lb), gp = 0ull;
         bool have_ga = !inr, have_gp = false;
         bool next = false;
+        if (windows && !groups_done) ++*windows;      // (diagnostics)
         for (;;) {
             if (polls) ++*polls;                // (diagnostics)
             if (!have_a) a = lb_ld(&lb.agg[(size_t)G * LB_GROUP + l]);
@@ -124,6 +124,7 @@ __device__ __forceinline__ bool lb_prefix(const LookBack &lb, uint32_t g, uint32
                                                       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)gp, (int)d);
                         accg += part + (gl & LB_VALUE_MASK);
                         groups_done = true;
+                        if (dist) *dist = d;    // (diagnostics)
                     }
                 } else if (gav == ~0ull) {      // no prefix among them, but all their amounts: on to the next window
                     accg += lb_wave_sum64(inr ? (ga & LB_VALUE_MASK) : 0ull);

@@ -265,6 +265,37 @@ class Context:
             raise II2Error(-1, "ii2_merge_events: the library knows another number of events than ii2_merge_event_name")
         return {name: int(out[i]) for i, name in enumerate(names)}
 
+    def lookback_check(self, n_wg: int, amount, spin: int, g_base: int = 0, seed_state=None, seed_value=None, delay=None):
+        """The look-back protocol without a payload, on this context's records and epochs (ii2_lookback_check: a test and
+        diagnostic facility).  amount: n_wg words; seed_state / seed_value: g_base + 2 * (g_base // 64) entries, the amounts of
+        the workgroups before g_base and then {amount, inclusive prefix} of each group before it; delay: None or n_wg words.
+        Returns a dict of arrays, one entry per launched workgroup: prefix (u64), state (0 or II2_LB_GAVE_UP_* bits), windows,
+        dist (II2_LB_NO_PREFIX: none), polls; the raw records agg / grp of the launched workgroups and groups; and the words
+        epoch, err (the error word afterwards) and cap (workgroups the records hold)."""
+        n_wg, g_base = int(n_wg), int(g_base)
+        n, n_grp = max(n_wg - g_base, 0), max((n_wg + 63) // 64 - g_base // 64, 0)
+        amount = _np(amount, np.uint64)
+        if amount.size != n_wg:
+            raise ValueError("one amount per workgroup of the logical grid")
+        n_seed = g_base + 2 * (g_base // 64)
+        if g_base:
+            seed_state, seed_value = _np(seed_state, np.uint8), _np(seed_value, np.uint64)
+            if seed_state.size != n_seed or seed_value.size != n_seed:
+                raise ValueError("g_base + 2 * (g_base // 64) seeds")
+        else:
+            seed_state = seed_value = None
+        if delay is not None:
+            delay = _np(delay, np.uint16)
+            if delay.size != n_wg:
+                raise ValueError("one delay per workgroup of the logical grid")
+        prefix, agg, grp = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(2 * n_grp, np.uint64)
+        state, walk, polls = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        info = np.zeros(4, np.uint64)
+        self._ck(self.lib.ii2_lookback_check(self.h, n_wg, g_base, _ptr(amount), int(spin), _ptr(seed_state), _ptr(seed_value), _ptr(delay),
+                                             _ptr(prefix), _ptr(state), _ptr(walk), _ptr(polls), _ptr(agg), _ptr(grp), _ptr(info)))
+        return dict(prefix=prefix, state=state, windows=walk & 0xFFFFFF, dist=walk >> 24, polls=polls, agg=agg, grp=grp,
+                    epoch=int(info[0]), err=int(info[1]), cap=int(info[2]))
+
     def profile_read(self):
         """(total device ms, launches) of the dominant kernel since the last read (option profile.events)."""
         ms, n = C.c_double(), C.c_uint64()
