@@ -348,6 +348,80 @@ func (c *Ctx) DictFind(dicts []*Dictionary, probes [][]byte, prefix []uint8) (fi
 	return first[:len(probes)*len(dicts)], end[:len(probes)*len(dicts)], uint64(n), nil
 }
 
+// Kinds of DictMatch (II2_MATCH_*); MatchNoCase is OR-ed into a kind: ASCII A-Z and a-z compare equal, no other byte folds.
+const (
+	MatchContains uint8 = 0
+	MatchSuffix   uint8 = 1
+	MatchGlob     uint8 = 2
+	MatchNoCase   uint8 = 0x80
+)
+
+// MatchStats mirrors ii2_match_stats.
+type MatchStats struct {
+	Terms, Matched, Runs uint64
+	Staged, Global       uint32
+}
+
+// DictMatch is the substring, suffix and wildcard term search in k resident dictionaries (ii2_dict_match): what neither DictFind
+// nor the FST can answer, because both walk a term from its front.  At most 64 patterns of at most 64 bytes per call (callers
+// chunk); kinds[p] is MatchContains / MatchSuffix / MatchGlob (`*`, `?`, `\x`; the whole term), optionally | MatchNoCase.  Pair
+// (p, s) - pattern p in dicts[s] - owns the runs runOff[p*k+s] .. runOff[p*k+s+1]-1; run j is the terms [first[j], end[j]) of
+// dictionary dict[j].  The runs of pattern p, runOff[p*k] .. runOff[(p+1)*k]-1, are one group of the range calls, with
+// segs[j] the segment of dicts[dict[j]].  A result above the first buffer of 4096 runs takes the second call the library asks
+// for, with the exact size.
+func (c *Ctx) DictMatch(dicts []*Dictionary, patterns [][]byte, kinds []uint8) (runOff, first, end []uint64, dict []uint32, st MatchStats, err error) {
+	if len(dicts) == 0 {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict match: no dictionaries")
+	}
+	if len(kinds) != len(patterns) {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict match: one kind per pattern")
+	}
+	hs := make([]*C.ii2_dict, len(dicts))
+	for i, d := range dicts {
+		hs[i] = d.h
+	}
+	off := make([]uint64, len(patterns)+1)
+	var blob []byte
+	for i, p := range patterns {
+		blob = append(blob, p...)
+		off[i+1] = uint64(len(blob))
+	}
+	blob = append(blob, 0) // never an empty array
+	kd := append([]uint8{}, kinds...)
+	kd = append(kd, 0)
+	runOff = make([]uint64, len(patterns)*len(dicts)+1)
+	capRuns := uint64(4096)
+	var cs C.ii2_match_stats
+	for attempt := 0; ; attempt++ {
+		first, end, dict = make([]uint64, capRuns+1), make([]uint64, capRuns+1), make([]uint32, capRuns+1)
+		rc := C.ii2_dict_match(c.h, C.uint32_t(len(hs)), (**C.ii2_dict)(unsafe.Pointer(&hs[0])), C.uint32_t(len(patterns)),
+			(*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off), (*C.uint8_t)(unsafe.Pointer(&kd[0])), u64ptr(runOff), u64ptr(first), u64ptr(end),
+			(*C.uint32_t)(unsafe.Pointer(&dict[0])), C.uint64_t(capRuns), &cs)
+		if rc == C.II2_ECAPACITY && attempt == 0 {
+			capRuns = runOff[len(runOff)-1]
+			continue
+		}
+		if rc != 0 {
+			return nil, nil, nil, nil, st, c.err("dict match", rc)
+		}
+		break
+	}
+	n := runOff[len(runOff)-1]
+	st = MatchStats{uint64(cs.n_terms), uint64(cs.n_matched), uint64(cs.n_runs), uint32(cs.n_staged), uint32(cs.n_global)}
+	return runOff, first[:n], end[:n], dict[:n], st, nil
+}
+
+// TermMatch is one pattern against one term by the functions DictMatch's kernel runs (ii2_term_match); needs no GPU.
+func TermMatch(kind uint8, pattern, term []byte) (bool, error) {
+	p, t := append(append([]byte{}, pattern...), 0), append(append([]byte{}, term...), 0)
+	var m C.int
+	if rc := C.ii2_term_match(C.uint32_t(kind), (*C.uint8_t)(unsafe.Pointer(&p[0])), C.uint64_t(len(pattern)), (*C.uint8_t)(unsafe.Pointer(&t[0])),
+		C.uint64_t(len(term)), &m); rc != 0 {
+		return false, fmt.Errorf("term match: error %d", int(rc))
+	}
+	return m != 0, nil
+}
+
 // AlignDicts is AlignTerms on resident dictionaries (ii2_align_dicts): nothing is uploaded, nothing is sorted.
 func (c *Ctx) AlignDicts(dicts []*Dictionary) (*Alignment, error) {
 	hs := make([]*C.ii2_dict, len(dicts))
@@ -526,6 +600,40 @@ func (c *Ctx) QueryBatch(op []uint8, queryFirst []uint64, segs []*Segment, listF
 		return nil, c.err("query batch", rc)
 	}
 	return offsets, nil
+}
+
+// QueryBatchHost is QueryBatch with the results in host memory: a device buffer of firstCap ids, a second call with the size the
+// first one reported when the results did not fit (nothing was written then), one download.  Returns the packed ids and the
+// offsets that delimit the queries' results.
+func (c *Ctx) QueryBatchHost(op []uint8, queryFirst []uint64, segs []*Segment, listFirst, listEnd []uint64, firstCap uint64) ([]uint32, []uint64, error) {
+	capIDs := firstCap
+	for attempt := 0; ; attempt++ {
+		var d unsafe.Pointer
+		if rc := C.ii2_dev_alloc(c.h, C.size_t((capIDs+1)*4), &d); rc != 0 {
+			return nil, nil, c.err("query batch", rc)
+		}
+		offs, err := c.QueryBatch(op, queryFirst, segs, listFirst, listEnd, d, capIDs+1)
+		if err == ErrCapacity && attempt == 0 {
+			C.ii2_dev_free(c.h, d)
+			capIDs = offs[len(offs)-1]
+			continue
+		}
+		if err != nil {
+			C.ii2_dev_free(c.h, d)
+			return nil, nil, err
+		}
+		n := offs[len(offs)-1]
+		ids := make([]uint32, n)
+		var rc C.int
+		if n > 0 {
+			rc = C.ii2_copy_d2h(c.h, unsafe.Pointer(&ids[0]), d, C.size_t(n*4))
+		}
+		C.ii2_dev_free(c.h, d)
+		if rc != 0 {
+			return nil, nil, c.err("query batch", rc)
+		}
+		return ids, offs, nil
+	}
 }
 
 // QueryBatchGroups answers MANY AND-of-ORs / NOT queries over resident segments in one call (ii2_query_batch_groups): QueryBatch

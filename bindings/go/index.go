@@ -316,6 +316,89 @@ type ResidentIndex interface {
 	Release()
 }
 
+// MatchIndex is what a host that keeps its segments and their dictionaries resident provides for MatchSearch: every segment of
+// every shard with its resident dictionary (Ctx.DictCreate once per segment), in any fixed order.  The segments stay read-locked
+// until Release.
+type MatchIndex interface {
+	ResidentSegments() (segs []*Segment, dicts []*Dictionary)
+	Release()
+}
+
+// MatchSearch (additive): substring, suffix and wildcard search - for every pattern of kind (MatchContains / MatchSuffix /
+// MatchGlob, | MatchNoCase) the ids under any term it matches, over every segment of every shard: a pattern selects no shard.
+// Ctx.DictMatch per chunk of at most 64 dictionaries and 64 patterns turns the patterns into runs of lists, then ONE
+// Ctx.QueryBatch call - an OpOr query per pattern over all its runs - and one download, with a second call when the results
+// exceed the first buffer: what the C++ host mirror's InvertedIndex::MatchSearch does (host/host_index.cpp).  A pattern that
+// matches no term has no entry.  Like Read, no tombstone filter.
+func MatchSearch(c *Ctx, ix MatchIndex, patterns [][]byte, kind uint8) (found map[string][]uint32, err error) {
+	defer ix.Release()
+	segs, dicts := ix.ResidentSegments()
+	type ranges struct {
+		segs       []*Segment
+		first, end []uint64
+	}
+	per := make([]ranges, len(patterns))
+	for p0 := 0; p0 < len(patterns); p0 += 64 {
+		p1 := p0 + 64
+		if p1 > len(patterns) {
+			p1 = len(patterns)
+		}
+		kinds := make([]uint8, p1-p0)
+		for i := range kinds {
+			kinds[i] = kind
+		}
+		for s0 := 0; s0 < len(dicts); s0 += 64 {
+			s1 := s0 + 64
+			if s1 > len(dicts) {
+				s1 = len(dicts)
+			}
+			k := s1 - s0
+			runOff, first, end, dict, _, err := c.DictMatch(dicts[s0:s1], patterns[p0:p1], kinds)
+			if err != nil {
+				return nil, fmt.Errorf("match search: %w", err)
+			}
+			for p := 0; p < p1-p0; p++ {
+				r := &per[p0+p]
+				for j := runOff[p*k]; j < runOff[(p+1)*k]; j++ {
+					r.segs = append(r.segs, segs[s0+int(dict[j])])
+					r.first = append(r.first, first[j])
+					r.end = append(r.end, end[j])
+				}
+			}
+		}
+	}
+	var names []string
+	var op []uint8
+	queryFirst := []uint64{0}
+	var qsegs []*Segment
+	var qfirst, qend []uint64
+	seen := map[string]bool{}
+	for p, r := range per {
+		if len(r.segs) == 0 || seen[string(patterns[p])] {
+			continue
+		}
+		seen[string(patterns[p])] = true
+		names = append(names, string(patterns[p]))
+		op = append(op, OpOr)
+		qsegs = append(qsegs, r.segs...)
+		qfirst = append(qfirst, r.first...)
+		qend = append(qend, r.end...)
+		queryFirst = append(queryFirst, uint64(len(qsegs)))
+	}
+	found = map[string][]uint32{}
+	if len(names) == 0 {
+		return found, nil
+	}
+	all, offs, err := c.QueryBatchHost(op, queryFirst, qsegs, qfirst, qend, uint64(1)<<22)
+	if err != nil {
+		return nil, fmt.Errorf("match search: %w", err)
+	}
+	for q, name := range names {
+		found[name] = all[offs[q]:offs[q+1]]
+	}
+	return found, nil
+}
+
 // IntersectAtLeast (additive): the ids under at least minMatch of terms and under none of except - minimum-should-match, "any two
 // of these tags".  One group per term as IntersectExcept builds them, but a required term found in no segment is a group without
 // ranges (it matches no doc), not an empty result; ONE Ctx.AtLeastRanges call with one download - what the C++ host mirror's

@@ -199,6 +199,50 @@ int ii2_dict_find(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint64
  * term_off not ascending from 0, prefix other than 0 / 1.  II2_ERANGE: 2^31 or more terms. */
 int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_t n_terms, const uint8_t *probe, uint64_t probe_len,
                     int prefix, uint64_t *first, uint64_t *end);
+/* Substring, suffix and wildcard term search in k resident dictionaries: the terms a pattern selects, as list ranges for the
+ * range entry points - what neither ii2_dict_find nor the reference's FST can answer, because both walk a term from the front.
+ * The dictionaries are scanned whole, at memory speed; all arrays are host memory.
+ * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) of kind pat_kind[p], one of II2_MATCH_CONTAINS / SUFFIX / GLOB, optionally
+ * OR-ed with II2_MATCH_NOCASE (ASCII A-Z and a-z compare equal; no other byte folds).  Everything compares bytes (no UTF-8):
+ *   CONTAINS  the pattern is literal and matches a term that holds it anywhere; the empty pattern matches every term;
+ *   SUFFIX    the pattern is literal and matches a term that ends with it; the empty pattern matches every term;
+ *   GLOB      matches the WHOLE term: `*` any run of bytes (the empty one included), `?` exactly one byte, `\x` the byte x
+ *             literally; no bracket classes; a lone `\` at the end is II2_EINVAL; the empty pattern matches only the empty term.
+ * Pair (p, s) - pattern p in dicts[s] - is entry p * k + s, ii2_dict_find's layout.  Its answer is the maximal runs of
+ * consecutive matching term indices, ascending: run j of the call is [run_first[j], run_end[j]) in dictionary run_dict[j], and
+ * pair (p, s) owns the runs run_off[p * k + s] .. run_off[p * k + s + 1] - 1.  So pattern p is ONE group of the range entry
+ * points: group_first[p] = run_off[p * k], segs[j] = the segment of dictionary run_dict[j], list_first / list_end = run_first /
+ * run_end (plus first_list where a dictionary names lists from there on).  An empty dictionary gives no run.
+ * Every check runs before anything is launched or written: II2_EINVAL for a NULL array with n_patterns > 0 (run_dict and stats
+ * excepted; the three run arrays may be NULL with cap == 0), k == 0 or k > II2_MAX_LISTS, a dictionary that is NULL or of
+ * another device, pat_off that does not start at 0 or descends, an unknown kind, a trailing `\`; II2_ERANGE for a pattern above
+ * II2_MATCH_MAX_PATTERN bytes or more than II2_MATCH_MAX_PATTERNS patterns (callers chunk).  n_patterns == 0 sets run_off[0] = 0
+ * and launches nothing.  More runs than cap: II2_ECAPACITY with run_off and *stats completely filled and the three run arrays
+ * untouched - allocate run_off[n_patterns * k] entries and call again.
+ * At most two waits per call.  Not a set operation: it takes no kernel path of ii2_ctx_paths.  No workgroup waits for another.
+ * Never reads past the 16 bytes of padding behind a dictionary's bytes.  Option "match.stage" (default 1): a workgroup copies
+ * the bytes of its 256 terms into LDS first when they fit; 0: every thread reads global memory.  Results are identical
+ * (dict_match.hip). */
+#define II2_MATCH_MAX_PATTERN  64u   /* bytes per pattern; longer: II2_ERANGE */
+#define II2_MATCH_MAX_PATTERNS 64u   /* patterns per call; more: II2_ERANGE (callers chunk) */
+enum { II2_MATCH_CONTAINS = 0, II2_MATCH_SUFFIX = 1, II2_MATCH_GLOB = 2 };
+#define II2_MATCH_NOCASE 0x80u       /* OR-ed into a kind: ASCII A-Z and a-z compare equal, no other byte folds */
+typedef struct {
+    uint64_t n_terms;     /* terms tested, summed over the k dictionaries */
+    uint64_t n_matched;   /* (pattern, term) pairs that matched */
+    uint64_t n_runs;      /* runs = run_off[n_patterns * k] */
+    uint32_t n_staged;    /* workgroups that matched out of the LDS stage */
+    uint32_t n_global;    /* workgroups that matched from global memory */
+} ii2_match_stats;        /* 32 bytes */
+int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes,
+                   const uint64_t *pat_off /* n_patterns + 1, from 0 */, const uint8_t *pat_kind /* n_patterns */,
+                   uint64_t *run_off /* n_patterns * k + 1 */, uint64_t *run_first, uint64_t *run_end,
+                   uint32_t *run_dict /* may be NULL */, uint64_t cap, ii2_match_stats *stats /* may be NULL */);
+/* The matchers' arithmetic, host only (no GPU needed): one pattern of `kind` (as above, II2_MATCH_NOCASE included) against one
+ * term by the functions the kernel runs - the same parse, the same three matchers.  *match = 0 / 1.  II2_EINVAL: a NULL output,
+ * NULL pat with pat_len > 0, NULL term with term_len > 0, an unknown kind, a trailing `\`.  II2_ERANGE: pat_len above
+ * II2_MATCH_MAX_PATTERN. */
+int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const uint8_t *term, uint64_t term_len, int *match);
 /* Dictionary build step (bulk Put, in front of ii2_seg_build).  Replaces the std::sort over every term occurrence, the
  * std::unique and the string bisection per occurrence that a bulk Put does on the host before ii2_seg_build (order = bytes.Compare,
  * file/types.go:24-26).  Input: n_terms terms in any order, repeats allowed, any bytes, the empty term included - term i is

@@ -1,0 +1,327 @@
+// dict_match.hip — substring, suffix and wildcard term search in resident dictionaries, hand-written: patterns in, list ranges
+// out, for every range entry point.
+//
+// Neither the term lookup (dict_find.hip) nor the reference's FST can answer "which terms hold `timeout`": both walk a term from
+// its front.  A dictionary that lies in HBM as flat bytes can be read whole instead - a million terms are some 15 MB.  The
+// answer of pattern p in dictionary s (entry p * k + s, as in ii2_dict_find) is the maximal runs of consecutive matching terms.
+//
+// Method, two kernels around one scan, no workgroup waits for another:
+//   k_dict_match   a workgroup of 256 threads takes 256 consecutive terms of ONE dictionary, a thread per term.  The parsed
+//                  patterns (match_device.h) and - where they fit MATCH_STAGE bytes - the terms' bytes are copied into LDS
+//                  first, 16 bytes per lane; a span that does not fit (one very long term) is matched from global memory, by
+//                  that workgroup alone.  Every thread leaves a 64-bit match word (bit p = pattern p) in workspace; the
+//                  workgroup counts per pattern its run starts (m[i] && !m[i - 1]) and run ends (m[i] && !m[i + 1]) with one
+//                  ballot per wave, and only for the patterns some lane of the wave has a start or an end of.  The neighbour
+//                  across a workgroup's edge is matched again by that workgroup, a lane per pattern, never fetched from the
+//                  other one.  The call's counters ride through the scans as one more row of the tables: no atomics.
+//   scan           of the two tables [pattern][workgroup] (the workgroups dictionary by dictionary, so a pair's entries are
+//                  adjacent): the entry of a pair's first workgroup is its run_off, every entry is its workgroup's place.
+//   k_match_place  reads the match words, not the terms: the j-th start of a pair writes run_first / run_dict at j, the j-th
+//                  end writes run_end at j - they belong to one run.  Launched only when the total fits the caller's cap.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "dv1_device.h"
+#include "internal.h"
+#include "match_device.h"
+
+namespace ii2 {
+
+constexpr uint32_t DM_THREADS = 256;
+constexpr uint32_t DM_WAVES = DM_THREADS / 64;
+// LDS stage of a workgroup's term bytes: 64 bytes per term on average.  With the patterns (5.5 KB) and the small arrays a
+// workgroup holds 25.5 KB of the CU's 160 KB: six workgroups per CU.
+constexpr uint32_t MATCH_STAGE = 16384;
+static_assert(II2_MATCH_MAX_PATTERNS == 64, "a match word is 64 bits, a wave's lane p counts pattern p");
+
+struct MatchDicts {
+    const uint64_t *off[MAX_LISTS];
+    const uint8_t *bytes[MAX_LISTS];
+    uint32_t n[MAX_LISTS];
+    uint32_t wg_first[MAX_LISTS + 1];     // workgroups of the dictionaries before s: ceil(n / 256) each
+    uint64_t term_first[MAX_LISTS + 1];   // terms of the dictionaries before s: where its match words start
+    uint32_t k;
+    uint32_t n_patterns;
+};
+
+// the dictionary of workgroup wg: the last s with wg_first[s] <= wg (dictionaries without terms have no workgroup)
+__device__ __forceinline__ uint32_t match_dict_of(const MatchDicts &d, uint32_t wg) {
+    uint32_t lo = 0, hi = d.k;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (d.wg_first[mid] <= wg) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint64_t wave_or64(uint64_t x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x |= (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
+    return x;
+}
+
+// Per pattern the run starts and run ends among this wave's lanes: lane p of the wave keeps pattern p's two counts.  The loop
+// runs over the patterns that have a start or an end in the wave at all (wave-uniform).
+__device__ __forceinline__ void wave_run_counts(uint64_t st, uint64_t en, uint32_t *n_st, uint32_t *n_en) {
+    const uint32_t l = (uint32_t)lane_id();
+    uint32_t cs = 0, ce = 0;
+    for (uint64_t live = wave_or64(st | en); live; live &= live - 1ull) {
+        const uint32_t p = (uint32_t)__builtin_ctzll(live);
+        const uint32_t a = (uint32_t)__popcll(__ballot((st >> p) & 1ull)), b = (uint32_t)__popcll(__ballot((en >> p) & 1ull));
+        if (l == p) { cs = a; ce = b; }
+    }
+    *n_st = cs;
+    *n_en = ce;
+}
+
+// workgroup wg: terms [t0, t0 + 256) of its dictionary.  words[term_first[s] + t] = the match word of term t;
+// tab_st / tab_en[p * n_wg + wg] = its run starts / ends of pattern p.  Row P of the two tables carries the call's counters
+// through the same scans, so that no workgroup touches a shared word (3907 atomics on one word took longer than the matching of
+// one pattern): tab_st[P * n_wg + wg] = its matched (pattern, term) pairs, tab_en[P * n_wg + wg] = 1 when it matched out of LDS.
+__global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const MatchPattern *__restrict__ pats, uint32_t stage_on, uint32_t n_wg,
+                                                           uint64_t *__restrict__ words, uint32_t *__restrict__ tab_st, uint32_t *__restrict__ tab_en) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[MATCH_STAGE];
+    __shared__ __attribute__((aligned(16))) MatchPattern lp[II2_MATCH_MAX_PATTERNS];
+    __shared__ uint64_t lw[DM_THREADS + 2];                 // lw[1 + i] = word of term t0 + i; lw[0] / lw[257] the neighbours outside
+    __shared__ uint32_t wcnt[DM_WAVES][2][64];
+    __shared__ uint32_t wmatched[DM_WAVES];
+    const uint32_t tid = threadIdx.x, wg = blockIdx.x;
+    const uint32_t s = match_dict_of(d, wg), n = d.n[s], P = d.n_patterns;
+    const uint64_t *__restrict__ off = d.off[s];
+    const uint8_t *__restrict__ bytes = d.bytes[s];
+    const uint32_t t0 = (wg - d.wg_first[s]) * DM_THREADS, t1 = min(t0 + DM_THREADS, n);      // t0 < n
+    const uint32_t l = (uint32_t)lane_id(), wv = tid >> 6;
+    {       // the patterns: 88 bytes each, word by word
+        const uint32_t *src = (const uint32_t *)pats;
+        uint32_t *dst = (uint32_t *)lp;
+        for (uint32_t i = tid; i < P * (uint32_t)(sizeof(MatchPattern) / 4); i += DM_THREADS) dst[i] = src[i];
+    }
+    // The stage holds the workgroup's own terms when they fit - and the two neighbours across its edges as well when those fit
+    // too (`wide`).  The dictionary's bytes are 256-byte aligned and padded by 16: every 16-byte load from a multiple of 16 up to
+    // the one that covers the span's last byte stays inside.  (All of this is workgroup-uniform.)
+    const uint32_t tl = t0 > 0 ? t0 - 1u : t0, tr = t1 < n ? t1 + 1u : t1;
+    const uint64_t b0 = off[t0], b1 = off[t1], bl = off[tl], br = off[tr];
+    const bool staged = stage_on && b1 - (b0 & ~15ull) <= MATCH_STAGE;
+    const bool wide = staged && br - (bl & ~15ull) <= MATCH_STAGE;
+    const uint64_t a0 = (wide ? bl : b0) & ~15ull, a1 = wide ? br : b1;
+    if (staged)
+        for (uint64_t i = (uint64_t)tid * 16u; a0 + i < a1; i += DM_THREADS * 16u)
+            *(uint4 *)(stage + i) = *(const uint4 *)(bytes + a0 + i);
+    __syncthreads();
+    const uint32_t t = t0 + tid;
+    uint64_t m = 0;
+    if (t < t1) {
+        const uint64_t b = off[t], len = off[t + 1] - b;
+        m = staged ? match_word(lp, P, stage + (b - a0), len) : match_word(lp, P, bytes + b, len);
+        words[d.term_first[s] + t] = m;
+    }
+    lw[1 + tid] = m;
+    // The neighbours across the edges are matched again here, not fetched from their workgroups (no neighbour before a
+    // dictionary's first term or behind its last): wave 0 takes the term before t0, wave 1 the term at t1, lane p pattern p, and
+    // the wave's ballot is the neighbour's match word - one pattern per lane instead of 64 for the thread at the edge.
+    if (wv < 2u) {
+        const bool have = wv == 0 ? t0 > 0 : t1 < n;
+        const uint32_t tn = wv == 0 ? tl : t1;
+        bool hit = false;
+        if (have && l < P) {
+            const uint64_t b = off[tn], len = off[tn + 1] - b;
+            hit = wide ? match_term(lp[l], stage + (b - a0), len) : match_term(lp[l], bytes + b, len);
+        }
+        const uint64_t w = __ballot(hit);
+        if (l == 0) lw[wv == 0 ? 0 : DM_THREADS + 1] = w;
+    }
+    __syncthreads();
+    const uint64_t st = m & ~lw[tid], en = m & ~lw[tid + 2];      // (a thread behind t1 has m = 0; the one at t1 - 1 sees 0 after it)
+    uint32_t cs, ce;
+    wave_run_counts(st, en, &cs, &ce);
+    wcnt[wv][0][l] = cs;
+    wcnt[wv][1][l] = ce;
+    uint32_t mine = (uint32_t)__popcll(m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+    if (l == 0) wmatched[wv] = mine;
+    __syncthreads();
+    if (tid < 2u * 64u) {
+        const uint32_t which = tid >> 6, p = tid & 63u;
+        if (p < P) {
+            uint32_t c = 0;
+            for (uint32_t w = 0; w < DM_WAVES; w++) c += wcnt[w][which][p];
+            (which ? tab_en : tab_st)[(uint64_t)p * n_wg + wg] = c;
+        }
+    }
+    if (tid == DM_THREADS - 1) {
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < DM_WAVES; w++) all += wmatched[w];
+        tab_st[(uint64_t)P * n_wg + wg] = all;
+        tab_en[(uint64_t)P * n_wg + wg] = staged ? 1u : 0u;
+    }
+}
+
+// run_off[p * k + s] = the runs before pair (p, s) = the scanned start table at the pair's first workgroup; run_off[P * k] = all
+// of them; behind it the counters the tables' row P carried: [P * k + 1] = matched pairs, [P * k + 2] = staged workgroups
+__global__ void k_match_offsets(MatchDicts d, uint32_t n_wg, const uint64_t *__restrict__ pre_st, const uint64_t *__restrict__ pre_en,
+                                uint64_t *__restrict__ run_off) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = d.n_patterns * d.k;
+    const uint64_t row_p = (uint64_t)d.n_patterns * n_wg;
+    if (i > n + 2u) return;
+    if (i == n + 1u) { run_off[i] = pre_st[row_p + n_wg] - pre_st[row_p]; return; }
+    if (i == n + 2u) { run_off[i] = pre_en[row_p + n_wg] - pre_en[row_p]; return; }
+    const uint32_t p = i / d.k, s = i - p * d.k;
+    run_off[i] = i == n ? pre_st[row_p] : pre_st[(uint64_t)p * n_wg + d.wg_first[s]];
+}
+
+// the same workgroups again, over the match words: every run start and every run end goes to its rank
+__global__ __launch_bounds__(DM_THREADS) void k_match_place(MatchDicts d, uint32_t n_wg, const uint64_t *__restrict__ words, const uint64_t *__restrict__ pre_st,
+                                                            const uint64_t *__restrict__ pre_en, uint64_t n_runs, uint64_t *__restrict__ run_first,
+                                                            uint64_t *__restrict__ run_end, uint32_t *__restrict__ run_dict) {
+    __shared__ uint32_t wcnt[DM_WAVES][2][64];
+    const uint32_t tid = threadIdx.x, wg = blockIdx.x;
+    const uint32_t s = match_dict_of(d, wg), n = d.n[s];
+    const uint32_t t = (wg - d.wg_first[s]) * DM_THREADS + tid;
+    const uint64_t *__restrict__ w = words + d.term_first[s];
+    uint64_t st = 0, en = 0;
+    if (t < n) {
+        const uint64_t m = w[t];
+        st = m & ~(t > 0 ? w[t - 1] : 0ull);
+        en = m & ~(t + 1u < n ? w[t + 1] : 0ull);
+    }
+    uint32_t cs, ce;
+    wave_run_counts(st, en, &cs, &ce);
+    const uint32_t l = (uint32_t)lane_id(), wv = tid >> 6;
+    wcnt[wv][0][l] = cs;
+    wcnt[wv][1][l] = ce;
+    __syncthreads();
+    const uint64_t below = (1ull << l) - 1ull;
+    for (uint64_t live = wave_or64(st | en); live; live &= live - 1ull) {
+        const uint32_t p = (uint32_t)__builtin_ctzll(live);
+        const uint64_t bs = __ballot((st >> p) & 1ull), be = __ballot((en >> p) & 1ull);
+        uint32_t before_s = 0, before_e = 0;
+        for (uint32_t v = 0; v < wv; v++) { before_s += wcnt[v][0][p]; before_e += wcnt[v][1][p]; }
+        const uint64_t at = (uint64_t)p * n_wg + wg;
+        if ((st >> p) & 1ull) {
+            const uint64_t j = pre_st[at] + before_s + (uint32_t)__popcll(bs & below);
+            if (j < n_runs) {       // (always: the scan's total is n_runs)
+                run_first[j] = t;
+                run_dict[j] = s;
+            }
+        }
+        if ((en >> p) & 1ull) {
+            const uint64_t j = pre_en[at] + before_e + (uint32_t)__popcll(be & below);
+            if (j < n_runs) run_end[j] = (uint64_t)t + 1u;
+        }
+    }
+}
+
+}  // namespace ii2
+
+using namespace ii2;
+
+extern "C" {
+
+int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes, const uint64_t *pat_off,
+                   const uint8_t *pat_kind, uint64_t *run_off, uint64_t *run_first, uint64_t *run_end, uint32_t *run_dict, uint64_t cap,
+                   ii2_match_stats *stats) {
+    if (!ctx || !dicts || k == 0 || k > II2_MAX_LISTS) return fail(ctx, II2_EINVAL, "ii2_dict_match: bad argument");
+    if (n_patterns > II2_MATCH_MAX_PATTERNS) return fail(ctx, II2_ERANGE, "ii2_dict_match: more than 64 patterns in one call");
+    if (n_patterns && (!pat_bytes || !pat_off || !pat_kind || !run_off || (cap && (!run_first || !run_end))))
+        return fail(ctx, II2_EINVAL, "ii2_dict_match: an array is NULL");
+    std::lock_guard<std::mutex> g(ctx->mu);
+    MatchDicts md;
+    std::memset(&md, 0, sizeof md);
+    md.k = k;
+    md.n_patterns = n_patterns;
+    for (uint32_t s = 0; s < k; s++) {
+        if (!dicts[s] || dicts[s]->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_dict_match: a dictionary is NULL or lives on another device");
+        if (dicts[s]->n >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_dict_match: a dictionary of 2^31 or more terms");
+        md.off[s] = dicts[s]->d_off; md.bytes[s] = dicts[s]->d_bytes;
+        md.n[s] = (uint32_t)dicts[s]->n;
+        md.wg_first[s + 1] = md.wg_first[s] + (md.n[s] + DM_THREADS - 1) / DM_THREADS;
+        md.term_first[s + 1] = md.term_first[s] + md.n[s];
+    }
+    std::vector<MatchPattern> pats(n_patterns);
+    if (n_patterns && pat_off[0] != 0) return fail(ctx, II2_EINVAL, "ii2_dict_match: pat_off must start at 0 and be non-decreasing");
+    for (uint32_t p = 0; p < n_patterns; p++) {
+        if (pat_off[p + 1] < pat_off[p]) return fail(ctx, II2_EINVAL, "ii2_dict_match: pat_off must start at 0 and be non-decreasing");
+        const int rc = match_parse(pat_kind[p], pat_bytes + pat_off[p], pat_off[p + 1] - pat_off[p], &pats[p]);
+        if (rc == II2_ERANGE) return fail(ctx, rc, "ii2_dict_match: a pattern of more than 64 bytes");
+        if (rc) return fail(ctx, rc, "ii2_dict_match: an unknown kind, or a glob that ends in a lone backslash");
+    }
+    const uint64_t n_pairs = (uint64_t)n_patterns * k, n_terms = md.term_first[k];
+    const uint32_t n_wg = md.wg_first[k];
+    if (n_patterns == 0 || n_wg == 0) {        // nothing to scan: no pattern, or no term in any dictionary
+        for (uint64_t i = 0; run_off && i <= n_pairs; i++) run_off[i] = 0;
+        if (stats) { std::memset(stats, 0, sizeof *stats); stats->n_terms = n_patterns ? n_terms : 0; }
+        return II2_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // a pair's runs are at most every other term of its dictionary; the caller's cap bounds what is ever written
+    uint64_t most = 0;
+    for (uint32_t s = 0; s < k; s++) most += (uint64_t)n_patterns * ((md.n[s] + 1u) / 2u);
+    const uint64_t n_place = std::min(cap, most);
+    const uint64_t n_tab = ((uint64_t)n_patterns + 1) * n_wg + 1;   // the patterns' rows, the counters' row, + 1: the scan's total
+    const size_t tmp_bytes = scan_temp_bytes(n_tab);
+    int rc = ii2_ws_reserve(ctx, align_up(n_patterns * sizeof(MatchPattern)) + align_up(n_terms * sizeof(uint64_t)) + 2 * align_up(n_tab * sizeof(uint32_t)) +
+                                     2 * align_up(n_tab * sizeof(uint64_t)) + tmp_bytes + align_up((n_pairs + 3) * sizeof(uint64_t)) +
+                                     2 * align_up(n_place * sizeof(uint64_t)) + align_up(n_place * sizeof(uint32_t)));
+    if (rc) return rc;
+    MatchPattern *d_pats = ws_take<MatchPattern>(ctx, n_patterns);
+    uint64_t *d_words = ws_take<uint64_t>(ctx, n_terms);
+    uint32_t *d_tab_st = ws_take<uint32_t>(ctx, n_tab), *d_tab_en = ws_take<uint32_t>(ctx, n_tab);
+    uint64_t *d_pre_st = ws_take<uint64_t>(ctx, n_tab), *d_pre_en = ws_take<uint64_t>(ctx, n_tab);
+    void *d_tmp = ws_take<uint8_t>(ctx, tmp_bytes);
+    uint64_t *d_run_off = ws_take<uint64_t>(ctx, n_pairs + 3);       // run_off, then {matched pairs, staged workgroups}
+    uint64_t *d_first = ws_take<uint64_t>(ctx, n_place), *d_end = ws_take<uint64_t>(ctx, n_place);
+    uint32_t *d_dict = ws_take<uint32_t>(ctx, n_place);
+    HIP_TRY(ctx, hipMemsetAsync(d_tab_st + (n_tab - 1), 0, sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_tab_en + (n_tab - 1), 0, sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pats, pats.data(), n_patterns * sizeof(MatchPattern), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, st, md, (const MatchPattern *)d_pats, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words,
+                       d_tab_st, d_tab_en);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_st, d_pre_st, n_tab, st));
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_en, d_pre_en, n_tab, st));
+    hipLaunchKernelGGL(k_match_offsets, dim3((unsigned)((n_pairs + 3 + 255) / 256)), dim3(256), 0, st, md, n_wg, (const uint64_t *)d_pre_st,
+                       (const uint64_t *)d_pre_en, d_run_off);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint64_t> h_off(n_pairs + 3), h_first, h_end;       // the caller's arrays are written only once nothing can fail any more:
+    std::vector<uint32_t> h_dict;                                   // an error return leaves all of them untouched
+    HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), d_run_off, (n_pairs + 3) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                       // the first wait: the sizes
+    const uint64_t n_runs = h_off[n_pairs];
+    if (n_runs <= cap && n_runs) {
+        hipLaunchKernelGGL(k_match_place, dim3(n_wg), dim3(DM_THREADS), 0, st, md, n_wg, (const uint64_t *)d_words, (const uint64_t *)d_pre_st,
+                           (const uint64_t *)d_pre_en, n_runs, d_first, d_end, d_dict);
+        HIP_TRY(ctx, hipGetLastError());
+        h_first.resize(n_runs); h_end.resize(n_runs); h_dict.resize(run_dict ? n_runs : 0);
+        HIP_TRY(ctx, hipMemcpyAsync(h_first.data(), d_first, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(h_end.data(), d_end, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (run_dict) HIP_TRY(ctx, hipMemcpyAsync(h_dict.data(), d_dict, n_runs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                   // the second wait: the runs
+        std::memcpy(run_first, h_first.data(), n_runs * sizeof(uint64_t));
+        std::memcpy(run_end, h_end.data(), n_runs * sizeof(uint64_t));
+        if (run_dict) std::memcpy(run_dict, h_dict.data(), n_runs * sizeof(uint32_t));
+    }
+    std::memcpy(run_off, h_off.data(), (n_pairs + 1) * sizeof(uint64_t));
+    if (stats) {
+        stats->n_terms = n_terms;
+        stats->n_matched = h_off[n_pairs + 1];
+        stats->n_runs = n_runs;
+        stats->n_staged = (uint32_t)h_off[n_pairs + 2];
+        stats->n_global = n_wg - stats->n_staged;
+    }
+    return n_runs > cap ? fail(ctx, II2_ECAPACITY, "ii2_dict_match: more runs than cap (run_off is filled: allocate run_off[n_patterns * k] and call again)") : II2_OK;
+}
+
+// host only: one pattern against one term, by the parse and the matchers k_dict_match runs
+int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const uint8_t *term, uint64_t term_len, int *match) {
+    if (!match || (pat_len && !pat) || (term_len && !term)) return II2_EINVAL;
+    MatchPattern m;
+    const int rc = match_parse(kind, pat, pat_len, &m);
+    if (rc) return rc;
+    *match = match_term(m, term, term_len) ? 1 : 0;
+    return II2_OK;
+}
+
+}  // extern "C"

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_DEVICE, II2_HOST, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -153,6 +153,18 @@ def merge_event_names():
         if name is None:
             return names
         names.append(name.decode())
+
+
+def term_match(kind: int, pattern: bytes, term: bytes) -> bool:
+    """One pattern against one term by the functions ii2_dict_match's kernel runs (ii2_term_match).  kind: II2_MATCH_CONTAINS /
+    SUFFIX / GLOB, optionally | II2_MATCH_NOCASE.  Needs no context and no GPU."""
+    lib = _lib.load()
+    m = C.c_int(-1)
+    rc = lib.ii2_term_match(int(kind), C.c_char_p(bytes(pattern)) if pattern else None, len(pattern), C.c_char_p(bytes(term)) if term else None,
+                            len(term), C.byref(m))
+    if rc:
+        raise II2Error(rc, "ii2_term_match")
+    return bool(m.value)
 
 
 class DeviceArray:
@@ -480,6 +492,43 @@ class Context:
         if where == II2_HOST:
             list_first, list_end = list_first[: n * len(dicts)], list_end[: n * len(dicts)]
         return list_first, list_end, found.value
+
+    def dict_match(self, dicts, patterns, kind=II2_MATCH_CONTAINS):
+        """Substring, suffix and wildcard term search on the device (ii2_dict_match): every pattern of `patterns` (bytes, at
+        most 64 of at most 64 bytes) in every one of the k resident dictionaries.  kind: II2_MATCH_CONTAINS / SUFFIX / GLOB,
+        optionally | II2_MATCH_NOCASE - one for all the patterns or one per pattern.  Returns (run_off, run_first, run_end,
+        run_dict, stats): pair (p, s) owns the runs run_off[p * k + s] .. run_off[p * k + s + 1] - 1, run j is the terms
+        [run_first[j], run_end[j]) of dictionary run_dict[j]; the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1,
+        are one group of the range entry points.  A result that outgrows the first buffer takes a second call of the exact size."""
+        patterns = list(patterns)
+        kinds = np.full(len(patterns), int(kind), np.uint8) if isinstance(kind, (int, np.integer)) else _np(kind, np.uint8)
+        if kinds.size != len(patterns):
+            raise ValueError("dict_match: one kind per pattern")
+        off = np.zeros(len(patterns) + 1, np.uint64)
+        if patterns:
+            off[1:] = np.cumsum([len(p) for p in patterns])
+        blob = np.frombuffer(b"".join(patterns) + b"\0", dtype=np.uint8).copy()
+        run_off = np.zeros(len(patterns) * len(dicts) + 1, np.uint64)
+        cap = 4096
+        while True:
+            first, end, which = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
+            rc, st = self.dict_match_flat(dicts, blob, off, kinds, run_off, first, end, which, cap)
+            if rc != -4 or int(run_off[-1]) <= cap:      # II2_ECAPACITY: run_off is filled, the second call is exact
+                self._ck(rc)
+                n = int(run_off[-1])
+                return run_off, first[:n], end[:n], which[:n], st
+            cap = int(run_off[-1])
+
+    def dict_match_flat(self, dicts, pat_bytes, pat_off, pat_kind, run_off, run_first, run_end, run_dict, cap: int, n_patterns=None):
+        """The same from flat host arrays (numpy, of the ABI's element types), outputs included; any of them may be None to pass
+        NULL.  n_patterns: len(pat_off) - 1 unless given.  Returns (return code, MatchStats) without raising, so that a caller
+        can run the two-call protocol itself."""
+        arr = (C.c_void_p * len(dicts))(*[d.h if d is not None else None for d in dicts])
+        n = int(n_patterns) if n_patterns is not None else (0 if pat_off is None else pat_off.size - 1)
+        st = MatchStats()
+        rc = self.lib.ii2_dict_match(self.h, len(dicts), arr, max(n, 0), _ptr(pat_bytes), _ptr(pat_off), _ptr(pat_kind), _ptr(run_off),
+                                     _ptr(run_first), _ptr(run_end), _ptr(run_dict), int(cap), C.byref(st))
+        return rc, st
 
     def align_dicts(self, dicts) -> "Alignment":
         """The union of k resident dictionaries and every dictionary's place in it (ii2_align_dicts): no upload, no sort."""
@@ -1027,6 +1076,12 @@ class Dictionary:
         """(list_first, list_end) u64 [len(terms)] of every term of `terms` in this dictionary (Context.dict_find with k = 1)."""
         first, end, _ = self.ctx.dict_find([self], terms, prefix)
         return first[:, 0].copy(), end[:, 0].copy()
+
+    def match(self, patterns, kind=II2_MATCH_CONTAINS):
+        """(run_off, run_first, run_end, stats) of every pattern of `patterns` in this dictionary (Context.dict_match with k = 1):
+        pattern p matches the terms [run_first[j], run_end[j]) for j in run_off[p] .. run_off[p + 1] - 1."""
+        run_off, first, end, _, st = self.ctx.dict_match([self], patterns, kind)
+        return run_off, first, end, st
 
     def info(self):
         """(number of terms, bytes of the terms) - ii2_dict_info"""

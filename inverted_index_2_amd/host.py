@@ -61,6 +61,8 @@ def _lib_typed():
         lib.ii2h_merge.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         lib.ii2h_read.argtypes = [vp, C.c_char_p, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64, C.c_int, u64p]
         lib.ii2h_prefix_search.argtypes = [vp, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_match_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, u64p]
+        lib.ii2h_match_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
@@ -71,6 +73,8 @@ def _lib_typed():
         lib.ii2h_set_first_cap.argtypes = [vp, C.c_uint64]
         lib.ii2h_second_calls.restype = C.c_uint64
         lib.ii2h_second_calls.argtypes = [vp]
+        lib.ii2h_union_bound.restype = C.c_uint64
+        lib.ii2h_union_bound.argtypes = [vp, C.c_uint64, vp]
         lib.ii2h_intersect_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_removed_values.argtypes = [vp, u64p]
@@ -97,6 +101,14 @@ def _pack(terms: List[bytes]):
         off[1:] = np.cumsum([len(t) for t in terms])
     blob = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
     return blob, off
+
+
+def union_bound(range_seg, seg_postings) -> int:
+    """For the tests, no device: the output bound prefix_search and match_search give one name whose range i lies in segment
+    `range_seg[i]`, segment s holding `seg_postings[s]` postings - every distinct segment counted once, however many ranges."""
+    seg = np.ascontiguousarray(list(range_seg) + [0], np.uint64)
+    posts = np.ascontiguousarray(list(seg_postings) + [0], np.uint64)
+    return _lib_typed().ii2h_union_bound(seg.ctypes.data, len(range_seg), posts.ctypes.data)
 
 
 class _Target:
@@ -182,6 +194,23 @@ class _Target:
     def _remove(self, values) -> None:
         v = np.ascontiguousarray(values, dtype=np.uint32)
         self._ck(self.lib.ii2h_remove(self.h, v.ctypes.data, v.size))
+
+    def match_search(self, patterns: List[bytes], kind: int = 0) -> Dict[bytes, List[int]]:
+        """Substring, suffix and wildcard search (MatchSearch): {pattern: ids under any term it matches}, over every segment (of
+        every shard); a pattern that matches no term has no entry.  kind: II2_MATCH_CONTAINS (0) / SUFFIX (1) / GLOB (2),
+        optionally | II2_MATCH_NOCASE (0x80), for all the patterns; any number of patterns (the device call takes 64 at a time).
+        Like read, no tombstone filter."""
+        blob, off = _pack(list(patterns))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_match_search(self.h, blob.ctypes.data, off.ctypes.data, len(patterns), int(kind), C.byref(n)))
+        return dict(self._results(n.value))
+
+    def match_terms(self, pattern: bytes, kind: int = 0, limit: int = 1 << 62) -> List[bytes]:
+        """The distinct terms the pattern matches (MatchTerms), in byte order, at most `limit`."""
+        pat = np.frombuffer(bytes(pattern) + b"\0", np.uint8).copy()
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_match_terms(self.h, pat.ctypes.data, len(pattern), int(kind), int(limit), C.byref(n)))
+        return [t for t, _ in self._results(n.value)]
 
     def removed_values(self) -> List[int]:
         n = C.c_uint64()

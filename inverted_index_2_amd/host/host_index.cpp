@@ -23,6 +23,7 @@
 //   IntersectTopBatch(queries)                       additive: many IntersectTopWeighted queries in one device call
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
+//   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
 //   SetResolve(mode)                                 additive: the two bulk calls look their terms up on the host or on the device (ii2_dict_find)
 //   SetFirstCap(ids) / SecondCalls()                 additive, for the tests: the first buffer of the calls that may need a second one (two_call)
 //   SetBuild(mode)                                   additive: PutBatch sorts and looks up its terms on the host or on the device (ii2_dict_build)
@@ -34,6 +35,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -129,6 +131,175 @@ static int64_t now_ns() {      // strictly increasing across threads (segment ke
     if (t <= last) t = last + 1;
     last = t;
     return t;
+}
+
+// ---- the two-call output protocol (InvertedIndex::two_call; Shard::MatchSearch) ----
+// No call allocates more than first_cap ids at first: a result that does not fit is written by a second call with the size the
+// first one reported (II2_ECAPACITY writes nothing; the batch calls fill their offsets under it).  Either call passes one entry
+// more than it needs.  `arrays`: the uint32 arrays of `cap` entries the output holds, back to back.  call(d_out, cap, &n) makes
+// the library call and returns its rc, n = the size it reported.  *second_calls (may be null) counts the retries.
+constexpr uint64_t FIRST_CAP_IDS = 1ull << 22;
+struct DevOutput {
+    DevMem mem;
+    uint64_t cap, n;           // entries per array, entries written
+};
+template <class Call> static DevOutput two_call_dev(ii2_ctx *ctx, uint64_t first_cap, std::atomic<uint64_t> *second_calls, uint64_t bound, unsigned arrays,
+                                                    const char *what, Call call) {
+    DevOutput o{DevMem(ctx), std::min(bound, first_cap) + 1, 0};
+    for (int attempt = 0;; attempt++) {
+        ck(ctx, ii2_dev_alloc(ctx, arrays * o.cap * sizeof(uint32_t), &o.mem.p), what);
+        const int rc = call((uint32_t *)o.mem.p, o.cap, &o.n);
+        if (rc != II2_ECAPACITY || attempt) {
+            ck(ctx, rc, what);
+            return o;
+        }
+        if (second_calls) (*second_calls)++;
+        ck(ctx, ii2_dev_free(ctx, o.mem.p), what);
+        o.mem.p = nullptr;
+        o.cap = o.n + 1;
+    }
+}
+
+// ---- one union per name over list ranges (MatchSearch; InvertedIndex::PrefixSearch keeps its own copy of this loop, which
+// tests/test_query_batch_cpu.py pins inside its body, and shares the bound) ----
+struct NamedRanges {
+    std::vector<const ii2_seg *> segs;
+    std::vector<uint64_t> first, end;
+};
+// The ids a union over ranges in `segs` (the segment of each range) can give at most: the postings of every DISTINCT segment,
+// once.  A prefix has one range per segment, a substring search any number of runs in one, and however many they are they hold
+// no more postings than the segment does.  postings(seg): that segment's count.
+template <class Seg, class Postings> static uint64_t union_bound(std::vector<Seg> segs, Postings postings) {
+    std::sort(segs.begin(), segs.end(), std::less<Seg>());
+    segs.erase(std::unique(segs.begin(), segs.end()), segs.end());
+    uint64_t b = 0;
+    for (const Seg &s : segs) b += postings(s);
+    return b;
+}
+static uint64_t seg_postings(const ii2_seg *h) {
+    ii2_seg_info info;
+    ii2_seg_get_info(h, &info);
+    return info.n_postings;
+}
+// ONE ii2_query_batch call, one wait and one download for all the names (an OR query each), through two_call(bound, call).  The
+// output's size: the C ABI gives no per-list counts, so a name is bounded by the postings of the segments its ranges lie in
+// (union_bound).  Names whose bounds add up to the call's limit of 2^32 ids go in several calls; one that reaches it alone goes
+// through ii2_union_ranges.
+template <class TwoCall> static std::map<Term, std::vector<uint32_t>> or_per_name(ii2_ctx *ctx, const std::map<Term, NamedRanges> &found, const char *what,
+                                                                                  TwoCall two_call) {
+    std::map<Term, std::vector<uint32_t>> out;
+    auto download = [&](const DevMem &d, uint64_t n) {
+        std::vector<uint32_t> v(n);
+        if (n) ck(ctx, ii2_copy_d2h(ctx, v.data(), d.p, n * sizeof(uint32_t)), what);
+        return v;
+    };
+    constexpr uint64_t CALL_IDS = 0xFFFFFFFFull;
+    auto it = found.begin();
+    while (it != found.end()) {
+        std::vector<const Term *> names;
+        std::vector<uint8_t> op;
+        std::vector<uint64_t> query_first{0}, first, end;
+        std::vector<const ii2_seg *> segs;
+        uint64_t bound = 0;
+        for (; it != found.end(); ++it) {
+            const NamedRanges &r = it->second;
+            const uint64_t b = union_bound(r.segs, seg_postings);
+            if (!names.empty() && bound + b >= CALL_IDS) break;
+            bound += b;
+            names.push_back(&it->first);
+            op.push_back(II2_OP_OR);
+            segs.insert(segs.end(), r.segs.begin(), r.segs.end());
+            first.insert(first.end(), r.first.begin(), r.first.end());
+            end.insert(end.end(), r.end.begin(), r.end.end());
+            query_first.push_back(segs.size());
+        }
+        if (bound >= CALL_IDS) {                                          // (one name, alone in its call)
+            DevMem d_out(ctx);
+            uint64_t n = 0;
+            ck(ctx, ii2_dev_alloc(ctx, (bound + 1) * sizeof(uint32_t), &d_out.p), what);
+            ck(ctx, ii2_union_ranges(ctx, segs.size(), segs.data(), first.data(), end.data(), nullptr, (uint32_t *)d_out.p, bound + 1, &n), what);
+            out[*names[0]] = download(d_out, n);
+            continue;
+        }
+        std::vector<uint64_t> off(names.size() + 1, 0);
+        const DevOutput o = two_call(bound, [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+            const int rc = ii2_query_batch(ctx, names.size(), op.data(), query_first.data(), segs.data(), first.data(), end.data(), nullptr, d_ids, cap,
+                                           off.data());
+            *n = off.back();
+            return rc;
+        });
+        const std::vector<uint32_t> all = download(o.mem, o.n);          // sort + compact, on the GPU
+        for (size_t q = 0; q < names.size(); q++) out[*names[q]] = std::vector<uint32_t>(all.begin() + off[q], all.begin() + off[q + 1]);
+    }
+    return out;
+}
+
+// ---- substring, suffix and wildcard search (additive: the reference's FST walks a term from its front only) ----
+// fn(pattern index, segment, j0, j1) for every run [j0, j1) of consecutive terms of every segment that pattern `patterns[p]` of
+// `kind` (II2_MATCH_*) matches: ii2_dict_match over the segments' resident dictionaries, in chunks of at most II2_MAX_LISTS
+// dictionaries and II2_MATCH_MAX_PATTERNS patterns - no host pass over the terms.  Per pattern the runs come segment by
+// segment, ascending inside one.  A result above the first buffer takes the second call ii2_dict_match asks for.
+template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t kind,
+                                           Fn fn) {
+    for (size_t p0 = 0; p0 < patterns.size(); p0 += II2_MATCH_MAX_PATTERNS) {
+        const size_t np = std::min<size_t>(II2_MATCH_MAX_PATTERNS, patterns.size() - p0);
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> off(np + 1, 0);
+        const std::vector<uint8_t> kinds(np, (uint8_t)kind);
+        for (size_t p = 0; p < np; p++) {
+            bytes.insert(bytes.end(), patterns[p0 + p].begin(), patterns[p0 + p].end());
+            off[p + 1] = bytes.size();
+        }
+        bytes.push_back(0);                                               // (never empty)
+        for (size_t s0 = 0; s0 < segs.size(); s0 += II2_MAX_LISTS) {
+            const size_t k = std::min<size_t>(II2_MAX_LISTS, segs.size() - s0);
+            std::vector<const ii2_dict *> dicts;
+            for (size_t s = 0; s < k; s++) dicts.push_back(segs[s0 + s]->resident_dict(ctx));
+            std::vector<uint64_t> run_off(np * k + 1, 0), first, end;
+            std::vector<uint32_t> which;
+            uint64_t cap = 4096;
+            for (int attempt = 0;; attempt++) {
+                first.resize(cap);
+                end.resize(cap);
+                which.resize(cap);
+                const int rc = ii2_dict_match(ctx, (uint32_t)k, dicts.data(), (uint32_t)np, bytes.data(), off.data(), kinds.data(), run_off.data(), first.data(),
+                                              end.data(), which.data(), cap, nullptr);
+                if (rc != II2_ECAPACITY || attempt) {
+                    ck(ctx, rc, "match search");
+                    break;
+                }
+                cap = run_off.back();
+            }
+            for (size_t p = 0; p < np; p++)
+                for (uint64_t j = run_off[p * k]; j < run_off[(p + 1) * k]; j++) fn(p0 + p, segs[s0 + which[j]], (size_t)first[j], (size_t)end[j]);
+        }
+    }
+}
+// map<pattern, ids> over `segs`: every pattern's runs, then one OR query per pattern (or_per_name).  A pattern that matches no
+// term has no entry.  No tombstone filter, as in Read.
+template <class TwoCall> static std::map<Term, std::vector<uint32_t>> match_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
+                                                                                   std::vector<Term> patterns, uint32_t kind, TwoCall two_call) {
+    std::sort(patterns.begin(), patterns.end(), term_less);
+    patterns.erase(std::unique(patterns.begin(), patterns.end()), patterns.end());
+    std::map<Term, NamedRanges> found;
+    match_runs(ctx, segs, patterns, kind, [&](size_t p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+        NamedRanges &r = found[patterns[p]];
+        r.segs.push_back(sg->seg->h);
+        r.first.push_back(j0);
+        r.end.push_back(j1);
+    });
+    return or_per_name(ctx, found, "match search", two_call);
+}
+// the distinct terms of `segs` that the pattern matches, in bytes.Compare order, at most `limit`: read from the runs
+static std::vector<Term> match_terms(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const Term &pattern, uint32_t kind, uint64_t limit) {
+    std::vector<Term> out;
+    match_runs(ctx, segs, {pattern}, kind, [&](size_t, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+        out.insert(out.end(), sg->terms.begin() + j0, sg->terms.begin() + j1);
+    });
+    std::sort(out.begin(), out.end(), term_less);
+    out.erase(std::unique(out.begin(), out.end()), out.end());
+    if (out.size() > limit) out.resize(limit);
+    return out;
 }
 
 // ---- file.Writer / file.Reader over segment_file.h (file/writer.go, file/reader.go) -----------------------------
@@ -352,6 +523,16 @@ class Shard {
         for (auto &s : snap) segs.push_back(s.get());
         return merged(segs, min, max, nullptr);
     }
+
+    // additive: substring, suffix and wildcard search over this shard's segments (InvertedIndex::MatchSearch / MatchTerms say what
+    // they return); no tombstone filter, as in Read
+    std::map<Term, std::vector<uint32_t>> MatchSearch(const std::vector<Term> &patterns, uint32_t kind) const {
+        const std::vector<std::shared_ptr<Segment>> segs = snapshot();
+        return match_search(ctx_, segs, patterns, kind, [&](uint64_t bound, auto call) {
+            return two_call_dev(ctx_, FIRST_CAP_IDS, nullptr, bound, 1, "match search", call);
+        });
+    }
+    std::vector<Term> MatchTerms(const Term &pattern, uint32_t kind, uint64_t limit) const { return match_terms(ctx_, snapshot(), pattern, kind, limit); }
 
     // shard.go:78-105
     void Remove(const std::vector<uint32_t> &values) {
@@ -886,12 +1067,7 @@ class InvertedIndex {
             uint64_t bound = 0;
             for (; it != found.end(); ++it) {
                 const Ranges &r = it->second;
-                uint64_t b = 0;
-                for (const ii2_seg *h : r.segs) {
-                    ii2_seg_info info;
-                    ii2_seg_get_info(h, &info);
-                    b += info.n_postings;
-                }
+                const uint64_t b = union_bound(r.segs, seg_postings);
                 if (!names.empty() && bound + b >= CALL_IDS) break;
                 bound += b;
                 names.push_back(&it->first);
@@ -922,6 +1098,16 @@ class InvertedIndex {
         }
         return out;
     }
+    // additive: substring, suffix and wildcard search - map<pattern, ids> of every pattern of `kind` (II2_MATCH_CONTAINS / SUFFIX /
+    // GLOB, | II2_MATCH_NOCASE).  It visits every segment of every shard (a pattern selects no shard): ii2_dict_match over the
+    // segments' resident dictionaries (match_runs), then one OR query per pattern over all its runs in ONE ii2_query_batch call,
+    // through two_call, as PrefixSearch does.  A pattern that matches no term has no entry.  Like Read, no tombstone filter.
+    std::map<Term, std::vector<uint32_t>> MatchSearch(const std::vector<Term> &patterns, uint32_t kind) const {
+        const std::vector<std::shared_ptr<Segment>> segs = all_segments();      // alive until the unions are done
+        return match_search(ctx_, segs, patterns, kind, [&](uint64_t bound, auto call) { return two_call(bound, 1, "match search", call); });
+    }
+    // additive: the distinct terms the pattern matches, over every segment of every shard, in bytes.Compare order, at most `limit`
+    std::vector<Term> MatchTerms(const Term &pattern, uint32_t kind, uint64_t limit) const { return match_terms(ctx_, all_segments(), pattern, kind, limit); }
     // additive: ids present under every term.  A term's postings are spread over the segments of its shard (every Put writes
     // one): one group per term, one one-list range per segment that holds it (Plan::add), and ONE ii2_intersect_ranges call - no
     // list is merged, downloaded or uploaded again.  The output's size: the smallest term's bound.  Like Read, no tombstone filter.
@@ -1219,25 +1405,10 @@ class InvertedIndex {
     // fit is written by a second call with the size the first one reported (II2_ECAPACITY writes nothing; the batch calls fill
     // their offsets under it).  Either call passes one entry more than it needs.  `arrays`: the uint32 arrays of `cap` entries the output holds, back to back (1: ids, 2: ids then
     // scores).  call(d_out, cap, &n) makes the library call and returns its rc, n = the size it reported.
-    static constexpr uint64_t FIRST_CAP = 1ull << 22;
-    struct Output {
-        DevMem mem;
-        uint64_t cap, n;           // entries per array, entries written
-    };
+    static constexpr uint64_t FIRST_CAP = FIRST_CAP_IDS;
+    using Output = DevOutput;
     template <class Call> Output two_call(uint64_t bound, unsigned arrays, const char *what, Call call) const {
-        Output o{DevMem(ctx_), std::min(bound, first_cap_.load()) + 1, 0};
-        for (int attempt = 0;; attempt++) {
-            ck(ctx_, ii2_dev_alloc(ctx_, arrays * o.cap * sizeof(uint32_t), &o.mem.p), what);
-            const int rc = call((uint32_t *)o.mem.p, o.cap, &o.n);
-            if (rc != II2_ECAPACITY || attempt) {
-                ck(ctx_, rc, what);
-                return o;
-            }
-            second_calls_++;
-            ck(ctx_, ii2_dev_free(ctx_, o.mem.p), what);
-            o.mem.p = nullptr;
-            o.cap = o.n + 1;
-        }
+        return two_call_dev(ctx_, first_cap_.load(), &second_calls_, bound, arrays, what, call);
     }
     std::vector<uint32_t> download(const DevMem &d, uint64_t n, const char *what) const {
         std::vector<uint32_t> v(n);
@@ -1443,6 +1614,14 @@ class InvertedIndex {
         std::lock_guard<std::mutex> g(mu_);
         std::vector<std::pair<uint32_t, Shard *>> v;
         for (auto &s : shards_) v.emplace_back(s.first, s.second.get());
+        return v;
+    }
+    std::vector<std::shared_ptr<Segment>> all_segments() const {          // of every shard, shard by shard in key order
+        std::vector<std::shared_ptr<Segment>> v;
+        for (auto &s : shard_list()) {
+            const auto snap = s.second->snapshot();
+            v.insert(v.end(), snap.begin(), snap.end());
+        }
         return v;
     }
     Shard *find_shard(uint32_t key) const {
@@ -1655,6 +1834,25 @@ int ii2h_prefix_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off
         *n_found = t->result.size();
     })
 }
+// map<pattern, ids> of the patterns (packed like terms) into the result slots, one per pattern that matched, in pattern order
+int ii2h_match_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint32_t kind, uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const std::vector<Term> patterns = unpack_terms(bytes, off, n);
+        for (auto &kv : t->index ? t->index->MatchSearch(patterns, kind) : t->shard->MatchSearch(patterns, kind))
+            t->result.push_back(TermValues{kv.first, kv.second});
+        *n_found = t->result.size();
+    });
+}
+// the distinct terms one pattern matches, at most `limit`, into the result slots (terms only)
+int ii2h_match_terms(ii2h_target *t, const uint8_t *pattern, uint64_t pattern_len, uint32_t kind, uint64_t limit, uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const Term p((const char *)pattern, pattern_len);
+        for (auto &term : t->index ? t->index->MatchTerms(p, kind, limit) : t->shard->MatchTerms(p, kind, limit)) t->result.push_back(TermValues{term, {}});
+        *n_found = t->result.size();
+    });
+}
 int ii2h_intersect(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->Intersect(unpack_terms(bytes, off, n)); *n_ids = t->ids.size(); })
 }
@@ -1702,6 +1900,11 @@ int ii2h_set_first_cap(ii2h_target *t, uint64_t ids) {
     });
 }
 uint64_t ii2h_second_calls(const ii2h_target *t) { return t->index ? t->index->SecondCalls() : 0; }
+// tests, no device: the output bound or_per_name gives one name (union_bound) whose range i lies in segment range_seg[i], segment
+// s holding postings[s] postings
+uint64_t ii2h_union_bound(const uint64_t *range_seg, uint64_t n_ranges, const uint64_t *postings) {
+    return union_bound(std::vector<uint64_t>(range_seg, range_seg + n_ranges), [&](uint64_t s) { return postings[s]; });
+}
 // n_q queries laid out as split_queries takes them.  Result q: the values of the target's result q (its term is empty)
 int ii2h_intersect_batch(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, const uint64_t *q_first, const uint64_t *q_req, uint64_t n_q,
                          uint64_t *n_results) {
