@@ -946,6 +946,14 @@ int ii2_selftest(ii2_ctx *ctx);
  *                                           0 (default) 2 exactly when the grid at 1 is larger than the device holds at once
  *   intersect.and2_slots                    ... the workgroups "the device holds at once" of that rule: 0 (default) CUs x the runtime's
  *                                           occupancy answer for the kernel; N > 0 (tests) N
+ *   intersect.and2_words                    the one-launch 2-list AND reads BOTH lists as cached bitmaps and ANDs them word by word - no
+ *                                           block of either list is read: 1 (default) when intersect.dense_form != 0, each list's bitmap is
+ *                                           at most half its payload bytes and the shorter list holds at least intersect.and2_words_min
+ *                                           blocks - the shorter list's bitmap is then made by the first such query on the pair, which
+ *                                           waits for the build once; 0 never; 2 (tests) for any pair the one-launch AND takes, unless
+ *                                           intersect.dense_form = 0.  Same results, same path name (and.and2_fused)
+ *   intersect.and2_words_min                ... the fewest blocks of the shorter list: 0 (default) CUs x the runtime's occupancy answer
+ *                                           for the present kernel x 16 (16 384 on an MI355X); N > 0 (tests) N
  *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0);
  *                                           tests: -1 / -2 force a give-up of the one-pass encoder's look-back (see below)
  *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters).

@@ -824,7 +824,7 @@ int ii2_tomb_create(ii2_ctx *ctx, const uint32_t *removed, uint64_t n, int where
     t->device = ctx->device;
     t->n_words = n ? (uint64_t)(mx >> 5) + 1 : 0;
     // bitmap, then its summary (1 bit per (1 << TOMB_SUM_SHIFT) docs) in the same allocation
-    const uint64_t words_padded = (t->n_words + 4 + 3) & ~3ull;
+    const uint64_t words_padded = (t->n_words + TOMB_PAD_WORDS + 3) & ~3ull;      // (k_and2_words loads 16 bytes from the last word)
     const uint64_t n_sum = (t->n_words >> TOMB_SUM_SHIFT) + 2;
     if (ii2::dm_malloc_retry((void **)&t->d_words, (words_padded + n_sum) * sizeof(uint32_t)) != hipSuccess) {
         delete t;
@@ -1190,6 +1190,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "intersect.and2_spin") ctx->opt_and2_spin = value;
     else if (k == "intersect.and2_tiles") ctx->opt_and2_tiles = value;    // 0: auto (setop.cpp and2_tiles_pick), 1, 2: tiles per wave where the longer list has a dense form
     else if (k == "intersect.and2_slots") ctx->opt_and2_slots = value;    // auto's "workgroups the device holds at once" (0: asked of the runtime)
+    else if (k == "intersect.and2_words") ctx->opt_and2_words = value;    // two dense lists, both as cached bitmaps, ANDed word by word: 0 never, 1 by the rule (setop.cpp and2_words_pick), 2 always (tests)
+    else if (k == "intersect.and2_words_min") ctx->opt_and2_words_min = value;    // the rule's "blocks the shorter list holds at least" (0: CUs x the runtime's occupancy answer x 16)
     else if (k == "intersect.dense_form") ctx->opt_dense_form = value;    // 0: never, 1: where the form is <= half the list's payload, 2: always (tests)
     else if (k == "encode.stream") ctx->opt_encode_stream = value;        // 1: one-pass encoder behind a merge (default), 0: two-pass, -1: forced fallback (tests)
     else return fail(ctx, II2_EINVAL, "unknown option");

@@ -89,6 +89,8 @@ struct ii2_ctx {
     int64_t opt_and2_tiles = 0;         // tiles a wave of the one-launch two-list AND owns where the longer list has a dense form: 0 auto, 1, 2
     int64_t opt_and2_slots = 0;         // ... auto: workgroups of the one-tile instance the device holds at once (0 = CUs x the occupancy query; tests inject one)
     int and2_wgs_per_cu = -1;           // the occupancy query's answer, asked once (-1: not yet)
+    int64_t opt_and2_words = 1;         // two dense lists: AND the cached dense forms of BOTH word by word (intersect_words.hip): 0 never, 1 by the rule of setop.cpp and2_words_pick, 2 always (tests)
+    int64_t opt_and2_words_min = 0;     // ... the rule: blocks the shorter list holds at least (0 = CUs x the occupancy query x 16; tests inject one)
     unsigned long long *d_lb = nullptr; // look-back records of the fused two-list AND: [0] error word, then agg[], grp[]
     size_t lb_cap = 0;                  // workgroups the records hold
     uint32_t lb_epoch = 0;              // launches so far
@@ -218,12 +220,13 @@ struct ii2_seg {
 };
 
 namespace ii2 { constexpr uint32_t TOMB_SUM_SHIFT = 4; }    // docs per bit of a tombstone bitmap's summary: 1 << TOMB_SUM_SHIFT
+namespace ii2 { constexpr uint32_t TOMB_PAD_WORDS = 4; }    // zero words every tombstone bitmap carries behind its n_words (ii2_tomb_create): a 16-byte load of its last word is legal
 
 struct ii2_tomb {
     int device = 0;
     uint32_t *d_words = nullptr;
     uint32_t *d_summary = nullptr;   // bit g set <=> some doc of [g << TOMB_SUM_SHIFT, (g + 1) << TOMB_SUM_SHIFT) is removed (same allocation as d_words)
-    uint64_t n_words = 0;   // bitmap covers doc ids [0, 32*n_words)
+    uint64_t n_words = 0;   // bitmap covers doc ids [0, 32*n_words); TOMB_PAD_WORDS zero words follow
 };
 
 // a term dictionary resident in HBM: sorted, duplicate-free terms of one segment (made by align.hip, looked up by dict_find.hip)
@@ -530,6 +533,10 @@ struct DenseParams {
     uint32_t a_origin;           // a multiple of 32
     uint32_t a_nwords;
     uint32_t and2_tiles;         // k_and2_fused with a dense form: tiles of sixteen lists[0] blocks a wave owns (2: the grid is half as many workgroups; else 1)
+    const uint32_t *b_bits;      // k_and2_words: lists[0]'s dense form as well (null: one of the kernels above) ...
+    uint32_t b_origin;           // a multiple of 32
+    uint32_t b_nwords;
+    uint32_t w_lo, w_n;          // ... and the window both forms cover, by and2_words_plan: its first word (doc >> 5) and its words (0: no common doc)
 };
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})
@@ -539,6 +546,10 @@ Path intersect_dense_path(const DenseParams &p);
 Path intersect_and2_path(const DenseParams &p);
 // workgroups of the one-tile dense-form instance of k_and2_fused that a CU holds at once (occupancy query; 0: unknown)
 uint32_t and2_fused_wgs_per_cu();
+// both lists have a dense form (intersect_words.hip): sets p.w_lo / p.w_n and returns the workgroups of k_and2_words (>= 1: what
+// the look-back records are prepared for); launch_intersect_and2 runs that kernel for a p with b_bits set
+uint32_t and2_words_plan(DenseParams &p);
+hipError_t launch_and2_words(const DenseParams &p, hipStream_t s);
 // the dense form of list L: bits[0, n_words) (all zero before) get bit d - origin for every doc d of the list
 hipError_t launch_dense_form_build(const ListView &L, uint32_t origin, uint32_t n_words, uint32_t *bits, hipStream_t s);
 

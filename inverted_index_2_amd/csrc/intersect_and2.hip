@@ -1421,7 +1421,8 @@ hipError_t launch_intersect_and2(const DenseParams &p, hipStream_t s, hipEvent_t
     if (ev0) (void)hipEventRecord(ev0, s);
     const uint32_t grid = (p.n_waves + 3u) / 4u;
     if (intersect_and2_path(p) == P_AND_AND2_FUSED) {
-        if (p.a_bits && p.and2_tiles == 2u) hipLaunchKernelGGL(k_and2_fused_x2, dim3((grid + 1u) / 2u), dim3(256), 0, s, p);
+        if (p.a_bits && p.b_bits) (void)launch_and2_words(p, s);     // both lists as bitmaps: intersect_words.hip
+        else if (p.a_bits && p.and2_tiles == 2u) hipLaunchKernelGGL(k_and2_fused_x2, dim3((grid + 1u) / 2u), dim3(256), 0, s, p);
         else if (p.a_bits) hipLaunchKernelGGL(k_and2_fused<true>, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_and2_fused<false>, dim3(grid), dim3(256), 0, s, p);
         if (ev1) (void)hipEventRecord(ev1, s);

@@ -269,12 +269,17 @@ static int tiles_setup(ii2_ctx *ctx, IntersectParams &p, uint32_t G, const SetOu
 }
 
 // ---- AND ------------------------------------------------------------------------------------
-// The dense form of l - lists[1] of a one-launch two-list AND, whose docs are sp - into dp (a_bits stays null: the call marks the
-// list as before).  Found in the store's cache, or made now when option intersect.dense_form allows it: 1 = the form's bytes are
-// at most half the list's payload bytes (it must be clearly smaller than what it replaces), 2 = always (tests).  The store's mutex
-// is held from the look-up until the build kernel has FINISHED: a context on another thread that asks for the same list
-// waits here and then reads a complete form, whatever its stream.  An allocation failure is not the query's: no form.
-static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpan &sp, DenseParams &dp) {
+// The dense form of l - a list of a one-launch two-list AND, whose docs are sp - into *out (bits stays null: the call reads the
+// list's blocks as before), and into *meets_b whether criterion (b) holds for the list: the form's bytes are at most half the
+// list's payload bytes (it must be clearly smaller than what it replaces).  Found in the store's cache, or made now when the
+// policy allows it: FORM_BY_OPTION = as option intersect.dense_form says (1: where (b) holds, 2: whatever it says - tests),
+// FORM_IF_B = where (b) holds and only there, not even a form that exists otherwise, FORM_ALWAYS = whatever (b) says.  The
+// store's mutex is held from the look-up until the build kernel has FINISHED: a context on another thread that asks for the
+// same list waits here and then reads a complete form, whatever its stream.  An allocation failure is not the query's: no form.
+struct FormRef { const uint32_t *bits; uint32_t origin, n_words; };
+enum FormPolicy { FORM_BY_OPTION, FORM_IF_B, FORM_ALWAYS };
+static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpan &sp, FormPolicy policy, FormRef *out, bool *meets_b) {
+    *meets_b = false;
     ii2_seg_store *store = l.seg->store.get();
     if (!store || !ctx->opt_dense_form || sp.last_doc < sp.first_doc) return II2_OK;
     hipStream_t st = ctx->stream;
@@ -293,9 +298,12 @@ static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpa
         it = store->forms.emplace(key, f).first;
     }
     ii2_seg_store::DenseForm &f = it->second;
+    const uint64_t bytes = (uint64_t)f.n_words * sizeof(uint32_t);
+    const bool fits = 2 * bytes <= f.payload_bytes;
+    *meets_b = fits;
+    if (policy == FORM_IF_B && !fits) return II2_OK;
     if (!f.d_words) {
-        const uint64_t bytes = (uint64_t)f.n_words * sizeof(uint32_t);
-        if (ctx->opt_dense_form != 2 && 2 * bytes > f.payload_bytes) return II2_OK;
+        if (policy == FORM_BY_OPTION && ctx->opt_dense_form != 2 && !fits) return II2_OK;
         uint32_t *w = nullptr;
         if (dm_alloc((void **)&w, bytes + 16) != hipSuccess) { (void)hipGetLastError(); return II2_OK; }      // (16-byte loads of the last words are legal)
         hipError_t e = hipMemsetAsync(w, 0, bytes + 16, st);
@@ -309,10 +317,30 @@ static int dense_form_get(ii2_ctx *ctx, const SetList &l, const ii2_seg::ListSpa
         f.d_words = w;
         store->form_bytes += bytes + 16;
     }
-    dp.a_bits = f.d_words;
-    dp.a_origin = f.origin;
-    dp.a_nwords = f.n_words;
+    out->bits = f.d_words;
+    out->origin = f.origin;
+    out->n_words = f.n_words;
     return II2_OK;
+}
+
+// Both lists of a one-launch two-list AND as dense forms, ANDed word by word (intersect_words.hip; option intersect.and2_words:
+// 0 never, 2 always - tests -, 1 = the rule).  That kernel reads two bitmaps where the present ones read one and the shorter
+// list's payload: it moves less when the shorter list, too, meets criterion (b) - so (ii) both lists meet it, each on its own
+// (whatever intersect.dense_form = 2 forces; the caller learns that from its one dense_form_get per list) - and a second form
+// costs memory and a build, which pays on a pair large enough to be asked often: (iii), answered here, the shorter list holds
+// at least intersect.and2_words_min blocks.  0 = CUs x workgroups of the one-tile instance per CU, by the occupancy query, x 16
+// blocks: 16 384 on an MI355X, a quarter of what the present kernel takes in one round.  The word AND measured 8 - 15 % faster
+// than the present kernel at 8 k, 16 k and 32 k blocks and 23 % at 130 k (DESIGN.md 4.1a', profiles/and2_words_threshold.txt);
+// below 16 k blocks that is under a microsecond a query for a second form.  (i), the one-launch path and intersect.dense_form
+// != 0, is the caller's and dense_form_get's.
+static bool and2_words_large_enough(ii2_ctx *ctx, const SetList *L) {
+    uint64_t min_blocks = ctx->opt_and2_words_min > 0 ? (uint64_t)ctx->opt_and2_words_min : 0u;
+    if (!min_blocks) {
+        if (ctx->and2_wgs_per_cu < 0) ctx->and2_wgs_per_cu = (int)and2_fused_wgs_per_cu();
+        min_blocks = (uint64_t)ctx->cu_count * (uint64_t)ctx->and2_wgs_per_cu * 16u;
+        if (!min_blocks) return false;                      // (the query failed: nothing to judge by)
+    }
+    return L[0].v.nblk >= min_blocks;
 }
 
 // Tiles a wave of the one-launch two-list AND owns when the longer list has a dense form (option intersect.and2_tiles: 1, 2, or
@@ -353,17 +381,29 @@ static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double pe
     const bool and2 = n == 2 && ctx->opt_intersect_and2 && bpw == 16u;
     if (int rc = dense_setup(ctx, dp, bpw, and2, o)) return rc;
     if (and2 && ctx->opt_intersect_and2 == 1) {
-        // one launch (k_and2_fused): the look-back records live in a buffer of their own (only these kernels write it, every
-        // word tagged with its launch's number: nothing to clear between launches)
-        if (int rcl = ii2_lookback_prepare(ctx, dp.n_meta / 4u, &dp.lb)) return rcl;
-        if (ctx->opt_and2_spin)
-            dp.lb.spin = ctx->opt_and2_spin > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_and2_spin, 0x7FFFFFFF) : ctx->opt_and2_spin == -2 ? LB_SPIN_LATE : LB_SPIN_EARLY;
         const double spanA = (double)dp.last_doc[1] - (double)dp.first_doc[1] + 1.0;
         dp.a_scale = (float)((double)L[1].v.nblk / spanA);
         dp.b_dpb = (float)per_block;
-        // the longer list as a cached bitmap where it has (or now gets) one: that instance of the kernel marks nothing
-        if (int rcf = dense_form_get(ctx, L[1], ii2_seg::ListSpan{dp.first_doc[1], 0u, dp.last_doc[1]}, dp)) return rcf;
+        // the longer list as a cached bitmap where it has (or now gets) one: that instance of the kernel marks nothing; both
+        // lists where option intersect.and2_words says so (the rule: and2_words_large_enough): that kernel reads no block at
+        // all.  One look-up per list.  A form that cannot be had (an allocation failure): the call goes on with what it has
+        const int64_t wmode = ctx->opt_dense_form ? ctx->opt_and2_words : 0;
+        FormRef fa{}, fb{};
+        bool a_meets_b = false, b_meets_b = false;
+        if (int rcf = dense_form_get(ctx, L[1], ii2_seg::ListSpan{dp.first_doc[1], 0u, dp.last_doc[1]}, wmode == 2 ? FORM_ALWAYS : FORM_BY_OPTION, &fa, &a_meets_b))
+            return rcf;
+        if (fa.bits && (wmode == 2 || (wmode == 1 && a_meets_b && and2_words_large_enough(ctx, L))))
+            if (int rcf = dense_form_get(ctx, L[0], ii2_seg::ListSpan{dp.first_doc[0], 0u, dp.last_doc[0]}, wmode == 2 ? FORM_ALWAYS : FORM_IF_B, &fb, &b_meets_b))
+                return rcf;
+        dp.a_bits = fa.bits; dp.a_origin = fa.origin; dp.a_nwords = fa.n_words;
+        dp.b_bits = fb.bits; dp.b_origin = fb.origin; dp.b_nwords = fb.n_words;
         dp.and2_tiles = dp.a_bits ? and2_tiles_pick(ctx, dp.n_meta / 4u) : 1u;
+        // one launch: the look-back records - one per workgroup of the kernel that runs - live in a buffer of their own (only
+        // these kernels write it, every word tagged with its launch's number: nothing to clear between launches)
+        const uint32_t wgs = dp.b_bits ? and2_words_plan(dp) : dp.n_meta / 4u;
+        if (int rcl = ii2_lookback_prepare(ctx, wgs, &dp.lb)) return rcl;
+        if (ctx->opt_and2_spin)
+            dp.lb.spin = ctx->opt_and2_spin > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_and2_spin, 0x7FFFFFFF) : ctx->opt_and2_spin == -2 ? LB_SPIN_LATE : LB_SPIN_EARLY;
     }
     if (ctx->opt_debug_stamps) {
         if (int rcd = ensure_debug(ctx, true)) return rcd;

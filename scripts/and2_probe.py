@@ -1,6 +1,10 @@
 """C2 (2-term AND over 100M docs) through the two dense paths: intersect.and2 = 1 (intersect_and2.hip) against 0 (the n-list
 streaming kernel), device time per pass from an event pair around a run of back-to-back passes, result checked against numpy
-once.  Extra arguments `name=value` are set as options first; `stamps` prints the per-phase cycle shares of the and2 kernels."""
+once.  Extra arguments `name=value` are set as options first; `stamps` prints the per-phase cycle shares of the and2 kernels;
+`words` times the one-launch form with intersect.and2_words = 0 (the shorter list's blocks against the longer list's dense form)
+and = 2 (both lists' dense forms ANDed word by word, intersect_words.hip) in this one process, alternating, and the first query
+of the pair - the one that builds the forms - before that."""
+import time
 import os
 import sys
 
@@ -13,10 +17,10 @@ from inverted_index_2_amd import Context, synth
 
 D = int(os.environ.get("D", 100_000_000))
 ctx = Context(0)
-want_stamps = False
+want_stamps = want_words = False
 for kv in sys.argv[1:]:
-    if kv == "stamps":
-        want_stamps = True
+    if kv in ("stamps", "words"):
+        want_stamps, want_words = want_stamps or kv == "stamps", want_words or kv == "words"
         continue
     k, v = kv.split("=")
     ctx.set_option(k, int(v))
@@ -43,7 +47,25 @@ def timed(tb, steps=50, warm=10):
     return ctx.profile_region_ms() * 1e3 / steps
 
 
-for and2 in (1, 2, 0, 1):
+if want_words:
+    for w in (0, 2):                    # the first query on the pair: w = 0 builds the longer list's form, w = 2 the shorter one's as well
+        ctx.set_option("intersect.and2_words", w)
+        ctx.sync()
+        t0 = time.perf_counter()
+        ctx.intersect_async(lists, None, out, dcnt)
+        ctx.sync()
+        print(f"and2_words={w} first query {(time.perf_counter() - t0) * 1e6:9.1f} us (host clock, forms built: {seg.dense_form_bytes()} bytes held)", flush=True)
+    for w in (0, 2, 0, 2):
+        ctx.set_option("intersect.and2_words", w)
+        for tb, wnt, name in ((None, want, "plain"), (tomb, want_t, "tombstones")):
+            ctx.intersect_async(lists, tb, out, dcnt)
+            ctx.sync()
+            n = int(dcnt.download(1)[0])
+            ok = n == wnt.size and np.array_equal(out.download(n), wnt)
+            print(f"and2_words={w} {name:10s} ok={ok} n={n} {timed(tb):8.2f} us per pass", flush=True)
+    ctx.set_option("intersect.and2_words", 1)
+
+for and2 in (() if want_words else (1, 2, 0, 1)):
     ctx.set_option("intersect.and2", and2)
     for tb, w, name in ((None, want, "plain"), (tomb, want_t, "tombstones")):
         ctx.intersect_async(lists, tb, out, dcnt)
@@ -58,17 +80,26 @@ if want_stamps:
     # (with A's dense form - intersect.dense_form=0 turns it off - phase 1 is the requests and phase 2 the form's words into LDS;
     # at two tiles a wave - intersect.and2_tiles=1 turns that off - a row is a workgroup of half the grid and every phase is the
     # sum over both tiles: the entries and the requests happen once, the landing, test, stage and flush once per tile)
-    names = {1: ["prologue", "clear+fetch", "mark A", "tomb+test B", "count+publish", "stage", "look-back", "flush"]}
-    for mode in (1,):
-        ctx.set_option("debug.stamps", mode)
+    # (the word-by-word instance - intersect_words.hip - has five phases of its own and a row per workgroup of 2048 words)
+    names = {0: ["prologue", "clear+fetch", "mark A", "tomb+test B", "count+publish", "stage", "look-back", "flush"],
+             2: ["requests", "landing+count+publish", "stage, first rounds", "look-back", "flush"]}
+    # with `words` both instances, each forced; else the one the options in force give
+    for w in ((0, 2) if want_words else (None,)):
+        if w is not None:
+            ctx.set_option("intersect.and2_words", w)
+        ctx.set_option("debug.stamps", 1)
         ctx.intersect_async(lists, None, out, dcnt)
         ctx.sync()
         buf = (C.c_uint64 * (2048 * 8))()
         ctx._ck(ctx.lib.ii2_debug_read(ctx.h, buf, 2048 * 8))
+        ctx.set_option("debug.stamps", 0)
+        if w is None:                   # the word AND ran if, and only if, the options in force gave the shorter list a form
+            w = 2 if seg.dense_form(0 if a.size <= b.size else 1, words=False) is not None else 0
         arr = np.frombuffer(buf, dtype=np.uint64).reshape(-1, 8).astype(np.float64)
         arr = arr[arr.sum(axis=1) > 0]
         tot = arr.sum(axis=1).mean() / 4
-        print("mode", mode, "rows", arr.shape[0], "mean cycles per wave", tot)
-        for i, nm in enumerate(names[mode]):
+        print("and2_words", w, "rows", arr.shape[0], "mean cycles per wave", tot)
+        for i, nm in enumerate(names[w]):
             print(f"    {nm:22s} {arr[:, i].mean() / 4:10.0f}  {100 * arr[:, i].mean() / 4 / tot:5.1f}%")
-    ctx.set_option("debug.stamps", 0)
+    if want_words:
+        ctx.set_option("intersect.and2_words", 1)
