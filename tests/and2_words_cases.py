@@ -39,12 +39,11 @@ def tomb_words(removed, lo, n):
     out = np.zeros(n, np.uint32)
     if removed is None or removed.size == 0 or n == 0:
         return out
-    nw = (int(removed[-1]) >> 5) + 1
-    bits = np.zeros(32 * nw, np.uint8)
-    bits[removed.astype(np.int64)] = 1
-    words = np.packbits(bits, bitorder="little").view("<u4")
-    take = words[lo:lo + n]
-    out[:take.size] = take
+    r = removed.astype(np.int64)                          # (64-bit, and only the asked words: a bitmap up to doc 2^32 - 1 is 512 MiB)
+    r = r[(r >= 32 * lo) & (r < 32 * (lo + n))]
+    bits = np.zeros(32 * n, np.uint8)
+    bits[r - 32 * lo] = 1
+    out[:] = np.packbits(bits, bitorder="little").view("<u4")
     return out
 
 

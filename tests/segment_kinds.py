@@ -23,7 +23,9 @@ tests/test_segment_kinds_cpu.py checks the table itself, tests/test_gpu_segment_
 every (kind, shape), tests/test_gpu_segment_kinds.py runs the readers of the derived arrays on every kind.
 
 The shapes are the smallest at which each array can go wrong (under 60 k postings each, doc spans of 2^19 so that a union in
-windows of 2048 docs stays at 256 windows): see SHAPES."""
+windows of 2048 docs stays at 256 windows): see SHAPES.  One shape is large, `pair` (~ 1.5 M postings): the dense two-list AND
+takes lists of at least 1024 blocks, and tests/test_gpu_segment_kinds_dense.py runs that family of kernels (tests/dense_edge_cases.py)
+on what every maker but merge_small, whose limit is 8192 postings, derives for such lists (dense_queries)."""
 import functools
 from types import SimpleNamespace
 
@@ -35,6 +37,7 @@ SPAN_MIRROR_MAX = 1 << 16
 BIG_LISTS = SPAN_MIRROR_MAX + 1
 SMALL_MERGE_TERMS, SMALL_MERGE_POSTINGS = 512, 8192          # include/ii2.h: II2_SMALL_MERGE_*
 SPAN = 1 << 19                                               # docs a shape spreads over
+PAIR_DOCS = 14 << 16                                         # ... and of the dense lists of `pair`: the smallest multiple of 65536 at which every plan keeps them dense (13: the tombstoned merges leave 969 blocks)
 E = np.empty(0, np.uint32)
 
 
@@ -51,7 +54,16 @@ def draw(rng, n, lo, hi):
 # ---- shapes ---------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def shape(name):
-    rng = np.random.default_rng({"lengths": 1, "high": 2, "crowd": 3}[name])
+    rng = np.random.default_rng({"lengths": 1, "high": 2, "crowd": 3, "pair": 4}[name])
+    if name == "pair":
+        # what the dense two-list AND family needs of a maker (dense_queries): a shorter dense list B and a longer one A - under
+        # every kind's plan both keep >= 1024 blocks at <= 1100 docs per block and a dense form of at most half their payload -,
+        # a third dense list, and a list A2 at one posting in five docs whose form would be 5 / 8 of its payload (no form);
+        # empty lists first, between the long lists and last, a short sparse list in front of the pair and one behind it; A2 is
+        # the last non-empty list: the skip entry behind its last block is a whole segment's sentinel
+        bern = lambda p, hi: np.flatnonzero(rng.random(hi) < p).astype(np.uint32)
+        B, A, third = bern(1 / 3, PAIR_DOCS), bern(1 / 2, PAIR_DOCS), bern(0.36, PAIR_DOCS)
+        return [E, draw(rng, 400, 1, PAIR_DOCS - 1), B, E, A, draw(rng, 100, 1, PAIR_DOCS - 1), third, E, bern(1 / 5, 2 * PAIR_DOCS), E]
     if name == "lengths":
         # every block-count edge; [0], whose last_doc is an empty list's; a list from 0; runs of empty lists first, inside, last;
         # a(255) / b(256) / c(257): b starts at a's last doc (their spans touch by one doc), c lies wholly behind b
@@ -80,8 +92,9 @@ def shape(name):
     return [draw(rng, int(n), 0, SPAN - 1) for n in lens]
 
 
-SHAPES = ("lengths", "high", "crowd")
+SHAPES = ("lengths", "high", "crowd", "pair")
 READER_SHAPE = "lengths"          # the shape the readers run on: it holds the 513- and the 16384-posting list and the a / b / c lists
+DENSE_SHAPE = "pair"              # the shape the dense two-list AND family runs on (dense_queries)
 
 
 # ---- the reference: the derived arrays from the lists alone ----------------------------------------------------------------
@@ -439,3 +452,40 @@ def queries(kind, shape_name=READER_SHAPE):
     q.merged = [np.union1d(a, b).astype(np.uint32) if len(a) or len(b) else E for a, b in zip(s, q.other)]
     return q
 
+
+DENSE_MIN_BLOCKS, DENSE_MAX_DOCS_PER_BLOCK = 1024, 1100.0   # the dense chooser: blocks of the list with the fewest, its docs per block
+DENSE_EXEMPT = ("merge_small",)                              # 8192 postings are 32 blocks: no dense list fits that maker
+
+
+def docs_per_block(l):
+    """what the set-op choosers look at: (first doc of the last block - first doc) / (blocks - 1)"""
+    return (int(l[BLOCK * (nblk(l) - 1)]) - int(l[0])) / (nblk(l) - 1)
+
+
+def form_bytes(l):
+    """bytes of a list's dense form: one bit per doc from its first doc's 32-doc word to its last doc's"""
+    return 4 * (((int(l[-1]) - (int(l[0]) & ~31)) >> 5) + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_queries(kind, shape_name=DENSE_SHAPE):
+    """What tests/test_gpu_segment_kinds_dense.py asks of one kind, by slot numbers, with the answers:
+      b, a, third         the slots of the main pair (b: fewer blocks) and of the third dense list; B, A, T: their lists
+      removed             every fifth doc of the union of all the lists
+      crit                (slot of the third list, slot of A2): the pair for criterion (b) - A2, at one posting in five docs, gets
+                          no dense form where the option leaves it to the criterion; A2 is the kind's last non-empty slot
+      others              every other slot: none of them may ever show a form
+      parent              slot -> list number in the store (what a view's parent calls the list); a whole segment's is its own"""
+    p = plan(kind, shape_name)
+    s = p.slots
+    ne = [i for i, l in enumerate(s) if len(l)]
+    assert len(ne) == 6, kind                                # sparse, B, A, sparse, third, A2 - in this order under every plan
+    q = SimpleNamespace()
+    _, q.b, q.a, _, q.third, q.a2 = ne
+    q.B, q.A, q.T, q.A2 = s[q.b], s[q.a], s[q.third], s[q.a2]
+    q.crit = (q.third, q.a2)
+    q.removed = union_of(s)[::5].copy()
+    q.others = [i for i in range(len(s)) if i not in (q.b, q.a)]
+    q.parent = {slot: j for j, (_, slot) in enumerate(p.store) if slot is not None}
+    q.last_non_empty_of_store = max(j for j, (l, _) in enumerate(p.store) if len(l)) == q.parent[q.a2]
+    return q

@@ -125,12 +125,37 @@ def test_dense_with_sparse_stretches_and_multibyte_gaps(ctx):
 
 
 def test_dense_lists_next_to_the_top_of_the_id_space(ctx):
+    """The tile path over a 4G-doc gap: the shorter list also holds docs 5 and 17, which puts its docs per block at millions - far
+    beyond the dense chooser's 1100 - so no streaming kernel takes this pair (_check asserts that) and the general tile kernels
+    meet two lists that are dense next to 2^32 behind a gap of almost the whole id space."""
     rng = np.random.default_rng(5)
     base = (1 << 32) - 1_200_000
     a, b = bernoulli(rng, 0.5, base, (1 << 32)), bernoulli(rng, 0.4, base, (1 << 32))
     a = np.union1d(a, np.asarray([0xFFFFFFFF, 0xFFFFFFFE], np.uint32)).astype(np.uint32)
     b = np.union1d(b, np.asarray([0xFFFFFFFF, 5, 17], np.uint32)).astype(np.uint32)       # one list also starts near 0: a 4G-doc gap
+    assert not dense_driver([a, b])
     _check(ctx, [a, b])
+
+
+def test_dense_kernels_at_the_top_of_the_id_space(ctx):
+    """The same two lists without docs 5 and 17: the streaming kernels (two to four lists, every and2 form, dense_bpw 32 / 64) on
+    docs up to 0xFFFFFFFF, and with a tombstone bitmap of all 2^27 words whose last word removes hits."""
+    rng = np.random.default_rng(5)
+    base, top = (1 << 32) - 1_200_000, 0xFFFFFFFF
+    a, b, c, d = (bernoulli(rng, p, base, (1 << 32)) for p in (0.5, 0.4, 0.6, 0.7))
+    a = np.union1d(a, np.asarray([top, top - 1], np.uint32)).astype(np.uint32)
+    b, c, d = (np.union1d(l[l < top - 1], np.asarray([top], np.uint32)).astype(np.uint32) for l in (b, c, d))      # 0xFFFFFFFE: in a alone
+    lists = [a, b]
+    assert dense_driver(lists) and dense_driver([a, b, c]) and dense_driver([a, b, c, d])
+    want = _check(ctx, lists)
+    assert want[-1] == top and top - 1 not in want and want.size > 1000
+    assert _check(ctx, [a, b, c])[-1] == top
+    assert _check(ctx, [a, b, c, d])[-1] == top
+    last_word = np.arange(0xFFFFFFE0, 1 << 32, 3, dtype=np.int64).astype(np.uint32)      # ... 0xFFFFFFFE is removed, 0xFFFFFFFF is not
+    removed = np.union1d(bernoulli(rng, 0.02, base, top), last_word).astype(np.uint32)
+    assert (int(removed[-1]) >> 5) + 1 == 1 << 27 and np.intersect1d(want, last_word).size > 0
+    got = _check(ctx, lists, removed=removed)
+    assert got.size < want.size and got[-1] == top
 
 
 def test_dense_zipf_pairs_match_the_oracle(ctx):

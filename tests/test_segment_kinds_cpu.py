@@ -27,8 +27,10 @@ def test_the_shapes_hold_every_edge():
     assert any(len(l) > 1 and l[0] == 0 for l in every)
     assert any(len(l) > 256 and len(l) % 256 == 1 for l in every)                   # a last block of one posting
     for name, s in shapes.items():
-        assert sum(len(l) for l in s) < 60_000, name
         assert all(l.dtype == np.uint32 and np.all(np.diff(l.astype(np.int64)) > 0) for l in s), name
+        if name == sk.DENSE_SHAPE:                                                   # (the one large shape: see the tests of dense_queries)
+            continue
+        assert sum(len(l) for l in s) < 60_000, name
         span = max(int(l[-1]) for l in s if len(l)) - min(int(l[0]) for l in s if len(l))
         assert 2048 < span < (1 << 19), name                                         # several 2048-doc windows, not thousands
     s = shapes["lengths"]
@@ -149,3 +151,45 @@ def test_the_readers_questions_are_not_trivial(kind):
     r, e = q.miss
     assert s[e][0] > s[r][-1]
     assert any(len(m) > len(a) > 0 for m, a in zip(q.merged, s))
+
+
+def test_the_pair_shape_has_the_layout_the_dense_family_asks_for():
+    s = sk.shape(sk.DENSE_SHAPE)
+    n = [len(l) for l in s]
+    assert n[0] == 0 and n[-1] == 0 and n[3] == 0 and n[7] == 0                      # empty first, between the long lists, last
+    assert 256 < n[1] < 512 and n[5] == 100                                          # a short sparse list in front of the pair, one behind
+    assert sk.nblk(s[2]) < sk.nblk(s[6]) < sk.nblk(s[8]) < sk.nblk(s[4])             # B, the third list, A2, A
+    assert len(s[4]) == max(n)                                                       # (A is the list the tombstoned merges thin out)
+    assert sk.PAIR_DOCS % 65536 == 0 and max(int(l[-1]) for l in s[:7] if len(l)) < sk.PAIR_DOCS and int(s[8][-1]) < 2 * sk.PAIR_DOCS
+
+
+@pytest.mark.parametrize("kind", list(sk.KINDS))
+def test_every_kind_keeps_the_pair_dense(kind):
+    """What tests/test_gpu_segment_kinds_dense.py asks of every kind: under the kind's plan the slots of B, A and the third list
+    still go to the dense kernels, a form of B and A meets criterion (b), A2's does not."""
+    p = sk.plan(kind, sk.DENSE_SHAPE)
+    if kind in sk.DENSE_EXEMPT:                                                      # no list of 1024 blocks fits the small merge
+        assert sk.SMALL_MERGE_POSTINGS < sk.DENSE_MIN_BLOCKS * sk.BLOCK and max(sk.nblk(l) for l in p.slots) < sk.DENSE_MIN_BLOCKS
+        return
+    q = sk.dense_queries(kind)
+    s = p.slots
+    assert q.b < q.a < q.third < q.a2 and q.crit == (q.third, q.a2)
+    for l in (q.B, q.A, q.T):                                                        # the chooser, whichever of them has the fewest blocks
+        assert sk.nblk(l) >= sk.DENSE_MIN_BLOCKS and 0 < sk.docs_per_block(l) <= sk.DENSE_MAX_DOCS_PER_BLOCK
+    assert sk.nblk(q.B) < sk.nblk(q.A) and sk.nblk(q.B) <= sk.nblk(q.T) < sk.nblk(q.A2)      # the roles: B and the third list pace
+    for l in (q.B, q.A):
+        assert 2 * sk.form_bytes(l) <= sk.payload_bytes(l)                           # criterion (b) holds ...
+    assert 2 * sk.form_bytes(q.A2) > sk.payload_bytes(q.A2)                          # ... and fails: no form
+    assert abs(sk.form_bytes(q.A2) / sk.payload_bytes(q.A2) - 5 / 8) < 0.05
+    own = int(q.A[-1]) - int(q.A[0]) + 1                                             # the streaming OR: A paces, B lies inside its reach
+    assert max(int(q.A[-1]), int(q.B[-1])) - min(int(q.A[0]), int(q.B[0])) + 1 <= own + own // 4 + 65536
+    hits = np.intersect1d(q.B, q.A)
+    assert 1000 < np.setdiff1d(hits, q.removed).size < hits.size and 1000 < np.intersect1d(q.T, q.A2).size
+    assert all(len(s[i]) == 0 or i in (q.third, q.a2) or len(s[i]) <= 400 for i in q.others)
+    assert any(len(s[i]) == 0 for i in range(q.b + 1, q.a))                          # an empty slot between B and A: it shares A's block number
+    assert len(s[0]) == 0 and len(s[-1]) == 0
+    if p.is_view:
+        assert (q.parent[q.b], q.parent[q.a]) != (q.b, q.a)                          # the parent numbers the lists differently
+    else:
+        assert all(q.parent[i] == i for i in (q.b, q.a, q.third, q.a2))
+        assert q.last_non_empty_of_store                                             # A2's one-past-last skip entry is the store's sentinel
