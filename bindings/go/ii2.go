@@ -422,6 +422,87 @@ func TermMatch(kind uint8, pattern, term []byte) (bool, error) {
 	return m != 0, nil
 }
 
+// FuzzyTranspose is a flag of DictFuzzy (II2_FUZZY_TRANSPOSE): an adjacent transposition costs 1 (optimal string alignment).
+// MatchNoCase is the only other flag.
+const FuzzyTranspose uint8 = 0x01
+
+// FuzzyStats mirrors ii2_fuzzy_stats.
+type FuzzyStats struct {
+	Terms, Matched, Runs, Tested uint64
+	Staged, Global, WordBits     uint32
+}
+
+// DictFuzzy is the typo-tolerant term search in k resident dictionaries (ii2_dict_fuzzy): every term within dist[p] edits of
+// pattern p that shares its first prefix[p] bytes.  At most 16 patterns of at most 64 bytes per call (callers chunk); flags[p] is
+// 0, FuzzyTranspose and / or MatchNoCase; prefix and flags may be nil (all 0).  The answer is laid out as DictMatch's: pair
+// (p, s) owns the runs runOff[p*k+s] .. runOff[p*k+s+1]-1, run j is the terms [first[j], end[j]) of dictionary dict[j], and the
+// runs of pattern p are one group of the range calls.  The runs carry no distance: send a pattern with distances 0, 1 and 2 for
+// tiers - the groups nest, so their weights add up in TopKWeightedRanges.  A result above the first buffer of 4096 runs takes the
+// second call the library asks for, with the exact size.
+func (c *Ctx) DictFuzzy(dicts []*Dictionary, patterns [][]byte, dist, prefix, flags []uint8) (runOff, first, end []uint64, dict []uint32, st FuzzyStats, err error) {
+	if len(dicts) == 0 {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict fuzzy: no dictionaries")
+	}
+	if len(dist) != len(patterns) || (prefix != nil && len(prefix) != len(patterns)) || (flags != nil && len(flags) != len(patterns)) {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict fuzzy: one distance, prefix and flag byte per pattern")
+	}
+	hs := make([]*C.ii2_dict, len(dicts))
+	for i, d := range dicts {
+		hs[i] = d.h
+	}
+	off := make([]uint64, len(patterns)+1)
+	var blob []byte
+	for i, p := range patterns {
+		blob = append(blob, p...)
+		off[i+1] = uint64(len(blob))
+	}
+	blob = append(blob, 0) // never an empty array
+	ds := append(append([]uint8{}, dist...), 0)
+	var pp, fp *C.uint8_t
+	if prefix != nil {
+		pre := append(append([]uint8{}, prefix...), 0)
+		pp = (*C.uint8_t)(unsafe.Pointer(&pre[0]))
+	}
+	if flags != nil {
+		fl := append(append([]uint8{}, flags...), 0)
+		fp = (*C.uint8_t)(unsafe.Pointer(&fl[0]))
+	}
+	runOff = make([]uint64, len(patterns)*len(dicts)+1)
+	capRuns := uint64(4096)
+	var cs C.ii2_fuzzy_stats
+	for attempt := 0; ; attempt++ {
+		first, end, dict = make([]uint64, capRuns+1), make([]uint64, capRuns+1), make([]uint32, capRuns+1)
+		rc := C.ii2_dict_fuzzy(c.h, C.uint32_t(len(hs)), (**C.ii2_dict)(unsafe.Pointer(&hs[0])), C.uint32_t(len(patterns)),
+			(*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off), (*C.uint8_t)(unsafe.Pointer(&ds[0])), pp, fp, u64ptr(runOff), u64ptr(first), u64ptr(end),
+			(*C.uint32_t)(unsafe.Pointer(&dict[0])), C.uint64_t(capRuns), &cs)
+		if rc == C.II2_ECAPACITY && attempt == 0 {
+			capRuns = runOff[len(runOff)-1]
+			continue
+		}
+		if rc != 0 {
+			return nil, nil, nil, nil, st, c.err("dict fuzzy", rc)
+		}
+		break
+	}
+	n := runOff[len(runOff)-1]
+	st = FuzzyStats{uint64(cs.n_terms), uint64(cs.n_matched), uint64(cs.n_runs), uint64(cs.n_tested), uint32(cs.n_staged), uint32(cs.n_global),
+		uint32(cs.word_bits)}
+	return runOff, first[:n], end[:n], dict[:n], st, nil
+}
+
+// TermFuzzy is one pattern against one term by the functions DictFuzzy's kernel runs (ii2_term_fuzzy): whether the term matches,
+// and the exact distance under flags whatever prefix and maxDist are; needs no GPU.
+func TermFuzzy(pattern, term []byte, maxDist, prefix uint32, flags uint8) (bool, uint32, error) {
+	p, t := append(append([]byte{}, pattern...), 0), append(append([]byte{}, term...), 0)
+	var m C.int
+	var d C.uint32_t
+	if rc := C.ii2_term_fuzzy(C.uint32_t(flags), (*C.uint8_t)(unsafe.Pointer(&p[0])), C.uint64_t(len(pattern)), C.uint32_t(prefix), C.uint32_t(maxDist),
+		(*C.uint8_t)(unsafe.Pointer(&t[0])), C.uint64_t(len(term)), &m, &d); rc != 0 {
+		return false, 0, fmt.Errorf("term fuzzy: error %d", int(rc))
+	}
+	return m != 0, uint32(d), nil
+}
+
 // AlignDicts is AlignTerms on resident dictionaries (ii2_align_dicts): nothing is uploaded, nothing is sorted.
 func (c *Ctx) AlignDicts(dicts []*Dictionary) (*Alignment, error) {
 	hs := make([]*C.ii2_dict, len(dicts))

@@ -399,6 +399,152 @@ func MatchSearch(c *Ctx, ix MatchIndex, patterns [][]byte, kind uint8) (found ma
 	return found, nil
 }
 
+// fuzzyRuns calls fn(p, segment index, j0, j1) for every run [j0, j1) of consecutive terms of every segment within maxDist edits of
+// patterns[p]: Ctx.DictFuzzy per chunk of at most 64 dictionaries and 16 patterns.  A pattern shorter than prefix is compared as
+// a whole.
+func fuzzyRuns(c *Ctx, dicts []*Dictionary, patterns [][]byte, maxDist, prefix, flags uint8, fn func(p, seg int, j0, j1 uint64)) error {
+	for p0 := 0; p0 < len(patterns); p0 += 16 {
+		p1 := p0 + 16
+		if p1 > len(patterns) {
+			p1 = len(patterns)
+		}
+		dist, pre, fl := make([]uint8, p1-p0), make([]uint8, p1-p0), make([]uint8, p1-p0)
+		for i := range dist {
+			dist[i], pre[i], fl[i] = maxDist, prefix, flags
+			if int(prefix) > len(patterns[p0+i]) {
+				pre[i] = uint8(len(patterns[p0+i]))
+			}
+		}
+		for s0 := 0; s0 < len(dicts); s0 += 64 {
+			s1 := s0 + 64
+			if s1 > len(dicts) {
+				s1 = len(dicts)
+			}
+			k := s1 - s0
+			runOff, first, end, dict, _, err := c.DictFuzzy(dicts[s0:s1], patterns[p0:p1], dist, pre, fl)
+			if err != nil {
+				return err
+			}
+			for p := 0; p < p1-p0; p++ {
+				for j := runOff[p*k]; j < runOff[(p+1)*k]; j++ {
+					fn(p0+p, s0+int(dict[j]), first[j], end[j])
+				}
+			}
+		}
+	}
+	return nil
+}
+
+// FuzzySearch (additive): typo-tolerant search - for every query term the ids under any term within maxDist edits of it that
+// shares its first prefix bytes (flags: FuzzyTranspose, MatchNoCase), over every segment of every shard.  Ctx.DictFuzzy per chunk
+// of at most 64 dictionaries and 16 patterns turns the terms into runs of lists, then ONE Ctx.QueryBatch call - an OpOr query per
+// term over all its runs - and one download, with a second call when the results exceed the first buffer: what the C++ host
+// mirror's InvertedIndex::FuzzySearch does (host/host_index.cpp).  A term that matches nothing has no entry.  Like Read, no
+// tombstone filter.
+func FuzzySearch(c *Ctx, ix MatchIndex, terms [][]byte, maxDist, prefix, flags uint8) (found map[string][]uint32, err error) {
+	defer ix.Release()
+	segs, dicts := ix.ResidentSegments()
+	type ranges struct {
+		segs       []*Segment
+		first, end []uint64
+	}
+	per := make([]ranges, len(terms))
+	if err := fuzzyRuns(c, dicts, terms, maxDist, prefix, flags, func(p, seg int, j0, j1 uint64) {
+		r := &per[p]
+		r.segs = append(r.segs, segs[seg])
+		r.first = append(r.first, j0)
+		r.end = append(r.end, j1)
+	}); err != nil {
+		return nil, fmt.Errorf("fuzzy search: %w", err)
+	}
+	var names []string
+	var op []uint8
+	queryFirst := []uint64{0}
+	var qsegs []*Segment
+	var qfirst, qend []uint64
+	seen := map[string]bool{}
+	for p, r := range per {
+		if len(r.segs) == 0 || seen[string(terms[p])] {
+			continue
+		}
+		seen[string(terms[p])] = true
+		names = append(names, string(terms[p]))
+		op = append(op, OpOr)
+		qsegs = append(qsegs, r.segs...)
+		qfirst = append(qfirst, r.first...)
+		qend = append(qend, r.end...)
+		queryFirst = append(queryFirst, uint64(len(qsegs)))
+	}
+	found = map[string][]uint32{}
+	if len(names) == 0 {
+		return found, nil
+	}
+	all, offs, err := c.QueryBatchHost(op, queryFirst, qsegs, qfirst, qend, uint64(1)<<22)
+	if err != nil {
+		return nil, fmt.Errorf("fuzzy search: %w", err)
+	}
+	for q, name := range names {
+		found[name] = all[offs[q]:offs[q+1]]
+	}
+	return found, nil
+}
+
+// FuzzyTerm is one answer of FuzzyTerms: a term and its exact distance to the pattern.
+type FuzzyTerm struct {
+	Term []byte
+	Dist uint32
+}
+
+// FuzzyTerms (additive): the distinct terms within maxDist edits of the pattern with their distances, distance ascending, then in
+// bytes.Compare order, at most limit.  The matched terms are read from the runs (Ctx.DictExport of the dictionaries that hold
+// one) and only those get their distance, from TermFuzzy on the host: what InvertedIndex::FuzzyTerms does.
+func FuzzyTerms(c *Ctx, ix MatchIndex, pattern []byte, maxDist, prefix, flags uint8, limit int) ([]FuzzyTerm, error) {
+	defer ix.Release()
+	_, dicts := ix.ResidentSegments()
+	exported := map[int][][]byte{}
+	seen := map[string]bool{}
+	var out []FuzzyTerm
+	var failed error
+	if err := fuzzyRuns(c, dicts, [][]byte{pattern}, maxDist, prefix, flags, func(_, seg int, j0, j1 uint64) {
+		if failed != nil {
+			return
+		}
+		if _, ok := exported[seg]; !ok {
+			exported[seg], failed = c.DictExport(dicts[seg])
+			if failed != nil {
+				return
+			}
+		}
+		for _, t := range exported[seg][j0:j1] {
+			if seen[string(t)] {
+				continue
+			}
+			seen[string(t)] = true
+			_, d, err := TermFuzzy(pattern, t, uint32(maxDist), 0, flags)
+			if err != nil {
+				failed = err
+				return
+			}
+			out = append(out, FuzzyTerm{append([]byte{}, t...), d})
+		}
+	}); err != nil {
+		return nil, fmt.Errorf("fuzzy terms: %w", err)
+	}
+	if failed != nil {
+		return nil, fmt.Errorf("fuzzy terms: %w", failed)
+	}
+	sort.Slice(out, func(i, j int) bool {
+		if out[i].Dist != out[j].Dist {
+			return out[i].Dist < out[j].Dist
+		}
+		return bytes.Compare(out[i].Term, out[j].Term) < 0
+	})
+	if len(out) > limit {
+		out = out[:limit]
+	}
+	return out, nil
+}
+
 // IntersectAtLeast (additive): the ids under at least minMatch of terms and under none of except - minimum-should-match, "any two
 // of these tags".  One group per term as IntersectExcept builds them, but a required term found in no segment is a group without
 // ranges (it matches no doc), not an empty result; ONE Ctx.AtLeastRanges call with one download - what the C++ host mirror's

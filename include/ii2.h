@@ -243,6 +243,62 @@ int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
  * NULL pat with pat_len > 0, NULL term with term_len > 0, an unknown kind, a trailing `\`.  II2_ERANGE: pat_len above
  * II2_MATCH_MAX_PATTERN. */
 int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const uint8_t *term, uint64_t term_len, int *match);
+/* Typo-tolerant term search in k resident dictionaries: every term within an edit distance of a pattern, as list ranges for the
+ * range entry points - the third mode of a search front end beside ii2_dict_find and ii2_dict_match (Lucene's FuzzyQuery; the
+ * reference's dictionary library answers it with a Levenshtein automaton over the FST).  The dictionaries are scanned whole; all
+ * arrays are host memory.  Everything compares bytes, as ii2_dict_match does (no UTF-8).
+ * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) and matches a term when BOTH hold: the term's first pat_prefix[p] bytes
+ * equal the pattern's first pat_prefix[p] bytes (Lucene's prefix_length: stripping a common prefix changes no distance; a term
+ * shorter than the prefix does not match), and the edit distance between the whole pattern and the whole term is at most
+ * pat_dist[p].  pat_flags[p] is 0 or an OR of
+ *   II2_FUZZY_TRANSPOSE  the distance is optimal string alignment: beside insert, delete and substitute (1 each: plain
+ *                        Levenshtein, the default) swapping two adjacent bytes costs 1, and no substring is edited twice -
+ *                        `ca` to `abc` is 3, not 2;
+ *   II2_MATCH_NOCASE     ASCII A-Z and a-z compare equal, in the prefix test and in the distance; no other byte folds.
+ * The empty pattern has distance term_len to every term.
+ * The answer's layout is exactly ii2_dict_match's: pair (p, s) is entry p * k + s, its runs are the maximal stretches of
+ * consecutive matching term indices, in run_off / run_first / run_end / run_dict - so pattern p is ONE group of every range entry
+ * point.  The runs carry no distance, on purpose: a caller that wants tiers sends the same pattern with distances 0, 1 and 2; the
+ * three groups nest, so in ii2_topk_weighted_ranges their weights add up for the closer terms.
+ * Every check runs before anything is launched or written: II2_EINVAL for a NULL array with n_patterns > 0 (pat_prefix,
+ * pat_flags, run_dict and stats excepted; the three run arrays may be NULL with cap == 0), k == 0 or k > II2_MAX_LISTS, a
+ * dictionary that is NULL or of another device, pat_off that does not start at 0 or descends, a flag bit other than the two
+ * above, a pat_prefix[p] above the pattern's length; II2_ERANGE for a pattern above II2_FUZZY_MAX_PATTERN bytes, more than
+ * II2_FUZZY_MAX_PATTERNS patterns (callers chunk) or a dictionary of 2^31 terms or more.  n_patterns == 0, or no term in any
+ * dictionary: run_off is all zero and nothing is launched.  More runs than cap: II2_ECAPACITY with run_off and *stats completely
+ * filled and the three run arrays untouched - allocate run_off[n_patterns * k] entries and call again.
+ * At most two waits per call.  Not a set operation: it takes no kernel path of ii2_ctx_paths.  No workgroup waits for another.
+ * Never reads past the 16 bytes of padding behind a dictionary's bytes.  On the device (dict_fuzzy.hip) a thread per term runs
+ * the bit-parallel recurrence of Myers / Hyyro with a DP column in one register; terms whose length differs from the pattern's
+ * by more than the distance, or whose prefix differs, are skipped before it (stats->n_tested counts the rest).  Options:
+ * "fuzzy.stage" (default 1): a workgroup copies the bytes of its 256 terms into LDS first when they fit; 0: every thread reads
+ * global memory.  "fuzzy.wide" (default 0): the 32-bit instance of the kernel runs when every pattern of the call holds at most
+ * 32 bytes; 1: always the 64-bit one.  Results are identical under all four settings. */
+#define II2_FUZZY_MAX_PATTERN  64u   /* bytes per pattern; longer: II2_ERANGE */
+#define II2_FUZZY_MAX_PATTERNS 16u   /* patterns per call; more: II2_ERANGE (callers chunk) */
+#define II2_FUZZY_TRANSPOSE    0x01u /* an adjacent transposition costs 1 (optimal string alignment) */
+/* II2_MATCH_NOCASE (0x80) is the only other flag */
+typedef struct {
+    uint64_t n_terms;    /* terms read, summed over the k dictionaries */
+    uint64_t n_matched;  /* (pattern, term) pairs within distance */
+    uint64_t n_runs;     /* runs = run_off[n_patterns * k] */
+    uint64_t n_tested;   /* pairs that passed the length and prefix filter and ran the recurrence */
+    uint32_t n_staged, n_global;   /* workgroups that matched out of LDS / from global memory */
+    uint32_t word_bits;  /* 32 or 64: the instance that ran; 0 when nothing was launched */
+    uint32_t pad;
+} ii2_fuzzy_stats;       /* 48 bytes */
+int ii2_dict_fuzzy(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes,
+                   const uint64_t *pat_off /* n_patterns + 1, from 0 */, const uint8_t *pat_dist /* n_patterns: max distance 0 .. 255 */,
+                   const uint8_t *pat_prefix /* n_patterns; NULL: all 0 */, const uint8_t *pat_flags /* n_patterns; NULL: all 0 */,
+                   uint64_t *run_off /* n_patterns * k + 1 */, uint64_t *run_first, uint64_t *run_end,
+                   uint32_t *run_dict /* may be NULL */, uint64_t cap, ii2_fuzzy_stats *stats /* may be NULL */);
+/* The matcher's arithmetic, host only (no GPU needed): one pattern against one term by the functions the kernel runs - the same
+ * parse, the same filters, the same recurrence.  *match = 0 / 1 as the kernel decides it; *dist (may be NULL) = the exact
+ * distance under `flags`, whatever prefix and max_dist are and for any term length.  prefix and max_dist are 32-bit here and any
+ * max_dist is accepted.  II2_EINVAL: a NULL match, NULL pat with pat_len > 0, NULL term with term_len > 0, a flag bit other than
+ * the two above, prefix above pat_len.  II2_ERANGE: pat_len above II2_FUZZY_MAX_PATTERN. */
+int ii2_term_fuzzy(uint32_t flags, const uint8_t *pat, uint64_t pat_len, uint32_t prefix, uint32_t max_dist, const uint8_t *term,
+                   uint64_t term_len, int *match, uint32_t *dist /* may be NULL */);
 /* Dictionary build step (bulk Put, in front of ii2_seg_build).  Replaces the std::sort over every term occurrence, the
  * std::unique and the string bisection per occurrence that a bulk Put does on the host before ii2_seg_build (order = bytes.Compare,
  * file/types.go:24-26).  Input: n_terms terms in any order, repeats allowed, any bytes, the empty term included - term i is

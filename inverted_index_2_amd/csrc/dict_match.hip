@@ -18,80 +18,35 @@
 //                  adjacent): the entry of a pair's first workgroup is its run_off, every entry is its workgroup's place.
 //   k_match_place  reads the match words, not the terms: the j-th start of a pair writes run_first / run_dict at j, the j-th
 //                  end writes run_end at j - they belong to one run.  Launched only when the total fits the caller's cap.
+// Everything behind the match word - the counting of run starts and ends (match_runs_tail), the scans, the two kernels under them
+// and the copies (match_runs_drive) - is shared with ii2_dict_fuzzy (dict_fuzzy.hip) through match_runs.h and defined here.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "dv1_device.h"
 #include "internal.h"
 #include "match_device.h"
+#include "match_runs.h"
 
 namespace ii2 {
 
-constexpr uint32_t DM_THREADS = 256;
-constexpr uint32_t DM_WAVES = DM_THREADS / 64;
-// LDS stage of a workgroup's term bytes: 64 bytes per term on average.  With the patterns (5.5 KB) and the small arrays a
-// workgroup holds 25.5 KB of the CU's 160 KB: six workgroups per CU.
-constexpr uint32_t MATCH_STAGE = 16384;
+// With the patterns (5.5 KB) and the small arrays a workgroup holds 25.5 KB of the CU's 160 KB beside its stage (match_runs.h):
+// six workgroups per CU.
 static_assert(II2_MATCH_MAX_PATTERNS == 64, "a match word is 64 bits, a wave's lane p counts pattern p");
 
-struct MatchDicts {
-    const uint64_t *off[MAX_LISTS];
-    const uint8_t *bytes[MAX_LISTS];
-    uint32_t n[MAX_LISTS];
-    uint32_t wg_first[MAX_LISTS + 1];     // workgroups of the dictionaries before s: ceil(n / 256) each
-    uint64_t term_first[MAX_LISTS + 1];   // terms of the dictionaries before s: where its match words start
-    uint32_t k;
-    uint32_t n_patterns;
-};
-
-// the dictionary of workgroup wg: the last s with wg_first[s] <= wg (dictionaries without terms have no workgroup)
-__device__ __forceinline__ uint32_t match_dict_of(const MatchDicts &d, uint32_t wg) {
-    uint32_t lo = 0, hi = d.k;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (d.wg_first[mid] <= wg) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint64_t wave_or64(uint64_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x |= (uint64_t)__shfl_xor((unsigned long long)x, o, 64);
-    return x;
-}
-
-// Per pattern the run starts and run ends among this wave's lanes: lane p of the wave keeps pattern p's two counts.  The loop
-// runs over the patterns that have a start or an end in the wave at all (wave-uniform).
-__device__ __forceinline__ void wave_run_counts(uint64_t st, uint64_t en, uint32_t *n_st, uint32_t *n_en) {
-    const uint32_t l = (uint32_t)lane_id();
-    uint32_t cs = 0, ce = 0;
-    for (uint64_t live = wave_or64(st | en); live; live &= live - 1ull) {
-        const uint32_t p = (uint32_t)__builtin_ctzll(live);
-        const uint32_t a = (uint32_t)__popcll(__ballot((st >> p) & 1ull)), b = (uint32_t)__popcll(__ballot((en >> p) & 1ull));
-        if (l == p) { cs = a; ce = b; }
-    }
-    *n_st = cs;
-    *n_en = ce;
-}
-
-// workgroup wg: terms [t0, t0 + 256) of its dictionary.  words[term_first[s] + t] = the match word of term t;
-// tab_st / tab_en[p * n_wg + wg] = its run starts / ends of pattern p.  Row P of the two tables carries the call's counters
-// through the same scans, so that no workgroup touches a shared word (3907 atomics on one word took longer than the matching of
-// one pattern): tab_st[P * n_wg + wg] = its matched (pattern, term) pairs, tab_en[P * n_wg + wg] = 1 when it matched out of LDS.
+// workgroup wg: terms [t0, t0 + 256) of its dictionary.  words[term_first[s] + t] = the match word of term t; the two tables and
+// their counter row are match_runs_tail's.
 __global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const MatchPattern *__restrict__ pats, uint32_t stage_on, uint32_t n_wg,
                                                            uint64_t *__restrict__ words, uint32_t *__restrict__ tab_st, uint32_t *__restrict__ tab_en) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[MATCH_STAGE];
     __shared__ __attribute__((aligned(16))) MatchPattern lp[II2_MATCH_MAX_PATTERNS];
-    __shared__ uint64_t lw[DM_THREADS + 2];                 // lw[1 + i] = word of term t0 + i; lw[0] / lw[257] the neighbours outside
-    __shared__ uint32_t wcnt[DM_WAVES][2][64];
-    __shared__ uint32_t wmatched[DM_WAVES];
     const uint32_t tid = threadIdx.x, wg = blockIdx.x;
     const uint32_t s = match_dict_of(d, wg), n = d.n[s], P = d.n_patterns;
     const uint64_t *__restrict__ off = d.off[s];
     const uint8_t *__restrict__ bytes = d.bytes[s];
     const uint32_t t0 = (wg - d.wg_first[s]) * DM_THREADS, t1 = min(t0 + DM_THREADS, n);      // t0 < n
-    const uint32_t l = (uint32_t)lane_id(), wv = tid >> 6;
     {       // the patterns: 88 bytes each, word by word
         const uint32_t *src = (const uint32_t *)pats;
         uint32_t *dst = (uint32_t *)lp;
@@ -116,57 +71,29 @@ __global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const M
         m = staged ? match_word(lp, P, stage + (b - a0), len) : match_word(lp, P, bytes + b, len);
         words[d.term_first[s] + t] = m;
     }
-    lw[1 + tid] = m;
-    // The neighbours across the edges are matched again here, not fetched from their workgroups (no neighbour before a
-    // dictionary's first term or behind its last): wave 0 takes the term before t0, wave 1 the term at t1, lane p pattern p, and
-    // the wave's ballot is the neighbour's match word - one pattern per lane instead of 64 for the thread at the edge.
-    if (wv < 2u) {
-        const bool have = wv == 0 ? t0 > 0 : t1 < n;
-        const uint32_t tn = wv == 0 ? tl : t1;
-        bool hit = false;
-        if (have && l < P) {
-            const uint64_t b = off[tn], len = off[tn + 1] - b;
-            hit = wide ? match_term(lp[l], stage + (b - a0), len) : match_term(lp[l], bytes + b, len);
-        }
-        const uint64_t w = __ballot(hit);
-        if (l == 0) lw[wv == 0 ? 0 : DM_THREADS + 1] = w;
-    }
-    __syncthreads();
-    const uint64_t st = m & ~lw[tid], en = m & ~lw[tid + 2];      // (a thread behind t1 has m = 0; the one at t1 - 1 sees 0 after it)
-    uint32_t cs, ce;
-    wave_run_counts(st, en, &cs, &ce);
-    wcnt[wv][0][l] = cs;
-    wcnt[wv][1][l] = ce;
-    uint32_t mine = (uint32_t)__popcll(m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
-    if (l == 0) wmatched[wv] = mine;
-    __syncthreads();
-    if (tid < 2u * 64u) {
-        const uint32_t which = tid >> 6, p = tid & 63u;
-        if (p < P) {
-            uint32_t c = 0;
-            for (uint32_t w = 0; w < DM_WAVES; w++) c += wcnt[w][which][p];
-            (which ? tab_en : tab_st)[(uint64_t)p * n_wg + wg] = c;
-        }
-    }
-    if (tid == DM_THREADS - 1) {
-        uint32_t all = 0;
-        for (uint32_t w = 0; w < DM_WAVES; w++) all += wmatched[w];
-        tab_st[(uint64_t)P * n_wg + wg] = all;
-        tab_en[(uint64_t)P * n_wg + wg] = staged ? 1u : 0u;
-    }
+    // (no neighbour before a dictionary's first term or behind its last)
+    match_runs_tail<1>(P, wg, n_wg, t0 > 0, t1 < n, m, 0u, staged, [&](uint32_t right, uint32_t p) {
+        const uint32_t tn = right ? t1 : tl;
+        const uint64_t b = off[tn], len = off[tn + 1] - b;
+        return wide ? match_term(lp[p], stage + (b - a0), len) : match_term(lp[p], bytes + b, len);
+    }, tab_st, tab_en);
 }
 
 // run_off[p * k + s] = the runs before pair (p, s) = the scanned start table at the pair's first workgroup; run_off[P * k] = all
-// of them; behind it the counters the tables' row P carried: [P * k + 1] = matched pairs, [P * k + 2] = staged workgroups
-__global__ void k_match_offsets(MatchDicts d, uint32_t n_wg, const uint64_t *__restrict__ pre_st, const uint64_t *__restrict__ pre_en,
+// of them; behind it the counters the tables' rows P .. P + n_rows - 1 carried, two per row: [P * k + 1 + 2 r] = the total of row
+// r of the start table (row 0: matched pairs), [P * k + 2 + 2 r] = of the end table (row 0: staged workgroups)
+__global__ void k_match_offsets(MatchDicts d, uint32_t n_wg, uint32_t n_rows, const uint64_t *__restrict__ pre_st, const uint64_t *__restrict__ pre_en,
                                 uint64_t *__restrict__ run_off) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = d.n_patterns * d.k;
     const uint64_t row_p = (uint64_t)d.n_patterns * n_wg;
-    if (i > n + 2u) return;
-    if (i == n + 1u) { run_off[i] = pre_st[row_p + n_wg] - pre_st[row_p]; return; }
-    if (i == n + 2u) { run_off[i] = pre_en[row_p + n_wg] - pre_en[row_p]; return; }
+    if (i > n + 2u * n_rows) return;
+    if (i > n) {
+        const uint32_t c = i - n - 1u;
+        const uint64_t row = row_p + (uint64_t)(c >> 1) * n_wg;
+        const uint64_t *__restrict__ pre = (c & 1u) ? pre_en : pre_st;
+        run_off[i] = pre[row + n_wg] - pre[row];
+        return;
+    }
     const uint32_t p = i / d.k, s = i - p * d.k;
     run_off[i] = i == n ? pre_st[row_p] : pre_st[(uint64_t)p * n_wg + d.wg_first[s]];
 }
@@ -213,6 +140,67 @@ __global__ __launch_bounds__(DM_THREADS) void k_match_place(MatchDicts d, uint32
     }
 }
 
+int match_runs_drive(ii2_ctx *ctx, const char *name, const MatchDicts &md, uint32_t n_rows, size_t head_bytes, const MatchLaunch &launch,
+                     const MatchRunsOut &out, uint64_t *n_runs_out, uint64_t *counters) {
+    const uint32_t k = md.k, n_patterns = md.n_patterns, n_wg = md.wg_first[k];
+    const uint64_t n_pairs = (uint64_t)n_patterns * k, n_terms = md.term_first[k], cap = out.cap;
+    const uint64_t n_off = n_pairs + 1 + 2ull * n_rows;              // run_off, then two counters per row
+    hipStream_t st = ctx->stream;
+    // a pair's runs are at most every other term of its dictionary; the caller's cap bounds what is ever written
+    uint64_t most = 0;
+    for (uint32_t s = 0; s < k; s++) most += (uint64_t)n_patterns * ((md.n[s] + 1u) / 2u);
+    const uint64_t n_place = std::min(cap, most);
+    const uint64_t n_tab = ((uint64_t)n_patterns + n_rows) * n_wg + 1;   // the patterns' rows, the counters' rows, + 1: the scan's total
+    const size_t tmp_bytes = scan_temp_bytes(n_tab);
+    int rc = ii2_ws_reserve(ctx, align_up(head_bytes) + align_up(n_terms * sizeof(uint64_t)) + 2 * align_up(n_tab * sizeof(uint32_t)) +
+                                     2 * align_up(n_tab * sizeof(uint64_t)) + tmp_bytes + align_up(n_off * sizeof(uint64_t)) +
+                                     2 * align_up(n_place * sizeof(uint64_t)) + align_up(n_place * sizeof(uint32_t)));
+    if (rc) return rc;
+    void *d_head = ws_take<uint8_t>(ctx, head_bytes);
+    uint64_t *d_words = ws_take<uint64_t>(ctx, n_terms);
+    uint32_t *d_tab_st = ws_take<uint32_t>(ctx, n_tab), *d_tab_en = ws_take<uint32_t>(ctx, n_tab);
+    uint64_t *d_pre_st = ws_take<uint64_t>(ctx, n_tab), *d_pre_en = ws_take<uint64_t>(ctx, n_tab);
+    void *d_tmp = ws_take<uint8_t>(ctx, tmp_bytes);
+    uint64_t *d_run_off = ws_take<uint64_t>(ctx, n_off);
+    uint64_t *d_first = ws_take<uint64_t>(ctx, n_place), *d_end = ws_take<uint64_t>(ctx, n_place);
+    uint32_t *d_dict = ws_take<uint32_t>(ctx, n_place);
+    HIP_TRY(ctx, hipMemsetAsync(d_tab_st + (n_tab - 1), 0, sizeof(uint32_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_tab_en + (n_tab - 1), 0, sizeof(uint32_t), st));
+    rc = launch(d_head, d_words, d_tab_st, d_tab_en);
+    if (rc) return rc;
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_st, d_pre_st, n_tab, st));
+    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_en, d_pre_en, n_tab, st));
+    hipLaunchKernelGGL(k_match_offsets, dim3((unsigned)((n_off + 255) / 256)), dim3(256), 0, st, md, n_wg, n_rows, (const uint64_t *)d_pre_st,
+                       (const uint64_t *)d_pre_en, d_run_off);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<uint64_t> h_off(n_off), h_first, h_end;             // the caller's arrays are written only once nothing can fail any more:
+    std::vector<uint32_t> h_dict;                                   // an error return leaves all of them untouched
+    HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), d_run_off, n_off * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));                       // the first wait: the sizes
+    const uint64_t n_runs = h_off[n_pairs];
+    if (n_runs <= cap && n_runs) {
+        hipLaunchKernelGGL(k_match_place, dim3(n_wg), dim3(DM_THREADS), 0, st, md, n_wg, (const uint64_t *)d_words, (const uint64_t *)d_pre_st,
+                           (const uint64_t *)d_pre_en, n_runs, d_first, d_end, d_dict);
+        HIP_TRY(ctx, hipGetLastError());
+        h_first.resize(n_runs); h_end.resize(n_runs); h_dict.resize(out.run_dict ? n_runs : 0);
+        HIP_TRY(ctx, hipMemcpyAsync(h_first.data(), d_first, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(h_end.data(), d_end, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        if (out.run_dict) HIP_TRY(ctx, hipMemcpyAsync(h_dict.data(), d_dict, n_runs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));                   // the second wait: the runs
+        std::memcpy(out.run_first, h_first.data(), n_runs * sizeof(uint64_t));
+        std::memcpy(out.run_end, h_end.data(), n_runs * sizeof(uint64_t));
+        if (out.run_dict) std::memcpy(out.run_dict, h_dict.data(), n_runs * sizeof(uint32_t));
+    }
+    std::memcpy(out.run_off, h_off.data(), (n_pairs + 1) * sizeof(uint64_t));
+    *n_runs_out = n_runs;
+    for (uint32_t c = 0; c < 2u * n_rows; c++) counters[c] = h_off[n_pairs + 1 + c];
+    if (n_runs > cap) {
+        ctx->err = std::string(name) + ": more runs than cap (run_off is filled: allocate run_off[n_patterns * k] and call again)";
+        return II2_ECAPACITY;
+    }
+    return II2_OK;
+}
+
 }  // namespace ii2
 
 using namespace ii2;
@@ -256,62 +244,24 @@ int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // a pair's runs are at most every other term of its dictionary; the caller's cap bounds what is ever written
-    uint64_t most = 0;
-    for (uint32_t s = 0; s < k; s++) most += (uint64_t)n_patterns * ((md.n[s] + 1u) / 2u);
-    const uint64_t n_place = std::min(cap, most);
-    const uint64_t n_tab = ((uint64_t)n_patterns + 1) * n_wg + 1;   // the patterns' rows, the counters' row, + 1: the scan's total
-    const size_t tmp_bytes = scan_temp_bytes(n_tab);
-    int rc = ii2_ws_reserve(ctx, align_up(n_patterns * sizeof(MatchPattern)) + align_up(n_terms * sizeof(uint64_t)) + 2 * align_up(n_tab * sizeof(uint32_t)) +
-                                     2 * align_up(n_tab * sizeof(uint64_t)) + tmp_bytes + align_up((n_pairs + 3) * sizeof(uint64_t)) +
-                                     2 * align_up(n_place * sizeof(uint64_t)) + align_up(n_place * sizeof(uint32_t)));
-    if (rc) return rc;
-    MatchPattern *d_pats = ws_take<MatchPattern>(ctx, n_patterns);
-    uint64_t *d_words = ws_take<uint64_t>(ctx, n_terms);
-    uint32_t *d_tab_st = ws_take<uint32_t>(ctx, n_tab), *d_tab_en = ws_take<uint32_t>(ctx, n_tab);
-    uint64_t *d_pre_st = ws_take<uint64_t>(ctx, n_tab), *d_pre_en = ws_take<uint64_t>(ctx, n_tab);
-    void *d_tmp = ws_take<uint8_t>(ctx, tmp_bytes);
-    uint64_t *d_run_off = ws_take<uint64_t>(ctx, n_pairs + 3);       // run_off, then {matched pairs, staged workgroups}
-    uint64_t *d_first = ws_take<uint64_t>(ctx, n_place), *d_end = ws_take<uint64_t>(ctx, n_place);
-    uint32_t *d_dict = ws_take<uint32_t>(ctx, n_place);
-    HIP_TRY(ctx, hipMemsetAsync(d_tab_st + (n_tab - 1), 0, sizeof(uint32_t), st));
-    HIP_TRY(ctx, hipMemsetAsync(d_tab_en + (n_tab - 1), 0, sizeof(uint32_t), st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pats, pats.data(), n_patterns * sizeof(MatchPattern), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, st, md, (const MatchPattern *)d_pats, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words,
-                       d_tab_st, d_tab_en);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_st, d_pre_st, n_tab, st));
-    HIP_TRY(ctx, scan_excl_u32_to_u64(d_tmp, tmp_bytes, d_tab_en, d_pre_en, n_tab, st));
-    hipLaunchKernelGGL(k_match_offsets, dim3((unsigned)((n_pairs + 3 + 255) / 256)), dim3(256), 0, st, md, n_wg, (const uint64_t *)d_pre_st,
-                       (const uint64_t *)d_pre_en, d_run_off);
-    HIP_TRY(ctx, hipGetLastError());
-    std::vector<uint64_t> h_off(n_pairs + 3), h_first, h_end;       // the caller's arrays are written only once nothing can fail any more:
-    std::vector<uint32_t> h_dict;                                   // an error return leaves all of them untouched
-    HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), d_run_off, (n_pairs + 3) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));                       // the first wait: the sizes
-    const uint64_t n_runs = h_off[n_pairs];
-    if (n_runs <= cap && n_runs) {
-        hipLaunchKernelGGL(k_match_place, dim3(n_wg), dim3(DM_THREADS), 0, st, md, n_wg, (const uint64_t *)d_words, (const uint64_t *)d_pre_st,
-                           (const uint64_t *)d_pre_en, n_runs, d_first, d_end, d_dict);
+    uint64_t n_runs = 0, counters[2] = {0, 0};          // {matched pairs, staged workgroups}
+    const int rc = match_runs_drive(ctx, "ii2_dict_match", md, 1, n_patterns * sizeof(MatchPattern),
+                                    [&](void *head, uint64_t *d_words, uint32_t *d_tab_st, uint32_t *d_tab_en) -> int {
+        HIP_TRY(ctx, hipMemcpyAsync(head, pats.data(), n_patterns * sizeof(MatchPattern), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, st, md, (const MatchPattern *)head, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words,
+                           d_tab_st, d_tab_en);
         HIP_TRY(ctx, hipGetLastError());
-        h_first.resize(n_runs); h_end.resize(n_runs); h_dict.resize(run_dict ? n_runs : 0);
-        HIP_TRY(ctx, hipMemcpyAsync(h_first.data(), d_first, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(h_end.data(), d_end, n_runs * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        if (run_dict) HIP_TRY(ctx, hipMemcpyAsync(h_dict.data(), d_dict, n_runs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));                   // the second wait: the runs
-        std::memcpy(run_first, h_first.data(), n_runs * sizeof(uint64_t));
-        std::memcpy(run_end, h_end.data(), n_runs * sizeof(uint64_t));
-        if (run_dict) std::memcpy(run_dict, h_dict.data(), n_runs * sizeof(uint32_t));
-    }
-    std::memcpy(run_off, h_off.data(), (n_pairs + 1) * sizeof(uint64_t));
+        return II2_OK;
+    }, MatchRunsOut{run_off, run_first, run_end, run_dict, cap}, &n_runs, counters);
+    if (rc && rc != II2_ECAPACITY) return rc;
     if (stats) {
         stats->n_terms = n_terms;
-        stats->n_matched = h_off[n_pairs + 1];
+        stats->n_matched = counters[0];
         stats->n_runs = n_runs;
-        stats->n_staged = (uint32_t)h_off[n_pairs + 2];
+        stats->n_staged = (uint32_t)counters[1];
         stats->n_global = n_wg - stats->n_staged;
     }
-    return n_runs > cap ? fail(ctx, II2_ECAPACITY, "ii2_dict_match: more runs than cap (run_off is filled: allocate run_off[n_patterns * k] and call again)") : II2_OK;
+    return rc;
 }
 
 // host only: one pattern against one term, by the parse and the matchers k_dict_match runs

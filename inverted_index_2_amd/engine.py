@@ -14,6 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._lib import II2_FUZZY_TRANSPOSE, FuzzyStats  # noqa: F401
 from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
@@ -165,6 +166,19 @@ def term_match(kind: int, pattern: bytes, term: bytes) -> bool:
     if rc:
         raise II2Error(rc, "ii2_term_match")
     return bool(m.value)
+
+
+def term_fuzzy(pattern: bytes, term: bytes, max_dist: int, prefix: int = 0, flags: int = 0):
+    """One pattern against one term by the functions ii2_dict_fuzzy's kernel runs (ii2_term_fuzzy): (match, dist) - whether the
+    term shares the pattern's first `prefix` bytes and lies within `max_dist` edits, and the exact distance whatever those two
+    are.  flags: 0, II2_FUZZY_TRANSPOSE and / or II2_MATCH_NOCASE.  Needs no context and no GPU."""
+    lib = _lib.load()
+    m, d = C.c_int(-1), C.c_uint32(0)
+    rc = lib.ii2_term_fuzzy(int(flags), C.c_char_p(bytes(pattern)) if pattern else None, len(pattern), int(prefix), int(max_dist),
+                            C.c_char_p(bytes(term)) if term else None, len(term), C.byref(m), C.byref(d))
+    if rc:
+        raise II2Error(rc, "ii2_term_fuzzy")
+    return bool(m.value), d.value
 
 
 class DeviceArray:
@@ -528,6 +542,49 @@ class Context:
         st = MatchStats()
         rc = self.lib.ii2_dict_match(self.h, len(dicts), arr, max(n, 0), _ptr(pat_bytes), _ptr(pat_off), _ptr(pat_kind), _ptr(run_off),
                                      _ptr(run_first), _ptr(run_end), _ptr(run_dict), int(cap), C.byref(st))
+        return rc, st
+
+    def dict_fuzzy(self, dicts, patterns, max_dist, prefix=0, flags=0):
+        """Typo-tolerant term search on the device (ii2_dict_fuzzy): every pattern of `patterns` (bytes, at most 16 of at most 64
+        bytes) in every one of the k resident dictionaries.  A term matches when it shares the pattern's first `prefix` bytes and
+        lies within `max_dist` edits (0 .. 255) of it; flags: 0, II2_FUZZY_TRANSPOSE and / or II2_MATCH_NOCASE.  Each of the
+        three is one value for all the patterns or one per pattern.  Returns (run_off, run_first, run_end, run_dict, stats), laid
+        out as dict_match's: the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1, are one group of the range
+        entry points.  A result that outgrows the first buffer takes a second call of the exact size."""
+        patterns = list(patterns)
+
+        def per_pattern(v, what):
+            a = np.full(len(patterns), int(v), np.uint8) if isinstance(v, (int, np.integer)) else _np(v, np.uint8)
+            if a.size != len(patterns):
+                raise ValueError(f"dict_fuzzy: one {what} per pattern")
+            return a
+
+        dist, pre, fl = per_pattern(max_dist, "max_dist"), per_pattern(prefix, "prefix"), per_pattern(flags, "flags")
+        off = np.zeros(len(patterns) + 1, np.uint64)
+        if patterns:
+            off[1:] = np.cumsum([len(p) for p in patterns])
+        blob = np.frombuffer(b"".join(patterns) + b"\0", dtype=np.uint8).copy()
+        run_off = np.zeros(len(patterns) * len(dicts) + 1, np.uint64)
+        cap = 4096
+        while True:
+            first, end, which = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
+            rc, st = self.dict_fuzzy_flat(dicts, blob, off, dist, pre, fl, run_off, first, end, which, cap)
+            if rc != -4 or int(run_off[-1]) <= cap:      # II2_ECAPACITY: run_off is filled, the second call is exact
+                self._ck(rc)
+                n = int(run_off[-1])
+                return run_off, first[:n], end[:n], which[:n], st
+            cap = int(run_off[-1])
+
+    def dict_fuzzy_flat(self, dicts, pat_bytes, pat_off, pat_dist, pat_prefix, pat_flags, run_off, run_first, run_end, run_dict, cap: int,
+                        n_patterns=None):
+        """The same from flat host arrays (numpy, of the ABI's element types), outputs included; any of them may be None to pass
+        NULL.  n_patterns: len(pat_off) - 1 unless given.  Returns (return code, FuzzyStats) without raising, so that a caller
+        can run the two-call protocol itself."""
+        arr = (C.c_void_p * len(dicts))(*[d.h if d is not None else None for d in dicts])
+        n = int(n_patterns) if n_patterns is not None else (0 if pat_off is None else pat_off.size - 1)
+        st = FuzzyStats()
+        rc = self.lib.ii2_dict_fuzzy(self.h, len(dicts), arr, max(n, 0), _ptr(pat_bytes), _ptr(pat_off), _ptr(pat_dist), _ptr(pat_prefix),
+                                     _ptr(pat_flags), _ptr(run_off), _ptr(run_first), _ptr(run_end), _ptr(run_dict), int(cap), C.byref(st))
         return rc, st
 
     def align_dicts(self, dicts) -> "Alignment":
@@ -1081,6 +1138,12 @@ class Dictionary:
         """(run_off, run_first, run_end, stats) of every pattern of `patterns` in this dictionary (Context.dict_match with k = 1):
         pattern p matches the terms [run_first[j], run_end[j]) for j in run_off[p] .. run_off[p + 1] - 1."""
         run_off, first, end, _, st = self.ctx.dict_match([self], patterns, kind)
+        return run_off, first, end, st
+
+    def fuzzy(self, patterns, max_dist, prefix=0, flags=0):
+        """(run_off, run_first, run_end, stats) of every pattern of `patterns` in this dictionary (Context.dict_fuzzy with k = 1):
+        the terms within `max_dist` edits of pattern p are [run_first[j], run_end[j]) for j in run_off[p] .. run_off[p + 1] - 1."""
+        run_off, first, end, _, st = self.ctx.dict_fuzzy([self], patterns, max_dist, prefix, flags)
         return run_off, first, end, st
 
     def info(self):

@@ -63,6 +63,8 @@ def _lib_typed():
         lib.ii2h_prefix_search.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_match_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, u64p]
         lib.ii2h_match_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p]
+        lib.ii2h_fuzzy_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p]
+        lib.ii2h_fuzzy_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
@@ -211,6 +213,24 @@ class _Target:
         n = C.c_uint64()
         self._ck(self.lib.ii2h_match_terms(self.h, pat.ctypes.data, len(pattern), int(kind), int(limit), C.byref(n)))
         return [t for t, _ in self._results(n.value)]
+
+    def fuzzy_search(self, terms: List[bytes], max_dist: int, prefix: int = 0, flags: int = 0) -> Dict[bytes, List[int]]:
+        """Typo-tolerant search (FuzzySearch): {query term: ids under any term within `max_dist` edits of it}, over every segment
+        (of every shard); a query term that matches nothing has no entry.  prefix: leading bytes a term must share with the query
+        term (a shorter query term is compared as a whole); flags: II2_FUZZY_TRANSPOSE (1) and / or II2_MATCH_NOCASE (0x80); any
+        number of query terms (the device call takes 16 at a time).  Like read, no tombstone filter."""
+        blob, off = _pack(list(terms))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_fuzzy_search(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(max_dist), int(prefix), int(flags), C.byref(n)))
+        return dict(self._results(n.value))
+
+    def fuzzy_terms(self, pattern: bytes, max_dist: int, prefix: int = 0, flags: int = 0, limit: int = 1 << 62) -> List[Tuple[bytes, int]]:
+        """The distinct terms within `max_dist` edits of the pattern with their distances (FuzzyTerms): [(term, distance), ...],
+        distance ascending, then in byte order, at most `limit`."""
+        pat = np.frombuffer(bytes(pattern) + b"\0", np.uint8).copy()
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_fuzzy_terms(self.h, pat.ctypes.data, len(pattern), int(max_dist), int(prefix), int(flags), int(limit), C.byref(n)))
+        return [(t, v[0]) for t, v in self._results(n.value)]
 
     def removed_values(self) -> List[int]:
         n = C.c_uint64()

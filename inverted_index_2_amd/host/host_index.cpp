@@ -24,6 +24,7 @@
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
+//   FuzzySearch(terms, max_dist, prefix, flags) / FuzzyTerms(pattern, max_dist, prefix, flags, limit)   additive: typo-tolerant search (ii2_dict_fuzzy)
 //   SetResolve(mode)                                 additive: the two bulk calls look their terms up on the host or on the device (ii2_dict_find)
 //   SetFirstCap(ids) / SecondCalls()                 additive, for the tests: the first buffer of the calls that may need a second one (two_call)
 //   SetBuild(mode)                                   additive: PutBatch sorts and looks up its terms on the host or on the device (ii2_dict_build)
@@ -302,6 +303,89 @@ static std::vector<Term> match_terms(ii2_ctx *ctx, const std::vector<std::shared
     return out;
 }
 
+// ---- typo-tolerant search (additive: what the reference's dictionary library answers with a Levenshtein automaton) ----
+// fn(pattern index, segment, j0, j1) for every run [j0, j1) of consecutive terms of every segment that lie within `max_dist`
+// edits of `patterns[p]` and share its first `prefix` bytes (flags: II2_FUZZY_TRANSPOSE, II2_MATCH_NOCASE): ii2_dict_fuzzy over
+// the segments' resident dictionaries, in chunks of at most II2_MAX_LISTS dictionaries and II2_FUZZY_MAX_PATTERNS patterns - no
+// host pass over the terms.  A pattern shorter than the prefix is compared as a whole.  Per pattern the runs come segment by
+// segment, ascending inside one.  A result above the first buffer takes the second call ii2_dict_fuzzy asks for.
+template <class Fn> static void fuzzy_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t max_dist,
+                                           uint32_t prefix, uint32_t flags, Fn fn) {
+    if (max_dist > 255 || flags > 255) throw Error("fuzzy search: max_dist and flags are at most 255");
+    for (size_t p0 = 0; p0 < patterns.size(); p0 += II2_FUZZY_MAX_PATTERNS) {
+        const size_t np = std::min<size_t>(II2_FUZZY_MAX_PATTERNS, patterns.size() - p0);
+        std::vector<uint8_t> bytes, pre(np);
+        std::vector<uint64_t> off(np + 1, 0);
+        const std::vector<uint8_t> dist(np, (uint8_t)max_dist), fl(np, (uint8_t)flags);
+        for (size_t p = 0; p < np; p++) {
+            bytes.insert(bytes.end(), patterns[p0 + p].begin(), patterns[p0 + p].end());
+            off[p + 1] = bytes.size();
+            pre[p] = (uint8_t)std::min<size_t>(prefix, patterns[p0 + p].size());
+        }
+        bytes.push_back(0);                                               // (never empty)
+        for (size_t s0 = 0; s0 < segs.size(); s0 += II2_MAX_LISTS) {
+            const size_t k = std::min<size_t>(II2_MAX_LISTS, segs.size() - s0);
+            std::vector<const ii2_dict *> dicts;
+            for (size_t s = 0; s < k; s++) dicts.push_back(segs[s0 + s]->resident_dict(ctx));
+            std::vector<uint64_t> run_off(np * k + 1, 0), first, end;
+            std::vector<uint32_t> which;
+            uint64_t cap = 4096;
+            for (int attempt = 0;; attempt++) {
+                first.resize(cap);
+                end.resize(cap);
+                which.resize(cap);
+                const int rc = ii2_dict_fuzzy(ctx, (uint32_t)k, dicts.data(), (uint32_t)np, bytes.data(), off.data(), dist.data(), pre.data(), fl.data(),
+                                              run_off.data(), first.data(), end.data(), which.data(), cap, nullptr);
+                if (rc != II2_ECAPACITY || attempt) {
+                    ck(ctx, rc, "fuzzy search");
+                    break;
+                }
+                cap = run_off.back();
+            }
+            for (size_t p = 0; p < np; p++)
+                for (uint64_t j = run_off[p * k]; j < run_off[(p + 1) * k]; j++) fn(p0 + p, segs[s0 + which[j]], (size_t)first[j], (size_t)end[j]);
+        }
+    }
+}
+// map<query term, ids under any term within distance> over `segs`: every query term's runs, then ONE batch of OR queries
+// (or_per_name).  A query term that matches nothing has no entry.  No tombstone filter, as in Read.
+template <class TwoCall> static std::map<Term, std::vector<uint32_t>> fuzzy_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
+                                                                                   std::vector<Term> terms, uint32_t max_dist, uint32_t prefix, uint32_t flags,
+                                                                                   TwoCall two_call) {
+    std::sort(terms.begin(), terms.end(), term_less);
+    terms.erase(std::unique(terms.begin(), terms.end()), terms.end());
+    std::map<Term, NamedRanges> found;
+    fuzzy_runs(ctx, segs, terms, max_dist, prefix, flags, [&](size_t p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+        NamedRanges &r = found[terms[p]];
+        r.segs.push_back(sg->seg->h);
+        r.first.push_back(j0);
+        r.end.push_back(j1);
+    });
+    return or_per_name(ctx, found, "fuzzy search", two_call);
+}
+// the distinct terms of `segs` within distance of the pattern with their distances, distance ascending, then bytes ascending, at
+// most `limit`: the terms are read from the runs, and only those get their distance, from ii2_term_fuzzy on the host
+static std::vector<std::pair<Term, uint32_t>> fuzzy_terms(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const Term &pattern,
+                                                          uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit) {
+    std::vector<Term> hit;
+    fuzzy_runs(ctx, segs, {pattern}, max_dist, prefix, flags, [&](size_t, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+        hit.insert(hit.end(), sg->terms.begin() + j0, sg->terms.begin() + j1);
+    });
+    std::sort(hit.begin(), hit.end(), term_less);
+    hit.erase(std::unique(hit.begin(), hit.end()), hit.end());
+    std::vector<std::pair<Term, uint32_t>> out;
+    for (const Term &t : hit) {
+        int match = 0;
+        uint32_t dist = 0;
+        ck(ctx, ii2_term_fuzzy(flags, (const uint8_t *)pattern.data(), pattern.size(), 0, max_dist, (const uint8_t *)t.data(), t.size(), &match, &dist),
+           "fuzzy terms");
+        out.emplace_back(t, dist);
+    }
+    std::stable_sort(out.begin(), out.end(), [](const std::pair<Term, uint32_t> &a, const std::pair<Term, uint32_t> &b) { return a.second < b.second; });
+    if (out.size() > limit) out.resize(limit);
+    return out;
+}
+
 // ---- file.Writer / file.Reader over segment_file.h (file/writer.go, file/reader.go) -----------------------------
 // The encode and decode steps run on the device through the C ABI (ii2_seg_encode / ii2_seg_import + ii2_seg_decode):
 // there is no host codec in the product.
@@ -533,6 +617,17 @@ class Shard {
         });
     }
     std::vector<Term> MatchTerms(const Term &pattern, uint32_t kind, uint64_t limit) const { return match_terms(ctx_, snapshot(), pattern, kind, limit); }
+    // additive: typo-tolerant search over this shard's segments (InvertedIndex::FuzzySearch / FuzzyTerms say what they return); no
+    // tombstone filter, as in Read
+    std::map<Term, std::vector<uint32_t>> FuzzySearch(const std::vector<Term> &terms, uint32_t max_dist, uint32_t prefix, uint32_t flags) const {
+        const std::vector<std::shared_ptr<Segment>> segs = snapshot();
+        return fuzzy_search(ctx_, segs, terms, max_dist, prefix, flags, [&](uint64_t bound, auto call) {
+            return two_call_dev(ctx_, FIRST_CAP_IDS, nullptr, bound, 1, "fuzzy search", call);
+        });
+    }
+    std::vector<std::pair<Term, uint32_t>> FuzzyTerms(const Term &pattern, uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit) const {
+        return fuzzy_terms(ctx_, snapshot(), pattern, max_dist, prefix, flags, limit);
+    }
 
     // shard.go:78-105
     void Remove(const std::vector<uint32_t> &values) {
@@ -1108,6 +1203,20 @@ class InvertedIndex {
     }
     // additive: the distinct terms the pattern matches, over every segment of every shard, in bytes.Compare order, at most `limit`
     std::vector<Term> MatchTerms(const Term &pattern, uint32_t kind, uint64_t limit) const { return match_terms(ctx_, all_segments(), pattern, kind, limit); }
+    // additive: typo-tolerant search - map<query term, ids under any term within `max_dist` edits of it> (flags: II2_FUZZY_TRANSPOSE,
+    // II2_MATCH_NOCASE; `prefix` leading bytes must be equal, Lucene's prefix_length).  It visits every segment of every shard:
+    // ii2_dict_fuzzy over the segments' resident dictionaries (fuzzy_runs), then one OR query per query term over all its runs in
+    // ONE ii2_query_batch call, through two_call, as MatchSearch does.  A term that matches nothing has no entry.  Like Read, no
+    // tombstone filter.
+    std::map<Term, std::vector<uint32_t>> FuzzySearch(const std::vector<Term> &terms, uint32_t max_dist, uint32_t prefix, uint32_t flags) const {
+        const std::vector<std::shared_ptr<Segment>> segs = all_segments();      // alive until the unions are done
+        return fuzzy_search(ctx_, segs, terms, max_dist, prefix, flags, [&](uint64_t bound, auto call) { return two_call(bound, 1, "fuzzy search", call); });
+    }
+    // additive: the distinct terms within distance of the pattern and their distances, over every segment of every shard, distance
+    // ascending, then in bytes.Compare order, at most `limit`
+    std::vector<std::pair<Term, uint32_t>> FuzzyTerms(const Term &pattern, uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit) const {
+        return fuzzy_terms(ctx_, all_segments(), pattern, max_dist, prefix, flags, limit);
+    }
     // additive: ids present under every term.  A term's postings are spread over the segments of its shard (every Put writes
     // one): one group per term, one one-list range per segment that holds it (Plan::add), and ONE ii2_intersect_ranges call - no
     // list is merged, downloaded or uploaded again.  The output's size: the smallest term's bound.  Like Read, no tombstone filter.
@@ -1850,6 +1959,28 @@ int ii2h_match_terms(ii2h_target *t, const uint8_t *pattern, uint64_t pattern_le
         t->result.clear();
         const Term p((const char *)pattern, pattern_len);
         for (auto &term : t->index ? t->index->MatchTerms(p, kind, limit) : t->shard->MatchTerms(p, kind, limit)) t->result.push_back(TermValues{term, {}});
+        *n_found = t->result.size();
+    });
+}
+// map<query term, ids> of the query terms (packed like terms) into the result slots, one per term that matched, in term order
+int ii2h_fuzzy_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint32_t max_dist, uint32_t prefix, uint32_t flags,
+                      uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const std::vector<Term> terms = unpack_terms(bytes, off, n);
+        for (auto &kv : t->index ? t->index->FuzzySearch(terms, max_dist, prefix, flags) : t->shard->FuzzySearch(terms, max_dist, prefix, flags))
+            t->result.push_back(TermValues{kv.first, kv.second});
+        *n_found = t->result.size();
+    });
+}
+// the distinct terms within distance of one pattern, at most `limit`, into the result slots: a term's single value is its distance
+int ii2h_fuzzy_terms(ii2h_target *t, const uint8_t *pattern, uint64_t pattern_len, uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit,
+                     uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const Term p((const char *)pattern, pattern_len);
+        for (auto &td : t->index ? t->index->FuzzyTerms(p, max_dist, prefix, flags, limit) : t->shard->FuzzyTerms(p, max_dist, prefix, flags, limit))
+            t->result.push_back(TermValues{td.first, {td.second}});
         *n_found = t->result.size();
     });
 }
