@@ -1010,6 +1010,12 @@ int ii2_selftest(ii2_ctx *ctx);
  *                                           intersect.dense_form = 0.  Same results, same path name (and.and2_fused)
  *   intersect.and2_words_min                ... the fewest blocks of the shorter list: 0 (default) CUs x the runtime's occupancy answer
  *                                           for the present kernel x 16 (16 384 on an MI355X); N > 0 (tests) N
+ *   intersect.and2_words_store              ... how that kernel stores the result ids: 1 (default) write-through - the bytes leave the
+ *                                           L2 as they are stored, the kernel's end has nothing to write back - as 16-byte stores to
+ *                                           16-byte-aligned addresses between single ids; 0 plain 16-byte stores at any 4-byte
+ *                                           alignment.  Same results
+ *   intersect.and2_words_order              ... and when: 0 (default) both chunks of a wave are extracted before its first store;
+ *                                           1 (measurements: slower) the first chunk's stores leave before the second is extracted
  *   encode.stream                           merged segments encoded in one pass over the ids (1) or by the two-pass encoder (0);
  *                                           tests: -1 / -2 force a give-up of the one-pass encoder's look-back (see below)
  *   merge.spin, intersect.and2_spin         polls a bounded inter-workgroup wait may take (tests shorten them; see ii2_ctx_counters).

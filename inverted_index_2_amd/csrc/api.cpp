@@ -1193,6 +1193,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "intersect.and2_tiles") ctx->opt_and2_tiles = value;    // 0: auto (setop.cpp and2_tiles_pick), 1, 2: tiles per wave where the longer list has a dense form
     else if (k == "intersect.and2_slots") ctx->opt_and2_slots = value;    // auto's "workgroups the device holds at once" (0: asked of the runtime)
     else if (k == "intersect.and2_words") ctx->opt_and2_words = value;    // two dense lists, both as cached bitmaps, ANDed word by word: 0 never, 1 by the rule (setop.cpp and2_words_pick), 2 always (tests)
+    else if (k == "intersect.and2_words_store") ctx->opt_and2_words_store = value;    // ... its id stores: 0 plain, 1 (default) write-through and 16-byte aligned
+    else if (k == "intersect.and2_words_order") ctx->opt_and2_words_order = value;    // ... 0 (default) both chunks staged before the first store, 1 (measurements) chunk 0's stores first
     else if (k == "intersect.and2_words_min") ctx->opt_and2_words_min = value;    // the rule's "blocks the shorter list holds at least" (0: CUs x the runtime's occupancy answer x 16)
     else if (k == "intersect.dense_form") ctx->opt_dense_form = value;    // 0: never, 1: where the form is <= half the list's payload, 2: always (tests)
     else if (k == "encode.stream") ctx->opt_encode_stream = value;        // 1: one-pass encoder behind a merge (default), 0: two-pass, -1: forced fallback (tests)

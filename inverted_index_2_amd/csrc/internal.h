@@ -90,7 +90,9 @@ struct ii2_ctx {
     int64_t opt_and2_slots = 0;         // ... auto: workgroups of the one-tile instance the device holds at once (0 = CUs x the occupancy query; tests inject one)
     int and2_wgs_per_cu = -1;           // the occupancy query's answer, asked once (-1: not yet)
     int64_t opt_and2_words = 1;         // two dense lists: AND the cached dense forms of BOTH word by word (intersect_words.hip): 0 never, 1 by the rule of setop.cpp and2_words_pick, 2 always (tests)
-    int64_t opt_and2_words_min = 0;     // ... the rule: blocks the shorter list holds at least (0 = CUs x the occupancy query x 16; tests inject one)
+    int64_t opt_and2_words_store = 1;   // ... its id stores: 0 plain, 1 write-through (sc1) to 16-byte-aligned addresses
+    int64_t opt_and2_words_order = 0;   // ... 0 both chunks of a wave are staged before the first store, 1 (measurements) chunk 0's stores leave first and chunk 1 is staged behind them
+    int64_t opt_and2_words_min = 0;    // ... the rule: blocks the shorter list holds at least (0 = CUs x the occupancy query x 16; tests inject one)
     unsigned long long *d_lb = nullptr; // look-back records of the fused two-list AND: [0] error word, then agg[], grp[]
     size_t lb_cap = 0;                  // workgroups the records hold
     uint32_t lb_epoch = 0;              // launches so far
@@ -539,6 +541,8 @@ struct DenseParams {
     uint32_t b_origin;           // a multiple of 32
     uint32_t b_nwords;
     uint32_t w_lo, w_n;          // ... and the window both forms cover, by and2_words_plan: its first word (doc >> 5) and its words (0: no common doc)
+    uint32_t words_store;        // ... its id stores: 0 plain, 1 write-through at 16-byte alignment
+    uint32_t words_early;        // ... chunk 0's stores leave before chunk 1 is staged (else both chunks are staged first)
 };
 hipError_t launch_intersect_dense(const DenseParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // AND of exactly two lists: lists[1] is marked, the postings of lists[0] are tested against it (meta = {first doc, last doc, ids, flags})

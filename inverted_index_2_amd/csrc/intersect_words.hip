@@ -15,6 +15,16 @@
 // lanes carry their position across them.  Every chunk has a stage of its own: the first round of all of them is staged while the
 // look-back record travels, and the stores then go out in one run (one stage for both chunks, the second one staged between the
 // two runs of stores: 22.0 us against 20.4 on the 100M-doc pair of DESIGN.md 4.1a').
+//
+// Two things about the stores are template parameters (options intersect.and2_words_order / intersect.and2_words_store):
+//   WT     (the default) the id stores are write-through (sc1): the bytes leave the XCD's L2 as they are stored, none stay dirty
+//          for the kernel's end to write back - 19.0 us against 21.7 with plain stores.  A partial 128-byte line then goes to
+//          the fabric as it is, so the 16-byte stores go to 16-byte-aligned addresses: a head of up to three single ids, the
+//          aligned body, a tail of single ids.  The stores go through a buffer resource that starts at the workgroup's first
+//          id and ends with its last one or with the capacity, whichever comes first.
+//   EARLY  (measurements: it loses, 20.1 us with WT and 23.2 without) only chunk 0 is staged while the record travels; its
+//          stores leave as soon as the workgroup's offset is known and chunk 1 is staged behind them (stage c0 / flush c0 /
+//          stage c1 / flush c1).
 #include "dv1_device.h"
 #include "internal.h"
 #include "lookback.h"
@@ -72,6 +82,35 @@ __device__ __forceinline__ void aw_flush(const DenseParams &p, const uint16_t *s
     }
 }
 
+// the same, write-through and aligned (WT above).  rs covers out[wg_off, wg_off + lim): rel = the round's first place in it,
+// mis = the ids by which out + wg_off lies behind a 16-byte boundary.  Stage reads at any 2-byte alignment.  (A head of up to 31
+// ids, so that a wave instruction's 1 KB starts on a 128-byte line: 18.9 us against 19.0, not kept)
+__device__ __forceinline__ void aw_store1(uint32_t v, __amdgpu_buffer_rsrc_t rs, uint32_t place) {
+    __builtin_amdgcn_raw_buffer_store_b32(v, rs, (int)(4u * place), 0, 16);              // (aux 16 = sc1)
+}
+__device__ __forceinline__ void aw_flush_wt(const uint16_t *st, uint32_t n, uint32_t doc0, __amdgpu_buffer_rsrc_t rs, uint32_t rel, uint32_t lim, uint32_t mis) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const uint32_t l = (uint32_t)lane_id();
+    if (rel + n > lim) {                                            // the capacity edge: id by id
+        for (uint32_t c = l; c < n; c += 64u)
+            if (rel + c < lim) aw_store1(doc0 + st[c], rs, rel + c);
+        return;
+    }
+    const uint32_t h0 = (0u - (mis + rel)) & 3u;
+    const uint32_t h = h0 < n ? h0 : n;                             // head: up to the first aligned place
+    if (l < h) aw_store1(doc0 + st[l], rs, rel + l);
+    const uint32_t nb = (n - h) & ~3u;                              // body: 16 bytes a lane
+    for (uint32_t c = 4u * l; c < nb; c += 256u) {
+        uint16_t o[4];
+        __builtin_memcpy(o, &st[h + c], 8);
+        const v4u ids = {doc0 + o[0], doc0 + o[1], doc0 + o[2], doc0 + o[3]};
+        __builtin_amdgcn_raw_buffer_store_b128(ids, rs, (int)(4u * (rel + h + c)), 0, 16);
+    }
+    const uint32_t t0 = h + nb;                                     // tail: up to three ids
+    if (t0 + l < n) aw_store1(doc0 + st[t0 + l], rs, rel + t0 + l);
+}
+
+template <bool EARLY, bool WT>
 __global__ __launch_bounds__(256, 6) void k_and2_words(DenseParams p) {
     __shared__ __align__(16) uint16_t stage[4][AW_K][AW_STAGE + 8];      // (+ the flush's read-ahead)
     __shared__ uint32_t wcnt[4];
@@ -162,9 +201,9 @@ __global__ __launch_bounds__(256, 6) void k_and2_words(DenseParams p) {
     if (wv == 1u && lb_is_leader(g, gridDim.x)) {            // the group's ids, as soon as its other members have published theirs
         if (!lb_group_publish(p.lb, g, total) && l == 0) { wg_err = 1u; lb_fail(p.lb); }
     }
-    // ---- while the record travels: the first round of every chunk into its stage
+    // ---- while the record travels: the first round of every chunk (EARLY: of chunk 0) into its stage
 #pragma unroll
-    for (uint32_t c = 0; c < AW_K; c++) aw_stage(stage[wv][c], L[c], 0u);
+    for (uint32_t c = 0; c < (EARLY ? 1u : AW_K); c++) aw_stage(stage[wv][c], L[c], 0u);
     II2_STAMP(2)              // stage, first rounds
     // ---- the ids of all workgroups before mine (wave 0)
     if (wv == 0u) {
@@ -185,24 +224,37 @@ __global__ __launch_bounds__(256, 6) void k_and2_words(DenseParams p) {
         *p.d_count = anyerr ? ~0ull : wg_off + total;
         if (p.lb.spin == LB_SPIN_LATE) lb_late_done(p.lb);
     }
-    // ---- out: chunk by chunk, round by round (a chunk's first round is staged already: staging it again places nothing)
+    // ---- out: chunk by chunk, round by round (a round that is staged already: staging it again places nothing).  EARLY: chunk
+    // 1's first round is staged here, behind chunk 0's stores
     if (!err && count != 0u) {
         unsigned long long pos = wg_off + before;
         const uint32_t doc_wave = 32u * (p.w_lo + g * AW_W + wv * AW_WAVE);
+        // (WT) the workgroup's ids as a buffer: from its first id to its last one or to the capacity
+        const unsigned long long wgo = wg_off;
+        const uint32_t off_lo = aw_uni((uint32_t)wgo), off_hi = aw_uni((uint32_t)(wgo >> 32));
+        const unsigned long long base = ((unsigned long long)off_hi << 32) | off_lo;
+        const unsigned long long room = p.out_cap > base ? p.out_cap - base : 0ull;
+        const uint32_t lim = room < total ? (uint32_t)room : total;
+        const uint32_t mis = (uint32_t)((uintptr_t)(p.out + base) >> 2) & 3u;
+        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.out + base, 0, (int)(4u * lim), 0x00020000);
+        uint32_t rel = before;
 #pragma unroll
         for (uint32_t c = 0; c < AW_K; c++) {
             uint16_t *st = stage[wv][c];
             for (uint32_t rb = 0; rb < ctot[c]; rb += AW_STAGE) {
                 aw_stage(st, L[c], rb);
                 __builtin_amdgcn_wave_barrier();
+                if (c == 1u && rb == 0u) { II2_STAMP(5) }      // stage c1 (not EARLY: staged already)
                 const uint32_t n = ctot[c] - rb < AW_STAGE ? ctot[c] - rb : AW_STAGE;
-                aw_flush(p, st, n, doc_wave + 32u * AW_CHUNK * c, pos + rb);
+                if (WT) aw_flush_wt(st, n, doc_wave + 32u * AW_CHUNK * c, rs, rel + rb, lim, mis);
+                else aw_flush(p, st, n, doc_wave + 32u * AW_CHUNK * c, pos + rb);
                 __builtin_amdgcn_wave_barrier();
             }
             pos += ctot[c];
+            rel += ctot[c];
+            if (c == 0u) { II2_STAMP(4) } else { II2_STAMP(6) }   // flush c0 / flush c1 (and the staging of rounds behind the first)
         }
     }
-    II2_STAMP(4)              // flush (and the staging of rounds behind the first)
     if (stamps && l == 0)
         for (int i = 0; i < 8; i++) atomicAdd(&p.debug[(uint64_t)(blockIdx.x % 2048u) * 8u + i], tacc[i]);
 #undef II2_STAMP
@@ -220,7 +272,11 @@ uint32_t and2_words_plan(DenseParams &p) {
 
 hipError_t launch_and2_words(const DenseParams &p, hipStream_t s) {
     const uint32_t grid = p.w_n ? (p.w_n + AW_W - 1u) / AW_W : 1u;
-    hipLaunchKernelGGL(k_and2_words, dim3(grid), dim3(256), 0, s, p);
+    const dim3 gd(grid), bd(256);
+#define II2_AW(E, W) hipLaunchKernelGGL((k_and2_words<E, W>), gd, bd, 0, s, p)
+    if (p.words_early) { if (p.words_store) II2_AW(true, true); else II2_AW(true, false); }
+    else { if (p.words_store) II2_AW(false, true); else II2_AW(false, false); }
+#undef II2_AW
     return hipGetLastError();
 }
 

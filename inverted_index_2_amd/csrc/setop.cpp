@@ -397,6 +397,8 @@ static int intersect_dense(ii2_ctx *ctx, const SetList *L, uint32_t n, double pe
                 return rcf;
         dp.a_bits = fa.bits; dp.a_origin = fa.origin; dp.a_nwords = fa.n_words;
         dp.b_bits = fb.bits; dp.b_origin = fb.origin; dp.b_nwords = fb.n_words;
+        dp.words_store = ctx->opt_and2_words_store != 0 ? 1u : 0u;
+        dp.words_early = ctx->opt_and2_words_order == 1 ? 1u : 0u;
         dp.and2_tiles = dp.a_bits ? and2_tiles_pick(ctx, dp.n_meta / 4u) : 1u;
         // one launch: the look-back records - one per workgroup of the kernel that runs - live in a buffer of their own (only
         // these kernels write it, every word tagged with its launch's number: nothing to clear between launches)
