@@ -19,7 +19,8 @@
 //   k_match_place  reads the match words, not the terms: the j-th start of a pair writes run_first / run_dict at j, the j-th
 //                  end writes run_end at j - they belong to one run.  Launched only when the total fits the caller's cap.
 // Everything behind the match word - the counting of run starts and ends (match_runs_tail), the scans, the two kernels under them
-// and the copies (match_runs_drive) - is shared with ii2_dict_fuzzy (dict_fuzzy.hip) through match_runs.h and defined here.
+// and the copies (match_runs_drive) - is shared with ii2_dict_fuzzy (dict_fuzzy.hip) through match_runs.h and defined here; so is
+// everything in front of it but the matcher: the patterns' copy, the stage (TermStage) and the entry point's frame (match_call).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -42,40 +43,18 @@ __global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const M
                                                            uint64_t *__restrict__ words, uint32_t *__restrict__ tab_st, uint32_t *__restrict__ tab_en) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[MATCH_STAGE];
     __shared__ __attribute__((aligned(16))) MatchPattern lp[II2_MATCH_MAX_PATTERNS];
-    const uint32_t tid = threadIdx.x, wg = blockIdx.x;
-    const uint32_t s = match_dict_of(d, wg), n = d.n[s], P = d.n_patterns;
-    const uint64_t *__restrict__ off = d.off[s];
-    const uint8_t *__restrict__ bytes = d.bytes[s];
-    const uint32_t t0 = (wg - d.wg_first[s]) * DM_THREADS, t1 = min(t0 + DM_THREADS, n);      // t0 < n
-    {       // the patterns: 88 bytes each, word by word
-        const uint32_t *src = (const uint32_t *)pats;
-        uint32_t *dst = (uint32_t *)lp;
-        for (uint32_t i = tid; i < P * (uint32_t)(sizeof(MatchPattern) / 4); i += DM_THREADS) dst[i] = src[i];
-    }
-    // The stage holds the workgroup's own terms when they fit - and the two neighbours across its edges as well when those fit
-    // too (`wide`).  The dictionary's bytes are 256-byte aligned and padded by 16: every 16-byte load from a multiple of 16 up to
-    // the one that covers the span's last byte stays inside.  (All of this is workgroup-uniform.)
-    const uint32_t tl = t0 > 0 ? t0 - 1u : t0, tr = t1 < n ? t1 + 1u : t1;
-    const uint64_t b0 = off[t0], b1 = off[t1], bl = off[tl], br = off[tr];
-    const bool staged = stage_on && b1 - (b0 & ~15ull) <= MATCH_STAGE;
-    const bool wide = staged && br - (bl & ~15ull) <= MATCH_STAGE;
-    const uint64_t a0 = (wide ? bl : b0) & ~15ull, a1 = wide ? br : b1;
-    if (staged)
-        for (uint64_t i = (uint64_t)tid * 16u; a0 + i < a1; i += DM_THREADS * 16u)
-            *(uint4 *)(stage + i) = *(const uint4 *)(bytes + a0 + i);
+    const uint32_t wg = blockIdx.x, s = match_dict_of(d, wg), P = d.n_patterns;
+    match_patterns_to_lds(lp, pats, P);                 // 88 bytes each
+    const TermStage ts(d, s, wg, stage_on, stage);
     __syncthreads();
-    const uint32_t t = t0 + tid;
+    const uint32_t t = ts.t0 + threadIdx.x;
     uint64_t m = 0;
-    if (t < t1) {
-        const uint64_t b = off[t], len = off[t + 1] - b;
-        m = staged ? match_word(lp, P, stage + (b - a0), len) : match_word(lp, P, bytes + b, len);
+    if (t < ts.t1) {
+        m = ts.own(t, [&](const uint8_t *term, uint64_t len) { return match_word(lp, P, term, len); });
         words[d.term_first[s] + t] = m;
     }
-    // (no neighbour before a dictionary's first term or behind its last)
-    match_runs_tail<1>(P, wg, n_wg, t0 > 0, t1 < n, m, 0u, staged, [&](uint32_t right, uint32_t p) {
-        const uint32_t tn = right ? t1 : tl;
-        const uint64_t b = off[tn], len = off[tn + 1] - b;
-        return wide ? match_term(lp[p], stage + (b - a0), len) : match_term(lp[p], bytes + b, len);
+    match_runs_tail<1>(P, wg, n_wg, ts.have_left, ts.have_right, m, 0u, ts.staged, [&](uint32_t right, uint32_t p) {
+        return ts.neighbour(right, [&](const uint8_t *term, uint64_t len) { return match_term(lp[p], term, len); });
     }, tab_st, tab_en);
 }
 
@@ -210,57 +189,23 @@ extern "C" {
 int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes, const uint64_t *pat_off,
                    const uint8_t *pat_kind, uint64_t *run_off, uint64_t *run_first, uint64_t *run_end, uint32_t *run_dict, uint64_t cap,
                    ii2_match_stats *stats) {
-    if (!ctx || !dicts || k == 0 || k > II2_MAX_LISTS) return fail(ctx, II2_EINVAL, "ii2_dict_match: bad argument");
-    if (n_patterns > II2_MATCH_MAX_PATTERNS) return fail(ctx, II2_ERANGE, "ii2_dict_match: more than 64 patterns in one call");
-    if (n_patterns && (!pat_bytes || !pat_off || !pat_kind || !run_off || (cap && (!run_first || !run_end))))
-        return fail(ctx, II2_EINVAL, "ii2_dict_match: an array is NULL");
-    std::lock_guard<std::mutex> g(ctx->mu);
-    MatchDicts md;
-    std::memset(&md, 0, sizeof md);
-    md.k = k;
-    md.n_patterns = n_patterns;
-    for (uint32_t s = 0; s < k; s++) {
-        if (!dicts[s] || dicts[s]->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_dict_match: a dictionary is NULL or lives on another device");
-        if (dicts[s]->n >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_dict_match: a dictionary of 2^31 or more terms");
-        md.off[s] = dicts[s]->d_off; md.bytes[s] = dicts[s]->d_bytes;
-        md.n[s] = (uint32_t)dicts[s]->n;
-        md.wg_first[s + 1] = md.wg_first[s] + (md.n[s] + DM_THREADS - 1) / DM_THREADS;
-        md.term_first[s + 1] = md.term_first[s] + md.n[s];
-    }
-    std::vector<MatchPattern> pats(n_patterns);
-    if (n_patterns && pat_off[0] != 0) return fail(ctx, II2_EINVAL, "ii2_dict_match: pat_off must start at 0 and be non-decreasing");
-    for (uint32_t p = 0; p < n_patterns; p++) {
-        if (pat_off[p + 1] < pat_off[p]) return fail(ctx, II2_EINVAL, "ii2_dict_match: pat_off must start at 0 and be non-decreasing");
-        const int rc = match_parse(pat_kind[p], pat_bytes + pat_off[p], pat_off[p + 1] - pat_off[p], &pats[p]);
-        if (rc == II2_ERANGE) return fail(ctx, rc, "ii2_dict_match: a pattern of more than 64 bytes");
-        if (rc) return fail(ctx, rc, "ii2_dict_match: an unknown kind, or a glob that ends in a lone backslash");
-    }
-    const uint64_t n_pairs = (uint64_t)n_patterns * k, n_terms = md.term_first[k];
-    const uint32_t n_wg = md.wg_first[k];
-    if (n_patterns == 0 || n_wg == 0) {        // nothing to scan: no pattern, or no term in any dictionary
-        for (uint64_t i = 0; run_off && i <= n_pairs; i++) run_off[i] = 0;
-        if (stats) { std::memset(stats, 0, sizeof *stats); stats->n_terms = n_patterns ? n_terms : 0; }
-        return II2_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    uint64_t n_runs = 0, counters[2] = {0, 0};          // {matched pairs, staged workgroups}
-    const int rc = match_runs_drive(ctx, "ii2_dict_match", md, 1, n_patterns * sizeof(MatchPattern),
-                                    [&](void *head, uint64_t *d_words, uint32_t *d_tab_st, uint32_t *d_tab_en) -> int {
-        HIP_TRY(ctx, hipMemcpyAsync(head, pats.data(), n_patterns * sizeof(MatchPattern), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, st, md, (const MatchPattern *)head, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words,
-                           d_tab_st, d_tab_en);
-        HIP_TRY(ctx, hipGetLastError());
-        return II2_OK;
-    }, MatchRunsOut{run_off, run_first, run_end, run_dict, cap}, &n_runs, counters);
-    if (rc && rc != II2_ECAPACITY) return rc;
-    if (stats) {
-        stats->n_terms = n_terms;
-        stats->n_matched = counters[0];
-        stats->n_runs = n_runs;
-        stats->n_staged = (uint32_t)counters[1];
-        stats->n_global = n_wg - stats->n_staged;
-    }
+    static const MatchCallTexts texts = {"ii2_dict_match", II2_MATCH_MAX_PATTERNS, "ii2_dict_match: more than 64 patterns in one call",
+                                         "ii2_dict_match: a pattern of more than 64 bytes",
+                                         "ii2_dict_match: an unknown kind, or a glob that ends in a lone backslash"};
+    MatchSums sums;                                     // one counter row: {matched pairs, staged workgroups}
+    const int rc = match_call<MatchPattern>(ctx, texts, MatchCallIn{k, dicts, n_patterns, pat_bytes, pat_off, pat_kind},
+                                            MatchRunsOut{run_off, run_first, run_end, run_dict, cap}, stats, 1,
+        [&](uint32_t p, const uint8_t *bytes, uint64_t len, MatchPattern *out) { return match_parse(pat_kind[p], bytes, len, out); },
+        [&](const MatchDicts &md, const MatchPattern *d_pats, uint32_t n_wg, uint64_t *d_words, uint32_t *d_tab_st, uint32_t *d_tab_en) {
+            hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, ctx->stream, md, d_pats, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words, d_tab_st,
+                               d_tab_en);
+        }, &sums);
+    if ((rc && rc != II2_ECAPACITY) || !sums.n_wg || !stats) return rc;
+    stats->n_terms = sums.n_terms;
+    stats->n_matched = sums.counters[0];
+    stats->n_runs = sums.n_runs;
+    stats->n_staged = (uint32_t)sums.counters[1];
+    stats->n_global = sums.n_wg - stats->n_staged;
     return rc;
 }
 

@@ -42,6 +42,33 @@ def _ptr(a) -> C.c_void_p:
     raise TypeError(type(a))
 
 
+def _flat(byte_strings):
+    """(blob, off) of a list of bytes as the ABI takes them: u8 bytes, padded by one so that the array is never empty, and u64
+    offsets [n + 1] from 0."""
+    off = np.zeros(len(byte_strings) + 1, np.uint64)
+    if byte_strings:
+        off[1:] = np.cumsum([len(t) for t in byte_strings])
+    return np.frombuffer(b"".join(byte_strings) + b"\0", dtype=np.uint8).copy(), off
+
+
+def _flat_dicts(dictionaries):
+    """(flat, blob, off, first) of k dictionaries (lists of bytes): all their terms in one list, those flattened (_flat), and
+    the u64 first term of each dictionary [k + 1]."""
+    flat = [t for d in dictionaries for t in d]
+    first = np.zeros(len(dictionaries) + 1, np.uint64)
+    first[1:] = np.cumsum([len(d) for d in dictionaries])
+    return (flat, *_flat(flat), first)
+
+
+def _per_pattern(v, n, who, what):
+    """A per-pattern u8 argument of `who`: one value for all the n patterns (a Python or numpy integer) or one per pattern;
+    `what` names it in the error, as in "kind per pattern"."""
+    a = np.full(n, int(v), np.uint8) if isinstance(v, (int, np.integer)) else _np(v, np.uint8)
+    if a.size != n:
+        raise ValueError(f"{who}: one {what}")
+    return a
+
+
 _BATCH_OPS = {"and": II2_OP_AND, "or": II2_OP_OR}
 
 
@@ -409,13 +436,7 @@ class Context:
     def align_terms(self, dictionaries) -> "Alignment":
         """k sorted, duplicate-free term dictionaries (lists of bytes) -> their union, on the device (the k-way term walk of
         makeIterator, shard.go:253-278, in bytes.Compare order)."""
-        flat = [t for d in dictionaries for t in d]
-        off = np.zeros(len(flat) + 1, np.uint64)
-        if flat:
-            off[1:] = np.cumsum([len(t) for t in flat])
-        blob = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8).copy()
-        first = np.zeros(len(dictionaries) + 1, np.uint64)
-        first[1:] = np.cumsum([len(d) for d in dictionaries])
+        flat, blob, off, first = _flat_dicts(dictionaries)
         h = C.c_void_p()
         self._ck(self.lib.ii2_align_terms(self.h, len(dictionaries), _ptr(blob), _ptr(off), _ptr(first), C.byref(h)))
         return Alignment(self, h, flat)
@@ -430,11 +451,7 @@ class Context:
     def dictionary(self, terms) -> "Dictionary":
         """A segment's sorted, duplicate-free term dictionary (list of bytes), made resident in HBM (ii2_dict_create)."""
         terms = list(terms)
-        off = np.zeros(len(terms) + 1, np.uint64)
-        if terms:
-            off[1:] = np.cumsum([len(t) for t in terms])
-        blob = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
-        return self.dictionary_flat(blob, off, terms)
+        return self.dictionary_flat(*_flat(terms), terms)
 
     def dictionary_flat(self, term_bytes, term_off, terms=None) -> "Dictionary":
         """Same, from flat arrays: u8 bytes and u64 offsets [n + 1] starting at 0."""
@@ -450,11 +467,7 @@ class Context:
         with II2_DEVICE.  Returns (Dictionary, term_id, DictBuildStats): term_id is a u32 numpy array, or with II2_DEVICE a
         DeviceArray that ii2_seg_build takes as its list_id (None with want_ids=False)."""
         if term_off is None:
-            terms = list(terms)
-            term_off = np.zeros(len(terms) + 1, np.uint64)
-            if terms:
-                term_off[1:] = np.cumsum([len(t) for t in terms])
-            terms = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
+            terms, term_off = _flat(list(terms))
             where = II2_HOST
         if where == II2_HOST:
             terms, term_off = _np(terms, np.uint8), _np(term_off, np.uint64)
@@ -477,13 +490,8 @@ class Context:
         Returns (list_first, list_end, n_found): u64 arrays of shape (len(terms), k) and the number of non-empty ranges.  Row p,
         flattened with the k segments repeated, is one group of the range entry points."""
         terms = list(terms)
-        off = np.zeros(len(terms) + 1, np.uint64)
-        if terms:
-            off[1:] = np.cumsum([len(t) for t in terms])
-        blob = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
-        flags = np.full(len(terms), 1 if prefix else 0, np.uint8) if isinstance(prefix, (bool, int)) else _np(prefix, np.uint8)
-        if flags.size != len(terms):
-            raise ValueError("dict_find: one prefix flag per term")
+        blob, off = _flat(terms)
+        flags = _per_pattern(bool(prefix) if isinstance(prefix, (int, np.integer)) else prefix, len(terms), "dict_find", "prefix flag per term")
         first, end, found = self.dict_find_flat(dicts, blob, off, flags, II2_HOST)
         return first.reshape(len(terms), len(dicts)), end.reshape(len(terms), len(dicts)), found
 
@@ -515,18 +523,18 @@ class Context:
         [run_first[j], run_end[j]) of dictionary run_dict[j]; the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1,
         are one group of the range entry points.  A result that outgrows the first buffer takes a second call of the exact size."""
         patterns = list(patterns)
-        kinds = np.full(len(patterns), int(kind), np.uint8) if isinstance(kind, (int, np.integer)) else _np(kind, np.uint8)
-        if kinds.size != len(patterns):
-            raise ValueError("dict_match: one kind per pattern")
-        off = np.zeros(len(patterns) + 1, np.uint64)
-        if patterns:
-            off[1:] = np.cumsum([len(p) for p in patterns])
-        blob = np.frombuffer(b"".join(patterns) + b"\0", dtype=np.uint8).copy()
-        run_off = np.zeros(len(patterns) * len(dicts) + 1, np.uint64)
+        kinds = _per_pattern(kind, len(patterns), "dict_match", "kind per pattern")
+        blob, off = _flat(patterns)
+        return self._dict_runs(dicts, len(patterns), lambda *out: self.dict_match_flat(dicts, blob, off, kinds, *out))
+
+    def _dict_runs(self, dicts, n_patterns, flat_call):
+        """The two-call protocol of dict_match and dict_fuzzy: flat_call(run_off, run_first, run_end, run_dict, cap) -> (return
+        code, stats) with a first buffer of 4096 runs, and where the result outgrows it once more with the exact size."""
+        run_off = np.zeros(n_patterns * len(dicts) + 1, np.uint64)
         cap = 4096
         while True:
             first, end, which = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
-            rc, st = self.dict_match_flat(dicts, blob, off, kinds, run_off, first, end, which, cap)
+            rc, st = flat_call(run_off, first, end, which, cap)
             if rc != -4 or int(run_off[-1]) <= cap:      # II2_ECAPACITY: run_off is filled, the second call is exact
                 self._ck(rc)
                 n = int(run_off[-1])
@@ -552,28 +560,10 @@ class Context:
         out as dict_match's: the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1, are one group of the range
         entry points.  A result that outgrows the first buffer takes a second call of the exact size."""
         patterns = list(patterns)
-
-        def per_pattern(v, what):
-            a = np.full(len(patterns), int(v), np.uint8) if isinstance(v, (int, np.integer)) else _np(v, np.uint8)
-            if a.size != len(patterns):
-                raise ValueError(f"dict_fuzzy: one {what} per pattern")
-            return a
-
-        dist, pre, fl = per_pattern(max_dist, "max_dist"), per_pattern(prefix, "prefix"), per_pattern(flags, "flags")
-        off = np.zeros(len(patterns) + 1, np.uint64)
-        if patterns:
-            off[1:] = np.cumsum([len(p) for p in patterns])
-        blob = np.frombuffer(b"".join(patterns) + b"\0", dtype=np.uint8).copy()
-        run_off = np.zeros(len(patterns) * len(dicts) + 1, np.uint64)
-        cap = 4096
-        while True:
-            first, end, which = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
-            rc, st = self.dict_fuzzy_flat(dicts, blob, off, dist, pre, fl, run_off, first, end, which, cap)
-            if rc != -4 or int(run_off[-1]) <= cap:      # II2_ECAPACITY: run_off is filled, the second call is exact
-                self._ck(rc)
-                n = int(run_off[-1])
-                return run_off, first[:n], end[:n], which[:n], st
-            cap = int(run_off[-1])
+        dist, pre, fl = (_per_pattern(v, len(patterns), "dict_fuzzy", what + " per pattern")
+                         for v, what in ((max_dist, "max_dist"), (prefix, "prefix"), (flags, "flags")))
+        blob, off = _flat(patterns)
+        return self._dict_runs(dicts, len(patterns), lambda *out: self.dict_fuzzy_flat(dicts, blob, off, dist, pre, fl, *out))
 
     def dict_fuzzy_flat(self, dicts, pat_bytes, pat_off, pat_dist, pat_prefix, pat_flags, run_off, run_first, run_end, run_dict, cap: int,
                         n_patterns=None):
@@ -882,13 +872,7 @@ class Context:
         """The common Shard.Merge in one launch (ii2_merge_small): k small segments with their term dictionaries (lists of
         bytes, segs[s] holding one list per term of dictionaries[s]) and RemovedLists.Values().  Returns (merged Segment or
         None, its terms, MergeStats)."""
-        flat = [t for d in dictionaries for t in d]
-        off = np.zeros(len(flat) + 1, np.uint64)
-        if flat:
-            off[1:] = np.cumsum([len(t) for t in flat])
-        blob = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8).copy()
-        first = np.zeros(len(dictionaries) + 1, np.uint64)
-        first[1:] = np.cumsum([len(d) for d in dictionaries])
+        flat, blob, off, first = _flat_dicts(dictionaries)
         rem = _np(removed, np.uint32)
         arr = (C.c_void_p * len(segs))(*[s.h for s in segs])
         out = C.c_void_p()
@@ -903,13 +887,7 @@ class Context:
     def read_small(self, segs: Sequence["Segment"], dictionaries, list_first=None):
         """The small Shard.Read in one launch (ii2_read_small): the merged lists of k small segments (dictionaries[s] names the
         lists list_first[s] .. of segs[s]) on the host.  Returns (terms, post_off, values)."""
-        flat = [t for d in dictionaries for t in d]
-        off = np.zeros(len(flat) + 1, np.uint64)
-        if flat:
-            off[1:] = np.cumsum([len(t) for t in flat])
-        blob = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8).copy()
-        first = np.zeros(len(dictionaries) + 1, np.uint64)
-        first[1:] = np.cumsum([len(d) for d in dictionaries])
+        flat, blob, off, first = _flat_dicts(dictionaries)
         lf = _np(list_first, np.uint64) if list_first is not None else None
         arr = (C.c_void_p * len(segs))(*[s.h for s in segs])
         cap = int(sum(s.info.n_postings for s in segs))
@@ -1009,13 +987,7 @@ def seg_gather_plan(shapes):
 def align_plan(dictionaries) -> _lib.AlignPlan:
     """Host arithmetic of the alignment (ii2_align_plan, no GPU): the brackets the ranking kernel would bisect for these k sorted,
     duplicate-free dictionaries (lists of bytes) - how many in LDS, in global memory and empty - and its constants."""
-    flat = [t for d in dictionaries for t in d]
-    off = np.zeros(len(flat) + 1, np.uint64)
-    if flat:
-        off[1:] = np.cumsum([len(t) for t in flat])
-    blob = np.frombuffer(b"".join(flat) + b"\0", dtype=np.uint8)
-    first = np.zeros(len(dictionaries) + 1, np.uint64)
-    first[1:] = np.cumsum([len(d) for d in dictionaries])
+    _, blob, off, first = _flat_dicts(dictionaries)
     plan = _lib.AlignPlan()
     rc = _lib.load().ii2_align_plan(len(dictionaries), _ptr(blob), _ptr(off), _ptr(first), C.byref(plan))
     if rc:

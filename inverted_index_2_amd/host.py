@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .engine import Context
+from .engine import Context, _flat
 
 vp = C.c_void_p
 u64p = C.POINTER(C.c_uint64)
@@ -97,14 +97,6 @@ def _lib_typed():
     return lib
 
 
-def _pack(terms: List[bytes]):
-    off = np.zeros(len(terms) + 1, np.uint64)
-    if terms:
-        off[1:] = np.cumsum([len(t) for t in terms])
-    blob = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8).copy()
-    return blob, off
-
-
 def union_bound(range_seg, seg_postings) -> int:
     """For the tests, no device: the output bound prefix_search and match_search give one name whose range i lies in segment
     `range_seg[i]`, segment s holding `seg_postings[s]` postings - every distinct segment counted once, however many ranges."""
@@ -151,7 +143,7 @@ class _Target:
             pass
 
     def put(self, terms: List[bytes], val: int) -> None:
-        blob, off = _pack(list(terms))
+        blob, off = _flat(list(terms))
         self._ck(self.lib.ii2h_put(self.h, blob.ctypes.data, off.ctypes.data, len(terms), val))
 
     def set_build(self, mode: int) -> None:
@@ -164,7 +156,7 @@ class _Target:
         """Many puts at once, docs = [(terms, val), ...]: one merged-quality segment per shard that receives a term (PutBatch:
         one ii2_seg_build call each) instead of one direct segment per put."""
         docs = [(list(terms), int(val)) for terms, val in docs]
-        blob, off = _pack([t for terms, _ in docs for t in terms])
+        blob, off = _flat([t for terms, _ in docs for t in terms])
         doc_first = np.zeros(len(docs) + 1, np.uint64)
         if docs:
             doc_first[1:] = np.cumsum([len(terms) for terms, _ in docs])
@@ -202,7 +194,7 @@ class _Target:
         every shard); a pattern that matches no term has no entry.  kind: II2_MATCH_CONTAINS (0) / SUFFIX (1) / GLOB (2),
         optionally | II2_MATCH_NOCASE (0x80), for all the patterns; any number of patterns (the device call takes 64 at a time).
         Like read, no tombstone filter."""
-        blob, off = _pack(list(patterns))
+        blob, off = _flat(list(patterns))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_match_search(self.h, blob.ctypes.data, off.ctypes.data, len(patterns), int(kind), C.byref(n)))
         return dict(self._results(n.value))
@@ -219,7 +211,7 @@ class _Target:
         (of every shard); a query term that matches nothing has no entry.  prefix: leading bytes a term must share with the query
         term (a shorter query term is compared as a whole); flags: II2_FUZZY_TRANSPOSE (1) and / or II2_MATCH_NOCASE (0x80); any
         number of query terms (the device call takes 16 at a time).  Like read, no tombstone filter."""
-        blob, off = _pack(list(terms))
+        blob, off = _flat(list(terms))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_fuzzy_search(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(max_dist), int(prefix), int(flags), C.byref(n)))
         return dict(self._results(n.value))
@@ -287,13 +279,13 @@ class InvertedIndex(_Target):
         return self.lib.ii2h_second_calls(self.h)
 
     def prefix_search(self, prefixes: List[bytes]) -> Dict[bytes, List[int]]:
-        blob, off = _pack(list(prefixes))
+        blob, off = _flat(list(prefixes))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_prefix_search(self.h, blob.ctypes.data, off.ctypes.data, len(prefixes), C.byref(n)))
         return dict(self._results(n.value))
 
     def intersect(self, terms: List[bytes]) -> List[int]:
-        blob, off = _pack(list(terms))
+        blob, off = _flat(list(terms))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect(self.h, blob.ctypes.data, off.ctypes.data, len(terms), C.byref(n)))
         out = np.zeros(max(n.value, 1), np.uint32)
@@ -302,8 +294,8 @@ class InvertedIndex(_Target):
 
     def intersect_except(self, terms: List[bytes], exclude: List[bytes]) -> List[int]:
         """ids under every term of `terms` and under no term of `exclude` (IntersectExcept: one ii2_andnot_ranges call)."""
-        blob, off = _pack(list(terms))
-        x_blob, x_off = _pack(list(exclude))
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_except(self.h, blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data, x_off.ctypes.data,
                                                 len(exclude), C.byref(n)))
@@ -314,8 +306,8 @@ class InvertedIndex(_Target):
     def intersect_at_least(self, terms: List[bytes], min_match: int, exclude: List[bytes] = ()) -> List[int]:
         """ids under at least `min_match` of `terms` and under no term of `exclude` (IntersectAtLeast: one ii2_atleast_ranges call);
         a term found in no segment matches no doc."""
-        blob, off = _pack(list(terms))
-        x_blob, x_off = _pack(list(exclude))
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_at_least(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(min_match), x_blob.ctypes.data,
                                                   x_off.ctypes.data, len(exclude), C.byref(n)))
@@ -326,8 +318,8 @@ class InvertedIndex(_Target):
     def intersect_top(self, terms: List[bytes], k: int, min_match: int = 1, exclude: List[bytes] = ()) -> List[Tuple[int, int]]:
         """the `k` ids under the most of `terms` - at least `min_match` of them, under no term of `exclude` - as (id, score) pairs,
         score descending, then id ascending (IntersectTop: one ii2_topk_ranges call); a term found in no segment matches no doc."""
-        blob, off = _pack(list(terms))
-        x_blob, x_off = _pack(list(exclude))
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_top(self.h, blob.ctypes.data, off.ctypes.data, len(terms), int(k), int(min_match), x_blob.ctypes.data,
                                              x_off.ctypes.data, len(exclude), C.byref(n)))
@@ -343,8 +335,8 @@ class InvertedIndex(_Target):
         in no segment keeps its slot and matches no doc."""
         if len(weights) != len(terms):
             raise ValueError("intersect_top_weighted: one weight per term")
-        blob, off = _pack(list(terms))
-        x_blob, x_off = _pack(list(exclude))
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
         w = np.asarray(list(weights) + [0], np.uint32)
         n = C.c_uint64()
         self._ck(self.lib.ii2h_intersect_top_weighted(self.h, blob.ctypes.data, off.ctypes.data, len(terms), w.ctypes.data, int(k), int(min_score),
@@ -359,7 +351,7 @@ class InvertedIndex(_Target):
         ii2_query_batch_groups call - a second one when the results exceed its first buffer - and one download); result q is
         that of intersect_except(*queries[q])."""
         queries = [(list(t), list(x)) for t, x in queries]
-        blob, off = _pack([term for t, x in queries for term in t + x])
+        blob, off = _flat([term for t, x in queries for term in t + x])
         q_first = np.zeros(len(queries) + 1, np.uint64)
         q_first[1:] = np.cumsum([len(t) + len(x) for t, x in queries], dtype=np.uint64) if queries else []
         q_req = np.array([len(t) for t, _ in queries], np.uint64)
@@ -376,7 +368,7 @@ class InvertedIndex(_Target):
         for q, (t, w, _, _, _) in enumerate(queries):
             if len(w) != len(t):
                 raise ValueError(f"intersect_top_batch: query {q}: one weight per term")
-        blob, off = _pack([term for t, _, _, _, x in queries for term in t + x])
+        blob, off = _flat([term for t, _, _, _, x in queries for term in t + x])
         q_first = np.zeros(len(queries) + 1, np.uint64)
         q_first[1:] = np.cumsum([len(t) + len(x) for t, _, _, _, x in queries], dtype=np.uint64) if queries else []
         q_req = np.array([len(t) for t, _, _, _, _ in queries], np.uint64)
@@ -400,8 +392,8 @@ class InvertedIndex(_Target):
         segment): for every term that starts with `prefix`, the number of distinct docs under it among
         intersect_except(terms, exclude); terms with count 0 are left out.  Without `terms` the doc set is every doc: the
         document frequency of each term under the prefix."""
-        blob, off = _pack(list(terms))
-        x_blob, x_off = _pack(list(exclude))
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
         pre = np.frombuffer(bytes(prefix) + b"\0", dtype=np.uint8).copy()
         n = C.c_uint64()
         self._ck(self.lib.ii2h_term_counts(self.h, pre.ctypes.data, len(prefix), blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data,
@@ -434,7 +426,7 @@ class SegmentFiles(_Target):
 
     def write(self, directory: str, term_values: List[Tuple[bytes, List[int]]], direct: bool = False) -> str:
         """NewWriter / NewDirectWriter + Append for every (term, values) + Close; returns GetKey()."""
-        blob, off = _pack([t for t, _ in term_values])
+        blob, off = _flat([t for t, _ in term_values])
         po = np.zeros(len(term_values) + 1, np.uint64)
         if term_values:
             po[1:] = np.cumsum([len(v) for _, v in term_values])

@@ -235,18 +235,18 @@ template <class TwoCall> static std::map<Term, std::vector<uint32_t>> or_per_nam
     return out;
 }
 
-// ---- substring, suffix and wildcard search (additive: the reference's FST walks a term from its front only) ----
-// fn(pattern index, segment, j0, j1) for every run [j0, j1) of consecutive terms of every segment that pattern `patterns[p]` of
-// `kind` (II2_MATCH_*) matches: ii2_dict_match over the segments' resident dictionaries, in chunks of at most II2_MAX_LISTS
-// dictionaries and II2_MATCH_MAX_PATTERNS patterns - no host pass over the terms.  Per pattern the runs come segment by
-// segment, ascending inside one.  A result above the first buffer takes the second call ii2_dict_match asks for.
-template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t kind,
-                                           Fn fn) {
-    for (size_t p0 = 0; p0 < patterns.size(); p0 += II2_MATCH_MAX_PATTERNS) {
-        const size_t np = std::min<size_t>(II2_MATCH_MAX_PATTERNS, patterns.size() - p0);
+// ---- term search over the resident dictionaries: what substring and typo-tolerant search share ----
+// fn(pattern index, segment, j0, j1) for every run [j0, j1) of consecutive terms of every segment that `patterns[p]` matches,
+// with no host pass over the terms: the segments' resident dictionaries in chunks of at most II2_MAX_LISTS, the patterns in
+// chunks of at most max_patterns.  call(p0, np, k, dicts, bytes, off, run_off, first, end, which, cap) makes the ABI call for
+// patterns [p0, p0 + np) - its per-pattern arrays are its own - and returns its code; a result above the first buffer takes the
+// second call that II2_ECAPACITY asks for.  Per pattern the runs come segment by segment, ascending inside one.
+template <class Call, class Fn> static void term_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns,
+                                                      size_t max_patterns, const char *what, Call call, Fn fn) {
+    for (size_t p0 = 0; p0 < patterns.size(); p0 += max_patterns) {
+        const size_t np = std::min(max_patterns, patterns.size() - p0);
         std::vector<uint8_t> bytes;
         std::vector<uint64_t> off(np + 1, 0);
-        const std::vector<uint8_t> kinds(np, (uint8_t)kind);
         for (size_t p = 0; p < np; p++) {
             bytes.insert(bytes.end(), patterns[p0 + p].begin(), patterns[p0 + p].end());
             off[p + 1] = bytes.size();
@@ -263,10 +263,9 @@ template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::
                 first.resize(cap);
                 end.resize(cap);
                 which.resize(cap);
-                const int rc = ii2_dict_match(ctx, (uint32_t)k, dicts.data(), (uint32_t)np, bytes.data(), off.data(), kinds.data(), run_off.data(), first.data(),
-                                              end.data(), which.data(), cap, nullptr);
+                const int rc = call(p0, np, (uint32_t)k, dicts.data(), bytes.data(), off.data(), run_off.data(), first.data(), end.data(), which.data(), cap);
                 if (rc != II2_ECAPACITY || attempt) {
-                    ck(ctx, rc, "match search");
+                    ck(ctx, rc, what);
                     break;
                 }
                 cap = run_off.back();
@@ -276,20 +275,38 @@ template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::
         }
     }
 }
-// map<pattern, ids> over `segs`: every pattern's runs, then one OR query per pattern (or_per_name).  A pattern that matches no
-// term has no entry.  No tombstone filter, as in Read.
-template <class TwoCall> static std::map<Term, std::vector<uint32_t>> match_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
-                                                                                   std::vector<Term> patterns, uint32_t kind, TwoCall two_call) {
+// map<pattern, ids>: the distinct patterns' runs - runs(patterns, fn) is match_runs or fuzzy_runs with its own arguments bound -
+// then ONE batch of OR queries, one per pattern (or_per_name).  A pattern that matches no term has no entry.  No tombstone
+// filter, as in Read.
+template <class Runs, class TwoCall> static std::map<Term, std::vector<uint32_t>> runs_search(ii2_ctx *ctx, std::vector<Term> patterns, const char *what,
+                                                                                              Runs runs, TwoCall two_call) {
     std::sort(patterns.begin(), patterns.end(), term_less);
     patterns.erase(std::unique(patterns.begin(), patterns.end()), patterns.end());
     std::map<Term, NamedRanges> found;
-    match_runs(ctx, segs, patterns, kind, [&](size_t p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+    runs(patterns, [&](size_t p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
         NamedRanges &r = found[patterns[p]];
         r.segs.push_back(sg->seg->h);
         r.first.push_back(j0);
         r.end.push_back(j1);
     });
-    return or_per_name(ctx, found, "match search", two_call);
+    return or_per_name(ctx, found, what, two_call);
+}
+
+// ---- substring, suffix and wildcard search (additive: the reference's FST walks a term from its front only) ----
+// term_runs for the patterns of `kind` (II2_MATCH_*): ii2_dict_match
+template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t kind,
+                                           Fn fn) {
+    term_runs(ctx, segs, patterns, II2_MATCH_MAX_PATTERNS, "match search",
+              [&](size_t, size_t np, uint32_t k, const ii2_dict *const *dicts, const uint8_t *bytes, const uint64_t *off, uint64_t *run_off, uint64_t *first,
+                  uint64_t *end, uint32_t *which, uint64_t cap) {
+                  const std::vector<uint8_t> kinds(np, (uint8_t)kind);
+                  return ii2_dict_match(ctx, k, dicts, (uint32_t)np, bytes, off, kinds.data(), run_off, first, end, which, cap, nullptr);
+              }, fn);
+}
+template <class TwoCall> static std::map<Term, std::vector<uint32_t>> match_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
+                                                                                   std::vector<Term> patterns, uint32_t kind, TwoCall two_call) {
+    return runs_search(ctx, std::move(patterns), "match search", [&](const std::vector<Term> &distinct, auto fn) { match_runs(ctx, segs, distinct, kind, fn); },
+                       two_call);
 }
 // the distinct terms of `segs` that the pattern matches, in bytes.Compare order, at most `limit`: read from the runs
 static std::vector<Term> match_terms(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const Term &pattern, uint32_t kind, uint64_t limit) {
@@ -304,64 +321,26 @@ static std::vector<Term> match_terms(ii2_ctx *ctx, const std::vector<std::shared
 }
 
 // ---- typo-tolerant search (additive: what the reference's dictionary library answers with a Levenshtein automaton) ----
-// fn(pattern index, segment, j0, j1) for every run [j0, j1) of consecutive terms of every segment that lie within `max_dist`
-// edits of `patterns[p]` and share its first `prefix` bytes (flags: II2_FUZZY_TRANSPOSE, II2_MATCH_NOCASE): ii2_dict_fuzzy over
-// the segments' resident dictionaries, in chunks of at most II2_MAX_LISTS dictionaries and II2_FUZZY_MAX_PATTERNS patterns - no
-// host pass over the terms.  A pattern shorter than the prefix is compared as a whole.  Per pattern the runs come segment by
-// segment, ascending inside one.  A result above the first buffer takes the second call ii2_dict_fuzzy asks for.
+// term_runs for the terms within `max_dist` edits of a pattern that share its first `prefix` bytes (flags: II2_FUZZY_TRANSPOSE,
+// II2_MATCH_NOCASE): ii2_dict_fuzzy.  A pattern shorter than the prefix is compared as a whole.
 template <class Fn> static void fuzzy_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t max_dist,
                                            uint32_t prefix, uint32_t flags, Fn fn) {
     if (max_dist > 255 || flags > 255) throw Error("fuzzy search: max_dist and flags are at most 255");
-    for (size_t p0 = 0; p0 < patterns.size(); p0 += II2_FUZZY_MAX_PATTERNS) {
-        const size_t np = std::min<size_t>(II2_FUZZY_MAX_PATTERNS, patterns.size() - p0);
-        std::vector<uint8_t> bytes, pre(np);
-        std::vector<uint64_t> off(np + 1, 0);
-        const std::vector<uint8_t> dist(np, (uint8_t)max_dist), fl(np, (uint8_t)flags);
-        for (size_t p = 0; p < np; p++) {
-            bytes.insert(bytes.end(), patterns[p0 + p].begin(), patterns[p0 + p].end());
-            off[p + 1] = bytes.size();
-            pre[p] = (uint8_t)std::min<size_t>(prefix, patterns[p0 + p].size());
-        }
-        bytes.push_back(0);                                               // (never empty)
-        for (size_t s0 = 0; s0 < segs.size(); s0 += II2_MAX_LISTS) {
-            const size_t k = std::min<size_t>(II2_MAX_LISTS, segs.size() - s0);
-            std::vector<const ii2_dict *> dicts;
-            for (size_t s = 0; s < k; s++) dicts.push_back(segs[s0 + s]->resident_dict(ctx));
-            std::vector<uint64_t> run_off(np * k + 1, 0), first, end;
-            std::vector<uint32_t> which;
-            uint64_t cap = 4096;
-            for (int attempt = 0;; attempt++) {
-                first.resize(cap);
-                end.resize(cap);
-                which.resize(cap);
-                const int rc = ii2_dict_fuzzy(ctx, (uint32_t)k, dicts.data(), (uint32_t)np, bytes.data(), off.data(), dist.data(), pre.data(), fl.data(),
-                                              run_off.data(), first.data(), end.data(), which.data(), cap, nullptr);
-                if (rc != II2_ECAPACITY || attempt) {
-                    ck(ctx, rc, "fuzzy search");
-                    break;
-                }
-                cap = run_off.back();
-            }
-            for (size_t p = 0; p < np; p++)
-                for (uint64_t j = run_off[p * k]; j < run_off[(p + 1) * k]; j++) fn(p0 + p, segs[s0 + which[j]], (size_t)first[j], (size_t)end[j]);
-        }
-    }
+    term_runs(ctx, segs, patterns, II2_FUZZY_MAX_PATTERNS, "fuzzy search",
+              [&](size_t p0, size_t np, uint32_t k, const ii2_dict *const *dicts, const uint8_t *bytes, const uint64_t *off, uint64_t *run_off, uint64_t *first,
+                  uint64_t *end, uint32_t *which, uint64_t cap) {
+                  const std::vector<uint8_t> dist(np, (uint8_t)max_dist), fl(np, (uint8_t)flags);
+                  std::vector<uint8_t> pre(np);
+                  for (size_t p = 0; p < np; p++) pre[p] = (uint8_t)std::min<size_t>(prefix, patterns[p0 + p].size());
+                  return ii2_dict_fuzzy(ctx, k, dicts, (uint32_t)np, bytes, off, dist.data(), pre.data(), fl.data(), run_off, first, end, which, cap, nullptr);
+              }, fn);
 }
-// map<query term, ids under any term within distance> over `segs`: every query term's runs, then ONE batch of OR queries
-// (or_per_name).  A query term that matches nothing has no entry.  No tombstone filter, as in Read.
+// (the names are query terms here: ids under any term within distance)
 template <class TwoCall> static std::map<Term, std::vector<uint32_t>> fuzzy_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
                                                                                    std::vector<Term> terms, uint32_t max_dist, uint32_t prefix, uint32_t flags,
                                                                                    TwoCall two_call) {
-    std::sort(terms.begin(), terms.end(), term_less);
-    terms.erase(std::unique(terms.begin(), terms.end()), terms.end());
-    std::map<Term, NamedRanges> found;
-    fuzzy_runs(ctx, segs, terms, max_dist, prefix, flags, [&](size_t p, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
-        NamedRanges &r = found[terms[p]];
-        r.segs.push_back(sg->seg->h);
-        r.first.push_back(j0);
-        r.end.push_back(j1);
-    });
-    return or_per_name(ctx, found, "fuzzy search", two_call);
+    return runs_search(ctx, std::move(terms), "fuzzy search",
+                       [&](const std::vector<Term> &distinct, auto fn) { fuzzy_runs(ctx, segs, distinct, max_dist, prefix, flags, fn); }, two_call);
 }
 // the distinct terms of `segs` within distance of the pattern with their distances, distance ascending, then bytes ascending, at
 // most `limit`: the terms are read from the runs, and only those get their distance, from ii2_term_fuzzy on the host

@@ -1,5 +1,6 @@
 """GPU: ii2_dict_fuzzy (csrc/dict_fuzzy.hip) - every case of tests/fuzzy_cases.py through the kernels under the four settings of
-fuzzy.stage x fuzzy.wide; one very long term that sends its workgroup alone to global memory; the two-call capacity protocol;
+fuzzy.stage x fuzzy.wide; runs at the workgroup boundary of 256 terms; one very long term that sends its workgroup alone to
+global memory; workgroups that stage their own terms but not a neighbour across their edge; the two-call capacity protocol;
 every argument error with the outputs verified untouched; no patterns and empty dictionaries; and the runs fed verbatim to
 ii2_union_ranges and, as nested distance tiers, to ii2_topk_weighted_ranges.  The kernel-path counters must not move."""
 import ctypes as C
@@ -83,6 +84,96 @@ def test_one_very_long_term_takes_the_global_path_alone(ctx):
 def _numbered(n, hit):
     """n sorted terms; term i is five digits and `x` where hit(i) (6 bytes), else five digits and seven `o` (12 bytes)"""
     return [b"%05d" % i + (b"x" if hit(i) else b"ooooooo") for i in range(n)]
+
+
+@pytest.mark.parametrize("stage", (1, 0))
+@pytest.mark.parametrize("n", (255, 256, 257, 512))
+def test_workgroup_boundaries(ctx, n, stage):
+    """every term matches, none, and alternate terms (both phases): runs across the boundary, at both ends, the most runs.  Five
+    edits cover the digits, not the six bytes between the two lengths: pattern 0 takes the x terms, pattern 1 the o terms"""
+    shapes = {"all": lambda i: True, "none": lambda i: False, "even": lambda i: i % 2 == 0, "odd": lambda i: i % 2 == 1,
+              "but-the-boundary": lambda i: i not in (255, 256), "only-the-boundary": lambda i: i in (255, 256),
+              "last-of-each": lambda i: i % 256 == 255, "first-of-each": lambda i: i % 256 == 0}
+    names = list(shapes)
+    dicts = [_numbered(n, shapes[name]) for name in names]
+    res = [ctx.dictionary(d) for d in dicts]
+    case = fuzzy_cases.Case(f"boundary-{n}", dicts, [b"00000x", b"00000ooooooo"], [5, 5], [0, 2], [0, 0])
+    ctx.set_option("fuzzy.stage", stage)
+    try:
+        got = _call(ctx, res, case)
+    finally:
+        ctx.set_option("fuzzy.stage", 1)
+    _check(got, fuzzy_cases.expected_table(case))
+    run_off = got[0]
+    k = len(names)
+    per = lambda p, name: int(run_off[p * k + names.index(name) + 1] - run_off[p * k + names.index(name)])
+    assert per(0, "all") == 1 and per(0, "none") == 0 and per(0, "even") == (n + 1) // 2 and per(0, "odd") == n // 2
+    assert per(1, "all") == 0 and per(1, "none") == 1 and per(1, "even") == n // 2
+    for d in res:
+        d.free()
+
+
+def _runs(want, k, p, s):
+    off, first, end = want[0], want[1], want[2]
+    return list(zip(first[off[p * k + s]:off[p * k + s + 1]], end[off[p * k + s]:off[p * k + s + 1]]))
+
+
+def test_a_long_term_astride_a_workgroup_edge(ctx):
+    """term 256 (255) of 512 carries 20 000 bytes more: its own workgroup goes to global memory, the one next to it stages its
+    terms but not that neighbour (staged, not wide) and matches it from global memory.  No pattern of at most 64 bytes lies
+    within 255 edits of such a term, so here it only ever breaks a run: one ends exactly at it, one starts right behind it."""
+    tail = b"m" * 20_000
+    ats, hits = (256, 255), (lambda i: i % 10 != 0, lambda i: i % 10 == 0)
+    dicts = []
+    for at, hit in zip(ats, hits):
+        terms = _numbered(512, hit)
+        terms[at] += tail
+        dicts.append(terms)
+    case = fuzzy_cases.Case("long-term-astride", dicts, [b"00000x", b"00000ooooooo"], [5, 5], [0, 2], [0, 0])
+    want = fuzzy_cases.expected_table(case)
+    for s, at in enumerate(ats):                                # the hits of pattern s surround the long term of dictionary s
+        runs = _runs(want, 2, s, s)
+        assert any(e == at for _, e in runs) and any(f == at + 1 for f, _ in runs) and not any(f <= at < e for f, e in runs)
+    res = [ctx.dictionary(d) for d in dicts]
+    for wide in (0, 1):
+        ctx.set_option("fuzzy.wide", wide)
+        try:
+            got = _call(ctx, res, case)
+        finally:
+            ctx.set_option("fuzzy.wide", 0)
+        _check(got, want)
+        st = got[4]
+        assert st.n_staged == 2 and st.n_global == 2 and st.word_bits == (64 if wide else 32)
+    for d in res:
+        d.free()
+
+
+def test_neighbours_that_match_outside_a_full_stage(ctx):
+    """staged, not wide, with neighbours a pattern can match: one term in the middle of each workgroup is padded until the
+    workgroup's own 256 terms fill the 16 KB stage to the byte, so the 6- or 12-byte neighbour across the edge no longer fits and
+    is matched from global memory.  One dictionary has a run across the edge, one a run that ends at it and one that starts there."""
+    dicts = []
+    for hit in (lambda i: 250 <= i < 260, lambda i: i % 3 != 0):
+        terms = _numbered(512, hit)
+        for mid, w0 in ((100, 0), (400, 256)):
+            terms[mid] += b"m" * (16384 - sum(len(t) for t in terms[w0:w0 + 256]))
+        assert [sum(len(t) for t in terms[w0:w0 + 256]) for w0 in (0, 256)] == [16384, 16384]
+        dicts.append(terms)
+    case = fuzzy_cases.Case("full-stage", dicts, [b"00000x", b"00000ooooooo"], [5, 5], [0, 2], [0, 0])
+    want = fuzzy_cases.expected_table(case)
+    assert (250, 260) in _runs(want, 2, 0, 0) and any(e == 250 for _, e in _runs(want, 2, 1, 0)) and any(f == 260 for f, _ in _runs(want, 2, 1, 0))
+    assert any(f == 256 for f, _ in _runs(want, 2, 0, 1)) and any(e == 256 for _, e in _runs(want, 2, 1, 1))      # 255 is an o term, 256 an x term
+    res = [ctx.dictionary(d) for d in dicts]
+    for wide in (0, 1):
+        ctx.set_option("fuzzy.wide", wide)
+        try:
+            got = _call(ctx, res, case)
+        finally:
+            ctx.set_option("fuzzy.wide", 0)
+        _check(got, want)
+        assert got[4].n_staged == 4 and got[4].n_global == 0
+    for d in res:
+        d.free()
 
 
 def _raw_setup(ctx):

@@ -1,6 +1,7 @@
 """GPU: ii2_dict_match (csrc/dict_match.hip) - every case of tests/match_cases.py through the kernels with the LDS stage and
 without it; runs at the workgroup boundary of 256 terms, at a dictionary's first and last term and the largest run count; a run
-across three workgroups; one very long term that sends its workgroup alone to global memory; the two-call capacity protocol;
+across three workgroups; one very long term that sends its workgroup alone to global memory, and one astride a workgroup edge,
+which the workgroup beside it reads from global memory while its own terms are staged; the two-call capacity protocol;
 every argument error with the outputs verified untouched; no patterns; and the runs fed verbatim to ii2_union_ranges and
 ii2_intersect_ranges against plain Python sets.  The kernel-path counters must not move."""
 import ctypes as C
@@ -112,6 +113,33 @@ def test_one_very_long_term_takes_the_global_path_alone(ctx):
     assert st.n_global == 1 and st.n_staged == (len(terms) + 255) // 256 - 1 and st.n_staged > 0
     assert any(f <= at < e for f, e in zip(got[1][int(got[0][2]):int(got[0][3])].tolist(), got[2][int(got[0][2]):int(got[0][3])].tolist()))
     d.free()
+
+
+def test_a_long_term_astride_a_workgroup_edge(ctx):
+    """term 256 (255) of 512 carries 20 000 bytes more: its own workgroup goes to global memory, the one next to it stages its
+    terms but not that neighbour (staged, not wide) and matches it from global memory.  The long term holds an `x` and ends in
+    `o`: it joins the CONTAINS run around it and breaks the SUFFIX run - one ends exactly at it, one starts right behind it."""
+    tail = b"y" * 19_999 + b"o"
+    ats = (256, 255)
+    dicts = []
+    for at in ats:
+        terms = _numbered(512, lambda i: i % 10 != 0)
+        assert terms[at].endswith(b"x")
+        terms[at] += tail
+        dicts.append(terms)
+    case = match_cases.Case("long-term-astride", dicts, [b"x", b"x", b"y", b"o"], [SUFFIX, CONTAINS, CONTAINS, SUFFIX])
+    want = match_cases.expected_table(case)
+    off, first, end = want[0], want[1], want[2]
+    runs = lambda p, s: list(zip(first[off[p * 2 + s]:off[p * 2 + s + 1]], end[off[p * 2 + s]:off[p * 2 + s + 1]]))
+    for s, at in enumerate(ats):
+        assert any(e == at for _, e in runs(0, s)) and any(f == at + 1 for f, _ in runs(0, s))       # SUFFIX x: broken at the long term
+        assert (251, 260) in runs(1, s) and runs(2, s) == [(at, at + 1)] and (at, at + 1) in runs(3, s)      # CONTAINS x: across it
+    res = [ctx.dictionary(d) for d in dicts]
+    got = ctx.dict_match(res, case.patterns, np.array(case.kinds, np.uint8))
+    _check(got, want)
+    assert got[4].n_staged == 2 and got[4].n_global == 2
+    for d in res:
+        d.free()
 
 
 def _raw_setup(ctx):
