@@ -503,6 +503,79 @@ func TermFuzzy(pattern, term []byte, maxDist, prefix uint32, flags uint8) (bool,
 	return m != 0, uint32(d), nil
 }
 
+// RegexStats mirrors ii2_regex_stats.
+type RegexStats struct {
+	Terms, Matched, Runs, Tested uint64
+	Staged, Global, MaxPositions uint32
+}
+
+// DictRegex is the regular-expression term search in k resident dictionaries (ii2_dict_regex): every term that pattern p
+// matches as a WHOLE (write `.*foo.*` for "contains").  The syntax is the subset of Python's re on bytes that include/ii2.h
+// lists - classes, alternation, groups, counted repetition, no anchors, `.` matches any byte.  At most 8 patterns of at most 256
+// bytes and 64 positions per call (callers chunk); flags[p] is 0 or MatchNoCase; flags may be nil (all 0).  The answer is laid
+// out as DictMatch's: pair (p, s) owns the runs runOff[p*k+s] .. runOff[p*k+s+1]-1, run j is the terms [first[j], end[j]) of
+// dictionary dict[j], and the runs of pattern p are one group of the range calls.  A result above the first buffer of 4096 runs
+// takes the second call the library asks for, with the exact size.
+func (c *Ctx) DictRegex(dicts []*Dictionary, patterns [][]byte, flags []uint8) (runOff, first, end []uint64, dict []uint32, st RegexStats, err error) {
+	if len(dicts) == 0 {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict regex: no dictionaries")
+	}
+	if flags != nil && len(flags) != len(patterns) {
+		return nil, nil, nil, nil, st, fmt.Errorf("dict regex: one flag byte per pattern")
+	}
+	hs := make([]*C.ii2_dict, len(dicts))
+	for i, d := range dicts {
+		hs[i] = d.h
+	}
+	off := make([]uint64, len(patterns)+1)
+	var blob []byte
+	for i, p := range patterns {
+		blob = append(blob, p...)
+		off[i+1] = uint64(len(blob))
+	}
+	blob = append(blob, 0) // never an empty array
+	var fp *C.uint8_t
+	if flags != nil {
+		fl := append(append([]uint8{}, flags...), 0)
+		fp = (*C.uint8_t)(unsafe.Pointer(&fl[0]))
+	}
+	runOff = make([]uint64, len(patterns)*len(dicts)+1)
+	capRuns := uint64(4096)
+	var cs C.ii2_regex_stats
+	for attempt := 0; ; attempt++ {
+		first, end, dict = make([]uint64, capRuns+1), make([]uint64, capRuns+1), make([]uint32, capRuns+1)
+		rc := C.ii2_dict_regex(c.h, C.uint32_t(len(hs)), (**C.ii2_dict)(unsafe.Pointer(&hs[0])), C.uint32_t(len(patterns)),
+			(*C.uint8_t)(unsafe.Pointer(&blob[0])), u64ptr(off), fp, u64ptr(runOff), u64ptr(first), u64ptr(end),
+			(*C.uint32_t)(unsafe.Pointer(&dict[0])), C.uint64_t(capRuns), &cs)
+		if rc == C.II2_ECAPACITY && attempt == 0 {
+			capRuns = runOff[len(runOff)-1]
+			continue
+		}
+		if rc != 0 {
+			return nil, nil, nil, nil, st, c.err("dict regex", rc)
+		}
+		break
+	}
+	n := runOff[len(runOff)-1]
+	st = RegexStats{uint64(cs.n_terms), uint64(cs.n_matched), uint64(cs.n_runs), uint64(cs.n_tested), uint32(cs.n_staged), uint32(cs.n_global),
+		uint32(cs.max_positions)}
+	return runOff, first[:n], end[:n], dict[:n], st, nil
+}
+
+// TermRegex is one pattern against one term by the functions DictRegex's kernel runs (ii2_term_regex): whether the pattern
+// matches the whole term, and the positions of its automaton - also set when they are too many (the error then is II2_ERANGE);
+// needs no GPU.
+func TermRegex(pattern, term []byte, flags uint8) (bool, uint32, error) {
+	p, t := append(append([]byte{}, pattern...), 0), append(append([]byte{}, term...), 0)
+	var m C.int
+	var n C.uint32_t
+	if rc := C.ii2_term_regex(C.uint32_t(flags), (*C.uint8_t)(unsafe.Pointer(&p[0])), C.uint64_t(len(pattern)), (*C.uint8_t)(unsafe.Pointer(&t[0])),
+		C.uint64_t(len(term)), &m, &n); rc != 0 {
+		return false, uint32(n), fmt.Errorf("term regex: error %d", int(rc))
+	}
+	return m != 0, uint32(n), nil
+}
+
 // AlignDicts is AlignTerms on resident dictionaries (ii2_align_dicts): nothing is uploaded, nothing is sorted.
 func (c *Ctx) AlignDicts(dicts []*Dictionary) (*Alignment, error) {
 	hs := make([]*C.ii2_dict, len(dicts))

@@ -545,6 +545,135 @@ func FuzzyTerms(c *Ctx, ix MatchIndex, pattern []byte, maxDist, prefix, flags ui
 	return out, nil
 }
 
+// regexRuns calls fn(p, segment index, j0, j1) for every run [j0, j1) of consecutive terms of every segment that patterns[p] matches
+// as a whole: Ctx.DictRegex per chunk of at most 64 dictionaries and 8 patterns.  Every pattern is parsed first (TermRegex), so
+// that one that does not parse fails the call before any search runs.
+func regexRuns(c *Ctx, dicts []*Dictionary, patterns [][]byte, flags uint8, fn func(p, seg int, j0, j1 uint64)) error {
+	for _, p := range patterns {
+		if _, _, err := TermRegex(p, nil, flags); err != nil {
+			return fmt.Errorf("pattern %q: %w", p, err)
+		}
+	}
+	for p0 := 0; p0 < len(patterns); p0 += 8 {
+		p1 := p0 + 8
+		if p1 > len(patterns) {
+			p1 = len(patterns)
+		}
+		fl := make([]uint8, p1-p0)
+		for i := range fl {
+			fl[i] = flags
+		}
+		for s0 := 0; s0 < len(dicts); s0 += 64 {
+			s1 := s0 + 64
+			if s1 > len(dicts) {
+				s1 = len(dicts)
+			}
+			k := s1 - s0
+			runOff, first, end, dict, _, err := c.DictRegex(dicts[s0:s1], patterns[p0:p1], fl)
+			if err != nil {
+				return err
+			}
+			for p := 0; p < p1-p0; p++ {
+				for j := runOff[p*k]; j < runOff[(p+1)*k]; j++ {
+					fn(p0+p, s0+int(dict[j]), first[j], end[j])
+				}
+			}
+		}
+	}
+	return nil
+}
+
+// RegexSearch (additive): regular-expression search - for every pattern the ids under any term it matches as a whole (flags: 0
+// or MatchNoCase), over every segment of every shard.  Ctx.DictRegex per chunk of at most 64 dictionaries and 8 patterns turns
+// the patterns into runs of lists, then ONE Ctx.QueryBatch call - an OpOr query per pattern over all its runs - and one download,
+// with a second call when the results exceed the first buffer: what the C++ host mirror's InvertedIndex::RegexSearch does
+// (host/host_index.cpp).  A pattern that matches nothing has no entry.  Like Read, no tombstone filter.
+func RegexSearch(c *Ctx, ix MatchIndex, patterns [][]byte, flags uint8) (found map[string][]uint32, err error) {
+	defer ix.Release()
+	segs, dicts := ix.ResidentSegments()
+	type ranges struct {
+		segs       []*Segment
+		first, end []uint64
+	}
+	per := make([]ranges, len(patterns))
+	if err := regexRuns(c, dicts, patterns, flags, func(p, seg int, j0, j1 uint64) {
+		r := &per[p]
+		r.segs = append(r.segs, segs[seg])
+		r.first = append(r.first, j0)
+		r.end = append(r.end, j1)
+	}); err != nil {
+		return nil, fmt.Errorf("regex search: %w", err)
+	}
+	var names []string
+	var op []uint8
+	queryFirst := []uint64{0}
+	var qsegs []*Segment
+	var qfirst, qend []uint64
+	seen := map[string]bool{}
+	for p, r := range per {
+		if len(r.segs) == 0 || seen[string(patterns[p])] {
+			continue
+		}
+		seen[string(patterns[p])] = true
+		names = append(names, string(patterns[p]))
+		op = append(op, OpOr)
+		qsegs = append(qsegs, r.segs...)
+		qfirst = append(qfirst, r.first...)
+		qend = append(qend, r.end...)
+		queryFirst = append(queryFirst, uint64(len(qsegs)))
+	}
+	found = map[string][]uint32{}
+	if len(names) == 0 {
+		return found, nil
+	}
+	all, offs, err := c.QueryBatchHost(op, queryFirst, qsegs, qfirst, qend, uint64(1)<<22)
+	if err != nil {
+		return nil, fmt.Errorf("regex search: %w", err)
+	}
+	for q, name := range names {
+		found[name] = all[offs[q]:offs[q+1]]
+	}
+	return found, nil
+}
+
+// RegexTerms (additive): the distinct terms the pattern matches, in bytes.Compare order, at most limit.  The matched terms are
+// read from the runs (Ctx.DictExport of the dictionaries that hold one): what InvertedIndex::RegexTerms does.
+func RegexTerms(c *Ctx, ix MatchIndex, pattern []byte, flags uint8, limit int) ([][]byte, error) {
+	defer ix.Release()
+	_, dicts := ix.ResidentSegments()
+	exported := map[int][][]byte{}
+	seen := map[string]bool{}
+	var out [][]byte
+	var failed error
+	if err := regexRuns(c, dicts, [][]byte{pattern}, flags, func(_, seg int, j0, j1 uint64) {
+		if failed != nil {
+			return
+		}
+		if _, ok := exported[seg]; !ok {
+			exported[seg], failed = c.DictExport(dicts[seg])
+			if failed != nil {
+				return
+			}
+		}
+		for _, t := range exported[seg][j0:j1] {
+			if !seen[string(t)] {
+				seen[string(t)] = true
+				out = append(out, append([]byte{}, t...))
+			}
+		}
+	}); err != nil {
+		return nil, fmt.Errorf("regex terms: %w", err)
+	}
+	if failed != nil {
+		return nil, fmt.Errorf("regex terms: %w", failed)
+	}
+	sort.Slice(out, func(i, j int) bool { return bytes.Compare(out[i], out[j]) < 0 })
+	if len(out) > limit {
+		out = out[:limit]
+	}
+	return out, nil
+}
+
 // IntersectAtLeast (additive): the ids under at least minMatch of terms and under none of except - minimum-should-match, "any two
 // of these tags".  One group per term as IntersectExcept builds them, but a required term found in no segment is a group without
 // ranges (it matches no doc), not an empty result; ONE Ctx.AtLeastRanges call with one download - what the C++ host mirror's

@@ -299,6 +299,74 @@ int ii2_dict_fuzzy(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
  * the two above, prefix above pat_len.  II2_ERANGE: pat_len above II2_FUZZY_MAX_PATTERN. */
 int ii2_term_fuzzy(uint32_t flags, const uint8_t *pat, uint64_t pat_len, uint32_t prefix, uint32_t max_dist, const uint8_t *term,
                    uint64_t term_len, int *match, uint32_t *dist /* may be NULL */);
+/* Regular-expression term search in k resident dictionaries: every term a pattern matches, as list ranges for the range entry
+ * points - the fourth mode of a search front end beside ii2_dict_find, ii2_dict_match and ii2_dict_fuzzy (Lucene's RegexpQuery;
+ * the reference's dictionary library answers it with a regex automaton walked over the FST).  It replaces the loop over every term
+ * of every segment with a host regex library that a front end would run otherwise.  The dictionaries are scanned whole; all
+ * arrays are host memory.  Everything compares bytes, as ii2_dict_match does (no UTF-8).
+ * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) and matches a term when it matches the WHOLE term (GLOB's rule, vellum's
+ * and Lucene's; write `.*foo.*` for "contains").  Where a pattern is accepted it means what Python's
+ * re.fullmatch(pattern, term, re.DOTALL) means on bytes:
+ *   literal     any byte other than \ . [ ( ) | * + ? { ^ $; an unescaped `]` outside a class and an unescaped `}` outside a
+ *               counted repetition are literal;
+ *   .           any byte, `\n` included;
+ *   escapes     \d \D \w \W \s \S (ASCII: [0-9], [A-Za-z0-9_], [ \t\n\r\f\v] and their complements), \n \r \t \f \v, \xHH
+ *               (two hex digits), `\` and an ASCII punctuation byte: that byte; anything else behind `\` is II2_EINVAL (other
+ *               letters, digits, a lone `\` at the end);
+ *   [...]       bytes, ranges lo-hi and the escapes above (\D \W \S included); a leading `^` negates; a `]` right after `[` or
+ *               `[^` is literal, so is a `-` first or last and a `[`; hi < lo, a range that ends in a class escape or an
+ *               unterminated class is II2_EINVAL;
+ *   ( ) (?: )   groups, the same thing: there are no captures; any other `(?` is II2_EINVAL; empty groups and empty alternatives
+ *               (`(a|)`, `a|`) match the empty string; unbalanced parentheses are II2_EINVAL;
+ *   |           alternation;
+ *   * + ? {m} {m,} {m,n}   on the preceding byte, `.`, class, escape or group; one `?` directly behind a quantifier is accepted
+ *               and ignored (laziness cannot change a whole-term match); II2_EINVAL: any other quantifier behind a quantifier
+ *               (`a**`, `a*+`, `a{2}{3}`), a quantifier with nothing in front, `{,n}`, n < m, a `{` that starts none of the three;
+ *   ^ $         outside a class II2_EINVAL (there are no zero-width assertions; the literals are \^ and \$);
+ *   the empty pattern matches only the empty term.
+ * pat_flags[p] is 0 or II2_MATCH_NOCASE: ASCII A-Z and a-z compare equal and no other byte folds - a byte c is in a position's
+ * set when fold(c) is in the fold of the listed set, and a negated class is the complement of that (`[^a]` rejects `a` and `A`,
+ * `[Z-a]` accepts `z` and `A`).
+ * A pattern becomes its Glushkov position automaton on the host: every byte, `.`, class or escape is one position; x{m,n} is m
+ * copies of x followed by n - m nested optionals, x{m,} m copies followed by x*, x{0} nothing.  At most II2_REGEX_MAX_POSITIONS
+ * positions after that expansion, II2_REGEX_MAX_PATTERN raw bytes and II2_REGEX_MAX_PATTERNS patterns: more is II2_ERANGE.
+ * The answer's layout is exactly ii2_dict_match's: pair (p, s) is entry p * k + s, its runs are the maximal stretches of
+ * consecutive matching term indices, in run_off / run_first / run_end / run_dict - so pattern p is ONE group of every range entry
+ * point.
+ * Every check runs before anything is launched or written: II2_EINVAL for a NULL array with n_patterns > 0 (pat_flags, run_dict
+ * and stats excepted; the three run arrays may be NULL with cap == 0), k == 0 or k > II2_MAX_LISTS, a dictionary that is NULL or
+ * of another device, pat_off that does not start at 0 or descends, a flag bit other than II2_MATCH_NOCASE, a pattern outside the
+ * syntax; II2_ERANGE for the three limits or a dictionary of 2^31 terms or more.  n_patterns == 0, or no term in any dictionary:
+ * run_off is all zero and nothing is launched.  More runs than cap: II2_ECAPACITY with run_off and *stats completely filled and
+ * the three run arrays untouched - allocate run_off[n_patterns * k] entries and call again.
+ * At most two waits per call.  Not a set operation: it takes no kernel path of ii2_ctx_paths.  No workgroup waits for another.
+ * Never reads past the 16 bytes of padding behind a dictionary's bytes.  On the device (dict_regex.hip) a thread per term keeps
+ * the automaton's states in one 64-bit register; terms shorter than the language's shortest or longer than its longest are
+ * skipped before it (stats->n_tested counts the rest).  Option "regex.stage" (default 1): a workgroup copies the bytes of its
+ * 256 terms into LDS first when they fit; 0: every thread reads global memory.  Results are identical under both settings. */
+#define II2_REGEX_MAX_PATTERN   256u  /* raw bytes per pattern; longer: II2_ERANGE */
+#define II2_REGEX_MAX_POSITIONS 64u   /* positions after expansion; more: II2_ERANGE */
+#define II2_REGEX_MAX_PATTERNS  8u    /* patterns per call; more: II2_ERANGE (callers chunk) */
+typedef struct {
+    uint64_t n_terms;    /* terms read, summed over the k dictionaries */
+    uint64_t n_matched;  /* (pattern, term) pairs that matched */
+    uint64_t n_runs;     /* runs = run_off[n_patterns * k] */
+    uint64_t n_tested;   /* pairs that passed the length filter and ran the automaton */
+    uint32_t n_staged, n_global;   /* workgroups that matched out of LDS / from global memory */
+    uint32_t max_positions;   /* the largest position count among the call's patterns; 0 when nothing was launched */
+    uint32_t pad;
+} ii2_regex_stats;            /* 48 bytes */
+int ii2_dict_regex(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes,
+                   const uint64_t *pat_off /* n_patterns + 1, from 0 */, const uint8_t *pat_flags /* n_patterns; NULL: all 0 */,
+                   uint64_t *run_off /* n_patterns * k + 1 */, uint64_t *run_first, uint64_t *run_end,
+                   uint32_t *run_dict /* may be NULL */, uint64_t cap, ii2_regex_stats *stats /* may be NULL */);
+/* The matcher's arithmetic, host only (no GPU needed): one pattern against one term by the functions the kernel runs - the same
+ * parse, the same filter, the same step.  *match = 0 / 1.  *n_pos (may be NULL) = the pattern's positions, set whenever the
+ * syntax holds: also on II2_ERANGE from the position limit, when it is the count that was too large (a caller sizes patterns by
+ * it).  II2_EINVAL: a NULL match, NULL pat with pat_len > 0, NULL term with term_len > 0, a flag bit other than
+ * II2_MATCH_NOCASE, a pattern outside the syntax.  II2_ERANGE: the two limits of a pattern. */
+int ii2_term_regex(uint32_t flags, const uint8_t *pat, uint64_t pat_len, const uint8_t *term, uint64_t term_len, int *match,
+                   uint32_t *n_pos /* may be NULL */);
 /* Dictionary build step (bulk Put, in front of ii2_seg_build).  Replaces the std::sort over every term occurrence, the
  * std::unique and the string bisection per occurrence that a bulk Put does on the host before ii2_seg_build (order = bytes.Compare,
  * file/types.go:24-26).  Input: n_terms terms in any order, repeats allowed, any bytes, the empty term included - term i is

@@ -58,6 +58,14 @@ II2_FUZZY_MAX_PATTERN, II2_FUZZY_MAX_PATTERNS = 64, 16
 II2_FUZZY_TRANSPOSE = 0x01
 
 
+class RegexStats(C.Structure):
+    _fields_ = [("n_terms", C.c_uint64), ("n_matched", C.c_uint64), ("n_runs", C.c_uint64), ("n_tested", C.c_uint64), ("n_staged", C.c_uint32),
+                ("n_global", C.c_uint32), ("max_positions", C.c_uint32), ("pad", C.c_uint32)]
+
+
+II2_REGEX_MAX_PATTERN, II2_REGEX_MAX_POSITIONS, II2_REGEX_MAX_PATTERNS = 256, 64, 8
+
+
 class AlignPlan(C.Structure):
     _fields_ = [("n_terms", C.c_uint64), ("n_workgroups", C.c_uint64), ("brackets_staged", C.c_uint64), ("brackets_global", C.c_uint64),
                 ("brackets_empty", C.c_uint64), ("max_bracket", C.c_uint64), ("long_terms", C.c_uint32), ("terms_per_workgroup", C.c_uint32),
@@ -128,6 +136,8 @@ PROTOTYPES = {
     "ii2_term_match": (C.c_int, [C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_int)]),
     "ii2_dict_fuzzy": (C.c_int, [vp, C.c_uint32, vpp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(FuzzyStats)]),
     "ii2_term_fuzzy": (C.c_int, [C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_int), u32p]),
+    "ii2_dict_regex": (C.c_int, [vp, C.c_uint32, vpp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(RegexStats)]),
+    "ii2_term_regex": (C.c_int, [C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_int), u32p]),
     "ii2_dict_build": (C.c_int, [vp, C.c_uint64, vp, vp, C.c_int, vpp, vp, C.POINTER(DictBuildStats)]),
     "ii2_dict_info": (C.c_int, [vp, u64p, u64p]),
     "ii2_dict_export": (C.c_int, [vp, vp, vp, vp]),

@@ -1176,6 +1176,7 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "match.stage") ctx->opt_match_stage = value;
     else if (k == "fuzzy.stage") ctx->opt_fuzzy_stage = value;
     else if (k == "fuzzy.wide") ctx->opt_fuzzy_wide = value;
+    else if (k == "regex.stage") ctx->opt_regex_stage = value;
     else if (k == "intersect.ranges") ctx->opt_intersect_ranges = value;
     else if (k == "intersect.ranges_mark") ctx->opt_ir_mark = value;
     else if (k == "andnot.small") ctx->opt_andnot_small = value;

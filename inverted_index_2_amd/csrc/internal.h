@@ -126,6 +126,7 @@ struct ii2_ctx {
                                         //     fewer than 4 runs of 256 candidates per CU (0: always probe)
     int64_t opt_match_stage = 1;        // ii2_dict_match: a workgroup matches its 256 terms out of an LDS copy of their bytes where they fit (0: always from global memory)
     int64_t opt_fuzzy_stage = 1;        // ii2_dict_fuzzy: the same stage (0: always from global memory)
+    int64_t opt_regex_stage = 1;        // ii2_dict_regex: the same stage (0: always from global memory)
     int64_t opt_fuzzy_wide = 0;         // ... 1: the 64-bit instance of its kernel even where every pattern holds at most 32 bytes
     uint32_t *d_ir = nullptr;           // its two candidate arrays (ping-pong; grow-only: the driver's union reserves the workspace itself)
     size_t ir_words = 0;

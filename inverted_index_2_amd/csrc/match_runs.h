@@ -1,4 +1,4 @@
-// match_runs.h — what ii2_dict_match (dict_match.hip) and ii2_dict_fuzzy (dict_fuzzy.hip) share: a workgroup of 256 threads takes
+// match_runs.h — what ii2_dict_match (dict_match.hip), ii2_dict_fuzzy (dict_fuzzy.hip) and ii2_dict_regex (dict_regex.hip) share: a workgroup of 256 threads takes
 // 256 consecutive terms of ONE dictionary and every thread ends up with a 64-bit match word (bit p = pattern p).  From there on
 // the two calls are one: the run starts and ends per workgroup (match_runs_tail, below), the two scans, k_match_offsets,
 // k_match_place and the copies (match_runs_drive, defined once in dict_match.hip).  In front of the match word they are one as
@@ -24,7 +24,7 @@ constexpr uint32_t DM_WAVES = DM_THREADS / 64;
 // LDS stage of a workgroup's term bytes: 64 bytes per term on average
 constexpr uint32_t MATCH_STAGE = 16384;
 // the counters a call carries through the scans, one row of the two tables each: row 0 = {matched (pattern, term) pairs, workgroups
-// that matched out of LDS}, row 1 (ii2_dict_fuzzy) = {pairs that ran the recurrence, -}
+// that matched out of LDS}, row 1 (ii2_dict_fuzzy, ii2_dict_regex) = {pairs that passed the filters in front of the matcher, -}
 constexpr uint32_t MATCH_MAX_ROWS = 2;
 
 struct MatchDicts {
@@ -53,6 +53,14 @@ template <class Pattern> __device__ __forceinline__ void match_patterns_to_lds(P
     const uint32_t *src = (const uint32_t *)pats;
     uint32_t *dst = (uint32_t *)lp;
     for (uint32_t i = threadIdx.x; i < P * (uint32_t)(sizeof(Pattern) / 4); i += DM_THREADS) dst[i] = src[i];
+}
+
+// the same for patterns whose size is a multiple of 16 (ii2_dict_regex: 2.6 KB each), in 16-byte loads; lp and pats are 16-byte aligned
+template <class Pattern> __device__ __forceinline__ void match_patterns_to_lds16(Pattern *lp, const Pattern *__restrict__ pats, uint32_t P) {
+    static_assert(sizeof(Pattern) % 16 == 0, "a parsed pattern is copied into LDS in 16-byte loads");
+    const uint4 *src = (const uint4 *)pats;
+    uint4 *dst = (uint4 *)lp;
+    for (uint32_t i = threadIdx.x; i < P * (uint32_t)(sizeof(Pattern) / 16); i += DM_THREADS) dst[i] = src[i];
 }
 
 // The term bytes of workgroup wg, which takes terms [t0, t1) of dictionary s: where they are and how a matcher reads them.  The

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import II2_FUZZY_TRANSPOSE, FuzzyStats  # noqa: F401
+from ._lib import RegexStats
 from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
@@ -206,6 +207,22 @@ def term_fuzzy(pattern: bytes, term: bytes, max_dist: int, prefix: int = 0, flag
     if rc:
         raise II2Error(rc, "ii2_term_fuzzy")
     return bool(m.value), d.value
+
+
+def term_regex(pattern: bytes, term: bytes, flags: int = 0):
+    """One pattern against one term by the functions ii2_dict_regex's kernel runs (ii2_term_regex): (match, n_pos) - whether the
+    regular expression matches the WHOLE term, and the positions of its automaton (at most 64).  flags: 0 or II2_MATCH_NOCASE.
+    A pattern outside the syntax or above a limit raises II2Error; on the position limit its n_pos attribute holds the count
+    that was too large.  Needs no context and no GPU."""
+    lib = _lib.load()
+    m, n = C.c_int(-1), C.c_uint32(0)
+    rc = lib.ii2_term_regex(int(flags), C.c_char_p(bytes(pattern)) if pattern else None, len(pattern), C.c_char_p(bytes(term)) if term else None,
+                            len(term), C.byref(m), C.byref(n))
+    if rc:
+        e = II2Error(rc, "ii2_term_regex")
+        e.n_pos = n.value
+        raise e
+    return bool(m.value), n.value
 
 
 class DeviceArray:
@@ -528,7 +545,7 @@ class Context:
         return self._dict_runs(dicts, len(patterns), lambda *out: self.dict_match_flat(dicts, blob, off, kinds, *out))
 
     def _dict_runs(self, dicts, n_patterns, flat_call):
-        """The two-call protocol of dict_match and dict_fuzzy: flat_call(run_off, run_first, run_end, run_dict, cap) -> (return
+        """The two-call protocol of dict_match, dict_fuzzy and dict_regex: flat_call(run_off, run_first, run_end, run_dict, cap) -> (return
         code, stats) with a first buffer of 4096 runs, and where the result outgrows it once more with the exact size."""
         run_off = np.zeros(n_patterns * len(dicts) + 1, np.uint64)
         cap = 4096
@@ -575,6 +592,29 @@ class Context:
         st = FuzzyStats()
         rc = self.lib.ii2_dict_fuzzy(self.h, len(dicts), arr, max(n, 0), _ptr(pat_bytes), _ptr(pat_off), _ptr(pat_dist), _ptr(pat_prefix),
                                      _ptr(pat_flags), _ptr(run_off), _ptr(run_first), _ptr(run_end), _ptr(run_dict), int(cap), C.byref(st))
+        return rc, st
+
+    def dict_regex(self, dicts, patterns, flags=0):
+        """Regular-expression term search on the device (ii2_dict_regex): every pattern of `patterns` (bytes, at most 8 of at most
+        256 bytes and 64 positions; the syntax is in include/ii2.h) in every one of the k resident dictionaries.  A pattern
+        matches a term when it matches the WHOLE term; flags: 0 or II2_MATCH_NOCASE, one value for all the patterns or one per
+        pattern.  Returns (run_off, run_first, run_end, run_dict, stats), laid out as dict_match's: the runs of pattern p,
+        run_off[p * k] .. run_off[(p + 1) * k] - 1, are one group of the range entry points.  A result that outgrows the first
+        buffer takes a second call of the exact size."""
+        patterns = list(patterns)
+        fl = _per_pattern(flags, len(patterns), "dict_regex", "flags per pattern")
+        blob, off = _flat(patterns)
+        return self._dict_runs(dicts, len(patterns), lambda *out: self.dict_regex_flat(dicts, blob, off, fl, *out))
+
+    def dict_regex_flat(self, dicts, pat_bytes, pat_off, pat_flags, run_off, run_first, run_end, run_dict, cap: int, n_patterns=None):
+        """The same from flat host arrays (numpy, of the ABI's element types), outputs included; any of them may be None to pass
+        NULL.  n_patterns: len(pat_off) - 1 unless given.  Returns (return code, RegexStats) without raising, so that a caller
+        can run the two-call protocol itself."""
+        arr = (C.c_void_p * len(dicts))(*[d.h if d is not None else None for d in dicts])
+        n = int(n_patterns) if n_patterns is not None else (0 if pat_off is None else pat_off.size - 1)
+        st = RegexStats()
+        rc = self.lib.ii2_dict_regex(self.h, len(dicts), arr, max(n, 0), _ptr(pat_bytes), _ptr(pat_off), _ptr(pat_flags), _ptr(run_off),
+                                     _ptr(run_first), _ptr(run_end), _ptr(run_dict), int(cap), C.byref(st))
         return rc, st
 
     def align_dicts(self, dicts) -> "Alignment":
@@ -1116,6 +1156,12 @@ class Dictionary:
         """(run_off, run_first, run_end, stats) of every pattern of `patterns` in this dictionary (Context.dict_fuzzy with k = 1):
         the terms within `max_dist` edits of pattern p are [run_first[j], run_end[j]) for j in run_off[p] .. run_off[p + 1] - 1."""
         run_off, first, end, _, st = self.ctx.dict_fuzzy([self], patterns, max_dist, prefix, flags)
+        return run_off, first, end, st
+
+    def regex(self, patterns, flags=0):
+        """(run_off, run_first, run_end, stats) of every pattern of `patterns` in this dictionary (Context.dict_regex with k = 1):
+        the terms that regular expression p matches are [run_first[j], run_end[j]) for j in run_off[p] .. run_off[p + 1] - 1."""
+        run_off, first, end, _, st = self.ctx.dict_regex([self], patterns, flags)
         return run_off, first, end, st
 
     def info(self):

@@ -65,6 +65,8 @@ def _lib_typed():
         lib.ii2h_match_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p]
         lib.ii2h_fuzzy_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p]
         lib.ii2h_fuzzy_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, u64p]
+        lib.ii2h_regex_search.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, u64p]
+        lib.ii2h_regex_terms.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, u64p]
         lib.ii2h_intersect.argtypes = [vp, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
@@ -223,6 +225,24 @@ class _Target:
         n = C.c_uint64()
         self._ck(self.lib.ii2h_fuzzy_terms(self.h, pat.ctypes.data, len(pattern), int(max_dist), int(prefix), int(flags), int(limit), C.byref(n)))
         return [(t, v[0]) for t, v in self._results(n.value)]
+
+    def regex_search(self, patterns: List[bytes], flags: int = 0) -> Dict[bytes, List[int]]:
+        """Regular-expression search (RegexSearch): {pattern: ids under any term the pattern matches as a whole}, over every
+        segment (of every shard); a pattern that matches no term has no entry.  The syntax is include/ii2.h's (a subset of
+        Python's `re` on bytes with re.DOTALL; at most 256 bytes and 64 positions a pattern); flags: 0 or II2_MATCH_NOCASE (0x80)
+        for all the patterns; any number of patterns (the device call takes 8 at a time).  A pattern that does not parse fails
+        the whole call, before any search runs.  Like read, no tombstone filter."""
+        blob, off = _flat(list(patterns))
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_regex_search(self.h, blob.ctypes.data, off.ctypes.data, len(patterns), int(flags), C.byref(n)))
+        return dict(self._results(n.value))
+
+    def regex_terms(self, pattern: bytes, flags: int = 0, limit: int = 1 << 62) -> List[bytes]:
+        """The distinct terms the regular expression matches (RegexTerms), in byte order, at most `limit`."""
+        pat = np.frombuffer(bytes(pattern) + b"\0", np.uint8).copy()
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_regex_terms(self.h, pat.ctypes.data, len(pattern), int(flags), int(limit), C.byref(n)))
+        return [t for t, _ in self._results(n.value)]
 
     def removed_values(self) -> List[int]:
         n = C.c_uint64()

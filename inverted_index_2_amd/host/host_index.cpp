@@ -25,6 +25,7 @@
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
 //   FuzzySearch(terms, max_dist, prefix, flags) / FuzzyTerms(pattern, max_dist, prefix, flags, limit)   additive: typo-tolerant search (ii2_dict_fuzzy)
+//   RegexSearch(patterns, flags) / RegexTerms(pattern, flags, limit)   additive: regular-expression search (ii2_dict_regex)
 //   SetResolve(mode)                                 additive: the two bulk calls look their terms up on the host or on the device (ii2_dict_find)
 //   SetFirstCap(ids) / SecondCalls()                 additive, for the tests: the first buffer of the calls that may need a second one (two_call)
 //   SetBuild(mode)                                   additive: PutBatch sorts and looks up its terms on the host or on the device (ii2_dict_build)
@@ -365,6 +366,45 @@ static std::vector<std::pair<Term, uint32_t>> fuzzy_terms(ii2_ctx *ctx, const st
     return out;
 }
 
+// ---- regular-expression search (additive: what the reference's dictionary library answers with a regex automaton over the FST) ----
+// term_runs for the terms a pattern matches as a whole (flags: 0 or II2_MATCH_NOCASE; the syntax is include/ii2.h's): ii2_dict_regex
+// in chunks of II2_REGEX_MAX_PATTERNS patterns.  Every pattern is parsed on the host first (ii2_term_regex), so that one that
+// does not parse fails the whole call, with the library's return code, before any search runs.
+template <class Fn> static void regex_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t flags,
+                                           Fn fn) {
+    if (flags > 255) throw Error("regex search: flags are at most 255");      // (they travel as one byte per pattern below)
+    for (const Term &p : patterns) {
+        int match = 0;
+        uint32_t n_pos = 0;
+        const int rc = ii2_term_regex(flags, (const uint8_t *)p.data(), p.size(), nullptr, 0, &match, &n_pos);
+        if (rc)             // (ii2_term_regex has no context to leave a text in: the code it returned, and the count behind II2_ERANGE)
+            throw Error("regex search: ii2_term_regex returned " + std::to_string(rc) + (rc == II2_ERANGE ? " (II2_ERANGE: " + std::to_string(p.size()) +
+                        " bytes, " + std::to_string(n_pos) + " positions)" : rc == II2_EINVAL ? " (II2_EINVAL)" : "") + " for the pattern " + p);
+    }
+    term_runs(ctx, segs, patterns, II2_REGEX_MAX_PATTERNS, "regex search",
+              [&](size_t, size_t np, uint32_t k, const ii2_dict *const *dicts, const uint8_t *bytes, const uint64_t *off, uint64_t *run_off, uint64_t *first,
+                  uint64_t *end, uint32_t *which, uint64_t cap) {
+                  const std::vector<uint8_t> fl(np, (uint8_t)flags);
+                  return ii2_dict_regex(ctx, k, dicts, (uint32_t)np, bytes, off, fl.data(), run_off, first, end, which, cap, nullptr);
+              }, fn);
+}
+template <class TwoCall> static std::map<Term, std::vector<uint32_t>> regex_search(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs,
+                                                                                   std::vector<Term> patterns, uint32_t flags, TwoCall two_call) {
+    return runs_search(ctx, std::move(patterns), "regex search", [&](const std::vector<Term> &distinct, auto fn) { regex_runs(ctx, segs, distinct, flags, fn); },
+                       two_call);
+}
+// the distinct terms of `segs` that the pattern matches, in bytes.Compare order, at most `limit`: read from the runs
+static std::vector<Term> regex_terms(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const Term &pattern, uint32_t flags, uint64_t limit) {
+    std::vector<Term> out;
+    regex_runs(ctx, segs, {pattern}, flags, [&](size_t, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+        out.insert(out.end(), sg->terms.begin() + j0, sg->terms.begin() + j1);
+    });
+    std::sort(out.begin(), out.end(), term_less);
+    out.erase(std::unique(out.begin(), out.end()), out.end());
+    if (out.size() > limit) out.resize(limit);
+    return out;
+}
+
 // ---- file.Writer / file.Reader over segment_file.h (file/writer.go, file/reader.go) -----------------------------
 // The encode and decode steps run on the device through the C ABI (ii2_seg_encode / ii2_seg_import + ii2_seg_decode):
 // there is no host codec in the product.
@@ -607,6 +647,15 @@ class Shard {
     std::vector<std::pair<Term, uint32_t>> FuzzyTerms(const Term &pattern, uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit) const {
         return fuzzy_terms(ctx_, snapshot(), pattern, max_dist, prefix, flags, limit);
     }
+    // additive: regular-expression search over this shard's segments (InvertedIndex::RegexSearch / RegexTerms say what they return);
+    // no tombstone filter, as in Read
+    std::map<Term, std::vector<uint32_t>> RegexSearch(const std::vector<Term> &patterns, uint32_t flags) const {
+        const std::vector<std::shared_ptr<Segment>> segs = snapshot();
+        return regex_search(ctx_, segs, patterns, flags, [&](uint64_t bound, auto call) {
+            return two_call_dev(ctx_, FIRST_CAP_IDS, nullptr, bound, 1, "regex search", call);
+        });
+    }
+    std::vector<Term> RegexTerms(const Term &pattern, uint32_t flags, uint64_t limit) const { return regex_terms(ctx_, snapshot(), pattern, flags, limit); }
 
     // shard.go:78-105
     void Remove(const std::vector<uint32_t> &values) {
@@ -1196,6 +1245,17 @@ class InvertedIndex {
     std::vector<std::pair<Term, uint32_t>> FuzzyTerms(const Term &pattern, uint32_t max_dist, uint32_t prefix, uint32_t flags, uint64_t limit) const {
         return fuzzy_terms(ctx_, all_segments(), pattern, max_dist, prefix, flags, limit);
     }
+    // additive: regular-expression search - map<pattern, ids under any term the pattern matches as a whole> (flags: 0 or
+    // II2_MATCH_NOCASE; the syntax is include/ii2.h's).  It visits every segment of every shard: ii2_dict_regex over the segments'
+    // resident dictionaries (regex_runs, chunks of 8 patterns), then one OR query per pattern over all its runs in ONE
+    // ii2_query_batch call, through two_call, as MatchSearch does.  A pattern that matches nothing has no entry; one that does not
+    // parse fails the whole call before any search runs.  Like Read, no tombstone filter.
+    std::map<Term, std::vector<uint32_t>> RegexSearch(const std::vector<Term> &patterns, uint32_t flags) const {
+        const std::vector<std::shared_ptr<Segment>> segs = all_segments();      // alive until the unions are done
+        return regex_search(ctx_, segs, patterns, flags, [&](uint64_t bound, auto call) { return two_call(bound, 1, "regex search", call); });
+    }
+    // additive: the distinct terms the pattern matches, over every segment of every shard, in bytes.Compare order, at most `limit`
+    std::vector<Term> RegexTerms(const Term &pattern, uint32_t flags, uint64_t limit) const { return regex_terms(ctx_, all_segments(), pattern, flags, limit); }
     // additive: ids present under every term.  A term's postings are spread over the segments of its shard (every Put writes
     // one): one group per term, one one-list range per segment that holds it (Plan::add), and ONE ii2_intersect_ranges call - no
     // list is merged, downloaded or uploaded again.  The output's size: the smallest term's bound.  Like Read, no tombstone filter.
@@ -1960,6 +2020,25 @@ int ii2h_fuzzy_terms(ii2h_target *t, const uint8_t *pattern, uint64_t pattern_le
         const Term p((const char *)pattern, pattern_len);
         for (auto &td : t->index ? t->index->FuzzyTerms(p, max_dist, prefix, flags, limit) : t->shard->FuzzyTerms(p, max_dist, prefix, flags, limit))
             t->result.push_back(TermValues{td.first, {td.second}});
+        *n_found = t->result.size();
+    });
+}
+// map<pattern, ids> of the regular expressions (packed like terms) into the result slots, one per pattern that matched, in pattern order
+int ii2h_regex_search(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint32_t flags, uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const std::vector<Term> patterns = unpack_terms(bytes, off, n);
+        for (auto &kv : t->index ? t->index->RegexSearch(patterns, flags) : t->shard->RegexSearch(patterns, flags))
+            t->result.push_back(TermValues{kv.first, kv.second});
+        *n_found = t->result.size();
+    });
+}
+// the distinct terms one regular expression matches, at most `limit`, into the result slots (terms only)
+int ii2h_regex_terms(ii2h_target *t, const uint8_t *pattern, uint64_t pattern_len, uint32_t flags, uint64_t limit, uint64_t *n_found) {
+    H_TRY(t, {
+        t->result.clear();
+        const Term p((const char *)pattern, pattern_len);
+        for (auto &term : t->index ? t->index->RegexTerms(p, flags, limit) : t->shard->RegexTerms(p, flags, limit)) t->result.push_back(TermValues{term, {}});
         *n_found = t->result.size();
     });
 }
