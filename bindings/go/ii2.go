@@ -349,10 +349,13 @@ func (c *Ctx) DictFind(dicts []*Dictionary, probes [][]byte, prefix []uint8) (fi
 }
 
 // Kinds of DictMatch (II2_MATCH_*); MatchNoCase is OR-ed into a kind: ASCII A-Z and a-z compare equal, no other byte folds.
+// MatchUtf8 (II2_MATCH_UTF8) is OR-ed into a kind or into DictFuzzy's flags: positions are UTF-8 symbols - a code point per
+// well-formed sequence, one symbol per ill-formed byte of a term - instead of bytes, and the pattern must be well-formed UTF-8.
 const (
 	MatchContains uint8 = 0
 	MatchSuffix   uint8 = 1
 	MatchGlob     uint8 = 2
+	MatchUtf8     uint8 = 0x08
 	MatchNoCase   uint8 = 0x80
 )
 
@@ -364,7 +367,7 @@ type MatchStats struct {
 
 // DictMatch is the substring, suffix and wildcard term search in k resident dictionaries (ii2_dict_match): what neither DictFind
 // nor the FST can answer, because both walk a term from its front.  At most 64 patterns of at most 64 bytes per call (callers
-// chunk); kinds[p] is MatchContains / MatchSuffix / MatchGlob (`*`, `?`, `\x`; the whole term), optionally | MatchNoCase.  Pair
+// chunk); kinds[p] is MatchContains / MatchSuffix / MatchGlob (`*`, `?`, `\x`; the whole term), optionally | MatchNoCase, | MatchUtf8.  Pair
 // (p, s) - pattern p in dicts[s] - owns the runs runOff[p*k+s] .. runOff[p*k+s+1]-1; run j is the terms [first[j], end[j]) of
 // dictionary dict[j].  The runs of pattern p, runOff[p*k] .. runOff[(p+1)*k]-1, are one group of the range calls, with
 // segs[j] the segment of dicts[dict[j]].  A result above the first buffer of 4096 runs takes the second call the library asks
@@ -411,6 +414,21 @@ func (c *Ctx) DictMatch(dicts []*Dictionary, patterns [][]byte, kinds []uint8) (
 	return runOff, first[:n], end[:n], dict[:n], st, nil
 }
 
+// Utf8Decode is the symbols of a byte string by the decoder the kernels run under MatchUtf8 (ii2_utf8_decode): a well-formed
+// sequence is its code point, any other byte b alone is 0xDC00 + b; wellFormed says that every byte belongs to a sequence - what a
+// pattern must be.  Needs no GPU.
+func Utf8Decode(data []byte) (symbols []uint32, wellFormed bool, err error) {
+	b := append(append([]byte{}, data...), 0)
+	symbols = make([]uint32, len(data)+1)
+	var n C.uint64_t
+	var ok C.int
+	if rc := C.ii2_utf8_decode((*C.uint8_t)(unsafe.Pointer(&b[0])), C.uint64_t(len(data)), (*C.uint32_t)(unsafe.Pointer(&symbols[0])),
+		C.uint64_t(len(data)), &n, &ok); rc != 0 {
+		return nil, false, fmt.Errorf("utf8 decode: error %d", int(rc))
+	}
+	return symbols[:n], ok != 0, nil
+}
+
 // TermMatch is one pattern against one term by the functions DictMatch's kernel runs (ii2_term_match); needs no GPU.
 func TermMatch(kind uint8, pattern, term []byte) (bool, error) {
 	p, t := append(append([]byte{}, pattern...), 0), append(append([]byte{}, term...), 0)
@@ -423,18 +441,19 @@ func TermMatch(kind uint8, pattern, term []byte) (bool, error) {
 }
 
 // FuzzyTranspose is a flag of DictFuzzy (II2_FUZZY_TRANSPOSE): an adjacent transposition costs 1 (optimal string alignment).
-// MatchNoCase is the only other flag.
+// MatchNoCase and MatchUtf8 (distance, prefix and length filter count UTF-8 symbols) are the only other flags.
 const FuzzyTranspose uint8 = 0x01
 
 // FuzzyStats mirrors ii2_fuzzy_stats.
 type FuzzyStats struct {
 	Terms, Matched, Runs, Tested uint64
 	Staged, Global, WordBits     uint32
+	Utf8                         uint32 // patterns that carried MatchUtf8; 0: the byte instances ran
 }
 
 // DictFuzzy is the typo-tolerant term search in k resident dictionaries (ii2_dict_fuzzy): every term within dist[p] edits of
 // pattern p that shares its first prefix[p] bytes.  At most 16 patterns of at most 64 bytes per call (callers chunk); flags[p] is
-// 0, FuzzyTranspose and / or MatchNoCase; prefix and flags may be nil (all 0).  The answer is laid out as DictMatch's: pair
+// 0, FuzzyTranspose, MatchNoCase and / or MatchUtf8 (edits and prefix in symbols); prefix and flags may be nil (all 0).  The answer is laid out as DictMatch's: pair
 // (p, s) owns the runs runOff[p*k+s] .. runOff[p*k+s+1]-1, run j is the terms [first[j], end[j]) of dictionary dict[j], and the
 // runs of pattern p are one group of the range calls.  The runs carry no distance: send a pattern with distances 0, 1 and 2 for
 // tiers - the groups nest, so their weights add up in TopKWeightedRanges.  A result above the first buffer of 4096 runs takes the
@@ -486,7 +505,7 @@ func (c *Ctx) DictFuzzy(dicts []*Dictionary, patterns [][]byte, dist, prefix, fl
 	}
 	n := runOff[len(runOff)-1]
 	st = FuzzyStats{uint64(cs.n_terms), uint64(cs.n_matched), uint64(cs.n_runs), uint64(cs.n_tested), uint32(cs.n_staged), uint32(cs.n_global),
-		uint32(cs.word_bits)}
+		uint32(cs.word_bits), uint32(cs.n_utf8)}
 	return runOff, first[:n], end[:n], dict[:n], st, nil
 }
 

@@ -203,11 +203,25 @@ int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_
  * range entry points - what neither ii2_dict_find nor the reference's FST can answer, because both walk a term from the front.
  * The dictionaries are scanned whole, at memory speed; all arrays are host memory.
  * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) of kind pat_kind[p], one of II2_MATCH_CONTAINS / SUFFIX / GLOB, optionally
- * OR-ed with II2_MATCH_NOCASE (ASCII A-Z and a-z compare equal; no other byte folds).  Everything compares bytes (no UTF-8):
+ * OR-ed with II2_MATCH_NOCASE (ASCII A-Z and a-z compare equal; no other byte folds) and / or II2_MATCH_UTF8 (below).  Without
+ * II2_MATCH_UTF8 everything compares bytes:
  *   CONTAINS  the pattern is literal and matches a term that holds it anywhere; the empty pattern matches every term;
  *   SUFFIX    the pattern is literal and matches a term that ends with it; the empty pattern matches every term;
  *   GLOB      matches the WHOLE term: `*` any run of bytes (the empty one included), `?` exactly one byte, `\x` the byte x
  *             literally; no bracket classes; a lone `\` at the end is II2_EINVAL; the empty pattern matches only the empty term.
+ * II2_MATCH_UTF8 reads the term as a sequence of SYMBOLS, left to right: where a well-formed UTF-8 sequence starts at byte i (RFC
+ * 3629, Unicode table 3-7: no overlong form, no U+D800..DFFF, nothing above U+10FFFF, the whole sequence inside the term) it is
+ * one symbol, its code point; otherwise byte i alone is one symbol, 0xDC00 + byte, and reading goes on at i + 1 - exactly Python's
+ * bytes.decode("utf-8", "surrogateescape"), total on arbitrary bytes and injective.  The pattern must be well-formed UTF-8, else
+ * II2_EINVAL: so an ill-formed byte of a term equals no pattern symbol.  Under the flag
+ *   GLOB      matches the pattern against the term's symbols: `?` is exactly one symbol (one code point, or one ill-formed
+ *             byte), `*` any run of whole symbols - it never ends inside a sequence, `*??` does not match a term of one 3-byte
+ *             symbol -, `\x` the symbol x literally;
+ *   CONTAINS, SUFFIX   accept the flag and answer as without it: a well-formed pattern starts with a non-continuation byte, so an
+ *             occurrence of its bytes in a term always starts and ends on symbol boundaries of the term.  Only the pattern check
+ *             is new.
+ * II2_MATCH_NOCASE still folds ASCII A-Z only; the limit stays II2_MATCH_MAX_PATTERN bytes.  Flagged and unflagged patterns may be
+ * mixed in one call.  A call without a flagged pattern launches the kernel it always did.
  * Pair (p, s) - pattern p in dicts[s] - is entry p * k + s, ii2_dict_find's layout.  Its answer is the maximal runs of
  * consecutive matching term indices, ascending: run j of the call is [run_first[j], run_end[j]) in dictionary run_dict[j], and
  * pair (p, s) owns the runs run_off[p * k + s] .. run_off[p * k + s + 1] - 1.  So pattern p is ONE group of the range entry
@@ -215,7 +229,8 @@ int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_
  * run_end (plus first_list where a dictionary names lists from there on).  An empty dictionary gives no run.
  * Every check runs before anything is launched or written: II2_EINVAL for a NULL array with n_patterns > 0 (run_dict and stats
  * excepted; the three run arrays may be NULL with cap == 0), k == 0 or k > II2_MAX_LISTS, a dictionary that is NULL or of
- * another device, pat_off that does not start at 0 or descends, an unknown kind, a trailing `\`; II2_ERANGE for a pattern above
+ * another device, pat_off that does not start at 0 or descends, an unknown kind, a trailing `\`, an ill-formed pattern under
+ * II2_MATCH_UTF8; II2_ERANGE for a pattern above
  * II2_MATCH_MAX_PATTERN bytes or more than II2_MATCH_MAX_PATTERNS patterns (callers chunk).  n_patterns == 0 sets run_off[0] = 0
  * and launches nothing.  More runs than cap: II2_ECAPACITY with run_off and *stats completely filled and the three run arrays
  * untouched - allocate run_off[n_patterns * k] entries and call again.
@@ -227,6 +242,7 @@ int ii2_term_bounds(const uint8_t *term_bytes, const uint64_t *term_off, uint64_
 #define II2_MATCH_MAX_PATTERNS 64u   /* patterns per call; more: II2_ERANGE (callers chunk) */
 enum { II2_MATCH_CONTAINS = 0, II2_MATCH_SUFFIX = 1, II2_MATCH_GLOB = 2 };
 #define II2_MATCH_NOCASE 0x80u       /* OR-ed into a kind: ASCII A-Z and a-z compare equal, no other byte folds */
+#define II2_MATCH_UTF8 0x08u         /* OR-ed into a kind or into ii2_dict_fuzzy's flags: positions are UTF-8 symbols, not bytes */
 typedef struct {
     uint64_t n_terms;     /* terms tested, summed over the k dictionaries */
     uint64_t n_matched;   /* (pattern, term) pairs that matched */
@@ -240,13 +256,19 @@ int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
                    uint32_t *run_dict /* may be NULL */, uint64_t cap, ii2_match_stats *stats /* may be NULL */);
 /* The matchers' arithmetic, host only (no GPU needed): one pattern of `kind` (as above, II2_MATCH_NOCASE included) against one
  * term by the functions the kernel runs - the same parse, the same three matchers.  *match = 0 / 1.  II2_EINVAL: a NULL output,
- * NULL pat with pat_len > 0, NULL term with term_len > 0, an unknown kind, a trailing `\`.  II2_ERANGE: pat_len above
- * II2_MATCH_MAX_PATTERN. */
+ * NULL pat with pat_len > 0, NULL term with term_len > 0, an unknown kind, a trailing `\`, an ill-formed pattern under
+ * II2_MATCH_UTF8.  II2_ERANGE: pat_len above II2_MATCH_MAX_PATTERN. */
 int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const uint8_t *term, uint64_t term_len, int *match);
+/* The decoder's arithmetic, host only (no GPU needed): the symbols of bytes[0 .. len) by the one decoder the kernels run under
+ * II2_MATCH_UTF8 (the rule above).  *n_symbols is always the full count; symbols (may be NULL with cap == 0) receives the first
+ * min(cap, *n_symbols) of them; *well_formed (may be NULL) = 1 when every byte belongs to a well-formed sequence - what a pattern
+ * must be.  II2_EINVAL: a NULL n_symbols, NULL bytes with len > 0, NULL symbols with cap > 0. */
+int ii2_utf8_decode(const uint8_t *bytes, uint64_t len, uint32_t *symbols /* may be NULL */, uint64_t cap, uint64_t *n_symbols,
+                    int *well_formed /* may be NULL */);
 /* Typo-tolerant term search in k resident dictionaries: every term within an edit distance of a pattern, as list ranges for the
  * range entry points - the third mode of a search front end beside ii2_dict_find and ii2_dict_match (Lucene's FuzzyQuery; the
  * reference's dictionary library answers it with a Levenshtein automaton over the FST).  The dictionaries are scanned whole; all
- * arrays are host memory.  Everything compares bytes, as ii2_dict_match does (no UTF-8).
+ * arrays are host memory.  Everything compares bytes, as ii2_dict_match does, unless a pattern carries II2_MATCH_UTF8.
  * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) and matches a term when BOTH hold: the term's first pat_prefix[p] bytes
  * equal the pattern's first pat_prefix[p] bytes (Lucene's prefix_length: stripping a common prefix changes no distance; a term
  * shorter than the prefix does not match), and the edit distance between the whole pattern and the whole term is at most
@@ -255,15 +277,24 @@ int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const ui
  *                        Levenshtein, the default) swapping two adjacent bytes costs 1, and no substring is edited twice -
  *                        `ca` to `abc` is 3, not 2;
  *   II2_MATCH_NOCASE     ASCII A-Z and a-z compare equal, in the prefix test and in the distance; no other byte folds.
- * The empty pattern has distance term_len to every term.
+ *   II2_MATCH_UTF8       pattern and term are read as sequences of symbols (ii2_dict_match's rule above: a code point per
+ *                        well-formed sequence, one symbol per ill-formed byte of a term) and every "byte" of this contract is a
+ *                        symbol: the distance, Levenshtein or optimal string alignment, is taken between the two symbol
+ *                        sequences (`cafe` is 1 edit from the 5 bytes of cafe with an acute e, not 2), pat_prefix[p] counts
+ *                        symbols (above the pattern's symbol count: II2_EINVAL), the length filter compares symbol counts and
+ *                        n_tested counts the pairs that pass the filters so defined.  The pattern must be well-formed UTF-8,
+ *                        else II2_EINVAL.  II2_MATCH_NOCASE still folds ASCII A-Z only, and the limit stays
+ *                        II2_FUZZY_MAX_PATTERN BYTES.  Flagged and unflagged patterns may be mixed in one call, each with its
+ *                        own rule.
+ * The empty pattern has distance term_len (symbols under II2_MATCH_UTF8) to every term.
  * The answer's layout is exactly ii2_dict_match's: pair (p, s) is entry p * k + s, its runs are the maximal stretches of
  * consecutive matching term indices, in run_off / run_first / run_end / run_dict - so pattern p is ONE group of every range entry
  * point.  The runs carry no distance, on purpose: a caller that wants tiers sends the same pattern with distances 0, 1 and 2; the
  * three groups nest, so in ii2_topk_weighted_ranges their weights add up for the closer terms.
  * Every check runs before anything is launched or written: II2_EINVAL for a NULL array with n_patterns > 0 (pat_prefix,
  * pat_flags, run_dict and stats excepted; the three run arrays may be NULL with cap == 0), k == 0 or k > II2_MAX_LISTS, a
- * dictionary that is NULL or of another device, pat_off that does not start at 0 or descends, a flag bit other than the two
- * above, a pat_prefix[p] above the pattern's length; II2_ERANGE for a pattern above II2_FUZZY_MAX_PATTERN bytes, more than
+ * dictionary that is NULL or of another device, pat_off that does not start at 0 or descends, a flag bit other than the three
+ * above, a pat_prefix[p] above the pattern's length, an ill-formed pattern under II2_MATCH_UTF8; II2_ERANGE for a pattern above II2_FUZZY_MAX_PATTERN bytes, more than
  * II2_FUZZY_MAX_PATTERNS patterns (callers chunk) or a dictionary of 2^31 terms or more.  n_patterns == 0, or no term in any
  * dictionary: run_off is all zero and nothing is launched.  More runs than cap: II2_ECAPACITY with run_off and *stats completely
  * filled and the three run arrays untouched - allocate run_off[n_patterns * k] entries and call again.
@@ -273,11 +304,13 @@ int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const ui
  * by more than the distance, or whose prefix differs, are skipped before it (stats->n_tested counts the rest).  Options:
  * "fuzzy.stage" (default 1): a workgroup copies the bytes of its 256 terms into LDS first when they fit; 0: every thread reads
  * global memory.  "fuzzy.wide" (default 0): the 32-bit instance of the kernel runs when every pattern of the call holds at most
- * 32 bytes; 1: always the 64-bit one.  Results are identical under all four settings. */
+ * 32 positions (symbols under II2_MATCH_UTF8, bytes otherwise); 1: always the 64-bit one.  Results are identical under all four
+ * settings.  A call in which no pattern carries II2_MATCH_UTF8 launches the kernels it always did; with one, the instances that
+ * decode the term as they read it run (stats->n_utf8 > 0). */
 #define II2_FUZZY_MAX_PATTERN  64u   /* bytes per pattern; longer: II2_ERANGE */
 #define II2_FUZZY_MAX_PATTERNS 16u   /* patterns per call; more: II2_ERANGE (callers chunk) */
 #define II2_FUZZY_TRANSPOSE    0x01u /* an adjacent transposition costs 1 (optimal string alignment) */
-/* II2_MATCH_NOCASE (0x80) is the only other flag */
+/* II2_MATCH_NOCASE (0x80) and II2_MATCH_UTF8 (0x08) are the only other flags */
 typedef struct {
     uint64_t n_terms;    /* terms read, summed over the k dictionaries */
     uint64_t n_matched;  /* (pattern, term) pairs within distance */
@@ -285,7 +318,7 @@ typedef struct {
     uint64_t n_tested;   /* pairs that passed the length and prefix filter and ran the recurrence */
     uint32_t n_staged, n_global;   /* workgroups that matched out of LDS / from global memory */
     uint32_t word_bits;  /* 32 or 64: the instance that ran; 0 when nothing was launched */
-    uint32_t pad;
+    uint32_t n_utf8;     /* patterns of the call that carry II2_MATCH_UTF8; 0: the byte instances ran */
 } ii2_fuzzy_stats;       /* 48 bytes */
 int ii2_dict_fuzzy(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint32_t n_patterns, const uint8_t *pat_bytes,
                    const uint64_t *pat_off /* n_patterns + 1, from 0 */, const uint8_t *pat_dist /* n_patterns: max distance 0 .. 255 */,
@@ -294,16 +327,17 @@ int ii2_dict_fuzzy(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
                    uint32_t *run_dict /* may be NULL */, uint64_t cap, ii2_fuzzy_stats *stats /* may be NULL */);
 /* The matcher's arithmetic, host only (no GPU needed): one pattern against one term by the functions the kernel runs - the same
  * parse, the same filters, the same recurrence.  *match = 0 / 1 as the kernel decides it; *dist (may be NULL) = the exact
- * distance under `flags`, whatever prefix and max_dist are and for any term length.  prefix and max_dist are 32-bit here and any
- * max_dist is accepted.  II2_EINVAL: a NULL match, NULL pat with pat_len > 0, NULL term with term_len > 0, a flag bit other than
- * the two above, prefix above pat_len.  II2_ERANGE: pat_len above II2_FUZZY_MAX_PATTERN. */
+ * distance under `flags` (in symbols under II2_MATCH_UTF8), whatever prefix and max_dist are and for any term length.  prefix and
+ * max_dist are 32-bit here and any max_dist is accepted.  II2_EINVAL: a NULL match, NULL pat with pat_len > 0, NULL term with
+ * term_len > 0, a flag bit other than the three above, prefix above the pattern's length (pat_len, or its symbols), an ill-formed
+ * pattern under II2_MATCH_UTF8.  II2_ERANGE: pat_len above II2_FUZZY_MAX_PATTERN. */
 int ii2_term_fuzzy(uint32_t flags, const uint8_t *pat, uint64_t pat_len, uint32_t prefix, uint32_t max_dist, const uint8_t *term,
                    uint64_t term_len, int *match, uint32_t *dist /* may be NULL */);
 /* Regular-expression term search in k resident dictionaries: every term a pattern matches, as list ranges for the range entry
  * points - the fourth mode of a search front end beside ii2_dict_find, ii2_dict_match and ii2_dict_fuzzy (Lucene's RegexpQuery;
  * the reference's dictionary library answers it with a regex automaton walked over the FST).  It replaces the loop over every term
  * of every segment with a host regex library that a front end would run otherwise.  The dictionaries are scanned whole; all
- * arrays are host memory.  Everything compares bytes, as ii2_dict_match does (no UTF-8).
+ * arrays are host memory.  Everything compares bytes (no UTF-8: II2_MATCH_UTF8 is II2_EINVAL here, as any unknown flag bit).
  * Pattern p is pat_bytes[pat_off[p] .. pat_off[p + 1]) and matches a term when it matches the WHOLE term (GLOB's rule, vellum's
  * and Lucene's; write `.*foo.*` for "contains").  Where a pattern is accepted it means what Python's
  * re.fullmatch(pattern, term, re.DOTALL) means on bytes:

@@ -47,11 +47,12 @@ class MatchStats(C.Structure):
 II2_MATCH_MAX_PATTERN, II2_MATCH_MAX_PATTERNS = 64, 64
 II2_MATCH_CONTAINS, II2_MATCH_SUFFIX, II2_MATCH_GLOB = range(3)
 II2_MATCH_NOCASE = 0x80
+II2_MATCH_UTF8 = 0x08
 
 
 class FuzzyStats(C.Structure):
     _fields_ = [("n_terms", C.c_uint64), ("n_matched", C.c_uint64), ("n_runs", C.c_uint64), ("n_tested", C.c_uint64), ("n_staged", C.c_uint32),
-                ("n_global", C.c_uint32), ("word_bits", C.c_uint32), ("pad", C.c_uint32)]
+                ("n_global", C.c_uint32), ("word_bits", C.c_uint32), ("n_utf8", C.c_uint32)]
 
 
 II2_FUZZY_MAX_PATTERN, II2_FUZZY_MAX_PATTERNS = 64, 16
@@ -138,6 +139,7 @@ PROTOTYPES = {
     "ii2_term_fuzzy": (C.c_int, [C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_int), u32p]),
     "ii2_dict_regex": (C.c_int, [vp, C.c_uint32, vpp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, C.POINTER(RegexStats)]),
     "ii2_term_regex": (C.c_int, [C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_int), u32p]),
+    "ii2_utf8_decode": (C.c_int, [vp, C.c_uint64, u32p, C.c_uint64, u64p, C.POINTER(C.c_int)]),
     "ii2_dict_build": (C.c_int, [vp, C.c_uint64, vp, vp, C.c_int, vpp, vp, C.POINTER(DictBuildStats)]),
     "ii2_dict_info": (C.c_int, [vp, u64p, u64p]),
     "ii2_dict_export": (C.c_int, [vp, vp, vp, vp]),

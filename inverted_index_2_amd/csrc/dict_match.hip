@@ -38,7 +38,9 @@ namespace ii2 {
 static_assert(II2_MATCH_MAX_PATTERNS == 64, "a match word is 64 bits, a wave's lane p counts pattern p");
 
 // workgroup wg: terms [t0, t0 + 256) of its dictionary.  words[term_first[s] + t] = the match word of term t; the two tables and
-// their counter row are match_runs_tail's.
+// their counter row are match_runs_tail's.  UTF8 = false is the kernel of every call without II2_MATCH_UTF8; the other instance
+// runs when a pattern of the call carries the flag, and its glob steps over the term by symbols for those patterns (match_device.h).
+template <bool UTF8>
 __global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const MatchPattern *__restrict__ pats, uint32_t stage_on, uint32_t n_wg,
                                                            uint64_t *__restrict__ words, uint32_t *__restrict__ tab_st, uint32_t *__restrict__ tab_en) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[MATCH_STAGE];
@@ -50,11 +52,11 @@ __global__ __launch_bounds__(DM_THREADS) void k_dict_match(MatchDicts d, const M
     const uint32_t t = ts.t0 + threadIdx.x;
     uint64_t m = 0;
     if (t < ts.t1) {
-        m = ts.own(t, [&](const uint8_t *term, uint64_t len) { return match_word(lp, P, term, len); });
+        m = ts.own(t, [&](const uint8_t *term, uint64_t len) { return match_word<UTF8>(lp, P, term, len); });
         words[d.term_first[s] + t] = m;
     }
     match_runs_tail<1>(P, wg, n_wg, ts.have_left, ts.have_right, m, 0u, ts.staged, [&](uint32_t right, uint32_t p) {
-        return ts.neighbour(right, [&](const uint8_t *term, uint64_t len) { return match_term(lp[p], term, len); });
+        return ts.neighbour(right, [&](const uint8_t *term, uint64_t len) { return match_term<UTF8>(lp[p], term, len); });
     }, tab_st, tab_en);
 }
 
@@ -191,14 +193,19 @@ int ii2_dict_match(ii2_ctx *ctx, uint32_t k, const ii2_dict *const *dicts, uint3
                    ii2_match_stats *stats) {
     static const MatchCallTexts texts = {"ii2_dict_match", II2_MATCH_MAX_PATTERNS, "ii2_dict_match: more than 64 patterns in one call",
                                          "ii2_dict_match: a pattern of more than 64 bytes",
-                                         "ii2_dict_match: an unknown kind, or a glob that ends in a lone backslash"};
+                                         "ii2_dict_match: an unknown kind, a glob that ends in a lone backslash, or an ill-formed pattern under II2_MATCH_UTF8"};
     MatchSums sums;                                     // one counter row: {matched pairs, staged workgroups}
+    bool utf8 = false;                                  // a pattern carries II2_MATCH_UTF8
     const int rc = match_call<MatchPattern>(ctx, texts, MatchCallIn{k, dicts, n_patterns, pat_bytes, pat_off, pat_kind},
                                             MatchRunsOut{run_off, run_first, run_end, run_dict, cap}, stats, 1,
-        [&](uint32_t p, const uint8_t *bytes, uint64_t len, MatchPattern *out) { return match_parse(pat_kind[p], bytes, len, out); },
+        [&](uint32_t p, const uint8_t *bytes, uint64_t len, MatchPattern *out) {
+            const int rc = match_parse(pat_kind[p], bytes, len, out);
+            if (!rc && out->utf8) utf8 = true;
+            return rc;
+        },
         [&](const MatchDicts &md, const MatchPattern *d_pats, uint32_t n_wg, uint64_t *d_words, uint32_t *d_tab_st, uint32_t *d_tab_en) {
-            hipLaunchKernelGGL(k_dict_match, dim3(n_wg), dim3(DM_THREADS), 0, ctx->stream, md, d_pats, ctx->opt_match_stage ? 1u : 0u, n_wg, d_words, d_tab_st,
-                               d_tab_en);
+            hipLaunchKernelGGL(utf8 ? k_dict_match<true> : k_dict_match<false>, dim3(n_wg), dim3(DM_THREADS), 0, ctx->stream, md, d_pats,
+                               ctx->opt_match_stage ? 1u : 0u, n_wg, d_words, d_tab_st, d_tab_en);
         }, &sums);
     if ((rc && rc != II2_ECAPACITY) || !sums.n_wg || !stats) return rc;
     stats->n_terms = sums.n_terms;
@@ -215,7 +222,24 @@ int ii2_term_match(uint32_t kind, const uint8_t *pat, uint64_t pat_len, const ui
     MatchPattern m;
     const int rc = match_parse(kind, pat, pat_len, &m);
     if (rc) return rc;
-    *match = match_term(m, term, term_len) ? 1 : 0;
+    *match = match_term<true>(m, term, term_len) ? 1 : 0;
+    return II2_OK;
+}
+
+// host only: a byte string's symbols by the decoder the kernels run under II2_MATCH_UTF8 (utf8_device.h)
+int ii2_utf8_decode(const uint8_t *bytes, uint64_t len, uint32_t *symbols, uint64_t cap, uint64_t *n_symbols, int *well_formed) {
+    if (!n_symbols || (len && !bytes) || (cap && !symbols)) return II2_EINVAL;
+    uint64_t n = 0;
+    bool fine = true;
+    for (uint64_t i = 0; i < len; n++) {
+        uint32_t sym;
+        const uint32_t w = utf8_at(bytes, i, len, &sym);
+        if (bytes[i] >= 0x80u && w == 1u) fine = false;
+        if (n < cap) symbols[n] = sym;
+        i += w;
+    }
+    *n_symbols = n;
+    if (well_formed) *well_formed = fine ? 1 : 0;
     return II2_OK;
 }
 

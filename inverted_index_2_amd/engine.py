@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import II2_FUZZY_TRANSPOSE, FuzzyStats  # noqa: F401
+from ._lib import II2_FUZZY_TRANSPOSE, II2_MATCH_UTF8, FuzzyStats  # noqa: F401
 from ._lib import RegexStats
 from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
@@ -186,7 +186,8 @@ def merge_event_names():
 
 def term_match(kind: int, pattern: bytes, term: bytes) -> bool:
     """One pattern against one term by the functions ii2_dict_match's kernel runs (ii2_term_match).  kind: II2_MATCH_CONTAINS /
-    SUFFIX / GLOB, optionally | II2_MATCH_NOCASE.  Needs no context and no GPU."""
+    SUFFIX / GLOB, optionally | II2_MATCH_NOCASE and / or II2_MATCH_UTF8 (the glob's `?` and `*` take whole UTF-8 symbols of the
+    term; the pattern must be well-formed UTF-8).  Needs no context and no GPU."""
     lib = _lib.load()
     m = C.c_int(-1)
     rc = lib.ii2_term_match(int(kind), C.c_char_p(bytes(pattern)) if pattern else None, len(pattern), C.c_char_p(bytes(term)) if term else None,
@@ -199,7 +200,8 @@ def term_match(kind: int, pattern: bytes, term: bytes) -> bool:
 def term_fuzzy(pattern: bytes, term: bytes, max_dist: int, prefix: int = 0, flags: int = 0):
     """One pattern against one term by the functions ii2_dict_fuzzy's kernel runs (ii2_term_fuzzy): (match, dist) - whether the
     term shares the pattern's first `prefix` bytes and lies within `max_dist` edits, and the exact distance whatever those two
-    are.  flags: 0, II2_FUZZY_TRANSPOSE and / or II2_MATCH_NOCASE.  Needs no context and no GPU."""
+    are.  flags: 0, II2_FUZZY_TRANSPOSE, II2_MATCH_NOCASE and / or II2_MATCH_UTF8 - then prefix and distance count UTF-8 symbols
+    (a code point, or one ill-formed byte of the term), and the pattern must be well-formed UTF-8.  Needs no context and no GPU."""
     lib = _lib.load()
     m, d = C.c_int(-1), C.c_uint32(0)
     rc = lib.ii2_term_fuzzy(int(flags), C.c_char_p(bytes(pattern)) if pattern else None, len(pattern), int(prefix), int(max_dist),
@@ -207,6 +209,20 @@ def term_fuzzy(pattern: bytes, term: bytes, max_dist: int, prefix: int = 0, flag
     if rc:
         raise II2Error(rc, "ii2_term_fuzzy")
     return bool(m.value), d.value
+
+
+def utf8_decode(data: bytes):
+    """The symbols of a byte string by the decoder the kernels run under II2_MATCH_UTF8 (ii2_utf8_decode): (symbols, well_formed).
+    A well-formed sequence is its code point, any other byte b alone is 0xDC00 + b - bytes.decode("utf-8", "surrogateescape").
+    Needs no context and no GPU."""
+    lib = _lib.load()
+    data = bytes(data)
+    n, ok = C.c_uint64(0), C.c_int(-1)
+    out = (C.c_uint32 * max(len(data), 1))()
+    rc = lib.ii2_utf8_decode(C.c_char_p(data) if data else None, len(data), out, len(data), C.byref(n), C.byref(ok))
+    if rc:
+        raise II2Error(rc, "ii2_utf8_decode")
+    return list(out[:n.value]), bool(ok.value)
 
 
 def term_regex(pattern: bytes, term: bytes, flags: int = 0):
@@ -535,7 +551,8 @@ class Context:
     def dict_match(self, dicts, patterns, kind=II2_MATCH_CONTAINS):
         """Substring, suffix and wildcard term search on the device (ii2_dict_match): every pattern of `patterns` (bytes, at
         most 64 of at most 64 bytes) in every one of the k resident dictionaries.  kind: II2_MATCH_CONTAINS / SUFFIX / GLOB,
-        optionally | II2_MATCH_NOCASE - one for all the patterns or one per pattern.  Returns (run_off, run_first, run_end,
+        optionally | II2_MATCH_NOCASE and / or II2_MATCH_UTF8 (`?` and `*` take whole UTF-8 symbols of the term) - one for all the
+        patterns or one per pattern.  Returns (run_off, run_first, run_end,
         run_dict, stats): pair (p, s) owns the runs run_off[p * k + s] .. run_off[p * k + s + 1] - 1, run j is the terms
         [run_first[j], run_end[j]) of dictionary run_dict[j]; the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1,
         are one group of the range entry points.  A result that outgrows the first buffer takes a second call of the exact size."""
@@ -572,7 +589,8 @@ class Context:
     def dict_fuzzy(self, dicts, patterns, max_dist, prefix=0, flags=0):
         """Typo-tolerant term search on the device (ii2_dict_fuzzy): every pattern of `patterns` (bytes, at most 16 of at most 64
         bytes) in every one of the k resident dictionaries.  A term matches when it shares the pattern's first `prefix` bytes and
-        lies within `max_dist` edits (0 .. 255) of it; flags: 0, II2_FUZZY_TRANSPOSE and / or II2_MATCH_NOCASE.  Each of the
+        lies within `max_dist` edits (0 .. 255) of it; flags: 0, II2_FUZZY_TRANSPOSE, II2_MATCH_NOCASE and / or II2_MATCH_UTF8 (prefix,
+        edits and the length filter count UTF-8 symbols; stats.n_utf8 = the patterns that carry it).  Each of the
         three is one value for all the patterns or one per pattern.  Returns (run_off, run_first, run_end, run_dict, stats), laid
         out as dict_match's: the runs of pattern p, run_off[p * k] .. run_off[(p + 1) * k] - 1, are one group of the range
         entry points.  A result that outgrows the first buffer takes a second call of the exact size."""

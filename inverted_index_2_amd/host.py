@@ -194,8 +194,8 @@ class _Target:
     def match_search(self, patterns: List[bytes], kind: int = 0) -> Dict[bytes, List[int]]:
         """Substring, suffix and wildcard search (MatchSearch): {pattern: ids under any term it matches}, over every segment (of
         every shard); a pattern that matches no term has no entry.  kind: II2_MATCH_CONTAINS (0) / SUFFIX (1) / GLOB (2),
-        optionally | II2_MATCH_NOCASE (0x80), for all the patterns; any number of patterns (the device call takes 64 at a time).
-        Like read, no tombstone filter."""
+        optionally | II2_MATCH_NOCASE (0x80) and / or II2_MATCH_UTF8 (0x08: `?` and `*` take whole UTF-8 symbols), for all the
+        patterns; any number of patterns (the device call takes 64 at a time).  Like read, no tombstone filter."""
         blob, off = _flat(list(patterns))
         n = C.c_uint64()
         self._ck(self.lib.ii2h_match_search(self.h, blob.ctypes.data, off.ctypes.data, len(patterns), int(kind), C.byref(n)))
@@ -211,7 +211,8 @@ class _Target:
     def fuzzy_search(self, terms: List[bytes], max_dist: int, prefix: int = 0, flags: int = 0) -> Dict[bytes, List[int]]:
         """Typo-tolerant search (FuzzySearch): {query term: ids under any term within `max_dist` edits of it}, over every segment
         (of every shard); a query term that matches nothing has no entry.  prefix: leading bytes a term must share with the query
-        term (a shorter query term is compared as a whole); flags: II2_FUZZY_TRANSPOSE (1) and / or II2_MATCH_NOCASE (0x80); any
+        term (a shorter query term is compared as a whole); flags: II2_FUZZY_TRANSPOSE (1), II2_MATCH_NOCASE (0x80) and / or II2_MATCH_UTF8
+        (0x08: edits, prefix and the clamp of a shorter query term count UTF-8 symbols, not bytes); any
         number of query terms (the device call takes 16 at a time).  Like read, no tombstone filter."""
         blob, off = _flat(list(terms))
         n = C.c_uint64()

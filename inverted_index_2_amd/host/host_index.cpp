@@ -294,7 +294,7 @@ template <class Runs, class TwoCall> static std::map<Term, std::vector<uint32_t>
 }
 
 // ---- substring, suffix and wildcard search (additive: the reference's FST walks a term from its front only) ----
-// term_runs for the patterns of `kind` (II2_MATCH_*): ii2_dict_match
+// term_runs for the patterns of `kind` (II2_MATCH_*, | II2_MATCH_NOCASE, | II2_MATCH_UTF8: passed through): ii2_dict_match
 template <class Fn> static void match_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t kind,
                                            Fn fn) {
     term_runs(ctx, segs, patterns, II2_MATCH_MAX_PATTERNS, "match search",
@@ -323,7 +323,8 @@ static std::vector<Term> match_terms(ii2_ctx *ctx, const std::vector<std::shared
 
 // ---- typo-tolerant search (additive: what the reference's dictionary library answers with a Levenshtein automaton) ----
 // term_runs for the terms within `max_dist` edits of a pattern that share its first `prefix` bytes (flags: II2_FUZZY_TRANSPOSE,
-// II2_MATCH_NOCASE): ii2_dict_fuzzy.  A pattern shorter than the prefix is compared as a whole.
+// II2_MATCH_NOCASE, II2_MATCH_UTF8 - then edits and prefix count UTF-8 symbols): ii2_dict_fuzzy.  A pattern shorter than the prefix,
+// in bytes or under II2_MATCH_UTF8 in symbols, is compared as a whole.
 template <class Fn> static void fuzzy_runs(ii2_ctx *ctx, const std::vector<std::shared_ptr<Segment>> &segs, const std::vector<Term> &patterns, uint32_t max_dist,
                                            uint32_t prefix, uint32_t flags, Fn fn) {
     if (max_dist > 255 || flags > 255) throw Error("fuzzy search: max_dist and flags are at most 255");
@@ -332,7 +333,13 @@ template <class Fn> static void fuzzy_runs(ii2_ctx *ctx, const std::vector<std::
                   uint64_t *end, uint32_t *which, uint64_t cap) {
                   const std::vector<uint8_t> dist(np, (uint8_t)max_dist), fl(np, (uint8_t)flags);
                   std::vector<uint8_t> pre(np);
-                  for (size_t p = 0; p < np; p++) pre[p] = (uint8_t)std::min<size_t>(prefix, patterns[p0 + p].size());
+                  for (size_t p = 0; p < np; p++) {
+                      const Term &pat = patterns[p0 + p];
+                      uint64_t positions = pat.size();
+                      if (flags & II2_MATCH_UTF8)
+                          ck(ctx, ii2_utf8_decode((const uint8_t *)pat.data(), pat.size(), nullptr, 0, &positions, nullptr), "fuzzy search");
+                      pre[p] = (uint8_t)std::min<uint64_t>(prefix, positions);
+                  }
                   return ii2_dict_fuzzy(ctx, k, dicts, (uint32_t)np, bytes, off, dist.data(), pre.data(), fl.data(), run_off, first, end, which, cap, nullptr);
               }, fn);
 }
@@ -1222,7 +1229,7 @@ class InvertedIndex {
         return out;
     }
     // additive: substring, suffix and wildcard search - map<pattern, ids> of every pattern of `kind` (II2_MATCH_CONTAINS / SUFFIX /
-    // GLOB, | II2_MATCH_NOCASE).  It visits every segment of every shard (a pattern selects no shard): ii2_dict_match over the
+    // GLOB, | II2_MATCH_NOCASE, | II2_MATCH_UTF8).  It visits every segment of every shard (a pattern selects no shard): ii2_dict_match over the
     // segments' resident dictionaries (match_runs), then one OR query per pattern over all its runs in ONE ii2_query_batch call,
     // through two_call, as PrefixSearch does.  A pattern that matches no term has no entry.  Like Read, no tombstone filter.
     std::map<Term, std::vector<uint32_t>> MatchSearch(const std::vector<Term> &patterns, uint32_t kind) const {
@@ -1232,7 +1239,7 @@ class InvertedIndex {
     // additive: the distinct terms the pattern matches, over every segment of every shard, in bytes.Compare order, at most `limit`
     std::vector<Term> MatchTerms(const Term &pattern, uint32_t kind, uint64_t limit) const { return match_terms(ctx_, all_segments(), pattern, kind, limit); }
     // additive: typo-tolerant search - map<query term, ids under any term within `max_dist` edits of it> (flags: II2_FUZZY_TRANSPOSE,
-    // II2_MATCH_NOCASE; `prefix` leading bytes must be equal, Lucene's prefix_length).  It visits every segment of every shard:
+    // II2_MATCH_NOCASE, II2_MATCH_UTF8 - symbols instead of bytes; `prefix` leading bytes must be equal, Lucene's prefix_length).  It visits every segment of every shard:
     // ii2_dict_fuzzy over the segments' resident dictionaries (fuzzy_runs), then one OR query per query term over all its runs in
     // ONE ii2_query_batch call, through two_call, as MatchSearch does.  A term that matches nothing has no entry.  Like Read, no
     // tombstone filter.
