@@ -1280,6 +1280,46 @@ func (c *Ctx) CountRanges(segs []*Segment, listFirst, listEnd []uint64, set unsa
 	return counts, CountStats{uint64(st.n_lists), uint64(st.n_blocks), uint64(st.n_decoded), uint64(st.n_hits), uint32(st.n_windows)}, nil
 }
 
+// ExplainStats mirrors ii2_explain_stats.
+type ExplainStats struct {
+	IDs, Lists, Blocks, Decoded, Hits uint64
+	Windows, Words, Log2Slots         uint32
+}
+
+// ExplainRanges says which groups each doc lies in (ii2_explain_ranges): group g is the ranges groupFirst[g] ..
+// groupFirst[g+1]-1 - lists [listFirst[i], listEnd[i]) of segs[i] - exactly as IntersectRanges takes them.  ids is a device
+// buffer of nIDs doc ids in any order: a query's ascending result or a ranked page (TopkRanges).  Returns nIDs rows of
+// words = ceil(groups / 64) mask words, doc-major: bit g&63 of word i*words + g>>6 is set when ids[i] lies in a list of group g.
+// An id given twice has its mask in its first row and zeros after.  One pass over the groups' blocks, whatever their number.
+func (c *Ctx) ExplainRanges(groupFirst []uint64, segs []*Segment, listFirst, listEnd []uint64, ids unsafe.Pointer, nIDs uint64) ([]uint64, ExplainStats, error) {
+	if len(groupFirst) == 0 || len(listFirst) != len(segs) || len(listEnd) != len(segs) || groupFirst[len(groupFirst)-1] != uint64(len(segs)) {
+		return nil, ExplainStats{}, fmt.Errorf("explain ranges: array lengths disagree")
+	}
+	nGroups := uint64(len(groupFirst) - 1)
+	words := (nGroups + 63) / 64
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	masks := make([]uint64, nIDs*words)
+	var d unsafe.Pointer
+	if rc := C.ii2_dev_alloc(c.h, C.size_t((nIDs*words+1)*8), &d); rc != 0 {
+		return nil, ExplainStats{}, c.err("explain ranges", rc)
+	}
+	var st C.ii2_explain_stats
+	rc := C.ii2_explain_ranges(c.h, C.uint64_t(nGroups), u64ptr(groupFirst), (**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd),
+		(*C.uint32_t)(ids), C.uint64_t(nIDs), (*C.uint64_t)(d), C.uint64_t(nIDs*words), &st)
+	if rc == 0 && len(masks) > 0 {
+		rc = C.ii2_copy_d2h(c.h, unsafe.Pointer(&masks[0]), d, C.size_t(len(masks)*8))
+	}
+	C.ii2_dev_free(c.h, d)
+	if rc != 0 {
+		return nil, ExplainStats{}, c.err("explain ranges", rc)
+	}
+	return masks, ExplainStats{uint64(st.n_ids), uint64(st.n_lists), uint64(st.n_blocks), uint64(st.n_decoded), uint64(st.n_hits),
+		uint32(st.n_windows), uint32(st.n_words), uint32(st.log2_slots)}, nil
+}
+
 // Union replaces PrefixSearch's append + slices.Sort + slices.Compact (inverted_index.go:274-292).
 func (c *Ctx) Union(listOff []uint64, values, removed []uint32) ([]uint32, error) {
 	return c.lists(true, listOff, values, removed)

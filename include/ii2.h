@@ -754,6 +754,52 @@ int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const
                      const uint64_t *list_end, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb,
                      uint64_t *counts, uint64_t counts_cap, ii2_count_stats *stats /* may be NULL */);
 
+/* Which groups each doc of an id array lies in - what ii2_atleast_ranges, the ii2_topk_* calls and a term search's one group of
+ * many lists do not say: highlighting, "matched queries", which 3 of 5 groups gave a score of 3, the d = 0 tier of a fuzzy hit
+ * against its d = 2 tier.  The transpose of ii2_count_ranges: one pass over the groups' blocks, a hit sets a bit in its doc's row.
+ *   - groups and ranges are exactly those of ii2_intersect_ranges (arrays in host memory, group_first[0] = 0; segments and views
+ *     alike; a list may appear in any number of ranges and groups; ranges may overlap; empty ranges, empty lists and empty groups
+ *     are allowed).  There is no group_not and no tomb: an excluded group is one more group whose bit the caller reads, and the
+ *     ids are given, not filtered.
+ *   - the ids: d_ids[n_ids], a device array of this context's device, IN ANY ORDER - a boolean query's ascending result or a
+ *     ranked page (score-descending) alike.
+ *   - the masks: d_masks (device) receives n_ids * n_words 64-bit words, doc-major, n_words = ceil(n_groups / 64): bit g & 63 of
+ *     word i * n_words + (g >> 6) is set exactly when d_ids[i] lies in at least one list of group g.  The bits at and above
+ *     n_groups in a row's last word are 0.
+ *   - an id that is repeated: its FIRST row holds its mask, every later row is all zero (deterministic).  A repeated id never
+ *     causes an access outside the call's buffers.
+ *   - n_ids == 0 or n_groups == 0: nothing is launched or written, the device pointers may be NULL.  No group owns a block, or the
+ *     ids' span misses the lists' span: the masks are zeroed and n_decoded = 0.
+ *   - every check runs before anything is launched or written; stats is written only on success.  II2_EINVAL: a NULL array with
+ *     something to read or write, bad ranges (rejected as ii2_count_ranges rejects them, under this entry point's name),
+ *     group_first not ascending from 0, a segment of another device.  II2_ERANGE: n_ids > II2_EXPLAIN_MAX_IDS (the pointer is
+ *     not read), 2^32 - 2 blocks or ranges, 2^32 - 1 groups.  II2_ECAPACITY: masks_cap < n_ids * n_words, nothing is written.
+ * The ids are inserted into an open-addressing table of (id, row) entries in workspace - 1 << log2_slots slots, the smallest
+ * power of two >= 2 * n_ids and at least 64, linear probing from ii2_explain_slot(id), the smaller row winning a repeated id - and
+ * marked into the per-context doc bitmap of ii2_union_ranges, window by window over the doc span that the ids and the lists share
+ * (option union.many_window_log2); then every block of the groups that can hold one of them is decoded (blocks that meet no
+ * marked 2048-doc chunk are not read: option count.summary_skip), and each id whose bit is marked looks its row up and ORs its
+ * group's bit in.  The bitmap and its summary are all zero again when the call returns.  The call waits at most twice (the spans,
+ * the stats).  It is not a set operation: it takes no kernel path (ii2_ctx_paths). */
+#define II2_EXPLAIN_MAX_IDS (1u << 24)   /* ids per call; more: II2_ERANGE (rows are independent: callers chunk) */
+typedef struct {
+    uint64_t n_ids;      /* rows */
+    uint64_t n_lists;    /* lists named by the ranges */
+    uint64_t n_blocks;   /* DV1 blocks those lists own */
+    uint64_t n_decoded;  /* blocks decoded, summed over the windows */
+    uint64_t n_hits;     /* (doc, group) bits set = popcount of all masks */
+    uint32_t n_windows;  /* doc windows processed (0: nothing was marked) */
+    uint32_t n_words;    /* mask words per doc = ceil(n_groups / 64) */
+    uint32_t log2_slots; /* size of the id -> row table; 0 when nothing was launched */
+    uint32_t pad;
+} ii2_explain_stats;     /* 56 bytes */
+int ii2_explain_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs,
+                       const uint64_t *list_first, const uint64_t *list_end, const uint32_t *d_ids, uint64_t n_ids,
+                       uint64_t *d_masks, uint64_t masks_cap, ii2_explain_stats *stats /* may be NULL */);
+/* Host only, no GPU: the slot an id's probe starts at in a table of 1 << log2_slots entries, by the function the kernels run
+ * (a multiplicative hash; tests choose colliding ids with it).  log2_slots outside 1 .. 31 or slot == NULL: II2_EINVAL. */
+int ii2_explain_slot(uint32_t id, uint32_t log2_slots, uint32_t *slot);
+
 /* THRESHOLD query - "docs that lie in at least min_match of these n groups" (minimum-should-match, n-gram / fuzzy term matching,
  * "any two of these tags"): the ascending, duplicate-free ids that lie in at least one list of AT LEAST min_match required groups
  * and in NO list of ANY excluded group, minus the tombstones when tomb != NULL.  An id that sits in several lists of one group

@@ -78,6 +78,14 @@ class CountStats(C.Structure):
                 ("n_windows", C.c_uint32)]
 
 
+class ExplainStats(C.Structure):
+    _fields_ = [("n_ids", C.c_uint64), ("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64),
+                ("n_windows", C.c_uint32), ("n_words", C.c_uint32), ("log2_slots", C.c_uint32), ("pad", C.c_uint32)]
+
+
+II2_EXPLAIN_MAX_IDS = 1 << 24
+
+
 class AtleastStats(C.Structure):
     _fields_ = [("n_counted", C.c_uint64), ("bound", C.c_uint64), ("form", C.c_uint32), ("n_planes", C.c_uint32),
                 ("n_windows", C.c_uint32), ("n_late", C.c_uint32)]
@@ -173,6 +181,8 @@ PROTOTYPES = {
     "ii2_query_batch": (C.c_int, [vp, C.c_uint64, u8p, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_query_batch_groups": (C.c_int, [vp, C.c_uint64, u64p, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_count_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, C.c_uint64, vp, u64p, C.c_uint64, C.POINTER(CountStats)]),
+    "ii2_explain_ranges": (C.c_int, [vp, C.c_uint64, u64p, vpp, u64p, u64p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(ExplainStats)]),
+    "ii2_explain_slot": (C.c_int, [C.c_uint32, C.c_uint32, u32p]),
     "ii2_atleast_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, C.c_uint32, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p, C.POINTER(AtleastStats)]),
     "ii2_atleast_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, u32p, u64p, u64p]),
     "ii2_atleast_word": (C.c_int, [C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]),

@@ -719,6 +719,23 @@ hipError_t launch_cr_edges(const CountParams &p, hipStream_t s);
 hipError_t launch_cr_mark(const CountParams &p, hipStream_t s);
 hipError_t launch_cr_count(const CountParams &p, bool every_doc, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
+// which groups each doc of an id array lies in (explain_ranges.hip): the count's walk with another sink - a hit ORs its group's bit
+// into the row of its doc, which an open-addressing table of (id << 32 | row) entries finds (empty slots are all-ones)
+constexpr uint64_t EX_EMPTY = ~0ull;
+// the slot an id's probe starts at in a table of 1 << log2_slots entries, 1 <= log2_slots <= 31 (ii2_explain_slot)
+__host__ __device__ static inline uint32_t ex_slot(uint32_t id, uint32_t log2_slots) { return (id * 0x9E3779B1u) >> (32u - log2_slots); }
+struct ExplainParams {
+    CountParams c;               // the walk and the mark: set = the ids (any order), out_first = the group of each range; counts, edges unused
+    unsigned long long *table;   // [1 << log2_slots]
+    unsigned long long *masks;   // [n_set * n_words] doc-major, zeroed by the host
+    unsigned long long *hits;    // [CR_DECODED_SLOTS] mask bits that were clear when their hit set them
+    uint32_t *span;              // [2] the ids' minimum (starts all-ones) and maximum (starts 0)
+    uint32_t log2_slots;
+    uint32_t n_words;            // mask words per doc
+};
+hipError_t launch_ex_prepare(const ExplainParams &p, hipStream_t s);
+hipError_t launch_ex_match(const ExplainParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
 }  // namespace ii2
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held
 void ii2_lookback_forget(ii2_ctx *ctx);      // api.cpp: the context's stream is about to be destroyed

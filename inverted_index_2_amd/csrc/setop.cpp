@@ -795,6 +795,21 @@ static uint32_t um_per_wave(const ii2_ctx *ctx, uint64_t n_blocks) {
     return (uint32_t)std::max<uint64_t>(1, (n_blocks + target_waves - 1) / target_waves);
 }
 
+// the doc span of the ranges' non-empty lists from the segments' mirrored spans; false when a segment has none (the caller then
+// reduces over the blocks: k_um_bounds)
+static bool mirrored_span(const std::vector<RangeIn> &rs, uint32_t *lo, uint32_t *hi) {
+    for (const RangeIn &q : rs) {
+        const ii2_seg *s = q.seg;
+        if (!spans_mirrored(s)) return false;
+        for (uint64_t j = q.l0; j < q.l1; j++) {
+            if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
+            *lo = std::min(*lo, s->h_spans[3 * j]);
+            *hi = std::max(*hi, s->h_spans[3 * j + 2]);
+        }
+    }
+    return true;
+}
+
 // The block-wise OR (union_many.hip) of the ranges' blocks: per window of the doc range mark, count, scan, compact.
 static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_blocks, const ii2_tomb *tomb, uint32_t *d_out, uint64_t cap,
                       uint64_t *count) {
@@ -808,16 +823,7 @@ static int union_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, uint64_t n_b
     um_desc_fill(rs, 0, nr, (uint8_t *)ctx->h_um);
     // the doc range: from the lists' mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    bool mirrored = true;
-    for (const RangeIn &q : rs) {
-        const ii2_seg *s = q.seg;
-        if (!spans_mirrored(s)) { mirrored = false; break; }
-        for (uint64_t j = q.l0; j < q.l1; j++) {
-            if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
-            lo = std::min(lo, s->h_spans[3 * j]);
-            hi = std::max(hi, s->h_spans[3 * j + 2]);
-        }
-    }
+    const bool mirrored = mirrored_span(rs, &lo, &hi);
     const uint64_t W = um_window(ctx);                          // docs per window
     // workspace: descriptors, counts, offsets, scan temp, the running offset and the bounds (sized for the largest window possible
     // before the bounds are known: min(W, 2^32) docs)
@@ -947,6 +953,39 @@ static int count_done(const CountIn &in, uint64_t *counts, ii2_count_stats *stat
     return II2_OK;
 }
 
+// The windows of a walk that tests ids against a marked doc set (count_many, explain_many): the docs [lo, hi] in windows of
+// um_window(ctx) docs, per window k_cr_mark of p.set, `walk` - the launch that reads the marks through p's window fields, set here -
+// and k_ir_clear.  *n_win grows by the windows run.
+template <class Walk>
+static int marked_windows(ii2_ctx *ctx, const char *who, CountParams &p, uint32_t lo, uint32_t hi, uint32_t *n_win, Walk walk) {
+    hipStream_t st = ctx->stream;
+    const uint64_t W = um_window(ctx);
+    const uint32_t base = lo & ~2047u;                          // the summary's bits are the docs' 2048-doc chunks: doc >> 11
+    const uint64_t span = (uint64_t)hi - base + 1;
+    if (int rc = um_scratch_reserve(ctx, who, span, W)) return rc;
+    for (uint64_t wlo = base; wlo <= hi; wlo += W, ++*n_win) {
+        UnionManyParams wp;
+        um_set_window(ctx, wp, wlo, std::min<uint64_t>(W, (uint64_t)hi - wlo + 1));
+        p.win_lo = wp.win_lo;
+        p.win_docs = wp.win_docs;
+        p.n_sum = wp.n_sum;
+        p.bitmap = wp.bitmap;
+        p.summary = wp.summary;
+        p.doc_lo = std::max(lo, p.win_lo);
+        p.doc_hi = (uint32_t)std::min<uint64_t>(hi, wlo + p.win_docs - 1);
+        IrParams ip;
+        std::memset(&ip, 0, sizeof ip);
+        ip.n_sum = p.n_sum;
+        ip.bitmap = p.bitmap;
+        ip.summary = p.summary;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
+        HIP_TRY(ctx, launch_cr_mark(p, st));
+        HIP_TRY(ctx, walk());
+        HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
+    }
+    return II2_OK;
+}
+
 // The block-wise count (count_ranges.hip) of the ranges' blocks against d_set - per window of the doc span that the set and the
 // lists share mark, count, clear - or, with d_set == NULL, against "every doc" minus the tombstones in one launch.  At most two
 // waits: the span fetch and the final read.
@@ -968,17 +1007,7 @@ static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, ui
     uint32_t *h_words = (uint32_t *)(h + up_bytes);
     // the lists' doc span: from the mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    bool mirrored = true;
-    if (!every_doc)
-        for (const RangeIn &q : rs) {
-            const ii2_seg *s = q.seg;
-            if (!spans_mirrored(s)) { mirrored = false; break; }
-            for (uint64_t j = q.l0; j < q.l1; j++) {
-                if (s->h_blk_off[j + 1] == s->h_blk_off[j]) continue;
-                lo = std::min(lo, s->h_spans[3 * j]);
-                hi = std::max(hi, s->h_spans[3 * j + 2]);
-            }
-        }
+    const bool mirrored = every_doc || mirrored_span(rs, &lo, &hi);
     if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_words * sizeof(uint32_t)) + 2 * 256 + 4096)) return rc;
     uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
     uint32_t *d_words = ws_take<uint32_t>(ctx, n_words);
@@ -1035,31 +1064,12 @@ static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, ui
             ctx->um_dirty = false;
             return count_done(in, counts, stats);
         }
-        const uint64_t W = um_window(ctx);
-        const uint32_t base = lo & ~2047u;                      // the summary's bits are the docs' 2048-doc chunks: doc >> 11
-        const uint64_t span = (uint64_t)hi - base + 1;
-        if (int rc = um_scratch_reserve(ctx, "ii2_count_ranges", span, W)) return rc;
-        for (uint64_t wlo = base; wlo <= hi; wlo += W, n_win++) {
-            UnionManyParams wp;
-            um_set_window(ctx, wp, wlo, std::min<uint64_t>(W, (uint64_t)hi - wlo + 1));
-            p.win_lo = wp.win_lo;
-            p.win_docs = wp.win_docs;
-            p.n_sum = wp.n_sum;
-            p.bitmap = wp.bitmap;
-            p.summary = wp.summary;
-            p.doc_lo = std::max(lo, p.win_lo);
-            p.doc_hi = (uint32_t)std::min<uint64_t>(hi, wlo + p.win_docs - 1);
-            IrParams ip;
-            std::memset(&ip, 0, sizeof ip);
-            ip.n_sum = p.n_sum;
-            ip.bitmap = p.bitmap;
-            ip.summary = p.summary;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((p.n_sum + 3) / 4, (uint64_t)ctx->cu_count * 8u);
-            HIP_TRY(ctx, launch_cr_mark(p, st));
-            HIP_TRY(ctx, launch_cr_count(p, false, st, e0, e1));
-            HIP_TRY(ctx, launch_ir_clear(ip, grid, st));
-            e0 = e1 = nullptr;
-        }
+        if (int rc = marked_windows(ctx, "ii2_count_ranges", p, lo, hi, &n_win, [&]() {
+                const hipError_t e = launch_cr_count(p, false, st, e0, e1);
+                e0 = e1 = nullptr;
+                return e;
+            }))
+            return rc;
     }
     HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1447,6 +1457,158 @@ extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint6
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return intersect_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, tomb, d_out, cap, count);
+}
+
+// ---- which groups each doc of an id array lies in ------------------------------------------------------
+// The transpose of count_many (explain_ranges.hip): the ids are the marked set, the groups' blocks are walked once and a hit ORs
+// its group's bit into its doc's row of d_masks (zeroed first), found through a table of (id, row) built in workspace.  rs are the
+// checked ranges that own blocks, group_of the group of each.  At most two waits: the spans and the final read.
+static int explain_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std::vector<uint32_t> &group_of, const uint32_t *d_ids, uint64_t n_ids,
+                        uint64_t *d_masks, ii2_explain_stats *res) {
+    hipStream_t st = ctx->stream;
+    const size_t nr = rs.size();
+    if (int rc = um_scratch_clean(ctx)) return rc;
+    uint32_t log2_slots = 6;
+    while ((1ull << log2_slots) < 2 * n_ids) log2_slots++;
+    const size_t n_slots = (size_t)1 << log2_slots;
+    // staging: range descriptors + block prefix, the ranges' groups, the spans' start values, and room for the two sets of spread
+    // counters on their way back
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), span_at = um_bytes + align_up(nr * sizeof(uint32_t));
+    const size_t up_bytes = span_at + 256;
+    const size_t cnt_bytes = CR_DECODED_SLOTS * (sizeof(uint64_t) + sizeof(uint32_t));
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + cnt_bytes, false, "ii2_explain_ranges: staging allocation failed")) return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    um_desc_fill(rs, 0, nr, h);
+    std::memcpy(h + um_bytes, group_of.data(), nr * sizeof(uint32_t));
+    const uint32_t span0[4] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};      // {lists' first doc, lists' last doc, smallest id, largest id} before any
+    std::memcpy(h + span_at, span0, sizeof span0);
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    const bool mirrored = mirrored_span(rs, &lo, &hi);
+    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_slots * sizeof(uint64_t)) + align_up(cnt_bytes) + 4096)) return rc;
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
+    unsigned long long *d_table = ws_take<unsigned long long>(ctx, n_slots);
+    uint8_t *d_cnt = ws_take<uint8_t>(ctx, cnt_bytes);          // hits [CR_DECODED_SLOTS] u64, then decoded [CR_DECODED_SLOTS] u32
+    uint32_t *d_span = (uint32_t *)(d_stage + span_at);
+    UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
+    std::memset(&bp, 0, sizeof bp);
+    bp.ranges = (const UmRange *)d_stage;
+    bp.pre = (const uint32_t *)(d_stage + desc_bytes);
+    bp.n_ranges = (uint32_t)nr;
+    bp.n_blocks = (uint32_t)res->n_blocks;
+    bp.bounds = d_span;
+    ExplainParams q;
+    std::memset(&q, 0, sizeof q);
+    CountParams &p = q.c;
+    p.ranges = bp.ranges;
+    p.pre = bp.pre;
+    p.out_first = (const uint32_t *)(d_stage + um_bytes);
+    p.n_ranges = bp.n_ranges;
+    p.n_blocks = bp.n_blocks;
+    p.per_wave = um_per_wave(ctx, res->n_blocks);
+    p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
+    p.set = d_ids;
+    p.n_set = n_ids;
+    p.decoded = (uint32_t *)(d_cnt + CR_DECODED_SLOTS * sizeof(uint64_t));
+    q.table = d_table;
+    q.masks = (unsigned long long *)d_masks;
+    q.hits = (unsigned long long *)d_cnt;
+    q.span = d_span + 2;
+    q.log2_slots = log2_slots;
+    q.n_words = res->n_words;
+    res->log2_slots = log2_slots;
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_masks, 0, n_ids * res->n_words * sizeof(uint64_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_table, 0xFF, n_slots * sizeof(uint64_t), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, cnt_bytes, st));
+    if (!mirrored) HIP_TRY(ctx, launch_union_many_bounds(bp, st));
+    HIP_TRY(ctx, launch_ex_prepare(q, st));
+    uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (!mirrored) {
+        lo = hb[0];
+        hi = hb[1];
+    }
+    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: inconsistent list bounds");
+    // the docs that can hit: the lists' span clipped to the ids'
+    lo = std::max(lo, hb[2]);
+    hi = std::min(hi, hb[3]);
+    if (lo > hi) {                                              // no overlap: nothing was marked, the masks are zero and waited for
+        ctx->um_dirty = false;
+        return II2_OK;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    if (int rc = marked_windows(ctx, "ii2_explain_ranges", p, lo, hi, &res->n_windows, [&]() {
+            const hipError_t e = launch_ex_match(q, st, e0, e1);
+            e0 = e1 = nullptr;
+            return e;
+        }))
+        return rc;
+    uint8_t *h_cnt = h + up_bytes;
+    HIP_TRY(ctx, hipMemcpyAsync(h_cnt, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->um_dirty = false;
+    const uint64_t *h_hits = (const uint64_t *)h_cnt;
+    const uint32_t *h_dec = (const uint32_t *)(h_cnt + CR_DECODED_SLOTS * sizeof(uint64_t));
+    for (uint32_t k = 0; k < CR_DECODED_SLOTS; k++) {
+        res->n_hits += h_hits[k];
+        res->n_decoded += h_dec[k];
+    }
+    return II2_OK;
+}
+
+static int explain_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs, const uint64_t *list_first,
+                                   const uint64_t *list_end, const uint32_t *d_ids, uint64_t n_ids, uint64_t *d_masks, uint64_t masks_cap,
+                                   ii2_explain_stats *stats) {
+    const char *who = "ii2_explain_ranges";
+    if (n_ids > II2_EXPLAIN_MAX_IDS) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: more than II2_EXPLAIN_MAX_IDS ids in one call (rows are independent: split them)");
+    if (n_groups >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: 2^32 - 1 groups or more in one call");
+    ii2_explain_stats res;
+    std::memset(&res, 0, sizeof res);
+    res.n_ids = n_ids;
+    res.n_words = (uint32_t)((n_groups + 63) / 64);
+    std::vector<RangeIn> rs;
+    std::vector<uint32_t> group_of;
+    if (n_groups) {
+        std::vector<GroupIn> gs;
+        if (group_first && group_first[0] != 0) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: group_first does not ascend from 0");
+        if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, rs, gs, &res.n_blocks)) return rc;
+        if (res.n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: more than 2^32 - 2 blocks in one call");
+        for (uint64_t i = 0; i < group_first[n_groups]; i++) res.n_lists += list_end[i] - list_first[i];
+        group_of.resize(rs.size());
+        for (uint64_t g = 0; g < n_groups; g++)
+            for (size_t r = gs[g].r0; r < gs[g].r1; r++) group_of[r] = (uint32_t)g;
+    }
+    const uint64_t n_out = n_ids * res.n_words;
+    if (n_out && (!d_ids || !d_masks)) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: ids or masks is NULL");
+    if (masks_cap < n_out) return fail(ctx, II2_ECAPACITY, "ii2_explain_ranges: masks holds fewer words than ids x words per id (nothing written)");
+    if (n_out) {
+        if (res.n_blocks) {
+            if (int rc = explain_many(ctx, rs, group_of, d_ids, n_ids, d_masks, &res)) return rc;
+        } else {                                                // no group owns a block: every mask is 0
+            HIP_TRY(ctx, hipMemsetAsync(d_masks, 0, n_out * sizeof(uint64_t), ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    }
+    if (stats) *stats = res;
+    return II2_OK;
+}
+
+extern "C" int ii2_explain_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs, const uint64_t *list_first,
+                                  const uint64_t *list_end, const uint32_t *d_ids, uint64_t n_ids, uint64_t *d_masks, uint64_t masks_cap,
+                                  ii2_explain_stats *stats) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return explain_ranges_unlocked(ctx, n_groups, group_first, segs, list_first, list_end, d_ids, n_ids, d_masks, masks_cap, stats);
+}
+
+extern "C" int ii2_explain_slot(uint32_t id, uint32_t log2_slots, uint32_t *slot) {
+    if (!slot || log2_slots == 0 || log2_slots > 31) return II2_EINVAL;
+    *slot = ex_slot(id, log2_slots);
+    return II2_OK;
 }
 
 // ---- AND of ORs minus excluded groups -----------------------------------------------------------------

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import II2_FUZZY_TRANSPOSE, II2_MATCH_UTF8, FuzzyStats  # noqa: F401
 from ._lib import RegexStats
-from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, ExplainStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -239,6 +239,17 @@ def term_regex(pattern: bytes, term: bytes, flags: int = 0):
         e.n_pos = n.value
         raise e
     return bool(m.value), n.value
+
+
+def explain_slot(id: int, log2_slots: int) -> int:
+    """The slot an id's probe starts at in ii2_explain_ranges' id -> row table of 1 << log2_slots entries, by the function the
+    kernels run (ii2_explain_slot).  Needs no context and no GPU."""
+    lib = _lib.load()
+    slot = C.c_uint32(0)
+    rc = lib.ii2_explain_slot(int(id), int(log2_slots), C.byref(slot))
+    if rc:
+        raise II2Error(rc, "ii2_explain_slot")
+    return slot.value
 
 
 class DeviceArray:
@@ -903,6 +914,33 @@ class Context:
         self._ck(self.lib.ii2_count_ranges(self.h, n, segs, first, end, _ptr(dset), int(n_set), tomb.h if tomb else None,
                                            counts.ctypes.data_as(_lib.u64p), counts.size, C.byref(st)))
         return counts, st
+
+    def explain_ranges(self, groups, ids: DeviceArray, n_ids: Optional[int] = None, stats: bool = False, out: Optional[DeviceArray] = None):
+        """Which groups each doc lies in (ii2_explain_ranges): groups = [[(Segment, first, end), ...], ...] as intersect_ranges
+        takes them; ids is a DeviceArray of doc ids IN ANY ORDER - a query's ascending result or a ranked page - of which the first
+        n_ids count (default: all of it).  Returns a uint64 DeviceArray of n_ids * n_words mask words, doc-major, n_words =
+        ceil(len(groups) / 64), its `shape` attribute (n_ids, n_words): bit g & 63 of word i * n_words + (g >> 6) says ids[i] lies
+        in a list of group g; a repeated id has its mask in its first row and zeros after.  With stats=True (masks, ExplainStats).
+        `out`: a uint64 DeviceArray of at least n_ids * n_words words to write into instead of a fresh one."""
+        groups = [[(s, int(a), int(b)) for s, a, b in g] for g in groups]
+        ranges = [r for g in groups for r in g]
+        n = len(ranges)
+        gf = np.zeros(len(groups) + 1, np.uint64)
+        gf[1:] = np.cumsum([len(g) for g in groups], dtype=np.uint64) if groups else []
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s, _, _ in ranges])
+        first = np.array([a for _, a, _ in ranges] or [0], np.uint64)
+        end = np.array([b for _, _, b in ranges] or [0], np.uint64)
+        n_ids = ids.count if n_ids is None else int(n_ids)
+        n_words = (len(groups) + 63) // 64
+        if out is None:
+            out = self.empty(max(n_ids * n_words, 1), np.uint64)
+        if out.dtype != np.uint64:
+            raise ValueError("explain_ranges: out is not a uint64 array")
+        st = ExplainStats()
+        self._ck(self.lib.ii2_explain_ranges(self.h, len(groups), gf.ctypes.data_as(_lib.u64p), segs, first.ctypes.data_as(_lib.u64p),
+                                             end.ctypes.data_as(_lib.u64p), _ptr(ids), n_ids, _ptr(out), out.count, C.byref(st)))
+        out.shape = (n_ids, n_words)
+        return (out, st) if stats else out
 
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):

@@ -71,6 +71,8 @@ def _lib_typed():
         lib.ii2h_intersect_except.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_at_least.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_matched_terms.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
+        lib.ii2h_masks_copy.argtypes = [vp, vp]
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_set_resolve.argtypes = [vp, C.c_int]
         lib.ii2h_set_build.argtypes = [vp, C.c_int]
@@ -272,7 +274,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts, MatchedTerms)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -348,6 +350,19 @@ class InvertedIndex(_Target):
         self.lib.ii2h_ids_copy(self.h, ids.ctypes.data)
         self.lib.ii2h_scores_copy(self.h, scores.ctypes.data)
         return list(zip(ids[: n.value].tolist(), scores[: n.value].tolist()))
+
+    def matched_terms(self, ids, terms: List[bytes]) -> np.ndarray:
+        """which of `terms` each of `ids` lies under (MatchedTerms: one ii2_explain_ranges call): a uint64 array of shape (len(ids),
+        ceil(len(terms) / 64)), bit j & 63 of word [i, j >> 6] set when ids[i] lies under terms[j].  ids in any order - an ascending
+        result or intersect_top's ranked page; an id given twice has its bits in its first row and zeros after; a term found in no
+        segment never has its bit set."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        blob, off = _flat(list(terms))
+        nw = C.c_uint64()
+        self._ck(self.lib.ii2h_matched_terms(self.h, ids.ctypes.data, ids.size, blob.ctypes.data, off.ctypes.data, len(terms), C.byref(nw)))
+        out = np.zeros(max(ids.size * nw.value, 1), np.uint64)
+        self.lib.ii2h_masks_copy(self.h, out.ctypes.data)
+        return out[: ids.size * nw.value].reshape(ids.size, nw.value)
 
     def intersect_top_weighted(self, terms: List[bytes], weights: List[int], k: int, min_score: int = 1,
                                exclude: List[bytes] = ()) -> List[Tuple[int, int]]:

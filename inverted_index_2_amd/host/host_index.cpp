@@ -23,6 +23,7 @@
 //   IntersectTopBatch(queries)                       additive: many IntersectTopWeighted queries in one device call
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
+//   MatchedTerms(ids, terms)                         additive: per id, which of the terms it lies under (ii2_explain_ranges)
 //   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
 //   FuzzySearch(terms, max_dist, prefix, flags) / FuzzyTerms(pattern, max_dist, prefix, flags, limit)   additive: typo-tolerant search (ii2_dict_fuzzy)
 //   RegexSearch(patterns, flags) / RegexTerms(pattern, flags, limit)   additive: regular-expression search (ii2_dict_regex)
@@ -1321,6 +1322,27 @@ class InvertedIndex {
                                    plan.first.data(), plan.end.data(), nullptr, d_ids, d_scores, n, nullptr, nullptr);
         });
     }
+    // additive: which of `terms` each of `ids` lies under (highlighting, "matched queries": which 3 of 5 terms gave a score of 3).
+    // ids in any order - an ascending result or IntersectTop's ranked page.  One group per term as IntersectTop builds them (a term
+    // found in no segment is an empty group: its bit is never set), one upload of the ids, ONE ii2_explain_ranges call and one
+    // download.  Returns ids.size() rows of ceil(terms.size() / 64) words: bit j & 63 of word i * n_words + (j >> 6) says ids[i]
+    // lies under terms[j]; an id given twice has its bits in its first row and zeros after.  Like Intersect, no tombstone filter.
+    std::vector<uint64_t> MatchedTerms(const std::vector<uint32_t> &ids, const std::vector<Term> &terms) const {
+        if (ids.size() > II2_EXPLAIN_MAX_IDS) throw std::runtime_error("matched terms: more than II2_EXPLAIN_MAX_IDS ids");
+        const uint64_t n_words = (terms.size() + 63) / 64, n_out = ids.size() * n_words;
+        std::vector<uint64_t> masks(n_out, 0);
+        Resolver where(*this);
+        Plan plan;
+        if (plan.add(where, terms, {}, Absent::EmptyGroup).empty() || !n_out) return masks;      // no term in any segment: every row is 0
+        DevMem d_ids(ctx_), d_masks(ctx_);
+        ck(ctx_, ii2_dev_alloc(ctx_, ids.size() * sizeof(uint32_t), &d_ids.p), "matched terms");
+        ck(ctx_, ii2_dev_alloc(ctx_, n_out * sizeof(uint64_t), &d_masks.p), "matched terms");
+        ck(ctx_, ii2_copy_h2d(ctx_, d_ids.p, ids.data(), ids.size() * sizeof(uint32_t)), "matched terms");
+        ck(ctx_, ii2_explain_ranges(ctx_, plan.n_groups(), plan.group_first.data(), plan.segs.data(), plan.first.data(), plan.end.data(),
+                                    (const uint32_t *)d_ids.p, ids.size(), (uint64_t *)d_masks.p, n_out, nullptr), "matched terms");
+        ck(ctx_, ii2_copy_d2h(ctx_, masks.data(), d_masks.p, n_out * sizeof(uint64_t)), "matched terms");
+        return masks;
+    }
     // additive: IntersectTop with a weight per term (an idf tier, a field boost): a doc's score is the sum of the weights of the terms it
     // lies under, 1 .. 255 each and at most 255 together; at least min_score.  The groups are IntersectTop's - a term found in no
     // segment keeps its slot, and its weight, and matches nothing - and the call is ONE ii2_topk_weighted_ranges.
@@ -1825,6 +1847,7 @@ struct ii2h_target {
     std::vector<uint32_t> ids;          // last Intersect / RemovedValues result
     std::vector<uint32_t> scores;       // last IntersectTop result: the score of each of ids
     std::vector<std::pair<Term, uint64_t>> counts;      // last TermCounts result
+    std::vector<uint64_t> masks;        // last MatchedTerms result
 };
 
 static std::vector<Term> unpack_terms(const uint8_t *bytes, const uint64_t *off, uint64_t n) {
@@ -2074,6 +2097,16 @@ int ii2h_intersect_top_weighted(ii2h_target *t, const uint8_t *bytes, const uint
                                                    unpack_terms(x_bytes, x_off, n_x)), t->ids, t->scores);
         *n_ids = t->ids.size();
     })
+}
+// which of the n terms each of the n_ids ids lies under: n_ids rows of *n_words words (bit j of a row: term j), fetched by ii2h_masks_copy
+int ii2h_matched_terms(ii2h_target *t, const uint32_t *ids, uint64_t n_ids, const uint8_t *bytes, const uint64_t *off, uint64_t n, uint64_t *n_words) {
+    H_TRY(t, {
+        t->masks = t->index->MatchedTerms(std::vector<uint32_t>(ids, ids + n_ids), unpack_terms(bytes, off, n));
+        *n_words = (n + 63) / 64;
+    })
+}
+void ii2h_masks_copy(const ii2h_target *t, uint64_t *out) {
+    if (!t->masks.empty()) std::memcpy(out, t->masks.data(), t->masks.size() * 8);
 }
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
