@@ -1320,6 +1320,73 @@ func (c *Ctx) ExplainRanges(groupFirst []uint64, segs []*Segment, listFirst, lis
 		uint32(st.n_windows), uint32(st.n_words), uint32(st.log2_slots)}, nil
 }
 
+// ExplainBatchStats mirrors ii2_explain_batch_stats.
+type ExplainBatchStats struct {
+	Tiny, Small, Single, Empty uint32
+	Rows, Words, Hits          uint64
+}
+
+// ExplainBatchIDs is II2_EXPLAIN_BATCH_IDS: the ids of a page the batch kernel takes.
+const ExplainBatchIDs = 1024
+
+// ExplainBatch is ExplainRanges for many pages in one call (ii2_explain_batch): query q owns the groups queryFirst[q] ..
+// queryFirst[q+1]-1, exactly as QueryBatchGroups takes them, and explains the ids ids[idsOff[q] .. idsOff[q+1]) of the device
+// buffer ids - the buffer and the offsets TopKBatch and QueryBatchGroups hand back.  Returns the packed masks and maskOff: query
+// q's rows, (idsOff[q+1]-idsOff[q]) x ceil(groups of q / 64) words, start at word maskOff[q] and are what ExplainRanges returns for
+// that query alone.  The queries that fit one workgroup share one launch and one wait.
+func (c *Ctx) ExplainBatch(queryFirst, groupFirst []uint64, segs []*Segment, listFirst, listEnd []uint64, ids unsafe.Pointer, idsOff []uint64) ([]uint64, []uint64, ExplainBatchStats, error) {
+	if len(queryFirst) == 0 || len(groupFirst) == 0 || len(idsOff) != len(queryFirst) || len(listFirst) != len(segs) || len(listEnd) != len(segs) ||
+		queryFirst[len(queryFirst)-1] != uint64(len(groupFirst)-1) || groupFirst[len(groupFirst)-1] != uint64(len(segs)) {
+		return nil, nil, ExplainBatchStats{}, fmt.Errorf("explain batch: array lengths disagree")
+	}
+	nQ := len(queryFirst) - 1
+	maskOff := make([]uint64, nQ+1)
+	for q := 0; q < nQ; q++ {
+		if queryFirst[q+1] < queryFirst[q] || idsOff[q+1] < idsOff[q] {
+			return nil, nil, ExplainBatchStats{}, fmt.Errorf("explain batch: query %d: offsets do not ascend", q)
+		}
+		maskOff[q+1] = maskOff[q] + (idsOff[q+1]-idsOff[q])*((queryFirst[q+1]-queryFirst[q]+63)/64)
+	}
+	total := maskOff[nQ]
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	masks := make([]uint64, total)
+	var d unsafe.Pointer
+	if rc := C.ii2_dev_alloc(c.h, C.size_t((total+1)*8), &d); rc != 0 {
+		return nil, nil, ExplainBatchStats{}, c.err("explain batch", rc)
+	}
+	var st C.ii2_explain_batch_stats
+	rc := C.ii2_explain_batch(c.h, C.uint64_t(nQ), u64ptr(queryFirst), u64ptr(groupFirst), (**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst),
+		u64ptr(listEnd), (*C.uint32_t)(ids), u64ptr(idsOff), (*C.uint64_t)(d), C.uint64_t(total), u64ptr(maskOff), &st)
+	if rc == 0 && total > 0 {
+		rc = C.ii2_copy_d2h(c.h, unsafe.Pointer(&masks[0]), d, C.size_t(total*8))
+	}
+	C.ii2_dev_free(c.h, d)
+	if rc != 0 {
+		return nil, nil, ExplainBatchStats{}, c.err("explain batch", rc)
+	}
+	return masks, maskOff, ExplainBatchStats{uint32(st.n_tiny), uint32(st.n_small), uint32(st.n_single), uint32(st.n_empty),
+		uint64(st.n_rows), uint64(st.n_words), uint64(st.n_hits)}, nil
+}
+
+// ExplainBatchHost is ExplainBatch for ids in host memory: one upload of all ids, the call, one download.
+func (c *Ctx) ExplainBatchHost(queryFirst, groupFirst []uint64, segs []*Segment, listFirst, listEnd []uint64, ids []uint32, idsOff []uint64) ([]uint64, []uint64, error) {
+	var d unsafe.Pointer
+	if rc := C.ii2_dev_alloc(c.h, C.size_t((len(ids)+1)*4), &d); rc != 0 {
+		return nil, nil, c.err("explain batch", rc)
+	}
+	defer C.ii2_dev_free(c.h, d)
+	if len(ids) > 0 {
+		if rc := C.ii2_copy_h2d(c.h, d, unsafe.Pointer(&ids[0]), C.size_t(len(ids)*4)); rc != 0 {
+			return nil, nil, c.err("explain batch", rc)
+		}
+	}
+	masks, maskOff, _, err := c.ExplainBatch(queryFirst, groupFirst, segs, listFirst, listEnd, d, idsOff)
+	return masks, maskOff, err
+}
+
 // Union replaces PrefixSearch's append + slices.Sort + slices.Compact (inverted_index.go:274-292).
 func (c *Ctx) Union(listOff []uint64, values, removed []uint32) ([]uint32, error) {
 	return c.lists(true, listOff, values, removed)

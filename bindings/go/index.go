@@ -940,6 +940,67 @@ func IntersectTopBatch(c *Ctx, ix ResidentIndex, queries []TopQuery) ([][]Scored
 	return out, nil
 }
 
+// TermsPage is one page of MatchedTermsBatch: doc ids in any order and the terms to test them against.
+type TermsPage struct {
+	IDs   []uint32
+	Terms [][]byte
+}
+
+// MatchedTermsBatch (additive): for MANY pages - the ranked pages IntersectTopBatch returns, each with its own terms - which of
+// its terms each id of a page lies under.  Result p holds len(IDs) rows of ceil(len(Terms) / 64) words: bit j&63 of word
+// i*words + j>>6 says IDs[i] lies under Terms[j]; an id given twice in a page has its bits in its first row and zeros after.  One
+// group per term, one one-list range per segment that holds it; a term found in no segment keeps its bit and never sets it; a
+// page none of whose terms is in a segment keeps its place without a group and its rows are 0.  One upload of all ids, ONE
+// Ctx.ExplainBatch call and one download - what the C++ host mirror's InvertedIndex::MatchedTermsBatch does
+// (host/host_index.cpp).  Like Read, no tombstone filter.
+func MatchedTermsBatch(c *Ctx, ix ResidentIndex, pages []TermsPage) ([][]uint64, error) {
+	if len(pages) == 0 {
+		return nil, nil
+	}
+	defer ix.Release()
+	out := make([][]uint64, len(pages))
+	queryFirst, groupFirst, idsOff := []uint64{0}, []uint64{0}, []uint64{0}
+	var segs []*Segment
+	var first, end []uint64
+	var ids []uint32
+	nOut := uint64(0)
+	for p, P := range pages {
+		out[p] = make([]uint64, uint64(len(P.IDs))*uint64((len(P.Terms)+63)/64))
+		gMark, rMark := len(groupFirst), len(segs)
+		found := false
+		for _, t := range P.Terms {
+			s, l, _ := ix.TermLists(t)
+			found = found || len(s) > 0
+			segs = append(segs, s...)
+			for _, j := range l {
+				first = append(first, j)
+				end = append(end, j+1)
+			}
+			groupFirst = append(groupFirst, uint64(len(segs)))
+		}
+		if found {
+			nOut += uint64(len(out[p]))
+		} else { // the page keeps its place, without a group
+			groupFirst = groupFirst[:gMark]
+			segs, first, end = segs[:rMark], first[:rMark], end[:rMark]
+		}
+		queryFirst = append(queryFirst, uint64(len(groupFirst)-1))
+		ids = append(ids, P.IDs...)
+		idsOff = append(idsOff, uint64(len(ids)))
+	}
+	if nOut == 0 {
+		return out, nil
+	}
+	masks, maskOff, err := c.ExplainBatchHost(queryFirst, groupFirst, segs, first, end, ids, idsOff)
+	if err != nil {
+		return nil, fmt.Errorf("matched terms batch: %w", err)
+	}
+	for p := range pages {
+		copy(out[p], masks[maskOff[p]:maskOff[p+1]])
+	}
+	return out, nil
+}
+
 // IntersectExcept (additive, beside the additive Intersect): the ids under every term of terms and under none of except -
 // "error AND db NOT healthcheck".  One group per term, one one-list range per segment that holds it, the excluded terms' groups
 // flagged, and ONE Ctx.AndNotRanges call with one download - what the C++ host mirror's InvertedIndex::IntersectExcept does

@@ -800,6 +800,54 @@ int ii2_explain_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_fi
  * (a multiplicative hash; tests choose colliding ids with it).  log2_slots outside 1 .. 31 or slot == NULL: II2_EINVAL. */
 int ii2_explain_slot(uint32_t id, uint32_t log2_slots, uint32_t *slot);
 
+/* MANY explains in one call - the pages that ii2_topk_batch / ii2_query_batch_groups hand back, each explained against its own
+ * groups: query q owns the groups query_first[q] .. query_first[q + 1] - 1 of an ii2_explain_ranges call and the ids
+ * d_ids[ids_off[q] .. ids_off[q + 1]) - the d_ids / out_off of those calls fit as they are.
+ *   - query_first, group_first and the range arrays are exactly those of ii2_query_batch_groups (host memory, ascending from 0).
+ *     As in ii2_explain_ranges there is no group_not and no tomb.  d_ids is a device array, the ids of a page in any order;
+ *     ids_off (host, n_queries + 1) ascends from 0.
+ *   - the masks: with n_words_q = ceil(n_groups_q / 64), query q's rows are the n_ids_q * n_words_q words of d_masks (device) from
+ *     word mask_off[q] = the sum over the queries p before it of n_ids_p * n_words_p, and they are bit for bit what
+ *     ii2_explain_ranges writes for that query alone: the first-row rule of a repeated id, zero bits at and above n_groups_q,
+ *     all-zero rows for ids that lie in no list.  mask_off (host, n_queries + 1, may be NULL) depends on the arguments alone - no
+ *     two-call protocol - and is filled on success and on II2_ECAPACITY.
+ *   - all or nothing: every check runs before anything is launched or written.  II2_EINVAL ("ii2_explain_batch: query N: ..."):
+ *     a NULL array with something to read or write, query_first / group_first / ids_off not ascending from 0, a bad range
+ *     (rejected as ii2_explain_ranges rejects it), a segment of another device.  II2_ERANGE: more than 2^20 queries, a query of
+ *     more than II2_EXPLAIN_MAX_IDS ids, 2^32 rows or more in all, the per-query block / range / group limits of
+ *     ii2_explain_ranges.  II2_ECAPACITY: masks_cap < mask_off[n_queries]; d_masks is untouched and stats is not written.
+ *     n_queries == 0: mask_off[0] = 0, the device pointers may be NULL.
+ * A query whose non-empty lists are at most II2_MAX_LISTS and hold at most 8192 postings in at most 128 blocks, with at most
+ * II2_EXPLAIN_BATCH_IDS ids, is answered by one workgroup of the batch kernel (option batch.explain; option batch.tiny picks the
+ * 256- or the 1024-thread form): every list decoded into LDS, the page's ids in an LDS table that keeps a repeated id's first
+ * row, one bisection per (row, list) pair, a hit ORed into its row.  No per-context scratch is touched and no workgroup waits for
+ * another; the call waits ONCE for all of them.  Every other query with ids and blocks runs through ii2_explain_ranges' form on
+ * its own slices, with that form's waits; a query without ids, without groups or whose groups own no block runs nothing (its
+ * rows, if any, are zero).  The call takes no kernel path (ii2_ctx_paths). */
+#define II2_EXPLAIN_BATCH_IDS 1024u     /* ids of a page the batch kernel takes: table + ids + decoded postings stay below 64 KB of LDS */
+typedef struct {
+    uint32_t n_tiny, n_small;   /* queries answered by the batch kernel, per size class */
+    uint32_t n_single;          /* queries run one by one through ii2_explain_ranges' form */
+    uint32_t n_empty;           /* queries for which nothing ran */
+    uint64_t n_rows;            /* rows = ids_off[n_queries] */
+    uint64_t n_words;           /* mask words written = mask_off[n_queries] */
+    uint64_t n_hits;            /* (doc, group) bits set = popcount of all masks */
+} ii2_explain_batch_stats;      /* 40 bytes: four 32-bit words, then three 64-bit ones at offsets 16, 24, 32 - no padding anywhere */
+int ii2_explain_batch(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first,
+                      const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                      const uint32_t *d_ids, const uint64_t *ids_off /* host, n_queries + 1, ascending from 0 */,
+                      uint64_t *d_masks, uint64_t masks_cap /* words */, uint64_t *mask_off /* host, n_queries + 1, may be NULL */,
+                      ii2_explain_batch_stats *stats /* may be NULL */);
+/* Host only, no GPU: the form the planner of ii2_explain_batch gives a query whose n_lists non-empty lists hold n_postings
+ * postings in n_blocks blocks, with n_ids ids, under the values batch_explain / batch_tiny of the two options - by the function
+ * the driver bins its queries with.  EMPTY: no ids or no block.  form == NULL: II2_EINVAL. */
+#define II2_EXPLAIN_BATCH_EMPTY 0
+#define II2_EXPLAIN_BATCH_TINY 1
+#define II2_EXPLAIN_BATCH_SMALL 2
+#define II2_EXPLAIN_BATCH_SINGLE 3
+int ii2_explain_batch_plan(uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_ids, int64_t batch_explain,
+                           int64_t batch_tiny, uint32_t *form);
+
 /* THRESHOLD query - "docs that lie in at least min_match of these n groups" (minimum-should-match, n-gram / fuzzy term matching,
  * "any two of these tags"): the ascending, duplicate-free ids that lie in at least one list of AT LEAST min_match required groups
  * and in NO list of ANY excluded group, minus the tombstones when tomb != NULL.  An id that sits in several lists of one group
@@ -1120,6 +1168,9 @@ int ii2_selftest(ii2_ctx *ctx);
  *   batch.topk                              ii2_topk_batch: 1 (default) the queries that fit one workgroup share the batch kernel
  *                                           (batch.tiny picks its form as above), 0 every query of a batch goes through
  *                                           ii2_topk_weighted_ranges' form one after the other
+ *   batch.explain                           ii2_explain_batch: 1 (default) the queries that fit one workgroup share the batch kernel
+ *                                           (batch.tiny picks its form as above), 0 every query of a batch that has ids and blocks
+ *                                           goes through ii2_explain_ranges' form one after the other
  *   union.many                             ii2_union_ranges: 1 = the block-wise path even for <= 64 lists (default 0: only above)
  *   union.many_window_log2                  tests: docs per window of that path, 1 << N (11 .. 30, default 30)
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)

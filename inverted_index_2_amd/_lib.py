@@ -86,6 +86,15 @@ class ExplainStats(C.Structure):
 II2_EXPLAIN_MAX_IDS = 1 << 24
 
 
+class ExplainBatchStats(C.Structure):
+    _fields_ = [("n_tiny", C.c_uint32), ("n_small", C.c_uint32), ("n_single", C.c_uint32), ("n_empty", C.c_uint32), ("n_rows", C.c_uint64),
+                ("n_words", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+II2_EXPLAIN_BATCH_IDS = 1024
+II2_EXPLAIN_BATCH_EMPTY, II2_EXPLAIN_BATCH_TINY, II2_EXPLAIN_BATCH_SMALL, II2_EXPLAIN_BATCH_SINGLE = range(4)
+
+
 class AtleastStats(C.Structure):
     _fields_ = [("n_counted", C.c_uint64), ("bound", C.c_uint64), ("form", C.c_uint32), ("n_planes", C.c_uint32),
                 ("n_windows", C.c_uint32), ("n_late", C.c_uint32)]
@@ -183,6 +192,8 @@ PROTOTYPES = {
     "ii2_count_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, C.c_uint64, vp, u64p, C.c_uint64, C.POINTER(CountStats)]),
     "ii2_explain_ranges": (C.c_int, [vp, C.c_uint64, u64p, vpp, u64p, u64p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(ExplainStats)]),
     "ii2_explain_slot": (C.c_int, [C.c_uint32, C.c_uint32, u32p]),
+    "ii2_explain_batch": (C.c_int, [vp, C.c_uint64, u64p, u64p, vpp, u64p, u64p, vp, u64p, vp, C.c_uint64, u64p, C.POINTER(ExplainBatchStats)]),
+    "ii2_explain_batch_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, u32p]),
     "ii2_atleast_ranges": (C.c_int, [vp, C.c_uint64, u64p, u8p, C.c_uint32, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p, C.POINTER(AtleastStats)]),
     "ii2_atleast_plan": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, u32p, u64p, u64p]),
     "ii2_atleast_word": (C.c_int, [C.c_uint32, C.c_uint32, u32p, C.c_uint32, u32p]),

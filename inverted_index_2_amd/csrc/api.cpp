@@ -1169,6 +1169,7 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "batch.tiny") ctx->opt_batch_tiny = value;
     else if (k == "batch.groups") ctx->opt_batch_groups = value;
     else if (k == "batch.topk") ctx->opt_batch_topk = value;
+    else if (k == "batch.explain") ctx->opt_batch_explain = value;
     else if (k == "union.many") ctx->opt_union_many = value;
     else if (k == "union.many_window_log2") ctx->opt_union_many_window_log2 = value;
     else if (k == "debug.union_many_no_atomics") ctx->opt_union_many_no_atomics = value;

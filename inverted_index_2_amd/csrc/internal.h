@@ -144,7 +144,8 @@ struct ii2_ctx {
     int64_t opt_batch_tiny = 1;         // ... of both entry points: those of <= 2048 postings in <= 32 blocks in the 256-thread form (0: all in the 1024-thread one)
     int64_t opt_batch_groups = 1;       // ii2_query_batch_groups: queries that fit share its batch kernel (0: every query through ii2_andnot_ranges' paths)
     int64_t opt_batch_topk = 1;         // ii2_topk_batch: queries that fit share its batch kernel (0: every query through ii2_topk_weighted_ranges' form)
-    uint8_t *d_batch = nullptr;         // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
+    int64_t opt_batch_explain = 1;      // ii2_explain_batch: queries that fit share its batch kernel (0: every query through ii2_explain_ranges' form)
+    uint8_t *d_batch = nullptr;        // its device block: descriptor table, counts, offsets, scan temp, staged results (grow-only)
     size_t batch_cap = 0;
     void *h_batch = nullptr;            // pinned: the descriptor table on its way up, the offsets on their way down (grow-only)
     size_t h_batch_cap = 0;
@@ -735,6 +736,24 @@ struct ExplainParams {
 };
 hipError_t launch_ex_prepare(const ExplainParams &p, hipStream_t s);
 hipError_t launch_ex_match(const ExplainParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// the same for many short pages in one launch (explain_batch.hip): the batch kernels' table - every query's non-empty lists in
+// group order, stage_off = the first word of its rows in masks, bound = its ids (<= II2_EXPLAIN_BATCH_IDS); tomb, stage, is_union
+// and n_req unused - plus, parallel to it, the group number of every list and one ExplainBatchQuery per query of the table.  The
+// rows are zero before the launch; cnt[slot] receives the query's hits.
+struct ExplainBatchQuery {
+    uint64_t ids_first;          // its page: ids[ids_first .. ids_first + bound)
+    uint32_t n_words;            // mask words per row
+    uint32_t pad;
+};
+struct ExplainBatchParams {
+    BatchParams b;
+    const uint32_t *grp;         // [lists of the table]
+    const ExplainBatchQuery *pages;   // [n_tiny + n_small], in the table's order
+    const uint32_t *ids;
+    unsigned long long *masks;
+};
+hipError_t launch_explain_batch(const ExplainBatchParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 }  // namespace ii2
 int ii2_lookback_prepare(ii2_ctx *ctx, size_t n_wg, ii2::LookBack *lb);      // api.cpp; ctx->mu held

@@ -1559,9 +1559,10 @@ static int explain_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std:
     return II2_OK;
 }
 
+// sliced (ii2_explain_batch): the groups are a query's slice of a batch's, so group_first[0] is where its ranges start, not 0
 static int explain_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64_t *group_first, const ii2_seg *const *segs, const uint64_t *list_first,
                                    const uint64_t *list_end, const uint32_t *d_ids, uint64_t n_ids, uint64_t *d_masks, uint64_t masks_cap,
-                                   ii2_explain_stats *stats) {
+                                   ii2_explain_stats *stats, bool sliced = false) {
     const char *who = "ii2_explain_ranges";
     if (n_ids > II2_EXPLAIN_MAX_IDS) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: more than II2_EXPLAIN_MAX_IDS ids in one call (rows are independent: split them)");
     if (n_groups >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: 2^32 - 1 groups or more in one call");
@@ -1573,10 +1574,10 @@ static int explain_ranges_unlocked(ii2_ctx *ctx, uint64_t n_groups, const uint64
     std::vector<uint32_t> group_of;
     if (n_groups) {
         std::vector<GroupIn> gs;
-        if (group_first && group_first[0] != 0) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: group_first does not ascend from 0");
+        if (!sliced && group_first && group_first[0] != 0) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: group_first does not ascend from 0");
         if (int rc = collect_groups(ctx, who, n_groups, group_first, segs, list_first, list_end, rs, gs, &res.n_blocks)) return rc;
         if (res.n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_explain_ranges: more than 2^32 - 2 blocks in one call");
-        for (uint64_t i = 0; i < group_first[n_groups]; i++) res.n_lists += list_end[i] - list_first[i];
+        for (uint64_t i = group_first[0]; i < group_first[n_groups]; i++) res.n_lists += list_end[i] - list_first[i];
         group_of.resize(rs.size());
         for (uint64_t g = 0; g < n_groups; g++)
             for (size_t r = gs[g].r0; r < gs[g].r1; r++) group_of[r] = (uint32_t)g;
@@ -3098,6 +3099,161 @@ extern "C" int ii2_topk_batch_plan(uint64_t n_lists, uint64_t n_postings, uint64
     if (!form || !bound) return II2_EINVAL;
     *form = topk_batch_form(true, n_lists, n_postings, n_blocks, n_counted, batch_topk, batch_tiny);
     *bound = topk_batch_bound(n_counted, req_postings, k);
+    return II2_OK;
+}
+
+// ---- many explains in one call ------------------------------------------------------------------
+// The form a query of ii2_explain_batch takes: n_lists non-empty lists (`fits`: the walk saw every one and each is regular) of
+// n_post postings in n_blocks blocks, n_ids ids.  The host planner and ii2_explain_batch_plan call it.
+static_assert(BP_EMPTY == II2_EXPLAIN_BATCH_EMPTY && BP_TINY == II2_EXPLAIN_BATCH_TINY && BP_SMALL == II2_EXPLAIN_BATCH_SMALL && BP_LARGE == II2_EXPLAIN_BATCH_SINGLE,
+              "ii2_explain_batch_plan reports the planner's kinds");
+static uint8_t explain_batch_form(bool fits, uint64_t n_lists, uint64_t n_post, uint64_t n_blocks, uint64_t n_ids, int64_t opt_explain, int64_t opt_tiny) {
+    if (!n_ids || !n_blocks) return BP_EMPTY;
+    if (!opt_explain || !fits || n_ids > II2_EXPLAIN_BATCH_IDS || n_lists > MAX_LISTS || n_post > SMALL_SET_POSTINGS || n_blocks > SMALL_SET_BLOCKS) return BP_LARGE;
+    return opt_tiny && n_blocks <= BATCH_TINY_BLOCKS && n_post <= BATCH_TINY_POSTINGS ? BP_TINY : BP_SMALL;
+}
+
+// Query q owns the groups query_first[q] .. query_first[q + 1] - 1 of an ii2_explain_ranges call and the ids d_ids[ids_off[q] ..
+// ids_off[q + 1]); its rows are that call's.  Nothing is staged, scanned or packed: every row's place follows from the arguments.
+static int explain_batch_unlocked(ii2_ctx *ctx, uint64_t nq, const uint64_t *query_first, const uint64_t *group_first, const ii2_seg *const *segs,
+                                  const uint64_t *list_first, const uint64_t *list_end, const uint32_t *d_ids, const uint64_t *ids_off, uint64_t *d_masks,
+                                  uint64_t masks_cap, uint64_t *mask_off, ii2_explain_batch_stats *stats) {
+    const char *const who = "ii2_explain_batch";
+    const std::string w(who);
+    if (nq > BATCH_MAX_QUERIES) return fail(ctx, II2_ERANGE, (w + ": more than 2^20 queries in one call").c_str());
+    if (nq == 0) {
+        if (mask_off) mask_off[0] = 0;
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return II2_OK;
+    }
+    if (!query_first || !ids_off) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (int rc = batch_group_args(ctx, w, nq, query_first, group_first)) return rc;
+    if (ids_off[0] != 0) return batch_bad(ctx, w, 0, "ids_off does not ascend from 0");
+    for (uint64_t q = 0; q < nq; q++)
+        if (ids_off[q + 1] < ids_off[q]) return batch_bad(ctx, w, q, "ids_off does not ascend from 0");
+    // 1. every query checked and sized before anything is launched or written
+    std::vector<BatchPlan> plan(nq);
+    std::vector<uint64_t> moff(nq + 1);
+    std::vector<BatchList> tl;             // the table's lists and their groups, the queries in batch order
+    std::vector<uint32_t> tg;
+    std::vector<RangeIn> rs;
+    std::vector<GroupIn> gs;
+    BatchTally T;
+    moff[0] = 0;
+    for (uint64_t q = 0; q < nq; q++) {
+        const uint64_t g0 = query_first[q], ng = query_first[q + 1] - g0, n_ids = ids_off[q + 1] - ids_off[q];
+        BatchPlan &pl = plan[q];
+        pl = BatchPlan{0, 0, tl.size(), 0, 0, BP_EMPTY, 0, 0};
+        if (n_ids > II2_EXPLAIN_MAX_IDS) return fail(ctx, II2_ERANGE, (w + ": query " + std::to_string(q) + ": more than II2_EXPLAIN_MAX_IDS ids").c_str());
+        if (ng >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, (w + ": query " + std::to_string(q) + ": 2^32 - 1 groups or more").c_str());
+        const uint64_t n_words = (ng + 63) / 64, n_out = n_ids * n_words;
+        moff[q + 1] = moff[q] + n_out;
+        uint64_t n_blocks = 0;
+        rs.clear();
+        if (ng) {
+            if (int rc = collect_groups(ctx, who, ng, group_first + g0, segs, list_first, list_end, rs, gs, &n_blocks)) return batch_named(ctx, w, q, rc);
+            if (n_blocks >= 0xFFFFFFFFull || rs.size() >= 0xFFFFFFFFull)
+                return fail(ctx, II2_ERANGE, (w + ": query " + std::to_string(q) + ": more than 2^32 - 2 blocks").c_str());
+        }
+        if (n_out && (!d_ids || !d_masks)) return batch_bad(ctx, w, q, "ids or masks is NULL");
+        // A query takes the batch kernel when its non-empty lists, group by group, fit one workgroup and its page fits the LDS
+        // table.  No postings x lists bound applies: the alternative is the single form's waits once per query.
+        Counted t{0, 0, 0, ctx->opt_batch_explain && n_ids && n_ids <= II2_EXPLAIN_BATCH_IDS && n_blocks && n_blocks <= SMALL_SET_BLOCKS, II2_OK};
+        for (uint64_t g = 0; t.fits && g < ng; g++)
+            for (size_t r = gs[g].r0; t.fits && r < gs[g].r1; r++) {
+                const ii2_seg *s = rs[r].seg;
+                if (int rc = ii2_seg_host_cnt(ctx, s)) return rc;
+                for (uint64_t j = rs[r].l0; j < rs[r].l1; j++) {
+                    const uint32_t b0 = s->h_blk_off[j], nb = s->h_blk_off[j + 1] - b0, c = s->h_cnt[j];
+                    if (!nb) continue;
+                    if (t.m == MAX_LISTS || t.sum + c > SMALL_SET_POSTINGS || !blocks_full(nb, c)) { t.fits = false; break; }
+                    tl.push_back(BatchList{s->d_skip + b0, s->d_payload, nb, c});
+                    tg.push_back((uint32_t)g);
+                    t.m++;
+                    t.nb += nb;
+                    t.sum += c;
+                }
+            }
+        pl.kind = explain_batch_form(t.fits, t.m, t.sum, t.fits ? t.nb : n_blocks, n_ids, ctx->opt_batch_explain, ctx->opt_batch_tiny);
+        if (pl.kind == BP_TINY || pl.kind == BP_SMALL) {
+            pl.nl = t.m;
+            pl.n_blocks = t.nb;
+        } else {
+            tl.resize(pl.l0);
+            tg.resize(pl.l0);
+        }
+        if (int rc = batch_planned(ctx, w, pl, T)) return rc;
+    }
+    if (ids_off[nq] >= (1ull << 32)) return fail(ctx, II2_ERANGE, (w + ": 2^32 rows or more in one call").c_str());
+    if (mask_off) std::memcpy(mask_off, moff.data(), (nq + 1) * sizeof(uint64_t));
+    if (masks_cap < moff[nq]) return fail(ctx, II2_ECAPACITY, (w + ": masks holds fewer words than the rows of all queries (nothing written; mask_off holds the places)").c_str());
+    ii2_explain_batch_stats bst{T.n_kind[BP_TINY], T.n_kind[BP_SMALL], T.n_kind[BP_LARGE], T.n_kind[BP_EMPTY], ids_off[nq], moff[nq], 0};
+    // 2. the blocks: [queries | lists | groups | pages | staging offsets (unused) | hit counts] travel up in one copy
+    const size_t o_lists = T.o_lists(), o_grp = o_lists + align_up(tl.size() * sizeof(BatchList));
+    const size_t o_pages = o_grp + align_up(tg.size() * sizeof(uint32_t));
+    BatchMem m;
+    if (int rc = batch_blocks(ctx, o_pages + align_up((size_t)T.n_table() * sizeof(ExplainBatchQuery)), nq, 0, &m)) return rc;
+    BatchQuery *hq = (BatchQuery *)m.h;
+    ExplainBatchQuery *hx = (ExplainBatchQuery *)(m.h + o_pages);
+    if (!tl.empty()) {
+        std::memcpy(m.h + o_lists, tl.data(), tl.size() * sizeof(BatchList));
+        std::memcpy(m.h + o_grp, tg.data(), tg.size() * sizeof(uint32_t));
+    }
+    // 3. every row zero, in front of everything that sets a bit; then the queries that do not fit, one after the other through
+    // ii2_explain_ranges' form on their own slices (each with that form's waits); the table up
+    if (moff[nq]) HIP_TRY(ctx, hipMemsetAsync(d_masks, 0, moff[nq] * sizeof(uint64_t), ctx->stream));
+    if (int rc = batch_fill(ctx, w, plan, T, m,
+            [&](uint64_t q, const BatchPlan &, uint64_t *) -> int {
+                const uint64_t g0 = query_first[q];
+                ii2_explain_stats es;
+                if (int rc = explain_ranges_unlocked(ctx, query_first[q + 1] - g0, group_first + g0, segs, list_first, list_end, d_ids + ids_off[q],
+                                                     ids_off[q + 1] - ids_off[q], d_masks + moff[q], moff[q + 1] - moff[q], &es, true))
+                    return rc;
+                bst.n_hits += es.n_hits;
+                return II2_OK;
+            },
+            [&](uint64_t q, const BatchPlan &pl, uint32_t at) {
+                hq[at] = BatchQuery{moff[q], (uint32_t)(ids_off[q + 1] - ids_off[q]), (uint32_t)pl.l0, pl.nl, 0u, (uint32_t)q, 0u};
+                hx[at] = ExplainBatchQuery{ids_off[q], (uint32_t)((query_first[q + 1] - query_first[q] + 63) / 64), 0u};
+            }))
+        return rc;
+    // 4. the queries that fit in one launch per size class; their hit counts down: the call's one wait
+    if (T.n_table()) {
+        ExplainBatchParams xp;
+        std::memset(&xp, 0, sizeof xp);
+        batch_params(xp.b, m, o_lists, T, nullptr);
+        xp.grp = (const uint32_t *)(m.d + o_grp);
+        xp.pages = (const ExplainBatchQuery *)(m.d + o_pages);
+        xp.ids = d_ids;
+        xp.masks = (unsigned long long *)d_masks;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, launch_explain_batch(xp, ctx->stream, e0, e1));
+        uint32_t *h_hits = (uint32_t *)(m.h + m.up_bytes);
+        HIP_TRY(ctx, hipMemcpyAsync(h_hits, m.d + m.o_cnt, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint64_t q = 0; q < nq; q++) bst.n_hits += h_hits[q];
+    } else if (moff[nq]) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));              // (the zeroed rows of queries for which nothing ran)
+    }
+    if (stats) *stats = bst;
+    return II2_OK;
+}
+
+extern "C" int ii2_explain_batch(ii2_ctx *ctx, uint64_t n_queries, const uint64_t *query_first, const uint64_t *group_first, const ii2_seg *const *segs,
+                                 const uint64_t *list_first, const uint64_t *list_end, const uint32_t *d_ids, const uint64_t *ids_off, uint64_t *d_masks,
+                                 uint64_t masks_cap, uint64_t *mask_off, ii2_explain_batch_stats *stats) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return explain_batch_unlocked(ctx, n_queries, query_first, group_first, segs, list_first, list_end, d_ids, ids_off, d_masks, masks_cap, mask_off, stats);
+}
+
+// host only: the form the planner above gives a query
+extern "C" int ii2_explain_batch_plan(uint64_t n_lists, uint64_t n_postings, uint64_t n_blocks, uint64_t n_ids, int64_t batch_explain, int64_t batch_tiny,
+                                      uint32_t *form) {
+    if (!form) return II2_EINVAL;
+    *form = explain_batch_form(true, n_lists, n_postings, n_blocks, n_ids, batch_explain, batch_tiny);
     return II2_OK;
 }
 

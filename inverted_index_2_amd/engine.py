@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import II2_FUZZY_TRANSPOSE, II2_MATCH_UTF8, FuzzyStats  # noqa: F401
 from ._lib import RegexStats
-from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, ExplainStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, ExplainBatchStats, ExplainStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -160,6 +160,26 @@ def pack_topk_batch(queries):
         weight += [1] * len(list(exclude))
     group_weight = None if all(w is None for _, w, _, _, _ in queries) else np.array(weight, np.uint32)
     return packed + (group_weight, np.array([int(m) for _, _, _, m, _ in queries], np.uint32), np.array([int(k) for _, _, k, _, _ in queries], np.uint32))
+
+
+def pack_explain_batch(queries):
+    """The flat arrays ii2_explain_batch takes, from queries = [groups, ...] with groups = [[(segment, first, end), ...], ...] as
+    explain_ranges takes them: (query_first u64 [Q + 1], group_first u64 [G + 1], segments [R], list_first u64 [R], list_end u64
+    [R]) - pack_group_batch's arrays without the flags: an excluded group is one more group.  Pure host code."""
+    query_first, group_first, _, segs, first, end = pack_group_batch([(groups, []) for groups in queries])
+    return query_first, group_first, segs, first, end
+
+
+def explain_batch_plan(n_lists: int, n_postings: int, n_blocks: int, n_ids: int, batch_explain: int = 1, batch_tiny: int = 1) -> int:
+    """The form ii2_explain_batch's planner gives a query of n_lists non-empty lists that hold n_postings postings in n_blocks
+    blocks, with n_ids ids, under the two option values (ii2_explain_batch_plan): one of II2_EXPLAIN_BATCH_EMPTY / TINY / SMALL /
+    SINGLE.  Needs no context and no GPU."""
+    lib = _lib.load()
+    form = C.c_uint32(0)
+    rc = lib.ii2_explain_batch_plan(int(n_lists), int(n_postings), int(n_blocks), int(n_ids), int(batch_explain), int(batch_tiny), C.byref(form))
+    if rc != 0:
+        raise II2Error(rc, "ii2_explain_batch_plan")
+    return form.value
 
 
 def path_names():
@@ -941,6 +961,31 @@ class Context:
                                              end.ctypes.data_as(_lib.u64p), _ptr(ids), n_ids, _ptr(out), out.count, C.byref(st)))
         out.shape = (n_ids, n_words)
         return (out, st) if stats else out
+
+    def explain_batch(self, queries, ids: DeviceArray, ids_off, stats: bool = False, out: Optional[DeviceArray] = None):
+        """Many explains in one call (ii2_explain_batch): queries = [groups, ...], each as explain_ranges takes it; query q explains
+        ids[ids_off[q] : ids_off[q + 1]] - the ids / offsets topk_batch and query_batch_groups return fit as they are.  Returns
+        (uint64 DeviceArray of the packed masks, mask_off): query q's rows, (ids_off[q + 1] - ids_off[q]) x ceil(len(queries[q]) / 64)
+        words, start at word mask_off[q] and are what explain_ranges writes for it alone.  With stats=True also ExplainBatchStats.
+        `out`: a uint64 DeviceArray of at least mask_off[-1] words to write into instead of a fresh one."""
+        queries = [list(groups) for groups in queries]
+        query_first, group_first, qsegs, first, end = pack_explain_batch(queries)
+        ids_off = np.ascontiguousarray(ids_off, np.uint64)
+        if ids_off.size != len(queries) + 1:
+            raise ValueError("explain_batch: ids_off holds len(queries) + 1 offsets")
+        n = len(qsegs)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s in qsegs])
+        if out is None:
+            words = sum(int(ids_off[q + 1] - ids_off[q]) * ((len(g) + 63) // 64) for q, g in enumerate(queries) if ids_off[q + 1] > ids_off[q])
+            out = self.empty(max(words, 1), np.uint64)
+        if out.dtype != np.uint64:
+            raise ValueError("explain_batch: out is not a uint64 array")
+        mask_off = np.zeros(len(queries) + 1, np.uint64)
+        st = ExplainBatchStats()
+        self._ck(self.lib.ii2_explain_batch(self.h, len(queries), query_first.ctypes.data_as(_lib.u64p), group_first.ctypes.data_as(_lib.u64p), segs,
+                                            first.ctypes.data_as(_lib.u64p), end.ctypes.data_as(_lib.u64p), _ptr(ids), ids_off.ctypes.data_as(_lib.u64p),
+                                            _ptr(out), out.count, mask_off.ctypes.data_as(_lib.u64p), C.byref(st)))
+        return (out, mask_off, st) if stats else (out, mask_off)
 
     def merge(self, segs: Sequence["Segment"], tomb: Optional["Tombstones"] = None,
               out_off: Optional[DeviceArray] = None, out_values: Optional[DeviceArray] = None):

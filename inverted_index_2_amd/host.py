@@ -73,6 +73,8 @@ def _lib_typed():
         lib.ii2h_intersect_top.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_matched_terms.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]
         lib.ii2h_masks_copy.argtypes = [vp, vp]
+        lib.ii2h_matched_terms_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
+        lib.ii2h_masks_batch_copy.argtypes = [vp, vp]
         lib.ii2h_intersect_top_weighted.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, C.c_uint64, u64p]
         lib.ii2h_set_resolve.argtypes = [vp, C.c_int]
         lib.ii2h_set_build.argtypes = [vp, C.c_int]
@@ -274,7 +276,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts, MatchedTerms)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts, MatchedTerms, MatchedTermsBatch)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -286,7 +288,7 @@ class InvertedIndex(_Target):
         self._remove(values)
 
     def set_resolve(self, mode: int) -> None:
-        """How intersect_many and intersect_top_batch turn their terms into lists (SetResolve): 0 bisects the host dictionaries,
+        """How intersect_many, intersect_top_batch and matched_terms_batch turn their terms into lists (SetResolve): 0 bisects the host dictionaries,
         1 probes resident dictionaries on the device (ii2_dict_find), -1 (the default) decides by the call's size.  The results
         are the same in every mode."""
         self._ck(self.lib.ii2h_set_resolve(self.h, int(mode)))
@@ -363,6 +365,21 @@ class InvertedIndex(_Target):
         out = np.zeros(max(ids.size * nw.value, 1), np.uint64)
         self.lib.ii2h_masks_copy(self.h, out.ctypes.data)
         return out[: ids.size * nw.value].reshape(ids.size, nw.value)
+
+    def matched_terms_batch(self, pages) -> List[np.ndarray]:
+        """matched_terms for many pages = [(ids, terms), ...] in one device call (MatchedTermsBatch: one upload of all ids, ONE
+        ii2_explain_batch call, one download): result p equals matched_terms(*pages[p])."""
+        pages = [(np.ascontiguousarray(ids, np.uint32), list(terms)) for ids, terms in pages]
+        ids = np.concatenate([i for i, _ in pages] + [np.zeros(1, np.uint32)])              # (never an empty array)
+        ids_off = np.cumsum([0] + [i.size for i, _ in pages]).astype(np.uint64)
+        blob, off = _flat([t for _, terms in pages for t in terms])
+        term_first = np.cumsum([0] + [len(terms) for _, terms in pages]).astype(np.uint64)
+        words_off = np.zeros(len(pages) + 1, np.uint64)
+        self._ck(self.lib.ii2h_matched_terms_batch(self.h, ids.ctypes.data, ids_off.ctypes.data, blob.ctypes.data, off.ctypes.data,
+                                                   term_first.ctypes.data, len(pages), words_off.ctypes.data))
+        out = np.zeros(max(int(words_off[-1]), 1), np.uint64)
+        self.lib.ii2h_masks_batch_copy(self.h, out.ctypes.data)
+        return [out[int(words_off[p]): int(words_off[p + 1])].reshape(i.size, (len(terms) + 63) // 64) for p, (i, terms) in enumerate(pages)]
 
     def intersect_top_weighted(self, terms: List[bytes], weights: List[int], k: int, min_score: int = 1,
                                exclude: List[bytes] = ()) -> List[Tuple[int, int]]:

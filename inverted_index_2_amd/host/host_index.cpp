@@ -24,6 +24,7 @@
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
 //   MatchedTerms(ids, terms)                         additive: per id, which of the terms it lies under (ii2_explain_ranges)
+//   MatchedTermsBatch(pages)                         additive: MatchedTerms for many (ids, terms) pages in one device call (ii2_explain_batch)
 //   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
 //   FuzzySearch(terms, max_dist, prefix, flags) / FuzzyTerms(pattern, max_dist, prefix, flags, limit)   additive: typo-tolerant search (ii2_dict_fuzzy)
 //   RegexSearch(patterns, flags) / RegexTerms(pattern, flags, limit)   additive: regular-expression search (ii2_dict_regex)
@@ -1343,6 +1344,46 @@ class InvertedIndex {
         ck(ctx_, ii2_copy_d2h(ctx_, masks.data(), d_masks.p, n_out * sizeof(uint64_t)), "matched terms");
         return masks;
     }
+    // additive: MatchedTerms for MANY pages - the screenful of ranked pages IntersectTopBatch returns, each against its own terms -
+    // in one device call; result p is that of MatchedTerms(pages[p].ids, pages[p].terms).  Per page the groups are built exactly as
+    // MatchedTerms builds them (a term found in no segment keeps its bit and never sets it; a page none of whose terms is in a
+    // segment keeps its place without a group: its rows are 0), the terms resolved through Resolver::prepare like
+    // IntersectTopBatch's; one upload of all ids, ONE ii2_explain_batch call and one download.
+    struct TermsPage {
+        std::vector<uint32_t> ids;
+        std::vector<Term> terms;
+    };
+    std::vector<std::vector<uint64_t>> MatchedTermsBatch(const std::vector<TermsPage> &pages) const {
+        std::vector<std::vector<uint64_t>> out(pages.size());
+        if (pages.empty()) return out;
+        const std::vector<Term> none;
+        Resolver where(*this);
+        where.prepare(pages.size(), [&](size_t p, bool ex) -> const std::vector<Term> & { return ex ? none : pages[p].terms; });
+        Plan plan;
+        std::vector<uint32_t> ids;
+        std::vector<uint64_t> ids_off(1, 0), mask_off(pages.size() + 1, 0);
+        uint64_t n_out = 0;
+        for (size_t p = 0; p < pages.size(); p++) {
+            const TermsPage &P = pages[p];
+            if (P.ids.size() > II2_EXPLAIN_MAX_IDS) throw std::runtime_error("matched terms batch: page " + std::to_string(p) + ": more than II2_EXPLAIN_MAX_IDS ids");
+            out[p].assign(P.ids.size() * ((P.terms.size() + 63) / 64), 0);
+            if (!plan.add(where, P.terms, none, Absent::EmptyGroup).empty()) n_out += out[p].size();      // (else: no group, no row on the device)
+            ids.insert(ids.end(), P.ids.begin(), P.ids.end());
+            ids_off.push_back(ids.size());
+        }
+        if (!n_out) return out;
+        DevMem d_ids(ctx_), d_masks(ctx_);
+        ck(ctx_, ii2_dev_alloc(ctx_, ids.size() * sizeof(uint32_t), &d_ids.p), "matched terms batch");
+        ck(ctx_, ii2_dev_alloc(ctx_, n_out * sizeof(uint64_t), &d_masks.p), "matched terms batch");
+        ck(ctx_, ii2_copy_h2d(ctx_, d_ids.p, ids.data(), ids.size() * sizeof(uint32_t)), "matched terms batch");
+        ck(ctx_, ii2_explain_batch(ctx_, pages.size(), plan.query_first.data(), plan.group_first.data(), plan.segs.data(), plan.first.data(), plan.end.data(),
+                                   (const uint32_t *)d_ids.p, ids_off.data(), (uint64_t *)d_masks.p, n_out, mask_off.data(), nullptr), "matched terms batch");
+        std::vector<uint64_t> words(n_out);
+        ck(ctx_, ii2_copy_d2h(ctx_, words.data(), d_masks.p, n_out * sizeof(uint64_t)), "matched terms batch");
+        for (size_t p = 0; p < pages.size(); p++)
+            if (mask_off[p + 1] > mask_off[p]) std::copy(words.begin() + mask_off[p], words.begin() + mask_off[p + 1], out[p].begin());
+        return out;
+    }
     // additive: IntersectTop with a weight per term (an idf tier, a field boost): a doc's score is the sum of the weights of the terms it
     // lies under, 1 .. 255 each and at most 255 together; at least min_score.  The groups are IntersectTop's - a term found in no
     // segment keeps its slot, and its weight, and matches nothing - and the call is ONE ii2_topk_weighted_ranges.
@@ -1847,7 +1888,7 @@ struct ii2h_target {
     std::vector<uint32_t> ids;          // last Intersect / RemovedValues result
     std::vector<uint32_t> scores;       // last IntersectTop result: the score of each of ids
     std::vector<std::pair<Term, uint64_t>> counts;      // last TermCounts result
-    std::vector<uint64_t> masks;        // last MatchedTerms result
+    std::vector<uint64_t> masks;        // last MatchedTerms / MatchedTermsBatch result (the pages' rows back to back)
 };
 
 static std::vector<Term> unpack_terms(const uint8_t *bytes, const uint64_t *off, uint64_t n) {
@@ -2108,6 +2149,27 @@ int ii2h_matched_terms(ii2h_target *t, const uint32_t *ids, uint64_t n_ids, cons
 void ii2h_masks_copy(const ii2h_target *t, uint64_t *out) {
     if (!t->masks.empty()) std::memcpy(out, t->masks.data(), t->masks.size() * 8);
 }
+// the same for n_pages pages in one device call: page p holds the ids ids[ids_off[p] .. ids_off[p + 1]) and the terms term_first[p] ..
+// term_first[p + 1] - 1 of (bytes, off).  words_off[p] (n_pages + 1 entries): where page p's rows - ids x ceil(terms / 64) words -
+// start in the target's masks, fetched by ii2h_masks_batch_copy
+int ii2h_matched_terms_batch(ii2h_target *t, const uint32_t *ids, const uint64_t *ids_off, const uint8_t *bytes, const uint64_t *off,
+                             const uint64_t *term_first, uint64_t n_pages, uint64_t *words_off) {
+    H_TRY(t, {
+        std::vector<InvertedIndex::TermsPage> pages(n_pages);
+        for (uint64_t p = 0; p < n_pages; p++) {
+            pages[p].ids.assign(ids + ids_off[p], ids + ids_off[p + 1]);
+            pages[p].terms = unpack_terms(bytes, off + term_first[p], term_first[p + 1] - term_first[p]);
+        }
+        t->masks.clear();
+        words_off[0] = 0;
+        uint64_t p = 0;
+        for (auto &rows : t->index->MatchedTermsBatch(pages)) {
+            t->masks.insert(t->masks.end(), rows.begin(), rows.end());
+            words_off[++p] = t->masks.size();
+        }
+    })
+}
+void ii2h_masks_batch_copy(const ii2h_target *t, uint64_t *out) { ii2h_masks_copy(t, out); }
 int ii2h_intersect_except(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off,
                           uint64_t n_x, uint64_t *n_ids) {
     H_TRY(t, { t->ids = t->index->IntersectExcept(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x)); *n_ids = t->ids.size(); })
