@@ -1280,6 +1280,61 @@ func (c *Ctx) CountRanges(segs []*Segment, listFirst, listEnd []uint64, set unsa
 	return counts, CountStats{uint64(st.n_lists), uint64(st.n_blocks), uint64(st.n_decoded), uint64(st.n_hits), uint32(st.n_windows)}, nil
 }
 
+// HistStats mirrors ii2_hist_stats.
+type HistStats struct {
+	Lists, Blocks, Decoded, Hits, Whole, Split, Wide uint64
+	Windows, Buckets                                 uint32
+}
+
+// HistogramRanges is CountRanges over a value axis (ii2_histogram_ranges): edges holds nBuckets + 1 strictly ascending values, each
+// <= 2^32, bucket b is the ids edges[b] <= id < edges[b+1]; ids outside the axis are counted nowhere.  counts[k*nBuckets+b] is
+// the ids of the k-th list named in bucket b that lie in the doc set.  Ranges and set as CountRanges takes them; set == nil means
+// every doc.
+func (c *Ctx) HistogramRanges(segs []*Segment, listFirst, listEnd []uint64, set unsafe.Pointer, nSet uint64, edges []uint64) ([]uint64, HistStats, error) {
+	if len(listFirst) != len(segs) || len(listEnd) != len(segs) {
+		return nil, HistStats{}, fmt.Errorf("histogram ranges: array lengths disagree")
+	}
+	if len(edges) < 2 {
+		return nil, HistStats{}, fmt.Errorf("histogram ranges: fewer than two edges")
+	}
+	nb := uint64(len(edges) - 1)
+	var named uint64
+	for i := range segs {
+		if listEnd[i] < listFirst[i] {
+			return nil, HistStats{}, fmt.Errorf("histogram ranges: range %d ends before it begins", i)
+		}
+		named += listEnd[i] - listFirst[i]
+	}
+	hs := make([]*C.ii2_seg, len(segs)+1)
+	for i, s := range segs {
+		hs[i] = s.h
+	}
+	counts := make([]uint64, named*nb)
+	var st C.ii2_hist_stats
+	rc := C.ii2_histogram_ranges(c.h, C.uint64_t(len(segs)), (**C.ii2_seg)(unsafe.Pointer(&hs[0])), u64ptr(listFirst), u64ptr(listEnd),
+		(*C.uint32_t)(set), C.uint64_t(nSet), nil, C.uint32_t(nb), u64ptr(edges), u64ptr(counts), C.uint64_t(named*nb), &st)
+	if rc != 0 {
+		return nil, HistStats{}, c.err("histogram ranges", rc)
+	}
+	return counts, HistStats{uint64(st.n_lists), uint64(st.n_blocks), uint64(st.n_decoded), uint64(st.n_hits), uint64(st.n_whole),
+		uint64(st.n_split), uint64(st.n_wide), uint32(st.n_windows), uint32(st.n_buckets)}, nil
+}
+
+// HistogramIDs counts a device set per bucket of a value axis (ii2_histogram_ids): set is a device buffer of nSet ascending,
+// duplicate-free ids, edges as HistogramRanges takes them.
+func (c *Ctx) HistogramIDs(set unsafe.Pointer, nSet uint64, edges []uint64) ([]uint64, error) {
+	if len(edges) < 2 {
+		return nil, fmt.Errorf("histogram ids: fewer than two edges")
+	}
+	counts := make([]uint64, len(edges)-1)
+	rc := C.ii2_histogram_ids(c.h, (*C.uint32_t)(set), C.uint64_t(nSet), nil, C.uint32_t(len(edges)-1), u64ptr(edges), u64ptr(counts),
+		C.uint64_t(len(counts)))
+	if rc != 0 {
+		return nil, c.err("histogram ids", rc)
+	}
+	return counts, nil
+}
+
 // ExplainStats mirrors ii2_explain_stats.
 type ExplainStats struct {
 	IDs, Lists, Blocks, Decoded, Hits uint64

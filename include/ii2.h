@@ -754,6 +754,67 @@ int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const
                      const uint64_t *list_end, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb,
                      uint64_t *counts, uint64_t counts_cap, ii2_count_stats *stats /* may be NULL */);
 
+/* Hits per list AND value bucket - the counts of ii2_count_ranges over the value axis: "matches per hour" for a query (a date
+ * histogram), "matches per hour, per level=*" (terms over time) and, with the set "every doc", a term's frequency over time.  A
+ * posting is a uint32 value - in the reference's use a timestamp or a record id that grows with time - and the axis cuts the
+ * values into n_buckets buckets.
+ *   - the edges: edges[n_buckets + 1] (host memory), strictly ascending, each <= 2^32; bucket b is the ids edges[b] <= id <
+ *     edges[b + 1].  The values are 64-bit only so that edges[n_buckets] = 2^32 can include id 0xFFFFFFFF; on the device the axis
+ *     is a uint32 first id per bucket plus one inclusive last id.  Ids below edges[0] or at / above edges[n_buckets] are counted
+ *     nowhere - the value-range restriction: blocks wholly outside the axis are not read, the set is not marked outside it.
+ *   - ii2_histogram_ranges: ranges, set, tombstones and the order of the lists named are exactly ii2_count_ranges'.
+ *     counts[k * n_buckets + b] = the ids of list k in bucket b that lie in the set and are not in tomb.  d_set == NULL means
+ *     "every doc", minus tomb when given; unlike ii2_count_ranges that form always runs the walk.  With edges = {0, 2^32} the counts
+ *     equal ii2_count_ranges' on the same arguments.
+ *   - ii2_histogram_ids: counts[b] = the ids of the ascending, duplicate-free device set d_set[n_set] in bucket b, minus tomb.  A
+ *     set that is not ascending gives unspecified counts, never an access outside the call's buffers.  n_set == 0: zeros, no
+ *     launch.  Without tomb one thread per bucket bisects the set; with it every id finds its bucket and tests its bit.
+ *   - II2_EINVAL: n_buckets == 0, edges NULL, not strictly ascending or above 2^32; counts == NULL with cells to write; the range
+ *     errors of ii2_count_ranges under this entry point's name; tombstones of another device; NULL ctx; 2^32 ids or more
+ *     (ii2_histogram_ids).  II2_ERANGE: more than II2_HIST_MAX_BUCKETS buckets (chunk the axis), more than II2_HIST_MAX_CELLS
+ *     lists named x buckets (chunk the lists), and ii2_count_ranges' block / range / list limits.  II2_ECAPACITY: counts_cap <
+ *     lists named x n_buckets (ii2_histogram_ids: < n_buckets); nothing is launched and nothing written.
+ *   - all-or-nothing: every argument is checked before anything is launched; counts and stats are written only on success.
+ * ii2_histogram_ranges is ii2_count_ranges' pass with a two-dimensional counter index: one pass over the encoded lists whatever the
+ * number of buckets, the same marking of the set - over the doc span that the set, the lists AND the axis share -, the same summary
+ * skip (option count.summary_skip) and at most two waits (the "every doc" form: one).  A block's doc bounds say, before it is
+ * read, which buckets it can meet (ii2_hist_block): a block inside ONE bucket - most blocks - is counted as ii2_count_ranges
+ * counts it, one atomic per (wave, list, bucket); a block that meets 2 .. 64 buckets or leaves the axis sends each hit through a
+ * bucket search into 64 counters in LDS; a block that meets more adds each hit to its global counter (option hist.whole = 0
+ * sends every block through the bucket search).  Neither call is a set operation: they take no kernel path (ii2_ctx_paths). */
+#define II2_HIST_MAX_BUCKETS 4096u        /* buckets per call; more: II2_ERANGE (callers chunk the axis) */
+#define II2_HIST_MAX_CELLS (1u << 26)     /* lists named x buckets per call; more: II2_ERANGE (callers chunk the lists) */
+typedef struct {
+    uint64_t n_lists;    /* lists named by the ranges (counts written = n_lists x n_buckets) */
+    uint64_t n_blocks;   /* DV1 blocks those lists own */
+    uint64_t n_decoded;  /* blocks decoded, summed over the windows = n_whole + n_split + n_wide */
+    uint64_t n_hits;     /* sum of the counts */
+    uint64_t n_whole;    /* decoded blocks whose bounds lie in ONE bucket: no per-id bucket search */
+    uint64_t n_split;    /* decoded blocks whose bounds meet 2 .. 64 buckets or leave the axis (strip form) */
+    uint64_t n_wide;     /* decoded blocks whose bounds meet more than 64 buckets */
+    uint32_t n_windows;  /* doc windows processed (0: nothing was marked) */
+    uint32_t n_buckets;
+} ii2_hist_stats;        /* 64 bytes */
+int ii2_histogram_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first,
+                         const uint64_t *list_end, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb,
+                         uint32_t n_buckets, const uint64_t *edges /* n_buckets + 1, host */, uint64_t *counts,
+                         uint64_t counts_cap, ii2_hist_stats *stats /* may be NULL */);
+int ii2_histogram_ids(ii2_ctx *ctx, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint32_t n_buckets,
+                      const uint64_t *edges, uint64_t *counts, uint64_t counts_cap);
+/* Host only, no GPU: the arithmetic the histogram kernels run (the same functions).  Both check the edges as the calls above do.
+ * ii2_hist_bucket: *bucket = the bucket of id, -1 outside the axis.  ii2_hist_block: what a block with the doc bounds
+ * [first_doc, up] is to the axis - inside a list `up` is the next block's first doc, at a list's end the list's last doc -: SKIP
+ * the bounds miss the axis (b_lo, b_hi = 0); else *b_lo .. *b_hi are the buckets that the bounds, clipped to the axis, meet, and the
+ * block is WHOLE (both bounds inside one bucket), SPLIT (2 .. 64 buckets, or one bucket with a bound outside the axis) or WIDE
+ * (more than 64 buckets). */
+#define II2_HIST_SKIP 0
+#define II2_HIST_WHOLE 1
+#define II2_HIST_SPLIT 2
+#define II2_HIST_WIDE 3
+int ii2_hist_bucket(const uint64_t *edges, uint32_t n_buckets, uint32_t id, int64_t *bucket /* -1: outside */);
+int ii2_hist_block(const uint64_t *edges, uint32_t n_buckets, uint32_t first_doc, uint32_t up, int *kind, uint32_t *b_lo,
+                   uint32_t *b_hi);
+
 /* Which groups each doc of an id array lies in - what ii2_atleast_ranges, the ii2_topk_* calls and a term search's one group of
  * many lists do not say: highlighting, "matched queries", which 3 of 5 groups gave a score of 3, the d = 0 tier of a fuzzy hit
  * against its d = 2 tier.  The transpose of ii2_count_ranges: one pass over the groups' blocks, a hit sets a bit in its doc's row.
@@ -1176,6 +1237,12 @@ int ii2_selftest(ii2_ctx *ctx);
  *   debug.union_many_no_atomics             timing experiments: that path's mark kernel sets no bit (results wrong)
  *   count.summary_skip                      ii2_count_ranges: 1 (default) a block whose docs meet no marked 2048-doc chunk of the set's
  *                                           bitmap is not decoded; 0 (tests, measuring) every block that meets the window is
+ *                                           (ii2_histogram_ranges too)
+ *   hist.per_wave                           ii2_histogram_ranges: query blocks per wave of its count kernel; 0 (default) by the rule of
+ *                                           the block-wise paths (more than one only above 32 blocks per CU), N > 0 (tests) N
+ *   hist.whole                              ii2_histogram_ranges: 1 (default) a block whose doc bounds lie in one bucket is counted
+ *                                           without a bucket search per id; 0 (tests, measuring) every decoded block is searched.
+ *                                           Same results
  *   intersect.ranges                        ii2_intersect_ranges: 1 = the group path even for single-list groups (default 0: they go to
  *                                           ii2_intersect's paths when the result surely fits)
  *   intersect.ranges_mark                   its filters mark a group into the doc bitmap when the group holds at most N postings per

@@ -78,6 +78,15 @@ class CountStats(C.Structure):
                 ("n_windows", C.c_uint32)]
 
 
+class HistStats(C.Structure):
+    _fields_ = [("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64), ("n_whole", C.c_uint64),
+                ("n_split", C.c_uint64), ("n_wide", C.c_uint64), ("n_windows", C.c_uint32), ("n_buckets", C.c_uint32)]
+
+
+II2_HIST_MAX_BUCKETS, II2_HIST_MAX_CELLS = 4096, 1 << 26
+II2_HIST_SKIP, II2_HIST_WHOLE, II2_HIST_SPLIT, II2_HIST_WIDE = 0, 1, 2, 3
+
+
 class ExplainStats(C.Structure):
     _fields_ = [("n_ids", C.c_uint64), ("n_lists", C.c_uint64), ("n_blocks", C.c_uint64), ("n_decoded", C.c_uint64), ("n_hits", C.c_uint64),
                 ("n_windows", C.c_uint32), ("n_words", C.c_uint32), ("log2_slots", C.c_uint32), ("pad", C.c_uint32)]
@@ -190,6 +199,10 @@ PROTOTYPES = {
     "ii2_query_batch": (C.c_int, [vp, C.c_uint64, u8p, u64p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_query_batch_groups": (C.c_int, [vp, C.c_uint64, u64p, u64p, u8p, vpp, u64p, u64p, vp, vp, C.c_uint64, u64p]),
     "ii2_count_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, C.c_uint64, vp, u64p, C.c_uint64, C.POINTER(CountStats)]),
+    "ii2_histogram_ranges": (C.c_int, [vp, C.c_uint64, vpp, u64p, u64p, vp, C.c_uint64, vp, C.c_uint32, u64p, u64p, C.c_uint64, C.POINTER(HistStats)]),
+    "ii2_histogram_ids": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint32, u64p, u64p, C.c_uint64]),
+    "ii2_hist_bucket": (C.c_int, [u64p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64)]),
+    "ii2_hist_block": (C.c_int, [u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), u32p, u32p]),
     "ii2_explain_ranges": (C.c_int, [vp, C.c_uint64, u64p, vpp, u64p, u64p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(ExplainStats)]),
     "ii2_explain_slot": (C.c_int, [C.c_uint32, C.c_uint32, u32p]),
     "ii2_explain_batch": (C.c_int, [vp, C.c_uint64, u64p, u64p, vpp, u64p, u64p, vp, u64p, vp, C.c_uint64, u64p, C.POINTER(ExplainBatchStats)]),

@@ -1174,6 +1174,8 @@ int ii2_set_option(ii2_ctx *ctx, const char *name, int64_t value) {
     else if (k == "union.many_window_log2") ctx->opt_union_many_window_log2 = value;
     else if (k == "debug.union_many_no_atomics") ctx->opt_union_many_no_atomics = value;
     else if (k == "count.summary_skip") ctx->opt_count_summary_skip = value;
+    else if (k == "hist.per_wave") ctx->opt_hist_per_wave = value;
+    else if (k == "hist.whole") ctx->opt_hist_whole = value;
     else if (k == "match.stage") ctx->opt_match_stage = value;
     else if (k == "fuzzy.stage") ctx->opt_fuzzy_stage = value;
     else if (k == "fuzzy.wide") ctx->opt_fuzzy_wide = value;

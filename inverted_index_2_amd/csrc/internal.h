@@ -121,6 +121,8 @@ struct ii2_ctx {
     void *h_um = nullptr;               // pinned staging of its range descriptors (grow-only)
     size_t h_um_cap = 0;
     int64_t opt_count_summary_skip = 1; // ii2_count_ranges: blocks whose docs meet no marked chunk of the bitmap's summary are not decoded (0: tests, measuring)
+    int64_t opt_hist_per_wave = 0;      // ii2_histogram_ranges: query blocks per wave of its count kernel (0: um_per_wave's rule; tests inject one)
+    int64_t opt_hist_whole = 1;         // ... 0 (tests, measuring): every decoded block goes through the per-id bucket search
     int64_t opt_intersect_ranges = 0;   // 1: ii2_intersect_ranges takes the group path even where ii2_intersect's paths would do
     int64_t opt_ir_mark = 64;           // ... whose filters mark a group with at most this many postings per (list x 256 candidates), or
                                         //     fewer than 4 runs of 256 candidates per CU (0: always probe)
@@ -719,6 +721,21 @@ struct CountParams {
 hipError_t launch_cr_edges(const CountParams &p, hipStream_t s);
 hipError_t launch_cr_mark(const CountParams &p, hipStream_t s);
 hipError_t launch_cr_count(const CountParams &p, bool every_doc, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+
+// hits per (list, value bucket) (histogram.hip): the count's walk with a two-dimensional counter index.  The axis on the device:
+// first[b] = the first id of bucket b, last = the inclusive last id of the last bucket (hist_device.h)
+struct HistParams {
+    CountParams c;               // the walk and the mark; counts = [lists named x n_buckets], list-major; decoded = [3 x CR_DECODED_SLOTS]:
+                                 //     blocks decoded as WHOLE, as SPLIT, as WIDE; doc_lo / doc_hi clipped to the axis
+    const uint32_t *first;       // [n_buckets]
+    uint32_t n_buckets;          // 1 .. II2_HIST_MAX_BUCKETS
+    uint32_t last;
+    uint32_t whole;              // 0: a WHOLE block goes through the SPLIT sink (option hist.whole)
+    uint32_t first0;             // first[0]
+};
+hipError_t launch_hs_count(const HistParams &p, bool every_doc, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// ii2_histogram_ids: c.set / n_set / tomb, counts = [n_buckets]
+hipError_t launch_hs_ids(const HistParams &p, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // which groups each doc of an id array lies in (explain_ranges.hip): the count's walk with another sink - a hit ORs its group's bit
 // into the row of its doc, which an open-addressing table of (id << 32 | row) entries finds (empty slots are all-ones)

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "atleast_count.h"
+#include "hist_device.h"
 #include "internal.h"
 #include "topk_batch_run.h"
 #include "topk_count.h"
@@ -1084,24 +1085,32 @@ static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, ui
     return II2_OK;
 }
 
-static int count_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
-                                 const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts, uint64_t counts_cap,
-                                 ii2_count_stats *stats) {
-    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, "ii2_count_ranges: bad argument");
-    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_count_ranges: tombstones live on another device");
-    if (n_set > (1ull << 32)) return fail(ctx, II2_EINVAL, "ii2_count_ranges: more than 2^32 set ids");
-    // the ranges one by one: those that own blocks keep the index of their first list's count
-    CountIn in;
+// The checks that the counting entry points share (`who` names the one in the messages), and what they find out: the ranges one
+// by one - those that own blocks keep the index of their first list's count.
+static int count_collect(ii2_ctx *ctx, const char *who, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                         uint64_t n_set, const ii2_tomb *tomb, CountIn &in) {
+    const std::string w(who);
+    if (n && (!segs || !list_first || !list_end)) return fail(ctx, II2_EINVAL, (w + ": bad argument").c_str());
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, (w + ": tombstones live on another device").c_str());
+    if (n_set > (1ull << 32)) return fail(ctx, II2_EINVAL, (w + ": more than 2^32 set ids").c_str());
     uint64_t n_nonempty = 0;
     for (uint64_t i = 0; i < n; i++) {
         const size_t before = in.rs.size();
-        if (int rc = collect_ranges(ctx, "ii2_count_ranges", 1, segs + i, list_first + i, list_end + i, in.rs, &in.n_blocks, &n_nonempty)) return rc;
-        if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_count_ranges: 2^31 lists or more in one call");
+        if (int rc = collect_ranges(ctx, who, 1, segs + i, list_first + i, list_end + i, in.rs, &in.n_blocks, &n_nonempty)) return rc;
+        if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, (w + ": 2^31 lists or more in one call").c_str());
         if (in.rs.size() > before) in.out_first.push_back((uint32_t)in.n_named);
         in.n_named += list_end[i] - list_first[i];
     }
-    if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, "ii2_count_ranges: 2^31 lists or more in one call");
-    if (in.n_blocks >= 0xFFFFFFFFull || in.rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, "ii2_count_ranges: more than 2^32 - 2 blocks in one call");
+    if (in.n_named >= (1ull << 31)) return fail(ctx, II2_ERANGE, (w + ": 2^31 lists or more in one call").c_str());
+    if (in.n_blocks >= 0xFFFFFFFFull || in.rs.size() >= 0xFFFFFFFFull) return fail(ctx, II2_ERANGE, (w + ": more than 2^32 - 2 blocks in one call").c_str());
+    return II2_OK;
+}
+
+static int count_ranges_unlocked(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                 const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts, uint64_t counts_cap,
+                                 ii2_count_stats *stats) {
+    CountIn in;
+    if (int rc = count_collect(ctx, "ii2_count_ranges", n, segs, list_first, list_end, n_set, tomb, in)) return rc;
     if (in.n_named && !counts) return fail(ctx, II2_EINVAL, "ii2_count_ranges: counts is NULL");
     if (counts_cap < in.n_named) return fail(ctx, II2_ECAPACITY, "ii2_count_ranges: counts holds fewer entries than lists are named (nothing written)");
     if (!in.n_blocks || (d_set && !n_set)) return count_done(in, counts, stats);
@@ -1126,6 +1135,244 @@ extern "C" int ii2_count_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *
     std::lock_guard<std::mutex> g(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return count_ranges_unlocked(ctx, n, segs, list_first, list_end, d_set, n_set, tomb, counts, counts_cap, stats);
+}
+
+// ---- hits per list and value bucket --------------------------------------------------------------
+// the value axis of a histogram call as the device takes it (hist_device.h)
+struct HistAxis {
+    std::vector<uint32_t> first;                                // [n_buckets] edges[0 .. n_buckets)
+    uint32_t last = 0;                                          // edges[n_buckets] - 1
+};
+// the edge checks of every histogram entry point; *msg says what is wrong
+static int hist_check_edges(uint32_t n_buckets, const uint64_t *edges, const char **msg) {
+    *msg = "no bucket, or edges is NULL";
+    if (!n_buckets || !edges) return II2_EINVAL;
+    *msg = "more than II2_HIST_MAX_BUCKETS buckets in one call";
+    if (n_buckets > II2_HIST_MAX_BUCKETS) return II2_ERANGE;
+    *msg = "the edges are not strictly ascending values <= 2^32";
+    for (uint32_t b = 0; b < n_buckets; b++)
+        if (edges[b] >= edges[b + 1]) return II2_EINVAL;
+    if (edges[n_buckets] > (1ull << 32)) return II2_EINVAL;
+    return II2_OK;
+}
+static int hist_axis(ii2_ctx *ctx, const char *who, uint32_t n_buckets, const uint64_t *edges, HistAxis &ax) {
+    const char *msg = nullptr;
+    if (int rc = hist_check_edges(n_buckets, edges, &msg)) return fail(ctx, rc, (std::string(who) + ": " + msg).c_str());
+    ax.first.resize(n_buckets);
+    for (uint32_t b = 0; b < n_buckets; b++) ax.first[b] = (uint32_t)edges[b];
+    ax.last = (uint32_t)(edges[n_buckets] - 1u);
+    return II2_OK;
+}
+
+extern "C" int ii2_hist_bucket(const uint64_t *edges, uint32_t n_buckets, uint32_t id, int64_t *bucket) {
+    const char *msg = nullptr;
+    if (int rc = hist_check_edges(n_buckets, edges, &msg)) return rc;
+    if (!bucket) return II2_EINVAL;
+    *bucket = hist_bucket(edges, n_buckets, (uint32_t)(edges[n_buckets] - 1u), id);
+    return II2_OK;
+}
+
+extern "C" int ii2_hist_block(const uint64_t *edges, uint32_t n_buckets, uint32_t first_doc, uint32_t up, int *kind, uint32_t *b_lo, uint32_t *b_hi) {
+    const char *msg = nullptr;
+    if (int rc = hist_check_edges(n_buckets, edges, &msg)) return rc;
+    if (!kind || !b_lo || !b_hi) return II2_EINVAL;
+    uint32_t lo = 0, hi = 0;
+    *kind = hist_block(edges, n_buckets, edges[0], (uint32_t)(edges[n_buckets] - 1u), first_doc, up, &lo, &hi);
+    *b_lo = lo;
+    *b_hi = hi;
+    return II2_OK;
+}
+
+// counts and stats of a histogram call that succeeded with nothing to count: every cell 0
+static int hist_done(const CountIn &in, uint32_t n_buckets, uint64_t *counts, ii2_hist_stats *stats) {
+    if (in.n_named) std::memset(counts, 0, in.n_named * n_buckets * sizeof(uint64_t));
+    if (stats) *stats = ii2_hist_stats{in.n_named, in.n_blocks, 0, 0, 0, 0, 0, 0, n_buckets};
+    return II2_OK;
+}
+
+// count_many with a counter per (list, bucket) (histogram.hip): the axis goes up with the descriptors in the one staging copy, the
+// docs that can hit are the lists' span clipped to the set's AND to the axis.  At most two waits - the span fetch and the final
+// read; the "every doc" form waits once.
+static int hist_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, const HistAxis &ax, uint64_t *counts,
+                     ii2_hist_stats *stats) {
+    hipStream_t st = ctx->stream;
+    const std::vector<RangeIn> &rs = in.rs;
+    const size_t nr = rs.size();
+    const uint32_t nb = (uint32_t)ax.first.size();
+    const bool every_doc = !d_set;
+    if (int rc = um_scratch_clean(ctx)) return rc;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    const bool mirrored = mirrored_span(rs, &lo, &hi);
+    if (every_doc) {
+        // no set to fetch a span of: the lists' mirrored span where there is one, clipped to the axis, before anything goes up
+        if (!mirrored) lo = 0, hi = 0xFFFFFFFFu;
+        lo = std::max(lo, ax.first[0]);
+        hi = std::min(hi, ax.last);
+        if (lo > hi) return hist_done(in, nb, counts, stats);
+    }
+    // staging: range descriptors + block prefix, the ranges' first counters, the axis, and room for the counters on their way back
+    const size_t n_cells = (size_t)in.n_named * nb, n_words = n_cells + 3 * CR_DECODED_SLOTS;
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), ax_off = um_bytes + align_up(nr * sizeof(uint32_t));
+    const size_t up_bytes = ax_off + align_up(nb * sizeof(uint32_t));
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + n_words * sizeof(uint32_t), false, "ii2_histogram_ranges: staging allocation failed"))
+        return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    um_desc_fill(rs, 0, nr, h);
+    std::memcpy(h + um_bytes, in.out_first.data(), nr * sizeof(uint32_t));
+    std::memcpy(h + ax_off, ax.first.data(), nb * sizeof(uint32_t));
+    uint32_t *h_words = (uint32_t *)(h + up_bytes);
+    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_words * sizeof(uint32_t)) + 2 * 256 + 4096)) return rc;
+    uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
+    uint32_t *d_words = ws_take<uint32_t>(ctx, n_words);
+    uint32_t *d_span = ws_take<uint32_t>(ctx, 4);                // {lists' first doc, lists' last doc, set's first id, set's last id}
+    UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
+    std::memset(&bp, 0, sizeof bp);
+    bp.ranges = (const UmRange *)d_stage;
+    bp.pre = (const uint32_t *)(d_stage + desc_bytes);
+    bp.n_ranges = (uint32_t)nr;
+    bp.n_blocks = (uint32_t)in.n_blocks;
+    bp.bounds = d_span;
+    HistParams hp;
+    std::memset(&hp, 0, sizeof hp);
+    CountParams &p = hp.c;
+    p.ranges = bp.ranges;
+    p.pre = bp.pre;
+    p.out_first = (const uint32_t *)(d_stage + um_bytes);
+    p.n_ranges = bp.n_ranges;
+    p.n_blocks = bp.n_blocks;
+    p.per_wave = ctx->opt_hist_per_wave > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_hist_per_wave, 1 << 20) : um_per_wave(ctx, in.n_blocks);
+    p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
+    p.set = d_set;
+    p.n_set = n_set;
+    set_tomb(p, tomb);
+    p.counts = d_words;
+    p.decoded = d_words + n_cells;
+    p.edges = d_span + 2;
+    p.doc_lo = lo;                                              // (the "every doc" form; marked_windows sets them per window)
+    p.doc_hi = hi;
+    hp.first = (const uint32_t *)(d_stage + ax_off);
+    hp.n_buckets = nb;
+    hp.first0 = ax.first[0];
+    hp.last = ax.last;
+    hp.whole = ctx->opt_hist_whole ? 1u : 0u;
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_words, 0, n_words * sizeof(uint32_t), st));
+    uint32_t n_win = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    if (every_doc) {
+        HIP_TRY(ctx, launch_hs_count(hp, true, st, e0, e1));
+    } else {
+        if (!mirrored) {
+            HIP_TRY(ctx, hipMemsetAsync(d_span, 0xFF, sizeof(uint32_t), st));
+            HIP_TRY(ctx, hipMemsetAsync(d_span + 1, 0, sizeof(uint32_t), st));
+            HIP_TRY(ctx, launch_union_many_bounds(bp, st));
+        }
+        HIP_TRY(ctx, launch_cr_edges(p, st));
+        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
+        HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (!mirrored) {
+            lo = hb[0];
+            hi = hb[1];
+        }
+        if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_histogram_ranges: inconsistent list bounds");
+        // the docs that can hit: the lists' span clipped to the set's and to the axis
+        lo = std::max(std::max(lo, hb[2]), ax.first[0]);
+        hi = std::min(std::min(hi, hb[3]), ax.last);
+        if (lo > hi) {                                          // no overlap: nothing was marked, the staging copy has been waited for
+            ctx->um_dirty = false;
+            return hist_done(in, nb, counts, stats);
+        }
+        if (int rc = marked_windows(ctx, "ii2_histogram_ranges", p, lo, hi, &n_win, [&]() {
+                const hipError_t e = launch_hs_count(hp, false, st, e0, e1);
+                e0 = e1 = nullptr;
+                return e;
+            }))
+            return rc;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->um_dirty = false;
+    uint64_t hits = 0, kinds[3] = {0, 0, 0};
+    for (size_t k = 0; k < n_cells; k++) {
+        counts[k] = h_words[k];
+        hits += h_words[k];
+    }
+    for (uint32_t k = 0; k < 3 * CR_DECODED_SLOTS; k++) kinds[k / CR_DECODED_SLOTS] += h_words[n_cells + k];
+    if (stats) *stats = ii2_hist_stats{in.n_named, in.n_blocks, kinds[0] + kinds[1] + kinds[2], hits, kinds[0], kinds[1], kinds[2], n_win, nb};
+    return II2_OK;
+}
+
+extern "C" int ii2_histogram_ranges(ii2_ctx *ctx, uint64_t n, const ii2_seg *const *segs, const uint64_t *list_first, const uint64_t *list_end,
+                                    const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint32_t n_buckets, const uint64_t *edges,
+                                    uint64_t *counts, uint64_t counts_cap, ii2_hist_stats *stats) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HistAxis ax;
+    if (int rc = hist_axis(ctx, "ii2_histogram_ranges", n_buckets, edges, ax)) return rc;
+    CountIn in;
+    if (int rc = count_collect(ctx, "ii2_histogram_ranges", n, segs, list_first, list_end, n_set, tomb, in)) return rc;
+    if (in.n_named * n_buckets > II2_HIST_MAX_CELLS) return fail(ctx, II2_ERANGE, "ii2_histogram_ranges: more than II2_HIST_MAX_CELLS lists x buckets in one call");
+    if (in.n_named && !counts) return fail(ctx, II2_EINVAL, "ii2_histogram_ranges: counts is NULL");
+    if (counts_cap < in.n_named * n_buckets)
+        return fail(ctx, II2_ECAPACITY, "ii2_histogram_ranges: counts holds fewer entries than lists named x buckets (nothing written)");
+    if (!in.n_blocks || (d_set && !n_set)) return hist_done(in, n_buckets, counts, stats);
+    return hist_many(ctx, in, d_set, n_set, tomb, ax, counts, stats);
+}
+
+// The bucket counts of a device set: without tombstones a bisection of the set per edge, with them one pass over the ids.  One
+// wait: the counters' copy.
+extern "C" int ii2_histogram_ids(ii2_ctx *ctx, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint32_t n_buckets,
+                                 const uint64_t *edges, uint64_t *counts, uint64_t counts_cap) {
+    if (!ctx) return II2_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HistAxis ax;
+    if (int rc = hist_axis(ctx, "ii2_histogram_ids", n_buckets, edges, ax)) return rc;
+    if (tomb && tomb->device != ctx->device) return fail(ctx, II2_EINVAL, "ii2_histogram_ids: tombstones live on another device");
+    if (n_set >= (1ull << 32)) return fail(ctx, II2_EINVAL, "ii2_histogram_ids: 2^32 set ids or more");
+    if (n_set && !d_set) return fail(ctx, II2_EINVAL, "ii2_histogram_ids: the set is NULL");
+    if (!counts) return fail(ctx, II2_EINVAL, "ii2_histogram_ids: counts is NULL");
+    if (counts_cap < n_buckets) return fail(ctx, II2_ECAPACITY, "ii2_histogram_ids: counts holds fewer entries than buckets (nothing written)");
+    if (!n_set) {
+        std::memset(counts, 0, n_buckets * sizeof(uint64_t));
+        return II2_OK;
+    }
+    hipStream_t st = ctx->stream;
+    if (int rc = um_scratch_clean(ctx)) return rc;               // (a stopped call's copy out of the staging block may be pending)
+    const size_t ax_bytes = align_up(n_buckets * sizeof(uint32_t));
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, 2 * ax_bytes, false, "ii2_histogram_ids: staging allocation failed")) return rc;
+    uint8_t *h = (uint8_t *)ctx->h_um;
+    std::memcpy(h, ax.first.data(), n_buckets * sizeof(uint32_t));
+    uint32_t *h_words = (uint32_t *)(h + ax_bytes);
+    if (int rc = ii2_ws_reserve(ctx, 2 * ax_bytes + 4096)) return rc;
+    uint32_t *d_first = ws_take<uint32_t>(ctx, n_buckets);
+    uint32_t *d_words = ws_take<uint32_t>(ctx, n_buckets);
+    HistParams hp;
+    std::memset(&hp, 0, sizeof hp);
+    hp.c.set = d_set;
+    hp.c.n_set = n_set;
+    set_tomb(hp.c, tomb);
+    hp.c.counts = d_words;
+    hp.first = d_first;
+    hp.n_buckets = n_buckets;
+    hp.last = ax.last;
+    ctx->um_dirty = true;
+    HIP_TRY(ctx, hipMemcpyAsync(d_first, h, n_buckets * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (tomb) {
+        HIP_TRY(ctx, hipMemsetAsync(d_words, 0, n_buckets * sizeof(uint32_t), st));
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ii2_profile_pair(ctx, &e0, &e1);
+    HIP_TRY(ctx, launch_hs_ids(hp, st, e0, e1));
+    HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_buckets * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    ctx->um_dirty = false;
+    for (uint32_t b = 0; b < n_buckets; b++) counts[b] = h_words[b];
+    return II2_OK;
 }
 
 // ---- AND of ORs over list ranges ----------------------------------------------------------------

@@ -8,16 +8,25 @@
 
 namespace ii2 {
 
-// inclusive OR over the lanes of each run of equal keys (runs are contiguous): the run's last lane holds the run's OR
-__device__ __forceinline__ uint32_t seg_or(uint32_t key, uint32_t bits) {
+// inclusive scan by `op` over the lanes of each run of equal keys (runs are contiguous): the run's last lane holds the run's total
+template <class Op>
+__device__ __forceinline__ uint32_t seg_scan(uint32_t key, uint32_t v, Op op) {
     const int l = lane_id();
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t ok = (uint32_t)__shfl_up((int)key, d, 64);
-        const uint32_t ob = (uint32_t)__shfl_up((int)bits, d, 64);
-        if (l >= d && ok == key) bits |= ob;
+        const uint32_t ov = (uint32_t)__shfl_up((int)v, d, 64);
+        if (l >= d && ok == key) v = op(v, ov);
     }
-    return bits;
+    return v;
+}
+// ... the run's OR
+__device__ __forceinline__ uint32_t seg_or(uint32_t key, uint32_t bits) {
+    return seg_scan(key, bits, [](uint32_t a, uint32_t b) { return a | b; });
+}
+// ... the run's sum (histogram.hip)
+__device__ __forceinline__ uint32_t seg_add(uint32_t key, uint32_t n) {
+    return seg_scan(key, n, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
 // the range that holds query block g: the last r with pre[r] <= g

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import II2_FUZZY_TRANSPOSE, II2_MATCH_UTF8, FuzzyStats  # noqa: F401
 from ._lib import RegexStats
-from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, ExplainBatchStats, ExplainStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
+from ._lib import II2_DEVICE, II2_HOST, II2_MATCH_CONTAINS, II2_MATCH_GLOB, II2_MATCH_NOCASE, II2_MATCH_SUFFIX, II2_OP_AND, II2_OP_OR, AtleastStats, BuildStats, CountStats, DictBuildStats, ExplainBatchStats, ExplainStats, HistStats, MatchStats, MergeStats, SegInfo, TopkBatchStats, TopkStats, TopkwStats
 
 SKIP_DTYPE = np.dtype([("first_doc", "<u4"), ("byte_off", "<u4")])
 
@@ -270,6 +270,33 @@ def explain_slot(id: int, log2_slots: int) -> int:
     if rc:
         raise II2Error(rc, "ii2_explain_slot")
     return slot.value
+
+
+def _edges(edges):
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.uint64).ravel())
+    return e, max(int(e.size) - 1, 0)
+
+
+def hist_bucket(edges, id: int) -> int:
+    """The bucket of an id on a histogram axis, -1 outside it, by the function the histogram kernels run (ii2_hist_bucket): edges
+    = n_buckets + 1 strictly ascending values <= 2^32, bucket b = [edges[b], edges[b + 1]).  Needs no context and no GPU."""
+    e, nb = _edges(edges)
+    b = C.c_int64(0)
+    rc = _lib.load().ii2_hist_bucket(e.ctypes.data_as(_lib.u64p) if e.size else None, nb, int(id), C.byref(b))
+    if rc:
+        raise II2Error(rc, "ii2_hist_bucket")
+    return b.value
+
+
+def hist_block(edges, first_doc: int, up: int):
+    """What a block with the doc bounds [first_doc, up] is to a histogram axis (ii2_hist_block): (kind, b_lo, b_hi), kind one of
+    II2_HIST_SKIP / WHOLE / SPLIT / WIDE.  Needs no context and no GPU."""
+    e, nb = _edges(edges)
+    kind, lo, hi = C.c_int(-1), C.c_uint32(0), C.c_uint32(0)
+    rc = _lib.load().ii2_hist_block(e.ctypes.data_as(_lib.u64p) if e.size else None, nb, int(first_doc), int(up), C.byref(kind), C.byref(lo), C.byref(hi))
+    if rc:
+        raise II2Error(rc, "ii2_hist_block")
+    return kind.value, lo.value, hi.value
 
 
 class DeviceArray:
@@ -934,6 +961,39 @@ class Context:
         self._ck(self.lib.ii2_count_ranges(self.h, n, segs, first, end, _ptr(dset), int(n_set), tomb.h if tomb else None,
                                            counts.ctypes.data_as(_lib.u64p), counts.size, C.byref(st)))
         return counts, st
+
+    def histogram_ranges(self, ranges, edges, dset: Optional[DeviceArray] = None, n_set: Optional[int] = None,
+                         tomb: Optional["Tombstones"] = None):
+        """Hits per list and value bucket (ii2_histogram_ranges): ranges, dset, n_set and tomb as count_ranges takes them; edges =
+        n_buckets + 1 strictly ascending values <= 2^32, bucket b = the ids edges[b] <= id < edges[b + 1].  Returns (uint64 counts
+        of shape (lists named, n_buckets); HistStats)."""
+        ranges = [(s, int(a), int(b)) for s, a, b in ranges]
+        n = len(ranges)
+        segs = (C.c_void_p * max(n, 1))(*[s.h for s, _, _ in ranges])
+        first = (C.c_uint64 * max(n, 1))(*[a for _, a, _ in ranges])
+        end = (C.c_uint64 * max(n, 1))(*[b for _, _, b in ranges])
+        if dset is None:
+            n_set = 0
+        elif n_set is None:
+            n_set = dset.count
+        e, nb = _edges(edges)
+        n_named = sum(max(b - a, 0) for _, a, b in ranges)
+        counts = np.zeros((n_named, nb), np.uint64)
+        st = HistStats()
+        self._ck(self.lib.ii2_histogram_ranges(self.h, n, segs, first, end, _ptr(dset), int(n_set), tomb.h if tomb else None, nb,
+                                               e.ctypes.data_as(_lib.u64p), counts.ctypes.data_as(_lib.u64p), counts.size, C.byref(st)))
+        return counts, st
+
+    def histogram_ids(self, dset: DeviceArray, n_set: Optional[int], edges, tomb: Optional["Tombstones"] = None):
+        """The bucket counts of an ascending, duplicate-free device set (ii2_histogram_ids): uint64 [n_buckets], the first n_set ids
+        of dset (None: all of it) per bucket of `edges`, minus tomb."""
+        if n_set is None:
+            n_set = dset.count
+        e, nb = _edges(edges)
+        counts = np.zeros(nb, np.uint64)
+        self._ck(self.lib.ii2_histogram_ids(self.h, _ptr(dset), int(n_set), tomb.h if tomb else None, nb, e.ctypes.data_as(_lib.u64p),
+                                            counts.ctypes.data_as(_lib.u64p), counts.size))
+        return counts
 
     def explain_ranges(self, groups, ids: DeviceArray, n_ids: Optional[int] = None, stats: bool = False, out: Optional[DeviceArray] = None):
         """Which groups each doc lies in (ii2_explain_ranges): groups = [[(Segment, first, end), ...], ...] as intersect_ranges

@@ -90,6 +90,12 @@ def _lib_typed():
         lib.ii2h_count_term_len.restype = C.c_uint64
         lib.ii2h_count_term_len.argtypes = [vp, C.c_uint64]
         lib.ii2h_count_copy.argtypes = [vp, C.c_uint64, vp, u64p]
+        lib.ii2h_histogram.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]
+        lib.ii2h_hist_copy.argtypes = [vp, vp]
+        lib.ii2h_term_histogram.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, u64p]
+        lib.ii2h_term_hist_term_len.restype = C.c_uint64
+        lib.ii2h_term_hist_term_len.argtypes = [vp, C.c_uint64]
+        lib.ii2h_term_hist_copy.argtypes = [vp, C.c_uint64, vp, vp]
         for f in ("ii2h_result_term_len", "ii2h_result_values_len"):
             getattr(lib, f).restype = C.c_uint64
             getattr(lib, f).argtypes = [vp, C.c_uint64]
@@ -276,7 +282,7 @@ class Shard(_Target):
 
 
 class InvertedIndex(_Target):
-    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts, MatchedTerms, MatchedTermsBatch)."""
+    """inverted_index.go: Put / Read / Merge / PutRemoved / PrefixSearch (+ Intersect, IntersectExcept, IntersectAtLeast, IntersectTop, IntersectTopWeighted, IntersectTopBatch, IntersectMany, TermCounts, Histogram, TermHistogram, MatchedTerms, MatchedTermsBatch)."""
 
     def __init__(self, ctx: Context, basedir: Optional[str] = None):
         super().__init__(ctx, True, basedir)
@@ -458,6 +464,41 @@ class InvertedIndex(_Target):
             c = C.c_uint64()
             self.lib.ii2h_count_copy(self.h, i, tb.ctypes.data, C.byref(c))
             out[tb[:tl].tobytes()] = c.value
+        return out
+
+    def histogram(self, terms: List[bytes], edges, exclude: List[bytes] = ()) -> np.ndarray:
+        """The date histogram of a query (Histogram: the result stays on the device, one ii2_histogram_ids call): uint64
+        [n_buckets], how many ids of intersect_except(terms, exclude) fall into each bucket edges[b] <= id < edges[b + 1] of the
+        n_buckets + 1 strictly ascending `edges` (each <= 2^32); ids outside the axis are counted nowhere."""
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.uint64).ravel())
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_histogram(self.h, blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data, x_off.ctypes.data, len(exclude),
+                                         e.ctypes.data, e.size, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint64)
+        self.lib.ii2h_hist_copy(self.h, out.ctypes.data)
+        return out[: n.value]
+
+    def term_histogram(self, prefix: bytes, edges, terms: List[bytes] = (), exclude: List[bytes] = ()) -> Dict[bytes, np.ndarray]:
+        """Terms over time (TermHistogram: one ii2_histogram_ranges call over the prefix's run of every segment): term_counts per
+        bucket of `edges` - for every term that starts with `prefix` a uint64 [n_buckets] row, the distinct docs under it among
+        intersect_except(terms, exclude) per bucket; terms with an all-zero row are left out.  Without `terms` the doc set is
+        every doc: each term's frequency over the value axis."""
+        blob, off = _flat(list(terms))
+        x_blob, x_off = _flat(list(exclude))
+        pre = np.frombuffer(bytes(prefix) + b"\0", dtype=np.uint8).copy()
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.uint64).ravel())
+        n = C.c_uint64()
+        self._ck(self.lib.ii2h_term_histogram(self.h, pre.ctypes.data, len(prefix), blob.ctypes.data, off.ctypes.data, len(terms), x_blob.ctypes.data,
+                                              x_off.ctypes.data, len(exclude), e.ctypes.data, e.size, C.byref(n)))
+        out = {}
+        for i in range(n.value):
+            tl = self.lib.ii2h_term_hist_term_len(self.h, i)
+            tb = np.zeros(max(tl, 1), np.uint8)
+            row = np.zeros(max(e.size - 1, 1), np.uint64)
+            self.lib.ii2h_term_hist_copy(self.h, i, tb.ctypes.data, row.ctypes.data)
+            out[tb[:tl].tobytes()] = row[: e.size - 1]
         return out
 
     @property

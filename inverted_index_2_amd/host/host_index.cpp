@@ -23,6 +23,8 @@
 //   IntersectTopBatch(queries)                       additive: many IntersectTopWeighted queries in one device call
 //   IntersectMany(queries)                           additive: many IntersectExcept queries in one device call
 //   TermCounts(prefix, terms, except)                additive: per term under a prefix, the docs of IntersectExcept under it (facets)
+//   Histogram(terms, except, edges)                  additive: the docs of IntersectExcept per value bucket (ii2_histogram_ids)
+//   TermHistogram(prefix, terms, except, edges)      additive: TermCounts per value bucket (ii2_histogram_ranges)
 //   MatchedTerms(ids, terms)                         additive: per id, which of the terms it lies under (ii2_explain_ranges)
 //   MatchedTermsBatch(pages)                         additive: MatchedTerms for many (ids, terms) pages in one device call (ii2_explain_batch)
 //   MatchSearch(patterns, kind) / MatchTerms(pattern, kind, limit)   additive: substring, suffix and wildcard search (ii2_dict_match)
@@ -1772,6 +1774,128 @@ class InvertedIndex {
         }
         return out;
     }
+    // the buckets of a histogram's axis, its edges checked as the library checks them - by ii2_hist_bucket, which needs no device - so
+    // that bad edges are an error even where nothing is left to count
+    static uint32_t hist_buckets(const std::vector<uint64_t> &edges, const char *what) {
+        if (edges.size() < 2) throw Error(std::string(what) + ": fewer than two edges");
+        int64_t b = 0;
+        const int rc = ii2_hist_bucket(edges.data(), (uint32_t)std::min<size_t>(edges.size() - 1, 0xFFFFFFFFu), 0, &b);
+        if (rc == II2_ERANGE) throw Error(std::string(what) + ": more than II2_HIST_MAX_BUCKETS buckets");
+        if (rc) throw Error(std::string(what) + ": the edges are not strictly ascending values <= 2^32");
+        return (uint32_t)(edges.size() - 1);
+    }
+    // additive: the date histogram of a query - how many of the ids that IntersectExcept(terms, except) returns fall into each bucket
+    // of the value axis: edges = n_buckets + 1 strictly ascending values <= 2^32, bucket b = the ids edges[b] <= id < edges[b + 1]
+    // (2^32 as the last edge includes id 0xFFFFFFFF); ids outside the axis are counted nowhere.  IntersectExcept's body up to the
+    // download: the result stays on the device and ONE ii2_histogram_ids call counts it.  Like Intersect, no tombstone filter.
+    std::vector<uint64_t> Histogram(const std::vector<Term> &terms, const std::vector<Term> &except, const std::vector<uint64_t> &edges) const {
+        std::vector<uint64_t> out(hist_buckets(edges, "histogram"), 0);
+        Resolver where(*this);
+        Plan plan;
+        const uint64_t bound = smallest(plan.add(where, terms, except, Absent::EmptyQuery));
+        if (!bound) return out;
+        const Output set = filter_run(plan, bound, "histogram");
+        ck(ctx_, ii2_histogram_ids(ctx_, (const uint32_t *)set.mem.p, set.n, nullptr, (uint32_t)out.size(), edges.data(), out.data(), out.size()), "histogram");
+        return out;
+    }
+    // additive: terms over time - TermCounts over the value axis of Histogram: for every term that starts with `prefix`, per bucket
+    // the number of distinct docs under it that IntersectExcept(terms, except) returns; terms with an all-zero row are omitted.
+    // With `terms` empty the doc set is "every doc": each term's frequency over time (`except` must then be empty too).  TermCounts'
+    // plan with ONE ii2_histogram_ranges call over the prefix's runs; per term the per-segment rows are summed.  A term that hits
+    // in two or more segments may hold a doc twice, so those terms alone are counted again exactly: ONE ii2_query_batch_groups
+    // call per 2^20 of them - the filter's groups plus the term's own, the results kept on the device - and one ii2_histogram_ids
+    // call per such term on its slice of the output.  Like Read and Intersect, no tombstone filter.
+    std::map<Term, std::vector<uint64_t>> TermHistogram(const Term &prefix, const std::vector<Term> &terms, const std::vector<Term> &except,
+                                                        const std::vector<uint64_t> &edges) const {
+        std::map<Term, std::vector<uint64_t>> out;
+        if (terms.empty() && !except.empty()) throw Error("term histogram: an exclusion needs a required term");
+        const uint32_t nb = hist_buckets(edges, "term histogram");
+        Resolver where(*this, true);                             // (the re-count lays the filter's terms out again: the same lists)
+        Output set{DevMem(ctx_), 0, 0};
+        if (!terms.empty()) {
+            Plan filter;
+            const uint64_t bound = smallest(filter.add(where, terms, except, Absent::EmptyQuery));
+            if (!bound) return out;
+            set = filter_run(filter, bound, "term histogram");
+            if (!set.n) return out;
+        }
+        // the prefix's run in every segment of every shard, in calls of at most II2_HIST_MAX_CELLS counters
+        std::vector<std::shared_ptr<Segment>> held;
+        std::vector<const ii2_seg *> segs;
+        std::vector<uint64_t> first, end;
+        const uint64_t call_lists = std::max<uint64_t>(1, II2_HIST_MAX_CELLS / nb);
+        prefix_runs({prefix}, [&](const Term &, const std::shared_ptr<Segment> &sg, size_t j0, size_t j1) {
+            for (uint64_t j = j0; j < j1; j += call_lists) {         // (a run longer than a call's lists is cut)
+                held.push_back(sg);
+                segs.push_back(sg->seg->h);
+                first.push_back(j);
+                end.push_back(std::min<uint64_t>(j + call_lists, j1));
+            }
+        });
+        struct Hit {
+            std::vector<uint64_t> row;
+            Lists lists;                                         // (segment, list) of every segment with a hit
+        };
+        std::map<Term, Hit> hits;
+        std::vector<uint64_t> counts;
+        for (size_t r0 = 0; r0 < segs.size();) {
+            size_t r1 = r0;
+            uint64_t n_named = 0;
+            for (; r1 < segs.size() && (r1 == r0 || n_named + (end[r1] - first[r1]) <= call_lists); r1++) n_named += end[r1] - first[r1];
+            counts.assign(n_named * nb, 0);
+            ck(ctx_, ii2_histogram_ranges(ctx_, r1 - r0, segs.data() + r0, first.data() + r0, end.data() + r0, terms.empty() ? nullptr : (const uint32_t *)set.mem.p,
+                                          set.n, nullptr, nb, edges.data(), counts.data(), counts.size(), nullptr),
+               "term histogram");
+            size_t k = 0;
+            for (size_t r = r0; r < r1; r++)
+                for (uint64_t j = first[r]; j < end[r]; j++, k++) {
+                    const uint64_t *row = counts.data() + k * nb;
+                    if (std::all_of(row, row + nb, [](uint64_t c) { return c == 0; })) continue;
+                    Hit &h = hits[held[r]->terms[j]];
+                    h.row.resize(nb, 0);
+                    for (uint32_t b = 0; b < nb; b++) h.row[b] += row[b];
+                    h.lists.emplace_back(segs[r], j);
+                }
+            r0 = r1;
+        }
+        std::vector<const Term *> again;
+        for (auto &kv : hits) {
+            out[kv.first] = kv.second.row;
+            if (kv.second.lists.size() > 1) again.push_back(&kv.first);
+        }
+        // the exact re-count, as TermCounts lays it out - but the results are written: each term's slice is counted per bucket
+        constexpr size_t CALL_QUERIES = 1u << 20;
+        constexpr uint64_t CALL_IDS = 0xFFFFFFFFull;
+        size_t at = 0;
+        while (at < again.size()) {
+            Plan plan;
+            uint64_t bound = 0;
+            const size_t q0 = at;
+            for (; at < again.size() && at - q0 < CALL_QUERIES; at++) {
+                const Hit &h = hits[*again[at]];
+                uint64_t sum = 0;
+                for (uint64_t c : h.row) sum += c;
+                if (at > q0 && bound + sum >= CALL_IDS) break;
+                bound += sum;                                    // (the term's group holds at least its hits; the result is no longer)
+                plan.add(where, terms, except, Absent::EmptyQuery, nullptr, &h.lists);
+            }
+            const size_t nq = at - q0;
+            std::vector<uint64_t> off(nq + 1, 0);
+            const Output o = two_call(bound, 1, "term histogram", [&](uint32_t *d_ids, uint64_t cap, uint64_t *n) {
+                const int rc = ii2_query_batch_groups(ctx_, nq, plan.query_first.data(), plan.group_first.data(), plan.group_not.data(), plan.segs.data(),
+                                                      plan.first.data(), plan.end.data(), nullptr, d_ids, cap, off.data());
+                *n = off.back();
+                return rc;
+            });
+            for (size_t q = 0; q < nq; q++) {
+                std::vector<uint64_t> &row = out[*again[q0 + q]];
+                ck(ctx_, ii2_histogram_ids(ctx_, (const uint32_t *)o.mem.p + off[q], off[q + 1] - off[q], nullptr, nb, edges.data(), row.data(), row.size()),
+                   "term histogram");
+                if (std::all_of(row.begin(), row.end(), [](uint64_t c) { return c == 0; })) out.erase(*again[q0 + q]);
+            }
+        }
+        return out;
+    }
     // additive: MANY IntersectExcept queries, queries[q] = (terms, except), in one ii2_query_batch_groups call (through two_call),
     // one wait and one download.  Per term the groups are built exactly as IntersectExcept builds them.  A required term found in
     // no segment (or no term at all) makes that query one without groups - its result is empty, the call goes on.  The output's
@@ -1888,6 +2012,8 @@ struct ii2h_target {
     std::vector<uint32_t> ids;          // last Intersect / RemovedValues result
     std::vector<uint32_t> scores;       // last IntersectTop result: the score of each of ids
     std::vector<std::pair<Term, uint64_t>> counts;      // last TermCounts result
+    std::vector<uint64_t> hist;                         // last Histogram result
+    std::vector<std::pair<Term, std::vector<uint64_t>>> term_hist;      // last TermHistogram result
     std::vector<uint64_t> masks;        // last MatchedTerms / MatchedTermsBatch result (the pages' rows back to back)
 };
 
@@ -2247,6 +2373,30 @@ uint64_t ii2h_count_term_len(const ii2h_target *t, uint64_t i) { return t->count
 void ii2h_count_copy(const ii2h_target *t, uint64_t i, uint8_t *term, uint64_t *count) {
     std::memcpy(term, t->counts[i].first.data(), t->counts[i].first.size());
     *count = t->counts[i].second;
+}
+int ii2h_histogram(ii2h_target *t, const uint8_t *bytes, const uint64_t *off, uint64_t n, const uint8_t *x_bytes, const uint64_t *x_off, uint64_t n_x,
+                   const uint64_t *edges, uint64_t n_edges, uint64_t *n_buckets) {
+    H_TRY(t, {
+        t->hist = t->index->Histogram(unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x), std::vector<uint64_t>(edges, edges + n_edges));
+        *n_buckets = t->hist.size();
+    })
+}
+void ii2h_hist_copy(const ii2h_target *t, uint64_t *counts) {
+    if (!t->hist.empty()) std::memcpy(counts, t->hist.data(), t->hist.size() * sizeof(uint64_t));
+}
+int ii2h_term_histogram(ii2h_target *t, const uint8_t *prefix, uint64_t prefix_len, const uint8_t *bytes, const uint64_t *off, uint64_t n,
+                        const uint8_t *x_bytes, const uint64_t *x_off, uint64_t n_x, const uint64_t *edges, uint64_t n_edges, uint64_t *n_found) {
+    H_TRY(t, {
+        auto m = t->index->TermHistogram(Term((const char *)prefix, prefix_len), unpack_terms(bytes, off, n), unpack_terms(x_bytes, x_off, n_x),
+                                         std::vector<uint64_t>(edges, edges + n_edges));
+        t->term_hist.assign(m.begin(), m.end());
+        *n_found = t->term_hist.size();
+    })
+}
+uint64_t ii2h_term_hist_term_len(const ii2h_target *t, uint64_t i) { return t->term_hist[i].first.size(); }
+void ii2h_term_hist_copy(const ii2h_target *t, uint64_t i, uint8_t *term, uint64_t *counts) {
+    std::memcpy(term, t->term_hist[i].first.data(), t->term_hist[i].first.size());
+    std::memcpy(counts, t->term_hist[i].second.data(), t->term_hist[i].second.size() * sizeof(uint64_t));
 }
 int ii2h_removed_values(ii2h_target *t, uint64_t *n_ids) {
     H_TRY(t, { Shard *s = t->shard ? t->shard.get() : t->index->OnlyShard(); t->ids = s ? s->RemovedValues() : std::vector<uint32_t>(); *n_ids = t->ids.size(); })

@@ -1,0 +1,177 @@
+"""CPU: ii2_histogram_ranges / ii2_histogram_ids / Histogram / TermHistogram are wired through every layer - header, export map,
+binding, Makefile, host mirror and the Python faces - and the bucket arithmetic that their kernels run (ii2_hist_bucket,
+ii2_hist_block: host-only entry points over the same functions) agrees with numpy and with a plain statement of it."""
+import ctypes as C
+import fnmatch
+import os
+import re
+
+import numpy as np
+import pytest
+
+from inverted_index_2_amd import _lib
+from tests import hist_cases as hc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "inverted_index_2_amd", "csrc")
+NAMES = {"ii2_histogram_ranges": 13, "ii2_histogram_ids": 8, "ii2_hist_bucket": 4, "ii2_hist_block": 7}
+FIELDS = ["n_lists", "n_blocks", "n_decoded", "n_hits", "n_whole", "n_split", "n_wide", "n_windows", "n_buckets"]
+
+
+def _built():
+    from inverted_index_2_amd import host
+    if not (os.path.exists(_lib.LIB_PATH) and os.path.exists(host.HOST_LIB_PATH)):
+        import __graft_entry__
+        __graft_entry__.build()
+
+
+def _lib_loaded():
+    _built()
+    return _lib.load()
+
+
+def _u64(edges):
+    return np.ascontiguousarray(np.asarray(edges, np.uint64))
+
+
+def bucket_rc(edges, n_buckets, id):
+    e = _u64(edges) if edges is not None else None
+    b = C.c_int64(-7)
+    rc = _lib_loaded().ii2_hist_bucket(e.ctypes.data_as(_lib.u64p) if e is not None else None, n_buckets, id, C.byref(b))
+    return rc, b.value
+
+
+def block_rc(edges, first_doc, up):
+    e = _u64(edges)
+    kind, lo, hi = C.c_int(-7), C.c_uint32(0), C.c_uint32(0)
+    rc = _lib_loaded().ii2_hist_block(e.ctypes.data_as(_lib.u64p), len(edges) - 1, first_doc, up, C.byref(kind), C.byref(lo), C.byref(hi))
+    return rc, (kind.value, lo.value, hi.value)
+
+
+def test_declared_exported_and_bound():
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ii2.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(ii2_[a-z0-9_]+)\s*\(", text))
+    emap = re.sub(r"/\*.*?\*/", "", open(os.path.join(CSRC, "exports.map")).read(), flags=re.S)
+    exported = re.search(r"global:(.*?);\s*local:", emap, flags=re.S).group(1)
+    for name, arity in NAMES.items():
+        assert name in declared, name
+        assert any(fnmatch.fnmatchcase(name, pat.strip()) for pat in exported.split(";") if pat.strip()), name
+        res, args = _lib.PROTOTYPES[name]
+        assert res is C.c_int and len(args) == arity, name
+    for macro, value in (("II2_HIST_MAX_BUCKETS", "4096u"), ("II2_HIST_MAX_CELLS", "(1u << 26)"), ("II2_HIST_SKIP", "0"), ("II2_HIST_WHOLE", "1"),
+                         ("II2_HIST_SPLIT", "2"), ("II2_HIST_WIDE", "3")):
+        assert re.search(r"#define\s+%s\s+%s\s" % (macro, re.escape(value)), text), macro
+    assert (_lib.II2_HIST_MAX_BUCKETS, _lib.II2_HIST_MAX_CELLS) == (4096, 1 << 26)
+    assert (_lib.II2_HIST_SKIP, _lib.II2_HIST_WHOLE, _lib.II2_HIST_SPLIT, _lib.II2_HIST_WIDE) == (hc.SKIP, hc.WHOLE, hc.SPLIT, hc.WIDE)
+
+
+def test_hist_stats_layout():
+    assert [f[0] for f in _lib.HistStats._fields_] == FIELDS
+    assert C.sizeof(_lib.HistStats) == 64
+    header = open(os.path.join(ROOT, "include", "ii2.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\}\s*ii2_hist_stats;", header).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    assert re.findall(r"(\w+);", body) == FIELDS
+
+
+def test_sources():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    objs = next(line for line in mk.splitlines() if line.startswith("OBJS"))
+    assert "build/histogram.o" in objs.split()
+    hdrs = next(line for line in mk.splitlines() if line.startswith("HDRS"))
+    assert "hist_device.h" in hdrs.split() and "cr_walk.h" in hdrs.split()
+    src = open(os.path.join(CSRC, "histogram.hip")).read()
+    assert "lookback.h" not in src and "ii2_lookback_launch" not in src and "asm" not in src
+    for k in ("k_hs_count", "k_hs_ids_edges", "k_hs_ids_tomb", "cr_walk<", "decode_block_wave4", "seg_add(", "hist_block(", "hist_find("):
+        assert k in src, k
+    # the segmented sum lives beside the segmented OR, once; the walk is shared, not copied into the kernel file
+    n_defs = 0
+    for name in os.listdir(CSRC):
+        if name.endswith((".h", ".hip", ".cpp")):
+            n_defs += len(re.findall(r"uint32_t seg_add\(", open(os.path.join(CSRC, name)).read()))
+    assert n_defs == 1 and "uint32_t seg_add(" in open(os.path.join(CSRC, "um_device.h")).read()
+    assert "um_range_of(" not in src and "um_range_of(" in open(os.path.join(CSRC, "cr_walk.h")).read()
+    # the kernels and the host-only entry points run the same functions
+    host = open(os.path.join(CSRC, "setop.cpp")).read()
+    assert '#include "hist_device.h"' in host and '#include "hist_device.h"' in src
+    assert "__host__ __device__" in open(os.path.join(CSRC, "hist_device.h")).read()
+
+
+def test_options_are_documented():
+    header = open(os.path.join(ROOT, "include", "ii2.h")).read()
+    api = open(os.path.join(CSRC, "api.cpp")).read()
+    for opt in ("hist.per_wave", "hist.whole"):
+        assert opt in header and '"%s"' % opt in api, opt
+
+
+def test_null_context_is_einval():
+    lib = _lib_loaded()
+    e = _u64([0, 10])
+    assert lib.ii2_histogram_ranges(None, 0, None, None, None, None, 0, None, 1, e.ctypes.data_as(_lib.u64p), None, 0, None) == -1
+    assert lib.ii2_histogram_ids(None, None, 0, None, 1, e.ctypes.data_as(_lib.u64p), None, 0) == -1
+
+
+def test_host_library_exports():
+    from inverted_index_2_amd import host
+    _built()
+    C.CDLL(_lib.LIB_PATH)        # dependency first
+    lib = C.CDLL(host.HOST_LIB_PATH)
+    for name in ("ii2h_histogram", "ii2h_hist_copy", "ii2h_term_histogram", "ii2h_term_hist_term_len", "ii2h_term_hist_copy"):
+        assert hasattr(lib, name), name
+
+
+def test_python_faces():
+    import inverted_index_2_amd as pkg
+    from inverted_index_2_amd import Context, host
+    for name in ("histogram_ranges", "histogram_ids"):
+        assert callable(getattr(Context, name, None)), name
+    for name in ("histogram", "term_histogram"):
+        assert callable(getattr(host.InvertedIndex, name, None)), name
+    assert pkg.hist_bucket(hc.EDGE_SETS["uneven"], 9) == 1 and pkg.hist_block(hc.EDGE_SETS["uneven"], 1, 5) == (hc.WHOLE, 0, 0)
+
+
+@pytest.mark.parametrize("name", sorted(hc.EDGE_SETS))
+def test_hist_bucket_against_numpy(name):
+    edges = hc.EDGE_SETS[name]
+    ids = hc.probe_ids(edges)
+    want = hc.buckets(edges, ids)
+    got = []
+    for i in ids:
+        rc, b = bucket_rc(edges, len(edges) - 1, i)
+        assert rc == 0
+        got.append(b)
+    assert got == want.tolist()
+    assert want.max() == len(edges) - 2 and (want == -1).any() == (edges[0] > 0 or edges[-1] < hc.TOP)
+
+
+def test_hist_bucket_rejects_bad_edges():
+    for edges, want in hc.BAD_EDGES:
+        rc, b = bucket_rc(edges, len(edges) - 1, 5)
+        assert rc == want and b == -7, edges
+        if len(edges) > 1:
+            e = _u64(edges)
+            kind = C.c_int(-7)
+            lo, hi = C.c_uint32(9), C.c_uint32(9)
+            assert _lib_loaded().ii2_hist_block(e.ctypes.data_as(_lib.u64p), len(edges) - 1, 1, 2, C.byref(kind), C.byref(lo), C.byref(hi)) == want
+            assert (kind.value, lo.value, hi.value) == (-7, 9, 9)
+    assert bucket_rc(None, 3, 5) == (-1, -7)                             # NULL edges
+    assert bucket_rc([0, 10], 0, 5) == (-1, -7)                          # n_buckets == 0
+    rc, b = bucket_rc(list(range(4097)), 4096, 4095)                     # the limit itself is fine
+    assert (rc, b) == (0, 4095)
+
+
+def test_hist_block_against_the_plain_statement():
+    kinds = set()
+    for edges, first_doc, up in hc.BLOCKS:
+        rc, got = block_rc(edges, first_doc, up)
+        want = hc.block(edges, first_doc, up)
+        assert rc == 0 and got == want, (edges[:4], first_doc, up, got, want)
+        kinds.add(got[0])
+    assert kinds == {hc.SKIP, hc.WHOLE, hc.SPLIT, hc.WIDE}
+    # the cases the table must hold, by what they give
+    w1 = hc.EDGE_SETS["width 1"]
+    assert hc.block(w1, 1000, 1001) == (hc.SPLIT, 0, 1)
+    assert hc.block(w1, 1000, 1063) == (hc.SPLIT, 0, 63) and hc.block(w1, 1000, 1064) == (hc.WIDE, 0, 64)
+    assert hc.block(w1, 1099, 1100) == (hc.SPLIT, 99, 99)                # one bucket, but it leaves the axis
+    u = hc.EDGE_SETS["uneven"]
+    assert hc.block(u, 1, 5) == (hc.WHOLE, 0, 0) and hc.block(u, 1, 6) == (hc.SPLIT, 0, 1)
