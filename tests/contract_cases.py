@@ -6,7 +6,10 @@ Tombstones.  ii2_tomb_create sizes the bitmap by the largest removed id - n_word
 summary word).  Every kernel reads that bitmap with code of its own, and removed ids spread over the lists' whole range never show
 a reader that is wrong at the bitmap's END.  A layout here is a function (R, E) -> removed ids, R being the sorted union of the
 call's results without tombstones and E every id of every list; each puts the bitmap's last word, or its summary, where a reader
-can go wrong (LAYOUTS).  The reference of a (case, layout) pair is path_cases.reference(case, lists, removed).
+can go wrong (LAYOUTS).  The reference of a (case, layout) pair is path_cases.reference(case, lists, removed).  The readers the path
+table does not reach take the layouts with R and E of their own: the two-list AND instances, ii2_merge_segments, ii2_count_ranges,
+ii2_histogram_ranges (R: the ids of the set, or of the lists, that hit; reference: hist_cases.truth), ii2_histogram_ids (R = E = the
+set), ii2_atleast_ranges and the ranked calls.
 
 Capacity.  A result that does not fit `cap` is II2_ECAPACITY (include/ii2.h); capacities(n) are the values of `cap` a result of n
 ids runs at: exactly enough, one too few, none.

@@ -20,7 +20,8 @@ A kind is a pair: plan(shape) - pure numpy, no GPU - says what goes in (`inputs`
 (`store`: [(ids, slot or None)]; a whole segment's store is its slots); make(ctx, plan) calls the library.  reference(plan) is
 the derived arrays in plain numpy over those lists - it knows nothing of what the library answers.
 tests/test_segment_kinds_cpu.py checks the table itself, tests/test_gpu_segment_meta.py pins Segment.meta() to the reference for
-every (kind, shape), tests/test_gpu_segment_kinds.py runs the readers of the derived arrays on every kind.
+every (kind, shape), tests/test_gpu_segment_kinds.py and tests/test_gpu_segment_kinds_readers.py run the readers of the derived
+arrays on every kind.
 
 The shapes are the smallest at which each array can go wrong (under 60 k postings each, doc spans of 2^19 so that a union in
 windows of 2048 docs stays at 256 windows): see SHAPES.  One shape is large, `pair` (~ 1.5 M postings): the dense two-list AND
@@ -419,7 +420,8 @@ def queries(kind, shape_name=READER_SHAPE):
       pair                the longest list and the longest of the others that holds at most 513 postings: the 16384- and the
                           513-posting list wherever the kind keeps them whole
       miss / touch        (required, excluded) slots of 100 .. 300 postings: the excluded list starts behind the required list's
-                          last doc / AT its last doc - their spans share exactly one doc"""
+                          last doc / AT its last doc - their spans share exactly one doc
+    and what tests/test_gpu_segment_kinds_readers.py asks: see _later_readers."""
     p = plan(kind, shape_name)
     s = p.slots
     ne = [i for i, l in enumerate(s) if len(l)]
@@ -430,7 +432,7 @@ def queries(kind, shape_name=READER_SHAPE):
     q.dset = np.unique(np.concatenate([q.all[::3].astype(np.int64), near[near < (1 << 32)]])).astype(np.uint32)
     q.union = q.all
     q.union_tomb = np.setdiff1d(q.all, q.removed).astype(np.uint32)
-    q.counts = np.array([np.setdiff1d(np.intersect1d(l, q.dset), q.removed).size for l in s], np.uint64)
+    q.counts = np.array([np.setdiff1d(np.intersect1d(l, q.dset), q.removed).size if len(l) else 0 for l in s], np.uint64)
     q.lens = np.array([len(l) for l in s], np.uint64)
     cut = [0, len(ne) // 3, 2 * len(ne) // 3, len(ne)]
     q.groups = [(ne[cut[g]], ne[cut[g + 1] - 1] + 1) for g in range(3)]
@@ -450,7 +452,84 @@ def queries(kind, shape_name=READER_SHAPE):
     # the other segment of the merge: slot i holds every third doc of the next slot's list
     q.other = [s[(i + 1) % len(s)][::3] for i in range(len(s))]
     q.merged = [np.union1d(a, b).astype(np.uint32) if len(a) or len(b) else E for a, b in zip(s, q.other)]
+    _later_readers(q, s, ne, shape_name)
     return q
+
+
+# ---- ... and of the readers that came later (tests/test_gpu_segment_kinds_readers.py) -----------------------------------------
+TINY_POSTINGS, TINY_BLOCKS = 2048, 32            # csrc/internal.h: BATCH_TINY_* - the 256-thread form of the batch kernels
+SMALL_POSTINGS, SMALL_BLOCKS, SMALL_LISTS = 8192, 128, 64      # SMALL_SET_*, MAX_LISTS - one workgroup of 1024 threads
+ONE_LAUNCH_WORK = 32768                          # ANDNOT_SMALL_WORK: postings x lists of the one-launch threshold query
+TOP = 1 << 32
+
+
+def size_class(lists):
+    """Where lists that are named together run: "tiny" - the 256-thread form -, "small" - one workgroup of 1024 threads - or
+    "large" - the fallback; empty lists do not count."""
+    lists = [l for l in lists if len(l)]
+    post, blocks = sum(len(l) for l in lists), sum(nblk(l) for l in lists)
+    if len(lists) > SMALL_LISTS or post > SMALL_POSTINGS or blocks > SMALL_BLOCKS:
+        return "large"
+    return "tiny" if post <= TINY_POSTINGS and blocks <= TINY_BLOCKS else "small"
+
+
+def ranked(group_lists, k):
+    """(ids, scores, eligible docs): the k docs in the most groups, ties to the lower id"""
+    ids = union_of([l for g in group_lists for l in g])
+    score = np.zeros(ids.size, np.int64)
+    for g in group_lists:
+        score += np.isin(ids, union_of(g))
+    order = np.lexsort((ids, -score))[:k]
+    return ids[order], score[order].astype(np.uint32), int(ids.size)
+
+
+def _later_readers(q, s, ne, shape_name):
+    """What tests/test_gpu_segment_kinds_readers.py asks, by slot numbers, with the answers:
+      page                every 37th doc of the lists' union, docs that lie in no list (one below and one above all of them where
+                          the id space has room), the first and the last doc of every non-empty slot; shuffled, and the last
+                          doc of the longest slot twice more (70 .. 560 ids: the union's size decides)
+      explain_groups      (first slot, end slot) per group: every non-empty slot alone, then the three runs of `groups` - a doc of
+                          a list sets two bits at least, every list sits in two groups; explain_masks: the rows of `page`
+      top_edges           (shape `high`) an axis over the shape's span that ends with the edges 2^32 - 2, 2^32 - 1, 2^32
+    and, for the other shapes:
+      short / long        the non-empty slots of at most 513 postings / the longest slot
+      trio                the three longest slots of `short`, the shortest of them first; trio_and, trio_or
+      short_atleast2      the docs in at least two lists of `short`; short_top: ranked(one group per list of `short`, 10)
+      not_slot            the longest slot of at most 300 postings (the 300-posting list wherever the kind keeps it whole)
+      gq                  ((groups, excluded groups) by slots, the answer): (trio[0] OR trio[1]) AND trio[2], NOT not_slot - the
+                          excluded list's span meets the required groups' and, under today's plans, holds none of the answer's docs:
+                          it has to be read, and to remove nothing"""
+    from tests import explain_cases
+    by_len = sorted(ne, key=lambda i: (len(s[i]), i))
+    q.long = by_len[-1]
+    absent = q.all[1::7].astype(np.int64) + 1
+    absent = absent[(absent < TOP) & ~np.isin(absent, q.all)][:24]
+    around = [x for x in (int(q.all[0]) - 1, int(q.all[-1]) + 5) if 0 <= x < TOP]
+    ends = [x for i in ne for x in (s[i][0], s[i][-1])]
+    page = np.unique(np.concatenate([q.all[::37].astype(np.int64), absent, around, ends])).astype(np.uint32)
+    page = np.random.default_rng(37).permutation(page)
+    q.repeated = s[q.long][-1]
+    q.page = np.insert(page, [page.size // 3, page.size - 2], q.repeated).astype(np.uint32)
+    q.explain_groups = [(i, i + 1) for i in ne] + list(q.groups)
+    q.explain_masks = explain_cases.truth([s[a:b] for a, b in q.explain_groups], q.page)
+    if shape_name == "high":
+        lo = int(q.all[0])
+        q.top_edges = [lo + (TOP - 2 - lo) * b // 20 for b in range(20)] + [TOP - 2, TOP - 1, TOP]
+        return
+    q.short = [i for i in ne if len(s[i]) <= 513]
+    q.trio = [i for i in by_len if i in q.short][-3:]
+    t0, t1, t2 = (s[i] for i in q.trio)
+    q.trio_and = np.intersect1d(np.intersect1d(t0, t1), t2).astype(np.uint32)
+    q.trio_or = union_of([t0, t1, t2])
+    in_short = union_of([s[i] for i in q.short])
+    n_in = np.zeros(in_short.size, np.int64)
+    for i in q.short:
+        n_in += np.isin(in_short, s[i])
+    q.short_atleast2 = in_short[n_in >= 2]
+    q.short_top = ranked([[s[i]] for i in q.short], 10)
+    q.not_slot = max((i for i in ne if len(s[i]) <= 300), key=lambda i: (len(s[i]), i))
+    answer = np.setdiff1d(np.intersect1d(np.union1d(t0, t1), t2), s[q.not_slot]).astype(np.uint32)
+    q.gq = (([[q.trio[0], q.trio[1]], [q.trio[2]]], [[q.not_slot]]), answer)
 
 
 DENSE_MIN_BLOCKS, DENSE_MAX_DOCS_PER_BLOCK = 1024, 1100.0   # the dense chooser: blocks of the list with the fewest, its docs per block

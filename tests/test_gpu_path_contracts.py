@@ -5,7 +5,8 @@ the middle of the results with one bit or with 32 in its last word, summary bits
 a bitmap far past every list - and must return the numpy reference bit for bit, write nothing behind the result and take the path
 the table names.  The readers the path table does not reach run under the same layouts with their own references: the three
 instances of the one-launch two-list AND, ii2_merge_segments (direct and packed), ii2_count_ranges (against a set, and every doc),
-ii2_atleast_ranges (one launch, and counting) and the three ranked entry points.
+ii2_histogram_ranges (both forms, under an axis for each of its sinks), ii2_histogram_ids, ii2_atleast_ranges (one launch, and
+counting) and the three ranked entry points.
 
 Capacity: each case runs at exactly enough, one too few and none, into a buffer that is always allocated at the generous size and
 filled with a sentinel - a store past `cap` lands inside the allocation, where the test sees it.  The range and batch entry points
@@ -17,6 +18,7 @@ import pytest
 
 from tests import atleast_cases as ac
 from tests import contract_cases as cc
+from tests import hist_cases as hc
 from tests import merge_cases as mc
 from tests import path_cases as pc
 from tests import topk_batch_cases as bc
@@ -247,6 +249,75 @@ def test_count_ranges(ctx, form):
         seg.free()
         if dset is not None:
             dset.free()
+
+
+# ---- ii2_histogram_ranges, ii2_histogram_ids ---------------------------------------------------------------------------------------
+HIST_D = 60_000
+# axis -> (edges, the sink the blocks of these lists must reach under it: a whole block in one bucket, up to 64 buckets, more)
+HIST_AXES = {"one_bucket": ([0, hc.TOP], "n_whole"), "24_buckets": (hc.uniform(0, HIST_D, 24), "n_split"), "4096_buckets": (hc.uniform(0, HIST_D, 4096), "n_wide")}
+
+
+@pytest.mark.parametrize("axis", HIST_AXES)
+@pytest.mark.parametrize("form", ["set", "every_doc"])
+def test_histogram_ranges(ctx, form, axis):
+    """test_count_ranges' lists and set per bucket of an axis: k_hs_count<true> (every doc) tests each decoded id, k_hs_count<false>
+    relies on the facet count's marks"""
+    rng = np.random.default_rng(41)
+    lists = [sorted_unique(rng, n, HIST_D) for n in (255, 256, 1025)]
+    ids = sorted_unique(rng, 4097, HIST_D) if form == "set" else None
+    edges, sink = HIST_AXES[axis]
+    E = cc.every_id(lists)
+    R = E if ids is None else np.intersect1d(E, ids.astype(np.uint64))
+    assert R.size > 100
+    seg = ctx.encode_lists(lists)
+    dset = ctx.empty(ids.size).upload(ids) if ids is not None else None
+    n_set = None if dset is None else ids.size
+    try:
+        with Options(ctx, {"count.summary_skip": 0}, {"count.summary_skip": 1}):
+            got, st = ctx.histogram_ranges([(seg, 0, len(lists))], edges, dset, n_set)
+            print(form, axis, "whole", st.n_whole, "split", st.n_split, "wide", st.n_wide)
+            assert getattr(st, sink) > 0 and np.array_equal(got, hc.truth(lists, ids, edges)), (form, axis)
+            for layout in cc.LAYOUTS:
+                removed = cc.removed_for(layout, R, E)
+                tomb = ctx.tombstones(removed)
+                try:
+                    got, st = ctx.histogram_ranges([(seg, 0, len(lists))], edges, dset, n_set, tomb=tomb)
+                finally:
+                    tomb.free()
+                want = hc.truth(lists, ids, edges, removed)
+                print(form, axis, layout, "removed", removed.size, "hits", int(want.sum()))
+                assert np.array_equal(got, want), (form, axis, layout, np.argwhere(got != want)[:8].tolist())
+                assert st.n_hits == int(want.sum()), (form, axis, layout)
+                if layout == "all_hits":
+                    assert not want.any()
+    finally:
+        seg.free()
+        if dset is not None:
+            dset.free()
+
+
+def test_histogram_ids(ctx):
+    """k_hs_ids_tomb: runs of equal buckets that end inside and across waves where the bitmap ends"""
+    rng = np.random.default_rng(41)
+    ids = sorted_unique(rng, 4097, HIST_D)
+    R = ids.astype(np.uint64)
+    dset = ctx.empty(ids.size).upload(ids)
+    try:
+        for name, edges in (("edge_at_the_middle_hit", [0, cc.middle(R), HIST_D]), ("160_buckets", hc.uniform(0, HIST_D, 160))):
+            for layout in cc.LAYOUTS:
+                removed = cc.removed_for(layout, R, R)
+                tomb = ctx.tombstones(removed)
+                try:
+                    got = ctx.histogram_ids(dset, ids.size, edges, tomb=tomb)
+                finally:
+                    tomb.free()
+                want = hc.truth([ids], None, edges, removed)[0]
+                print(name, layout, "removed", removed.size, "left", int(want.sum()))
+                assert got.dtype == np.uint64 and np.array_equal(got, want), (name, layout, np.flatnonzero(got != want)[:8].tolist())
+                if layout == "all_hits":
+                    assert not want.any()
+    finally:
+        dset.free()
 
 
 # ---- the threshold and ranked queries -----------------------------------------------------------------------------------------------

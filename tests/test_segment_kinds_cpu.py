@@ -151,6 +151,45 @@ def test_the_readers_questions_are_not_trivial(kind):
     r, e = q.miss
     assert s[e][0] > s[r][-1]
     assert any(len(m) > len(a) > 0 for m, a in zip(q.merged, s))
+    # ---- what tests/test_gpu_segment_kinds_readers.py asks: the size classes of the one-workgroup forms, rows worth explaining
+    total = lambda slots: (sum(len(s[i]) for i in slots), sum(sk.nblk(s[i]) for i in slots))
+    assert len(q.trio) == 3 and len(set(q.trio)) == 3 and set(q.trio) <= set(q.short)
+    assert all(0 < len(s[i]) <= 513 for i in q.short) and len(s[q.long]) == max(len(l) for l in s)
+    assert 100 <= q.trio_and.size < min(len(s[i]) for i in q.trio) and q.trio_or.size > max(len(s[i]) for i in q.trio)
+    post, blocks = total(q.trio)
+    assert post <= 2048 and blocks <= 32 and sk.size_class([s[i] for i in q.trio]) == "tiny"                      # the 256-thread form
+    post, blocks = total(q.short)
+    assert 2048 < post <= 8192 and blocks <= 128 and len(q.short) <= 64                                         # the 1024-thread form
+    assert sk.size_class([s[i] for i in q.short]) == "small" and post * len(q.short) <= sk.ONE_LAUNCH_WORK
+    fallback = sk.size_class([s[i] for i in q.short + [q.long]]) == "large"
+    assert fallback == (len(s[q.long]) > 8192) == (kind != "merge_small")
+    assert (sk.size_class([s[q.trio[0]], s[q.long]]) == "large") == fallback and q.trio[0] != q.long
+    assert sk.size_class([s[i] for i in q.trio + [q.not_slot]]) == "tiny" and q.not_slot not in q.trio
+    bits = np.array([bin(int(w)).count("1") for w in q.explain_masks[:, 0]])
+    assert q.explain_masks.shape == (q.page.size, 1) and bits.max() >= 3 and np.any(bits == 0) and np.any(np.diff(q.page.astype(np.int64)) < 0)
+    rows = np.flatnonzero(q.page == q.repeated)
+    assert rows.size == 3 and bits[rows[0]] > 0 and not bits[rows[1:]].any()
+    assert np.unique(q.page).size == q.page.size - 2 and np.any(~np.isin(q.page, q.all))
+    assert len(q.explain_groups) == len([l for l in s if len(l)]) + 3 <= 64
+    assert 0 < q.short_atleast2.size < sk.union_of([s[i] for i in q.short]).size
+    ids, scores, eligible = q.short_top
+    assert ids.size == 10 and scores[0] >= 3 and scores[-1] >= 2 and np.all(np.diff(scores.astype(np.int64)) <= 0) and eligible > 2048
+    (groups, exclude), answer = q.gq
+    assert groups == [[q.trio[0], q.trio[1]], [q.trio[2]]] and exclude == [[q.not_slot]] and 0 < answer.size < len(s[q.trio[2]])
+    assert 250 <= len(s[q.not_slot]) <= 300
+
+
+@pytest.mark.parametrize("kind", list(sk.KINDS))
+def test_the_readers_questions_at_the_top_of_the_id_space(kind):
+    """... and of the shape `high`: a page with rows to explain and an axis whose last buckets are [2^32 - 2] and [2^32 - 1]."""
+    p, q = sk.plan(kind, "high"), sk.queries(kind, "high")
+    bits = np.array([bin(int(w)).count("1") for w in q.explain_masks[:, 0]])
+    assert bits.max() >= 3 and np.any(bits == 0) and 0xFFFFFFFF in q.page and q.page.size > 20
+    rows = np.flatnonzero(q.page == q.repeated)
+    assert rows.size == 3 and bits[rows[0]] > 0 and not bits[rows[1:]].any()
+    e = q.top_edges
+    assert e[-3:] == [sk.TOP - 2, sk.TOP - 1, sk.TOP] and all(a < b for a, b in zip(e, e[1:])) and e[0] == int(q.all[0])
+    assert any(len(l) and l[-1] == 0xFFFFFFFF for l in p.slots)
 
 
 def test_the_pair_shape_has_the_layout_the_dense_family_asks_for():
