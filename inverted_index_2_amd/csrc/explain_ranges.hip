@@ -1,22 +1,23 @@
 // explain_ranges.hip — which groups each doc of an id array lies in (ii2_explain_ranges: highlighting, "matched queries", the
 // tiers of a fuzzy hit).  The transpose of count_ranges.hip: the ids are marked into the per-context doc bitmap by k_cr_mark and
-// the groups' blocks are walked once, exactly as k_cr_count<false> walks them; a hit does not add 1 to its list's counter, it ORs
-// bit g of its group into the row of its doc.  The ids come in any order (a ranked page is score-descending), so a hit finds its
-// row through a table:
+// the groups' blocks are walked once, by the walk k_cr_count<false> runs (cr_walk.h, out_first[r] = the group of range r); a hit
+// does not add 1 to its list's counter, it ORs bit g of its group into the row of its doc.  The ids come in any order (a ranked
+// page is score-descending), so a hit finds its row through a table:
 //   1. k_ex_prepare: one thread per row inserts (id << 32 | row) into an open-addressing table of 64-bit entries, linear probing
 //      from ex_slot(id), wrapping at the end; an empty slot (all-ones) is claimed by a compare-and-swap, a slot that holds the same
 //      id takes the smaller entry by atomicMin: a repeated id keeps its FIRST row, whatever order the threads arrive in.  The table
 //      has at least twice as many slots as rows, so every probe ends.  The same kernel reduces the ids' minimum and maximum
 //      (k_cr_edges would read set[0] and set[n - 1] of an ascending set);
 //   2. k_cr_mark (count_ranges.hip), per window;
-//   3. k_ex_match, per window: one wave per run of query blocks, the count kernel's bound test and summary skip; every decoded id
-//      whose bit is set probes the table until it meets its id or an empty slot and issues one 64-bit atomicOr into its row.  The
-//      bits that were clear before (the call's n_hits) stay in a register: one wave sum and one atomicAdd per wave, spread over
-//      CR_DECODED_SLOTS words as the decoded blocks are;
+//   3. k_ex_match, per window: the walk of cr_walk.h, bounded and with the summary skip; every decoded id whose bit is set probes
+//      the table until it meets its id or an empty slot and issues one 64-bit atomicOr into its row.  The bits that were clear
+//      before (the call's n_hits) stay in a register: one wave sum and one atomicAdd per wave, spread over CR_DECODED_SLOTS words
+//      as the decoded blocks are;
 //   4. k_ir_clear (intersect_ranges.hip), per window.
 // No kernel waits for another workgroup.
 #include <hip/hip_runtime.h>
 
+#include "cr_walk.h"
 #include "dv1_device.h"
 #include "internal.h"
 #include "um_device.h"
@@ -79,64 +80,24 @@ __device__ __forceinline__ uint32_t ex_row_of(const ExplainParams &p, uint32_t i
 
 __global__ __launch_bounds__(256) void k_ex_match(ExplainParams q) {
     const CountParams &p = q.c;
-    const uint32_t l = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t g0 = ((uint64_t)blockIdx.x * 4u + wv) * p.per_wave;
-    if (g0 >= p.n_blocks) return;                                         // (wave-uniform; no workgroup barrier below)
-    const uint32_t g1 = (uint32_t)(g0 + p.per_wave < p.n_blocks ? g0 + p.per_wave : p.n_blocks);
-    uint32_t r = um_range_of(p.pre, p.n_ranges, (uint32_t)g0);
-    UmRange R = p.ranges[r];
-    uint32_t rbeg = p.pre[r], rend = p.pre[r + 1u], grp = p.out_first[r];
+    const CrWave w = cr_wave(p);
+    if (w.g0 == w.g1) return;                                             // (wave-uniform; no workgroup barrier below)
     uint32_t fresh = 0, n_dec = 0;                                        // mask bits this lane set first; blocks decoded
-    // the sink: the doc's row gets the group's bit (a repeated id's later rows are not in the table and stay 0)
-    auto sink = [&](uint32_t id, bool v) {
-        const uint32_t rel = id - p.win_lo;
-        const bool in = v && id >= p.win_lo && rel < p.win_docs;
-        const uint32_t w = in ? p.bitmap[rel >> 5] : 0u;
-        if (!((w >> (rel & 31u)) & 1u)) return;
-        const uint32_t row = ex_row_of(q, id);
-        if (row >= p.n_set) return;                                       // (not among the ids: cannot be, its bit was marked)
-        const unsigned long long bit = 1ull << (grp & 63u);
-        const unsigned long long old = atomicOr(&q.masks[(uint64_t)row * q.n_words + (grp >> 6)], bit);
-        fresh += (old & bit) ? 0u : 1u;
-    };
-    for (uint32_t g = (uint32_t)g0; g < g1; g++) {
-        while (g >= rend) {
-            r++;
-            R = p.ranges[r];
-            rbeg = rend;
-            rend = p.pre[r + 1u];
-            grp = p.out_first[r];
-        }
-        const uint32_t b = R.b0 + (g - rbeg);
-        const uint32_t j = R.blk_list[b];
-        if (j < R.l0 || j >= R.l1) continue;                              // no list of the range owns it
-        const ii2_skip e0 = R.skip[b], e1 = R.skip[b + 1u];
-        // a bound of the block's last doc: the next block's first doc, or the list's last doc
-        const uint32_t up = (b + 1u < R.b1 && R.blk_list[b + 1u] == j) ? e1.first_doc : R.last_doc[j];
-        if (e0.first_doc > p.doc_hi || up < p.doc_lo) continue;
-        if (p.summary_skip) {
-            const uint32_t ca = ((e0.first_doc > p.doc_lo ? e0.first_doc : p.doc_lo) - p.win_lo) >> 11;
-            const uint32_t cc = ((up < p.doc_hi ? up : p.doc_hi) - p.win_lo) >> 11;      // (<= (doc_hi - win_lo) >> 11 < 32 n_sum)
-            if (cc - ca < 64u) {                                          // one summary bit per lane
-                const uint32_t ch = ca + l;
-                const bool hit = ch <= cc && ((p.summary[ch >> 5] >> (ch & 31u)) & 1u) != 0u;
-                if (__ballot(hit) == 0ull) continue;
-            }
-        }
+    cr_walk<true, true>(p, w, [&](const UmRange &R, uint32_t grp, uint32_t, const ii2_skip &e0, const ii2_skip &e1, uint32_t) {
         n_dec++;
-        decode_block_wave4(GlobalBytes{R.payload}, e0.byte_off, e1.byte_off, e0.first_doc,
-                           [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
-                               const uint32_t i1 = ix + (mask & 1u), i2 = i1 + ((mask >> 1) & 1u), i3 = i2 + ((mask >> 2) & 1u);
-                               sink(id0, (mask & 1u) && ix < II2_DV1_BLOCK);
-                               sink(id1, (mask & 2u) && i1 < II2_DV1_BLOCK);
-                               sink(id2, (mask & 4u) && i2 < II2_DV1_BLOCK);
-                               sink(id3, (mask & 8u) && i3 < II2_DV1_BLOCK);
-                           });
-    }
+        // a hit: the doc's row gets the group's bit (a repeated id's later rows are not in the table and stay 0)
+        cr_block_ids(R, e0, e1, [&](uint32_t id, bool v) {
+            if (!cr_hit<false>(p, id, v)) return;
+            const uint32_t row = ex_row_of(q, id);
+            if (row >= p.n_set) return;                                   // (not among the ids: cannot be, its bit was marked)
+            const unsigned long long bit = 1ull << (grp & 63u);
+            const unsigned long long old = atomicOr(&q.masks[(uint64_t)row * q.n_words + (grp >> 6)], bit);
+            fresh += (old & bit) ? 0u : 1u;
+        });
+    });
     const uint32_t s = wave_sum(fresh);
-    if (l == 0 && s) atomicAdd(&q.hits[blockIdx.x % CR_DECODED_SLOTS], (unsigned long long)s);
-    if (l == 0 && n_dec) atomicAdd(&p.decoded[blockIdx.x % CR_DECODED_SLOTS], n_dec);
+    if (w.l == 0 && s) atomicAdd(&q.hits[blockIdx.x % CR_DECODED_SLOTS], (unsigned long long)s);
+    if (w.l == 0 && n_dec) atomicAdd(&p.decoded[blockIdx.x % CR_DECODED_SLOTS], n_dec);
 }
 
 hipError_t launch_ex_prepare(const ExplainParams &p, hipStream_t s) {
@@ -145,9 +106,8 @@ hipError_t launch_ex_prepare(const ExplainParams &p, hipStream_t s) {
 }
 
 hipError_t launch_ex_match(const ExplainParams &p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    const uint64_t waves = (p.c.n_blocks + (uint64_t)p.c.per_wave - 1u) / p.c.per_wave;
     if (ev0) (void)hipEventRecord(ev0, s);
-    hipLaunchKernelGGL(k_ex_match, dim3((unsigned)((waves + 3u) / 4u)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_ex_match, cr_grid(p.c), dim3(256), 0, s, p);
     if (ev1) (void)hipEventRecord(ev1, s);
     return hipGetLastError();
 }

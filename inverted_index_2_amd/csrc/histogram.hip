@@ -40,11 +40,9 @@ template <bool EVERY_DOC>
 __global__ __launch_bounds__(256) void k_hs_count(HistParams hp) {
     __shared__ uint32_t strips[4][HIST_STRIP];
     const CountParams &p = hp.c;
-    const uint32_t l = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t g0 = ((uint64_t)blockIdx.x * 4u + wv) * p.per_wave;
-    if (g0 >= p.n_blocks) return;                                         // (wave-uniform; no workgroup barrier below)
-    const uint32_t g1 = (uint32_t)(g0 + p.per_wave < p.n_blocks ? g0 + p.per_wave : p.n_blocks);
+    const CrWave w = cr_wave(p);
+    if (w.g0 == w.g1) return;                                             // (wave-uniform; no workgroup barrier below)
+    const uint32_t l = w.l, wv = w.wv;
     strips[wv][l] = 0u;                                                   // this wave's own strip: all-zero whenever it leaves a block
     strip_fence();
     const uint32_t nb = hp.n_buckets, first0 = hp.first0, last = hp.last;
@@ -57,14 +55,7 @@ __global__ __launch_bounds__(256) void k_hs_count(HistParams hp) {
         }
         acc = 0;
     };
-    auto test = [&](uint32_t id, bool v) -> uint32_t {
-        if (EVERY_DOC) return v && !tomb_has(p.tomb, p.tomb_nwords, id) ? 1u : 0u;
-        const uint32_t rel = id - p.win_lo;
-        const bool in = v && id >= p.win_lo && rel < p.win_docs;
-        const uint32_t w = in ? p.bitmap[rel >> 5] : 0u;
-        return (w >> (rel & 31u)) & 1u;
-    };
-    cr_walk<true, !EVERY_DOC>(p, (uint32_t)g0, g1, l, [&](const UmRange &R, uint32_t ofirst, uint32_t j, const ii2_skip &e0, const ii2_skip &e1, uint32_t up) {
+    cr_walk<true, !EVERY_DOC>(p, w, [&](const UmRange &R, uint32_t ofirst, uint32_t j, const ii2_skip &e0, const ii2_skip &e1, uint32_t up) {
         // the walk's values are wave-uniform but come out of vector loads: as scalars, the bucket search of the bounds below runs
         // on the scalar unit
         const uint32_t fd = (uint32_t)__builtin_amdgcn_readfirstlane((int)e0.first_doc), ub = (uint32_t)__builtin_amdgcn_readfirstlane((int)up);
@@ -80,15 +71,7 @@ __global__ __launch_bounds__(256) void k_hs_count(HistParams hp) {
                 cur = row + b_lo;
             }
             n_whole++;
-            decode_block_wave4(GlobalBytes{R.payload}, e0.byte_off, e1.byte_off, e0.first_doc,
-                               [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
-                                   const uint32_t i1 = ix + (mask & 1u), i2 = i1 + ((mask >> 1) & 1u), i3 = i2 + ((mask >> 2) & 1u);
-                                   const uint32_t h0 = test(id0, (mask & 1u) && ix < II2_DV1_BLOCK);
-                                   const uint32_t h1 = test(id1, (mask & 2u) && i1 < II2_DV1_BLOCK);
-                                   const uint32_t h2 = test(id2, (mask & 4u) && i2 < II2_DV1_BLOCK);
-                                   const uint32_t h3 = test(id3, (mask & 8u) && i3 < II2_DV1_BLOCK);
-                                   acc += (h0 + h1) + (h2 + h3);
-                               });
+            cr_block_ids(R, e0, e1, [&](uint32_t id, bool v) { acc += cr_hit<EVERY_DOC>(p, id, v); });
             return;
         }
         flush();
@@ -100,20 +83,12 @@ __global__ __launch_bounds__(256) void k_hs_count(HistParams hp) {
         // wave's strip in LDS (SPLIT) or to the global counter (WIDE): two instances, so that neither atomic goes through a
         // generic pointer
         auto searched = [&](auto to_strip) {
-            auto put = [&](uint32_t id, uint32_t hit) {
-                if (!hit || id < first0 || id > last) return;
+            cr_block_ids(R, e0, e1, [&](uint32_t id, bool v) {
+                if (!cr_hit<EVERY_DOC>(p, id, v) || id < first0 || id > last) return;
                 const uint32_t b = hist_find(hp.first, b_lo, b_hi, id);
                 if (decltype(to_strip)::value) atomicAdd(&strips[wv][b - b_lo], 1u);
                 else atomicAdd(&p.counts[row + b], 1u);
-            };
-            decode_block_wave4(GlobalBytes{R.payload}, e0.byte_off, e1.byte_off, e0.first_doc,
-                               [&](uint32_t ix, uint32_t id0, uint32_t id1, uint32_t id2, uint32_t id3, uint32_t mask) {
-                                   const uint32_t i1 = ix + (mask & 1u), i2 = i1 + ((mask >> 1) & 1u), i3 = i2 + ((mask >> 2) & 1u);
-                                   put(id0, test(id0, (mask & 1u) && ix < II2_DV1_BLOCK));
-                                   put(id1, test(id1, (mask & 2u) && i1 < II2_DV1_BLOCK));
-                                   put(id2, test(id2, (mask & 4u) && i2 < II2_DV1_BLOCK));
-                                   put(id3, test(id3, (mask & 8u) && i3 < II2_DV1_BLOCK));
-                               });
+            });
         };
         if (split) searched(std::true_type{});
         else searched(std::false_type{});
@@ -170,8 +145,7 @@ __global__ __launch_bounds__(256) void k_hs_ids_tomb(HistParams hp) {
 }
 
 hipError_t launch_hs_count(const HistParams &p, bool every_doc, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    const uint64_t waves = (p.c.n_blocks + (uint64_t)p.c.per_wave - 1u) / p.c.per_wave;
-    const dim3 grid((unsigned)((waves + 3u) / 4u));
+    const dim3 grid = cr_grid(p.c);
     if (ev0) (void)hipEventRecord(ev0, s);
     if (every_doc) hipLaunchKernelGGL(k_hs_count<true>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_hs_count<false>, grid, dim3(256), 0, s, p);

@@ -954,7 +954,7 @@ static int count_done(const CountIn &in, uint64_t *counts, ii2_count_stats *stat
     return II2_OK;
 }
 
-// The windows of a walk that tests ids against a marked doc set (count_many, explain_many): the docs [lo, hi] in windows of
+// The windows of a walk that tests ids against a marked doc set (marked_call): the docs [lo, hi] in windows of
 // um_window(ctx) docs, per window k_cr_mark of p.set, `walk` - the launch that reads the marks through p's window fields, set here -
 // and k_ir_clear.  *n_win grows by the windows run.
 template <class Walk>
@@ -987,32 +987,51 @@ static int marked_windows(ii2_ctx *ctx, const char *who, CountParams &p, uint32_
     return II2_OK;
 }
 
-// The block-wise count (count_ranges.hip) of the ranges' blocks against d_set - per window of the doc span that the set and the
-// lists share mark, count, clear - or, with d_set == NULL, against "every doc" minus the tombstones in one launch.  At most two
-// waits: the span fetch and the final read.
-static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts,
-                      ii2_count_stats *stats) {
+// What a reader of a marked doc set hands to marked_call.
+struct MarkedIn {
+    const char *who;                                            // the entry point in the messages
+    const std::vector<RangeIn> &rs;                             // the checked ranges that own blocks
+    const uint32_t *range_words;                                // [rs.size()] CountParams::out_first: each range's first counter / its group
+    uint64_t n_blocks;
+    const void *extra;                                          // the caller's own upload behind them (the histogram's axis) ...
+    size_t extra_bytes;
+    size_t back_bytes;                                          // ... its counters on the device: zeroed, read back at the end
+    size_t ws_bytes;                                            // ... and the workspace it takes in `setup`
+    const uint32_t *clip;                                       // {first, last} doc the docs that can hit are clipped to as well, or NULL
+    bool every_doc;                                             // no set: no span, no mark, no window - `walk` once, as the caller set p
+};
+
+// The host side of a walk of the ranges' blocks against a doc set (cr_walk.h), as ii2_count_ranges, ii2_histogram_ranges and
+// ii2_explain_ranges share it.  One staging copy takes up the range descriptors with their block prefix, the ranges' words, the
+// caller's extra and the start values of the four span words {lists' first doc, lists' last doc, set's smallest id, set's largest
+// id}; `setup(d_extra, d_back, d_span)` completes the caller's parameters around p and enqueues what else it needs.  Then the
+// span - the lists' from the segments' mirrors, else by k_um_bounds, the set's by `edges`, one copy, one wait - the windows of its
+// overlap (marked_windows around `walk(e0, e1)`, the profile events on the first one) and the caller's counters back behind a
+// second wait: *back, or NULL when the set and the lists (and the clip) share no doc - nothing was marked, every counter is 0.
+// The caller sets p.per_wave, the set and the tombstones; the walk's other fields are set here.
+template <class Setup, class Edges, class Walk>
+static int marked_call(ii2_ctx *ctx, const MarkedIn &in, CountParams &p, uint32_t *n_win, const uint8_t **back, Setup setup, Edges edges, Walk walk) {
     hipStream_t st = ctx->stream;
-    const std::vector<RangeIn> &rs = in.rs;
-    const size_t nr = rs.size();
-    const bool every_doc = !d_set;
+    const size_t nr = in.rs.size();
+    const std::string who(in.who);
+    *back = nullptr;
     if (int rc = um_scratch_clean(ctx)) return rc;
-    // staging: range descriptors + block prefix, the ranges' first counters, and room for the counters on their way back
-    const size_t n_words = (size_t)in.n_named + CR_DECODED_SLOTS;
-    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), up_bytes = um_bytes + align_up(nr * sizeof(uint32_t));
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + n_words * sizeof(uint32_t), false, "ii2_count_ranges: staging allocation failed"))
-        return rc;
+    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), extra_at = um_bytes + align_up(nr * sizeof(uint32_t));
+    const size_t span_at = extra_at + align_up(in.extra_bytes), up_bytes = span_at + 256;
+    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + in.back_bytes, false, (who + ": staging allocation failed").c_str())) return rc;
     uint8_t *h = (uint8_t *)ctx->h_um;
-    um_desc_fill(rs, 0, nr, h);
-    std::memcpy(h + um_bytes, in.out_first.data(), nr * sizeof(uint32_t));
-    uint32_t *h_words = (uint32_t *)(h + up_bytes);
+    um_desc_fill(in.rs, 0, nr, h);
+    std::memcpy(h + um_bytes, in.range_words, nr * sizeof(uint32_t));
+    if (in.extra_bytes) std::memcpy(h + extra_at, in.extra, in.extra_bytes);
+    const uint32_t span0[4] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};      // (k_um_bounds and k_ex_prepare reduce into them)
+    std::memcpy(h + span_at, span0, sizeof span0);
     // the lists' doc span: from the mirrored spans, else one reduction over the blocks (below, once the descriptors are up)
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    const bool mirrored = every_doc || mirrored_span(rs, &lo, &hi);
-    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_words * sizeof(uint32_t)) + 2 * 256 + 4096)) return rc;
+    const bool mirrored = in.every_doc || mirrored_span(in.rs, &lo, &hi);
+    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(in.back_bytes) + in.ws_bytes + 4096)) return rc;
     uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
-    uint32_t *d_words = ws_take<uint32_t>(ctx, n_words);
-    uint32_t *d_span = ws_take<uint32_t>(ctx, 4);                // {lists' first doc, lists' last doc, set's first id, set's last id}
+    uint8_t *d_back = ws_take<uint8_t>(ctx, in.back_bytes);
+    uint32_t *d_span = (uint32_t *)(d_stage + span_at);
     UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
     std::memset(&bp, 0, sizeof bp);
     bp.ranges = (const UmRange *)d_stage;
@@ -1020,36 +1039,24 @@ static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, ui
     bp.n_ranges = (uint32_t)nr;
     bp.n_blocks = (uint32_t)in.n_blocks;
     bp.bounds = d_span;
-    CountParams p;
-    std::memset(&p, 0, sizeof p);
     p.ranges = bp.ranges;
     p.pre = bp.pre;
     p.out_first = (const uint32_t *)(d_stage + um_bytes);
     p.n_ranges = bp.n_ranges;
     p.n_blocks = bp.n_blocks;
-    p.per_wave = um_per_wave(ctx, in.n_blocks);
     p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
-    p.set = d_set;
-    p.n_set = n_set;
-    set_tomb(p, tomb);
-    p.counts = d_words;
-    p.decoded = d_words + in.n_named;
     p.edges = d_span + 2;
     ctx->um_dirty = true;
     HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_words, 0, n_words * sizeof(uint32_t), st));
-    uint32_t n_win = 0;
+    HIP_TRY(ctx, hipMemsetAsync(d_back, 0, in.back_bytes, st));
+    if (int rc = setup(d_stage + extra_at, d_back, d_span)) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    if (every_doc) {
-        HIP_TRY(ctx, launch_cr_count(p, true, st, e0, e1));
+    if (in.every_doc) {
+        ii2_profile_pair(ctx, &e0, &e1);
+        HIP_TRY(ctx, walk(e0, e1));
     } else {
-        if (!mirrored) {
-            HIP_TRY(ctx, hipMemsetAsync(d_span, 0xFF, sizeof(uint32_t), st));
-            HIP_TRY(ctx, hipMemsetAsync(d_span + 1, 0, sizeof(uint32_t), st));
-            HIP_TRY(ctx, launch_union_many_bounds(bp, st));
-        }
-        HIP_TRY(ctx, launch_cr_edges(p, st));
+        if (!mirrored) HIP_TRY(ctx, launch_union_many_bounds(bp, st));
+        HIP_TRY(ctx, edges());
         uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
         HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1057,24 +1064,55 @@ static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, ui
             lo = hb[0];
             hi = hb[1];
         }
-        if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_count_ranges: inconsistent list bounds");
-        // the docs that can hit: the lists' span clipped to the set's
-        lo = std::max(lo, hb[2]);
-        hi = std::min(hi, hb[3]);
-        if (lo > hi) {                                          // no overlap: nothing was marked, the staging copy has been waited for
+        if (lo > hi) return fail(ctx, II2_EINVAL, (who + ": inconsistent list bounds").c_str());
+        // the docs that can hit: the lists' span clipped to the set's (and to the caller's clip)
+        lo = std::max(std::max(lo, hb[2]), in.clip ? in.clip[0] : 0u);
+        hi = std::min(std::min(hi, hb[3]), in.clip ? in.clip[1] : 0xFFFFFFFFu);
+        if (lo > hi) {                                          // no overlap: nothing was marked, what was enqueued has been waited for
             ctx->um_dirty = false;
-            return count_done(in, counts, stats);
+            return II2_OK;
         }
-        if (int rc = marked_windows(ctx, "ii2_count_ranges", p, lo, hi, &n_win, [&]() {
-                const hipError_t e = launch_cr_count(p, false, st, e0, e1);
+        ii2_profile_pair(ctx, &e0, &e1);
+        if (int rc = marked_windows(ctx, in.who, p, lo, hi, n_win, [&]() {
+                const hipError_t e = walk(e0, e1);
                 e0 = e1 = nullptr;
                 return e;
             }))
             return rc;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h + up_bytes, d_back, in.back_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     ctx->um_dirty = false;
+    *back = h + up_bytes;
+    return II2_OK;
+}
+
+// The block-wise count (count_ranges.hip) of the ranges' blocks against d_set - per window of the doc span that the set and the
+// lists share mark, count, clear - or, with d_set == NULL, against "every doc" minus the tombstones in one launch.  At most two
+// waits: the span fetch and the final read.
+static int count_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, uint64_t *counts,
+                      ii2_count_stats *stats) {
+    const size_t n_words = (size_t)in.n_named + CR_DECODED_SLOTS;
+    CountParams p;
+    std::memset(&p, 0, sizeof p);
+    p.per_wave = um_per_wave(ctx, in.n_blocks);
+    p.set = d_set;
+    p.n_set = n_set;
+    set_tomb(p, tomb);
+    const MarkedIn m{"ii2_count_ranges", in.rs, in.out_first.data(), in.n_blocks, nullptr, 0, n_words * sizeof(uint32_t), 0, nullptr, !d_set};
+    uint32_t n_win = 0;
+    const uint8_t *back = nullptr;
+    if (int rc = marked_call(ctx, m, p, &n_win, &back,
+                             [&](uint8_t *, uint8_t *d_back, uint32_t *) {
+                                 p.counts = (uint32_t *)d_back;
+                                 p.decoded = p.counts + in.n_named;
+                                 return II2_OK;
+                             },
+                             [&]() { return launch_cr_edges(p, ctx->stream); },
+                             [&](hipEvent_t e0, hipEvent_t e1) { return launch_cr_count(p, !d_set, ctx->stream, e0, e1); }))
+        return rc;
+    if (!back) return count_done(in, counts, stats);
+    const uint32_t *h_words = (const uint32_t *)back;
     uint64_t hits = 0, decoded = 0;
     for (uint64_t k = 0; k < in.n_named; k++) {
         counts[k] = h_words[k];
@@ -1195,106 +1233,43 @@ static int hist_done(const CountIn &in, uint32_t n_buckets, uint64_t *counts, ii
 // read; the "every doc" form waits once.
 static int hist_many(ii2_ctx *ctx, const CountIn &in, const uint32_t *d_set, uint64_t n_set, const ii2_tomb *tomb, const HistAxis &ax, uint64_t *counts,
                      ii2_hist_stats *stats) {
-    hipStream_t st = ctx->stream;
-    const std::vector<RangeIn> &rs = in.rs;
-    const size_t nr = rs.size();
     const uint32_t nb = (uint32_t)ax.first.size();
-    const bool every_doc = !d_set;
-    if (int rc = um_scratch_clean(ctx)) return rc;
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    const bool mirrored = mirrored_span(rs, &lo, &hi);
-    if (every_doc) {
-        // no set to fetch a span of: the lists' mirrored span where there is one, clipped to the axis, before anything goes up
-        if (!mirrored) lo = 0, hi = 0xFFFFFFFFu;
-        lo = std::max(lo, ax.first[0]);
-        hi = std::min(hi, ax.last);
-        if (lo > hi) return hist_done(in, nb, counts, stats);
-    }
-    // staging: range descriptors + block prefix, the ranges' first counters, the axis, and room for the counters on their way back
-    const size_t n_cells = (size_t)in.n_named * nb, n_words = n_cells + 3 * CR_DECODED_SLOTS;
-    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), ax_off = um_bytes + align_up(nr * sizeof(uint32_t));
-    const size_t up_bytes = ax_off + align_up(nb * sizeof(uint32_t));
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + n_words * sizeof(uint32_t), false, "ii2_histogram_ranges: staging allocation failed"))
-        return rc;
-    uint8_t *h = (uint8_t *)ctx->h_um;
-    um_desc_fill(rs, 0, nr, h);
-    std::memcpy(h + um_bytes, in.out_first.data(), nr * sizeof(uint32_t));
-    std::memcpy(h + ax_off, ax.first.data(), nb * sizeof(uint32_t));
-    uint32_t *h_words = (uint32_t *)(h + up_bytes);
-    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_words * sizeof(uint32_t)) + 2 * 256 + 4096)) return rc;
-    uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
-    uint32_t *d_words = ws_take<uint32_t>(ctx, n_words);
-    uint32_t *d_span = ws_take<uint32_t>(ctx, 4);                // {lists' first doc, lists' last doc, set's first id, set's last id}
-    UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
-    std::memset(&bp, 0, sizeof bp);
-    bp.ranges = (const UmRange *)d_stage;
-    bp.pre = (const uint32_t *)(d_stage + desc_bytes);
-    bp.n_ranges = (uint32_t)nr;
-    bp.n_blocks = (uint32_t)in.n_blocks;
-    bp.bounds = d_span;
+    const uint32_t axis[2] = {ax.first[0], ax.last};
     HistParams hp;
     std::memset(&hp, 0, sizeof hp);
     CountParams &p = hp.c;
-    p.ranges = bp.ranges;
-    p.pre = bp.pre;
-    p.out_first = (const uint32_t *)(d_stage + um_bytes);
-    p.n_ranges = bp.n_ranges;
-    p.n_blocks = bp.n_blocks;
+    if (!d_set) {
+        // no set to fetch a span of: the lists' mirrored span where there is one, clipped to the axis, before anything goes up
+        uint32_t lo = 0xFFFFFFFFu, hi = 0;
+        if (!mirrored_span(in.rs, &lo, &hi)) lo = 0, hi = 0xFFFFFFFFu;
+        p.doc_lo = std::max(lo, axis[0]);
+        p.doc_hi = std::min(hi, axis[1]);
+        if (p.doc_lo > p.doc_hi) return hist_done(in, nb, counts, stats);
+    }
+    const size_t n_cells = (size_t)in.n_named * nb, n_words = n_cells + 3 * CR_DECODED_SLOTS;
     p.per_wave = ctx->opt_hist_per_wave > 0 ? (uint32_t)std::min<int64_t>(ctx->opt_hist_per_wave, 1 << 20) : um_per_wave(ctx, in.n_blocks);
-    p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
     p.set = d_set;
     p.n_set = n_set;
     set_tomb(p, tomb);
-    p.counts = d_words;
-    p.decoded = d_words + n_cells;
-    p.edges = d_span + 2;
-    p.doc_lo = lo;                                              // (the "every doc" form; marked_windows sets them per window)
-    p.doc_hi = hi;
-    hp.first = (const uint32_t *)(d_stage + ax_off);
     hp.n_buckets = nb;
-    hp.first0 = ax.first[0];
-    hp.last = ax.last;
+    hp.first0 = axis[0];
+    hp.last = axis[1];
     hp.whole = ctx->opt_hist_whole ? 1u : 0u;
-    ctx->um_dirty = true;
-    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_words, 0, n_words * sizeof(uint32_t), st));
+    const MarkedIn m{"ii2_histogram_ranges", in.rs, in.out_first.data(), in.n_blocks, ax.first.data(), nb * sizeof(uint32_t), n_words * sizeof(uint32_t), 0, axis, !d_set};
     uint32_t n_win = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    if (every_doc) {
-        HIP_TRY(ctx, launch_hs_count(hp, true, st, e0, e1));
-    } else {
-        if (!mirrored) {
-            HIP_TRY(ctx, hipMemsetAsync(d_span, 0xFF, sizeof(uint32_t), st));
-            HIP_TRY(ctx, hipMemsetAsync(d_span + 1, 0, sizeof(uint32_t), st));
-            HIP_TRY(ctx, launch_union_many_bounds(bp, st));
-        }
-        HIP_TRY(ctx, launch_cr_edges(p, st));
-        uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
-        HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (!mirrored) {
-            lo = hb[0];
-            hi = hb[1];
-        }
-        if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_histogram_ranges: inconsistent list bounds");
-        // the docs that can hit: the lists' span clipped to the set's and to the axis
-        lo = std::max(std::max(lo, hb[2]), ax.first[0]);
-        hi = std::min(std::min(hi, hb[3]), ax.last);
-        if (lo > hi) {                                          // no overlap: nothing was marked, the staging copy has been waited for
-            ctx->um_dirty = false;
-            return hist_done(in, nb, counts, stats);
-        }
-        if (int rc = marked_windows(ctx, "ii2_histogram_ranges", p, lo, hi, &n_win, [&]() {
-                const hipError_t e = launch_hs_count(hp, false, st, e0, e1);
-                e0 = e1 = nullptr;
-                return e;
-            }))
-            return rc;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(h_words, d_words, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->um_dirty = false;
+    const uint8_t *back = nullptr;
+    if (int rc = marked_call(ctx, m, p, &n_win, &back,
+                             [&](uint8_t *d_axis, uint8_t *d_back, uint32_t *) {
+                                 hp.first = (const uint32_t *)d_axis;
+                                 p.counts = (uint32_t *)d_back;
+                                 p.decoded = p.counts + n_cells;
+                                 return II2_OK;
+                             },
+                             [&]() { return launch_cr_edges(p, ctx->stream); },
+                             [&](hipEvent_t e0, hipEvent_t e1) { return launch_hs_count(hp, !d_set, ctx->stream, e0, e1); }))
+        return rc;
+    if (!back) return hist_done(in, nb, counts, stats);
+    const uint32_t *h_words = (const uint32_t *)back;
     uint64_t hits = 0, kinds[3] = {0, 0, 0};
     for (size_t k = 0; k < n_cells; k++) {
         counts[k] = h_words[k];
@@ -1713,92 +1688,38 @@ extern "C" int ii2_intersect_ranges(ii2_ctx *ctx, uint64_t n_groups, const uint6
 static int explain_many(ii2_ctx *ctx, const std::vector<RangeIn> &rs, const std::vector<uint32_t> &group_of, const uint32_t *d_ids, uint64_t n_ids,
                         uint64_t *d_masks, ii2_explain_stats *res) {
     hipStream_t st = ctx->stream;
-    const size_t nr = rs.size();
-    if (int rc = um_scratch_clean(ctx)) return rc;
     uint32_t log2_slots = 6;
     while ((1ull << log2_slots) < 2 * n_ids) log2_slots++;
     const size_t n_slots = (size_t)1 << log2_slots;
-    // staging: range descriptors + block prefix, the ranges' groups, the spans' start values, and room for the two sets of spread
-    // counters on their way back
-    const size_t desc_bytes = align_up(nr * sizeof(UmRange)), um_bytes = um_desc_bytes(nr), span_at = um_bytes + align_up(nr * sizeof(uint32_t));
-    const size_t up_bytes = span_at + 256;
-    const size_t cnt_bytes = CR_DECODED_SLOTS * (sizeof(uint64_t) + sizeof(uint32_t));
-    if (int rc = grow_pinned(ctx, &ctx->h_um, &ctx->h_um_cap, up_bytes + cnt_bytes, false, "ii2_explain_ranges: staging allocation failed")) return rc;
-    uint8_t *h = (uint8_t *)ctx->h_um;
-    um_desc_fill(rs, 0, nr, h);
-    std::memcpy(h + um_bytes, group_of.data(), nr * sizeof(uint32_t));
-    const uint32_t span0[4] = {0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};      // {lists' first doc, lists' last doc, smallest id, largest id} before any
-    std::memcpy(h + span_at, span0, sizeof span0);
-    uint32_t lo = 0xFFFFFFFFu, hi = 0;
-    const bool mirrored = mirrored_span(rs, &lo, &hi);
-    if (int rc = ii2_ws_reserve(ctx, up_bytes + align_up(n_slots * sizeof(uint64_t)) + align_up(cnt_bytes) + 4096)) return rc;
-    uint8_t *d_stage = ws_take<uint8_t>(ctx, up_bytes);
-    unsigned long long *d_table = ws_take<unsigned long long>(ctx, n_slots);
-    uint8_t *d_cnt = ws_take<uint8_t>(ctx, cnt_bytes);          // hits [CR_DECODED_SLOTS] u64, then decoded [CR_DECODED_SLOTS] u32
-    uint32_t *d_span = (uint32_t *)(d_stage + span_at);
-    UnionManyParams bp;                                         // (k_um_bounds takes the union's parameters)
-    std::memset(&bp, 0, sizeof bp);
-    bp.ranges = (const UmRange *)d_stage;
-    bp.pre = (const uint32_t *)(d_stage + desc_bytes);
-    bp.n_ranges = (uint32_t)nr;
-    bp.n_blocks = (uint32_t)res->n_blocks;
-    bp.bounds = d_span;
+    const size_t cnt_bytes = CR_DECODED_SLOTS * (sizeof(uint64_t) + sizeof(uint32_t));      // hits [CR_DECODED_SLOTS] u64, then decoded [CR_DECODED_SLOTS] u32
     ExplainParams q;
     std::memset(&q, 0, sizeof q);
     CountParams &p = q.c;
-    p.ranges = bp.ranges;
-    p.pre = bp.pre;
-    p.out_first = (const uint32_t *)(d_stage + um_bytes);
-    p.n_ranges = bp.n_ranges;
-    p.n_blocks = bp.n_blocks;
     p.per_wave = um_per_wave(ctx, res->n_blocks);
-    p.summary_skip = ctx->opt_count_summary_skip ? 1u : 0u;
     p.set = d_ids;
     p.n_set = n_ids;
-    p.decoded = (uint32_t *)(d_cnt + CR_DECODED_SLOTS * sizeof(uint64_t));
-    q.table = d_table;
     q.masks = (unsigned long long *)d_masks;
-    q.hits = (unsigned long long *)d_cnt;
-    q.span = d_span + 2;
     q.log2_slots = log2_slots;
     q.n_words = res->n_words;
     res->log2_slots = log2_slots;
-    ctx->um_dirty = true;
-    HIP_TRY(ctx, hipMemcpyAsync(d_stage, h, up_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_masks, 0, n_ids * res->n_words * sizeof(uint64_t), st));
-    HIP_TRY(ctx, hipMemsetAsync(d_table, 0xFF, n_slots * sizeof(uint64_t), st));
-    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, cnt_bytes, st));
-    if (!mirrored) HIP_TRY(ctx, launch_union_many_bounds(bp, st));
-    HIP_TRY(ctx, launch_ex_prepare(q, st));
-    uint32_t *hb = (uint32_t *)(ctx->h_mail + II2_MAIL_COUNT + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(hb, d_span, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (!mirrored) {
-        lo = hb[0];
-        hi = hb[1];
-    }
-    if (lo > hi) return fail(ctx, II2_EINVAL, "ii2_explain_ranges: inconsistent list bounds");
-    // the docs that can hit: the lists' span clipped to the ids'
-    lo = std::max(lo, hb[2]);
-    hi = std::min(hi, hb[3]);
-    if (lo > hi) {                                              // no overlap: nothing was marked, the masks are zero and waited for
-        ctx->um_dirty = false;
-        return II2_OK;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ii2_profile_pair(ctx, &e0, &e1);
-    if (int rc = marked_windows(ctx, "ii2_explain_ranges", p, lo, hi, &res->n_windows, [&]() {
-            const hipError_t e = launch_ex_match(q, st, e0, e1);
-            e0 = e1 = nullptr;
-            return e;
-        }))
+    const MarkedIn m{"ii2_explain_ranges", rs, group_of.data(), res->n_blocks, nullptr, 0, cnt_bytes, align_up(n_slots * sizeof(uint64_t)), nullptr, false};
+    const uint8_t *back = nullptr;
+    if (int rc = marked_call(ctx, m, p, &res->n_windows, &back,
+                             [&](uint8_t *, uint8_t *d_cnt, uint32_t *d_span) {
+                                 q.table = ws_take<unsigned long long>(ctx, n_slots);
+                                 q.hits = (unsigned long long *)d_cnt;
+                                 p.decoded = (uint32_t *)(d_cnt + CR_DECODED_SLOTS * sizeof(uint64_t));
+                                 q.span = d_span + 2;
+                                 HIP_TRY(ctx, hipMemsetAsync(d_masks, 0, n_ids * res->n_words * sizeof(uint64_t), st));
+                                 HIP_TRY(ctx, hipMemsetAsync(q.table, 0xFF, n_slots * sizeof(uint64_t), st));
+                                 return II2_OK;
+                             },
+                             [&]() { return launch_ex_prepare(q, st); },
+                             [&](hipEvent_t e0, hipEvent_t e1) { return launch_ex_match(q, st, e0, e1); }))
         return rc;
-    uint8_t *h_cnt = h + up_bytes;
-    HIP_TRY(ctx, hipMemcpyAsync(h_cnt, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->um_dirty = false;
-    const uint64_t *h_hits = (const uint64_t *)h_cnt;
-    const uint32_t *h_dec = (const uint32_t *)(h_cnt + CR_DECODED_SLOTS * sizeof(uint64_t));
+    if (!back) return II2_OK;                                    // no overlap: the masks are zero and waited for
+    const uint64_t *h_hits = (const uint64_t *)back;
+    const uint32_t *h_dec = (const uint32_t *)(back + CR_DECODED_SLOTS * sizeof(uint64_t));
     for (uint32_t k = 0; k < CR_DECODED_SLOTS; k++) {
         res->n_hits += h_hits[k];
         res->n_decoded += h_dec[k];

@@ -153,6 +153,34 @@ def blocks_of(l):
     return (len(l) + 255) // 256
 
 
+def one_block_lists_past_a_wave(rng, universe, reach=6000):
+    """Lists for the walk of a wave over SEVERAL query blocks (cr_walk.h), which a call reaches only beyond 32 waves per CU of one
+    block each: two segments of one- to three-posting lists - every list owns one block, its ids within `reach` docs of each
+    other except in every 97th list, which spreads over the universe - named as six ranges of odd block counts, the segments in
+    turn.  Returns ([lists of A, lists of B], [(segment, first list, end list), ...], blocks a wave walks); asserts that the
+    ranges' blocks are more than two per wave and that range ends fall inside a wave's run."""
+    import torch
+    waves = 32 * torch.cuda.get_device_properties(0).multi_processor_count
+    sizes = (waves + 21, waves + 19)
+    segments = []
+    for n in sizes:
+        first = rng.integers(0, universe - 3 * reach, n)
+        gaps = rng.integers(1, reach, (n, 2))
+        wide = np.arange(n) % 97 == 0
+        first[wide] = rng.integers(0, universe // 8, int(wide.sum()))
+        gaps[wide] = rng.integers(universe // 4, universe // 3, (int(wide.sum()), 2))
+        ids = np.cumsum(np.column_stack([first, gaps]), axis=1)
+        segments.append([ids[j, :k].astype(np.uint32) for j, k in enumerate(rng.integers(1, 4, n))])
+    ranges = [(0, 0, 301), (1, 0, 77), (0, 301, 1002), (1, 77, 578), (0, 1002, sizes[0]), (1, 578, sizes[1])]
+    n_blocks = sum(b - a for _, a, b in ranges)
+    per_wave = -(-n_blocks // waves)
+    assert n_blocks > 2 * waves and per_wave >= 3 and all((b - a) % 2 == 1 for _, a, b in ranges)
+    ends = np.cumsum([b - a for _, a, b in ranges])[:-1]
+    assert np.count_nonzero(ends % per_wave) >= 3, (ends, per_wave)
+    assert sum(l.size for lists in segments for l in lists) < 50_000
+    return segments, ranges, per_wave
+
+
 def sorted_unique(rng, n, universe):
     if n == 0:
         return np.empty(0, np.uint32)

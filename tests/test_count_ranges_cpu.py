@@ -53,8 +53,14 @@ def test_count_ranges_object_is_in_the_makefile():
 def test_count_kernels_have_no_inter_workgroup_waits():
     src = open(os.path.join(CSRC, "count_ranges.hip")).read()
     assert "lookback.h" not in src and "ii2_lookback_launch" not in src
-    for k in ("k_cr_mark", "k_cr_count", "decode_block_wave4", "seg_or"):
+    for k in ("k_cr_mark", "k_cr_count", "cr_walk<", "seg_or"):
         assert k in src, k
+    # the walk and the block decode are shared with the other readers of a marked set, not copied into the kernel files
+    walk = open(os.path.join(CSRC, "cr_walk.h")).read()
+    assert "decode_block_wave4" in walk and "um_range_of(" in walk and "lookback.h" not in walk
+    for name in ("count_ranges.hip", "explain_ranges.hip", "histogram.hip"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert "um_range_of(" not in text and "cr_walk<" in text, name
     # the segmented OR is shared with the block-wise union, not copied
     assert "uint32_t seg_or(" not in src
     assert "uint32_t seg_or(" not in open(os.path.join(CSRC, "union_many.hip")).read()

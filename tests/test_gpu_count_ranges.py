@@ -6,9 +6,10 @@ import threading
 
 import numpy as np
 import pytest
+import torch
 
 from inverted_index_2_amd import Context, _lib
-from tests.gpu_util import ctx, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, one_block_lists_past_a_wave, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -252,6 +253,47 @@ def test_every_doc(ctx):
     got, st = count(ctx, ranges, None, ctx.tombstones(removed))
     assert np.array_equal(got, truth(named, None, removed)) and got[6] == 0
     assert st.n_windows == 0 and st.n_decoded == st.n_blocks
+
+
+def test_a_wave_walks_several_blocks_across_range_ends(ctx):
+    """More blocks than 2 x 32 waves per CU: every wave of k_cr_count walks three blocks, and range ends fall inside its run."""
+    rng = np.random.default_rng(52)
+    D = 1 << 22
+    segments, ranges, per_wave = one_block_lists_past_a_wave(rng, D)
+    segs = [ctx.encode_lists(lists) for lists in segments]
+    named = [segments[s][j] for s, a, b in ranges for j in range(a, b)]
+    flat, owner = np.concatenate(named), np.repeat(np.arange(len(named)), [l.size for l in named])
+    lo, hi = block_bounds(named)                                         # (one block per list)
+    assert lo.size == len(named) > 2 * 32 * torch.cuda.get_device_properties(0).multi_processor_count and per_wave >= 3
+
+    def want(ids, removed=()):
+        hit = (np.ones(flat.size, bool) if ids is None else np.isin(flat, ids)) & ~np.isin(flat, np.asarray(removed, np.uint32))
+        return np.bincount(owner[hit], minlength=len(named)).astype(np.uint64)
+
+    # the set: 300 ids of the middle half of the universe, a third of them out of the lists
+    mid = flat[(flat >= D // 4) & (flat < 3 * D // 4)]
+    ids = np.union1d(rng.choice(mid, 100, replace=False), sorted_unique(rng, 200, D // 2) + D // 4).astype(np.uint32)
+    doc_lo, doc_hi = max(int(lo.min()), int(ids[0])), min(int(hi.max()), int(ids[-1]))
+    meet = (lo <= doc_hi) & (hi >= doc_lo)                               # the bound test
+    base = doc_lo & ~2047
+    ca, cc = (np.maximum(lo, doc_lo) - base) >> 11, (np.minimum(hi, doc_hi) - base) >> 11
+    inside = ids[(ids >= doc_lo) & (ids <= doc_hi)].astype(np.int64)
+    marked = np.unique((inside - base) >> 11)                            # the summary: the 2048-doc chunks that hold a marked id
+    near = np.searchsorted(marked, ca) < np.searchsorted(marked, cc, side="right")
+    read = {0: int(meet.sum()), 1: int((meet & ((cc - ca >= 64) | near)).sum())}
+    assert 0 < read[1] < read[0] < lo.size and int((meet & (cc - ca >= 64)).sum()) > 50
+    R = [(segs[s], a, b) for s, a, b in ranges]
+    for skip in (0, 1):
+        with Option(ctx, "count.summary_skip", skip, 1):
+            got, st = count(ctx, R, ids)
+            assert np.array_equal(got, want(ids)), skip
+            assert (st.n_lists, st.n_blocks, st.n_windows, st.n_hits) == (len(named), lo.size, 1, int(got.sum()))
+            assert st.n_decoded == read[skip], (skip, st.n_decoded, read)
+    assert got.sum() >= 100
+    removed = np.union1d(rng.choice(flat, 5000, replace=False), ids[::3]).astype(np.uint32)
+    got, st = count(ctx, R, None, ctx.tombstones(removed))               # every doc: no bound test, every block is read
+    assert np.array_equal(got, want(None, removed)) and 0 < got.sum() < flat.size
+    assert st.n_windows == 0 and st.n_decoded == st.n_blocks == lo.size
 
 
 def test_scratch_stays_clean(ctx):

@@ -5,10 +5,11 @@ import ctypes as C
 
 import numpy as np
 import pytest
+import torch
 
 from inverted_index_2_amd import Context, _lib, explain_slot
 from tests import explain_cases as ec
-from tests.gpu_util import ctx, path_delta, sorted_unique  # noqa: F401
+from tests.gpu_util import ctx, one_block_lists_past_a_wave, path_delta, sorted_unique  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +167,28 @@ def test_explains_a_ranked_page(ctx):
     assert [bin(int(m)).count("1") for m in got[:, 0]] == scores.tolist()
     want = ec.truth([[lists[j] for j in range(a, b)] for ((_, a, b),) in groups], page)
     assert np.array_equal(got, want) and st.n_hits == int(scores.sum())
+
+
+def test_a_wave_walks_several_blocks_across_range_ends(ctx):
+    """More blocks than 2 x 32 waves per CU: every wave of k_ex_match walks three blocks, and range (group) ends fall inside its run."""
+    rng = np.random.default_rng(7106)
+    D = 1 << 22
+    segments, ranges, per_wave = one_block_lists_past_a_wave(rng, D)
+    flat = np.concatenate([segments[s][j] for s, a, b in ranges for j in range(a, b)])
+    page = np.union1d(rng.choice(flat, 150, replace=False), sorted_unique(rng, 150, D)).astype(np.uint32)
+    ids = rng.permutation(page).astype(np.uint32)
+    k = int(np.flatnonzero(np.isin(ids, flat))[0])                                        # a repeated id that hits: its first row keeps the mask
+    ids = np.insert(ids, [k + 30, k + 150], [ids[k], ids[k]]).astype(np.uint32)
+    case = ec.Case("past_a_wave", segments, [[r] for r in ranges[:4]] + [ranges[4:]], ids)    # five groups, the last of two ranges
+    want = case.expect()
+    n_blocks = sum(b - a for _, a, b in ranges)
+    assert per_wave >= 3 and case.n_blocks == n_blocks > 2 * 32 * torch.cuda.get_device_properties(0).multi_processor_count
+    assert ec.popcount(want) >= 150 and want[k].any() and not want[[k + 30, k + 151]].any() and np.all(ids[[k + 30, k + 151]] == ids[k])
+    for skip in (0, 1):
+        with Option(ctx, "count.summary_skip", skip, 1):
+            got, st = run_case(ctx, case)
+            assert np.array_equal(got, want), skip
+            check_stats(st, case, want)
 
 
 def raw(ctx, group_first, ranges, d_ids, n_ids, d_masks, cap, stats=None, n_groups=None):

@@ -82,15 +82,19 @@ def test_sources():
     assert "hist_device.h" in hdrs.split() and "cr_walk.h" in hdrs.split()
     src = open(os.path.join(CSRC, "histogram.hip")).read()
     assert "lookback.h" not in src and "ii2_lookback_launch" not in src and "asm" not in src
-    for k in ("k_hs_count", "k_hs_ids_edges", "k_hs_ids_tomb", "cr_walk<", "decode_block_wave4", "seg_add(", "hist_block(", "hist_find("):
+    for k in ("k_hs_count", "k_hs_ids_edges", "k_hs_ids_tomb", "cr_walk<", "seg_add(", "hist_block(", "hist_find("):
         assert k in src, k
+    walk = open(os.path.join(CSRC, "cr_walk.h")).read()
+    assert "decode_block_wave4" in walk                                  # (the block decode moved there with the walk's other pieces)
     # the segmented sum lives beside the segmented OR, once; the walk is shared, not copied into the kernel file
     n_defs = 0
     for name in os.listdir(CSRC):
         if name.endswith((".h", ".hip", ".cpp")):
             n_defs += len(re.findall(r"uint32_t seg_add\(", open(os.path.join(CSRC, name)).read()))
     assert n_defs == 1 and "uint32_t seg_add(" in open(os.path.join(CSRC, "um_device.h")).read()
-    assert "um_range_of(" not in src and "um_range_of(" in open(os.path.join(CSRC, "cr_walk.h")).read()
+    assert "um_range_of(" in walk
+    for name in ("count_ranges.hip", "explain_ranges.hip", "histogram.hip"):
+        assert "um_range_of(" not in open(os.path.join(CSRC, name)).read(), name
     # the kernels and the host-only entry points run the same functions
     host = open(os.path.join(CSRC, "setop.cpp")).read()
     assert '#include "hist_device.h"' in host and '#include "hist_device.h"' in src
